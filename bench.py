@@ -7,9 +7,12 @@ merges, weights, log Z-hat) over the alignment already resident in HBM.  Default
 
 What the line reports:
   value / ms_per_step   whole-job throughput of the timed region: independent sweeps (own seed, own resampling, own log
-                        Z-hat, each bit-identical to the sweep run alone) issued up to ten per set of launches
-                        (phylo_sweep_batch_async) on three contexts in flight.  The K steps are timed `repeats` times
-                        (>= 100 ms in all) and the MEDIAN repetition is reported.
+                        Z-hat, each bit-identical to the sweep run alone) issued up to twenty per set of launches
+                        (phylo_sweep_batch_async) on three contexts in flight.  The timed region is exactly the --steps
+                        steps, once (--min-timed-ms T > 0: repeated until T ms are covered, the MEDIAN repetition reported).
+
+A plain run does only that: set-up, --warmup steps, the timed steps, --dump-outputs if given, the line.  Everything below
+is measured with --full alone (--no-cpu-baseline / --no-parity / --no-vi-step drop parts of it):
   t_sweep_ms            device time of ONE sweep alone (hipEvents on its stream), median of >= 20 after 3 warm-ups: the
                         reference's own usage (one evaluation sweep per epoch; training steps are sequential).
   delta_logZ_max, ancestors_equal   seeds 0..9 at the bench's K against the C oracle (the |delta log Z-hat| half of the metric).
@@ -23,7 +26,13 @@ What the line reports:
                         valu_issue_occupancy (a DIAGNOSTIC, not a roofline: it rises when instructions are added), traffic / hbm_frac
                         (HBM bytes from FETCH_SIZE / WRITE_SIZE: with lazy nodes ~2 % of the 96 B/unit).
 
-  python bench.py --gpus 1 --steps 20 --warmup 3
+  vi_step, cpu_baseline the VI training step and the C oracle on this host's cores; N > 1: the independent-sweeps
+                        figure beside the sharded value (multi_gpu.independent_sweeps).
+
+--dump-outputs DIR writes the last timed step (the last sweep: what phylo_sweep_fetch hands its caller, rank 0's columns) as
+DIR/<name>.npy in float64; same arguments, same inputs and seeds, so two builds can be compared array by array.
+
+  python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  No PyTorch is imported: the ranks are joined through RCCL inside
@@ -79,7 +88,13 @@ def parse():
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--no-parity', action='store_true', help='skip the 10-seed comparison with the C oracle')
     p.add_argument('--no-vi-step', action='store_true', help='skip the timing of the VI training steps (SURVEY 8f.1) appended to the line')
-    p.add_argument('--min-timed-ms', type=float, default=2000.0, help='repeat the K timed steps until this much time is covered (the K steps alone last a few ms)')
+    p.add_argument('--min-timed-ms', type=float, default=0.0,
+                   help='repeat the K timed steps until this much time is covered and report the median repetition (0: the K steps once)')
+    p.add_argument('--full', action='store_true',
+                   help='also the figures beside the headline: t_sweep, roofline, parity with the C oracle, vi_step, cpu_baseline, '
+                        'and at N > 1 the independent-sweeps figure')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='write the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)')
     p.add_argument('--one-launch', action='store_true', help='single sweeps (t_sweep) in the one-launch form (phylo_persist.h)')
     p.add_argument('--cpu-seconds', type=float, default=12.0, help='target CPU-baseline duration')
     return p.parse_args()
@@ -147,6 +162,27 @@ def cpu_baseline(g, Q, pi, lam, jc, K_gpu, seconds, twist_M=0, lam_r=None):
     return {"value": units / dt, "unit": "particle-site-likelihoods/s", "cores": cores, "kind": "port",
             "sample": "%d sweep(s) of the same alignment at K=%d (oracle/csrc/oracle.c, reference dataflow, %d OpenMP threads, %.1f s)"
                       % (n, K, cores, dt)}
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ARRAYS = ('log_weights', 'log_likelihood', 'left_branches', 'right_branches', 'merges', 'ancestors')
+
+
+def dump_outputs(path, out, ctx, g0, k_sweep):
+    """The sweep whose particles are columns [g0, g0 + k_sweep) of ctx's last sweep_fetch(arrays=True) `out`: this rank's columns
+    of every array, as float64 (.npy; merges and ancestors are integers, exact in float64), and log_Z.  Over DUMP_MAX_BYTES in all,
+    a fixed seeded sample of the particle columns is kept and particle_index.npy says which (indices inside the sweep)."""
+    lo, hi = max(g0, ctx.k0), min(g0 + k_sweep, ctx.k0 + ctx.K_local)
+    cols = np.arange(lo, max(lo, hi)) - ctx.k0
+    bytes_per_col = sum(8 * out[n][:, :1].size for n in DUMP_ARRAYS)
+    keep = max(1, (DUMP_MAX_BYTES - 1024) // bytes_per_col)
+    os.makedirs(path, exist_ok=True)
+    if cols.size > keep:
+        cols = np.sort(np.random.default_rng(0).choice(cols, keep, replace=False))
+        np.save(os.path.join(path, 'particle_index.npy'), (cols + ctx.k0 - g0).astype(np.float64))
+    for n in DUMP_ARRAYS:
+        np.save(os.path.join(path, n + '.npy'), np.ascontiguousarray(out[n][:, cols], dtype=np.float64))
+    np.save(os.path.join(path, 'log_Z.npy'), np.array([out['logZ']], dtype=np.float64))
 
 
 def main():
@@ -357,11 +393,11 @@ def main():
         first_contact["remote_cache"] = {"kept": "cache" if keep_cache else "in place", "ms_per_launch_set_with_cache": t_on * 1e3,
                                          "ms_per_launch_set_in_place": t_off * 1e3, "slots_used_rank0": used, "slots": cap}
     run(-(-max(a.warmup, 0) // batch) * batch, a.seed + 1000)   # W warm-up steps, rounded up to whole launch sets
-    # the K steps, timed `repeats` times (each bracketed by the barrier; max over ranks), median reported: one repetition of
-    # the default K lasts a few ms, too short to quote alone
+    # the K steps, bracketed by the barrier (max over ranks).  With --min-timed-ms T > 0 the bracket is repeated until T ms are
+    # covered and the median repetition reported
     reps_dt = []
     inner = 1
-    if independent:                                   # the ranks meet through files (~0.1 ms of skew): time >= 50 ms per bracket
+    if independent and a.min_timed_ms > 0:            # the ranks meet through files (~0.1 ms of skew): time >= 50 ms per bracket
         t0 = time.perf_counter()
         run(a.steps, a.seed)
         inner = max(1, int(gmax(0.05 / max(time.perf_counter() - t0, 1e-6)) + 0.5))
@@ -372,165 +408,170 @@ def main():
             run(a.steps, a.seed)
         barrier()
         reps_dt.append(gmax(time.perf_counter() - t0) / inner)      # max over ranks (every rank takes the same decision below)
-        if sum(reps_dt) * 1e3 >= a.min_timed_ms and len(reps_dt) >= 3:
+        if a.min_timed_ms <= 0 or (sum(reps_dt) * 1e3 >= a.min_timed_ms and len(reps_dt) >= 3):
             break
         if len(reps_dt) >= 4000:
             break
     dt = float(np.median(reps_dt))
-    if batch > 1:
-        nb = a.steps // batch
-        last = single.sweep_fetch(arrays=False) if a.steps % batch else ctxs[(nb - 1) % n_streams].sweep_fetch(arrays=False)
-        if a.steps % batch == 0:
-            last['logZ'] = float(ctxs[(nb - 1) % n_streams].sweep_fetch_logz(batch)[-1])
+    # the last step: the last sweep of the last launch set (its group's columns), or of the single sweeps
+    last_in_batch = batch > 1 and a.steps % batch == 0
+    if last_in_batch:
+        last_ctx, g0 = ctxs[(a.steps // batch - 1) % n_streams], (batch - 1) * K_global
     else:
-        last = ctxs[(a.steps - 1) % n_streams].sweep_fetch(arrays=False)
+        last_ctx, g0 = (single if batch > 1 else ctxs[(a.steps - 1) % n_streams]), 0
+    dump = bool(a.dump_outputs) and rank == 0
+    last = last_ctx.sweep_fetch(arrays=dump)
+    if last_in_batch:
+        last['logZ'] = float(last_ctx.sweep_fetch_logz(batch)[-1])
+    if dump:
+        dump_outputs(a.dump_outputs, last, last_ctx, g0, K_global)
 
-    # one sweep at a time on one stream (latency of a single sweep), and the dominant kernel (the
-    # Felsenstein merge): average launch duration from HIP events on the ctx stream, nothing else in flight
-    single_flags = sweep_flags | (_ffi.ONE_LAUNCH if a.one_launch else 0)
-    for s in range(3):                              # 3 warm-ups
-        single.sweep_async(a.seed + 3000 + s, flags=single_flags, M=a.M)
-    single.synchronize()
-    ev_ms = []
-    for s in range(24):                             # device time of each sweep alone: hipEvents on the context's stream
-        single.sweep_async(a.seed + s, flags=single_flags, M=a.M)
-        ev_ms.append(single.sweep_fetch(arrays=False)['stats']['sweep_ms'])
-    t_sweep_ms = float(np.median(ev_ms))
-    t1 = time.perf_counter()
-    for s in range(10):
-        single.sweep_async(a.seed + s, flags=single_flags, M=a.M)
-    single.synchronize()
-    single_ms = (time.perf_counter() - t1) / 10 * 1e3
-    # the |delta log Z-hat| half of the metric: seeds 0..9 at this K against the C oracle (identical draws by contract)
-    # At N > 1 the same check is the 1 == N contract: the sharded sweep of K_total particles against the oracle's (unsharded) sweep;
-    # every rank runs the sweeps (they are collective), rank 0 runs the oracle and compares ITS columns and the global log Z-hat.
-    parity = None
-    if not a.no_parity and not a.no_cpu_baseline:
-        n_seeds = 10 if world <= 2 else 4                 # the oracle's K-replicated core grows with K_total: bounded at N > 2
-        worst, same = 0.0, True
-        for sd in range(n_seeds):
-            single.sweep_async(sd, flags=single_flags, M=a.M)
-            out = single.sweep_fetch()
-            if rank == 0:
-                from oracle import c_oracle as CO
-                if a.twisting:
-                    ref = CO.sweep_twisted(g, Q, pi, lam, lam_r, K_global, a.M, sd, jc=a.jcmodel)
-                else:
-                    ref = CO.sweep(g, Q, pi, lam, lam_r, K_global, sd, jc=a.jcmodel)
-                worst = max(worst, abs(out['logZ'] - ref['logZ']))
-                cols = slice(single.k0, single.k0 + single.K_local)
-                same = same and bool(np.array_equal(out['ancestors'], ref['ancestors'][:, cols]))
-            barrier()                                     # the other ranks wait for rank 0's oracle HERE, not inside a kernel's flag wait
-        parity = {"delta_logZ_max": worst, "ancestors_equal": same, "parity_seeds": n_seeds}
-    prof_sweeps = 3
-    merge_ms, merge_n = 0.0, 0
-    for s in range(prof_sweeps):                    # the launch form of the timed region, one at a time, kernel-stamped events
-        if batch > 1:
-            ctx.sweep_batch_async([a.seed + s * batch + j for j in range(batch)], flags=sweep_flags | _ffi.TIME_KERNELS)
-        else:
-            ctx.sweep_async(a.seed + s, flags=sweep_flags | _ffi.TIME_KERNELS, M=a.M)
-        st = ctx.sweep_fetch(arrays=False)['stats']
-        merge_ms += st['merge_ms']
-        merge_n += st['merge_launches']
-    bytes_per_launch = 96.0 * ctx.K_local * S       # 2 child reads + 1 parent write, 32 B each, per (particle, site)
-    # lazy nodes (plain proposal): the launch stores nothing and runs the row-per-thread form of the merge
-    lazy_nodes = not a.twisting and not a.eager and not os.environ.get('PHYLO_EAGER_NODES')
-    merge_kernel = "pk_rank_merge_nostore" if lazy_nodes else "pk_rank_merge"
-    if a.twisting:
-        # the dominant kernel of a twisted sweep is the look-ahead potentials (PHYLO_TIME_KERNELS stamps it): 64 B per look-ahead
-        # unit (two child reads, no store), K M S C(N+1,3) units per sweep, averaged over the N-1 launches of a sweep
-        merge_kernel = "pk_twist_potentials"
-        bytes_per_launch = 64.0 * ctx.K_local * a.M * S * ((N + 1) * N * (N - 1) / 6.0) / (N - 1)
-    avg_s = merge_ms / merge_n * 1e-3
-    alg_equiv = bytes_per_launch / avg_s / 1e9
-    # counters of the committed rocprofv3 --pmc runs at THIS launch shape (they cannot be read inside the run)
-    pmc = None
-    if a.twisting:
-        for tpath in sorted(__import__('glob').glob(os.path.join(ROOT, 'profiles', 'r*_twist_pmc.json')), reverse=True):
+    parity, independent_rate = None, None
+    if a.full:
+        # one sweep at a time on one stream (latency of a single sweep), and the dominant kernel (the
+        # Felsenstein merge): average launch duration from HIP events on the ctx stream, nothing else in flight
+        single_flags = sweep_flags | (_ffi.ONE_LAUNCH if a.one_launch else 0)
+        for s in range(3):                              # 3 warm-ups
+            single.sweep_async(a.seed + 3000 + s, flags=single_flags, M=a.M)
+        single.synchronize()
+        ev_ms = []
+        for s in range(24):                             # device time of each sweep alone: hipEvents on the context's stream
+            single.sweep_async(a.seed + s, flags=single_flags, M=a.M)
+            ev_ms.append(single.sweep_fetch(arrays=False)['stats']['sweep_ms'])
+        t_sweep_ms = float(np.median(ev_ms))
+        t1 = time.perf_counter()
+        for s in range(10):
+            single.sweep_async(a.seed + s, flags=single_flags, M=a.M)
+        single.synchronize()
+        single_ms = (time.perf_counter() - t1) / 10 * 1e3
+        # the |delta log Z-hat| half of the metric: seeds 0..9 at this K against the C oracle (identical draws by contract)
+        # At N > 1 the same check is the 1 == N contract: the sharded sweep of K_total particles against the oracle's (unsharded) sweep;
+        # every rank runs the sweeps (they are collective), rank 0 runs the oracle and compares ITS columns and the global log Z-hat.
+        if not a.no_parity and not a.no_cpu_baseline:
+            n_seeds = 10 if world <= 2 else 4                 # the oracle's K-replicated core grows with K_total: bounded at N > 2
+            worst, same = 0.0, True
+            for sd in range(n_seeds):
+                single.sweep_async(sd, flags=single_flags, M=a.M)
+                out = single.sweep_fetch()
+                if rank == 0:
+                    from oracle import c_oracle as CO
+                    if a.twisting:
+                        ref = CO.sweep_twisted(g, Q, pi, lam, lam_r, K_global, a.M, sd, jc=a.jcmodel)
+                    else:
+                        ref = CO.sweep(g, Q, pi, lam, lam_r, K_global, sd, jc=a.jcmodel)
+                    worst = max(worst, abs(out['logZ'] - ref['logZ']))
+                    cols = slice(single.k0, single.k0 + single.K_local)
+                    same = same and bool(np.array_equal(out['ancestors'], ref['ancestors'][:, cols]))
+                barrier()                                     # the other ranks wait for rank 0's oracle HERE, not inside a kernel's flag wait
+            parity = {"delta_logZ_max": worst, "ancestors_equal": same, "parity_seeds": n_seeds}
+        prof_sweeps = 3
+        merge_ms, merge_n = 0.0, 0
+        for s in range(prof_sweeps):                    # the launch form of the timed region, one at a time, kernel-stamped events
+            if batch > 1:
+                ctx.sweep_batch_async([a.seed + s * batch + j for j in range(batch)], flags=sweep_flags | _ffi.TIME_KERNELS)
+            else:
+                ctx.sweep_async(a.seed + s, flags=sweep_flags | _ffi.TIME_KERNELS, M=a.M)
+            st = ctx.sweep_fetch(arrays=False)['stats']
+            merge_ms += st['merge_ms']
+            merge_n += st['merge_launches']
+        bytes_per_launch = 96.0 * ctx.K_local * S       # 2 child reads + 1 parent write, 32 B each, per (particle, site)
+        # lazy nodes (plain proposal): the launch stores nothing and runs the row-per-thread form of the merge
+        lazy_nodes = not a.twisting and not a.eager and not os.environ.get('PHYLO_EAGER_NODES')
+        merge_kernel = "pk_rank_merge_nostore" if lazy_nodes else "pk_rank_merge"
+        if a.twisting:
+            # the dominant kernel of a twisted sweep is the look-ahead potentials (PHYLO_TIME_KERNELS stamps it): 64 B per look-ahead
+            # unit (two child reads, no store), K M S C(N+1,3) units per sweep, averaged over the N-1 launches of a sweep
+            merge_kernel = "pk_twist_potentials"
+            bytes_per_launch = 64.0 * ctx.K_local * a.M * S * ((N + 1) * N * (N - 1) / 6.0) / (N - 1)
+        avg_s = merge_ms / merge_n * 1e-3
+        alg_equiv = bytes_per_launch / avg_s / 1e9
+        # counters of the committed rocprofv3 --pmc runs at THIS launch shape (they cannot be read inside the run)
+        pmc = None
+        if a.twisting:
+            for tpath in sorted(__import__('glob').glob(os.path.join(ROOT, 'profiles', 'r*_twist_pmc.json')), reverse=True):
+                try:
+                    for e in json.load(open(tpath)).get('kernels', []):
+                        if e.get('workload') == wname and e.get('kernel') == merge_kernel and e.get('M') == a.M and e.get('particles') == ctx.K_local:
+                            pmc = dict(e, source=os.path.basename(tpath))
+                            break
+                except Exception:
+                    pass
+                if pmc:
+                    break
+        for tpath in ([] if a.twisting else sorted(__import__('glob').glob(os.path.join(ROOT, 'profiles', 'r*_merge_pmc.json')), reverse=True)):
             try:
-                for e in json.load(open(tpath)).get('kernels', []):
-                    if e.get('workload') == wname and e.get('kernel') == merge_kernel and e.get('M') == a.M and e.get('particles') == ctx.K_local:
+                for e in json.load(open(tpath)).get('launch_shapes', []):
+                    if e.get('workload') == wname and e.get('particles_per_launch') == ctx.K_local and e.get('kernel') == merge_kernel:
                         pmc = dict(e, source=os.path.basename(tpath))
                         break
             except Exception:
                 pass
             if pmc:
                 break
-    for tpath in ([] if a.twisting else sorted(__import__('glob').glob(os.path.join(ROOT, 'profiles', 'r*_merge_pmc.json')), reverse=True)):
-        try:
-            for e in json.load(open(tpath)).get('launch_shapes', []):
-                if e.get('workload') == wname and e.get('particles_per_launch') == ctx.K_local and e.get('kernel') == merge_kernel:
-                    pmc = dict(e, source=os.path.basename(tpath))
-                    break
-        except Exception:
-            pass
+        units_per_launch = float(ctx.K_local) * S
+        flops_per_launch = FLOP_PER_UNIT * units_per_launch
+        if a.twisting:
+            units_per_launch = float(ctx.K_local) * a.M * S * ((N + 1) * N * (N - 1) / 6.0) / (N - 1)   # averaged over the rank events
+            flops_per_launch = FLOP_PER_LOOKAHEAD_UNIT * units_per_launch
+        achieved = flops_per_launch / avg_s / 1e12
+        roof = {"kernel": merge_kernel, "avg_launch_us": avg_s * 1e6, "particles_per_launch": ctx.K_local, "units_per_launch": units_per_launch,
+                "bound": "valu", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS,
+                "flop_frac": achieved / FP64_PEAK_TFLOPS,
+                "basis": ("%.0f algorithmic flop per %s (SURVEY 8d) x units per launch / live launch duration, against the vector fp64 peak "
+                          "(1024 SIMDs x 16 lanes x 2 flop x 2.4 GHz); MFMA does not apply (4x4 contractions)"
+                          % ((FLOP_PER_LOOKAHEAD_UNIT, "look-ahead unit") if a.twisting else (FLOP_PER_UNIT, "particle-site-likelihood"))),
+                "alg_bytes_per_launch": bytes_per_launch, "alg_equiv_GBps": alg_equiv,
+                "alg_equiv_note": "bytes of the reference's dataflow per unit x units / duration: an algorithmic-equivalent rate, NOT HBM traffic "
+                                  "(lazy nodes store nothing; children are 1-byte codes or cache-resident)",
+                "traffic": None, "hbm_frac": None, "executed_fp64_TFLOPs": None, "executed_fp64_frac": None, "valu_issue_occupancy": None,
+                "pmc_source": pmc['source'] if pmc else None}
         if pmc:
-            break
-    units_per_launch = float(ctx.K_local) * S
-    flops_per_launch = FLOP_PER_UNIT * units_per_launch
-    if a.twisting:
-        units_per_launch = float(ctx.K_local) * a.M * S * ((N + 1) * N * (N - 1) / 6.0) / (N - 1)   # averaged over the rank events
-        flops_per_launch = FLOP_PER_LOOKAHEAD_UNIT * units_per_launch
-    achieved = flops_per_launch / avg_s / 1e12
-    roof = {"kernel": merge_kernel, "avg_launch_us": avg_s * 1e6, "particles_per_launch": ctx.K_local, "units_per_launch": units_per_launch,
-            "bound": "valu", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS,
-            "flop_frac": achieved / FP64_PEAK_TFLOPS,
-            "basis": ("%.0f algorithmic flop per %s (SURVEY 8d) x units per launch / live launch duration, against the vector fp64 peak "
-                      "(1024 SIMDs x 16 lanes x 2 flop x 2.4 GHz); MFMA does not apply (4x4 contractions)"
-                      % ((FLOP_PER_LOOKAHEAD_UNIT, "look-ahead unit") if a.twisting else (FLOP_PER_UNIT, "particle-site-likelihood"))),
-            "alg_bytes_per_launch": bytes_per_launch, "alg_equiv_GBps": alg_equiv,
-            "alg_equiv_note": "bytes of the reference's dataflow per unit x units / duration: an algorithmic-equivalent rate, NOT HBM traffic "
-                              "(lazy nodes store nothing; children are 1-byte codes or cache-resident)",
-            "traffic": None, "hbm_frac": None, "executed_fp64_TFLOPs": None, "executed_fp64_frac": None, "valu_issue_occupancy": None,
-            "pmc_source": pmc['source'] if pmc else None}
-    if pmc:
-        if pmc.get('hbm_bytes_per_launch') is not None:
-            roof["traffic"] = pmc['hbm_bytes_per_launch']
-            roof["hbm_GBps"] = pmc['hbm_bytes_per_launch'] / avg_s / 1e9
-            roof["hbm_frac"] = roof["hbm_GBps"] / HBM_PEAK_GBPS
-        fma, add, mul = (pmc.get('sq_insts_valu_%s_f64_per_launch' % k) for k in ('fma', 'add', 'mul'))
-        if None not in (fma, add, mul):
-            roof["executed_fp64_TFLOPs"] = (2.0 * fma + add + mul) * 64.0 / avg_s / 1e12
-            roof["executed_fp64_frac"] = roof["executed_fp64_TFLOPs"] / FP64_PEAK_TFLOPS
-            if pmc.get('sq_insts_valu_per_launch') is not None:
-                f64 = fma + add + mul
-                roof["valu_issue_occupancy"] = (4.0 * f64 + 2.0 * (pmc['sq_insts_valu_per_launch'] - f64)) / (N_SIMD * CLK_HZ * avg_s)
-                roof["valu_issue_note"] = ("diagnostic only: fp64 instructions priced at 4 cycles, every other VALU instruction at 2 (a lower "
-                                           "bound: shifts, compares and DPP moves measure 4); it goes UP when instructions are added")
-        if roof["frac"] > 1.0 and roof["executed_fp64_frac"] is not None:
-            # the algorithmic count prices arithmetic the kernel does not execute (coded leaves go through tables: contracts v3 / v4 of
-            # the twisted proposal): above 1 it is no fraction of any peak -- the executed fp64 rate is reported instead
-            roof.update({"alg_flop_frac": roof["frac"], "achieved": roof["executed_fp64_TFLOPs"], "frac": roof["executed_fp64_frac"],
-                         "frac_note": "executed fp64 (SQ_INSTS_VALU_{FMA,ADD,MUL}_F64 of the committed counter pass) / live duration: the "
-                                      "algorithmic flops / duration (alg_flop_frac) exceed the peak because table look-ups replace most of them"})
-        if roof["hbm_frac"] is not None and roof["hbm_frac"] > 0.5:        # eager nodes on large rows: the store stream binds
-            roof.update({"bound": "hbm", "achieved": roof["hbm_GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": roof["hbm_frac"]})
+            if pmc.get('hbm_bytes_per_launch') is not None:
+                roof["traffic"] = pmc['hbm_bytes_per_launch']
+                roof["hbm_GBps"] = pmc['hbm_bytes_per_launch'] / avg_s / 1e9
+                roof["hbm_frac"] = roof["hbm_GBps"] / HBM_PEAK_GBPS
+            fma, add, mul = (pmc.get('sq_insts_valu_%s_f64_per_launch' % k) for k in ('fma', 'add', 'mul'))
+            if None not in (fma, add, mul):
+                roof["executed_fp64_TFLOPs"] = (2.0 * fma + add + mul) * 64.0 / avg_s / 1e12
+                roof["executed_fp64_frac"] = roof["executed_fp64_TFLOPs"] / FP64_PEAK_TFLOPS
+                if pmc.get('sq_insts_valu_per_launch') is not None:
+                    f64 = fma + add + mul
+                    roof["valu_issue_occupancy"] = (4.0 * f64 + 2.0 * (pmc['sq_insts_valu_per_launch'] - f64)) / (N_SIMD * CLK_HZ * avg_s)
+                    roof["valu_issue_note"] = ("diagnostic only: fp64 instructions priced at 4 cycles, every other VALU instruction at 2 (a lower "
+                                               "bound: shifts, compares and DPP moves measure 4); it goes UP when instructions are added")
+            if roof["frac"] > 1.0 and roof["executed_fp64_frac"] is not None:
+                # the algorithmic count prices arithmetic the kernel does not execute (coded leaves go through tables: contracts v3 / v4 of
+                # the twisted proposal): above 1 it is no fraction of any peak -- the executed fp64 rate is reported instead
+                roof.update({"alg_flop_frac": roof["frac"], "achieved": roof["executed_fp64_TFLOPs"], "frac": roof["executed_fp64_frac"],
+                             "frac_note": "executed fp64 (SQ_INSTS_VALU_{FMA,ADD,MUL}_F64 of the committed counter pass) / live duration: the "
+                                          "algorithmic flops / duration (alg_flop_frac) exceed the peak because table look-ups replace most of them"})
+            if roof["hbm_frac"] is not None and roof["hbm_frac"] > 0.5:        # eager nodes on large rows: the store stream binds
+                roof.update({"bound": "hbm", "achieved": roof["hbm_GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": roof["hbm_frac"]})
 
-    # N > 1, sharded: the same steps once more as independent sweeps per rank (own contexts, no communicator): what N GPUs do
-    # without any exchange, next to which the sharded value shows the price of the global resampling
-    independent_rate = None
-    if world > 1 and not independent and not a.twisting and not os.environ.get('PHYLO_BENCH_NO_INDEPENDENT'):
-        Ks, sh, ns, cx, sg, c0, n_live = K_global, sharded, n_streams, ctxs, single, ctx, len(live)
-        try:
-            independent, sharded, K_global, n_streams = True, False, a.n_particles, (a.streams if a.streams > 0 else 3)
-            ctxs, single = make_contexts()
-            ctx = ctxs[0]
-            run(n_streams * batch, a.seed + 2000)
-            t0 = time.perf_counter()
-            run(a.steps, a.seed)
-            inner = max(1, int(gmax(0.05 / max(time.perf_counter() - t0, 1e-6)) + 0.5))
-            barrier()
-            t0 = time.perf_counter()
-            for _ in range(inner):
+        # N > 1, sharded: the same steps once more as independent sweeps per rank (own contexts, no communicator): what N GPUs do
+        # without any exchange, next to which the sharded value shows the price of the global resampling
+        if world > 1 and not independent and not a.twisting and not os.environ.get('PHYLO_BENCH_NO_INDEPENDENT'):
+            Ks, sh, ns, cx, sg, c0, n_live = K_global, sharded, n_streams, ctxs, single, ctx, len(live)
+            try:
+                independent, sharded, K_global, n_streams = True, False, a.n_particles, (a.streams if a.streams > 0 else 3)
+                ctxs, single = make_contexts()
+                ctx = ctxs[0]
+                run(n_streams * batch, a.seed + 2000)
+                t0 = time.perf_counter()
                 run(a.steps, a.seed)
-            barrier()
-            dti = gmax(time.perf_counter() - t0) / inner
-            independent_rate = float(a.n_particles) * S * (N - 1) * a.steps * world / dti
-        except (_ffi.PhyloError, TimeoutError, OSError):
-            independent_rate = None
-        while len(live) > n_live:
-            live.pop().close()
-        independent, sharded, K_global, n_streams, ctxs, single, ctx = False, sh, Ks, ns, cx, sg, c0
+                inner = max(1, int(gmax(0.05 / max(time.perf_counter() - t0, 1e-6)) + 0.5))
+                barrier()
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    run(a.steps, a.seed)
+                barrier()
+                dti = gmax(time.perf_counter() - t0) / inner
+                independent_rate = float(a.n_particles) * S * (N - 1) * a.steps * world / dti
+            except (_ffi.PhyloError, TimeoutError, OSError):
+                independent_rate = None
+            while len(live) > n_live:
+                live.pop().close()
+            independent, sharded, K_global, n_streams, ctxs, single, ctx = False, sh, Ks, ns, cx, sg, c0
     if rank == 0:
         units_per_step = float(K_global) * S * (N - 1)
         if a.twisting:                             # + K M S C(N+1,3) look-ahead merges
@@ -549,16 +590,19 @@ def main():
                        "sweeps_in_flight": n_streams * batch, "particles_in_flight": n_streams * batch * K_global},
             "timed_region": {"repeats": len(reps_dt), "ms_total": sum(reps_dt) * 1e3, "ms_per_step_min": min(reps_dt) / a.steps * 1e3,
                              "ms_per_step_max": max(reps_dt) / a.steps * 1e3, "reported": "median repetition"},
-            "t_sweep_ms": t_sweep_ms,
-            "t_sweep": {"n": len(ev_ms), "min_ms": min(ev_ms), "max_ms": max(ev_ms), "timer": "hipEvents on the sweep's stream",
-                        "form": "one launch (phylo_persist.h)" if a.one_launch else "launches per rank event",
-                        "units_per_s": units_per_step / world / (t_sweep_ms * 1e-3),
-                        "flop_frac": (FLOP_PER_UNIT * float(K_global) * S * (N - 1) + (FLOP_PER_LOOKAHEAD_UNIT * (units_per_step - float(K_global) * S * (N - 1))))
-                                     / world / (t_sweep_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS},
-            "single_sweep_wall_ms": single_ms,
             "log_Z": last['logZ'],
-            "roofline": roof,
         }
+        if a.full:
+            line.update({
+                "t_sweep_ms": t_sweep_ms,
+                "t_sweep": {"n": len(ev_ms), "min_ms": min(ev_ms), "max_ms": max(ev_ms), "timer": "hipEvents on the sweep's stream",
+                            "form": "one launch (phylo_persist.h)" if a.one_launch else "launches per rank event",
+                            "units_per_s": units_per_step / world / (t_sweep_ms * 1e-3),
+                            "flop_frac": (FLOP_PER_UNIT * float(K_global) * S * (N - 1) + (FLOP_PER_LOOKAHEAD_UNIT * (units_per_step - float(K_global) * S * (N - 1))))
+                                         / world / (t_sweep_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS},
+                "single_sweep_wall_ms": single_ms,
+                "roofline": roof,
+            })
         if parity is not None:
             line.update(parity)
         if world > 1 or sharded:
@@ -569,16 +613,6 @@ def main():
                                  "be read against" % (a.steps, world, a.n_particles)}
             # first contact with more than one device: what the run actually did, next to the one-GPU figures it should match
             n_coll = 0 if first_contact["exchange"] == 'p2p' else (N - 1) * (2 if not a.eager and not a.twisting else 1) - (1 if not a.eager and not a.twisting else 0)
-            ref_us = None
-            for tpath in sorted(__import__('glob').glob(os.path.join(ROOT, 'profiles', 'r*_merge_pmc.json')), reverse=True):
-                try:
-                    for e in json.load(open(tpath)).get('launch_shapes', []):
-                        if e.get('workload') == wname and e.get('particles_per_launch') == ctx.K_local and e.get('kernel') == merge_kernel:
-                            ref_us = e.get('avg_us_in_pmc_pass')
-                except Exception:
-                    pass
-                if ref_us:
-                    break
             # where the particles of a sweep live: a context's K = batch x K_total particle indices are sharded by contiguous ranges, so with
             # batch >= N a sweep's K_total particles lie on one rank or straddle a boundary; only straddling sweeps merge remote children
             kl_ctx = K_global * batch // max(world, 1)
@@ -592,14 +626,25 @@ def main():
                                  "exchange": first_contact["exchange"], "fallback": first_contact["fallback"],
                                  "remote_children": first_contact.get("remote_cache"),
                                  "collective_calls_per_sweep_and_rank": n_coll,
-                                 "merge_kernel": merge_kernel, "merge_avg_launch_us_rank0": avg_s * 1e6,
-                                 "merge_avg_launch_us_one_gpu_profile": ref_us,
                                  "note": "merge duration above the one-GPU figure at the same particles per launch = remote child rows are not "
                                          "served from this GPU's caches (DESIGN.md section 5); delta_logZ_max / ancestors_equal are the "
                                          "1 == N contract against the unsharded oracle sweep of K_total particles"}
-        if world == 1 and not a.no_vi_step and not a.synthetic:
+            if a.full:
+                ref_us = None
+                for tpath in sorted(__import__('glob').glob(os.path.join(ROOT, 'profiles', 'r*_merge_pmc.json')), reverse=True):
+                    try:
+                        for e in json.load(open(tpath)).get('launch_shapes', []):
+                            if e.get('workload') == wname and e.get('particles_per_launch') == ctx.K_local and e.get('kernel') == merge_kernel:
+                                ref_us = e.get('avg_us_in_pmc_pass')
+                    except Exception:
+                        pass
+                    if ref_us:
+                        break
+                line["multi_gpu"].update({"merge_kernel": merge_kernel, "merge_avg_launch_us_rank0": avg_s * 1e6,
+                                          "merge_avg_launch_us_one_gpu_profile": ref_us})
+        if a.full and world == 1 and not a.no_vi_step and not a.synthetic:
             line["vi_step"] = vi_step_timing(g, a.n_particles, device=local_rank % ndev)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(g, Q, pi, lam, a.jcmodel, a.n_particles, a.cpu_seconds, a.M if a.twisting else 0, lam_r)
         print(json.dumps(line), flush=True)
     close_all()                                       # (sharers before the owner of the communicator)

@@ -364,7 +364,7 @@ def _run_bench_ranks(world, extra_env, args):
 def test_bench_py_at_two_ranks_reports_the_sharded_value_and_the_independent_figure():
     """bench.py itself as the driver launches it at N = 2 (two processes on GPU 0, host-side collectives over hostshm): the
     value is the sharded sweep's, 1 == N parity against the oracle holds, the independent-sweeps figure stands beside it."""
-    line = _run_bench_ranks(2, {}, ['--steps', '12', '--warmup', '2', '--n_particles', '64', '--min-timed-ms', '20'])
+    line = _run_bench_ranks(2, {}, ['--steps', '12', '--warmup', '2', '--n_particles', '64', '--min-timed-ms', '20', '--full'])
     assert line['n_gpus'] == 2 and line['scaling'] == 'weak' and line['value'] > 0
     mg = line['multi_gpu']
     assert mg['form'].startswith("one sweep's particles sharded") and mg['exchange'] == 'p2p' and mg['fallback'] is None
@@ -378,7 +378,7 @@ def test_bench_py_at_two_ranks_reports_the_sharded_value_and_the_independent_fig
 def test_bench_py_falls_back_form_by_form(fail, form, exchange):
     """First contact gone wrong (forced): the device-side exchange fails -> every rank rebuilds on the collective path; that fails too
     -> independent sweeps per rank, the ranks meeting through files; the line says what happened and still carries a value."""
-    line = _run_bench_ranks(2, {'PHYLO_BENCH_FAIL': fail}, ['--steps', '12', '--warmup', '2', '--n_particles', '64', '--min-timed-ms', '20'])
+    line = _run_bench_ranks(2, {'PHYLO_BENCH_FAIL': fail}, ['--steps', '12', '--warmup', '2', '--n_particles', '64', '--min-timed-ms', '20', '--full'])
     mg = line['multi_gpu']
     assert mg['form'].startswith(form) and mg['exchange'] == exchange, mg
     assert 'forced failure' in mg['fallback'] and line['value'] > 0

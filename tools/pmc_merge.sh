@@ -8,7 +8,7 @@ TAG=${1:-x}; shift || true
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0 --steps 10 --warmup 10 --streams 1"
+COMMON="--full --no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0 --steps 10 --warmup 10 --streams 1"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_LDS --output-format csv -d "$OUT/sq" -- python3 "$REPO/bench.py" $COMMON "$@" > "$OUT/sq.log" 2>&1 || echo "sq pass: exit $?"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_WAVES --output-format csv -d "$OUT/f64" -- python3 "$REPO/bench.py" $COMMON "$@" > "$OUT/f64.log" 2>&1 || echo "f64 pass: exit $?"
 python3 - "$OUT" <<'PY'

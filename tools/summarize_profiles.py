@@ -39,7 +39,7 @@ RUNS = [("default", "`python bench.py --steps 40 --warmup 4` (launch sets of 20 
         ("nested", "`python tools/train_probe.py --steps 10 --nested --M 1` (twisted sweep with the graph kept + its reverse pass)")]
 lines = ["# rocprofv3 summary, round %s" % tag, "",
          "Workload: primate.p N=12 S=898, GTR-init, K=2048 per sweep.  All bench commands carry",
-         "`--no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0`.  Raw tables: `%s_kernel_stats_*.csv`; counters: `%s_merge_pmc.json`." % (tag, tag), ""]
+         "`--full --no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0`.  Raw tables: `%s_kernel_stats_*.csv`; counters: `%s_merge_pmc.json`." % (tag, tag), ""]
 for name, what in RUNS:
     st = one("trace_%s/*/*_kernel_stats.csv" % name)
     if not st:
@@ -138,7 +138,7 @@ if acc:
                            "correction": "2*FETCH_SIZE + WRITE_SIZE (KB -> bytes x1024), MI355X_MICROARCH.md HBM section",
                            "alg_bytes_per_launch": alg, "alg_flops_per_launch": FLOP_PER_UNIT * units, "avg_us_in_pmc_pass": us})
     json.dump({"round": tag, "command": "rocprofv3 --kernel-trace --pmc <counters> --output-format csv -- python3 bench.py --steps 20 --warmup 20 "
-               "--streams 1 --no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0 (four passes: SQ counters, fp64 / integer instruction classes, FETCH_SIZE, WRITE_SIZE)",
+               "--streams 1 --full --no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0 (four passes: SQ counters, fp64 / integer instruction classes, FETCH_SIZE, WRITE_SIZE)",
                "launch_shapes": shapes_out}, open(os.path.join(dst, "%s_merge_pmc.json" % tag), "w"), indent=1)
 # ---- twisted proposal: SQ counters per kernel (durations from the un-countered trace_twist pass)
 f = one("pmc_twist/*/*_counter_collection.csv")
@@ -186,6 +186,6 @@ if f:
                        "avg_us_in_trace_pass": us, "note": "averages over the N-1 rank events of a sweep (their launch sizes differ)"})
     lines.append("")
     json.dump({"round": tag, "command": "rocprofv3 --kernel-trace --pmc <SQ counters> -- python3 bench.py --twisting --M 1 --steps 3 --warmup 1 --streams 1 "
-               "--no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0", "kernels": tw_out}, open(os.path.join(dst, "%s_twist_pmc.json" % tag), "w"), indent=1)
+               "--full --no-cpu-baseline --no-parity --no-vi-step --min-timed-ms 0", "kernels": tw_out}, open(os.path.join(dst, "%s_twist_pmc.json" % tag), "w"), indent=1)
 open(os.path.join(dst, "%s_summary.md" % tag), "w").write("\n".join(lines) + "\n")
 print("\n".join(lines))

@@ -2,7 +2,7 @@
 # Development helper (run through gpurun): for each set of -D flags rebuild the library and run the eager workloads; prints the
 # storing merge's launch time.  tools/variants2.sh "" "-DPK_STORE_DEPTH=2" ...
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
-C="--no-cpu-baseline --no-vi-step --no-parity --batch 1 --streams 1 --steps 6 --warmup 2 --eager"
+C="--full --no-cpu-baseline --no-vi-step --no-parity --batch 1 --streams 1 --steps 6 --warmup 2 --eager"
 for flags in "$@"; do
   ./phylo_amd/csrc/build.sh $flags > /dev/null 2>&1 || { echo "build failed: $flags"; continue; }
   for w in "primate:" "flatDS1:--flat --dataset hohna_data_1 --n_particles 4096 --jcmodel true" "synth256:--synthetic 128,50000 --n_particles 256"; do
