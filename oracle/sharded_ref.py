@@ -7,7 +7,7 @@ the owner.  Integer state (root tables, leaf counts), two forms:
     of the owner's table slab over the peer mapping);
   * local_tables=False (PHYLO_REPLICATED_BOOK=1): rows of all K particles are REPLICATED and advanced on every
     rank from the shared counter-based draws.
-lazy=True (GPU: from S >= 8192, or PHYLO_LAZY_NODES=1): a node is written only when its creator is adopted at the next
+lazy=True (the GPU default with the plain proposal): a node is written only when its creator is adopted at the next
 resampling.  Every rank derives all K resampling indices (the weights are replicated), so each owner knows which of its
 nodes of the previous rank event were adopted; it writes them, a barrier orders the writes, then everybody merges.  A
 read of a node that was never written is an error in this model.  Per rank event the ranks all-gather three K-vectors

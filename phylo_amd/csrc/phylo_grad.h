@@ -76,7 +76,7 @@ struct pg_args {
     const unsigned int* mark;          // [R][K] or NULL: node (r, k) was adopted at rank event r + 1 (the lazy sweep's marks)
     int alpha_om;                      // alpha of a FREE parent is omega itself (the early pg_nodes_free: free = nobody adopted it): the
                                        // gathers then need nothing of the coefficient chain
-    int chunks_free_only;              // pg_parent_chunks sums the entries of free parents only (one launch for all rank events);
+    int chunks_free_only;              // pg_parent_chunks_rows sums the entries of free parents only (one launch for all rank events);
                                        // pg_nodes_rows adds the flagged parents' entries, which end a heavy node's list
     double* slowpart;                  // [flagged nodes][TS][PG_PART] (rows form; else NULL): their partial sums, TS tiles of 256 sites
     unsigned int* row_done;            // [R K][TS] (pg_nodes_rows_all): == row_epoch when that tile of the node's adjoint row is complete
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(256) void pg_leafterm(pg_args a) {
 // Pl_bar / Pr_bar (9 running sums per lane instead of 36).
 // After the first resamplings only a handful of lineages survive, so a few nodes have ~K parents and the rest
 // none: a node with more than PG_PCHUNK parents has its parent list cut into chunks of PG_HCHUNK that
-// pg_parent_chunks sums in parallel; pg_nodes then adds the chunk sums in order.  A light node gathers inline.
+// pg_parent_chunks_rows sums in parallel; pg_nodes then adds the chunk sums in order.  A light node gathers inline.
 template <int I>
 __device__ __forceinline__ double pg_quad(double v) {       // the value held by lane I of my quad
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -560,7 +560,7 @@ __device__ __forceinline__ void pg_stage_parents(const pg_args& a, int c0, int n
 
 // xb (state j of one site) += contributions of the nc staged parents; soff = s * 4 + j.  All 2 nc loads are issued before the
 // first is used (index clamped, so no branch surrounds a load): a loop with a load inside pays one memory latency per parent, and
-// that -- not bandwidth or arithmetic -- was what pg_parent_chunks and the heavy nodes of pg_nodes cost.
+// that -- not bandwidth or arithmetic -- was what the chunk sums and the heavy nodes of pg_nodes cost.
 __device__ __forceinline__ double pg_parent_quad(const pg_args& a, size_t soff, int j, int nc, const double (*shP)[32],
                                                  const int* shE, const int* shSib, const double* shA, double me, double xb) {
     const size_t row = (size_t)a.S * 4;
@@ -599,105 +599,6 @@ __device__ __forceinline__ double pg_parent_quad(const pg_args& a, size_t soff, 
         }
     }
     return xb;
-}
-
-// grid (groups of 16 PG_CSTEPS sites, chunks -- of rank event chunk0's range, or with chunks_free_only of ALL rank events, chunk0
-// = the first of the launch): cpart[chunk][s] = sum of the chunk's parent contributions (free parents' only with chunks_free_only).  The chunk's
-// (up to PG_HCHUNK = 4 PG_PCHUNK) parents are staged at once and each of the four waves gathers its own PG_PCHUNK of them for the
-// same 16 PG_CSTEPS sites (all sibling rows of the steps in flight together); the four partial sums are added in wave order.
-// (One wave after the other over 64 sites -- the first version -- paid a staging and a gather latency per PG_PCHUNK parents:
-// 19.5 us per launch.  A workgroup's time is staging, ~3 us, + ~2 us of arithmetic per step: one step needs two passes over the
-// chip on an average rank event, four steps make the pass too long: 18.7 / 21.7 us.)
-#define PG_CSTEPS 2
-__global__ __launch_bounds__(256) void pg_parent_chunks(pg_args a, int chunk0) {
-    static_assert(PG_HCHUNK == 4 * PG_PCHUNK, "one wave per PG_PCHUNK parents of a chunk");
-    __shared__ double shP[PG_HCHUNK][32];
-    __shared__ int shE[PG_HCHUNK];
-    __shared__ int shSib[PG_HCHUNK];
-    __shared__ double shA[PG_HCHUNK];
-    __shared__ int shMe;
-    __shared__ double shX[4][PG_CSTEPS][64];
-    const int ci = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c0 = a.chunk_beg[chunk0 + ci], cnt = a.chunk_cnt[chunk0 + ci];
-    const int j = lane & 3;
-    const size_t row = (size_t)a.S * 4;
-    size_t soff[PG_CSTEPS];
-    bool live[PG_CSTEPS];
-#pragma unroll
-    for (int it = 0; it < PG_CSTEPS; ++it) {
-        const int s = blockIdx.x * (16 * PG_CSTEPS) + it * 16 + (lane >> 2);
-        live[it] = s < a.S;
-        soff[it] = (size_t)(live[it] ? s : a.S - 1) * 4 + j;
-    }
-    for (int i = tid; i < cnt * 32; i += 256) {
-        const int e = i >> 5, q = i & 31;
-        const int enc = a.par_idx[c0 + e];
-        const int pn = (enc & (PG_FREE_PARENT - 1)) >> 1, side = enc & 1;
-        shP[e][q] = a.Pmat[(size_t)pn * 32 + q];
-        if (q == 0) { shE[e] = enc; shSib[e] = a.child[(size_t)pn * 2 + (1 - side)]; }
-        if (q == 1) shA[e] = pg_alpha_of(a, pn);
-        if (i == 2) shMe = a.child[(size_t)pn * 2 + side];   // the node all these are parents of
-    }
-    __syncthreads();
-    const int nc = cnt - wv * PG_PCHUNK < PG_PCHUNK ? cnt - wv * PG_PCHUNK : PG_PCHUNK;
-    double xb[PG_CSTEPS];
-#pragma unroll
-    for (int it = 0; it < PG_CSTEPS; ++it) xb[it] = 0.0;
-    if (nc > 0) {
-        const int e0 = wv * PG_PCHUNK;
-        const double* merow = pg_row(a, shMe);
-        double me[PG_CSTEPS], sbv[PG_CSTEPS][PG_PCHUNK];
-#pragma unroll
-        for (int it = 0; it < PG_CSTEPS; ++it) me[it] = merow[soff[it]];
-#pragma unroll
-        for (int e = 0; e < PG_PCHUNK; ++e) {
-            const double* sr = pg_row(a, shSib[e0 + (e < nc ? e : nc - 1)]);
-#pragma unroll
-            for (int it = 0; it < PG_CSTEPS; ++it) sbv[it][e] = sr[soff[it]];
-        }
-        const double pj = a.pi[j];
-#pragma unroll
-        for (int e = 0; e < PG_PCHUNK; ++e) {
-            if (e < nc) {                                    // wave-uniform
-                const int enc = __builtin_amdgcn_readfirstlane(shE[e0 + e]);
-                if (a.chunks_free_only && !(enc & PG_FREE_PARENT)) continue;   // a flagged parent: pg_nodes_rows adds it
-                const int side = enc & 1;
-                const double* Psib = shP[e0 + e] + (1 - side) * 16;
-                const double* Pme = shP[e0 + e] + side * 16;
-                const double al = shA[e0 + e];
-#pragma unroll
-                for (int it = 0; it < PG_CSTEPS; ++it) {
-                    const double sb = sbv[it][e];
-                    const double b0 = pg_quad<0>(sb), b1 = pg_quad<1>(sb), b2 = pg_quad<2>(sb), b3 = pg_quad<3>(sb);
-                    const double w = pg_dot4(b0, Psib[j], b1, Psib[4 + j], b2, Psib[8 + j], b3, Psib[12 + j]);
-                    double xp;
-                    if (enc & PG_FREE_PARENT) {              // alpha_p pi / (pi . X_p),  X_p = (me P_me) o (sib P_sib)
-                        const double m = me[it];
-                        const double m0 = pg_quad<0>(m), m1 = pg_quad<1>(m), m2 = pg_quad<2>(m), m3 = pg_quad<3>(m);
-                        const double u = pg_dot4(m0, Pme[j], m1, Pme[4 + j], m2, Pme[8 + j], m3, Pme[12 + j]);
-                        double lik = pj * (u * w);
-                        lik = lik + pg_quad_sum_step<1>(lik);
-                        lik = lik + pg_quad_sum_step<2>(lik);
-                        xp = (al * pj) * pg_rcp(lik);
-                    } else {                                 // a parent with parents of its own (rare in a heavy node's list): its stored row
-                        xp = a.adj[(size_t)(enc >> 1) * row + soff[it]];
-                    }
-                    const double t = xp * w;
-                    const double t0 = pg_quad<0>(t), t1 = pg_quad<1>(t), t2 = pg_quad<2>(t), t3 = pg_quad<3>(t);
-                    xb[it] = xb[it] + pg_dot4(t0, Pme[j * 4], t1, Pme[j * 4 + 1], t2, Pme[j * 4 + 2], t3, Pme[j * 4 + 3]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < PG_CSTEPS; ++it) shX[wv][it][lane] = xb[it];
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-        for (int it = 0; it < PG_CSTEPS; ++it)
-            if (live[it]) a.cpart[(size_t)ci * row + soff[it]] = ((shX[0][it][lane] + shX[1][it][lane]) + shX[2][it][lane]) + shX[3][it][lane];
-    }
 }
 
 // grid (tiles of PG_NT sites, K)
@@ -798,10 +699,12 @@ __global__ __launch_bounds__(256) void pg_nodes(pg_args a, int r) {
     }
 }
 
-// pg_parent_chunks in ROW form: grid (groups of 64 sites, chunks), lane = site (all four states: whole 32-byte rows per load, no
-// quad broadcasts -- the quad form above spends 24 of its ~50 instructions per quarter site on DPP moves), wave w gathers
-// parents w PG_PCHUNK .. of the chunk for the same 64 sites, the four partial sums are added in wave order.  Every sibling row
-// of a wave's parents is loaded before the first is used.  Same sum per chunk up to the order inside a 4-term dot product.
+// grid (groups of 64 sites, chunks -- of rank event chunk0's range, or with chunks_free_only of ALL rank events, chunk0 = the first
+// of the launch): cpart[chunk][s] = sum of the chunk's parent contributions (free parents' only with chunks_free_only).
+// Row form: lane = site (all four states: whole 32-byte rows per load, no quad broadcasts -- a quad form spent 24 of its ~50
+// instructions per quarter site on DPP moves, 114 us against 65-80 us), wave w gathers parents w PG_PCHUNK .. of the chunk
+// (up to PG_HCHUNK = 4 PG_PCHUNK) for the same 64 sites, the four partial sums are added in wave order.  Every sibling row
+// of a wave's parents is loaded before the first is used.
 __global__ __launch_bounds__(256) void pg_parent_chunks_rows(pg_args a, int chunk0) {
     static_assert(PG_HCHUNK == 4 * PG_PCHUNK, "one wave per PG_PCHUNK parents of a chunk");
     __shared__ double shP[PG_HCHUNK][32];

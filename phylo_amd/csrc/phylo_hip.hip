@@ -38,7 +38,7 @@ struct sweep_run {                       // a sweep being issued rank event by r
     uint64_t seed = 0;
     uint32_t flags = 0;
     int M = 1, launches = 0, next_r = 0;
-    bool twist = false, graph = false, lazy = false, timek = false, fuse_scan = false, active = false, local_book = false;
+    bool twist = false, graph = false, lazy = false, timek = false, active = false, local_book = false;
     bool mat_by_draws = false;             // sharded: owners find their adopted nodes from the draws (no pk_all_marks)
     bool logz_done = false;                // the last scan summed the log-normalisers (no pk_logz_total launch)
     bool book_mat = false;                 // bookkeeping and the writes of the adopted nodes share one launch (pk_rank_book_mat)
@@ -47,12 +47,12 @@ struct sweep_run {                       // a sweep being issued rank event by r
     int a_done_r = -1;                     // rank event whose first half (sweep_step_a) has been issued
 };
 
-// A/B switches of DESIGN.md section 6b, read from the environment ONCE (phylo_create): none changes a result bit
+// Switches of DESIGN.md section 6b, read from the environment ONCE (phylo_create): none changes a result bit.  Each one serves a
+// tool or a test (section 6b says which); a switch whose only use was to bring back a form that measured slower is not kept.
 struct env_switches {
-    bool eager_nodes = false, rehearse_sharded = false, replicated_book = false, fuse_scan = false,
-         book_one_per_wave = false, merge_pair_form = false, no_leaf_codes = false, one_launch = false,
-         persist_stamps = false, separate_materialise = false, grad_one_stream = false, grad_two_streams = false, rev_host_lists = false, no_remote_cache = false, no_spin_wait = false,
-         no_p2p = false, book_lp16 = false, no_sorted_draws = false, grad_quad_chunks = false, grad_rows_chain = false, grad_rows_no_overlap = false, grad_coeff_chain = false, grad_sort_late = false;
+    bool eager_nodes = false, rehearse_sharded = false, replicated_book = false, no_leaf_codes = false, one_launch = false,
+         persist_stamps = false, grad_one_stream = false, grad_two_streams = false, rev_host_lists = false, no_remote_cache = false,
+         no_p2p = false, grad_rows_chain = false, grad_coeff_chain = false;
     int persist_wgs = 0;                 // PHYLO_PERSIST_WGS: resident workgroups of the one-launch sweep (0 = default)
     unsigned long long p2p_wait_ticks = PK_P2P_WAIT_TICKS;   // PHYLO_P2P_WAIT_S: bound of a flag wait of the device-side exchange
     size_t p2p_copy_words = 65536;       // PHYLO_P2P_COPY_WORDS: exchanges beyond this many doubles copy with many workgroups (tests lower it)
@@ -63,27 +63,17 @@ struct env_switches {
         eager_nodes = getenv("PHYLO_EAGER_NODES") != nullptr;
         rehearse_sharded = getenv("PHYLO_REHEARSE_SHARDED") != nullptr;
         replicated_book = getenv("PHYLO_REPLICATED_BOOK") != nullptr;
-        fuse_scan = getenv("PHYLO_FUSE_SCAN") != nullptr;
-        book_one_per_wave = getenv("PHYLO_BOOK_ONE_PER_WAVE") != nullptr;
-        book_lp16 = getenv("PHYLO_BOOK_LP16") != nullptr;
-        no_sorted_draws = getenv("PHYLO_NO_SORTED_DRAWS") != nullptr;
-        grad_quad_chunks = getenv("PHYLO_GRAD_QUAD_CHUNKS") != nullptr;
         grad_rows_chain = getenv("PHYLO_GRAD_ROWS_CHAIN") != nullptr;
-        grad_rows_no_overlap = getenv("PHYLO_GRAD_ROWS_NO_OVERLAP") != nullptr;
         grad_coeff_chain = getenv("PHYLO_GRAD_COEFF_CHAIN") != nullptr;
-        grad_sort_late = getenv("PHYLO_GRAD_SORT_LATE") != nullptr;
-        merge_pair_form = getenv("PHYLO_MERGE_PAIR_FORM") != nullptr;
         no_leaf_codes = getenv("PHYLO_NO_LEAF_CODES") != nullptr;
         one_launch = getenv("PHYLO_ONE_LAUNCH") != nullptr;
         persist_stamps = getenv("PHYLO_PERSIST_STAMPS") != nullptr;
-        separate_materialise = getenv("PHYLO_SEPARATE_MATERIALISE") != nullptr;
         grad_one_stream = getenv("PHYLO_GRAD_ONE_STREAM") != nullptr;
         grad_two_streams = getenv("PHYLO_GRAD_TWO_STREAMS") != nullptr;
         rev_host_lists = getenv("PHYLO_REV_HOST_LISTS") != nullptr;
         no_remote_cache = getenv("PHYLO_NO_REMOTE_CACHE") != nullptr;
         { const char* e = getenv("PHYLO_REMOTE_CACHE_CAP"); remote_cache_cap = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_SCAN_MULTI_MIN"); scan_multi_min = e ? atoi(e) : 4096; }
-        no_spin_wait = getenv("PHYLO_NO_SPIN_WAIT") != nullptr;
         { const char* e = getenv("PHYLO_P2P"); no_p2p = e && atoi(e) == 0; }
         { const char* e = getenv("PHYLO_P2P_COPY_WORDS"); p2p_copy_words = e ? (size_t)atol(e) : 65536; }
         { const char* e = getenv("PHYLO_P2P_WAIT_S"); p2p_wait_ticks = e && atof(e) > 0 ? (unsigned long long)(atof(e) * 1e8) : PK_P2P_WAIT_TICKS; }
@@ -155,8 +145,7 @@ struct phylo_ctx {
     int32_t* d_merges = nullptr;         // [(N-1)][Kloc][2]
     int64_t* d_anc = nullptr;            // [(N-2)][Kloc]
     uint64_t* d_cdf[2] = {nullptr, nullptr};   // [K], double-buffered across rank events
-    unsigned int* d_counter = nullptr;   // [0] scan->bookkeeping flag, [1] hand-off timeout word
-    unsigned int epoch = 0;              // monotone hand-off epoch (never reset, never 0)
+    unsigned int* d_counter = nullptr;   // [1] timeout word of the bounded waits between workgroups ([0] unused)
     const double** d_pool_ptrs = nullptr; // [world] pool base of every rank (peer mappings)
     // sharded: remote nodes merged by this rank, fetched once per sweep (pk_pull_remote_children)
     int32_t* d_mirror = nullptr;         // [(N-1) K + 4]: node -> slot + 1 | 0 | -2; the last four words: [0] slots taken
@@ -583,7 +572,7 @@ int launch_scan(phylo_ctx* c, const double* logw, int Kg, int G, uint64_t* cdf, 
 // a training step, twice per step); after 2 ms of polling, block.
 int wait_event_spin(phylo_ctx* c, hipEvent_t ev) {
     const auto t0 = std::chrono::steady_clock::now();
-    for (; !c->env.no_spin_wait;) {
+    for (;;) {
         const hipError_t e = hipEventQuery(ev);
         if (e == hipSuccess) return PHYLO_OK;
         if (e != hipErrorNotReady) return fail(c, PHYLO_EHIP, "hipEventQuery: %s", hipGetErrorString(e));
@@ -1094,18 +1083,16 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     // primate.p's node size, more than a second collective costs
     const bool lazy = lazy_ok;
     int launches = 0;
-    const bool fuse_scan = !twist && !graph && G == 1 && c->env.fuse_scan;   // opt-in: measured neutral alone, -4 % with 3 sweeps in flight
     c->swept = false;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     // one sweep alone on one GPU with lazy nodes: the adopted nodes are written in the bookkeeping launch (pk_rank_book_mat), found
     // by the resampling draws, which pk_sweep_prologue then leaves in d_rdraw.  Batched sweeps keep the separate launch (measured:
     // 2.62e11 against 2.64e11 units/s with the grouped form of the combined launch in round 2; round 3, a launch set alone: 3.57e11 against 3.77e11).
-    const bool book_mat = lazy && c->world == 1 && c->comm.transport == 0 && !fuse_scan && N <= 64 && S <= 4096 && G == 1 && Kl <= 8192 &&
-                          !c->env.separate_materialise && !c->env.book_one_per_wave;
+    const bool book_mat = lazy && c->world == 1 && c->comm.transport == 0 && N <= 64 && S <= 4096 && G == 1 && Kl <= 8192;
     // sharded with lazy nodes: each owner finds ITS adopted nodes the same way (O(Kloc Kg / 64) comparisons) instead of every rank
     // searching the ancestors of all K particles (pk_all_marks, O(K) on every rank whatever the number of GPUs)
     const bool shard_form = c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded);
-    const bool mat_by_draws = lazy && shard_form && !twist && !c->env.replicated_book && !c->env.separate_materialise && S <= 4096 &&
+    const bool mat_by_draws = lazy && shard_form && !twist && !c->env.replicated_book && S <= 4096 &&
                               (((K / G) <= 4096 && Kl <= 8192) || ((K / G) % PK_MAT_GROUP == 0 && Kl % PK_MAT_GROUP == 0));
     const bool want_rdraw = book_mat || mat_by_draws;
     if (want_rdraw && !c->d_rdraw) CHK(dalloc(c, &c->d_rdraw, (size_t)R * K));
@@ -1124,7 +1111,7 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
         pa.mark = lazy ? c->d_mark : (unsigned int*)nullptr;
         pa.mark_words = lazy ? (unsigned int)mark_words : 0u;
         // large launches (batched sweeps): the matrices sorted by Pade order inside workgroups of 1024 (pk_sweep_draws_sorted)
-        const bool sorted = !c->jc && 2L * R * Kl >= 262144 && !c->env.no_sorted_draws;
+        const bool sorted = !c->jc && 2L * R * Kl >= 262144;
         const int NT = sorted ? 256 : 64;
         pa.draw_blocks = sorted ? cdiv(2L * R * Kl, PK_DRAW_ITEMS) : cdiv(2L * R * Kl, 64);
         pa.init_blocks = cdiv((long)K * N, 4 * NT);
@@ -1145,7 +1132,7 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     if (c->d_mirror) HIPCHK(c, hipMemsetAsync(c->d_mirror, 0, ((size_t)R * K + 4) * 4, c->stream));   // the cache of remote nodes is per sweep
     c->run = sweep_run{};
     c->run.seed = seed; c->run.flags = flags; c->run.M = M;
-    c->run.twist = twist; c->run.graph = graph; c->run.lazy = lazy; c->run.timek = timek; c->run.fuse_scan = fuse_scan;
+    c->run.twist = twist; c->run.graph = graph; c->run.lazy = lazy; c->run.timek = timek;
     c->run.book_mat = book_mat;
     c->run.mat_by_draws = mat_by_draws;
     c->run.launches = launches; c->run.next_r = 0; c->run.active = true;
@@ -1180,7 +1167,7 @@ static bool persist_plan(phylo_ctx* c, uint32_t flags, int G, int* Wg_out, int* 
     if (!(c->env.one_launch || (flags & PHYLO_ONE_LAUNCH))) return false;             // opt-in
     if (c->world != 1 || c->comm.transport != 0) return false;                       // sharded: collectives between launches
     if (flags & (PHYLO_TWISTING | PHYLO_KEEP_GRAPH | PHYLO_EAGER_NODES | PHYLO_TIME_KERNELS)) return false;   // launch path only
-    if (c->env.eager_nodes || c->env.fuse_scan || c->env.merge_pair_form || c->env.book_one_per_wave) return false;   // A/B switches of the launch path
+    if (c->env.eager_nodes) return false;                                           // A/B switch of the launch path
     if (c->N > 32 || c->N < 2) return false;                                        // one wave per particle: a lane per root slot, history rows in lanes
     const int Kg = c->K / G;
     if (Kg > PP_MAX_KG) return false;                                               // the group's cdf lives in LDS
@@ -1366,7 +1353,7 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
     const uint64_t seed = c->run.seed;
     const uint32_t flags = c->run.flags;
     const int M = c->run.M;
-    const bool twist = c->run.twist, graph = c->run.graph, lazy = c->run.lazy, timek = c->run.timek, fuse_scan = c->run.fuse_scan;
+    const bool twist = c->run.twist, graph = c->run.graph, lazy = c->run.lazy, timek = c->run.timek;
     int launches = 0;
     const size_t lds = pk_book_lds_bytes(N);
     const size_t plane = (size_t)K * N;
@@ -1476,17 +1463,6 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
             }
             CHK(launch_check(c, "pk_rank_book_mat"));
             ++launches;
-        } else if (r > 0 && fuse_scan) {
-            // scan of log w_{r-1} and the bookkeeping of rank event r in one launch
-            b.scan_logw = c->d_logw + (size_t)(r - 1) * K;
-            b.scan_cdf = c->d_cdf[cur];
-            b.scan_lse = c->d_lse + (r - 1);
-            b.flag = c->d_counter; b.epoch = ++c->epoch; b.timeout_word = c->d_counter + 1;
-            if (c->epoch == 0xffffffffu) c->epoch = 0;
-            const size_t lds2 = lds > pk_scan_lds_bytes(K) ? lds : pk_scan_lds_bytes(K);
-            hipLaunchKernelGGL(pk_rank_scan_book, dim3(K + 1), dim3(PK_COLS), lds2, c->stream, b);
-            CHK(launch_check(c, "pk_rank_scan_book"));
-            ++launches;
         } else {
             // sharded, plain proposal: every rank advances only ITS particles' root tables and reads an
             // adopted ancestor's row from the owner's slab over the peer mapping (ordered by the all-gather of the
@@ -1503,11 +1479,11 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
             // large launches (batched sweeps) are bound by instruction issue: 8 lanes per particle serve 8 particles with one
             // instruction stream (3.52e11 -> 3.68e11 units/s for a launch set of 20 sweeps; 4 lanes: no further gain); small
             // launches are latency chains and keep the shorter 16-lane form
-            if (N <= 16 && !c->env.book_one_per_wave && !c->env.book_lp16 && nbook >= 8192)
+            if (N <= 16 && nbook >= 8192)
                 hipLaunchKernelGGL(pk_rank_book_packed<8>, dim3(cdiv(nbook, 8)), dim3(64), lds * 8, c->stream, b);
-            else if (N <= 16 && !c->env.book_one_per_wave)   // 4 particles per wave (PK_AUX + 2 = 10 <= 16 lanes)
+            else if (N <= 16)                              // 4 particles per wave (PK_AUX + 2 = 10 <= 16 lanes)
                 hipLaunchKernelGGL(pk_rank_book_packed<16>, dim3(cdiv(nbook, 4)), dim3(64), lds * 4, c->stream, b);
-            else if (N <= 32 && !c->env.book_one_per_wave)   // 2 particles per wave
+            else if (N <= 32)                              // 2 particles per wave
                 hipLaunchKernelGGL(pk_rank_book_packed<32>, dim3(cdiv(nbook, 2)), dim3(64), lds * 2, c->stream, b);
             else
                 hipLaunchKernelGGL(pk_rank_book, dim3(nbook), dim3(64), lds, c->stream, b);
@@ -1524,7 +1500,8 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
             ++launches;
             if (c->comm.transport != 0) CHK(comm_exchange(c, nullptr, 0, 0, 1));   // peers read these nodes in place: order them before every rank's merge
         }
-        const bool nostore = (b.lazy || b.no_store) && !c->env.merge_pair_form;   // row-per-lane form when nothing is stored
+        // row-per-lane form when nothing is stored: pk_rank_merge is launched only when the node is stored
+        const bool nostore = b.lazy || b.no_store;
         const size_t mitems = (size_t)Kl * c->ntiles;                              // one wave per (particle, site tile)
         const dim3 mgrid((unsigned)mitems);
         if (timek && !twist) {  // events stamped with the kernel's own begin/end (what rocprofv3 --kernel-trace reports)
@@ -1567,7 +1544,7 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
                                 c->d_lse + r, R + 1, fold ? R : 0));
                 if (fold) c->run.logz_done = true;
                 ++launches;
-            } else if (!fuse_scan || twist || r + 1 == R) {    // otherwise the next rank event's launch scans these weights
+            } else {
                 const bool fold = r + 1 == R && K <= PP_SCAN_KERNEL_MAX_KG;
                 CHK(launch_scan(c, (const double*)(c->d_logw + (size_t)r * K), K, 1, (r + 1 < R) ? c->d_cdf[nxt] : (uint64_t*)nullptr,
                                 c->d_lse + r, 0, fold ? R : 0));
@@ -1732,7 +1709,7 @@ int phylo_synchronize(phylo_ctx* c) {
     return PHYLO_OK;
 }
 
-// The word every bounded wait between workgroups sets when it gives up (one-launch sweep, fused scan + bookkeeping): a sweep that
+// The word every bounded wait between workgroups sets when it gives up (one-launch sweep, device-side exchange): a sweep that
 // timed out is invalid.  The stream must be idle.  `pub`: the sweep's copy kernel left the word in pinned memory.
 static int check_timeout_word(phylo_ctx* c, bool pub) {
     unsigned int tmo = 0;
@@ -1998,7 +1975,7 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
     // stream, ahead of the early kernels below (they head the longest chain: lists -> sort -> chunk sums -> adopted nodes).
     // (their sort goes to the second stream as soon as the host has seen the sweep end: queued there behind the lists' event, it
     //  neither waits for the host to read the counts nor holds up the coefficient chain on this stream)
-    const bool sort_early = dev_lists && !c->env.grad_sort_late && !c->env.grad_one_stream;
+    const bool sort_early = dev_lists && !c->env.grad_one_stream;
     if (dev_lists) CHK(dev_lists_launch(c, c->stream, c->stream, true, false));
     hipLaunchKernelGGL(pg_omega, dim3(nrk), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_omega"));
@@ -2128,9 +2105,8 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
             const size_t cn = n_chunks - cbeg < 65535 ? n_chunks - cbeg : 65535;
             pg_args g2 = g;
             g2.cpart = g.cpart + cbeg * rowlen;
-            if (c->env.grad_quad_chunks) hipLaunchKernelGGL(pg_parent_chunks, dim3(cdiv(S, 16 * PG_CSTEPS), (unsigned)cn), dim3(256), 0, sB, g2, (int)cbeg);
-            else hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(S, 64), (unsigned)cn), dim3(256), 0, sB, g2, (int)cbeg);
-            CHK(launch_check(c, "pg_parent_chunks"));
+            hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(S, 64), (unsigned)cn), dim3(256), 0, sB, g2, (int)cbeg);
+            CHK(launch_check(c, "pg_parent_chunks_rows"));
         }
         return PHYLO_OK;
     };
@@ -2191,7 +2167,7 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
         g.row_timeout = (unsigned int*)(c->hd_dlmeta + PG_DL_META_INTS(R));
         // few enough workgroups to leave the coefficient chain room on every SIMD: the launch runs BESIDE that chain and waits, rank
         // event by rank event, for its completion words; else it is launched behind the chain's last event
-        rows_overlap = (size_t)pinfo.n_slow * (size_t)g.TS <= 512 && !c->env.grad_rows_no_overlap && g_backward_in_flight.load() <= 1;
+        rows_overlap = (size_t)pinfo.n_slow * (size_t)g.TS <= 512 && g_backward_in_flight.load() <= 1;
         g.coeff_done = c->d_row_done + (size_t)R * K * (size_t)cdiv(c->S, 256);
         g.coeff_ticket = g.coeff_done + R;
         g.coeff_mask = 0ull;
@@ -2390,9 +2366,8 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
         }
         const int nch = early_free ? 0 : rank_chunk0[r + 1] - rank_chunk0[r];   // (after the early pg_nodes_free: summed above, all rank events at once)
         if (nch > 0) {
-            if (c->env.grad_quad_chunks) hipLaunchKernelGGL(pg_parent_chunks, dim3(cdiv(S, 16 * PG_CSTEPS), nch), dim3(256), 0, sB, g, (int)rank_chunk0[r]);
-            else hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(S, 64), nch), dim3(256), 0, sB, g, (int)rank_chunk0[r]);
-            CHK(launch_check(c, "pg_parent_chunks"));
+            hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(S, 64), nch), dim3(256), 0, sB, g, (int)rank_chunk0[r]);
+            CHK(launch_check(c, "pg_parent_chunks_rows"));
             ++node_launches;
         }
         if (rows_form) {

@@ -447,11 +447,9 @@ __device__ __forceinline__ void pk_scan_tile(const double* logw, int K, int base
 }
 
 // `stage`: K-element scratch for the integer weights between the two passes: LDS when it fits, else cdf[].
-// `publish`: the final cdf is written with agent-scope (write-through) 8-byte stores, because workgroups
-// of the SAME launch read it after a flag hand-off (pk_rank_scan_book).
 __device__ __forceinline__ void pk_scan_block(const double* logw, int K, uint64_t* __restrict__ cdf,
                                               double* __restrict__ lse_out, pk_scan_lds* sh,
-                                              unsigned long long* stage, bool publish = false) {
+                                              unsigned long long* stage) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const bool one_tile = K <= 8 * PK_COLS;
     double v[8];
@@ -529,13 +527,7 @@ __device__ __forceinline__ void pk_scan_block(const double* logw, int K, uint64_
         __syncthreads();
         unsigned long long run = carry + incl - local;
         for (int i = 0; i < wv; ++i) run += sh->u4[i];
-        if (publish) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (lo + j < K)
-                    __hip_atomic_store(reinterpret_cast<unsigned long long*>(cdf) + lo + j, run + e[j], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-        } else if (lo + 8 <= K) {
+        if (lo + 8 <= K) {
             ulonglong2* q = reinterpret_cast<ulonglong2*>(cdf + lo);
             q[0] = make_ulonglong2(run + e[0], run + e[1]);
             q[1] = make_ulonglong2(run + e[2], run + e[3]);
@@ -585,17 +577,13 @@ __device__ __forceinline__ int pk_cdf_search(const uint64_t* __restrict__ cdf, i
 
 // the same search by one wave: 64 probes per step.  The first round's probe addresses do not depend on the
 // threshold, so `total` and the coarse probes travel together: 2 dependent round trips for K <= 4096.
-__device__ __forceinline__ uint64_t pk_cdf_ld(const uint64_t* cdf, int i, bool agent) {
-    if (agent) return __hip_atomic_load(reinterpret_cast<const unsigned long long*>(cdf) + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return cdf[i];
-}
-__device__ __forceinline__ int pk_cdf_search_wave(const uint64_t* cdf, int K, uint64_t R, int lane, bool agent = false) {
+__device__ __forceinline__ int pk_cdf_search_wave(const uint64_t* cdf, int K, uint64_t R, int lane) {
     int lo = 0, hi = K;             // invariant: answer in [lo, hi), cdf[hi-1] > thr
     int step = (K + 63) >> 6;
     int p = (lane + 1) * step - 1;
     if (p > K - 1) p = K - 1;
-    const uint64_t total = pk_cdf_ld(cdf, K - 1, agent);
-    uint64_t c = pk_cdf_ld(cdf, p, agent);
+    const uint64_t total = cdf[K - 1];
+    uint64_t c = cdf[p];
     const uint64_t thr = pm_mulhi64(R, total);
     for (;;) {
         const unsigned long long mask = __ballot(c > thr);
@@ -609,7 +597,7 @@ __device__ __forceinline__ int pk_cdf_search_wave(const uint64_t* cdf, int K, ui
         step = (hi - lo + 63) >> 6;
         p = lo + (lane + 1) * step - 1;
         if (p > hi - 1) p = hi - 1;
-        c = pk_cdf_ld(cdf, p, agent);
+        c = cdf[p];
     }
     return lo;
 }
@@ -682,10 +670,6 @@ struct pk_rank_args {
     double* logw_r; double* ll_r;                         // [K] rows (global columns)
     int32_t* merges;                                      // [R][Kloc][2]
     int64_t* ancestors;                                   // [R-1][Kloc]
-    // scan -> bookkeeping hand-off inside ONE launch (pk_rank_scan_book): workgroup 0 scans log w_{r-1}, publishes
-    // cdf[] write-through and then stores `epoch` into *flag; the bookkeeping workgroups poll it (bounded).
-    const double* scan_logw; uint64_t* scan_cdf; double* scan_lse;
-    unsigned int* flag; unsigned int epoch; unsigned int* timeout_word;
     // lazy nodes (single GPU, plain proposal): the merge kernel does not store the new node; a node is written
     // only when some particle adopts its creator's table at the next resampling (pk_materialize_node)
     int lazy;
@@ -780,18 +764,7 @@ __device__ __forceinline__ void pk_book_particle(const pk_rank_args& a, int kg, 
         }
         int anc = kg;
         if (a.r > 0) {
-            const uint64_t R = Rdraw;
-            if (a.flag) {                             // the scan runs in workgroup 0 of this launch: wait for its flag
-                unsigned int spins = 0;
-                while (__hip_atomic_load(a.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.epoch) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > (1u << 22)) {       // ~ seconds: give up loudly instead of hanging the GPU
-                        if (lane == 0) __hip_atomic_store(a.timeout_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                }
-            }
-            anc = gbase + pk_cdf_search_wave(a.cdf + gbase, a.group_seeds ? a.Kg : a.K, R, lane, a.flag != nullptr);
+            anc = gbase + pk_cdf_search_wave(a.cdf + gbase, a.group_seeds ? a.Kg : a.K, Rdraw, lane);
         }
         const int32_t* ro = a.roots_old + (size_t)anc * N;
         const int32_t* co = a.cnt_old + (size_t)anc * N;
@@ -1413,43 +1386,6 @@ __global__ __launch_bounds__(64) void pk_rank_book(const pk_rank_args a) {
     }
 }
 
-// Scan + bookkeeping in ONE launch: workgroup 0 (256 threads) runs the resampling scan of log w_{r-1} and
-// publishes the cdf; workgroups 1..K (their first wave) do the bookkeeping of particle blockIdx-1, overlapping
-// everything that does not depend on the resampling outcome with the scan and polling the flag just before
-// the index search.  Hand-off form: 8-byte agent-scope stores of the payload, every storing wave drained
-// (s_waitcnt vmcnt(0)), workgroup barrier, ONE agent-scope flag store; consumers poll the flag relaxed and read
-// the payload with agent-scope loads (cdna_hip_programming.md Guideline 16, "8-B agent atomics both sides").
-// Workgroup 0 is dispatched first and waits for nobody, so the launch cannot deadlock; the poll is bounded anyway.
-__global__ __launch_bounds__(PK_COLS) void pk_rank_scan_book(const pk_rank_args a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (blockIdx.x == 0) {
-        pk_scan_lds* sh = reinterpret_cast<pk_scan_lds*>(smem);
-        unsigned long long* stage = (a.K <= PK_SCAN_LDS_MAX_K) ? reinterpret_cast<unsigned long long*>(smem + sizeof(pk_scan_lds))
-                                                               : reinterpret_cast<unsigned long long*>(a.scan_cdf);
-        pk_scan_block(a.scan_logw, a.K, a.scan_cdf, a.scan_lse, sh, stage, true);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // every storing wave drains its stores
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(a.flag, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    if (threadIdx.x >= 64) return;                              // bookkeeping uses one wave
-    const int kg = blockIdx.x - 1;
-    const pk_book_lds L = pk_book_carve(smem, a.N);
-    const bool local = kg >= a.k0 && kg < a.k0 + a.Kloc;
-    pk_book_particle(a, kg, local, L);
-    if (local && threadIdx.x < PK_AUX + 2) {
-        const int k = kg - a.k0;
-        if (threadIdx.x < PK_AUX) a.aux[(size_t)k * PK_AUX + threadIdx.x] = L.aux[threadIdx.x];
-        else a.child[k * 2 + (threadIdx.x - PK_AUX)] = L.misc[threadIdx.x - PK_AUX];
-    }
-    if (a.lazy && a.r > 0 && threadIdx.x == 0) {
-        // this particle adopted the table of `anc`: the node anc created at the previous rank event is now live;
-        // pk_materialize_adopted writes the marked nodes of that rank event.
-        const int anc = L.misc[3];                    // every rank sees every adoption; the OWNER of the node writes it
-        a.mark[(size_t)(a.r - 1) * a.K + anc] = 1u;  // plain store: every adopter writes the same value (no contended atomics)
-    }
-}
-
 __device__ __forceinline__ const double* pk_node_ptr(const pk_rank_args& a, int id) {
     const size_t node_sz = (size_t)a.S * 4;
     // a child is a leaf (id < N, replicated on every GPU) or the node id = N + rho*K + kappa created at rank
@@ -1948,6 +1884,8 @@ __global__ __launch_bounds__(PK_COLS) __attribute__((amdgpu_waves_per_eu(5, 8)))
         if (codedR) pk_store_tile<false, true, ST>(s0, s1, wv, lane, Lp, Rp, Lc, Rc, out, Pl, Pr, tabL, tabR, pi, likbuf, stage);       \
         else pk_store_tile<false, false, ST>(s0, s1, wv, lane, Lp, Rp, Lc, Rc, out, Pl, Pr, tabL, tabR, pi, likbuf, stage);             \
     }
+    // the host launches this kernel only for a node that is stored (launches that store nothing take pk_rank_merge_nostore);
+    // the STORE=false branch is unreachable but kept: dropping it changes this kernel's register allocation, not measured
     if (a.lazy || a.no_store) { PK_MERGE_DISPATCH(false) } else { PK_MERGE_DISPATCH(true) }
 #undef PK_MERGE_DISPATCH
     __syncthreads();

@@ -399,23 +399,7 @@ def test_sweep_edge_shapes(N, S, K):
     ctx.close()
 
 
-def test_fused_scan_bookkeeping_launch(primate, monkeypatch):
-    """Opt-in single-launch scan + bookkeeping (bounded flag hand-off inside the launch): same bits."""
-    Q = O.get_Q(O.init_y_q())
-    a = make_ctx(primate, 200, Q)
-    ra = a.sweep(9)
-    a.close()
-    monkeypatch.setenv("PHYLO_FUSE_SCAN", "1")            # the switches are read when a context is created
-    b = make_ctx(primate, 200, Q)
-    for seed in (9, 10, 11):
-        rb = b.sweep(seed)
-        if seed == 9:
-            assert_bit_equal(ra['log_weights'], rb['log_weights'], "fused vs separate launches")
-            np.testing.assert_array_equal(ra['ancestors'], rb['ancestors'])
-    b.close()
-
-
-def test_lazy_nodes_equal_eager_nodes(monkeypatch):
+def test_lazy_nodes_equal_eager_nodes():
     """Lazy nodes (only nodes whose creator survives the next resampling are written) are an access-path
     optimisation: every output, and every node partial fetched afterwards, has the same bits."""
     g = load_dataset('primate_data')['genome']
@@ -423,7 +407,6 @@ def test_lazy_nodes_equal_eager_nodes(monkeypatch):
     Q = O.get_Q(O.init_y_q())
     lam = np.full(N - 1, 10.0)
     K = 160
-    monkeypatch.setenv("PHYLO_LAZY_NODES", "1")
     ctx = make_ctx(g, K, Q)
     for seed in (0, 1):
         out = ctx.sweep(seed)
@@ -434,8 +417,7 @@ def test_lazy_nodes_equal_eager_nodes(monkeypatch):
         for (r, k) in [(0, 0), (3, 17), (N - 2, K - 1), (5, 100)]:        # dead and live nodes alike
             assert_bit_equal(ctx.sweep_node(r, k), ref['nodes'][r, k], "lazy node (%d,%d)" % (r, k))
     ctx.close()
-    # large-S configuration where lazy nodes are the default
-    monkeypatch.delenv("PHYLO_LAZY_NODES")
+    # large-S configuration
     d = synthetic_alignment(6, 9000)
     ctx = make_ctx(d['genome'], 24, Q)
     out = ctx.sweep(4)

@@ -95,7 +95,7 @@ def test_sharded_lazy_nodes_bit_identical():
     """Lazy nodes when sharded: the owner writes an adopted node, a barrier collective orders it before the
     peers' merges; phylo_sweep_node completes the pool collectively."""
     world, K, seed = 2, 64, 7
-    parts = run_world(world, K, 'primate_data', seed, False, n_sweeps=2, extra_env={'PHYLO_LAZY_NODES': '1'})
+    parts = run_world(world, K, 'primate_data', seed, False, n_sweeps=2)
     g = load_dataset('primate_data')['genome']
     N = g.shape[0]
     Q = O.get_Q(O.init_y_q())
