@@ -56,7 +56,10 @@ enum {
                                           either (phylo_sweep_node writes them on demand) unless this flag is set */
     PHYLO_KEEP_GRAPH = 1u << 4,        /* keep what phylo_sweep_backward needs (root-table history of every rank
                                           event, every node; with PHYLO_TWISTING also every sub-sample's branch lengths,
-                                          transition matrices and potential); one GPU.  Nodes are stored eagerly with
+                                          transition matrices and potential).  On a sharded context: the plain proposal
+                                          with S <= 4096 only (PHYLO_EINVAL otherwise); the sweep then advances all K root
+                                          tables on every rank and ends with an exchange that makes the kept graph whole on
+                                          every rank.  Nodes are stored eagerly with
                                           PHYLO_TWISTING or more than 4096 sites; otherwise they stay lazy (the reverse pass then
                                           reads no node but the adopted ones) */
     PHYLO_ONE_LAUNCH = 1u << 5,        /* run the whole sweep as ONE launch of resident workgroups (phylo_persist.h) where that
@@ -207,7 +210,13 @@ int phylo_sweep_node(phylo_ctx* ctx, int r, int k, double* out_Sx4);
  * outputs are still produced (the reference holds them constant; the host ignores them).
  * May be called right after phylo_sweep_async (before the fetch): it is then queued behind the sweep without a host round trip.
  * perf (may be NULL): sweep_ms = device time of the reverse pass, host step included; merge_ms = that host step (building the
- * integer lists of adopters and parents) alone; n_launches. */
+ * integer lists of adopters and parents) alone; n_launches.
+ * Sharded context (phylo_comm_init / phylo_comm_share): a collective call -- every rank makes it, in the same order, after the
+ * same sweep -- that returns the gradient of the GLOBAL log Z-hat, the same bits on every rank (each rank runs the whole pass over
+ * the genealogy its sweep gathered, reading node rows from their owners' pools, and ends with a barrier; integer lists by the host
+ * builders, a launch per rank event).  Refused there: a sweep with
+ * PHYLO_TWISTING | PHYLO_KEEP_GRAPH, batched sweeps and more than 4096 sites (PHYLO_EINVAL, at the sweep); a backward without a
+ * kept graph is PHYLO_ESTATE as on one GPU. */
 int phylo_sweep_backward(phylo_ctx* ctx, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q,
                          phylo_stats* perf);
 
@@ -217,6 +226,8 @@ int phylo_sweep_backward(phylo_ctx* ctx, double* d_lam_l, double* d_lam_r, doubl
  * phylo_vi_gradients: model from the variables (vcsmc.py:133-148; jc != 0: the JC69 constants) -> phylo_set_model -> sweep with
  * PHYLO_KEEP_GRAPH on the context's leaves -> phylo_sweep_backward -> chain rules; grads = d logZ / d variables, packed alike
  * (zeros for y_q, y_station under JC69).  fwd / bwd (may be NULL): phylo_sweep_fetch's and phylo_sweep_backward's stats.
+ * On a sharded context phylo_vi_gradients is a collective call like phylo_sweep_backward (every rank passes the same seed and
+ * variables: it is ONE particle system) and every rank receives the same gradient bits.
  * phylo_vi_apply: kind 0 tf.train.GradientDescentOptimizer (var += lr d logZ / d var), 1 tf.train.AdamOptimizer (TF 1.15
  * defaults are beta1 0.9, beta2 0.999, eps 1e-8; t, m, v: its state, m and v packed like the variables, zero at the start). */
 int phylo_vi_gradients(phylo_ctx* ctx, uint64_t seed, uint32_t flags, int M, int jc, const double* vars, double* logZ, double* grads,

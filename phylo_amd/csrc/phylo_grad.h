@@ -54,6 +54,9 @@ struct pg_args {
     pg_twist tw;
     const double* leaves;              // [N][S][4]
     const double* pool;                // [R][K][S][4]
+    const double* const* pool_ptrs;    // NULL, or (sharded) [world] every rank's pool [R][Kloc][S][4] as mapped here: node (r, k) is
+                                       // read from its owner's pool (the merge's addressing, pk_node_ptr; `pool` is unused)
+    int Kloc;                          // particles per rank when pool_ptrs is set
     double* adj;                       // [R][K][S][4]: d logZ / d node
     const double* Pmat;                // [R][K][32]
     const double *bl, *br;             // [R][K]
@@ -126,8 +129,16 @@ __device__ __forceinline__ double pg_block_sum(double v, double* sh /*[4]*/) {
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
+// row of internal node x = r K + k (0-based)
+__device__ __forceinline__ const double* pg_node_row(const pg_args& a, size_t x) {
+    const size_t row = (size_t)a.S * 4;
+    if (__builtin_expect(a.pool_ptrs == nullptr, 1)) return a.pool + x * row;
+    // (32-bit unsigned divisions, kept off the unsharded path: R K < 2^31)
+    const unsigned xu = (unsigned)x, rho = xu / (unsigned)a.K, kap = xu - rho * (unsigned)a.K, owner = kap / (unsigned)a.Kloc;
+    return a.pool_ptrs[owner] + ((size_t)rho * a.Kloc + (kap - owner * (unsigned)a.Kloc)) * row;
+}
 __device__ __forceinline__ const double* pg_row(const pg_args& a, int id) {
-    return id < a.N ? a.leaves + (size_t)id * a.S * 4 : a.pool + (size_t)(id - a.N) * a.S * 4;
+    return id < a.N ? a.leaves + (size_t)id * a.S * 4 : pg_node_row(a, (size_t)(id - a.N));
 }
 
 __device__ __constant__ double pg_inv_k[19] = {0.0, 1.0 / 1, 1.0 / 2, 1.0 / 3, 1.0 / 4, 1.0 / 5, 1.0 / 6, 1.0 / 7, 1.0 / 8, 1.0 / 9, 1.0 / 10,
@@ -626,7 +637,7 @@ __global__ __launch_bounds__(256) void pg_nodes(pg_args a, int r) {
     __syncthreads();
     const double* Lrow = pg_row(a, a.child[node * 2]);
     const double* Rrow = pg_row(a, a.child[node * 2 + 1]);
-    const double* xrow = a.pool + node * row;
+    const double* xrow = pg_node_row(a, node);
     double* orow = a.adj + node * row;
     const double* Pl = shOwn;
     const double* Pr = shOwn + 16;
@@ -960,7 +971,7 @@ __device__ __forceinline__ void pg_nodes_rows_body(const pg_args& a, int r_arg, 
     const size_t so = (size_t)(live ? s : a.S - 1) * 4;
     const double* Lrow = pg_row(a, a.child[node * 2]);
     const double* Rrow = pg_row(a, a.child[node * 2 + 1]);
-    const double* xrow = a.pool + node * row;
+    const double* xrow = pg_node_row(a, node);
     double* orow = a.adj + node * row;
     double x[4], L[4], Rv[4], xb[4], x0[4];
 #pragma unroll
@@ -1546,7 +1557,7 @@ __global__ __launch_bounds__(256) void pg_twist_xchunks(pg_args a, int r, int ch
     const bool live = s < a.S;
     const size_t soff = (size_t)(live ? s : a.S - 1) * 4;
     const int n = a.N - r, M = a.tw.M, J = (n * (n - 1) / 2) * M;
-    const double* xr = a.pool + (size_t)(x - a.N) * a.S * 4 + soff;
+    const double* xr = pg_node_row(a, (size_t)(x - a.N)) + soff;
     const double x0 = xr[0], x1 = xr[1], x2 = xr[2], x3 = xr[3];
     const double pi[4] = {a.pi[0], a.pi[1], a.pi[2], a.pi[3]};
     double xb[4] = {0.0, 0.0, 0.0, 0.0};

@@ -40,6 +40,7 @@ struct sweep_run {                       // a sweep being issued rank event by r
     int M = 1, launches = 0, next_r = 0;
     bool twist = false, graph = false, lazy = false, timek = false, active = false, local_book = false;
     bool mat_by_draws = false;             // sharded: owners find their adopted nodes from the draws (no pk_all_marks)
+    bool replicated_book = false;          // sharded: every rank advances all K root tables (PHYLO_REPLICATED_BOOK; a kept graph)
     bool logz_done = false;                // the last scan summed the log-normalisers (no pk_logz_total launch)
     bool book_mat = false;                 // bookkeeping and the writes of the adopted nodes share one launch (pk_rank_book_mat)
     int G = 1;                             // independent sweeps batched in this context (phylo_sweep_batch_async)
@@ -199,6 +200,14 @@ struct phylo_ctx {
     hipEvent_t ev_gcopy = nullptr;
     std::vector<int32_t> h_cur;          // scratch of the counting sorts
     std::vector<double> h_vi_lam;        // phylo_vi_gradients: the rates of the step (phylo_set_model copies them)
+    // sharded PHYLO_KEEP_GRAPH: whole-K copies of the per-rank records the reverse pass reads, made after the last rank event
+    // (graph_gather), and their exchange buffer (pk_gx_pack / pk_gx_unpack); node rows stay in their owners' pools
+    int32_t* d_gchild = nullptr;         // [R][K][2]
+    double *d_gbl = nullptr, *d_gbr = nullptr, *d_gPmat = nullptr;   // [R][K], [R][K], [R][K][32]
+    int64_t* d_ganc = nullptr;           // [(R-1)][K]
+    unsigned long long* d_gx = nullptr;  // [chunks][world][gx_cl] words (fine-grained: peers read it over their mappings)
+    const unsigned long long** d_gx_src = nullptr;   // [world] where rank p's words are read from
+    size_t gx_seg = 0, gx_cl = 0;        // words per rank, words per chunk
     std::vector<int32_t> h_xlists;       // ... of its twisted part
     hipEvent_t evb0 = nullptr, evb1 = nullptr, ev_model = nullptr;
     // reverse pass: the adopted nodes' chain runs on gstream beside the coefficient chain on `stream`; ev_coeff[r]: C of rank event r done
@@ -317,12 +326,15 @@ void free_sweep_state(phylo_ctx* c) {
     c->htw_rows = 0;
     c->last_graph_twist = false;
     void* gr[] = {c->d_hroots, c->d_hcnt, c->d_pos, c->d_hrootll, c->d_adj, c->d_om, c->d_G, c->d_C, c->d_part, c->d_nodeg,
-                  c->d_leafpi, c->d_leafterm, c->d_terms, c->d_gout, c->d_ad_off};
+                  c->d_leafpi, c->d_leafterm, c->d_terms, c->d_gout, c->d_ad_off, c->d_gchild, c->d_gbl, c->d_gbr, c->d_gPmat,
+                  c->d_ganc, c->d_gx, (void*)c->d_gx_src};
     for (void* p : gr)
         if (p) (void)hipFree(p);
     c->d_hroots = c->d_hcnt = c->d_pos = nullptr;
     c->d_hrootll = c->d_adj = c->d_om = c->d_G = c->d_C = c->d_part = c->d_nodeg = nullptr;
     c->d_leafpi = c->d_leafterm = c->d_terms = c->d_gout = nullptr;
+    c->d_gchild = nullptr; c->d_gbl = c->d_gbr = c->d_gPmat = nullptr; c->d_ganc = nullptr;
+    c->d_gx = nullptr; c->d_gx_src = nullptr; c->gx_seg = c->gx_cl = 0;
     c->d_ad_off = c->d_ad_idx = c->d_par_off = c->d_par_idx = nullptr;
     c->d_heavy = c->d_chunk_beg = c->d_chunk_cnt = nullptr;
     c->d_slow_flag = c->d_slow_idx = c->d_adp = nullptr;
@@ -513,6 +525,31 @@ int ensure_graph_state(phylo_ctx* c) {
         c->d_ad_idx = D.ad_idx; c->d_par_off = D.par_off; c->d_par_idx = D.par_idx;
         c->d_heavy = D.heavy; c->d_chunk_beg = D.chunk_beg; c->d_chunk_cnt = D.chunk_cnt;
         c->d_slow_flag = D.slow_flag; c->d_slow_idx = D.slow_idx; c->d_adp = D.adp;
+    }
+    if (c->world > 1) {                                    // sharded: the whole-K records of graph_gather and its exchange buffer
+        const size_t Kl = c->Kloc, W = c->world;
+        CHK(dalloc(c, &c->d_gchild, R * K * 2));
+        CHK(dalloc(c, &c->d_gbl, R * K));
+        CHK(dalloc(c, &c->d_gbr, R * K));
+        CHK(dalloc(c, &c->d_gPmat, R * K * 32));
+        CHK(dalloc(c, &c->d_ganc, (R > 1 ? R - 1 : 1) * K));
+        // words per rank: children 2, branch lengths 2, matrices 32 per (r, k); ancestors
+        c->gx_seg = R * Kl * 36 + (R > 1 ? (R - 1) * Kl : 0);
+        c->gx_cl = c->gx_seg < PHYLO_SHM_SLOT / 8 ? c->gx_seg : PHYLO_SHM_SLOT / 8;   // (a chunk fits the host-mediated transport's slot)
+        const size_t words = (c->gx_seg + c->gx_cl - 1) / c->gx_cl * c->gx_cl * W;
+        void* buf = nullptr;
+        if (hipExtMallocWithFlags(&buf, words * 8, hipDeviceMallocFinegrained) != hipSuccess) {
+            (void)hipGetLastError();
+            HIPCHK(c, hipMalloc(&buf, words * 8));
+        }
+        c->d_gx = (unsigned long long*)buf;
+        CHK(dalloc(c, &c->d_gx_src, W));
+        std::vector<void*> src(W, buf);                    // collective path: every rank's words land in the own buffer
+        if (c->p2p) {                                      // device-side exchange: read from the peers' buffers (collective: mapped once)
+            int rc = phylo_comm_map_extra(c->comm, buf, &src, c->stream, &c->err);
+            if (rc != PHYLO_OK) return rc;
+        }
+        HIPCHK(c, hipMemcpy((void*)c->d_gx_src, src.data(), W * sizeof(void*), hipMemcpyHostToDevice));
     }
     if (!c->evb0) {
         HIPCHK(c, hipEventCreate(&c->evb0));
@@ -1043,7 +1080,10 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     // Pays when a node is large (HBM-bound merges); on small nodes the extra launch costs more than the stores.
     const bool graph = (flags & PHYLO_KEEP_GRAPH) != 0;
     if (graph) {
-        if (c->world != 1) return fail(c, PHYLO_EINVAL, "PHYLO_KEEP_GRAPH needs an unsharded context");
+        if (c->world != 1) {                               // sharded: the plain proposal on nodes of one site tile (graph_gather)
+            if (twist) return fail(c, PHYLO_EINVAL, "PHYLO_KEEP_GRAPH with PHYLO_TWISTING needs an unsharded context");
+            if (S > 4096) return fail(c, PHYLO_EINVAL, "PHYLO_KEEP_GRAPH on a sharded context needs S <= 4096 sites (got %d)", S);
+        }
         CHK(ensure_graph_state(c));
         if (twist) {                                       // every rank event keeps its sub-samples: rows [r][k][J_r]
             c->h_joff.assign((size_t)R + 1, 0);
@@ -1092,7 +1132,10 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     // sharded with lazy nodes: each owner finds ITS adopted nodes the same way (O(Kloc Kg / 64) comparisons) instead of every rank
     // searching the ancestors of all K particles (pk_all_marks, O(K) on every rank whatever the number of GPUs)
     const bool shard_form = c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded);
-    const bool mat_by_draws = lazy && shard_form && !twist && !c->env.replicated_book && S <= 4096 &&
+    // a sharded sweep that keeps its graph advances all K root tables on every rank: the history planes it writes are then whole
+    // everywhere (the owner-held tables that peers read are the two planes of d_tables, not the history)
+    const bool replicated_book = c->env.replicated_book || (graph && c->world > 1);
+    const bool mat_by_draws = lazy && shard_form && !twist && !replicated_book && S <= 4096 &&
                               (((K / G) <= 4096 && Kl <= 8192) || ((K / G) % PK_MAT_GROUP == 0 && Kl % PK_MAT_GROUP == 0));
     const bool want_rdraw = book_mat || mat_by_draws;
     if (want_rdraw && !c->d_rdraw) CHK(dalloc(c, &c->d_rdraw, (size_t)R * K));
@@ -1135,6 +1178,7 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     c->run.twist = twist; c->run.graph = graph; c->run.lazy = lazy; c->run.timek = timek;
     c->run.book_mat = book_mat;
     c->run.mat_by_draws = mat_by_draws;
+    c->run.replicated_book = replicated_book;
     c->run.launches = launches; c->run.next_r = 0; c->run.active = true;
     c->run.G = G;
     return PHYLO_OK;
@@ -1313,7 +1357,7 @@ static int sweep_step_a(phylo_ctx* c) {
     if (r >= R) return fail(c, PHYLO_ESTATE, "all %d rank events of this sweep have been issued", R);
     c->run.a_done_r = r;
     const bool shard_form = c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded);   // the env: one-rank rehearsal
-    if (!(shard_form && c->run.lazy && !c->run.twist && !c->env.replicated_book) || r == 0) return PHYLO_OK;
+    if (!(shard_form && c->run.lazy && !c->run.twist && !c->run.replicated_book) || r == 0) return PHYLO_OK;
     const int G = c->run.G;
     pk_rank_args b{};
     b.r = r; b.n = N - r; b.N = N; b.S = S; b.K = K; b.Kloc = Kl; b.k0 = c->k0;
@@ -1321,7 +1365,7 @@ static int sweep_step_a(phylo_ctx* c) {
     b.cdf = c->d_cdf[r & 1];
     b.Kg = K / G; b.group_seeds = G > 1 ? c->d_group_seeds : nullptr;
     b.leaves = c->d_leaves; b.pool = c->d_pool; b.pool_ptrs = c->d_pool_ptrs;
-    b.mirror = (c->run.twist || c->env.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
+    b.mirror = (c->run.twist || c->run.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
     b.leaf_codes = c->leaves_coded ? c->d_leaf_codes : nullptr;
     b.lazy = 1; b.mark = c->d_mark; b.child_all = c->d_child; b.Pmat_all = c->d_Pmat;
     if (c->run.mat_by_draws) {
@@ -1391,7 +1435,7 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
         b.leaves = c->d_leaves; b.pool = c->d_pool; b.pool_ptrs = c->d_pool_ptrs;
         // the cache of remote nodes is filled by the bookkeeping launch, which must come behind the owners' writes of this rank
         // event's adopted nodes: not so with replicated bookkeeping (and the twisted proposal reads its roots elsewhere)
-        b.mirror = (twist || c->env.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
+        b.mirror = (twist || c->run.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
         b.leaf_codes = c->leaves_coded ? c->d_leaf_codes : nullptr;
         b.Pmat = c->d_Pmat + (size_t)r * Kl * 32;
         b.pi = c->d_pi;
@@ -1467,7 +1511,7 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
             // sharded, plain proposal: every rank advances only ITS particles' root tables and reads an
             // adopted ancestor's row from the owner's slab over the peer mapping (ordered by the all-gather of the
             // previous rank event, like the node pool) instead of replicating the bookkeeping of all K particles
-            const bool local_book = (c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded)) && !c->env.replicated_book;
+            const bool local_book = (c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded)) && !c->run.replicated_book;
             if (local_book) {
                 b.tab_ptrs = c->d_tab_ptrs;
                 b.tab_off_rootll = (size_t)cur * K * N * 8;
@@ -1532,7 +1576,8 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
         {
             if (c->comm.transport != 0) {
                 if (!c->run.local_book) {
-                    hipLaunchKernelGGL(pk_fix_rootll, dim3(cdiv(K, 256)), dim3(256), 0, c->stream, c->d_rootll[nxt],
+                    hipLaunchKernelGGL(pk_fix_rootll, dim3(cdiv(K, 256)), dim3(256), 0, c->stream,
+                                       graph ? c->d_hrootll + plane * (r + 1) : c->d_rootll[nxt],
                                        (const double*)(c->d_nodell + N + (size_t)r * K), K, N, N - r, c->k0, Kl);
                     CHK(launch_check(c, "pk_fix_rootll"));
                     ++launches;
@@ -1605,6 +1650,53 @@ int phylo_sweep_step_group(phylo_ctx** ctxs, int n) {
     return PHYLO_OK;
 }
 
+// Sharded PHYLO_KEEP_GRAPH, behind the last rank event: every rank's records of its particles (children, branch lengths, matrices,
+// ancestors) into whole-K arrays on every rank (pk_gx_pack / pk_gx_unpack).  Node rows are not copied: the reverse pass reads
+// them from their owners' pools over the peer mappings (pg_node_row).  Device-side exchange: barrier, the peers' buffers read
+// over the mappings, barrier (nobody packs again before every reader is done); collective path: the all-gather of the buffers in
+// chunks, then the same tail.  A collective: every rank's sweep ends here.  *launches: kernels this issued.
+static int graph_gather(phylo_ctx* c, int* launches) {
+    const int K = c->K, Kl = c->Kloc, R = c->N - 1;
+    pk_gx_args a{};
+    a.world = c->world; a.me = c->rank; a.Kloc = Kl; a.K = K;
+    a.seg = c->gx_seg; a.cl = c->gx_cl;
+    a.xbuf = c->d_gx; a.xsrc = c->d_gx_src;
+    int nf = 0;
+    auto field = [&](const void* src, size_t stride, size_t off, void* dst, int rows, int w, int wide) {
+        pk_gx_field& f = a.f[nf++];
+        f.src = src; f.src_stride = stride; f.src_off = off; f.dst = dst; f.rows = rows; f.w = w; f.wide = wide;
+    };
+    field(c->d_child, (size_t)Kl * 2, 0, c->d_gchild, R, 2, 0);
+    field(c->d_bl, (size_t)Kl, 0, c->d_gbl, R, 1, 1);
+    field(c->d_br, (size_t)Kl, 0, c->d_gbr, R, 1, 1);
+    field(c->d_Pmat, (size_t)Kl * 32, 0, c->d_gPmat, R, 32, 1);
+    if (R > 1) field(c->d_anc, (size_t)Kl, 0, c->d_ganc, R - 1, 1, 1);
+    a.n_fields = nf;
+    {   // (the word count the buffer was sized for)
+        size_t words = 0;
+        for (int i = 0; i < nf; ++i) words += (size_t)a.f[i].rows * Kl * a.f[i].w;
+        if (words != a.seg) return fail(c, PHYLO_EINVAL, "graph_gather: %zu words against a buffer of %zu per rank", words, a.seg);
+    }
+    const unsigned pack_wgs = (unsigned)(a.seg / 256 + 1 < 2048 ? a.seg / 256 + 1 : 2048);
+    hipLaunchKernelGGL(pk_gx_pack, dim3(pack_wgs), dim3(256), 0, c->stream, a);
+    CHK(launch_check(c, "pk_gx_pack"));
+    if (c->p2p) {
+        CHK(comm_exchange(c, nullptr, 0, 0, 1));
+    } else {
+        const size_t chunks = (a.seg + a.cl - 1) / a.cl;
+        for (size_t j = 0; j < chunks; ++j) {
+            double* arr[1] = {reinterpret_cast<double*>(c->d_gx + j * (size_t)c->world * a.cl)};
+            int rc = phylo_comm_allgather_inplace(c->comm, arr, 1, a.cl, c->stream, &c->err);
+            if (rc != PHYLO_OK) return rc;
+        }
+    }
+    const size_t total = a.seg * (size_t)c->world;
+    hipLaunchKernelGGL(pk_gx_unpack, dim3((unsigned)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096)), dim3(256), 0, c->stream, a);
+    CHK(launch_check(c, "pk_gx_unpack"));
+    *launches += c->p2p ? 4 : 2;                           // pack, unpack (+ the two barrier kernels of the device-side exchange)
+    return comm_exchange(c, nullptr, 0, 0, 1);
+}
+
 int phylo_sweep_finish(phylo_ctx* c) {
     CHK(bind(c));
     const int N = c->N, Kl = c->Kloc, S = c->S, R = N - 1;
@@ -1623,11 +1715,15 @@ int phylo_sweep_finish(phylo_ctx* c) {
         CHK(launch_check(c, "pk_logz_total"));
         ++launches;
     }
+    if (graph && c->world > 1) {                           // sharded: the reverse pass reads the whole graph on every rank
+        CHK(graph_gather(c, &launches));
+    }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     if (graph) {                                           // the reverse pass builds its lists from these on the host
         pg_copy3 cp{};                                     // (by a kernel into the pinned buffers: pg_copy_words says why)
-        cp.src[0] = (const uint32_t*)c->d_anc; cp.dst[0] = c->hd_anc; cp.n[0] = R > 1 ? (size_t)(R - 1) * c->K * 2 : 0;
-        cp.src[1] = (const uint32_t*)c->d_child; cp.dst[1] = c->hd_child; cp.n[1] = (size_t)R * c->K * 2;
+        const bool whole = c->world > 1;
+        cp.src[0] = (const uint32_t*)(whole ? c->d_ganc : c->d_anc); cp.dst[0] = c->hd_anc; cp.n[0] = R > 1 ? (size_t)(R - 1) * c->K * 2 : 0;
+        cp.src[1] = (const uint32_t*)(whole ? c->d_gchild : c->d_child); cp.dst[1] = c->hd_child; cp.n[1] = (size_t)R * c->K * 2;
         if (twist) { cp.src[2] = (const uint32_t*)c->d_hroots_ad; cp.dst[2] = c->hd_rad; cp.n[2] = (size_t)R * c->K * N; }
         // ... and what phylo_sweep_fetch would otherwise copy one by one: log Z-hat, the timeout word of the bounded waits
         cp.src[3] = (const uint32_t*)(c->d_lse + R); cp.dst[3] = c->hd_pub; cp.n[3] = 2;
@@ -1944,10 +2040,14 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
     pg_args g{};
     g.N = N; g.S = S; g.K = K; g.R = R; g.T = T; g.jc = c->jc;
     g.twist = twist ? 1 : 0;
-    g.leaves = c->d_leaves; g.pool = c->d_pool; g.adj = c->d_adj; g.Pmat = c->d_Pmat;
-    g.bl = c->d_bl; g.br = c->d_br; g.logw = c->d_logw; g.lse = c->d_lse;
+    // sharded: the sweep made the per-rank records whole on every rank (graph_gather), node rows are read from their owners' pools,
+    // and every rank runs the whole pass over that genealogy
+    const bool whole = c->world > 1;
+    g.leaves = c->d_leaves; g.pool = c->d_pool; g.adj = c->d_adj; g.Pmat = whole ? c->d_gPmat : c->d_Pmat;
+    g.pool_ptrs = whole ? (const double* const*)c->d_pool_ptrs : nullptr; g.Kloc = c->Kloc;
+    g.bl = whole ? c->d_gbl : c->d_bl; g.br = whole ? c->d_gbr : c->d_br; g.logw = c->d_logw; g.lse = c->d_lse;
     g.pi = c->d_pi; g.Q = c->d_Q; g.lam_l = c->d_lam_l; g.lam_r = c->d_lam_r;
-    g.child = c->d_child; g.pos = c->d_pos; g.roots = c->d_hroots;
+    g.child = whole ? c->d_gchild : c->d_child; g.pos = c->d_pos; g.roots = c->d_hroots;
     g.ad_off = c->d_ad_off; g.ad_idx = c->d_ad_idx; g.par_off = c->d_par_off; g.par_idx = c->d_par_idx;
     g.heavy_first = c->d_heavy; g.chunk_beg = c->d_chunk_beg; g.chunk_cnt = c->d_chunk_cnt;
     g.slow_flag = c->d_slow_flag; g.slow_idx = c->d_slow_idx;
@@ -1970,7 +2070,10 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
     const bool early_free = rows_form && !twist && c->last_graph_marks;
     // After a lazy sweep with the plain proposal the lists are built by kernels (phylo_revlists_dev.h) and the host waits for a few
     // dozen integers; PHYLO_REV_HOST_LISTS keeps the host builders (the A/B switch, and what every other form uses).
-    const bool dev_lists = early_free && !c->env.rev_host_lists && c->Kloc == K && K <= PG_DL_MAX_K;
+    // (never on a sharded context: the device lists are what gates the one-launch chains, pg_coeff_all / pg_nodes_rows_all, which
+    //  hand values between workgroups and assume nobody else on the GPU waits likewise -- sharded ranks sharing a GPU run their
+    //  passes at once; a sharded pass takes the host lists and a launch per rank event)
+    const bool dev_lists = early_free && !whole && !c->env.rev_host_lists && c->Kloc == K && K <= PG_DL_MAX_K;
     // The list kernels need the sweep's ancestors and children and nothing else: they are queued right behind the sweep on its own
     // stream, ahead of the early kernels below (they head the longest chain: lists -> sort -> chunk sums -> adopted nodes).
     // (their sort goes to the second stream as soon as the host has seen the sweep end: queued there behind the lists' event, it
@@ -2398,6 +2501,9 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
     CHK(launch_check(c, "pg_scalars"));
     hipLaunchKernelGGL(pg_reduce, dim3(2 * R + 20), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_reduce"));
+    // sharded: the pass read node rows from the peers' pools; no owner may write its pool again (its next sweep) before every
+    // rank's pass is done -- the barrier makes phylo_sweep_backward a collective call
+    if (whole) CHK(comm_exchange(c, nullptr, 0, 0, 1));
     HIPCHK(c, hipEventRecord(c->evb1, c->stream));
     std::vector<double> out((size_t)2 * R + 20);
     HIPCHK(c, hipMemcpyAsync(out.data(), c->d_gout, out.size() * 8, hipMemcpyDeviceToHost, c->stream));

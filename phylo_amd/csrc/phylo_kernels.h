@@ -2302,6 +2302,67 @@ __global__ __launch_bounds__(1024) void pk_p2p_exchange(const pk_p2p_args a) {
     __syncthreads();
 }
 
+// ================================================================================================
+// The kept graph's per-rank records made whole on every rank (sharded PHYLO_KEEP_GRAPH): after the last rank
+// event every rank packs ITS slice of the records of its particles (children, branch lengths, matrices, ancestors) into an
+// exchange buffer, the buffers are all-gathered (peers' buffers read over the mappings after a barrier, or one collective), and
+// every rank unpacks all slices into whole-K arrays.  (The root-table history is whole already -- a sweep that keeps its graph
+// advances all K tables on every rank -- and so are the marks; node rows stay in their owners' pools.)  A field is [rows][K * w] globally, rank p's slice of a row is [p Kloc w, (p + 1) Kloc w).  Every element travels
+// as one 64-bit word; word e of rank p sits at ((e / cl) world + p) cl + e % cl of a buffer (chunks of cl words per rank, so
+// that the collective moves one chunk of every rank at a time).
+// ================================================================================================
+#define PK_GX_FIELDS 5                       // children, left / right branch lengths, matrices, ancestors
+struct pk_gx_field {
+    const void* src;                         // this rank's array; its row r starts at src + r * src_stride + src_off (elements)
+    size_t src_stride, src_off;
+    void* dst;                               // whole-K array [rows][K * w]
+    int rows, w, wide;                       // wide: 64-bit elements, else 32-bit
+};
+struct pk_gx_args {
+    int world, me, Kloc, K, n_fields;
+    size_t seg, cl;                          // words per rank, words per chunk
+    pk_gx_field f[PK_GX_FIELDS];
+    unsigned long long* xbuf;                // this rank's exchange buffer (pk_gx_pack writes its own words there)
+    const unsigned long long* const* xsrc;   // [world] the buffer rank p's words are read from (a peer mapping, or xbuf)
+};
+__device__ __forceinline__ size_t pk_gx_at(const pk_gx_args& a, int p, size_t e) {
+    return ((e / a.cl) * (size_t)a.world + (size_t)p) * a.cl + e % a.cl;
+}
+// field of word e, and the element index i inside this rank's slice of that field
+__device__ __forceinline__ int pk_gx_field_of(const pk_gx_args& a, size_t e, size_t* i) {
+    int f = 0;
+    for (; f + 1 < a.n_fields; ++f) {
+        const size_t n = (size_t)a.f[f].rows * a.Kloc * a.f[f].w;
+        if (e < n) break;
+        e -= n;
+    }
+    *i = e;
+    return f;
+}
+__global__ __launch_bounds__(256) void pk_gx_pack(const pk_gx_args a) {
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < a.seg; e += (size_t)gridDim.x * blockDim.x) {
+        size_t i = 0;
+        const pk_gx_field& F = a.f[pk_gx_field_of(a, e, &i)];
+        const size_t row = (size_t)a.Kloc * F.w, r = i / row, at = r * F.src_stride + F.src_off + (i - r * row);
+        const unsigned long long v = F.wide ? static_cast<const unsigned long long*>(F.src)[at]
+                                            : (unsigned long long)static_cast<const uint32_t*>(F.src)[at];
+        a.xbuf[pk_gx_at(a, a.me, e)] = v;
+    }
+}
+__global__ __launch_bounds__(256) void pk_gx_unpack(const pk_gx_args a) {
+    const size_t total = a.seg * (size_t)a.world;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(t / a.seg);
+        const size_t e = t - (size_t)p * a.seg;
+        size_t i = 0;
+        const pk_gx_field& F = a.f[pk_gx_field_of(a, e, &i)];
+        const unsigned long long v = a.xsrc[p][pk_gx_at(a, p, e)];
+        const size_t row = (size_t)a.Kloc * F.w, r = i / row;
+        const size_t at = r * (size_t)a.K * F.w + (size_t)p * row + (i - r * row);
+        if (F.wide) static_cast<unsigned long long*>(F.dst)[at] = v;
+        else static_cast<uint32_t*>(F.dst)[at] = (uint32_t)v;
+    }
+}
 // arithmetic probe
 __global__ void pk_math_probe(int op, const double* __restrict__ x, const double* __restrict__ y, int n,
                               double* __restrict__ out) {

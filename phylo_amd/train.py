@@ -154,11 +154,14 @@ class Trainer:
     """One device context sized for a minibatch of sites; `step` = sweep + reverse pass + update."""
 
     def __init__(self, genome_NxSxA, K, variables, optimizer, batch_sites, device=0, flags=_ffi.FLAGS_DEFAULT, nested=False, M=1,
-                 native=True):
+                 native=True, shard_with=None):
         """nested: the twisted proposal of vncsmc.py with M sub-samples per pair; its look-ahead potentials are differentiated
         like everything else (vncsmc.py:379-416 has no stop_gradient).  native: the host half of a step (model from the
         variables, chain rules, optimiser update) runs in the library (phylo_vi_gradients / phylo_vi_apply) instead of the NumPy
-        statements of this module (~60 small array operations, 65 us of a 0.9 ms step); same formulas."""
+        statements of this module (~60 small array operations, 65 us of a 0.9 ms step); same formulas.
+        shard_with: a context that has joined the ranks (phylo_comm_init): this trainer's context joins its communicator and every
+        step trains ONE K-particle system split over the ranks -- every rank must step with the same seeds, in the same order, and
+        every rank gets the same gradient bits (the plain proposal only)."""
         self.native = bool(native)
         self.genome = np.asarray(genome_NxSxA, dtype=np.float64)
         self.v, self.opt = variables, optimizer
@@ -168,6 +171,11 @@ class Trainer:
         self.M = int(M) if nested else 1
         N = self.genome.shape[0]
         self.ctx = _ffi.Context(K, N, int(batch_sites), device=device)
+        if shard_with is not None:
+            if nested:
+                self.ctx.close()
+                raise ValueError("a sharded trainer needs the plain proposal (nested=False)")
+            self.ctx.comm_share(shard_with)
         self.last = None
         self._sites = None
 

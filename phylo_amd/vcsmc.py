@@ -322,7 +322,10 @@ class VCSMC:
         # --train_parallel replicas (the default with --n_gpus > 1): data-parallel training -- on every minibatch each rank sweeps
         # its OWN K-particle system(s) (own seeds) on its own GPU and the optimiser steps on the mean of all gradients, i.e.
         # world x grad_samples independent ELBO samples per step.  redundant: every rank takes the identical step.
-        replicas = world > 1 and str(getattr(self.args, 'train_parallel', 'replicas') or 'replicas') == 'replicas'
+        # sharded: ONE K-particle system per step split over the ranks (same seeds everywhere), every rank the same gradient bits.
+        mode = str(getattr(self.args, 'train_parallel', 'replicas') or 'replicas')
+        replicas = world > 1 and mode == 'replicas'
+        sharded = world > 1 and mode == 'sharded'
         n_local = max(1, int(getattr(self.args, 'grad_samples', 1) or 1))   # particle systems per step and rank
         if world > 1:
             # all ranks must train on the SAME site minibatches; python's
@@ -335,7 +338,7 @@ class VCSMC:
         trainer = None
         if len(slices) > 1:
             trainer = train_mod.Trainer(self.genome_NxSxA, self.K, self.variables, self.optimizer, len(slices[0]),
-                                        device=self._device, nested=nested, M=self.M)
+                                        device=self._device, nested=nested, M=self.M, shard_with=ctx if sharded else None)
         initial = self.sample_phylogenies()
         print('===================\nInitial evaluation of ELBO:', round(initial, 3))
         print('Initial jump chain:')

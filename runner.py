@@ -32,10 +32,12 @@ def parse_args(argv=None):
                         help='one process per GPU (python -m torch.distributed.run --nproc-per-node N runner.py --n_gpus N ...): the '
                              'particles of the EVALUATION sweeps are sharded over the ranks (global resampling, same bits as one GPU); '
                              'training: see --train_parallel')
-    parser.add_argument('--train_parallel', choices=('replicas', 'redundant'), default='replicas',
+    parser.add_argument('--train_parallel', choices=('replicas', 'redundant', 'sharded'), default='replicas',
                         help='with --n_gpus N > 1: replicas = data-parallel training, every rank sweeps its own n_particles-particle '
                              'system per minibatch (own seed) and the optimiser steps on the mean gradient of the N ranks; '
-                             'redundant = every rank takes the identical step (equals the one-process run bit for bit)')
+                             'redundant = every rank takes the identical step (equals the one-process run bit for bit); '
+                             'sharded = ONE n_particles-particle system per minibatch split over the ranks, its reverse pass on every '
+                             'rank over the gathered genealogy (plain proposal only)')
     parser.add_argument('--grad_samples', type=int, default=1,
                         help='independent particle systems swept per optimiser step (and per rank with --train_parallel replicas); the '
                              'step is taken on their mean gradient')
@@ -44,6 +46,9 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.twisting is not None:
         args.nested = args.twisting
+    if args.train_parallel == 'sharded' and args.nested:
+        parser.error('--train_parallel sharded trains the plain proposal only: the reverse pass of a twisted sweep needs the '
+                     'whole particle system on one GPU (use --train_parallel replicas or redundant with --nested true)')
     return args
 
 
