@@ -261,6 +261,28 @@ int phylo_debug_device_lists(phylo_ctx* ctx, int32_t* lists, int64_t n_lists, in
 int phylo_debug_device_lists_of(phylo_ctx* ctx, const int64_t* ancestors, const int32_t* child, int32_t* lists, int64_t n_lists,
                                 int32_t* meta, int n_meta);
 
+/* Tree posterior of the last sweep (what get_tree_prob, csmc.py:335-349, is to the CSMC path): every final
+ * particle's tree as its N-2 non-trivial clades (taxon bitsets, W = ceil(N/64) uint64 words, taxon i = bit i % 64 of word i / 64),
+ * weighted by the resampling contract's integer weights u_k = floor(exp(logw[N-2][k] - max) 2^44) of the last rank event (same
+ * NaN / all-bad rules as the scan), U = sum u_k per group.  Clade weight C = sum of u_k over the particles whose tree holds the clade,
+ * topology (= clade set) weight T = sum of u_k over its particles; integer sums, exact.  All G groups of a batched sweep, each on
+ * its own: group g's rows equal the summary of the sweep of K/G particles with seeds[g].  Runs after the sweep on the context's
+ * stream and leaves the sweep's state alone (the next sweep's bits do not change).  Sharded context: a collective call (every rank
+ * gathers the children records) that returns the same tables on every rank, equal to the unsharded sweep's.
+ * phylo_tree_summary: counts n_clades <= K (N-2), n_topologies <= K, n_groups (may be NULL) = G; perf (may be NULL): sweep_ms = the
+ * summary's device time (hipEvents), n_launches.  Needs N >= 3.  PHYLO_ESTATE before any sweep; PHYLO_EHIP (message in
+ * phylo_last_error) when the summarised sweep timed out in a bounded wait, or when two different topologies share a 64-bit routing
+ * hash (never merged: the summary is refused).
+ * phylo_tree_summary_fetch copies the last summary's tables (any pointer may be NULL), rows group-major:
+ *   clade_bits [n_clades][W], clade_weight [n_clades], clade_group [n_clades]: per group by C descending, then bitset ascending
+ *     (as an unsigned integer, word W-1 most significant);
+ *   topo_weight, topo_count (particles), topo_rep (smallest particle inside its group), topo_group [n_topologies]: per group by
+ *     T descending, then representative ascending;
+ *   particle_topo [K]: the row of particle k's topology counted from its group's first row; u [K]; U [G]. */
+int phylo_tree_summary(phylo_ctx* ctx, int64_t* n_clades, int32_t* n_topologies, int32_t* n_groups, phylo_stats* perf);
+int phylo_tree_summary_fetch(phylo_ctx* ctx, uint64_t* clade_bits, uint64_t* clade_weight, int32_t* clade_group, uint64_t* topo_weight,
+                             int32_t* topo_count, int32_t* topo_rep, int32_t* topo_group, int32_t* particle_topo, uint64_t* u, uint64_t* U);
+
 /* Bit-level probe of the device arithmetic contract: op 0 exp(x), 1 log(x), 2 x/y, 3 fma(x,y,x). */
 int phylo_math_probe(phylo_ctx* ctx, int op, const double* x, const double* y, int n, double* out);
 

@@ -29,6 +29,7 @@ EXPORTS = [
     "phylo_forest_loglik", "phylo_tree_loglik", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward",
+    "phylo_tree_summary", "phylo_tree_summary_fetch",
     "phylo_math_probe", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache",
     "phylo_vi_gradients", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
@@ -317,6 +318,32 @@ class Context:
         out['backward_host_ms'] = st.merge_ms          # host time of the integer lists inside backward_ms (built, or waited for)
         out['backward_lists'] = 'device' if st.merge_launches else 'host'   # who built them (phylo_revlists_dev.h / phylo_revlists.h)
         out['backward_launches'] = st.n_launches
+        return out
+
+    def tree_summary(self):
+        """Tree posterior of the last sweep (phylo_tree_summary; every group of a batched sweep; a collective on a sharded context,
+        which returns the same tables on every rank).  NumPy arrays, rows group-major (`*_offsets[g]:*_offsets[g+1]` = group g):
+        clade_bits [n_clades, W] uint64 (taxon i = bit i % 64 of word i // 64), clade_weight [n_clades] uint64, clade_group;
+        topo_weight uint64, topo_count, topo_rep (smallest particle, inside its group), topo_group [n_topologies];
+        particle_topo [K] (row inside the particle's group), u [K] uint64, U [G] uint64; G, W, summary_ms (device time)."""
+        nc, nt, G = C.c_int64(), C.c_int32(), C.c_int32()
+        st = Stats()
+        self._check(self._lib.phylo_tree_summary(self._h, C.byref(nc), C.byref(nt), C.byref(G), C.byref(st)))
+        nc, nt, G = nc.value, nt.value, G.value
+        W = (self.N + 63) // 64
+        out = {'clade_bits': np.empty((nc, W), dtype=np.uint64), 'clade_weight': np.empty(nc, dtype=np.uint64),
+               'clade_group': np.empty(nc, dtype=np.int32), 'topo_weight': np.empty(nt, dtype=np.uint64),
+               'topo_count': np.empty(nt, dtype=np.int32), 'topo_rep': np.empty(nt, dtype=np.int32),
+               'topo_group': np.empty(nt, dtype=np.int32), 'particle_topo': np.empty(self.K, dtype=np.int32),
+               'u': np.empty(self.K, dtype=np.uint64), 'U': np.empty(G, dtype=np.uint64)}
+        names = ('clade_bits', 'clade_weight', 'clade_group', 'topo_weight', 'topo_count', 'topo_rep', 'topo_group', 'particle_topo',
+                 'u', 'U')
+        self._check(self._lib.phylo_tree_summary_fetch(self._h, *[_ptr(out[n]) for n in names]))
+        out['G'], out['W'] = G, W
+        out['clade_offsets'] = np.searchsorted(out['clade_group'], np.arange(G + 1))
+        out['topo_offsets'] = np.searchsorted(out['topo_group'], np.arange(G + 1))
+        out['summary_ms'] = st.sweep_ms
+        out['summary_launches'] = st.n_launches
         return out
 
     def vi_gradients(self, seed, flags, M, jc, packed_vars):

@@ -22,6 +22,10 @@
 #include "phylo_grad.h"
 #include "phylo_revlists_dev.h"
 #include "phylo_train.h"
+#include "phylo_trees.h"
+
+#include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -220,8 +224,14 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[12];                  // (8..10: the device-built lists of the reverse pass)
+    DevBuf scratch[13];                  // (8..10: the device-built lists of the reverse pass; 12: the tree summary's slab)
     phylo_comm comm;
+    // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
+    pt_bufs ts;
+    bool ts_done = false;
+    int ts_G = 1, ts_nt = 0;
+    long long ts_nc = 0;
+    hipEvent_t ev_ts0 = nullptr, ev_ts1 = nullptr;
 };
 
 namespace {
@@ -725,6 +735,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->evb0) (void)hipEventDestroy(c->evb0);
     if (c->evb1) (void)hipEventDestroy(c->evb1);
     if (c->ev_model) (void)hipEventDestroy(c->ev_model);
+    if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
+    if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
     if (c->ev_gjoin) (void)hipEventDestroy(c->ev_gjoin);
     if (c->ev_gup) (void)hipEventDestroy(c->ev_gup);
@@ -2646,6 +2658,261 @@ static int debug_device_lists_run(phylo_ctx* c, int32_t* lists, int64_t n_lists,
         meta[6 + r] = m.ev_adp0[r];
         meta[6 + (R + 1) + r] = 0;
         meta[6 + 2 * (R + 1) + r] = m.ev_slow0[r];
+    }
+    return PHYLO_OK;
+}
+
+// ---- tree posterior of the last sweep (phylo_trees.h) ---------------------------------------------------
+extern "C++" {
+#define PT_LAUNCH(kern, n, ...)                                                                                     \
+    do {                                                                                                            \
+        hipLaunchKernelGGL(kern, dim3((unsigned)(((n) + PT_NT - 1) / PT_NT)), dim3(PT_NT), 0, c->stream, __VA_ARGS__); \
+        CHK(launch_check(c, #kern));                                                                                \
+        ++launches;                                                                                                 \
+    } while (0)
+
+// one stable LSD pass over n (key, value) pairs on bits [0, bits); the sorted pairs end in kin / vin
+static int ts_sort(phylo_ctx* c, unsigned long long*& kin, unsigned long long*& kout, uint32_t*& vin, uint32_t*& vout, long long n,
+                   unsigned bits, int& launches) {
+    size_t bytes = c->ts.temp_bytes;
+    HIPCHK(c, rocprim::radix_sort_pairs(c->ts.temp, bytes, kin, kout, vin, vout, (size_t)n, 0u, bits, c->stream));
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+    ++launches;
+    return PHYLO_OK;
+}
+
+static int ts_scan32(phylo_ctx* c, const uint32_t* in, uint32_t* out, long long n, int& launches) {
+    size_t bytes = c->ts.temp_bytes;
+    HIPCHK(c, rocprim::inclusive_scan(c->ts.temp, bytes, in, out, (size_t)n, rocprim::plus<uint32_t>(), c->stream));
+    ++launches;
+    return PHYLO_OK;
+}
+
+static int ts_scan64(phylo_ctx* c, const unsigned long long* in, unsigned long long* out, long long n, int& launches) {
+    size_t bytes = c->ts.temp_bytes;
+    HIPCHK(c, rocprim::inclusive_scan(c->ts.temp, bytes, in, out, (size_t)n, rocprim::plus<unsigned long long>(), c->stream));
+    ++launches;
+    return PHYLO_OK;
+}
+
+// Sharded: every rank's children records [R][Kloc][2] -> whole-K [R][K][2] in b.child, by the host collective in chunks
+static int ts_gather_children(phylo_ctx* c) {
+    const size_t R = (size_t)c->N - 1, K = c->K, Kl = c->Kloc, P = c->world, mine_n = R * Kl * 2;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int32_t> mine(mine_n), all(P * mine_n), part, whole(R * K * 2);
+    HIPCHK(c, hipMemcpy(mine.data(), c->d_child, mine_n * 4, hipMemcpyDeviceToHost));
+    const size_t chunk = (size_t)1 << 18;                 // int32 per rank and call: 1 MiB, within the host-mediated transport's slot
+    for (size_t o = 0; o < mine_n; o += chunk) {
+        const size_t n = std::min(chunk, mine_n - o);
+        part.resize(n * P);
+        const int rc = phylo_comm_allgather_host(c->comm, mine.data() + o, n * 4, part.data(), c->stream, &c->err);
+        if (rc != PHYLO_OK) { g_last_error = c->err; return rc; }
+        for (size_t p = 0; p < P; ++p) memcpy(all.data() + p * mine_n + o, part.data() + p * n, n * 4);
+    }
+    for (size_t r = 0; r < R; ++r)
+        for (size_t p = 0; p < P; ++p)
+            memcpy(whole.data() + (r * K + p * Kl) * 2, all.data() + p * mine_n + r * Kl * 2, Kl * 2 * 4);
+    HIPCHK(c, hipMemcpy(c->ts.child, whole.data(), whole.size() * 4, hipMemcpyHostToDevice));
+    return PHYLO_OK;
+}
+
+static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topologies, int32_t* n_groups, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!n_clades || !n_topologies) return fail(c, PHYLO_EINVAL, "phylo_tree_summary: NULL count pointer");
+    if (!c->swept) return fail(c, PHYLO_ESTATE, "phylo_tree_summary: no sweep has been run");
+    if (c->run.active) return fail(c, PHYLO_ESTATE, "phylo_tree_summary: a sweep is being issued (phylo_sweep_finish first)");
+    const int N = c->N, K = c->K, R = N - 1, G = c->last_G, Kg = K / G, W = (N + 63) / 64, L = N - 2;
+    if (N < 3) return fail(c, PHYLO_EINVAL, "phylo_tree_summary needs N >= 3 taxa (got %d)", N);
+    const long long E = (long long)L * K, Emax = E > K ? E : K;
+    if (Emax >= 0xffffffffll) return fail(c, PHYLO_EINVAL, "phylo_tree_summary: (N - 2) K = %lld clade entries exceed 2^32 - 1", E);
+    hipStream_t s = c->stream;
+    pt_bufs& b = c->ts;
+    c->ts_done = false;
+    size_t temp = 0;
+    {   // rocPRIM's temporary storage: the largest of the sorts and scans below (the queries launch nothing)
+        size_t t = 0;
+        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, t, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
+                                            (uint32_t*)nullptr, (size_t)Emax, 0u, 64u, s));
+        temp = std::max(temp, t);
+        HIPCHK(c, rocprim::inclusive_scan(nullptr, t, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)Emax, rocprim::plus<uint32_t>(), s));
+        temp = std::max(temp, t);
+        HIPCHK(c, rocprim::inclusive_scan(nullptr, t, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)Emax,
+                                          rocprim::plus<unsigned long long>(), s));
+        temp = std::max(temp, t);
+    }
+    {   // every buffer carved from one grow-only slab (sizes first, then the pointers into it)
+        char* base = nullptr;
+        size_t off = 0;
+        auto take = [&](auto*& p, size_t n) {
+            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
+            off += (n * sizeof(*p) + 255) / 256 * 256;
+        };
+        const size_t Ks = K, Es = E, Em = Emax;
+        for (int pass = 0; pass < 2; ++pass) {
+            off = 0;
+            take(b.u, Ks); take(b.U, G); take(b.bits, (size_t)(R - 1) * W * Ks);
+            take(b.kA, Em); take(b.kB, Em); take(b.val, Em); take(b.scan, Em); take(b.weight, Em); take(b.srt, Es); take(b.hp, Ks);
+            take(b.o_cbits, Es * W); take(b.o_cw, Es); take(b.o_tw, Ks);
+            take(b.child, c->world > 1 ? (size_t)R * Ks * 2 : 0); take(b.slot, (size_t)R * Ks);
+            take(b.o_cg, Es); take(b.o_tn, Ks); take(b.o_trep, Ks); take(b.o_tg, Ks); take(b.o_ptopo, Ks);
+            take(b.vA, Em); take(b.vB, Em); take(b.flag, Em); take(b.sid, Em); take(b.cid, Es); take(b.seg_start, Em);
+            take(b.count, Em); take(b.group, Em); take(b.first, Em); take(b.tid, Ks); take(b.pos, Ks); take(b.err, 4);
+            take(b.temp, temp);
+            if (pass == 0) {
+                void* p = nullptr;
+                CHK(scratch_get(c, 12, off, &p));
+                base = (char*)p;
+            }
+        }
+        b.temp_bytes = temp;
+    }
+    const int32_t* child = c->d_child;
+    if (c->world > 1) {
+        CHK(ts_gather_children(c));
+        child = b.child;
+    }
+    if (!c->ev_ts0) {
+        HIPCHK(c, hipEventCreate(&c->ev_ts0));
+        HIPCHK(c, hipEventCreate(&c->ev_ts1));
+    }
+    int launches = 0;
+    HIPCHK(c, hipEventRecord(c->ev_ts0, s));
+    HIPCHK(c, hipMemsetAsync(b.err, 0, 16, s));
+    hipLaunchKernelGGL(pt_weights, dim3(G), dim3(PT_NT), 0, s, (const double*)(c->d_logw + (size_t)(R - 1) * K), Kg, b.u, b.U);
+    CHK(launch_check(c, "pt_weights"));
+    ++launches;
+    PT_LAUNCH(pt_walk, K, child, N, K, W, b.slot, b.bits, (unsigned int*)b.err);
+    unsigned long long *kin = b.kA, *kout = b.kB;
+    uint32_t *vin = b.vA, *vout = b.vB;
+    // clades: stable passes over the bitset words, least significant first, then the group
+    for (int w = 0; w < W; ++w) {
+        PT_LAUNCH(pt_clade_keys, E, (const unsigned long long*)b.bits, w ? (const uint32_t*)vin : nullptr, E, K, W, w, Kg, kin,
+                  w ? nullptr : vin);
+        CHK(ts_sort(c, kin, kout, vin, vout, E, (unsigned)std::min(64, N - 64 * w), launches));
+    }
+    if (G > 1) {
+        PT_LAUNCH(pt_clade_keys, E, (const unsigned long long*)b.bits, (const uint32_t*)vin, E, K, W, -1, Kg, kin, nullptr);
+        CHK(ts_sort(c, kin, kout, vin, vout, E, bit_length((size_t)G - 1), launches));
+    }
+    PT_LAUNCH(pt_clade_heads, E, (const unsigned long long*)b.bits, (const uint32_t*)vin, E, K, W, Kg, (const unsigned long long*)b.u,
+              b.flag, b.val);
+    CHK(ts_scan32(c, b.flag, b.sid, E, launches));
+    CHK(ts_scan64(c, b.val, b.scan, E, launches));
+    PT_LAUNCH(pt_seg_ids, E, (const uint32_t*)vin, (const uint32_t*)b.flag, (const uint32_t*)b.sid, E, b.cid, b.seg_start);
+    PT_LAUNCH(pt_seg_sums, E, (const uint32_t*)vin, (const uint32_t*)b.sid, (const uint32_t*)b.seg_start, (const unsigned long long*)b.scan,
+              E, K, Kg, G, b.weight, b.count, b.group, b.first);
+    HIPCHK(c, hipMemcpyAsync(b.err + 1, b.sid + (E - 1), 4, hipMemcpyDeviceToDevice, s));
+    // clade order: weight descending (the segments are in bitset order already), then the group
+    PT_LAUNCH(pt_order_keys, E, (const uint32_t*)nullptr, E, 0, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
+              (const uint32_t*)b.first, kin, vin);
+    CHK(ts_sort(c, kin, kout, vin, vout, E, 64u, launches));
+    if (G > 1) {
+        PT_LAUNCH(pt_order_keys, E, (const uint32_t*)vin, E, 1, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
+                  (const uint32_t*)b.first, kin, nullptr);
+        CHK(ts_sort(c, kin, kout, vin, vout, E, bit_length((size_t)G), launches));
+    }
+    PT_LAUNCH(pt_clade_out, E, (const uint32_t*)vin, (const uint32_t*)b.sid, E, K, W, (const unsigned long long*)b.bits,
+              (const unsigned long long*)b.weight, (const uint32_t*)b.group, (const uint32_t*)b.first, b.o_cbits, b.o_cw, b.o_cg);
+    // topologies: each particle's clade ids sorted inside the particle, then the particles by (group, hash of that vector)
+    PT_LAUNCH(pt_topo_pairs, E, (const uint32_t*)b.cid, E, K, b.kA, b.vA);
+    {
+        size_t bytes = b.temp_bytes;
+        HIPCHK(c, rocprim::radix_sort_pairs(b.temp, bytes, b.kA, b.srt, b.vA, b.vB, (size_t)E, 0u, 32u + bit_length((size_t)K - 1), s));
+        ++launches;
+    }
+    kin = b.kA; kout = b.kB; vin = b.vA; vout = b.vB;
+    PT_LAUNCH(pt_topo_hash, K, (const unsigned long long*)b.srt, K, L, kin, vin, b.hp);
+    CHK(ts_sort(c, kin, kout, vin, vout, K, 64u, launches));
+    if (G > 1) {
+        PT_LAUNCH(pt_clade_keys, K, (const unsigned long long*)b.bits, (const uint32_t*)vin, (long long)K, K, W, -1, Kg, kin, nullptr);
+        CHK(ts_sort(c, kin, kout, vin, vout, K, bit_length((size_t)G - 1), launches));
+    }
+    PT_LAUNCH(pt_topo_heads, K, (const unsigned long long*)b.hp, (const uint32_t*)vin, (const unsigned long long*)b.srt, K, L, Kg,
+              (const unsigned long long*)b.u, b.flag, b.val, (unsigned int*)b.err);
+    CHK(ts_scan32(c, b.flag, b.sid, K, launches));
+    CHK(ts_scan64(c, b.val, b.scan, K, launches));
+    PT_LAUNCH(pt_seg_ids, K, (const uint32_t*)vin, (const uint32_t*)b.flag, (const uint32_t*)b.sid, (long long)K, b.tid, b.seg_start);
+    PT_LAUNCH(pt_seg_sums, K, (const uint32_t*)vin, (const uint32_t*)b.sid, (const uint32_t*)b.seg_start, (const unsigned long long*)b.scan,
+              (long long)K, K, Kg, G, b.weight, b.count, b.group, b.first);
+    HIPCHK(c, hipMemcpyAsync(b.err + 2, b.sid + (K - 1), 4, hipMemcpyDeviceToDevice, s));
+    // topology order: representative ascending, then weight descending, then the group
+    PT_LAUNCH(pt_order_keys, K, (const uint32_t*)nullptr, (long long)K, 2, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
+              (const uint32_t*)b.first, kin, vin);
+    CHK(ts_sort(c, kin, kout, vin, vout, K, bit_length((size_t)K), launches));
+    PT_LAUNCH(pt_order_keys, K, (const uint32_t*)vin, (long long)K, 0, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
+              (const uint32_t*)b.first, kin, nullptr);
+    CHK(ts_sort(c, kin, kout, vin, vout, K, 64u, launches));
+    if (G > 1) {
+        PT_LAUNCH(pt_order_keys, K, (const uint32_t*)vin, (long long)K, 1, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
+                  (const uint32_t*)b.first, kin, nullptr);
+        CHK(ts_sort(c, kin, kout, vin, vout, K, bit_length((size_t)G), launches));
+    }
+    PT_LAUNCH(pt_topo_out, K, (const uint32_t*)vin, (const uint32_t*)b.sid, K, Kg, (const unsigned long long*)b.weight,
+              (const uint32_t*)b.count, (const uint32_t*)b.group, (const uint32_t*)b.first, b.o_tw, b.o_tn, b.o_trep, b.o_tg);
+    PT_LAUNCH(pt_invert, K, (const uint32_t*)vin, (long long)K, b.pos);
+    PT_LAUNCH(pt_particle_topo, K, (const uint32_t*)b.tid, (const uint32_t*)b.pos, K, b.o_ptopo);
+    HIPCHK(c, hipEventRecord(c->ev_ts1, s));
+    uint32_t hs[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(hs, b.err, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    {   // the summarised sweep's own timeout word (read, not cleared: phylo_sweep_fetch still reports it)
+        unsigned int tmo = 0;
+        if (c->last_graph && c->h_pub) tmo = c->h_pub[2];
+        else HIPCHK(c, hipMemcpy(&tmo, c->d_counter + 1, sizeof tmo, hipMemcpyDeviceToHost));
+        if (tmo) return fail(c, PHYLO_EHIP, "phylo_tree_summary: the sweep timed out in a bounded wait between workgroups; its results are invalid");
+    }
+    if (hs[0] & PT_ERR_TREE) return fail(c, PHYLO_EHIP, "phylo_tree_summary: the sweep's children records do not form one tree per particle");
+    if (hs[0] & PT_ERR_COLLISION)
+        return fail(c, PHYLO_EHIP, "phylo_tree_summary: two different topologies share a 64-bit routing hash (not merged; summary refused)");
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_ts0, c->ev_ts1));
+    c->ts_nc = hs[1];
+    c->ts_nt = (int)hs[2];
+    c->ts_G = G;
+    c->ts_done = true;
+    *n_clades = hs[1];
+    *n_topologies = (int32_t)hs[2];
+    if (n_groups) *n_groups = G;
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms;
+        st.n_launches = launches;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+#undef PT_LAUNCH
+}  // extern "C++"
+
+int phylo_tree_summary(phylo_ctx* c, int64_t* n_clades, int32_t* n_topologies, int32_t* n_groups, phylo_stats* perf) {
+    return tree_summary_impl(c, n_clades, n_topologies, n_groups, perf);
+}
+
+int phylo_tree_summary_fetch(phylo_ctx* c, uint64_t* clade_bits, uint64_t* clade_weight, int32_t* clade_group, uint64_t* topo_weight,
+                             int32_t* topo_count, int32_t* topo_rep, int32_t* topo_group, int32_t* particle_topo, uint64_t* u, uint64_t* U) {
+    CHK(bind(c));
+    if (!c->ts_done) return fail(c, PHYLO_ESTATE, "phylo_tree_summary_fetch: no phylo_tree_summary has been run");
+    const pt_bufs& b = c->ts;
+    const size_t nc = (size_t)c->ts_nc, nt = (size_t)c->ts_nt, K = c->K, W = ((size_t)c->N + 63) / 64;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (clade_bits && nc) HIPCHK(c, hipMemcpy(clade_bits, b.o_cbits, nc * W * 8, hipMemcpyDeviceToHost));
+    if (clade_weight && nc) HIPCHK(c, hipMemcpy(clade_weight, b.o_cw, nc * 8, hipMemcpyDeviceToHost));
+    if (clade_group && nc) HIPCHK(c, hipMemcpy(clade_group, b.o_cg, nc * 4, hipMemcpyDeviceToHost));
+    if (topo_weight) HIPCHK(c, hipMemcpy(topo_weight, b.o_tw, nt * 8, hipMemcpyDeviceToHost));
+    if (topo_count) HIPCHK(c, hipMemcpy(topo_count, b.o_tn, nt * 4, hipMemcpyDeviceToHost));
+    if (topo_rep) HIPCHK(c, hipMemcpy(topo_rep, b.o_trep, nt * 4, hipMemcpyDeviceToHost));
+    if (topo_group) HIPCHK(c, hipMemcpy(topo_group, b.o_tg, nt * 4, hipMemcpyDeviceToHost));
+    if (u) HIPCHK(c, hipMemcpy(u, b.u, K * 8, hipMemcpyDeviceToHost));
+    if (U) HIPCHK(c, hipMemcpy(U, b.U, (size_t)c->ts_G * 8, hipMemcpyDeviceToHost));
+    if (particle_topo) {                                   // rows counted from the first row of the particle's group
+        std::vector<int32_t> tg(nt);
+        HIPCHK(c, hipMemcpy(tg.data(), b.o_tg, nt * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(particle_topo, b.o_ptopo, K * 4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> start((size_t)c->ts_G, 0);
+        for (size_t j = nt; j-- > 0;) start[(size_t)tg[j]] = (int32_t)j;   // (rows are group-major; every group has a row)
+        const size_t Kg = K / (size_t)c->ts_G;
+        for (size_t k = 0; k < K; ++k) particle_topo[k] -= start[k / Kg];
     }
     return PHYLO_OK;
 }

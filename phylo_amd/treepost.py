@@ -1,0 +1,180 @@
+"""Host side of the tree posterior summary (VCSMC.tree_posterior; the device tables come from phylo_tree_summary, DESIGN.md
+section 10): clades in taxon names with their support, topologies with probability, count, representative and Newick, the
+majority-rule consensus tree, credible sets, and a Newick reader that turns a rooted tree back into its clade set."""
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+
+
+def bits_to_indices(row):
+    """taxon indices of one clade bitset (uint64 words, taxon i = bit i % 64 of word i // 64)"""
+    out = []
+    for w, word in enumerate(np.asarray(row, dtype=np.uint64).reshape(-1)):
+        x = int(word)
+        while x:
+            low = x & -x
+            out.append(64 * w + low.bit_length() - 1)
+            x ^= low
+    return out
+
+
+def group_table(tab, g=0):
+    """Group g's rows of Context.tree_summary()'s tables (a plain sweep has one group)."""
+    c0, c1 = int(tab['clade_offsets'][g]), int(tab['clade_offsets'][g + 1])
+    t0, t1 = int(tab['topo_offsets'][g]), int(tab['topo_offsets'][g + 1])
+    Kg = tab['u'].size // tab['G']
+    return {'clade_bits': tab['clade_bits'][c0:c1], 'clade_weight': tab['clade_weight'][c0:c1],
+            'topo_weight': tab['topo_weight'][t0:t1], 'topo_count': tab['topo_count'][t0:t1], 'topo_rep': tab['topo_rep'][t0:t1],
+            'particle_topo': tab['particle_topo'][g * Kg:(g + 1) * Kg], 'u': tab['u'][g * Kg:(g + 1) * Kg], 'U': int(tab['U'][g])}
+
+
+def _support_label(s, digits):
+    return '%.*g' % (digits, s)
+
+
+def consensus_newick(taxa, clades, threshold=0.5, digits=4):
+    """Majority-rule consensus of a clade table as Newick: the clades (taxon-index collections with their support) whose support
+    is strictly greater than `threshold`, nested by inclusion, supports as internal-node labels, the root unlabelled, children in
+    order of their smallest taxon index.  Clades above 0.5 are pairwise compatible; below that an incompatible pair raises
+    ValueError.  No clade above the threshold gives the star tree."""
+    n = len(taxa)
+    chosen = []
+    for members, support in clades:
+        m = frozenset(int(i) for i in members)
+        if 2 <= len(m) < n and support > threshold:
+            chosen.append((m, float(support)))
+    chosen.sort(key=lambda cs: (-len(cs[0]), min(cs[0])))
+    for i, (a, _) in enumerate(chosen):
+        for b, _ in chosen[:i]:
+            if not (a <= b or a.isdisjoint(b)):
+                raise ValueError("clades %s and %s are incompatible: no tree holds both (threshold %g < 0.5)"
+                                 % (sorted(a), sorted(b), threshold))
+    nodes = [frozenset(range(n))] + [m for m, _ in chosen]
+    support = [None] + [s for _, s in chosen]
+
+    def parent(m):
+        best = 0
+        for j in range(1, len(nodes)):
+            if m < nodes[j] and len(nodes[j]) < len(nodes[best]):
+                best = j
+        return best
+
+    children = [[] for _ in nodes]
+    for j in range(1, len(nodes)):
+        children[parent(nodes[j])].append((min(nodes[j]), j))
+    for i in range(n):
+        children[parent(frozenset([i]))].append((i, -1 - i))
+
+    def render(j):
+        parts = []
+        for _, x in sorted(children[j]):
+            parts.append(str(taxa[-1 - x]) if x < 0 else render(x) + _support_label(support[x], digits))
+        return '(' + ','.join(parts) + ')'
+
+    return render(0) + ';'
+
+
+def newick_clades(newick, taxa):
+    """The non-trivial clades (frozensets of taxon indices, sizes 2 .. N-1) of a rooted Newick tree over `taxa`; branch lengths
+    and internal-node labels are skipped."""
+    index = {str(t): i for i, t in enumerate(taxa)}
+    s = newick.strip()
+    if s.endswith(';'):
+        s = s[:-1]
+    pos = 0
+    found = []
+
+    def skip_annotation():
+        nonlocal pos
+        while pos < len(s) and s[pos] not in ',()':
+            pos += 1
+
+    def node():
+        nonlocal pos
+        if s[pos] == '(':
+            pos += 1
+            members = set()
+            while True:
+                members |= node()
+                if pos < len(s) and s[pos] == ',':
+                    pos += 1
+                    continue
+                if pos < len(s) and s[pos] == ')':
+                    pos += 1
+                    break
+                raise ValueError("malformed Newick at %d: %r" % (pos, s[pos:pos + 20]))
+            skip_annotation()
+            found.append(frozenset(members))
+            return members
+        start = pos
+        while pos < len(s) and s[pos] not in ',():':
+            pos += 1
+        name = s[start:pos]
+        skip_annotation()
+        if name not in index:
+            raise ValueError("unknown taxon %r in Newick" % name)
+        return {index[name]}
+
+    node()
+    if pos != len(s):
+        raise ValueError("trailing characters in Newick: %r" % s[pos:])
+    n = len(taxa)
+    return {c for c in found if 2 <= len(c) < n}
+
+
+class TreePosterior:
+    """The summary of one sweep's (or one group's) weighted final particles.
+
+    clades       [(sorted taxon-name tuple, support)], support = C / U, by C descending then bitset ascending
+    clade_sets   [(frozenset of taxon indices, support)], same order
+    topologies   [dict(probability, weight, count, representative, newick)], by T descending then representative ascending
+    particle_topology  [K] index of every particle's topology in `topologies`
+    consensus    majority-rule consensus (clades with support > threshold) as Newick with supports as labels
+    map          the most probable topology (topologies[0])"""
+
+    def __init__(self, taxa, table, newicks=None, threshold=0.5):
+        self.taxa = [str(t) for t in taxa]
+        self.threshold = float(threshold)
+        self.U = int(table['U'])
+        U = float(self.U)
+        self.clade_sets, self.clades = [], []
+        for row, w in zip(table['clade_bits'], table['clade_weight']):
+            idx = bits_to_indices(row)
+            sup = float(int(w)) / U
+            self.clade_sets.append((frozenset(idx), sup))
+            self.clades.append((tuple(sorted(self.taxa[i] for i in idx)), sup))
+        self.topologies = []
+        for w, n, r in zip(table['topo_weight'], table['topo_count'], table['topo_rep']):
+            self.topologies.append({'probability': float(int(w)) / U, 'weight': int(w), 'count': int(n), 'representative': int(r),
+                                    'newick': None if newicks is None else newicks[int(r)]})
+        self.particle_topology = np.asarray(table['particle_topo'])
+        self.consensus = consensus_newick(self.taxa, self.clade_sets, self.threshold)
+        self.map = self.topologies[0] if self.topologies else None
+
+    def credible_set(self, p):
+        """The fewest most probable topologies (table order: probability descending, ties by smallest representative) whose
+        probabilities add up to at least p; at least one topology."""
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("p must lie in [0, 1], got %r" % (p,))
+        out, acc = [], 0
+        for t in self.topologies:
+            if out and acc >= p * self.U:
+                break
+            out.append(t)
+            acc += t['weight']
+        return out
+
+    def to_json(self):
+        return {'taxa': self.taxa, 'threshold': self.threshold, 'total_weight': self.U,
+                'clades': [{'taxa': list(names), 'support': s} for names, s in self.clades],
+                'topologies': self.topologies, 'consensus': self.consensus, 'map': self.map}
+
+    def write(self, save_dir):
+        """tree_posterior.json (everything above) and consensus.tre (the consensus Newick) in save_dir"""
+        with open(os.path.join(save_dir, 'tree_posterior.json'), 'w') as f:
+            json.dump(self.to_json(), f, indent=1)
+        with open(os.path.join(save_dir, 'consensus.tre'), 'w') as f:
+            f.write(self.consensus + '\n')

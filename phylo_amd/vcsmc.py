@@ -263,6 +263,24 @@ class VCSMC:
     def newick(self, k=0):
         """Newick string of particle k's final tree, rebuilt from the integer merge records of the last
         sweep (branch lengths = the sampled left/right branches of each coalescence)."""
+        return self._newick_table()[k] + ';'
+
+    def tree_posterior(self, threshold=0.5):
+        """Summary of the last sweep's tree posterior (the K weighted final particles; the counterpart of the CSMC path's
+        get_tree_prob, csmc.py:335-349): clades with their support, topologies with probability, particle count,
+        representative and its Newick, the majority-rule consensus (clades with support > threshold, supports as labels), the
+        MAP topology and credible_set(p).  Clades, weights and topologies come from the device (phylo_tree_summary) in exact
+        integer weights; with --n_gpus > 1 a collective call that every rank makes, and every rank holds the same table."""
+        from . import treepost
+        if self._ctx is None or not hasattr(self, '_last_seed'):
+            raise RuntimeError("tree_posterior summarises the last sweep: call sample_phylogenies first")
+        table = treepost.group_table(self._ctx.tree_summary(), 0)
+        trees = self._newick_table()
+        newicks = {int(r): trees[int(r)] + ';' for r in table['topo_rep']}
+        return treepost.TreePosterior(self.taxa, table, newicks, threshold)
+
+    def _newick_table(self):
+        """the final Newick strings (without ';') of all K particles"""
         K, N = self.K, self.N
         tab = [[str(t) for t in self.taxa] for _ in range(K)]
         for r in range(N - 1):
@@ -279,7 +297,7 @@ class VCSMC:
                 node = '(%s:%.6g,%s:%.6g)' % (tab[kk][a], self.left_branches[r, kk], tab[kk][b], self.right_branches[r, kk])
                 new.append([tab[kk][i] for i in rems[kk]] + [node])
             tab = new
-        return tab[k][0] + ';'
+        return [row[0] for row in tab]
 
     def _save_results(self, save_dir, initial, history):
         """run_parameters.txt and results.p with the reference's keys (vcsmc.py:503-516, 618-642); no plots."""
@@ -384,12 +402,16 @@ class VCSMC:
                 trainer.close()
         print("Done training.")
         self.elbos = np.asarray(elbos)
+        # --tree_summary: the final evaluation sweep's tree posterior (a collective when sharded: every rank summarises)
+        self.posterior = self.tree_posterior() if getattr(self.args, 'tree_summary', False) else None
         if save_dir is not None and getattr(self, '_rank', 0) == 0:   # sharded: every rank holds the same results; rank 0 writes
             if save_dir == 'auto':                   # vcsmc.py:504-507
                 tm = str(datetime.now())
                 save_dir = './results/' + str(getattr(self.args, 'dataset', 'data')) + '/' + str(getattr(self.args, 'nested', False)) + \
                     '/' + str(getattr(self.args, 'n_particles', self.K)) + '/' + (tm[:10] + '-' + tm[11:13] + tm[14:16] + tm[17:19]) + '/'
             self.results = self._save_results(save_dir, initial, hist)
+            if self.posterior is not None:
+                self.posterior.write(save_dir)             # tree_posterior.json, consensus.tre
             self.save_dir = save_dir
             print("Finished...")
         return self.elbos

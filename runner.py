@@ -4,7 +4,8 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac` encodes them) are new.
+`--grad_samples`, `--tree_summary` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+encodes them) are new.
 """
 import argparse
 
@@ -43,6 +44,9 @@ def parse_args(argv=None):
                              'step is taken on their mean gradient')
     parser.add_argument('--ambiguity', choices=('error', 'iupac'), default='error',
                         help="characters outside the dataset's alphabet: KeyError like the reference, or IUPAC indicator rows")
+    parser.add_argument('--tree_summary', default=False, type=lambda x: (str(x).lower() == 'true'),
+                        help="after training, summarise the final evaluation sweep's tree posterior (clade supports, topology "
+                             "probabilities, majority-rule consensus) into tree_posterior.json and consensus.tre in the results directory")
     args = parser.parse_args(argv)
     if args.twisting is not None:
         args.nested = args.twisting
