@@ -283,6 +283,25 @@ int phylo_tree_summary(phylo_ctx* ctx, int64_t* n_clades, int32_t* n_topologies,
 int phylo_tree_summary_fetch(phylo_ctx* ctx, uint64_t* clade_bits, uint64_t* clade_weight, int32_t* clade_group, uint64_t* topo_weight,
                              int32_t* topo_count, int32_t* topo_rep, int32_t* topo_group, int32_t* particle_topo, uint64_t* u, uint64_t* U);
 
+/* Branch lengths of that tree posterior.  The node a particle's tree holds for a rank event has a left
+ * and a right child with their own sampled lengths (lbranch / rbranch of phylo_sweep_fetch): 2N-2 branches per tree, one above
+ * every leaf and every non-trivial clade.  Per segment of particles the pass returns four doubles, never a quotient:
+ *   S1 = sum of x, x = (double) u_k * b;  S2 = sum of x * b;  min b;  max b
+ * by the canonical segment sum (element j to column j mod 64, columns added in increasing j from +0.0, the 64 columns by the
+ * adjacent-pair tree): the host divides by the clade weight C (U_g for a leaf, T for a topology's branches); C = 0 has no mean.
+ * phylo_tree_branches runs the pass for the last phylo_tree_summary of the last sweep on the context's stream; perf (may be NULL):
+ * sweep_ms = device time, n_launches.  PHYLO_ESTATE when there is no summary of the current sweep (a newer sweep invalidates it).
+ * Collective on a sharded context (the branch lengths are all-gathered; every rank returns the unsharded tables).  The sweep's and
+ * the summary's state are left alone.
+ * phylo_tree_branches_fetch (any pointer may be NULL; row order that of phylo_tree_summary_fetch):
+ *   clade_stats [n_clades][4]: over the particles of the row's group that hold the clade, in ascending entry r K + k;
+ *   leaf_stats [G][N][4]: the branch above leaf i over all particles of group g, in ascending k;
+ *   topo_clades [n_topologies][N-2]: the topology's clade rows, ascending, counted from its group's first clade row;
+ *   topo_stats [n_topologies][2N-2][4]: over the topology's particles in ascending k, the N leaves in taxon order, then the
+ *     branches above its N-2 clades in the order of topo_clades. */
+int phylo_tree_branches(phylo_ctx* ctx, phylo_stats* perf);
+int phylo_tree_branches_fetch(phylo_ctx* ctx, double* clade_stats, double* leaf_stats, int32_t* topo_clades, double* topo_stats);
+
 /* Bit-level probe of the device arithmetic contract: op 0 exp(x), 1 log(x), 2 x/y, 3 fma(x,y,x). */
 int phylo_math_probe(phylo_ctx* ctx, int op, const double* x, const double* y, int n, double* out);
 

@@ -29,7 +29,7 @@ EXPORTS = [
     "phylo_forest_loglik", "phylo_tree_loglik", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward",
-    "phylo_tree_summary", "phylo_tree_summary_fetch",
+    "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
     "phylo_math_probe", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache",
     "phylo_vi_gradients", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
@@ -330,6 +330,7 @@ class Context:
         st = Stats()
         self._check(self._lib.phylo_tree_summary(self._h, C.byref(nc), C.byref(nt), C.byref(G), C.byref(st)))
         nc, nt, G = nc.value, nt.value, G.value
+        self._last_counts = (nc, nt, G)
         W = (self.N + 63) // 64
         out = {'clade_bits': np.empty((nc, W), dtype=np.uint64), 'clade_weight': np.empty(nc, dtype=np.uint64),
                'clade_group': np.empty(nc, dtype=np.int32), 'topo_weight': np.empty(nt, dtype=np.uint64),
@@ -344,6 +345,26 @@ class Context:
         out['topo_offsets'] = np.searchsorted(out['topo_group'], np.arange(G + 1))
         out['summary_ms'] = st.sweep_ms
         out['summary_launches'] = st.n_launches
+        return out
+
+    def tree_branches(self, summary=None):
+        """Branch-length sums of the last tree_summary() of the last sweep (phylo_tree_branches; collective when sharded).  `summary`:
+        that call's tables (for the row counts; default: fetched again).  Returns clade_stats [n_clades, 4], leaf_stats [G, N, 4],
+        topo_stats [n_topologies, 2N-2, 4] (float64: S1 = sum u b, S2 = sum u b b, min b, max b; the N leaves first, then the
+        topology's clades) and topo_clades [n_topologies, N-2] (clade rows inside the group, ascending); branches_ms, branches_launches."""
+        st = Stats()
+        self._check(self._lib.phylo_tree_branches(self._h, C.byref(st)))
+        if summary is None:
+            nc, nt, G = self._last_counts
+        else:
+            nc, nt, G = len(summary['clade_weight']), len(summary['topo_weight']), int(summary['G'])
+        N = self.N
+        out = {'clade_stats': np.empty((nc, 4)), 'leaf_stats': np.empty((G, N, 4)),
+               'topo_clades': np.empty((nt, N - 2), dtype=np.int32), 'topo_stats': np.empty((nt, 2 * N - 2, 4))}
+        self._check(self._lib.phylo_tree_branches_fetch(self._h, _ptr(out['clade_stats']), _ptr(out['leaf_stats']),
+                                                        _ptr(out['topo_clades']), _ptr(out['topo_stats'])))
+        out['branches_ms'] = st.sweep_ms
+        out['branches_launches'] = st.n_launches
         return out
 
     def vi_gradients(self, seed, flags, M, jc, packed_vars):

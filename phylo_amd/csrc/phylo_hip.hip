@@ -224,7 +224,7 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[13];                  // (8..10: the device-built lists of the reverse pass; 12: the tree summary's slab)
+    DevBuf scratch[14];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -232,6 +232,11 @@ struct phylo_ctx {
     int ts_G = 1, ts_nt = 0;
     long long ts_nc = 0;
     hipEvent_t ev_ts0 = nullptr, ev_ts1 = nullptr;
+    // the last phylo_tree_branches of that summary (scratch slot 13); a sweep begun since the summary makes both stale for it
+    pb_bufs tb;
+    bool tb_done = false;
+    unsigned long long sweep_serial = 0, ts_serial = 0;
+    hipEvent_t ev_tb0 = nullptr, ev_tb1 = nullptr;
 };
 
 namespace {
@@ -735,6 +740,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->evb0) (void)hipEventDestroy(c->evb0);
     if (c->evb1) (void)hipEventDestroy(c->evb1);
     if (c->ev_model) (void)hipEventDestroy(c->ev_model);
+    if (c->ev_tb0) (void)hipEventDestroy(c->ev_tb0);
+    if (c->ev_tb1) (void)hipEventDestroy(c->ev_tb1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -769,7 +776,7 @@ int phylo_set_site_tile(phylo_ctx* c, int T) {
     c->ntiles = (c->S + c->site_tile - 1) / c->site_tile;
     free_sweep_state(c);                                   // tile values, leaf log-likelihoods: rebuilt by the next sweep
     c->state_ready = false;
-    c->swept = false;
+    c->swept = false; ++c->sweep_serial;
     return PHYLO_OK;
 }
 
@@ -1135,7 +1142,7 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     // primate.p's node size, more than a second collective costs
     const bool lazy = lazy_ok;
     int launches = 0;
-    c->swept = false;
+    c->swept = false; ++c->sweep_serial;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     // one sweep alone on one GPU with lazy nodes: the adopted nodes are written in the bookkeeping launch (pk_rank_book_mat), found
     // by the resampling draws, which pk_sweep_prologue then leaves in d_rdraw.  Batched sweeps keep the separate launch (measured:
@@ -1299,7 +1306,7 @@ static int sweep_persistent(phylo_ctx* c, uint64_t seed, uint32_t flags, const u
         a.stamps = c->d_stamps;
     }
     const size_t lds = pp_layout(N, m, Kg).total;
-    c->swept = false;
+    c->swept = false; ++c->sweep_serial;
     CHK(persist_chain(c, false));
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (c->env.persist_nt == 512) hipLaunchKernelGGL((pp_sweep<512>), dim3(G * Wg), dim3(512), lds, c->stream, a);
@@ -2622,7 +2629,7 @@ int phylo_debug_device_lists_of(phylo_ctx* c, const int64_t* ancestors, const in
     CHK(ensure_graph_state(c));
     const int R = c->N - 1, K = c->K;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->swept = false;                                      // the sweep's genealogy is overwritten: no reverse pass on it after this
+    c->swept = false; ++c->sweep_serial;   // the sweep's genealogy is overwritten: no reverse pass on it after this
     c->last_graph = false;
     if (R > 1) HIPCHK(c, hipMemcpy(c->d_anc, ancestors, (size_t)(R - 1) * K * 8, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_child, child, (size_t)R * K * 2 * 4, hipMemcpyHostToDevice));
@@ -2729,6 +2736,7 @@ static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topolog
     hipStream_t s = c->stream;
     pt_bufs& b = c->ts;
     c->ts_done = false;
+    c->tb_done = false;
     size_t temp = 0;
     {   // rocPRIM's temporary storage: the largest of the sorts and scans below (the queries launch nothing)
         size_t t = 0;
@@ -2758,6 +2766,7 @@ static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topolog
             take(b.o_cg, Es); take(b.o_tn, Ks); take(b.o_trep, Ks); take(b.o_tg, Ks); take(b.o_ptopo, Ks);
             take(b.vA, Em); take(b.vB, Em); take(b.flag, Em); take(b.sid, Em); take(b.cid, Es); take(b.seg_start, Em);
             take(b.count, Em); take(b.group, Em); take(b.first, Em); take(b.tid, Ks); take(b.pos, Ks); take(b.err, 4);
+            take(b.vC, Em); take(b.vD, Em);
             take(b.temp, temp);
             if (pass == 0) {
                 void* p = nullptr;
@@ -2812,16 +2821,17 @@ static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topolog
                   (const uint32_t*)b.first, kin, nullptr);
         CHK(ts_sort(c, kin, kout, vin, vout, E, bit_length((size_t)G), launches));
     }
+    b.cord = vin;                                          // (stays: the topology stage sorts in vC / vD)
     PT_LAUNCH(pt_clade_out, E, (const uint32_t*)vin, (const uint32_t*)b.sid, E, K, W, (const unsigned long long*)b.bits,
               (const unsigned long long*)b.weight, (const uint32_t*)b.group, (const uint32_t*)b.first, b.o_cbits, b.o_cw, b.o_cg);
     // topologies: each particle's clade ids sorted inside the particle, then the particles by (group, hash of that vector)
-    PT_LAUNCH(pt_topo_pairs, E, (const uint32_t*)b.cid, E, K, b.kA, b.vA);
+    PT_LAUNCH(pt_topo_pairs, E, (const uint32_t*)b.cid, E, K, b.kA, b.vC);
     {
         size_t bytes = b.temp_bytes;
-        HIPCHK(c, rocprim::radix_sort_pairs(b.temp, bytes, b.kA, b.srt, b.vA, b.vB, (size_t)E, 0u, 32u + bit_length((size_t)K - 1), s));
+        HIPCHK(c, rocprim::radix_sort_pairs(b.temp, bytes, b.kA, b.srt, b.vC, b.vD, (size_t)E, 0u, 32u + bit_length((size_t)K - 1), s));
         ++launches;
     }
-    kin = b.kA; kout = b.kB; vin = b.vA; vout = b.vB;
+    kin = b.kA; kout = b.kB; vin = b.vC; vout = b.vD;
     PT_LAUNCH(pt_topo_hash, K, (const unsigned long long*)b.srt, K, L, kin, vin, b.hp);
     CHK(ts_sort(c, kin, kout, vin, vout, K, 64u, launches));
     if (G > 1) {
@@ -2870,6 +2880,7 @@ static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topolog
     c->ts_nc = hs[1];
     c->ts_nt = (int)hs[2];
     c->ts_G = G;
+    c->ts_serial = c->sweep_serial;
     c->ts_done = true;
     *n_clades = hs[1];
     *n_topologies = (int32_t)hs[2];
@@ -2882,6 +2893,165 @@ static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topolog
     }
     return PHYLO_OK;
 }
+
+// Sharded: every rank's rows [R][Kloc] of one branch-length array -> whole-K [R][K] in dst, by the host collective in chunks
+static int tb_gather_rows(phylo_ctx* c, const double* src, double* dst) {
+    const size_t R = (size_t)c->N - 1, K = c->K, Kl = c->Kloc, P = c->world, mine_n = R * Kl;
+    std::vector<double> mine(mine_n), all(P * mine_n), part, whole(R * K);
+    HIPCHK(c, hipMemcpy(mine.data(), src, mine_n * 8, hipMemcpyDeviceToHost));
+    const size_t chunk = (size_t)1 << 17;                 // doubles per rank and call: 1 MiB, as ts_gather_children
+    for (size_t o = 0; o < mine_n; o += chunk) {
+        const size_t n = std::min(chunk, mine_n - o);
+        part.resize(n * P);
+        const int rc = phylo_comm_allgather_host(c->comm, mine.data() + o, n * 8, part.data(), c->stream, &c->err);
+        if (rc != PHYLO_OK) { g_last_error = c->err; return rc; }
+        for (size_t p = 0; p < P; ++p) memcpy(all.data() + p * mine_n + o, part.data() + p * n, n * 8);
+    }
+    for (size_t r = 0; r < R; ++r)
+        for (size_t p = 0; p < P; ++p) memcpy(whole.data() + r * K + p * Kl, all.data() + p * mine_n + r * Kl, Kl * 8);
+    HIPCHK(c, hipMemcpy(dst, whole.data(), whole.size() * 8, hipMemcpyHostToDevice));
+    return PHYLO_OK;
+}
+
+template <typename KEY>
+static int tb_sort(phylo_ctx* c, KEY* kin, KEY* kout, uint32_t* vin, uint32_t* vout, long long n, unsigned bits, int& launches) {
+    size_t bytes = c->tb.temp_bytes;
+    HIPCHK(c, rocprim::radix_sort_pairs(c->tb.temp, bytes, kin, kout, vin, vout, (size_t)n, 0u, bits, c->stream));
+    ++launches;
+    return PHYLO_OK;
+}
+
+#define PB_SEGS(family, KEY, args, tkey)                                                                                           \
+    do {                                                                                                                           \
+        hipLaunchKernelGGL((pb_seg_sums<family, KEY>), dim3((unsigned)(((args).n_seg + PT_NT / 64 - 1) / (PT_NT / 64))), dim3(PT_NT), 0, \
+                           c->stream, args, tkey);                                                                                 \
+        CHK(launch_check(c, "pb_seg_sums"));                                                                                       \
+        ++launches;                                                                                                                \
+    } while (0)
+
+static int tree_branches_impl(phylo_ctx* c, phylo_stats* perf) {
+    CHK(bind(c));
+    if (c->run.active) return fail(c, PHYLO_ESTATE, "phylo_tree_branches: a sweep is being issued (phylo_sweep_finish first)");
+    if (!c->swept || !c->ts_done || c->ts_serial != c->sweep_serial)
+        return fail(c, PHYLO_ESTATE, "phylo_tree_branches: no phylo_tree_summary of the last sweep (a new sweep needs a new summary)");
+    const int N = c->N, K = c->K, R = N - 1, G = c->ts_G, Kg = K / G, L = N - 2;
+    const long long E = (long long)L * K, nc = c->ts_nc, nt = c->ts_nt, nb = 2LL * N - 2;
+    if (nc < 1 || nt < 1 || nc > E || nt > K) return fail(c, PHYLO_ESTATE, "phylo_tree_branches: the summary holds no rows");
+    const unsigned cbits = std::max(1u, (unsigned)bit_length((size_t)nc - 1)), tbits = std::max(1u, (unsigned)bit_length((size_t)nt - 1));
+    const bool wide = cbits + tbits > 32;                  // (topology, clade) keys: 32 bits hold them on all but huge tables
+    hipStream_t s = c->stream;
+    const pt_bufs& b = c->ts;
+    pb_bufs& t = c->tb;
+    c->tb_done = false;
+    const bool gather = c->world > 1 && !(c->last_graph && c->d_gbl && c->d_gbr);
+    size_t temp = 0;
+    {
+        size_t q = 0;
+        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, q, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                            (size_t)E, 0u, 32u, s));
+        temp = std::max(temp, q);
+        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, q, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
+                                            (uint32_t*)nullptr, (size_t)E, 0u, 64u, s));
+        if (wide) temp = std::max(temp, q);
+        HIPCHK(c, rocprim::exclusive_scan(nullptr, q, (const int32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)nt, rocprim::plus<uint32_t>(), s));
+        temp = std::max(temp, q);
+    }
+    {
+        char* base = nullptr;
+        size_t off = 0;
+        auto take = [&](auto*& p, size_t n) {
+            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
+            off += (n * sizeof(*p) + 255) / 256 * 256;
+        };
+        const size_t Ks = K, Es = E;
+        for (int pass = 0; pass < 2; ++pass) {
+            off = 0;
+            take(t.ebr, (size_t)(R - 1) * Ks); take(t.lbr, (size_t)N * Ks);
+            take(t.gbl, gather ? (size_t)R * Ks : 0); take(t.gbr, gather ? (size_t)R * Ks : 0);
+            take(t.o_cs, (size_t)nc * 4); take(t.o_ls, (size_t)G * N * 4); take(t.o_ts, (size_t)nt * nb * 4);
+            take(t.wA, wide ? Es : 0); take(t.wB, wide ? Es : 0);
+            take(t.cpos, Es); take(t.kA, Es); take(t.kB, Es); take(t.vA, Es); take(t.vB, Es);
+            take(t.cstart, (size_t)nc + 1); take(t.toff, (size_t)nt); take(t.o_tc, (size_t)nt * L);
+            take(t.temp, temp);
+            if (pass == 0) {
+                void* p = nullptr;
+                CHK(scratch_get(c, 13, off, &p));
+                base = (char*)p;
+            }
+        }
+        t.temp_bytes = temp;
+    }
+    const int32_t* child = c->world > 1 ? b.child : c->d_child;
+    const double *bl = c->d_bl, *br = c->d_br;
+    if (c->world > 1) {
+        if (gather) {                                      // a collective, like the summary's gather of the children records
+            HIPCHK(c, hipStreamSynchronize(s));
+            CHK(tb_gather_rows(c, c->d_bl, t.gbl));
+            CHK(tb_gather_rows(c, c->d_br, t.gbr));
+            bl = t.gbl; br = t.gbr;
+        } else {                                           // the sweep kept its graph: graph_gather made them whole already
+            bl = c->d_gbl; br = c->d_gbr;
+        }
+    }
+    if (!c->ev_tb0) {
+        HIPCHK(c, hipEventCreate(&c->ev_tb0));
+        HIPCHK(c, hipEventCreate(&c->ev_tb1));
+    }
+    int launches = 0;
+    unsigned int* err = (unsigned int*)b.err + 3;          // the summary's error words: [3] is this pass's
+    HIPCHK(c, hipEventRecord(c->ev_tb0, s));
+    HIPCHK(c, hipMemsetAsync(err, 0, 4, s));
+    PT_LAUNCH(pb_walk, K, child, (const int32_t*)b.slot, bl, br, N, K, t.ebr, t.lbr, err);
+    // clade rows: the entries sorted by their clade's output row (one narrow stable pass over ascending entries)
+    PT_LAUNCH(pt_invert, E, b.cord, E, t.cpos);
+    PT_LAUNCH(pb_entry_keys<uint32_t>, E, (const uint32_t*)b.cid, (const uint32_t*)t.cpos, (const int32_t*)nullptr, E, K, L, 0, t.kA, t.vA);
+    CHK(tb_sort(c, t.kA, t.kB, t.vA, t.vB, E, cbits, launches));
+    t.cperm = t.vB;
+    PT_LAUNCH(pb_clade_starts, E, (const uint32_t*)t.kB, E, (uint32_t)nc, t.cstart);
+    pb_seg_args a{};
+    a.u = b.u; a.ebr = t.ebr; a.lbr = t.lbr; a.cperm = t.cperm; a.cstart = t.cstart; a.toff = t.toff; a.tn = b.o_tn; a.o_tc = t.o_tc;
+    a.N = N; a.K = K; a.Kg = Kg; a.cmask_bits = (int)cbits;
+    a.out = t.o_cs; a.n_seg = nc;
+    PB_SEGS(PB_CLADES, uint32_t, a, (const uint32_t*)nullptr);
+    a.out = t.o_ls; a.n_seg = (long long)G * N;
+    PB_SEGS(PB_LEAVES, uint32_t, a, (const uint32_t*)nullptr);
+    // topology rows: the entries, particle-major, sorted by (topology row, clade row); row t's runs start at (N - 2) toff[t]
+    {
+        size_t bytes = t.temp_bytes;
+        HIPCHK(c, rocprim::exclusive_scan(t.temp, bytes, (const int32_t*)b.o_tn, t.toff, 0u, (size_t)nt, rocprim::plus<uint32_t>(), s));
+        ++launches;
+    }
+    a.out = t.o_ts; a.n_seg = nt * nb;
+    if (wide) {
+        PT_LAUNCH(pb_entry_keys<unsigned long long>, E, (const uint32_t*)b.cid, (const uint32_t*)t.cpos, (const int32_t*)b.o_ptopo, E, K, L,
+                  (int)cbits, t.wA, t.vA);
+        CHK(tb_sort(c, t.wA, t.wB, t.vA, t.kA, E, cbits + tbits, launches));
+        t.tperm = a.tperm = t.kA;
+        PB_SEGS(PB_TOPOS, unsigned long long, a, (const unsigned long long*)t.wB);
+    } else {
+        PT_LAUNCH(pb_entry_keys<uint32_t>, E, (const uint32_t*)b.cid, (const uint32_t*)t.cpos, (const int32_t*)b.o_ptopo, E, K, L, (int)cbits,
+                  t.kA, t.vA);
+        CHK(tb_sort(c, t.kA, t.kB, t.vA, t.cpos, E, cbits + tbits, launches));   // (cpos is free from here: the sorted entries)
+        t.tperm = a.tperm = t.cpos;
+        PB_SEGS(PB_TOPOS, uint32_t, a, (const uint32_t*)t.kB);
+    }
+    HIPCHK(c, hipEventRecord(c->ev_tb1, s));
+    unsigned int herr = 0;
+    HIPCHK(c, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (herr & PT_ERR_TREE) return fail(c, PHYLO_EHIP, "phylo_tree_branches: the sweep's children records do not form one tree per particle");
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tb0, c->ev_tb1));
+    c->tb_done = true;
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms;
+        st.n_launches = launches;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+#undef PB_SEGS
 #undef PT_LAUNCH
 }  // extern "C++"
 
@@ -2913,6 +3083,30 @@ int phylo_tree_summary_fetch(phylo_ctx* c, uint64_t* clade_bits, uint64_t* clade
         for (size_t j = nt; j-- > 0;) start[(size_t)tg[j]] = (int32_t)j;   // (rows are group-major; every group has a row)
         const size_t Kg = K / (size_t)c->ts_G;
         for (size_t k = 0; k < K; ++k) particle_topo[k] -= start[k / Kg];
+    }
+    return PHYLO_OK;
+}
+
+int phylo_tree_branches(phylo_ctx* c, phylo_stats* perf) { return tree_branches_impl(c, perf); }
+
+int phylo_tree_branches_fetch(phylo_ctx* c, double* clade_stats, double* leaf_stats, int32_t* topo_clades, double* topo_stats) {
+    CHK(bind(c));
+    if (!c->ts_done || !c->tb_done) return fail(c, PHYLO_ESTATE, "phylo_tree_branches_fetch: no phylo_tree_branches of the last summary");
+    const pb_bufs& t = c->tb;
+    const size_t nc = (size_t)c->ts_nc, nt = (size_t)c->ts_nt, N = c->N, L = N - 2, G = c->ts_G;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (clade_stats) HIPCHK(c, hipMemcpy(clade_stats, t.o_cs, nc * 32, hipMemcpyDeviceToHost));
+    if (leaf_stats) HIPCHK(c, hipMemcpy(leaf_stats, t.o_ls, G * N * 32, hipMemcpyDeviceToHost));
+    if (topo_stats) HIPCHK(c, hipMemcpy(topo_stats, t.o_ts, nt * (2 * N - 2) * 32, hipMemcpyDeviceToHost));
+    if (topo_clades) {                                     // rows counted from the first clade row of the topology's group
+        std::vector<int32_t> cg(nc), tg(nt);
+        HIPCHK(c, hipMemcpy(cg.data(), c->ts.o_cg, nc * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(tg.data(), c->ts.o_tg, nt * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(topo_clades, t.o_tc, nt * L * 4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> start(G, 0);
+        for (size_t j = nc; j-- > 0;) start[(size_t)cg[j]] = (int32_t)j;
+        for (size_t j = 0; j < nt; ++j)
+            for (size_t i = 0; i < L; ++i) topo_clades[j * L + i] -= start[(size_t)tg[j]];
     }
     return PHYLO_OK;
 }
@@ -2955,7 +3149,7 @@ int phylo_comm_init(phylo_ctx* c, int rank, int world, const char id[PHYLO_COMM_
     c->world = world;
     c->Kloc = c->K / world;
     c->k0 = rank * c->Kloc;
-    c->swept = false;
+    c->swept = false; ++c->sweep_serial;
     c->state_ready = false;
     CHK(alloc_sweep_state(c));                             // collective: every rank maps every peer's pool here
     CHK(refresh_leaf_ll(c));
@@ -2982,7 +3176,7 @@ int phylo_comm_share(phylo_ctx* c, phylo_ctx* owner) {
     c->world = owner->world;
     c->Kloc = c->K / c->world;
     c->k0 = c->rank * c->Kloc;
-    c->swept = false;
+    c->swept = false; ++c->sweep_serial;
     c->state_ready = false;
     CHK(alloc_sweep_state(c));                             // collective: every rank maps every peer's pool here
     CHK(refresh_leaf_ll(c));

@@ -25,6 +25,8 @@ struct pt_bufs {
     int32_t *child = nullptr, *slot = nullptr, *o_cg = nullptr, *o_tn = nullptr, *o_trep = nullptr, *o_tg = nullptr, *o_ptopo = nullptr;
     uint32_t *vA = nullptr, *vB = nullptr, *flag = nullptr, *sid = nullptr, *cid = nullptr, *seg_start = nullptr, *count = nullptr;
     uint32_t *group = nullptr, *first = nullptr, *tid = nullptr, *pos = nullptr;
+    uint32_t *vC = nullptr, *vD = nullptr;   // the topology stage's values: the clade order (cord, in vA or vB) outlives the summary
+    const uint32_t* cord = nullptr;          // clade segment of every output row (phylo_tree_branches inverts it)
     uint32_t* err = nullptr;                 // [0] PT_ERR_* bits, [1] clade count, [2] topology count
     unsigned char* temp = nullptr;           // rocPRIM's temporary storage
     size_t temp_bytes = 0;
@@ -285,4 +287,163 @@ __global__ void pt_particle_topo(const uint32_t* __restrict__ tid, const uint32_
     const int k = blockIdx.x * PT_NT + threadIdx.x;
     if (k >= K) return;
     out[k] = (int32_t)pos[tid[k]];
+}
+
+// ---- branch lengths of the tree posterior (phylo_tree_branches) ------------------------------------------
+// For the last summary: the length of the branch above every clade entry and every leaf of every final particle's tree (pb_walk),
+// then S1 = sum of u_k b, S2 = sum of (u_k b) b, min and max of b over three families of segments by ONE kernel (pb_seg_sums):
+// the clade rows, the leaves of every group, and the 2N - 2 branches of every topology row.  Canonical segment sum: element j of a
+// segment goes to column j mod 64, a column adds its elements in increasing j from +0.0, the 64 columns are added by the
+// adjacent-pair tree (pk_wave_tree_sum, phylo_kernels.h, included before this file).  One wavefront owns a segment, lane = column:
+// no atomics, and the result does not depend on how segments are spread over workgroups.
+struct pb_bufs {
+    double *ebr = nullptr, *lbr = nullptr;   // [R-1][K] branch above entry (r, k); [N][K] branch above leaf i of particle k
+    double *gbl = nullptr, *gbr = nullptr;   // sharded without a kept graph: the whole-K branch lengths [R][K]
+    uint32_t *cpos = nullptr, *kA = nullptr, *kB = nullptr, *vA = nullptr, *vB = nullptr, *cstart = nullptr, *toff = nullptr;
+    unsigned long long *wA = nullptr, *wB = nullptr;      // 64-bit (topology, clade) keys, only when 32 bits do not hold them
+    const uint32_t *cperm = nullptr, *tperm = nullptr;    // entries sorted by clade row / by (topology row, clade row)
+    double *o_cs = nullptr, *o_ls = nullptr, *o_ts = nullptr;   // [n_clades][4], [G][N][4], [n_topologies][2N-2][4]
+    int32_t* o_tc = nullptr;                 // [n_topologies][N-2] clade rows (over all groups; the fetch subtracts the group's first)
+    unsigned char* temp = nullptr;
+    size_t temp_bytes = 0;
+};
+
+// One thread per final particle k: the branch above each child of the node of every rank event of its tree.  slot was validated
+// by pt_walk; a record that does not fit is still refused here (PT_ERR_TREE in the word given) before anything is indexed by it.
+__global__ void __launch_bounds__(PT_NT) pb_walk(const int32_t* __restrict__ child, const int32_t* __restrict__ slot,
+                                                 const double* __restrict__ bl, const double* __restrict__ br, int N, int K,
+                                                 double* __restrict__ ebr, double* __restrict__ lbr, unsigned int* __restrict__ err) {
+    const int k = blockIdx.x * PT_NT + threadIdx.x;
+    if (k >= K) return;
+    const int R = N - 1;
+    const long long n_nodes = (long long)N + (long long)R * K;
+    for (int r = R - 1; r >= 0; --r) {
+        const int nd = slot[(size_t)r * K + k];
+        const int kk = nd - N - r * K;
+        if (nd < 0 || kk < 0 || kk >= K) { atomicOr(err, (unsigned int)PT_ERR_TREE); return; }
+        const size_t rec = (size_t)r * K + kk;
+        for (int s = 0; s < 2; ++s) {
+            const int c = child[rec * 2 + s];
+            const double b = s ? br[rec] : bl[rec];
+            if (c < 0 || c >= n_nodes) { atomicOr(err, (unsigned int)PT_ERR_TREE); return; }
+            if (c < N) lbr[(size_t)c * K + k] = b;
+            else {
+                const int rc = (c - N) / K;
+                if (rc >= r) { atomicOr(err, (unsigned int)PT_ERR_TREE); return; }
+                ebr[(size_t)rc * K + k] = b;
+            }
+        }
+    }
+}
+
+// keys of the two entry sorts, values = the entry.  topo == nullptr: element i is entry i, key = its clade's output row (stable
+// over ascending entries: the contract's order inside a clade segment).  Otherwise element i = k L + r is entry r K + k, key =
+// (topology row of k) << cbits | clade row: stable over ascending particles, and topology t's rows come out as N - 2 runs of
+// n(t) entries each.  KEY is uint32_t whenever the key fits.
+template <typename KEY>
+__global__ void pb_entry_keys(const uint32_t* __restrict__ cid, const uint32_t* __restrict__ cpos, const int32_t* __restrict__ topo,
+                              long long E, int K, int L, int cbits, KEY* __restrict__ key, uint32_t* __restrict__ val) {
+    const long long i = (long long)blockIdx.x * PT_NT + threadIdx.x;
+    if (i >= E) return;
+    uint32_t e = (uint32_t)i;
+    KEY x = 0;
+    if (topo) {
+        const uint32_t k = (uint32_t)(i / L), r = (uint32_t)(i % L);
+        e = r * (uint32_t)K + k;
+        x = (KEY)((KEY)(uint32_t)topo[k] << cbits);
+    }
+    key[i] = x | (KEY)cpos[cid[e]];
+    val[i] = e;
+}
+
+// first element of every clade row in the entries sorted by row (every row holds at least one entry); cstart[n_rows] = E
+__global__ void pb_clade_starts(const uint32_t* __restrict__ key, long long E, uint32_t n_rows, uint32_t* __restrict__ cstart) {
+    const long long i = (long long)blockIdx.x * PT_NT + threadIdx.x;
+    if (i >= E) return;
+    const uint32_t row = key[i];
+    if (row < n_rows && (i == 0 || key[i - 1] != row)) cstart[row] = (uint32_t)i;
+    if (i == 0) cstart[n_rows] = (uint32_t)E;
+}
+
+struct pb_seg_args {
+    const unsigned long long* u;      // [K]
+    const double *ebr, *lbr;
+    const uint32_t *cperm, *cstart;   // clade rows
+    const uint32_t *tperm, *toff;     // topology rows: toff[t] = particles in the rows before t
+    const int32_t* tn;                // [n_topologies] particle counts
+    double* out;                      // [n_seg][4]
+    int32_t* o_tc;
+    long long n_seg;
+    int N, K, Kg, cmask_bits;
+};
+
+enum { PB_CLADES = 0, PB_LEAVES = 1, PB_TOPOS = 2 };
+
+template <typename KEY>
+__device__ __forceinline__ uint32_t pb_low(const KEY* key, size_t i, int bits) {
+    return (uint32_t)(key[i] & (((KEY)1 << bits) - 1));
+}
+
+// One wavefront per segment, PT_NT / 64 segments per workgroup (the segments of a family are numbered densely, so short ones
+// pack four to a workgroup and a long one keeps one wave busy while the others retire).  S1, S2, min, max in one pass.
+template <int FAMILY, typename KEY>
+__global__ void __launch_bounds__(PT_NT) pb_seg_sums(pb_seg_args a, const KEY* __restrict__ tkey) {
+    const long long seg = (long long)blockIdx.x * (PT_NT / 64) + (threadIdx.x >> 6);   // wave-uniform
+    if (seg >= a.n_seg) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const int N = a.N, K = a.K, L = N - 2;
+    const uint32_t* list = nullptr;        // the segment's elements: entries (e % K = particle), or nullptr: particles base + j
+    const double* leaf = nullptr;          // the leaf's row of lbr, or nullptr: the branch above the entry
+    uint32_t len, base = 0;
+    if (FAMILY == PB_CLADES) {
+        const uint32_t b = a.cstart[seg];
+        len = a.cstart[seg + 1] - b;
+        list = a.cperm + b;
+    } else if (FAMILY == PB_LEAVES) {
+        const int g = (int)(seg / N), i = (int)(seg % N);
+        len = (uint32_t)a.Kg;
+        base = (uint32_t)g * (uint32_t)a.Kg;
+        leaf = a.lbr + (size_t)i * K;
+    } else {
+        const int nb = 2 * N - 2, t = (int)(seg / nb), q = (int)(seg % nb);
+        len = (uint32_t)a.tn[t];
+        const size_t first = (size_t)L * a.toff[t];            // topology t's N - 2 runs of len entries start here
+        if (q < N) {
+            list = a.tperm + first;                            // (the first run names t's particles in ascending order)
+            leaf = a.lbr + (size_t)q * K;
+        } else {
+            const size_t run = first + (size_t)(q - N) * len;
+            list = a.tperm + run;
+            if (lane == 0) a.o_tc[(size_t)t * L + (q - N)] = (int32_t)pb_low(tkey, run, a.cmask_bits);
+        }
+    }
+    double s1 = 0.0, s2 = 0.0, mn = pm_inf(), mx = -pm_inf();
+#pragma unroll 4
+    for (uint32_t j = lane; j < len; j += 64) {
+        uint32_t k = base + j;
+        double b;
+        if (list) {
+            const uint32_t e = list[j];
+            k = e % (uint32_t)K;
+            b = leaf ? leaf[k] : a.ebr[e];
+        } else b = leaf[k];
+        const double x = (double)a.u[k] * b;
+        const double y = x * b;
+        s1 = s1 + x;
+        s2 = s2 + y;
+        mn = b < mn ? b : mn;
+        mx = b > mx ? b : mx;
+    }
+    s1 = pk_wave_tree_sum(s1);
+    s2 = pk_wave_tree_sum(s2);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double on = __shfl_xor(mn, off, 64), ox = __shfl_xor(mx, off, 64);
+        mn = on < mn ? on : mn;
+        mx = ox > mx ? ox : mx;
+    }
+    if (lane == 0) {
+        double* o = a.out + (size_t)seg * 4;
+        o[0] = s1; o[1] = s2; o[2] = mn; o[3] = mx;
+    }
 }

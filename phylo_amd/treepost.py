@@ -26,7 +26,11 @@ def group_table(tab, g=0):
     c0, c1 = int(tab['clade_offsets'][g]), int(tab['clade_offsets'][g + 1])
     t0, t1 = int(tab['topo_offsets'][g]), int(tab['topo_offsets'][g + 1])
     Kg = tab['u'].size // tab['G']
-    return {'clade_bits': tab['clade_bits'][c0:c1], 'clade_weight': tab['clade_weight'][c0:c1],
+    extra = {}
+    if 'clade_stats' in tab:                               # Context.tree_branches()'s tables, merged into tab by the caller
+        extra = {'clade_stats': tab['clade_stats'][c0:c1], 'leaf_stats': tab['leaf_stats'][g],
+                 'topo_clades': tab['topo_clades'][t0:t1], 'topo_stats': tab['topo_stats'][t0:t1]}
+    return {**extra, 'clade_bits': tab['clade_bits'][c0:c1], 'clade_weight': tab['clade_weight'][c0:c1],
             'topo_weight': tab['topo_weight'][t0:t1], 'topo_count': tab['topo_count'][t0:t1], 'topo_rep': tab['topo_rep'][t0:t1],
             'particle_topo': tab['particle_topo'][g * Kg:(g + 1) * Kg], 'u': tab['u'][g * Kg:(g + 1) * Kg], 'U': int(tab['U'][g])}
 
@@ -125,6 +129,105 @@ def newick_clades(newick, taxa):
     return {c for c in found if 2 <= len(c) < n}
 
 
+def newick_branches(newick, taxa):
+    """{clade (frozenset of taxon indices) or leaf (taxon index) -> length of the branch above it} of a rooted Newick tree over
+    `taxa`; nodes without a ':length' (the root, or a branch with no estimate) are absent.  Internal-node labels are skipped."""
+    index = {str(t): i for i, t in enumerate(taxa)}
+    s = newick.strip()
+    if s.endswith(';'):
+        s = s[:-1]
+    pos = 0
+    out = {}
+
+    def annotation(key):
+        nonlocal pos
+        start = pos
+        while pos < len(s) and s[pos] not in ',()':
+            pos += 1
+        text = s[start:pos]
+        if ':' in text:
+            out[key] = float(text.split(':', 1)[1])
+
+    def node():
+        nonlocal pos
+        if s[pos] == '(':
+            pos += 1
+            members = set()
+            while True:
+                members |= node()
+                if pos < len(s) and s[pos] == ',':
+                    pos += 1
+                    continue
+                if pos < len(s) and s[pos] == ')':
+                    pos += 1
+                    break
+                raise ValueError("malformed Newick at %d: %r" % (pos, s[pos:pos + 20]))
+            annotation(frozenset(members))
+            return members
+        start = pos
+        while pos < len(s) and s[pos] not in ',():':
+            pos += 1
+        name = s[start:pos]
+        if name not in index:
+            raise ValueError("unknown taxon %r in Newick" % name)
+        annotation(index[name])
+        return {index[name]}
+
+    node()
+    if pos != len(s):
+        raise ValueError("trailing characters in Newick: %r" % s[pos:])
+    return out
+
+
+def branch_summary(stats, weight):
+    """mean, sd, min, max of one branch from its (S1, S2, min, max) row and the integer weight C it was summed over: mean = S1 / C,
+    variance = max(S2 / C - mean^2, 0); C = 0 (held only by particles of integer weight 0) has no estimate: mean and sd None."""
+    s1, s2, lo, hi = (float(x) for x in stats)
+    if int(weight) == 0:
+        return {'mean': None, 'sd': None, 'min': lo, 'max': hi}
+    c = float(int(weight))
+    mean = s1 / c
+    return {'mean': mean, 'sd': max(s2 / c - mean * mean, 0.0) ** 0.5, 'min': lo, 'max': hi}
+
+
+def _length(mean, digits):
+    return '' if mean is None else ':%.*g' % (digits, mean)
+
+
+def tree_newick(taxa, clades, leaf_means, labels=None, digits=6, label_digits=4):
+    """Newick of the tree whose non-trivial clades are `clades` = [(frozenset of taxon indices, mean length or None)] (pairwise
+    compatible), with ':mean' on every edge that has an estimate (leaf_means[i] above taxon i); labels: {clade: support} printed
+    as internal-node labels.  Children in order of their smallest taxon index, the root bare."""
+    n = len(taxa)
+    nodes = [frozenset(range(n))] + [m for m, _ in sorted(clades, key=lambda cm: (-len(cm[0]), min(cm[0])))]
+    mean = dict(clades)
+
+    def parent(m):
+        best = 0
+        for j in range(1, len(nodes)):
+            if m < nodes[j] and len(nodes[j]) < len(nodes[best]):
+                best = j
+        return best
+
+    children = [[] for _ in nodes]
+    for j in range(1, len(nodes)):
+        children[parent(nodes[j])].append((min(nodes[j]), j))
+    for i in range(n):
+        children[parent(frozenset([i]))].append((i, -1 - i))
+
+    def render(j):
+        parts = []
+        for _, x in sorted(children[j]):
+            if x < 0:
+                parts.append(str(taxa[-1 - x]) + _length(leaf_means[-1 - x], digits))
+            else:
+                lab = '' if labels is None else _support_label(labels[nodes[x]], label_digits)
+                parts.append(render(x) + lab + _length(mean[nodes[x]], digits))
+        return '(' + ','.join(parts) + ')'
+
+    return render(0) + ';'
+
+
 class TreePosterior:
     """The summary of one sweep's (or one group's) weighted final particles.
 
@@ -153,6 +256,46 @@ class TreePosterior:
         self.particle_topology = np.asarray(table['particle_topo'])
         self.consensus = consensus_newick(self.taxa, self.clade_sets, self.threshold)
         self.map = self.topologies[0] if self.topologies else None
+        if 'clade_stats' in table:
+            self._add_branches(table)
+
+    def _add_branches(self, table):
+        """branch lengths (Context.tree_branches): per clade the branch above it, per taxon the pendant branch, per topology its
+        clade rows and conditional means, the consensus and the MAP topology with mean lengths"""
+        n = len(self.taxa)
+        self.clade_branches = [branch_summary(st, w) for st, w in zip(table['clade_stats'], table['clade_weight'])]
+        leaves = [branch_summary(st, self.U) for st in table['leaf_stats']]
+        self.leaf_branches = {self.taxa[i]: leaves[i] for i in range(n)}
+        for t, rows, st in zip(self.topologies, table['topo_clades'], table['topo_stats']):
+            br = [branch_summary(x, t['weight']) for x in st]
+            t['clades'] = [int(j) for j in rows]
+            t['leaf_means'] = [b['mean'] for b in br[:n]]
+            t['clade_means'] = [b['mean'] for b in br[n:]]
+        chosen = [(m, self.clade_branches[j]['mean']) for j, (m, s) in enumerate(self.clade_sets)
+                  if 2 <= len(m) < n and s > self.threshold]
+        self.consensus_bl = tree_newick(self.taxa, chosen, [b['mean'] for b in leaves], labels=dict(self.clade_sets))
+        self.map_newick = None
+        if self.map is not None:
+            t = self.map
+            self.map_newick = tree_newick(self.taxa, [(self.clade_sets[j][0], m) for j, m in zip(t['clades'], t['clade_means'])],
+                                          t['leaf_means'])
+
+    def branches_json(self):
+        return {'taxa': self.taxa, 'total_weight': self.U,
+                'clades': [dict(taxa=list(names), support=s, **b) for (names, s), b in zip(self.clades, self.clade_branches)],
+                'leaves': self.leaf_branches,
+                'topologies': [{'probability': t['probability'], 'clades': t['clades'], 'leaf_means': t['leaf_means'],
+                                'clade_means': t['clade_means']} for t in self.topologies],
+                'consensus_bl': self.consensus_bl, 'map_newick': self.map_newick}
+
+    def write_branches(self, save_dir):
+        """consensus_bl.tre, map.tre and tree_branches.json in save_dir (a posterior built with branch lengths)"""
+        with open(os.path.join(save_dir, 'tree_branches.json'), 'w') as f:
+            json.dump(self.branches_json(), f, indent=1)
+        with open(os.path.join(save_dir, 'consensus_bl.tre'), 'w') as f:
+            f.write(self.consensus_bl + '\n')
+        with open(os.path.join(save_dir, 'map.tre'), 'w') as f:
+            f.write((self.map_newick or '') + '\n')
 
     def credible_set(self, p):
         """The fewest most probable topologies (table order: probability descending, ties by smallest representative) whose
@@ -168,9 +311,13 @@ class TreePosterior:
         return out
 
     def to_json(self):
+        def plain(t):                                      # (the branch-length keys go to tree_branches.json)
+            return {k: t[k] for k in ('probability', 'weight', 'count', 'representative', 'newick')}
+
         return {'taxa': self.taxa, 'threshold': self.threshold, 'total_weight': self.U,
                 'clades': [{'taxa': list(names), 'support': s} for names, s in self.clades],
-                'topologies': self.topologies, 'consensus': self.consensus, 'map': self.map}
+                'topologies': [plain(t) for t in self.topologies], 'consensus': self.consensus,
+                'map': None if self.map is None else plain(self.map)}
 
     def write(self, save_dir):
         """tree_posterior.json (everything above) and consensus.tre (the consensus Newick) in save_dir"""

@@ -265,16 +265,22 @@ class VCSMC:
         sweep (branch lengths = the sampled left/right branches of each coalescence)."""
         return self._newick_table()[k] + ';'
 
-    def tree_posterior(self, threshold=0.5):
+    def tree_posterior(self, threshold=0.5, branch_lengths=False):
         """Summary of the last sweep's tree posterior (the K weighted final particles; the counterpart of the CSMC path's
         get_tree_prob, csmc.py:335-349): clades with their support, topologies with probability, particle count,
         representative and its Newick, the majority-rule consensus (clades with support > threshold, supports as labels), the
         MAP topology and credible_set(p).  Clades, weights and topologies come from the device (phylo_tree_summary) in exact
-        integer weights; with --n_gpus > 1 a collective call that every rank makes, and every rank holds the same table."""
+        integer weights; with --n_gpus > 1 a collective call that every rank makes, and every rank holds the same table.
+        branch_lengths=True adds (phylo_tree_branches, no particle replayed): clade_branches (mean, sd, min, max of the branch
+        above every clade, conditional on the clade), leaf_branches by taxon name, per topology its `clades` rows and mean
+        lengths, consensus_bl (the consensus with :mean on every edge) and map_newick (the MAP topology with its mean lengths)."""
         from . import treepost
         if self._ctx is None or not hasattr(self, '_last_seed'):
             raise RuntimeError("tree_posterior summarises the last sweep: call sample_phylogenies first")
-        table = treepost.group_table(self._ctx.tree_summary(), 0)
+        tab = self._ctx.tree_summary()
+        if branch_lengths:
+            tab.update(self._ctx.tree_branches(tab))
+        table = treepost.group_table(tab, 0)
         trees = self._newick_table()
         newicks = {int(r): trees[int(r)] + ';' for r in table['topo_rep']}
         return treepost.TreePosterior(self.taxa, table, newicks, threshold)
@@ -307,6 +313,8 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
+                if key == 'tree_branches' and not v:       # (off: the file is what it was before the flag existed)
+                    continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))
         elbos = np.asarray(history['cost'])
@@ -403,7 +411,9 @@ class VCSMC:
         print("Done training.")
         self.elbos = np.asarray(elbos)
         # --tree_summary: the final evaluation sweep's tree posterior (a collective when sharded: every rank summarises)
-        self.posterior = self.tree_posterior() if getattr(self.args, 'tree_summary', False) else None
+        self.posterior = None
+        if getattr(self.args, 'tree_summary', False):
+            self.posterior = self.tree_posterior(branch_lengths=bool(getattr(self.args, 'tree_branches', False)))
         if save_dir is not None and getattr(self, '_rank', 0) == 0:   # sharded: every rank holds the same results; rank 0 writes
             if save_dir == 'auto':                   # vcsmc.py:504-507
                 tm = str(datetime.now())
@@ -412,6 +422,8 @@ class VCSMC:
             self.results = self._save_results(save_dir, initial, hist)
             if self.posterior is not None:
                 self.posterior.write(save_dir)             # tree_posterior.json, consensus.tre
+                if getattr(self.args, 'tree_branches', False):
+                    self.posterior.write_branches(save_dir)    # consensus_bl.tre, map.tre, tree_branches.json
             self.save_dir = save_dir
             print("Finished...")
         return self.elbos

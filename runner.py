@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--tree_summary` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--tree_summary`, `--tree_branches` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -47,7 +47,13 @@ def parse_args(argv=None):
     parser.add_argument('--tree_summary', default=False, type=lambda x: (str(x).lower() == 'true'),
                         help="after training, summarise the final evaluation sweep's tree posterior (clade supports, topology "
                              "probabilities, majority-rule consensus) into tree_posterior.json and consensus.tre in the results directory")
+    parser.add_argument('--tree_branches', default=False, type=lambda x: (str(x).lower() == 'true'),
+                        help="with --tree_summary true: also the branch lengths of that posterior (mean, sd, min, max above every "
+                             "clade and leaf) into tree_branches.json, consensus_bl.tre (consensus with mean lengths) and map.tre "
+                             "(the most probable topology with its mean lengths)")
     args = parser.parse_args(argv)
+    if args.tree_branches and not args.tree_summary:
+        parser.error('--tree_branches true needs --tree_summary true (it adds branch lengths to that summary)')
     if args.twisting is not None:
         args.nested = args.twisting
     if args.train_parallel == 'sharded' and args.nested:
