@@ -302,8 +302,15 @@ int phylo_tree_summary_fetch(phylo_ctx* ctx, uint64_t* clade_bits, uint64_t* cla
 int phylo_tree_branches(phylo_ctx* ctx, phylo_stats* perf);
 int phylo_tree_branches_fetch(phylo_ctx* ctx, double* clade_stats, double* leaf_stats, int32_t* topo_clades, double* topo_stats);
 
-/* Bit-level probe of the device arithmetic contract: op 0 exp(x), 1 log(x), 2 x/y, 3 fma(x,y,x). */
+/* Bit-level probe of the device arithmetic contract: op 0 exp(x), 1 log(x), 2 x/y, 3 fma(x,y,x), 4 exp(x) for x <= 0 (the scan's);
+ * op 5 is outside that contract: the reverse pass's reciprocal of a site likelihood (pg_rcp, an ulp or two off 1/x). */
 int phylo_math_probe(phylo_ctx* ctx, int op, const double* x, const double* y, int n, double* out);
+
+/* Test hook: the reverse pass's Frechet derivative of expm (a scaled Taylor series, phylo_grad.h) on n caller-given pairs of
+ * row-major 4x4 matrices, L = d/dt exp(A + t E) at t = 0.  form 0: one thread per matrix (pg_expm4_frechet, as pg_twist_finish
+ * runs it); form 1: four lanes per matrix, one row each (pg_expm4_frechet_row, as pg_node_finish runs it).  The kernels call
+ * the functions the pass calls; tests/test_gpu_grad_schemes.py compares both with a high-precision evaluation. */
+int phylo_debug_frechet(phylo_ctx* ctx, int form, const double* A_nx16, const double* E_nx16, int n, double* L_nx16);
 
 /* ---- multi-GPU: one process per GPU, particles sharded by contiguous ranges ------------------- */
 #define PHYLO_COMM_ID_BYTES 128

@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache",
     "phylo_vi_gradients", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -246,6 +246,17 @@ class Context:
         out = np.empty_like(x)
         self._check(self._lib.phylo_math_probe(self._h, C.c_int(op), _ptr(x), _ptr(y), C.c_int(x.size), _ptr(out)))
         return out
+
+    def frechet_probe(self, A, E, form):
+        """The reverse pass's Frechet derivative of expm on pairs of 4x4 matrices [n, 4, 4]: form 0 a lane per matrix
+        (pg_expm4_frechet), form 1 a quad per matrix (pg_expm4_frechet_row)."""
+        A = _f64(A).reshape(-1, 16)
+        E = _f64(E).reshape(-1, 16)
+        if A.shape != E.shape:
+            raise ValueError("A and E must hold the same number of 4x4 matrices")
+        L = np.empty_like(A)
+        self._check(self._lib.phylo_debug_frechet(self._h, C.c_int(int(form)), _ptr(A), _ptr(E), C.c_int(A.shape[0]), _ptr(L)))
+        return L.reshape(-1, 4, 4)
 
     # ---- sweep
     def sweep_async(self, seed, flags=FLAGS_DEFAULT, M=1):

@@ -298,11 +298,40 @@ __global__ __launch_bounds__(256) void pg_copy_words(pg_copy3 a) {
 }
 
 // ---- g1: omega = softmax_k(log w_r) ---------------------------------------------------------------
-__global__ __launch_bounds__(256) void pg_omega(pg_args a) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= a.R * a.K) return;
-    const int r = t / a.K;
-    a.om[t] = pm_exp((a.logw[t] - a.lse[r]) - pm_log((double)a.K));
+// One workgroup per rank event.  exp(log w - lse - log K) alone is a softmax only as far as lse is exact: the sweep stores it as
+// one double, so with log-weights of magnitude 1e5 (rates 1e4 apart between rank events: -lambda_r times every earlier branch
+// length) every omega of the event carries the same factor 1 + 1e-11, the sums over particles that should cancel in G and in
+// the rate adjoints do not, and d_lam is off by 2e-9 of its largest entry (tests/test_gpu_grad.py, regime mixed_alternating).
+// Hence the division by the event's own sum, which removes the common factor; fixed order of additions.
+#define PG_OMEGA_NT 1024
+#define PG_OMEGA_REG 4                                      // elements a thread keeps in registers between the two passes
+__global__ __launch_bounds__(PG_OMEGA_NT) void pg_omega(pg_args a) {
+    __shared__ double sh[PG_OMEGA_NT / 64];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const double* lw = a.logw + (size_t)r * a.K;
+    double* om = a.om + (size_t)r * a.K;
+    const double lse = a.lse[r], logK = pm_log((double)a.K);
+    double ev[PG_OMEGA_REG], sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < PG_OMEGA_REG; ++i) {
+        const int k = tid + i * PG_OMEGA_NT;
+        ev[i] = k < a.K ? pm_exp((lw[k] - lse) - logK) : 0.0;
+        sum = sum + ev[i];
+    }
+    for (int k = tid + PG_OMEGA_REG * PG_OMEGA_NT; k < a.K; k += PG_OMEGA_NT) sum = sum + pm_exp((lw[k] - lse) - logK);   // (again below)
+    sum = pg_wave_sum(sum);
+    if ((tid & 63) == 0) sh[tid >> 6] = sum;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < PG_OMEGA_NT / 64; ++w) tot = tot + sh[w];
+    const double inv = tot > 0.0 ? 1.0 / tot : 1.0;          // (no finite weight in the event: nothing to normalise)
+#pragma unroll
+    for (int i = 0; i < PG_OMEGA_REG; ++i) {
+        const int k = tid + i * PG_OMEGA_NT;
+        if (k < a.K) om[k] = ev[i] * inv;
+    }
+    for (int k = tid + PG_OMEGA_REG * PG_OMEGA_NT; k < a.K; k += PG_OMEGA_NT) om[k] = pm_exp((lw[k] - lse) - logK) * inv;
 }
 
 // ---- g2: G_r[k] = d logZ / d ll_r[k] = omega_r[k] - sum of omega_{r+1} over the particles that adopt k -----
@@ -1620,4 +1649,38 @@ __global__ __launch_bounds__(256) void pg_twist_xsum(pg_args a, int node0, int c
             if (cb + u < nc) v = v + q[u];
     }
     *dst = v;
+}
+
+// ---- test hooks (phylo_debug_frechet, phylo_math_probe op 5): the functions the pass calls, on caller-given inputs --------------
+// form 0: a lane per matrix, as pg_twist_finish calls the series
+__global__ __launch_bounds__(256) void pg_probe_frechet(const double* __restrict__ A, const double* __restrict__ E, int n,
+                                                        double* __restrict__ L) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n) return;
+    double a[16], e[16], l[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { a[i] = A[(size_t)m * 16 + i]; e[i] = E[(size_t)m * 16 + i]; }
+    pg_expm4_frechet(a, e, l);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) L[(size_t)m * 16 + i] = l[i];
+}
+// form 1: a quad per matrix, as pg_node_finish calls it (matrix = thread / 4, row = thread % 4); the lanes past the last matrix
+// repeat it and store nothing, so every quad of the ragged last workgroup stays whole
+__global__ __launch_bounds__(256) void pg_probe_frechet_row(const double* __restrict__ A, const double* __restrict__ E, int n,
+                                                            double* __restrict__ L) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, row = t & 3, m0 = t >> 2;
+    const bool valid = m0 < n;
+    const int m = valid ? m0 : n - 1;
+    double a[16], e[16], lr[4];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { a[i] = A[(size_t)m * 16 + i]; e[i] = E[(size_t)m * 16 + i]; }
+    pg_expm4_frechet_row(a, e, row, lr);
+    if (valid) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) L[(size_t)m * 16 + row * 4 + j] = lr[j];
+    }
+}
+__global__ __launch_bounds__(256) void pg_probe_rcp(const double* __restrict__ x, int n, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = pg_rcp(x[i]);
 }

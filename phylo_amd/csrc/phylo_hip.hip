@@ -2099,7 +2099,7 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
     //  neither waits for the host to read the counts nor holds up the coefficient chain on this stream)
     const bool sort_early = dev_lists && !c->env.grad_one_stream;
     if (dev_lists) CHK(dev_lists_launch(c, c->stream, c->stream, true, false));
-    hipLaunchKernelGGL(pg_omega, dim3(nrk), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(pg_omega, dim3(R), dim3(PG_OMEGA_NT), 0, c->stream, g);
     CHK(launch_check(c, "pg_omega"));
     hipLaunchKernelGGL(pg_leafpi, dim3(N), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_leafpi"));
@@ -3121,10 +3121,40 @@ int phylo_math_probe(phylo_ctx* c, int op, const double* x, const double* y, int
     CHK(scratch_get(c, 2, (size_t)n * 8, &dout));
     HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dy, y, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(pk_math_probe, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, op, (const double*)dx, (const double*)dy, n,
-                       (double*)dout);
-    CHK(launch_check(c, "pk_math_probe"));
+    if (op == 5) {                                         // the reverse pass's reciprocal (phylo_grad.h)
+        hipLaunchKernelGGL(pg_probe_rcp, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)dx, n, (double*)dout);
+        CHK(launch_check(c, "pg_probe_rcp"));
+    } else {
+        hipLaunchKernelGGL(pk_math_probe, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, op, (const double*)dx, (const double*)dy, n,
+                           (double*)dout);
+        CHK(launch_check(c, "pk_math_probe"));
+    }
     HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PHYLO_OK;
+}
+
+int phylo_debug_frechet(phylo_ctx* c, int form, const double* A, const double* E, int n, double* L) {
+    CHK(bind(c));
+    if ((form != 0 && form != 1) || n < 0 || n > (1 << 24) || (n > 0 && (!A || !E || !L)))
+        return fail(c, PHYLO_EINVAL, "phylo_debug_frechet: form 0 or 1, 0 <= n <= 2^24, A, E and L given");
+    if (n == 0) return PHYLO_OK;
+    const size_t bytes = (size_t)n * 16 * 8;
+    void *dA, *dE, *dL;
+    CHK(scratch_get(c, 0, bytes, &dA));
+    CHK(scratch_get(c, 1, bytes, &dE));
+    CHK(scratch_get(c, 2, bytes, &dL));
+    HIPCHK(c, hipMemcpyAsync(dA, A, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dE, E, bytes, hipMemcpyHostToDevice, c->stream));
+    if (form == 0) {
+        hipLaunchKernelGGL(pg_probe_frechet, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)dA, (const double*)dE, n, (double*)dL);
+        CHK(launch_check(c, "pg_probe_frechet"));
+    } else {                                               // whole workgroups: the quads past matrix n - 1 are padded by the kernel
+        hipLaunchKernelGGL(pg_probe_frechet_row, dim3(cdiv((long)n * 4, 256)), dim3(256), 0, c->stream, (const double*)dA, (const double*)dE, n,
+                           (double*)dL);
+        CHK(launch_check(c, "pg_probe_frechet_row"));
+    }
+    HIPCHK(c, hipMemcpyAsync(L, dL, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PHYLO_OK;
 }

@@ -1,4 +1,8 @@
 """Random small configurations of the reverse pass (plain and twisted proposal), GPU against oracle/cpu_grad.py at relative 1e-9.
+Every other iteration draws from the wide regime (log-rates uniform over [log 0.05, log 1e4], spread up to 2.5); the regime is
+printed with each failure.  A wide draw can be ill-conditioned in binary64 itself: seed 3 stops at iteration 1241 (N=2, S=130,
+K=18, spread 1.131, a rate of 0.0098 and branch lengths up to 336) with d_lam_r off by 2.1e-8 -- where the oracle's own d_lam_r
+moves by 3.6e-8 when the rates move by one ulp, so no two binary64 evaluations agree to 1e-9 there.
 python tests/fuzz_grad.py [seconds] [seed]"""
 import os
 import sys
@@ -20,9 +24,13 @@ while time.time() - t0 < budget:
     M = int(rng.integers(1, 5)) if twisted else 1
     generic = rng.integers(0, 5) == 0
     genome = rng.uniform(0.05, 1.0, size=(N, S, 4)) if generic else T._codes_genome(rng, N, S)
-    Q, pi, ll, lr = T._model(rng, N, spread=float(rng.uniform(0.1, 0.5)), lam=float(rng.uniform(1.0, 2.5)))
+    wide = n % 2 == 1                       # every other iteration: rates from 0.05 to 1e4, Q and pi from mild to skewed
+    spread = float(rng.uniform(0.1, 2.5)) if wide else float(rng.uniform(0.1, 0.5))
+    loglam = float(rng.uniform(np.log(0.05), np.log(1e4))) if wide else float(rng.uniform(1.0, 2.5))
+    Q, pi, ll, lr = T._model(rng, N, spread=spread, lam=loglam)
     seed = int(rng.integers(0, 2 ** 31))
-    what = "N=%d S=%d K=%d %s M=%d generic=%s seed=%d" % (N, S, K, 'twisted' if twisted else 'plain', M, generic, seed)
+    what = "N=%d S=%d K=%d %s M=%d generic=%s seed=%d regime=%s spread=%.3f log_lam=%.3f" % (
+        N, S, K, 'twisted' if twisted else 'plain', M, generic, seed, 'wide' if wide else 'corner', spread, loglam)
     try:
         if twisted:
             T._check_twisted(genome, Q, pi, ll, lr, K=K, M=M, seed=seed)
@@ -33,6 +41,7 @@ while time.time() - t0 < budget:
         raise
     n += 1
     kinds['twisted' if twisted else 'plain'] = kinds.get('twisted' if twisted else 'plain', 0) + 1
+    kinds['wide' if wide else 'corner'] = kinds.get('wide' if wide else 'corner', 0) + 1
     if time.time() - last > 30:
         print("  ... %d gradients so far (%s)" % (n, what), flush=True)
         last = time.time()

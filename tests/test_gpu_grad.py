@@ -8,6 +8,7 @@ from oracle import cpu_grad as G
 from oracle import cpu_ref as O
 from phylo_amd import _ffi
 from phylo_amd.datasets import load_dataset
+from tests.grad_regimes import REGIMES, SWITCH_REGIMES, regime
 
 pytestmark = pytest.mark.gpu
 
@@ -605,3 +606,64 @@ def test_twisted_gradient_more_sub_samples_than_lds_holds():
     rng = np.random.default_rng(43)
     Q, pi, ll, lr = _model(rng, genome.shape[0], spread=0.2, lam=2.3)
     _check_twisted(genome, Q, pi, ll, lr, K=2, M=44, seed=4)
+
+
+# ---- model regimes away from the corner every case above draws from (tests/grad_regimes.py; the oracle's fitness for each of them
+# is tests/test_oracle_grad.py::test_oracle_gradient_model_regimes) -----------------------------------------------------------
+def _block_errors(g, ref, jc):
+    out = {}
+    for key in ('d_lam_l', 'd_lam_r') + (() if jc else ('d_pi', 'd_Q')):
+        out[key] = float(np.max(np.abs(g[key] - ref[key])) / max(np.max(np.abs(ref[key])), 1e-300))
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(REGIMES))
+def test_gradient_model_regimes(name):
+    """Rates from 0.05 to 1e4 (the Frechet series at five to eight squarings on most nodes, and at its shortest class), rates 1e4
+    apart between the sides and between rank events, a skewed Q and stationary vector, generators scaled by 30 and by 1e-3, the JC69
+    closed form: the gradient within RTOL of the oracle -- and the forward sweep of the same context bit-equal to the C oracle's, so
+    that a regime that breaks the forward contract is told apart from one that breaks the reverse pass."""
+    from oracle import c_oracle as CO
+    c = regime(name)
+    genome, Q, pi, ll, lr, K, seed, jc = (c[k] for k in ('genome', 'Q', 'pi', 'll', 'lr', 'K', 'seed', 'jc'))
+    N, S, _ = genome.shape
+    with _ffi.Context(K, N, S) as ctx:
+        ctx.set_leaves(genome)
+        ctx.set_model(Q, pi, ll, lr, jc69_closed_form=jc)
+        out = ctx.sweep(seed)
+    ref = CO.sweep(genome, Q, pi, ll, lr, K, seed, jc=jc)
+    assert np.array_equal(out['ancestors'], ref['ancestors']) and np.array_equal(out['merges'], ref['merges'])
+    for key in ('left_branches', 'right_branches', 'log_likelihood', 'log_weights'):
+        assert np.array_equal(out[key].view(np.uint64), ref[key].view(np.uint64)), "forward sweep: " + key
+    assert np.float64(out['logZ']).view(np.uint64) == np.float64(ref['logZ']).view(np.uint64), (out['logZ'], ref['logZ'])
+    assert np.isfinite(out['logZ'])
+    g, gref = _check(genome, Q, pi, ll, lr, K=K, seed=seed, jc=jc)
+    print('regime %s: worst relative error per block %s' % (name, _block_errors(g, gref, jc)))
+
+
+@pytest.mark.parametrize("name", sorted(REGIMES))
+def test_twisted_gradient_model_regimes(name):
+    """The same regimes through the twisted proposal's reverse pass (M = 2: pg_twist_finish runs the one-lane form of the series on
+    every sub-sample), on the first 6 taxa and 40 sites of each case."""
+    c = regime(name)
+    genome = c['genome'][:6, :40]
+    g, gref = _check_twisted(genome, c['Q'], c['pi'], c['ll'][:5], c['lr'][:5], K=16, M=2, seed=c['seed'], jc=c['jc'])
+    print('twisted regime %s: worst relative error per block %s' % (name, _block_errors(g, gref, c['jc'])))
+
+
+@pytest.mark.parametrize("name", SWITCH_REGIMES)
+def test_gradient_model_regimes_same_under_the_switches(monkeypatch, name):
+    """A long-branch and a skewed regime with the host-built lists, with eager nodes, and with the launch per rank event of the
+    coefficient and row chains: the default's gradient within the 1e-12 of the tests of those switches above."""
+    c = regime(name)
+    args = (c['genome'], c['Q'], c['pi'], c['ll'], c['lr'])
+    g = _check(*args, K=c['K'], seed=c['seed'])[0]
+    for env in (('PHYLO_REV_HOST_LISTS',), ('PHYLO_EAGER_NODES',), ('PHYLO_GRAD_ROWS_CHAIN', 'PHYLO_GRAD_COEFF_CHAIN')):
+        for e in env:
+            monkeypatch.setenv(e, '1')
+        g_sw = _check(*args, K=c['K'], seed=c['seed'])[0]
+        for e in env:
+            monkeypatch.delenv(e)
+        for key in ('d_lam_l', 'd_lam_r', 'd_pi', 'd_Q'):
+            scale = max(np.max(np.abs(g[key])), 1e-300)
+            assert np.max(np.abs(g_sw[key] - g[key])) / scale < 1e-12, (env, key)

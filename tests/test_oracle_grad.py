@@ -114,3 +114,31 @@ def test_twisted_gradient_matches_central_differences(M):
             fd = G.finite_difference_twisted(genome, Q, pi, ll, lr, K, M, 31, st, which, idx)
             an = g[key][idx]
             assert abs(fd - an) <= 2e-6 * max(1.0, abs(an)), (which, idx, fd, an)
+
+
+def _regime_names():
+    from tests.grad_regimes import REGIMES
+    return sorted(REGIMES)
+
+
+@pytest.mark.parametrize("name", _regime_names())
+def test_oracle_gradient_model_regimes(name):
+    """The reference's fitness for every model regime tests/test_gpu_grad.py runs the device on (tests/grad_regimes.py: rates from
+    0.05 to 1e4, a skewed and an un-normalised Q, JC69): finite everywhere, and three entries of every block equal to central
+    differences within the 2e-6 of test_gradient_matches_central_differences."""
+    from tests.grad_regimes import regime
+    c = regime(name)
+    genome, Q, pi, ll, lr, K, seed = (c[k] for k in ('genome', 'Q', 'pi', 'll', 'lr', 'K', 'seed'))
+    R = genome.shape[0] - 1
+    g = G.sweep_grad(genome, Q, pi, ll, lr, K, seed)
+    assert np.isfinite(g['logZ'])
+    for key in ('d_lam_l', 'd_lam_r', 'd_pi', 'd_Q'):
+        assert np.all(np.isfinite(g[key])), key
+    for which, key, idxs in (('lam_l', 'd_lam_l', [(0,), (R // 2,), (R - 1,)]), ('lam_r', 'd_lam_r', [(0,), (R // 2,), (R - 1,)]),
+                             ('pi', 'd_pi', [(0,), (1,), (3,)]), ('Q', 'd_Q', [(0, 0), (1, 2), (3, 1)])):
+        for idx in idxs:
+            # (a step of 1e-6 relative to the entry: the rates span 0.05 .. 1e4)
+            h = 1e-6 * max(1.0, abs({'lam_l': ll, 'lam_r': lr, 'pi': pi[0], 'Q': Q}[which][idx]))
+            fd = G.finite_difference(genome, Q, pi, ll, lr, K, seed, g['struct'], which, idx, h=h)
+            an = g[key][idx]
+            assert abs(fd - an) <= 2e-6 * max(1.0, abs(an)), (which, idx, fd, an)
