@@ -312,6 +312,16 @@ int phylo_math_probe(phylo_ctx* ctx, int op, const double* x, const double* y, i
  * the functions the pass calls; tests/test_gpu_grad_schemes.py compares both with a high-precision evaluation. */
 int phylo_debug_frechet(phylo_ctx* ctx, int form, const double* A_nx16, const double* E_nx16, int n, double* L_nx16);
 
+/* Test hook: the two statements of the site-product update (phylo_amd/csrc/phylo_math.h) on n caller-given
+ * triples (p in [1,2), any x1, any x2), each from a fresh {p, 0, 0.0}: row 0 of the outputs [2][n] is the state (p', E', extra')
+ * after pm_lp_mul2(x1, x2) -- the pair form of the merge kernels --, row 1 after pm_lp_mul(x1); pm_lp_mul(x2) -- the contract's
+ * statement, what the oracle does.  ctx == NULL: a loop on the host, no GPU needed; otherwise one thread per triple on the
+ * context's device (n <= 2^22 per call: the 64 n bytes of device scratch stay with the context until it is destroyed, so use a
+ * throw-away context).  Both run the same functions the kernels call.  tests/test_site_product_host.py and
+ * tests/test_gpu_site_product_edges.py compare them with a restatement in Python. */
+int phylo_debug_site_product(phylo_ctx* ctx, const double* p, const double* x1, const double* x2, int n, double* out_p, int32_t* out_E,
+                             double* out_extra);
+
 /* ---- multi-GPU: one process per GPU, particles sharded by contiguous ranges ------------------- */
 #define PHYLO_COMM_ID_BYTES 128
 /* rank 0 makes the id (ncclGetUniqueId) and hands it to the other ranks out of band. */

@@ -71,6 +71,14 @@ def math_probe(op, x, y=None):
     return out
 
 
+def lp_probe(p, x1, x2):
+    """(p', E', extra') of the site product after ora_lp_mul(x1); ora_lp_mul(x2) from a fresh {p, 0, 0.0}, per triple"""
+    p, x1, x2 = _c(p).reshape(-1), _c(x1).reshape(-1), _c(x2).reshape(-1)
+    op, oE, ox = np.empty_like(p), np.empty(p.size, dtype=np.int32), np.empty_like(p)
+    lib().ora_lp_probe(_opt(p), _opt(x1), _opt(x2), C.c_int(p.size), _opt(op), _opt(oE), _opt(ox))
+    return op, oE, ox
+
+
 def philox(c0, c1, c2, c3, seed):
     out = (C.c_uint32 * 4)()
     lib().ora_philox4x32(C.c_uint32(c0), C.c_uint32(c1), C.c_uint32(c2), C.c_uint32(c3), C.c_uint64(seed), out)

@@ -59,6 +59,17 @@ void ora_math_probe(int op, const double* x, const double* y, int n, double* out
     }
 }
 
+/* the per-factor statement of the site product on n triples, each from a fresh {p, 0, 0.0}: ora_lp_mul(x1); ora_lp_mul(x2) */
+void ora_lp_probe(const double* p, const double* x1, const double* x2, int n, double* out_p, int32_t* out_E, double* out_extra) {
+    for (int i = 0; i < n; ++i) {
+        ora_lp a;
+        a.p = p[i]; a.E = 0; a.extra = 0.0;
+        ora_lp_mul(&a, x1[i]);
+        ora_lp_mul(&a, x2[i]);
+        out_p[i] = a.p; out_E[i] = a.E; out_extra[i] = a.extra;
+    }
+}
+
 void ora_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t seed, uint32_t* out4) {
     ora_philox(c0, c1, c2, c3, seed, out4);
 }

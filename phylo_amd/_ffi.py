@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -113,6 +113,25 @@ def _lists_dict(lists, meta, R, K):
     out["rank_chunk0"] = meta[6 + (R + 1):6 + 2 * (R + 1)].copy()
     out["ev_slow0"] = meta[6 + 2 * (R + 1):6 + 3 * (R + 1)].copy()
     return out
+
+
+def _site_product(handle, p, x1, x2):
+    lib = load()
+    p, x1, x2 = _f64(p).reshape(-1), _f64(x1).reshape(-1), _f64(x2).reshape(-1)
+    if not (p.size == x1.size == x2.size):
+        raise ValueError("p, x1 and x2 must hold the same number of values")
+    n = p.size
+    op, oE, ox = np.empty((2, n)), np.empty((2, n), dtype=np.int32), np.empty((2, n))
+    rc = lib.phylo_debug_site_product(handle, _ptr(p), _ptr(x1), _ptr(x2), C.c_int(n), _ptr(op), _ptr(oE), _ptr(ox))
+    if rc:
+        raise PhyloError(rc, (lib.phylo_last_error(handle) or b"").decode())
+    return {'pair': (op[0], oE[0], ox[0]), 'each': (op[1], oE[1], ox[1])}
+
+
+def debug_site_product(p, x1, x2):
+    """The site-product update on triples (p in [1,2), x1, x2) from a fresh {p, 0, 0.0}, ON THE HOST (no GPU needed): 'pair' =
+    (p', E', extra') after pm_lp_mul2(x1, x2), 'each' = the same after pm_lp_mul(x1); pm_lp_mul(x2)."""
+    return _site_product(None, p, x1, x2)
 
 
 def vi_apply(N, jc, packed_vars, packed_grads, kind, lr, beta1=0.9, beta2=0.999, eps=1e-8, state=None):
@@ -257,6 +276,10 @@ class Context:
         L = np.empty_like(A)
         self._check(self._lib.phylo_debug_frechet(self._h, C.c_int(int(form)), _ptr(A), _ptr(E), C.c_int(A.shape[0]), _ptr(L)))
         return L.reshape(-1, 4, 4)
+
+    def site_product_probe(self, p, x1, x2):
+        """debug_site_product through a kernel on this context's device"""
+        return _site_product(self._h, p, x1, x2)
 
     # ---- sweep
     def sweep_async(self, seed, flags=FLAGS_DEFAULT, M=1):

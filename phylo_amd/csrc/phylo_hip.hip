@@ -3159,6 +3159,36 @@ int phylo_debug_frechet(phylo_ctx* c, int form, const double* A, const double* E
     return PHYLO_OK;
 }
 
+int phylo_debug_site_product(phylo_ctx* c, const double* p, const double* x1, const double* x2, int n, double* out_p, int32_t* out_E,
+                             double* out_extra) {
+    if (n < 0 || n > (1 << 22) || (n > 0 && (!p || !x1 || !x2 || !out_p || !out_E || !out_extra)))
+        return fail(c, PHYLO_EINVAL, "phylo_debug_site_product: 0 <= n <= 2^22, inputs of n and outputs of 2 n values given");
+    if (!c) {                                              // the host body: no device is touched
+        for (int i = 0; i < n; ++i) pk_site_product_one(p[i], x1[i], x2[i], i, n, out_p, out_E, out_extra);
+        return PHYLO_OK;
+    }
+    CHK(bind(c));
+    if (n == 0) return PHYLO_OK;
+    const size_t in = (size_t)n * 8;
+    void *din, *dpx, *dE;
+    CHK(scratch_get(c, 0, 3 * in, &din));
+    CHK(scratch_get(c, 1, 4 * in, &dpx));                  // p' (2 n) | extra' (2 n)
+    CHK(scratch_get(c, 2, (size_t)n * 2 * 4, &dE));
+    double* d = static_cast<double*>(din);
+    double* o = static_cast<double*>(dpx);
+    HIPCHK(c, hipMemcpyAsync(d, p, in, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + n, x1, in, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + 2 * (size_t)n, x2, in, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(pk_site_product_probe, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d, (const double*)(d + n),
+                       (const double*)(d + 2 * (size_t)n), n, o, (int32_t*)dE, o + 2 * (size_t)n);
+    CHK(launch_check(c, "pk_site_product_probe"));
+    HIPCHK(c, hipMemcpyAsync(out_p, o, 2 * in, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_extra, o + 2 * (size_t)n, 2 * in, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_E, dE, (size_t)n * 2 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PHYLO_OK;
+}
+
 // ---- multi-GPU --------------------------------------------------------------------------------
 int phylo_comm_unique_id(char id[PHYLO_COMM_ID_BYTES]) {
     std::string err;

@@ -2378,3 +2378,21 @@ __global__ void pk_math_probe(int op, const double* __restrict__ x, const double
     }
     out[i] = v;
 }
+
+// The site-product contract's two statements side by side (phylo_debug_site_product): triple i starts from {p[i], 0, 0.0} and is
+// updated by pm_lp_mul2(x1, x2) -> row 0 of the outputs, and by pm_lp_mul(x1); pm_lp_mul(x2) -> row 1 (rows of n).  __host__
+// __device__: the entry point runs it in a loop on the CPU or through the kernel below, the same PM_HD functions either way.
+PM_HD void pk_site_product_one(double p, double x1, double x2, int i, int n, double* out_p, int32_t* out_E, double* out_extra) {
+    pm_lp a = {p, 0, 0.0}, b = {p, 0, 0.0};
+    pm_lp_mul2(a, x1, x2);
+    pm_lp_mul(b, x1);
+    pm_lp_mul(b, x2);
+    out_p[i] = a.p; out_E[i] = a.E; out_extra[i] = a.extra;
+    out_p[n + i] = b.p; out_E[n + i] = b.E; out_extra[n + i] = b.extra;
+}
+__global__ void pk_site_product_probe(const double* __restrict__ p, const double* __restrict__ x1, const double* __restrict__ x2, int n,
+                                      double* __restrict__ out_p, int32_t* __restrict__ out_E, double* __restrict__ out_extra) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    pk_site_product_one(p[i], x1[i], x2[i], i, n, out_p, out_E, out_extra);
+}
