@@ -250,6 +250,25 @@ int phylo_debug_reverse_lists(int N, int K, const int64_t* ancestors, const int3
                               const int32_t* lookahead_nodes, int n_lookahead, int32_t* lists, int64_t n_lists, int32_t* meta,
                               int n_meta);
 
+/* Test hook, no GPU needed: the twisted proposal's look-ahead lists of phylo_sweep_backward (pg_build_lookahead,
+ * phylo_amd/csrc/phylo_revlists.h) on caller-supplied adopted root tables roots_ad [N-1][K][N] (slots 0 .. N-r-1 of rank event r:
+ * a leaf id < N or a node id N + r' K + k of an earlier rank event r'; rank event 0 is not looked at).  S shapes the chunks; M (the
+ * look-ahead merges per pair) is checked and otherwise unused: the lists do not depend on it.  slow_flag [(N-1) K], in and out:
+ * bit 1 is set for every touched node.  image receives xent | xchunk_node | xchunk_beg | xchunk_cnt | xchunk_part | xnode_id |
+ * xnode_chunk0 | xnode_nchunks (n_xent + 4 n_xchunks + 3 n_xnodes + 1 ints; PHYLO_EINVAL when n_image is too small); meta: n_xent,
+ * n_xchunks, n_xnodes, tw_max_chunks, then ev_chunk0[R+1], ev_node0[R+1] (R = N - 1).  tests/test_revlists_cpu.py. */
+int phylo_debug_lookahead_lists(int N, int K, int S, int M, const int32_t* roots_ad, int32_t* slow_flag, int32_t* image,
+                                int64_t n_image, int32_t* meta, int n_meta);
+
+/* Test hook, no GPU needed: the form phylo_sweep_backward takes (pg_plan_form + pg_plan_chains, phylo_revlists.h; DESIGN.md
+ * section 4b "driver") for a shape, the last sweep's facts (twisted proposal; lazy sweep that left marks), the switches (bit 0
+ * PHYLO_REV_HOST_LISTS, 1 PHYLO_GRAD_ONE_STREAM, 2 PHYLO_GRAD_TWO_STREAMS, 3 PHYLO_GRAD_ROWS_CHAIN, 4 PHYLO_GRAD_COEFF_CHAIN) and
+ * the lists' counts (flagged nodes, tiles of 256 sites per row, workgroups of the coefficient chain, reverse passes in flight in
+ * the process).  mask: bit 0 rows_form, 1 whole, 2 early_free, 3 dev_lists, 4 sort_early, 5 bg_free, 6 two, 7 parents_first,
+ * 8 rows_all, 9 rows_overlap, 10 chunks_first, 11 interleave, 12 coeff_all.  tests/test_revplan_cpu.py restates the rules. */
+int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int twisted, int marks, uint32_t switches, int64_t n_slow,
+                             int TS, int64_t coeff_wgs, int passes_in_flight, uint32_t* mask);
+
 /* The same lists built by the device kernels (phylo_revlists_dev.h) from the graph of the preceding lazy sweep with
  * PHYLO_KEEP_GRAPH, copied back in the same layout (what the builders do not write reads -1; heavy[] holds GLOBAL chunk indices,
  * rank_chunk0 in meta is zero), plus, when not NULL, the ancestors [N-2][K] and children [N-1][K][2] they were built from:

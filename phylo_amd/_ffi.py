@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -94,6 +94,56 @@ def debug_reverse_lists(N, K, ancestors, child, early_free=True, rows_form=True,
     if rc:
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     return _lists_dict(lists, meta, R, K)
+
+
+def debug_lookahead_lists(N, K, S, M, roots_ad, slow_flag=None):
+    """The twisted proposal's look-ahead lists of the reverse pass on given adopted root tables [N-1][K][N] (no GPU needed).
+    Returns the arrays the device reads, the per-rank-event offsets and slow_flag [(N-1) K] with bit 1 set for the touched nodes."""
+    lib = load()
+    R = N - 1
+    rad = np.ascontiguousarray(roots_ad, dtype=np.int32)
+    if rad.shape != (R, K, N):
+        raise ValueError("roots_ad must be [N-1][K][N]")
+    flag = np.zeros(R * K, dtype=np.int32) if slow_flag is None else np.array(slow_flag, dtype=np.int32).reshape(R * K)
+    n_image = R * (8 * K * N + 8192) + 1                   # entries <= K N per rank event, chunks <= max(entries, 2048), nodes <= entries
+    image = np.zeros(n_image, dtype=np.int32)
+    meta = np.zeros(4 + 2 * (R + 1), dtype=np.int32)
+    rc = lib.phylo_debug_lookahead_lists(C.c_int(N), C.c_int(K), C.c_int(S), C.c_int(M), _ptr(rad), _ptr(flag), _ptr(image),
+                                         C.c_int64(n_image), _ptr(meta), C.c_int(meta.size))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    ne, nc, nx = int(meta[0]), int(meta[1]), int(meta[2])
+    out = {"n_xent": ne, "n_xchunks": nc, "n_xnodes": nx, "tw_max_chunks": int(meta[3]), "slow_flag": flag,
+           "ev_chunk0": meta[4:4 + R + 1].copy(), "ev_node0": meta[4 + R + 1:4 + 2 * (R + 1)].copy()}
+    o = 0
+    for name, n in (("xent", ne), ("xchunk_node", nc), ("xchunk_beg", nc), ("xchunk_cnt", nc), ("xchunk_part", nc), ("xnode_id", nx),
+                    ("xnode_chunk0", nx), ("xnode_nchunks", nx)):
+        out[name] = image[o:o + n].copy()
+        o += n
+    return out
+
+
+PLAN_BITS = ("rows_form", "whole", "early_free", "dev_lists", "sort_early", "bg_free", "two", "parents_first", "rows_all", "rows_overlap",
+             "chunks_first", "interleave", "coeff_all")
+PLAN_SWITCHES = ("rev_host_lists", "one_stream", "two_streams", "rows_chain", "coeff_chain")
+
+
+def debug_reverse_plan(N, K, S, K_local=None, world=1, twisted=False, marks=True, switches=(), n_slow=0, TS=None, coeff_wgs=0,
+                       passes_in_flight=1):
+    """The form phylo_sweep_backward takes for a shape, the last sweep's facts, the switches (names of PLAN_SWITCHES) and the lists'
+    counts (no GPU needed): a dict of the booleans of PLAN_BITS plus 'mask'."""
+    lib = load()
+    sw = sum(1 << PLAN_SWITCHES.index(name) for name in switches)
+    mask = C.c_uint32(0)
+    rc = lib.phylo_debug_reverse_plan(C.c_int(N), C.c_int(K), C.c_int(K if K_local is None else K_local), C.c_int(S), C.c_int(world),
+                                      C.c_int(int(twisted)), C.c_int(int(marks)), C.c_uint32(sw), C.c_int64(n_slow),
+                                      C.c_int((S + 255) // 256 if TS is None else TS), C.c_int64(coeff_wgs), C.c_int(passes_in_flight),
+                                      C.byref(mask))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    out = {name: bool(mask.value >> i & 1) for i, name in enumerate(PLAN_BITS)}
+    out["mask"] = mask.value
+    return out
 
 
 def _lists_dict(lists, meta, R, K):

@@ -1919,10 +1919,6 @@ int phylo_sweep_node(phylo_ctx* c, int r, int k, double* out) {
 }
 
 // ---- the reverse pass's integer lists built on the device (phylo_revlists_dev.h): launches, then the few integers the host needs
-struct dl_meta {
-    std::vector<int32_t> ev_adp0, ev_slow0;
-    int32_t n_adp = 0, n_chunks = 0, n_slow = 0, n_par = 0;
-};
 static unsigned bit_length(size_t v) { unsigned b = 0; while (v) { ++b; v >>= 1; } return b ? b : 1; }
 extern "C++" {
 template <int ITEMS>
@@ -2016,14 +2012,15 @@ static int dev_lists_launch(phylo_ctx* c, hipStream_t sL, hipStream_t sS, bool k
     }
     return PHYLO_OK;
 }
-static int dev_lists_wait(phylo_ctx* c, dl_meta& m) {
+static int dev_lists_wait(phylo_ctx* c, pg_list_counts& m) {
     CHK(wait_event_spin(c, c->ev_dl));
     const int R = c->N - 1;
     const int32_t* h = c->h_dlmeta;
     m.ev_adp0.assign(h, h + R + 1);
     m.ev_slow0.assign(h + R + 1, h + 2 * (R + 1));
+    m.rank_chunk0.assign((size_t)R + 1, 0);                // (heavy[] holds global chunk indices)
     const int32_t* t = h + 2 * (R + 1);
-    m.n_adp = t[0]; m.n_chunks = t[1]; m.n_slow = t[2]; m.n_par = t[3];
+    m.n_adp = t[0]; m.n_chunks = (size_t)t[1]; m.max_chunks = 0; m.n_slow = t[2]; m.n_par = t[3];
     return PHYLO_OK;
 }
 
@@ -2046,22 +2043,41 @@ int phylo_sweep_backward(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double*
     return rc;
 }
 
-static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->swept || !c->last_graph)
-        return fail(c, PHYLO_ESTATE, "phylo_sweep_backward needs a preceding sweep with PHYLO_KEEP_GRAPH");
-    const int N = c->N, K = c->K, S = c->S, R = N - 1;
-    const bool rows_form = S <= 4096;                     // pg_nodes_rows: one workgroup per node, one tile
-    const int T = rows_form ? 1 : (S + PG_NT - 1) / PG_NT;
-    const bool twist = c->last_graph_twist;
-    const size_t nn = (size_t)R * K;
-    // ---- what does not need the integer lists is launched first: the GPU works while the host builds them
+// ---- the reverse pass's driver ("driver"): the form is decided in phylo_revlists.h (pg_plan_form before the
+//      first launch, pg_plan_chains once the lists' counts are known); the stages below read the plan and issue the pass in the
+//      order sweep_backward_impl names them.  The order of the HIP calls on each stream, and where the host builders run between
+//      them, is what the measurements in the comments paid for.
+struct rev_pass {
+    phylo_ctx* c = nullptr;
     pg_args g{};
-    g.N = N; g.S = S; g.K = K; g.R = R; g.T = T; g.jc = c->jc;
-    g.twist = twist ? 1 : 0;
-    // sharded: the sweep made the per-rank records whole on every rank (graph_gather), node rows are read from their owners' pools,
-    // and every rank runs the whole pass over that genealogy
-    const bool whole = c->world > 1;
+    pg_plan plan{};
+    pg_list_counts n;                    // the lists' counts, from the host builders or from pg_dl_lists
+    pg_lookahead x;                      // twisted proposal: the look-ahead lists' counts
+    pg_lists L{};                        // the pinned image of the device slab (what the host builders write)
+    hipStream_t sB = nullptr;            // the adopted nodes' chain: the second stream (plan.two), else the context's
+    int node_launches = 0, tw_launches = 0;
+    std::chrono::steady_clock::time_point host_t0;
+    double host_ms = 0.0;
+};
+
+static pg_plan_in rev_plan_in(const phylo_ctx* c) {
+    pg_plan_in in{};
+    in.N = c->N; in.K = c->K; in.K_local = c->Kloc; in.S = c->S; in.world = c->world;
+    in.twist = c->last_graph_twist; in.marks = c->last_graph_marks;
+    in.rev_host_lists = c->env.rev_host_lists; in.one_stream = c->env.grad_one_stream; in.two_streams = c->env.grad_two_streams;
+    in.rows_chain = c->env.grad_rows_chain; in.coeff_chain = c->env.grad_coeff_chain;
+    in.dl_max_k = PG_DL_MAX_K;
+    return in;
+}
+
+// 1. the pointer block
+static int rev_bind(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    pg_args& g = p.g;
+    const int N = c->N, K = c->K, S = c->S, R = N - 1;
+    const bool whole = p.plan.whole;
+    g.N = N; g.S = S; g.K = K; g.R = R; g.T = p.plan.rows_form ? 1 : (S + PG_NT - 1) / PG_NT; g.jc = c->jc;
+    g.twist = p.plan.twist ? 1 : 0;
     g.leaves = c->d_leaves; g.pool = c->d_pool; g.adj = c->d_adj; g.Pmat = whole ? c->d_gPmat : c->d_Pmat;
     g.pool_ptrs = whole ? (const double* const*)c->d_pool_ptrs : nullptr; g.Kloc = c->Kloc;
     g.bl = whole ? c->d_gbl : c->d_bl; g.br = whole ? c->d_gbr : c->d_br; g.logw = c->d_logw; g.lse = c->d_lse;
@@ -2072,7 +2088,9 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
     g.slow_flag = c->d_slow_flag; g.slow_idx = c->d_slow_idx;
     g.om = c->d_om; g.G = c->d_G; g.C = c->d_C; g.part = c->d_part; g.nodeg = c->d_nodeg;
     g.leafpi = c->d_leafpi; g.leafterm = c->d_leafterm; g.terms = c->d_terms; g.out = c->d_gout;
-    if (twist) {
+    g.alpha_om = p.plan.early_free ? 1 : 0;                // a free parent then is a node nobody adopted: alpha = omega
+    if (p.plan.early_free) g.mark = c->d_mark;
+    if (p.plan.twist) {
         g.tw.M = c->last_M; g.tw.joff = c->d_joff; g.tw.roots_ad = c->d_hroots_ad;
         g.tw.tw_b = c->d_htw_b; g.tw.tw_P = c->d_htw_P; g.tw.pot = c->d_hpot; g.tw.chosen = c->d_hchosen;
         g.tw.tau = c->d_tau; g.tw.ctw = c->d_ctw; g.tw.twpart = c->d_twpart; g.tw.twnode = c->d_twnode;
@@ -2082,454 +2100,392 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
         CHK(scratch_get(c, 4, (size_t)K * ((J0 + 255) / 256) * PG_NODEG * 8, &sl));
         g.tw.twslice = (double*)sl;
     }
+    return PHYLO_OK;
+}
+
+// (2.) the twisted proposal's kernels over the look-ahead potentials: they need no list either
+static int rev_early_twist(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    const pg_args& g = p.g;
+    const int N = g.N, K = g.K, R = g.R;
+    const size_t J0 = (size_t)((N * (N - 1)) / 2) * c->last_M;
+    hipLaunchKernelGGL(pg_twist_tau, dim3(R * K), dim3(64), (J0 <= 8192 ? J0 : 8192) * 8, c->stream, g);   // later rank events have fewer rows and use LDS
+    CHK(launch_check(c, "pg_twist_tau"));
+    hipLaunchKernelGGL(pg_twist_pbar, dim3((unsigned)((c->h_joff[R] + 3) / 4)), dim3(256), 0, c->stream, g);
+    CHK(launch_check(c, "pg_twist_pbar"));
+    if (g.tw.pair_hist)
+        for (int r = 0; r < R; ++r) {
+            const long rows_r = (long)(c->h_joff[r + 1] - c->h_joff[r]);
+            hipLaunchKernelGGL(pg_twist_pbar_ll, dim3(cdiv(rows_r, 64)), dim3(64), 0, c->stream, g, r);
+            CHK(launch_check(c, "pg_twist_pbar_ll"));
+            ++p.tw_launches;
+        }
+    for (int r = 0; r < R; ++r) {
+        const int Jr = (((N - r) * (N - r - 1)) / 2) * c->last_M;
+        const int KB = Jr >= 256 ? 1 : 256 / Jr;
+        const int nsl = Jr > 256 ? cdiv(Jr, 256) : 1;
+        hipLaunchKernelGGL(pg_twist_finish, dim3(cdiv(K, KB), nsl), dim3(256), 0, c->stream, g, r);
+        CHK(launch_check(c, "pg_twist_finish"));
+        ++p.tw_launches;
+        if (nsl > 1) {
+            hipLaunchKernelGGL(pg_twist_finish_sum, dim3(cdiv((long)K * PG_NODEG, 256)), dim3(256), 0, c->stream, g, r, nsl);
+            CHK(launch_check(c, "pg_twist_finish_sum"));
+            ++p.tw_launches;
+        }
+    }
+    p.tw_launches += 2;
+    return PHYLO_OK;
+}
+
+// 2. what does not need the integer lists is launched first: the GPU works while the host builds them (or waits for them)
+static int rev_early(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    const pg_args& g = p.g;
+    const size_t nn = (size_t)g.R * g.K;
     HIPCHK(c, hipEventRecord(c->evb0, c->stream));
-    const int nrk = cdiv((long)R * K, 256);
-    // a lazy sweep left marks: a node nobody adopted has no parents and alpha = omega, known without any list -- nearly all
-    // nodes, done while the lists are built
-    const bool early_free = rows_form && !twist && c->last_graph_marks;
-    // After a lazy sweep with the plain proposal the lists are built by kernels (phylo_revlists_dev.h) and the host waits for a few
-    // dozen integers; PHYLO_REV_HOST_LISTS keeps the host builders (the A/B switch, and what every other form uses).
-    // (never on a sharded context: the device lists are what gates the one-launch chains, pg_coeff_all / pg_nodes_rows_all, which
-    //  hand values between workgroups and assume nobody else on the GPU waits likewise -- sharded ranks sharing a GPU run their
-    //  passes at once; a sharded pass takes the host lists and a launch per rank event)
-    const bool dev_lists = early_free && !whole && !c->env.rev_host_lists && c->Kloc == K && K <= PG_DL_MAX_K;
     // The list kernels need the sweep's ancestors and children and nothing else: they are queued right behind the sweep on its own
     // stream, ahead of the early kernels below (they head the longest chain: lists -> sort -> chunk sums -> adopted nodes).
-    // (their sort goes to the second stream as soon as the host has seen the sweep end: queued there behind the lists' event, it
-    //  neither waits for the host to read the counts nor holds up the coefficient chain on this stream)
-    const bool sort_early = dev_lists && !c->env.grad_one_stream;
-    if (dev_lists) CHK(dev_lists_launch(c, c->stream, c->stream, true, false));
-    hipLaunchKernelGGL(pg_omega, dim3(R), dim3(PG_OMEGA_NT), 0, c->stream, g);
+    if (p.plan.dev_lists) CHK(dev_lists_launch(c, c->stream, c->stream, true, false));
+    hipLaunchKernelGGL(pg_omega, dim3(g.R), dim3(PG_OMEGA_NT), 0, c->stream, g);
     CHK(launch_check(c, "pg_omega"));
-    hipLaunchKernelGGL(pg_leafpi, dim3(N), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(pg_leafpi, dim3(g.N), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_leafpi"));
-    g.alpha_om = early_free ? 1 : 0;                       // a free parent then is a node nobody adopted: alpha = omega
-    // That launch is 85 us of throughput work nothing waits for before pg_node_finish, while everything else below is a chain of
-    // small dependent launches: it runs on a stream of the lowest priority, in the background of the chains.
-    // (Measured, K = 2048: reverse pass 0.539 -> 0.511 ms with all 898 sites; with 256 sites the launch is 25 us and the extra
-    //  events and the fill launch cost more than they hide, 0.440 -> 0.473 ms: large sweeps only.)
-    const bool bg_free = early_free && !c->env.grad_one_stream && (c->env.grad_two_streams || nn * (size_t)S >= ((size_t)12 << 20));
-    if (early_free) {
-        g.mark = c->d_mark;
-        if (bg_free) {
-            hipLaunchKernelGGL(pg_fill_free, dim3(nrk), dim3(256), 0, c->stream, g);
-            CHK(launch_check(c, "pg_fill_free"));
-            HIPCHK(c, hipEventRecord(c->ev_bgfork, c->stream));
-            // (its launch follows the wait for the sweep's end below: a second queue with a pending wait slows the sweep's own
-            //  dependent launches by half a microsecond each -- 19 us per sweep, measured)
-        } else {
-            hipLaunchKernelGGL(pg_nodes_free, dim3((unsigned)((nn + 3) / 4)), dim3(256), 0, c->stream, g, 0);
-            CHK(launch_check(c, "pg_nodes_free"));
-        }
-    }
-    int tw_launches = 0;
-    if (twist) {
-        const size_t J0 = (size_t)((N * (N - 1)) / 2) * c->last_M;
-        hipLaunchKernelGGL(pg_twist_tau, dim3(R * K), dim3(64), (J0 <= 8192 ? J0 : 8192) * 8, c->stream, g);   // later rank events have fewer rows and use LDS
-        CHK(launch_check(c, "pg_twist_tau"));
-        hipLaunchKernelGGL(pg_twist_pbar, dim3((unsigned)((c->h_joff[R] + 3) / 4)), dim3(256), 0, c->stream, g);
-        CHK(launch_check(c, "pg_twist_pbar"));
-        if (g.tw.pair_hist)
-            for (int r = 0; r < R; ++r) {
-                const long rows_r = (long)(c->h_joff[r + 1] - c->h_joff[r]);
-                hipLaunchKernelGGL(pg_twist_pbar_ll, dim3(cdiv(rows_r, 64)), dim3(64), 0, c->stream, g, r);
-                CHK(launch_check(c, "pg_twist_pbar_ll"));
-                ++tw_launches;
-            }
-        for (int r = 0; r < R; ++r) {
-            const int Jr = (((N - r) * (N - r - 1)) / 2) * c->last_M;
-            const int KB = Jr >= 256 ? 1 : 256 / Jr;
-            const int nsl = Jr > 256 ? cdiv(Jr, 256) : 1;
-            hipLaunchKernelGGL(pg_twist_finish, dim3(cdiv(K, KB), nsl), dim3(256), 0, c->stream, g, r);
-            CHK(launch_check(c, "pg_twist_finish"));
-            ++tw_launches;
-            if (nsl > 1) {
-                hipLaunchKernelGGL(pg_twist_finish_sum, dim3(cdiv((long)K * PG_NODEG, 256)), dim3(256), 0, c->stream, g, r, nsl);
-                CHK(launch_check(c, "pg_twist_finish_sum"));
-                ++tw_launches;
-            }
-        }
-        tw_launches += 2;
-    }
-    // ---- integer bookkeeping of the reverse pass: who adopted whom, and which nodes have which parents.  The sweep left the
-    //      ancestors and children in pinned host memory (asynchronous copies behind its last launch); the lists are built straight
-    //      into the pinned image of the device slab (ad_off | ad_idx | par_off | par_idx | heavy | chunk_beg | chunk_cnt).
-    CHK(wait_event_spin(c, c->ev_gcopy));
-    auto launch_bg_free = [&]() -> int {
-        HIPCHK(c, hipStreamWaitEvent(c->bgstream, c->ev_bgfork, 0));
-        hipLaunchKernelGGL(pg_nodes_free, dim3((unsigned)((nn + 3) / 4)), dim3(256), 0, c->bgstream, g, 3);
+    if (p.plan.bg_free) {                                  // pg_nodes_free in the background (rev_bg_free): here only what it waits for
+        hipLaunchKernelGGL(pg_fill_free, dim3(cdiv((long)nn, 256)), dim3(256), 0, c->stream, g);
+        CHK(launch_check(c, "pg_fill_free"));
+        HIPCHK(c, hipEventRecord(c->ev_bgfork, c->stream));
+        // (its launch follows the wait for the sweep's end: a second queue with a pending wait slows the sweep's own
+        //  dependent launches by half a microsecond each -- 19 us per sweep, measured)
+    } else if (p.plan.early_free) {
+        hipLaunchKernelGGL(pg_nodes_free, dim3((unsigned)((nn + 3) / 4)), dim3(256), 0, c->stream, g, 0);
         CHK(launch_check(c, "pg_nodes_free"));
-        HIPCHK(c, hipEventRecord(c->ev_bgdone, c->bgstream));
-        return PHYLO_OK;
-    };
-    dl_meta dm;
-    if (bg_free && !dev_lists) CHK(launch_bg_free());
-    const auto host_t0 = std::chrono::steady_clock::now();
-    const int64_t* anc = c->h_anc_p;
-    const int32_t* child = c->h_child_p;
-    const pg_lists L = pg_lists_carve(c->h_csr_p, (size_t)R, (size_t)K);     // (phylo_revlists.h: the builders, tested on the CPU)
-    int32_t* const ad_off = L.ad_off;
-    int32_t* const par_off = L.par_off;
-    int32_t* const heavy = L.heavy;
-    int32_t* const slow_flag = L.slow_flag;
-    int32_t* const adp = L.adp;
-    const size_t cap = L.cap;
-    if (!dev_lists) pg_lists_clear(L, R, K);
-    std::vector<int32_t>& cur = c->h_cur;
-    // Two chains of small dependent launches remain, both newest rank event first: the coefficients (on the context's stream) and
-    // the adopted nodes' adjoints, which need the coefficients of their own and of later rank events only (ev_coeff[r]), on a
-    // second stream.  After the early pg_nodes_free the parents' lists are built FIRST (they need of the adopters only who was
-    // adopted: pg_mark_adopted), so that the one launch over all heavy nodes' free parents runs while the host sorts the adopters
-    // and beside the coefficient chain; the adopted nodes' chain then follows the coefficients one rank event behind.
-    // (Without that reordering and for small sweeps two streams gain nothing -- the host finishes the parents' lists only when the
-    //  coefficient chain is over -- and the events cost 13 us: primate.p, K = 2048, 0.542 against 0.555 ms; DS1, K = 4096: 2.48 -> 2.16.)
-    // (Measured, K = 2048: reverse pass 0.522 -> 0.476 ms with all 898 sites, 0.455 -> 0.466 with 256: large sweeps only, like the
-    //  background launch.)
-    const bool reorder = bg_free;
-    const bool two = !c->env.grad_one_stream && (c->env.grad_two_streams || nn >= 65536 || reorder || dev_lists);
-    hipStream_t sB = two ? c->gstream : c->stream;
+    }
+    if (p.plan.twist) CHK(rev_early_twist(p));
+    return PHYLO_OK;
+}
+
+// the background launch: every node nobody adopted, on the stream of the lowest priority
+static int rev_bg_free(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    const size_t nn = (size_t)p.g.R * p.g.K;
+    HIPCHK(c, hipStreamWaitEvent(c->bgstream, c->ev_bgfork, 0));
+    hipLaunchKernelGGL(pg_nodes_free, dim3((unsigned)((nn + 3) / 4)), dim3(256), 0, c->bgstream, p.g, 3);
+    CHK(launch_check(c, "pg_nodes_free"));
+    HIPCHK(c, hipEventRecord(c->ev_bgdone, c->bgstream));
+    return PHYLO_OK;
+}
+
+// 3. the host has seen the sweep end: the background launch, the early sort, the fork of the second stream.
+// ---- integer bookkeeping of the reverse pass: who adopted whom, and which nodes have which parents.  The sweep left the
+//      ancestors and children in pinned host memory (asynchronous copies behind its last launch); the lists are built straight
+//      into the pinned image of the device slab (ad_off | ad_idx | par_off | par_idx | heavy | chunk_beg | chunk_cnt).
+static int rev_fork(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    const int R = p.g.R, K = p.g.K;
+    CHK(wait_event_spin(c, c->ev_gcopy));
+    if (p.plan.bg_free && !p.plan.dev_lists) CHK(rev_bg_free(p));
+    p.host_t0 = std::chrono::steady_clock::now();
+    p.L = pg_lists_carve(c->h_csr_p, (size_t)R, (size_t)K);     // (phylo_revlists.h: the builders, tested on the CPU)
+    if (!p.plan.dev_lists) pg_lists_clear(p.L, R, K);
+    p.sB = p.plan.two ? c->gstream : c->stream;
     // (the host has seen the sweep end: the second stream needs no event to start on its outputs, and the list kernels run
     //  beside the early kernels)
-    if (dev_lists) {
+    if (p.plan.sort_early) {
         // (the list kernels run on the context's stream, ahead of the coefficient chain)
-        if (sort_early) {
-            HIPCHK(c, hipStreamWaitEvent(c->gstream, c->ev_dl, 0));
-            CHK(dev_lists_launch(c, c->gstream, c->gstream, false, true));
-        }
-        // the list kernels are workgroups of 1024 threads that everything else waits for: on a GPU that the background launch has
-        // filled they wait for a whole free CU each, kernel after kernel (lists ready after 120 us instead of 55): the background
-        // launch starts behind them.  (Measured, primate.p K = 2048 / DS1 K = 4096, reverse pass: background launch first 0.504 /
-        //  1.634 ms, behind the lists 0.486 / 1.653, behind the parents' sort 0.510 / 1.746; a high-priority second stream
-        //  changes nothing.)
-        if (bg_free) {
-            HIPCHK(c, hipStreamWaitEvent(c->bgstream, c->ev_dl, 0));
-            CHK(launch_bg_free());
-        }
+        HIPCHK(c, hipStreamWaitEvent(c->gstream, c->ev_dl, 0));
+        CHK(dev_lists_launch(c, c->gstream, c->gstream, false, true));
     }
-    if (two) {
+    // the list kernels are workgroups of 1024 threads that everything else waits for: on a GPU that the background launch has
+    // filled they wait for a whole free CU each, kernel after kernel (lists ready after 120 us instead of 55): the background
+    // launch starts behind them.  (Measured, primate.p K = 2048 / DS1 K = 4096, reverse pass: background launch first 0.504 /
+    //  1.634 ms, behind the lists 0.486 / 1.653, behind the parents' sort 0.510 / 1.746; a high-priority second stream
+    //  changes nothing.)
+    if (p.plan.bg_free && p.plan.dev_lists) {
+        HIPCHK(c, hipStreamWaitEvent(c->bgstream, c->ev_dl, 0));
+        CHK(rev_bg_free(p));
+    }
+    if (p.plan.two) {
         HIPCHK(c, hipEventRecord(c->ev_gfork, c->stream));                 // everything launched so far (the early kernels)
-        HIPCHK(c, hipStreamWaitEvent(sB, c->ev_gfork, 0));
+        HIPCHK(c, hipStreamWaitEvent(p.sB, c->ev_gfork, 0));
     }
-    std::vector<int32_t> rank_chunk0, ev_slow0;
-    pg_parents_info pinfo{};
-    size_t max_chunks = 0, n_chunks = 0;
-    if (early_free && !dev_lists) pg_mark_adopted(R, K, anc, L);
-    // the adopted nodes' chain as ONE launch (pg_nodes_rows_all; the plain proposal with the lists built on the device): the
-    // coefficient chain -- then the longest chain of the pass -- is issued first and in one go, the parents' sort and the chunk sums
-    // behind it, and the one launch waits for the last coefficients
-    bool rows_all = false, rows_overlap = false;
-    auto launch_chunks = [&]() -> int {
-        // The parents of a heavy node are nearly all nodes nobody merged again: their share of the node's adjoint needs their
-        // alpha = omega and nothing else.  ONE launch sums
-        // them for the chunks of all rank events; the chain below is then pg_nodes_rows alone, which adds the flagged parents.
-        const size_t rowlen = (size_t)S * 4;
-        for (size_t cbeg = 0; cbeg < n_chunks; cbeg += 65535) {
-            const size_t cn = n_chunks - cbeg < 65535 ? n_chunks - cbeg : 65535;
-            pg_args g2 = g;
-            g2.cpart = g.cpart + cbeg * rowlen;
-            hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(S, 64), (unsigned)cn), dim3(256), 0, sB, g2, (int)cbeg);
-            CHK(launch_check(c, "pg_parent_chunks_rows"));
-        }
-        return PHYLO_OK;
-    };
-    auto parents_block = [&]() -> int {
-    // ---- parents, heavy nodes' chunks, flagged nodes by rank event (pg_build_parents, or what pg_dl_lists reports)
-    if (dev_lists) {
-        CHK(dev_lists_wait(c, dm));
-        ev_slow0 = dm.ev_slow0;
-        pinfo.n_chunks = (size_t)dm.n_chunks; pinfo.max_chunks = 0; pinfo.n_slow = dm.n_slow; pinfo.n_par = dm.n_par;
-    } else {
-        pinfo = pg_build_parents(N, R, K, child, rows_form, early_free, L, cur, rank_chunk0, ev_slow0);
+    if (p.plan.early_free && !p.plan.dev_lists) pg_mark_adopted(R, K, c->h_anc_p, p.L);
+    return PHYLO_OK;
+}
+
+// The parents' sort when it was not queued early, then the chunk sums.  The parents of a heavy node are nearly all nodes nobody
+// merged again: their share of the node's adjoint needs their alpha = omega and nothing else.  ONE launch sums them for the chunks
+// of all rank events; the chain is then pg_nodes_rows alone, which adds the flagged parents.
+static int rev_sort_and_chunk_sums(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    const pg_args& g = p.g;
+    if (p.plan.dev_lists && !p.plan.sort_early) CHK(dev_lists_launch(c, p.sB, p.sB, false, true));   // (the host has seen the list kernels end)
+    if (!p.plan.early_free) return PHYLO_OK;               // (else: a rank event's chunks at a time, in the chain)
+    const size_t rowlen = (size_t)g.S * 4;
+    for (size_t cbeg = 0; cbeg < p.n.n_chunks; cbeg += 65535) {
+        const size_t cn = p.n.n_chunks - cbeg < 65535 ? p.n.n_chunks - cbeg : 65535;
+        pg_args g2 = g;
+        g2.cpart = g.cpart + cbeg * rowlen;
+        hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(g.S, 64), (unsigned)cn), dim3(256), 0, p.sB, g2, (int)cbeg);
+        CHK(launch_check(c, "pg_parent_chunks_rows"));
     }
-    max_chunks = pinfo.max_chunks; n_chunks = pinfo.n_chunks;
-    {
-        const int32_t ns = pinfo.n_slow;
-        void* cpart = nullptr;
-        // rows form: the chunk sums of ALL rank events are produced by one launch (free parents only: nothing of the chain is
-        // needed for them), so the buffer holds every chunk; else one rank event's at a time
-        CHK(scratch_get(c, 5, (early_free ? n_chunks : max_chunks) * (size_t)S * 4 * 8, &cpart));
-        g.cpart = (double*)cpart;
-        g.chunks_free_only = early_free ? 1 : 0;
-        g.TS = cdiv(S, 256);
-        {
-            void* fp = nullptr;
-            CHK(scratch_get(c, 2, ((nn + 31) / 32) * 20 * 8, &fp));
-            g.fin_part = (double*)fp;
-        }
-        if (rows_form) {
-            void* sp = nullptr;
-            CHK(scratch_get(c, 3, (size_t)(ns ? ns : 1) * g.TS * PG_PART * 8, &sp));
-            g.slowpart = (double*)sp;
-        }
+    return PHYLO_OK;
+}
+
+// (4.) pg_nodes_rows_all's completion words, one epoch per pass, and what it needs to follow pg_coeff_all
+static int rev_row_words(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    pg_args& g = p.g;
+    const int R = g.R, K = g.K;
+    const size_t row_words = (size_t)R * K * (size_t)cdiv(c->S, 256);
+    if (!c->d_row_done) {
+        const size_t words = row_words + 2 * (size_t)R;      // + coeff_done[R] | coeff_ticket[R]
+        CHK(dalloc(c, &c->d_row_done, words));
+        HIPCHK(c, hipMemsetAsync(c->d_row_done, 0, words * 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));     // (once per context: ahead of every launch, on any stream, that touches them)
+        c->row_epoch = 0;
     }
-    if (!dev_lists) {   // what was used of everything between the adopters' lists and the adopted particles, by a kernel (pg_copy_words)
+    if (++c->row_epoch == 0) ++c->row_epoch;             // (0 is what the words hold before their first pass)
+    g.row_done = c->d_row_done;
+    g.row_epoch = c->row_epoch;
+    g.row_timeout = (unsigned int*)(c->hd_dlmeta + PG_DL_META_INTS(R));
+    g.coeff_done = c->d_row_done + row_words;
+    g.coeff_ticket = g.coeff_done + R;
+    g.coeff_mask = 0ull;
+    for (int r = 0; r + 1 < R; ++r)
+        if (p.n.ev_adp0[r + 1] > p.n.ev_adp0[r]) g.coeff_mask |= 1ull << r;
+    return PHYLO_OK;
+}
+
+// workgroups of the coefficient chain's launches together (the adopted particles of every rank event but the last)
+static long rev_coeff_wgs(const rev_pass& p) {
+    long wgs = 0;
+    for (int r = p.g.R - 2; r >= 0; --r) wgs += (long)(p.n.ev_adp0[r + 1] - p.n.ev_adp0[r]) * cdiv(p.g.N - r - 1, 4);
+    return wgs;
+}
+
+// 4. parents, heavy nodes' chunks, flagged nodes by rank event (pg_build_parents, or what pg_dl_lists reports); with the counts the
+//    second half of the plan.  Runs ahead of the adopters' stage (plan.parents_first) or behind the look-ahead lists.
+static int rev_parents(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    pg_args& g = p.g;
+    const int N = g.N, K = g.K, S = g.S, R = g.R;
+    const size_t nn = (size_t)R * K;
+    if (p.plan.dev_lists) CHK(dev_lists_wait(c, p.n));
+    else pg_build_parents(N, R, K, c->h_child_p, p.plan.rows_form, p.plan.early_free, p.L, c->h_cur, p.n);
+    void* cpart = nullptr;
+    // rows form: the chunk sums of ALL rank events are produced by one launch (free parents only: nothing of the chain is
+    // needed for them), so the buffer holds every chunk; else one rank event's at a time
+    CHK(scratch_get(c, 5, (p.plan.early_free ? p.n.n_chunks : p.n.max_chunks) * (size_t)S * 4 * 8, &cpart));
+    g.cpart = (double*)cpart;
+    g.chunks_free_only = p.plan.early_free ? 1 : 0;
+    g.TS = cdiv(S, 256);
+    void* fp = nullptr;
+    CHK(scratch_get(c, 2, ((nn + 31) / 32) * 20 * 8, &fp));
+    g.fin_part = (double*)fp;
+    if (p.plan.rows_form) {
+        void* sp = nullptr;
+        CHK(scratch_get(c, 3, (size_t)(p.n.n_slow ? p.n.n_slow : 1) * g.TS * PG_PART * 8, &sp));
+        g.slowpart = (double*)sp;
+    }
+    if (!p.plan.dev_lists) {   // what was used of everything between the adopters' lists and the adopted particles, by a kernel (pg_copy_words)
+        const pg_lists& L = p.L;
         pg_copy3 cp{};
-        const size_t o0 = (size_t)(par_off - ad_off), o1 = (size_t)(heavy - ad_off), o2 = (size_t)(slow_flag - ad_off);
-        cp.src[0] = c->hd_csr + o0; cp.dst[0] = (uint32_t*)(c->d_ad_off + o0); cp.n[0] = nn + 1 + (size_t)par_off[nn];   // par_off | par_idx
-        cp.src[1] = c->hd_csr + o1; cp.dst[1] = (uint32_t*)(c->d_ad_off + o1); cp.n[1] = nn + cap + n_chunks;            // heavy | chunk_beg | chunk_cnt
-        cp.src[2] = c->hd_csr + o2; cp.dst[2] = (uint32_t*)(c->d_ad_off + o2); cp.n[2] = nn + (size_t)ev_slow0[R];       // slow_flag | slow_idx
+        const size_t o0 = (size_t)(L.par_off - L.ad_off), o1 = (size_t)(L.heavy - L.ad_off), o2 = (size_t)(L.slow_flag - L.ad_off);
+        cp.src[0] = c->hd_csr + o0; cp.dst[0] = (uint32_t*)(c->d_ad_off + o0); cp.n[0] = nn + 1 + (size_t)L.par_off[nn];   // par_off | par_idx
+        cp.src[1] = c->hd_csr + o1; cp.dst[1] = (uint32_t*)(c->d_ad_off + o1); cp.n[1] = nn + L.cap + p.n.n_chunks;        // heavy | chunk_beg | chunk_cnt
+        cp.src[2] = c->hd_csr + o2; cp.dst[2] = (uint32_t*)(c->d_ad_off + o2); cp.n[2] = nn + (size_t)p.n.ev_slow0[R];     // slow_flag | slow_idx
         const size_t words = cp.n[0] + cp.n[1] + cp.n[2];
-        hipLaunchKernelGGL(pg_copy_words, dim3((unsigned)(words / 1024 < 1 ? 1 : (words / 1024 > 1024 ? 1024 : words / 1024))), dim3(256), 0, sB, cp);
+        hipLaunchKernelGGL(pg_copy_words, dim3((unsigned)(words / 1024 < 1 ? 1 : (words / 1024 > 1024 ? 1024 : words / 1024))), dim3(256), 0, p.sB, cp);
         CHK(launch_check(c, "pg_copy_words"));
-        if (two) HIPCHK(c, hipEventRecord(c->ev_gup, sB));
+        if (p.plan.two) HIPCHK(c, hipEventRecord(c->ev_gup, p.sB));
     }
-    rows_all = rows_form && early_free && dev_lists && two && !c->env.grad_rows_chain && pinfo.n_slow > 0 &&
-               (size_t)pinfo.n_slow * (size_t)g.TS <= 16384;
-    if (rows_all) {
-        if (!c->d_row_done) {
-            const size_t words = (size_t)R * K * (size_t)cdiv(c->S, 256) + 2 * (size_t)R;   // + coeff_done[R] | coeff_ticket[R]
-            CHK(dalloc(c, &c->d_row_done, words));
-            HIPCHK(c, hipMemsetAsync(c->d_row_done, 0, words * 4, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));     // (once per context: ahead of every launch, on any stream, that touches them)
-            c->row_epoch = 0;
-        }
-        if (++c->row_epoch == 0) ++c->row_epoch;             // (0 is what the words hold before their first pass)
-        g.row_done = c->d_row_done;
-        g.row_epoch = c->row_epoch;
-        g.row_timeout = (unsigned int*)(c->hd_dlmeta + PG_DL_META_INTS(R));
-        // few enough workgroups to leave the coefficient chain room on every SIMD: the launch runs BESIDE that chain and waits, rank
-        // event by rank event, for its completion words; else it is launched behind the chain's last event
-        rows_overlap = (size_t)pinfo.n_slow * (size_t)g.TS <= 512 && g_backward_in_flight.load() <= 1;
-        g.coeff_done = c->d_row_done + (size_t)R * K * (size_t)cdiv(c->S, 256);
-        g.coeff_ticket = g.coeff_done + R;
-        g.coeff_mask = 0ull;
-        for (int r = 0; r + 1 < R; ++r)
-            if (dm.ev_adp0[r + 1] > dm.ev_adp0[r]) g.coeff_mask |= 1ull << r;
+    // (the adopters' counts are there with the device's lists only; no form without them takes pg_coeff_all)
+    pg_plan_chains(p.plan, p.n.n_slow, g.TS, p.plan.dev_lists ? rev_coeff_wgs(p) : 0, g_backward_in_flight.load(), R);
+    if (p.plan.rows_all) CHK(rev_row_words(p));
+    if (p.plan.chunks_first) CHK(rev_sort_and_chunk_sums(p));
+    return PHYLO_OK;
+}
+
+// 5. the adopters' lists, their upload, pg_G
+static int rev_adopters(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    pg_args& g = p.g;
+    const int K = g.K, R = g.R;
+    if (!p.plan.dev_lists) {
+        pg_build_adopters(R, K, c->h_anc_p, p.L, c->h_cur, p.n);
+        // the adopters' lists are all the coefficient chain needs: it runs while the host goes on with the parents' lists
+        const size_t ad_ints = (size_t)R * (K + 1) + (size_t)R * K;
+        HIPCHK(c, hipMemcpyAsync(c->d_ad_off, c->h_csr_p, ad_ints * 4, hipMemcpyHostToDevice, c->stream));
     }
-    // (the launch behind the coefficient chain: that chain is the longer one and is issued first; the launch beside it: the sort and
-    //  the chunk sums first, so that the adopted nodes follow the coefficients rank event by rank event)
-    const bool q3_first = !rows_all || rows_overlap;
-    if (dev_lists && q3_first && !sort_early) CHK(dev_lists_launch(c, sB, sB, false, true));   // the parents' sort (the host has seen the list kernels end)
-    if (early_free && n_chunks > 0 && q3_first) CHK(launch_chunks());
-        return PHYLO_OK;
-    };
-    if (reorder || dev_lists) CHK(parents_block());
-    std::vector<int32_t> ev_adp0;                          // adopted particles of rank event r: adp[ev_adp0[r] .. ev_adp0[r + 1])
-    int32_t n_adp = 0;
-    if (dev_lists) { ev_adp0 = dm.ev_adp0; n_adp = dm.n_adp; }
-    else n_adp = pg_build_adopters(R, K, anc, L, cur, ev_adp0);
-    // the adopters' lists are all the coefficient chain needs: it runs while the host goes on with the parents' lists.  When the
-    // early pg_nodes_free has dealt with everybody nobody adopted, the chain runs over the adopted particles alone.
-    const size_t ad_ints = (size_t)R * (K + 1) + nn;
-    // With the parents' lists already there, the two chains are launched in turn, a rank event of each: the host needs ~3 us per
-    // call, and the adopted nodes' chain queued behind all the coefficient launches would start ~70 us late.
-    const bool interleave = early_free && two && (reorder || dev_lists) && !rows_all;
-    auto launch_coeff = [&](int r) -> int {
-        const int na = ev_adp0[r + 1] - ev_adp0[r];
-        if (na > 0) {
-            hipLaunchKernelGGL(pg_coeff, dim3(na, cdiv(N - r - 1, 4)), dim3(256), 0, c->stream, g, r, (int)ev_adp0[r]);
-            CHK(launch_check(c, "pg_coeff"));
+    if (!p.plan.early_free) {
+        hipLaunchKernelGGL(pg_G, dim3(R * K), dim3(64), 0, c->stream, g);
+        return launch_check(c, "pg_G");
+    }
+    // When the early pg_nodes_free has dealt with everybody nobody adopted, pg_G and the chain run over the adopted particles alone.
+    const int32_t n_adp = p.n.n_adp;
+    if (!p.plan.dev_lists) HIPCHK(c, hipMemcpyAsync(c->d_adp, p.L.adp, (size_t)(n_adp ? n_adp : 1) * 4, hipMemcpyHostToDevice, c->stream));
+    g.adp = c->d_adp;
+    if (n_adp > 0) {
+        hipLaunchKernelGGL(pg_G, dim3(n_adp), dim3(64), 0, c->stream, g);
+        CHK(launch_check(c, "pg_G"));
+    }
+    if (p.plan.two) HIPCHK(c, hipEventRecord(c->ev_coeff[R - 1], c->stream));   // (the last rank event has no adopters: C is there)
+    return PHYLO_OK;
+}
+
+// the coefficients of rank event r: over its adopted particles after the early pg_nodes_free, else over all K
+static int rev_coeff(rev_pass& p, int r) {
+    phylo_ctx* c = p.c;
+    const int na = p.plan.early_free ? p.n.ev_adp0[r + 1] - p.n.ev_adp0[r] : p.g.K;
+    if (na > 0) {
+        hipLaunchKernelGGL(pg_coeff, dim3(na, cdiv(p.g.N - r - 1, 4)), dim3(256), 0, c->stream, p.g, r, p.plan.early_free ? (int)p.n.ev_adp0[r] : 0);
+        CHK(launch_check(c, "pg_coeff"));
+    }
+    if (p.plan.two) HIPCHK(c, hipEventRecord(c->ev_coeff[r], c->stream));
+    return PHYLO_OK;
+}
+
+static int rev_leafterm(rev_pass& p) {
+    hipLaunchKernelGGL(pg_leafterm, dim3(cdiv(p.g.K, 256)), dim3(256), 0, p.c->stream, p.g);
+    return launch_check(p.c, "pg_leafterm");
+}
+
+// 6. the coefficient chain, newest rank event first: one launch, a launch per rank event, or -- interleaved -- left to the node chain
+static int rev_coeff_chain(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    const pg_args& g = p.g;
+    const int N = g.N, R = g.R;
+    if (p.plan.coeff_all) {
+        pg_coeff_plan pl{};
+        int at = 0;
+        for (int r = R - 2; r >= 0; --r) {
+            pl.first[r] = at; pl.adp0[r] = p.n.ev_adp0[r]; pl.ny[r] = cdiv(N - r - 1, 4);
+            at += (p.n.ev_adp0[r + 1] - p.n.ev_adp0[r]) * pl.ny[r];
         }
-        if (two) HIPCHK(c, hipEventRecord(c->ev_coeff[r], c->stream));
-        return PHYLO_OK;
-    };
-    if (!dev_lists) HIPCHK(c, hipMemcpyAsync(c->d_ad_off, c->h_csr_p, ad_ints * 4, hipMemcpyHostToDevice, c->stream));
-    if (early_free) {
-        if (!dev_lists) HIPCHK(c, hipMemcpyAsync(c->d_adp, adp, (size_t)(n_adp ? n_adp : 1) * 4, hipMemcpyHostToDevice, c->stream));
-        g.adp = c->d_adp;
-        if (n_adp > 0) {
-            hipLaunchKernelGGL(pg_G, dim3(n_adp), dim3(64), 0, c->stream, g);
-            CHK(launch_check(c, "pg_G"));
-        }
-        if (two) HIPCHK(c, hipEventRecord(c->ev_coeff[R - 1], c->stream));   // (the last rank event has no adopters: C is there)
-        // with the adopted nodes in one launch, the coefficient chain is one launch too (pg_coeff_all) when all of its workgroups
-        // can be resident
-        long coeff_wgs = 0;
-        for (int r = R - 2; r >= 0; --r) coeff_wgs += (long)(ev_adp0[r + 1] - ev_adp0[r]) * cdiv(N - r - 1, 4);
-        if (rows_all && R - 1 <= 64 && coeff_wgs > 0 && coeff_wgs <= 2048 && !c->env.grad_coeff_chain) {
-            pg_coeff_plan pl{};
-            int at = 0;
-            for (int r = R - 2; r >= 0; --r) {
-                pl.first[r] = at; pl.adp0[r] = ev_adp0[r]; pl.ny[r] = cdiv(N - r - 1, 4);
-                at += (ev_adp0[r + 1] - ev_adp0[r]) * pl.ny[r];
-            }
-            hipLaunchKernelGGL(pg_coeff_all, dim3((unsigned)at), dim3(256), 0, c->stream, g, pl);
-            CHK(launch_check(c, "pg_coeff_all"));
-            if (two) HIPCHK(c, hipEventRecord(c->ev_coeff[0], c->stream));
-        } else if (!interleave) {
-            for (int r = R - 2; r >= 0; --r) CHK(launch_coeff(r));
+        hipLaunchKernelGGL(pg_coeff_all, dim3((unsigned)at), dim3(256), 0, c->stream, g, pl);
+        CHK(launch_check(c, "pg_coeff_all"));
+        if (p.plan.two) HIPCHK(c, hipEventRecord(c->ev_coeff[0], c->stream));
+    } else if (!p.plan.interleave) {
+        // (after the early pg_nodes_free the last rank event has no adopters: rev_adopters has recorded its event)
+        for (int r = p.plan.early_free ? R - 2 : R - 1; r >= 0; --r) CHK(rev_coeff(p, r));
+    }
+    if (!p.plan.interleave) CHK(rev_leafterm(p));
+    return PHYLO_OK;
+}
+
+// 7. twisted proposal: the look-ahead lists (pg_build_lookahead), all rank events in one upload
+static int rev_lookahead(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    pg_args& g = p.g;
+    if (!p.plan.twist) return PHYLO_OK;
+    std::vector<int32_t>& pk = c->h_xlists;
+    pg_build_lookahead(g.N, g.K, g.S, PG_XCH, c->h_rad_p, p.L.slow_flag, pk, p.x);   // (h_rad_p: pinned copy made when the sweep ended)
+    void *d_xlists = nullptr, *d_tpart = nullptr;
+    CHK(scratch_get(c, 6, pk.size() * 4, &d_xlists));
+    HIPCHK(c, hipMemcpyAsync(d_xlists, pk.data(), pk.size() * 4, hipMemcpyHostToDevice, p.sB));
+    CHK(scratch_get(c, 7, p.x.max_chunks * (size_t)g.S * 4 * 8, &d_tpart));
+    const int32_t* xl = (const int32_t*)d_xlists;
+    g.tw.xent = xl; xl += p.x.n_xent;
+    g.tw.xchunk_node = xl; xl += p.x.n_xchunks;
+    g.tw.xchunk_beg = xl; xl += p.x.n_xchunks;
+    g.tw.xchunk_cnt = xl; xl += p.x.n_xchunks;
+    g.tw.xchunk_part = xl; xl += p.x.n_xchunks;
+    g.tw.xnode_id = xl; xl += p.x.n_xnodes;
+    g.tw.xnode_chunk0 = xl; xl += p.x.n_xnodes;
+    g.tw.xnode_nchunks = xl;
+    g.tw.tpart = (double*)d_tpart;
+    return PHYLO_OK;
+}
+
+// one rank event of the adopted nodes' chain: look-ahead entries, chunk sums (when not summed in one launch), the nodes
+static int rev_nodes_of(rev_pass& p, int r) {
+    phylo_ctx* c = p.c;
+    const pg_args& g = p.g;
+    const pg_list_counts& n = p.n;
+    if (p.plan.twist && p.x.ev_chunk0[r + 1] > p.x.ev_chunk0[r]) {
+        const int32_t ch0 = p.x.ev_chunk0[r], nd0 = p.x.ev_node0[r];
+        hipLaunchKernelGGL(pg_twist_xchunks, dim3(p.x.ev_chunk0[r + 1] - ch0, cdiv(g.S, 256)), dim3(256), 0, p.sB, g, r, (int)ch0);
+        CHK(launch_check(c, "pg_twist_xchunks"));
+        hipLaunchKernelGGL(pg_twist_xsum, dim3(p.x.ev_node0[r + 1] - nd0, cdiv((long)g.S * 4, 256)), dim3(256), 0, p.sB, g, (int)nd0, (int)ch0);
+        CHK(launch_check(c, "pg_twist_xsum"));
+        p.tw_launches += 2;
+    }
+    const int nch = p.plan.early_free ? 0 : n.rank_chunk0[r + 1] - n.rank_chunk0[r];   // (after the early pg_nodes_free: summed already, all rank events at once)
+    if (nch > 0) {
+        hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(g.S, 64), nch), dim3(256), 0, p.sB, g, (int)n.rank_chunk0[r]);
+        CHK(launch_check(c, "pg_parent_chunks_rows"));
+        ++p.node_launches;
+    }
+    if (p.plan.rows_form) {
+        const int nslow = n.ev_slow0[r + 1] - n.ev_slow0[r];
+        if (nslow > 0) {
+            hipLaunchKernelGGL(pg_nodes_rows, dim3(nslow, g.TS), dim3(256), 0, p.sB, g, r, (int)n.ev_slow0[r],
+                               p.plan.early_free ? (int)n.rank_chunk0[r] : 0);   // (device-built lists: heavy[] is the global chunk index, rank_chunk0 zero)
+            ++p.node_launches;
         }
     } else {
-        hipLaunchKernelGGL(pg_G, dim3(R * K), dim3(64), 0, c->stream, g);
-        CHK(launch_check(c, "pg_G"));
-        for (int r = R - 1; r >= 0; --r) {
-            hipLaunchKernelGGL(pg_coeff, dim3(K, cdiv(N - r - 1, 4)), dim3(256), 0, c->stream, g, r, 0);
-            CHK(launch_check(c, "pg_coeff"));
-            if (two) HIPCHK(c, hipEventRecord(c->ev_coeff[r], c->stream));
-        }
+        hipLaunchKernelGGL(pg_nodes, dim3(g.T, g.K), dim3(256), 0, p.sB, g, r);
+        ++p.node_launches;
     }
-    if (!interleave) {
-        hipLaunchKernelGGL(pg_leafterm, dim3(cdiv(K, 256)), dim3(256), 0, c->stream, g);
-        CHK(launch_check(c, "pg_leafterm"));
-    }
-    // twisted proposal: the look-ahead merges of rank event r touch every internal node among the adopted roots.  Entries
-    // (adopter, slot) grouped by node (ascending adopter), cut into chunks of PG_XCH; lists for all rank events in one upload.
-    std::vector<int32_t> ev_chunk0((size_t)R + 1, 0), ev_node0((size_t)R + 1, 0);
-    size_t tw_max_chunks = 0;
-    void *d_xlists = nullptr, *d_tpart = nullptr;
-    size_t n_xent = 0, n_xchunks = 0, n_xnodes = 0;
-    if (twist) {
-        const int32_t* rad = c->h_rad_p;                            // pinned copy made when the sweep ended
-        std::vector<int32_t> xent, xc_node, xc_beg, xc_cnt, xc_part, xn_id, xn_c0, xn_nc;
-        std::vector<int32_t> cnt, first;
-        for (int r = 0; r < R; ++r) {
-            ev_chunk0[r] = (int32_t)xc_node.size();
-            ev_node0[r] = (int32_t)xn_id.size();
-            if (r == 0) continue;                                   // rank event 0 adopts leaves only
-            const int n = N - r;
-            const size_t nn_r = (size_t)r * K;                      // nodes that exist before rank event r
-            cnt.assign(nn_r + 1, 0);
-            const int32_t* tab = rad + (size_t)r * K * N;
-            for (int k = 0; k < K; ++k)
-                for (int i = 0; i < n; ++i) {
-                    const int x = tab[(size_t)k * N + i];
-                    if (x >= N) ++cnt[(size_t)(x - N) + 1];
-                }
-            for (size_t i = 0; i < nn_r; ++i) cnt[i + 1] += cnt[i];
-            const size_t base = xent.size();
-            xent.resize(base + (size_t)cnt[nn_r]);
-            first.assign(cnt.begin(), cnt.end() - 1);
-            for (int k = 0; k < K; ++k)
-                for (int i = 0; i < n; ++i) {
-                    const int x = tab[(size_t)k * N + i];
-                    if (x >= N) xent[base + (size_t)first[x - N]++] = k * N + i;
-                }
-            // chunk shape of this rank event: enough workgroups to fill the GPU, not more rows than pg_twist_xsum should add per node.
-            // Many entries (large K): up to PG_XCH entries per chunk, all partner slots.  Few entries (the K = 32..64 of the
-            // reference's experiments): one entry per chunk and the n - 1 partner slots cut into slices, or a chunk is one thread's
-            // walk over (n - 1) M merges per site, a few hundred microseconds with M = 10.
-            const long total_ent = cnt[nn_r];
-            const long target = 2048 / cdiv(S, 256) > 64 ? 2048 / cdiv(S, 256) : 64;
-            int xch = (int)((total_ent + target - 1) / target);
-            xch = xch < 1 ? 1 : (xch > PG_XCH ? PG_XCH : xch);
-            int slices = 1;
-            if (xch == 1 && total_ent > 0) {
-                slices = (int)(target / total_ent);
-                slices = slices < 1 ? 1 : (slices > n ? n : slices);
-            }
-            const int pw = (n + slices - 1) / slices;              // partner slots per slice
-            for (size_t x = 0; x < nn_r; ++x) {
-                const int m = cnt[x + 1] - cnt[x];
-                if (m == 0) continue;
-                xn_id.push_back((int32_t)(x + N));
-                xn_c0.push_back((int32_t)xc_node.size());
-                int nc = 0;
-                for (int b = 0; b < m; b += xch)
-                    for (int p0 = 0; p0 < n; p0 += pw) {
-                        xc_node.push_back((int32_t)(x + N));
-                        xc_beg.push_back((int32_t)(base + cnt[x] + b));
-                        xc_cnt.push_back(m - b < xch ? m - b : xch);
-                        xc_part.push_back(p0 | ((p0 + pw < n ? p0 + pw : n) << 16));
-                        ++nc;
-                    }
-                xn_nc.push_back(nc);
-            }
-            const size_t nch = xc_node.size() - (size_t)ev_chunk0[r];
-            if (nch > tw_max_chunks) tw_max_chunks = nch;
-        }
-        ev_chunk0[R] = (int32_t)xc_node.size();
-        ev_node0[R] = (int32_t)xn_id.size();
-        n_xent = xent.size(); n_xchunks = xc_node.size(); n_xnodes = xn_id.size();
-        // the newest rank event that touches a node is launched first: its pg_twist_xsum starts the node's adjoint row (bit 30)
-        // instead of adding to it, so nothing has to be cleared; such a node goes through pg_nodes_rows (flag bit 1)
-        for (size_t i = n_xnodes; i-- > 0;) {
-            int32_t& f = slow_flag[xn_id[i] - N];
-            if (!(f & 2)) { f |= 2; xn_nc[i] |= 1 << 30; }
-        }
-        std::vector<int32_t>& pk = c->h_xlists;
-        pk.resize(n_xent + 4 * n_xchunks + 3 * n_xnodes + 1);
-        int32_t* w = pk.data();
-        auto put = [&](const std::vector<int32_t>& v) { if (!v.empty()) memcpy(w, v.data(), v.size() * 4); w += v.size(); };
-        put(xent); put(xc_node); put(xc_beg); put(xc_cnt); put(xc_part); put(xn_id); put(xn_c0); put(xn_nc);
-        CHK(scratch_get(c, 6, pk.size() * 4, &d_xlists));
-        HIPCHK(c, hipMemcpyAsync(d_xlists, pk.data(), pk.size() * 4, hipMemcpyHostToDevice, sB));
-        CHK(scratch_get(c, 7, tw_max_chunks * (size_t)S * 4 * 8, &d_tpart));
-    }
-    if (!reorder && !dev_lists) CHK(parents_block());
-    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
-    if (twist) {
-        const int32_t* xl = (const int32_t*)d_xlists;
-        g.tw.xent = xl; xl += n_xent;
-        g.tw.xchunk_node = xl; xl += n_xchunks;
-        g.tw.xchunk_beg = xl; xl += n_xchunks;
-        g.tw.xchunk_cnt = xl; xl += n_xchunks;
-        g.tw.xchunk_part = xl; xl += n_xchunks;
-        g.tw.xnode_id = xl; xl += n_xnodes;
-        g.tw.xnode_chunk0 = xl; xl += n_xnodes;
-        g.tw.xnode_nchunks = xl;
-        g.tw.tpart = (double*)d_tpart;
-    }
-    int node_launches = early_free ? 1 : 0;
-    if (rows_form && !early_free) {                        // the sweep left no marks: every node nobody merged again, now
-        ++node_launches;
-        if (two) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gup, 0));   // (needs the flags of the second upload)
+    return launch_check(c, "pg_nodes");
+}
+
+// 8. the adopted nodes' chain on sB: pg_nodes_rows_all, or a rank event at a time behind that rank event's coefficients
+static int rev_node_chain(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    const pg_args& g = p.g;
+    const int R = g.R;
+    const size_t nn = (size_t)R * g.K;
+    p.node_launches = p.plan.early_free ? 1 : 0;
+    if (p.plan.rows_form && !p.plan.early_free) {          // the sweep left no marks: every node nobody merged again, now
+        ++p.node_launches;
+        if (p.plan.two) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gup, 0));   // (needs the flags of the second upload)
         hipLaunchKernelGGL(pg_nodes_free, dim3((unsigned)((nn + 3) / 4)), dim3(256), 0, c->stream, g, 1);
         CHK(launch_check(c, "pg_nodes_free"));
     }
-    if (rows_all && !rows_overlap) {                       // (behind the coefficient launches: they head the longer chain)
-        if (!sort_early) CHK(dev_lists_launch(c, sB, sB, false, true));
-        if (n_chunks > 0) CHK(launch_chunks());
-    }
-    if (rows_all) {
-        if (!rows_overlap) HIPCHK(c, hipStreamWaitEvent(sB, c->ev_coeff[0], 0));   // every alpha is there
-        hipLaunchKernelGGL(pg_nodes_rows_all, dim3((unsigned)pinfo.n_slow, g.TS), dim3(256), 0, sB, g, (int)pinfo.n_slow);
+    if (!p.plan.chunks_first) CHK(rev_sort_and_chunk_sums(p));   // (behind the coefficient launches: they head the longer chain)
+    if (p.plan.rows_all) {
+        if (!p.plan.rows_overlap) HIPCHK(c, hipStreamWaitEvent(p.sB, c->ev_coeff[0], 0));   // every alpha is there
+        hipLaunchKernelGGL(pg_nodes_rows_all, dim3((unsigned)p.n.n_slow, g.TS), dim3(256), 0, p.sB, g, (int)p.n.n_slow);
         CHK(launch_check(c, "pg_nodes_rows_all"));
-        ++node_launches;
-    }
-    for (int r = rows_all ? -1 : R - 1; r >= 0; --r) {
-        if (interleave && r >= 1) CHK(launch_coeff(r - 1));
-        if (two) HIPCHK(c, hipStreamWaitEvent(sB, c->ev_coeff[r], 0));
-        if (twist && ev_chunk0[r + 1] > ev_chunk0[r]) {
-            hipLaunchKernelGGL(pg_twist_xchunks, dim3(ev_chunk0[r + 1] - ev_chunk0[r], cdiv(S, 256)), dim3(256), 0, sB, g, r, (int)ev_chunk0[r]);
-            CHK(launch_check(c, "pg_twist_xchunks"));
-            hipLaunchKernelGGL(pg_twist_xsum, dim3(ev_node0[r + 1] - ev_node0[r], cdiv((long)S * 4, 256)), dim3(256), 0, sB, g, (int)ev_node0[r], (int)ev_chunk0[r]);
-            CHK(launch_check(c, "pg_twist_xsum"));
-            tw_launches += 2;
+        ++p.node_launches;
+    } else {
+        for (int r = R - 1; r >= 0; --r) {
+            if (p.plan.interleave && r >= 1) CHK(rev_coeff(p, r - 1));
+            if (p.plan.two) HIPCHK(c, hipStreamWaitEvent(p.sB, c->ev_coeff[r], 0));
+            CHK(rev_nodes_of(p, r));
         }
-        const int nch = early_free ? 0 : rank_chunk0[r + 1] - rank_chunk0[r];   // (after the early pg_nodes_free: summed above, all rank events at once)
-        if (nch > 0) {
-            hipLaunchKernelGGL(pg_parent_chunks_rows, dim3(cdiv(S, 64), nch), dim3(256), 0, sB, g, (int)rank_chunk0[r]);
-            CHK(launch_check(c, "pg_parent_chunks_rows"));
-            ++node_launches;
-        }
-        if (rows_form) {
-            const int nslow = ev_slow0[r + 1] - ev_slow0[r];
-            if (nslow > 0) {
-                hipLaunchKernelGGL(pg_nodes_rows, dim3(nslow, g.TS), dim3(256), 0, sB, g, r, (int)ev_slow0[r],
-                                   early_free && !dev_lists ? (int)rank_chunk0[r] : 0);   // (device-built lists: heavy[] is the global chunk index)
-                ++node_launches;
-            }
-        } else {
-            hipLaunchKernelGGL(pg_nodes, dim3(T, K), dim3(256), 0, sB, g, r);
-            ++node_launches;
-        }
-        CHK(launch_check(c, "pg_nodes"));
     }
-    if (interleave) {
-        hipLaunchKernelGGL(pg_leafterm, dim3(cdiv(K, 256)), dim3(256), 0, c->stream, g);
-        CHK(launch_check(c, "pg_leafterm"));
-    }
-    if (two) {
-        HIPCHK(c, hipEventRecord(c->ev_gjoin, sB));
+    if (p.plan.interleave) CHK(rev_leafterm(p));
+    return PHYLO_OK;
+}
+
+// 9. join the streams, finish the nodes, reduce, fetch
+static int rev_finish(rev_pass& p, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf) {
+    phylo_ctx* c = p.c;
+    const pg_args& g = p.g;
+    const int R = g.R;
+    if (p.plan.two) {
+        HIPCHK(c, hipEventRecord(c->ev_gjoin, p.sB));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gjoin, 0));
     }
-    if (bg_free) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_bgdone, 0));
-    hipLaunchKernelGGL(pg_node_finish, dim3(cdiv((long)R * K, 32)), dim3(256), 0, c->stream, g);
+    if (p.plan.bg_free) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_bgdone, 0));
+    hipLaunchKernelGGL(pg_node_finish, dim3(cdiv((long)R * g.K, 32)), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_node_finish"));
-    hipLaunchKernelGGL(pg_scalars, dim3(nrk), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(pg_scalars, dim3(cdiv((long)R * g.K, 256)), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_scalars"));
     hipLaunchKernelGGL(pg_reduce, dim3(2 * R + 20), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_reduce"));
     // sharded: the pass read node rows from the peers' pools; no owner may write its pool again (its next sweep) before every
     // rank's pass is done -- the barrier makes phylo_sweep_backward a collective call
-    if (whole) CHK(comm_exchange(c, nullptr, 0, 0, 1));
+    if (p.plan.whole) CHK(comm_exchange(c, nullptr, 0, 0, 1));
     HIPCHK(c, hipEventRecord(c->evb1, c->stream));
     std::vector<double> out((size_t)2 * R + 20);
     HIPCHK(c, hipMemcpyAsync(out.data(), c->d_gout, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_gjoin, c->stream));     // (free again: the stream has waited for it above)
     CHK(wait_event_spin(c, c->ev_gjoin));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (rows_all && c->h_dlmeta[PG_DL_META_INTS(R)] != 0) {
+    if (p.plan.rows_all && c->h_dlmeta[PG_DL_META_INTS(R)] != 0) {
         c->h_dlmeta[PG_DL_META_INTS(R)] = 0;
         return fail(c, PHYLO_EHIP, "reverse pass: a workgroup of pg_nodes_rows_all gave up waiting for a parent's adjoint tile "
                                        "(PHYLO_GRAD_ROWS_CHAIN=1 runs a launch per rank event instead)");
@@ -2543,11 +2499,33 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
         HIPCHK(c, hipEventElapsedTime(&ms, c->evb0, c->evb1));
         *perf = c->stats;
         perf->sweep_ms = ms;
-        perf->n_launches = R + 7 + node_launches + tw_launches;
-        perf->merge_ms = host_ms;                          // here: host time of the integer lists (built, or waited for: device lists)
-        perf->merge_launches = dev_lists ? 1 : 0;          // here: 1 = the lists were built by kernels (phylo_revlists_dev.h)
+        // (R + 7 stands for the coefficient chain's launch per rank event and the fixed launches: not a true count under
+        //  pg_coeff_all, where that chain is one launch; kept as it is, tools compare it between runs)
+        perf->n_launches = R + 7 + p.node_launches + p.tw_launches;
+        perf->merge_ms = p.host_ms;                        // here: host time of the integer lists (built, or waited for: device lists)
+        perf->merge_launches = p.plan.dev_lists ? 1 : 0;   // here: 1 = the lists were built by kernels (phylo_revlists_dev.h)
     }
     return PHYLO_OK;
+}
+
+static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!c->swept || !c->last_graph)
+        return fail(c, PHYLO_ESTATE, "phylo_sweep_backward needs a preceding sweep with PHYLO_KEEP_GRAPH");
+    rev_pass p;
+    p.c = c;
+    p.plan = pg_plan_form(rev_plan_in(c));                 // decision point one: before anything is launched
+    CHK(rev_bind(p));
+    CHK(rev_early(p));
+    CHK(rev_fork(p));
+    if (p.plan.parents_first) CHK(rev_parents(p));         // (decision point two, pg_plan_chains, is inside: the counts are known there)
+    CHK(rev_adopters(p));
+    CHK(rev_coeff_chain(p));
+    CHK(rev_lookahead(p));
+    if (!p.plan.parents_first) CHK(rev_parents(p));
+    p.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p.host_t0).count();
+    CHK(rev_node_chain(p));
+    return rev_finish(p, d_lam_l, d_lam_r, d_pi, d_Q, perf);
 }
 
 // ---- a VI training step's host half in C++ (phylo_train.h): variables -> model -> sweep + reverse pass -> gradients of the variables
@@ -2591,6 +2569,17 @@ int phylo_debug_stamps(phylo_ctx* c, uint64_t* out, int n) {
     return PHYLO_OK;
 }
 
+// meta of the two list hooks: n_adp, n_chunks, max_chunks, n_slow, n_par, cap, then ev_adp0[R+1], rank_chunk0[R+1], ev_slow0[R+1]
+static void debug_lists_meta(const pg_list_counts& n, size_t cap, int R, int32_t* meta) {
+    meta[0] = n.n_adp; meta[1] = (int32_t)n.n_chunks; meta[2] = (int32_t)n.max_chunks; meta[3] = n.n_slow; meta[4] = n.n_par;
+    meta[5] = (int32_t)cap;
+    for (int r = 0; r <= R; ++r) {
+        meta[6 + r] = n.ev_adp0[r];
+        meta[6 + (R + 1) + r] = n.rank_chunk0[r];
+        meta[6 + 2 * (R + 1) + r] = n.ev_slow0[r];
+    }
+}
+
 int phylo_debug_reverse_lists(int N, int K, const int64_t* ancestors, const int32_t* child, int early_free, int rows_form,
                               const int32_t* lookahead_nodes, int n_lookahead, int32_t* lists, int64_t n_lists, int32_t* meta, int n_meta) {
     if (N < 2 || K < 1 || !child || !lists || !meta || (N > 2 && !ancestors) || (n_lookahead > 0 && !lookahead_nodes))
@@ -2600,21 +2589,57 @@ int phylo_debug_reverse_lists(int N, int K, const int64_t* ancestors, const int3
         return fail(nullptr, PHYLO_EINVAL, "phylo_debug_reverse_lists: lists needs %zu ints, meta %d", pg_lists_ints((size_t)R, (size_t)K), 6 + 3 * (R + 1));
     const pg_lists L = pg_lists_carve(lists, (size_t)R, (size_t)K);
     pg_lists_clear(L, R, K);
-    std::vector<int32_t> cur, ev_adp0, rank_chunk0, ev_slow0;
-    const int32_t n_adp = pg_build_adopters(R, K, ancestors, L, cur, ev_adp0);
+    std::vector<int32_t> cur;
+    pg_list_counts n;
+    pg_build_adopters(R, K, ancestors, L, cur, n);
     if (early_free) pg_mark_adopted(R, K, ancestors, L);
     for (int i = 0; i < n_lookahead; ++i) {
         if (lookahead_nodes[i] < N || lookahead_nodes[i] >= N + R * K) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_reverse_lists: node id out of range");
         L.slow_flag[lookahead_nodes[i] - N] |= 2;
     }
-    const pg_parents_info o = pg_build_parents(N, R, K, child, rows_form != 0, rows_form != 0 && early_free != 0, L, cur, rank_chunk0, ev_slow0);
-    meta[0] = n_adp; meta[1] = (int32_t)o.n_chunks; meta[2] = (int32_t)o.max_chunks; meta[3] = o.n_slow; meta[4] = o.n_par;
-    meta[5] = (int32_t)L.cap;
+    pg_build_parents(N, R, K, child, rows_form != 0, rows_form != 0 && early_free != 0, L, cur, n);
+    debug_lists_meta(n, L.cap, R, meta);
+    return PHYLO_OK;
+}
+
+int phylo_debug_lookahead_lists(int N, int K, int S, int M, const int32_t* roots_ad, int32_t* slow_flag, int32_t* image, int64_t n_image,
+                                int32_t* meta, int n_meta) {
+    if (N < 2 || K < 1 || S < 1 || M < 1 || !roots_ad || !slow_flag || !image || !meta)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_lookahead_lists: bad arguments");
+    const int R = N - 1;
+    if (n_meta < 4 + 2 * (R + 1)) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_lookahead_lists: meta needs %d ints", 4 + 2 * (R + 1));
+    for (int r = 1; r < R; ++r)                              // slots 0 .. N - r - 1 of rank event r: a leaf or a node of an earlier rank event
+        for (int k = 0; k < K; ++k)
+            for (int i = 0; i < N - r; ++i) {
+                const int32_t x = roots_ad[((size_t)r * K + k) * N + i];
+                if (x < 0 || x >= N + r * K) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_lookahead_lists: root id out of range");
+            }
+    std::vector<int32_t> pk;
+    pg_lookahead x;
+    pg_build_lookahead(N, K, S, PG_XCH, roots_ad, slow_flag, pk, x);
+    if ((int64_t)pk.size() > n_image) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_lookahead_lists: image needs %zu ints", pk.size());
+    memcpy(image, pk.data(), pk.size() * 4);
+    meta[0] = (int32_t)x.n_xent; meta[1] = (int32_t)x.n_xchunks; meta[2] = (int32_t)x.n_xnodes; meta[3] = (int32_t)x.max_chunks;
     for (int r = 0; r <= R; ++r) {
-        meta[6 + r] = ev_adp0[r];
-        meta[6 + (R + 1) + r] = rank_chunk0[r];
-        meta[6 + 2 * (R + 1) + r] = ev_slow0[r];
+        meta[4 + r] = x.ev_chunk0[r];
+        meta[4 + (R + 1) + r] = x.ev_node0[r];
     }
+    return PHYLO_OK;
+}
+
+int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int twisted, int marks, uint32_t switches, int64_t n_slow, int TS,
+                             int64_t coeff_wgs, int passes_in_flight, uint32_t* mask) {
+    if (N < 2 || K < 1 || K_local < 1 || S < 1 || world < 1 || TS < 1 || n_slow < 0 || coeff_wgs < 0 || !mask)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_reverse_plan: bad arguments");
+    pg_plan_in in{};
+    in.N = N; in.K = K; in.K_local = K_local; in.S = S; in.world = world;
+    in.twist = twisted != 0; in.marks = marks != 0;
+    in.rev_host_lists = switches & 1; in.one_stream = switches & 2; in.two_streams = switches & 4;
+    in.rows_chain = switches & 8; in.coeff_chain = switches & 16;
+    in.dl_max_k = PG_DL_MAX_K;
+    pg_plan p = pg_plan_form(in);
+    pg_plan_chains(p, (long)n_slow, TS, (long)coeff_wgs, passes_in_flight, N - 1);
+    *mask = pg_plan_mask(p);
     return PHYLO_OK;
 }
 
@@ -2655,17 +2680,11 @@ static int debug_device_lists_run(phylo_ctx* c, int32_t* lists, int64_t n_lists,
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_ad_off, 0xff, ints * 4, c->stream));        // (what the builders do not write stays -1)
     CHK(dev_lists_launch(c, c->stream, c->stream));
-    dl_meta m;
+    pg_list_counts m;
     CHK(dev_lists_wait(c, m));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(lists, c->d_ad_off, ints * 4, hipMemcpyDeviceToHost));
-    meta[0] = m.n_adp; meta[1] = m.n_chunks; meta[2] = 0; meta[3] = m.n_slow; meta[4] = m.n_par;
-    meta[5] = (int32_t)pg_lists_cap((size_t)R, (size_t)K);
-    for (int r = 0; r <= R; ++r) {
-        meta[6 + r] = m.ev_adp0[r];
-        meta[6 + (R + 1) + r] = 0;
-        meta[6 + 2 * (R + 1) + r] = m.ev_slow0[r];
-    }
+    debug_lists_meta(m, pg_lists_cap((size_t)R, (size_t)K), R, meta);
     return PHYLO_OK;
 }
 
