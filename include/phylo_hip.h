@@ -171,7 +171,10 @@ int phylo_synchronize(phylo_ctx* ctx);
  * replicates): the context's K particles are G groups of K/G; group g is exactly the sweep of K/G particles with
  * seeds[g] (own draws, own resampling, own log Z-hat).  Outputs of phylo_sweep_fetch hold group g in columns
  * [g K/G, (g+1) K/G) (ancestors index inside the group); phylo_sweep_fetch_logz returns the G estimates.
- * Plain proposal.  Sharded contexts too: the K = G * (K/G) particle indices are sharded by contiguous ranges as
+ * Plain proposal.  With PHYLO_KEEP_GRAPH (G > 1): one GPU (unsharded context) and S <= 4096 sites -- the batch is then ONE
+ * block-diagonal genealogy of K particles that phylo_sweep_backward_batch differentiates; the sweep's bits are those of the
+ * batch without the flag (PHYLO_EINVAL names the failed condition: PHYLO_TWISTING, a sharded context, S > 4096).  Without the
+ * flag, sharded contexts too: the K = G * (K/G) particle indices are sharded by contiguous ranges as
  * always (a group may straddle ranks), one all-gather per rank event carries all G sweeps.
  * phylo_sweep_batch_begin + phylo_sweep_step(_group) + phylo_sweep_finish is the stepwise form. */
 int phylo_sweep_batch_async(phylo_ctx* ctx, const uint64_t* seeds, int G, uint32_t flags);
@@ -215,10 +218,18 @@ int phylo_sweep_node(phylo_ctx* ctx, int r, int k, double* out_Sx4);
  * same sweep -- that returns the gradient of the GLOBAL log Z-hat, the same bits on every rank (each rank runs the whole pass over
  * the genealogy its sweep gathered, reading node rows from their owners' pools, and ends with a barrier; integer lists by the host
  * builders, a launch per rank event).  Refused there: a sweep with
- * PHYLO_TWISTING | PHYLO_KEEP_GRAPH, batched sweeps and more than 4096 sites (PHYLO_EINVAL, at the sweep); a backward without a
+ * PHYLO_TWISTING | PHYLO_KEEP_GRAPH, batched sweeps with PHYLO_KEEP_GRAPH and more than 4096 sites (PHYLO_EINVAL, at the sweep); a backward without a
  * kept graph is PHYLO_ESTATE as on one GPU. */
 int phylo_sweep_backward(phylo_ctx* ctx, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q,
                          phylo_stats* perf);
+/* The reverse pass of a batched sweep (phylo_sweep_batch_async / _begin ... _finish with PHYLO_KEEP_GRAPH): one set of launches
+ * over the block-diagonal genealogy, G gradients out -- d_lam_l[G][N-1], d_lam_r[G][N-1], d_pi[G][4], d_Q[G][16]; row g is the
+ * gradient of log Z-hat_g alone (no mean is taken).  May be queued right behind the sweep like phylo_sweep_backward.  G must
+ * equal the last sweep's group count (PHYLO_EINVAL); without a kept graph PHYLO_ESTATE.  After a sweep of one group (G = 1, or
+ * phylo_sweep_async) it returns phylo_sweep_backward's bits; phylo_sweep_backward itself refuses a sweep of more than one group
+ * (PHYLO_ESTATE).  Run to run the same bits (no floating-point atomics). */
+int phylo_sweep_backward_batch(phylo_ctx* ctx, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, int G,
+                               phylo_stats* perf);
 
 /* The host half of a VI training step in the library (reference: optimizer.minimize(self.cost), vcsmc.py:488-491; the NumPy
  * statement of the same formulas is phylo_amd/train.py).  Variables packed as a_l[N-1] | a_r[N-1] | y_q[16] | y_station[4] (the
@@ -232,6 +243,10 @@ int phylo_sweep_backward(phylo_ctx* ctx, double* d_lam_l, double* d_lam_r, doubl
  * defaults are beta1 0.9, beta2 0.999, eps 1e-8; t, m, v: its state, m and v packed like the variables, zero at the start). */
 int phylo_vi_gradients(phylo_ctx* ctx, uint64_t seed, uint32_t flags, int M, int jc, const double* vars, double* logZ, double* grads,
                        phylo_stats* fwd, phylo_stats* bwd);
+/* phylo_vi_gradients for G independent particle systems of K / G particles behind one set of launches (seeds[G]; plain proposal):
+ * logZ[G], grads[G][2 (N-1) + 20], row g the gradient of log Z-hat_g with respect to the variables. */
+int phylo_vi_gradients_batch(phylo_ctx* ctx, const uint64_t* seeds, int G, uint32_t flags, int jc, const double* vars, double* logZ,
+                             double* grads, phylo_stats* fwd, phylo_stats* bwd);
 int phylo_vi_apply(int n_taxa, int jc, double* vars, const double* grads, int kind, double lr, double beta1, double beta2, double eps,
                    int64_t* t, double* m, double* v);
 
@@ -268,6 +283,10 @@ int phylo_debug_lookahead_lists(int N, int K, int S, int M, const int32_t* roots
  * 8 rows_all, 9 rows_overlap, 10 chunks_first, 11 interleave, 12 coeff_all.  tests/test_revplan_cpu.py restates the rules. */
 int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int twisted, int marks, uint32_t switches, int64_t n_slow,
                              int TS, int64_t coeff_wgs, int passes_in_flight, uint32_t* mask);
+/* ... after a batched sweep of G groups (K the total): the device lists' limit is per group (K / G <= 8192), every other
+ * limit sees the totals.  G = 1 is phylo_debug_reverse_plan. */
+int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,
+                                   int passes_in_flight, uint32_t* mask);
 
 /* The same lists built by the device kernels (phylo_revlists_dev.h) from the graph of the preceding lazy sweep with
  * PHYLO_KEEP_GRAPH, copied back in the same layout (what the builders do not write reads -1; heavy[] holds GLOBAL chunk indices,

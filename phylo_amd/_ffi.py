@@ -28,10 +28,10 @@ EXPORTS = [
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
     "phylo_forest_loglik", "phylo_tree_loglik", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
-    "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward",
+    "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
-    "phylo_vi_gradients", "phylo_vi_apply",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
     "phylo_comm_exchange_kind",
@@ -139,6 +139,21 @@ def debug_reverse_plan(N, K, S, K_local=None, world=1, twisted=False, marks=True
                                       C.c_int(int(twisted)), C.c_int(int(marks)), C.c_uint32(sw), C.c_int64(n_slow),
                                       C.c_int((S + 255) // 256 if TS is None else TS), C.c_int64(coeff_wgs), C.c_int(passes_in_flight),
                                       C.byref(mask))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    out = {name: bool(mask.value >> i & 1) for i, name in enumerate(PLAN_BITS)}
+    out["mask"] = mask.value
+    return out
+
+
+def debug_reverse_plan_batch(N, K, G, S, switches=(), n_slow=0, TS=None, coeff_wgs=0, passes_in_flight=1):
+    """debug_reverse_plan for the reverse pass of a batched sweep of G groups (K: the total; plain proposal, marks, one GPU)."""
+    lib = load()
+    sw = sum(1 << PLAN_SWITCHES.index(name) for name in switches)
+    mask = C.c_uint32(0)
+    rc = lib.phylo_debug_reverse_plan_batch(C.c_int(N), C.c_int(K), C.c_int(G), C.c_int(S), C.c_uint32(sw), C.c_int64(n_slow),
+                                            C.c_int((S + 255) // 256 if TS is None else TS), C.c_int64(coeff_wgs),
+                                            C.c_int(passes_in_flight), C.byref(mask))
     if rc:
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     out = {name: bool(mask.value >> i & 1) for i, name in enumerate(PLAN_BITS)}
@@ -334,15 +349,18 @@ class Context:
     # ---- sweep
     def sweep_async(self, seed, flags=FLAGS_DEFAULT, M=1):
         self._check(self._lib.phylo_sweep_async(self._h, C.c_uint64(seed), C.c_uint32(flags), C.c_int(M)))
+        self._last_batch = 1
 
     def sweep_batch_async(self, seeds, flags=FLAGS_DEFAULT):
         """len(seeds) independent sweeps of K/len(seeds) particles each, in one set of launches."""
         sd = np.ascontiguousarray(seeds, dtype=np.uint64)
         self._check(self._lib.phylo_sweep_batch_async(self._h, _ptr(sd), C.c_int(sd.size), C.c_uint32(flags)))
+        self._last_batch = sd.size
 
     def sweep_batch_begin(self, seeds, flags=FLAGS_DEFAULT):
         sd = np.ascontiguousarray(seeds, dtype=np.uint64)
         self._check(self._lib.phylo_sweep_batch_begin(self._h, _ptr(sd), C.c_int(sd.size), C.c_uint32(flags)))
+        self._last_batch = sd.size
 
     def sweep_fetch_logz(self, G):
         out = np.empty(int(G))
@@ -404,6 +422,21 @@ class Context:
         out['backward_launches'] = st.n_launches
         return out
 
+    def sweep_backward_batch(self, G=None):
+        """Gradients of the G log Z-hat of the last batched sweep (run with KEEP_GRAPH): the arrays of sweep_backward with a leading
+        G axis, from one reverse pass over the block-diagonal genealogy (phylo_sweep_backward_batch)."""
+        R = self.N - 1
+        G = int(self._last_batch if G is None else G)
+        out = {'d_lam_l': np.empty((G, R)), 'd_lam_r': np.empty((G, R)), 'd_pi': np.empty((G, 4)), 'd_Q': np.empty((G, 4, 4))}
+        st = Stats()
+        self._check(self._lib.phylo_sweep_backward_batch(self._h, _ptr(out['d_lam_l']), _ptr(out['d_lam_r']), _ptr(out['d_pi']),
+                                                         _ptr(out['d_Q']), C.c_int(G), C.byref(st)))
+        out['backward_ms'] = st.sweep_ms
+        out['backward_host_ms'] = st.merge_ms
+        out['backward_lists'] = 'device' if st.merge_launches else 'host'
+        out['backward_launches'] = st.n_launches
+        return out
+
     def tree_summary(self):
         """Tree posterior of the last sweep (phylo_tree_summary; every group of a batched sweep; a collective on a sharded context,
         which returns the same tables on every rank).  NumPy arrays, rows group-major (`*_offsets[g]:*_offsets[g+1]` = group g):
@@ -460,6 +493,20 @@ class Context:
         self._check(self._lib.phylo_vi_gradients(self._h, C.c_uint64(seed), C.c_uint32(flags), C.c_int(M), C.c_int(int(jc)), _ptr(vars_),
                                                  C.byref(z), _ptr(grads), C.byref(fwd), C.byref(bwd)))
         return z.value, grads, fwd, bwd
+
+    def vi_gradients_batch(self, seeds, flags, jc, packed_vars):
+        """vi_gradients for len(seeds) independent systems of K / len(seeds) particles in one batched sweep and one reverse pass
+        (phylo_vi_gradients_batch).  Returns (logZ [G], grads [G, 2 (N-1) + 20], forward stats, backward stats)."""
+        vars_ = _f64(packed_vars)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        G = sd.size
+        grads = np.empty((G, 2 * (self.N - 1) + 20))
+        z = np.empty(G)
+        fwd, bwd = Stats(), Stats()
+        self._check(self._lib.phylo_vi_gradients_batch(self._h, _ptr(sd), C.c_int(G), C.c_uint32(flags), C.c_int(int(jc)), _ptr(vars_),
+                                                       _ptr(z), _ptr(grads), C.byref(fwd), C.byref(bwd)))
+        self._last_batch = G
+        return z, grads, fwd, bwd
 
     def debug_device_lists(self, ancestors=None, child=None):
         """The reverse pass's integer lists as the device kernels build them from the last (lazy, KEEP_GRAPH, plain proposal) sweep,

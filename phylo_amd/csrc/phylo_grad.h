@@ -9,6 +9,9 @@
 //   * the expm, the merges, log, logsumexp are differentiated.
 // Accumulation orders are fixed (no floating-point atomics): a gradient is reproducible run to run.
 // Parity: oracle/cpu_grad.py (which is checked against central differences), to a relative 1e-9.
+// A batched sweep's graph (G systems of K / G particles, plain proposal) is ONE K-particle genealogy with global indices in which
+// adoption never crosses a group: one pass, G gradients (phylo_sweep_backward_batch).  Group-aware are pg_omega, pg_node_finish's
+// workgroup sums and pg_reduce here and pg_dl_adopters in phylo_revlists_dev.h; everything else follows the lists.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +53,9 @@ struct pg_twist {
 
 struct pg_args {
     int N, S, K, R, T, jc;             // T tiles of PG_NT sites per node
+    int ngrp, Kg, lse_stride;          // a batched sweep: ngrp independent systems of Kg = K / ngrp particles, group g's particles
+                                       // g Kg .. (g + 1) Kg - 1 of ONE genealogy with global indices (adoption never crosses a group);
+                                       // lse of (group g, rank event r) at lse[g lse_stride + r].  One sweep alone: 1, K, 0
     int twist;                         // the sweep used the twisted proposal: tw is set
     pg_twist tw;
     const double* leaves;              // [N][S][4]
@@ -60,7 +66,7 @@ struct pg_args {
     double* adj;                       // [R][K][S][4]: d logZ / d node
     const double* Pmat;                // [R][K][32]
     const double *bl, *br;             // [R][K]
-    const double *logw, *lse;          // [R][K], [R] (lse = logsumexp - log K)
+    const double *logw, *lse;          // [R][K], [R] (lse = logsumexp - log Kg; batched: [ngrp][lse_stride])
     const double *pi, *Q;              // [4], [16]
     const double *lam_l, *lam_r;       // [R]
     const int32_t* child;              // [R][K][2] node ids
@@ -94,10 +100,12 @@ struct pg_args {
     double* part;                      // [R][K][T][PG_PART]
     double* nodeg;                     // [R][K][PG_NODEG] (pg_node_finish writes the two branch adjoints only; the rest: fin_part)
     double* fin_part;                  // [ceil(R K / 32)][20]: Q_bar[16], pi_bar[4] summed over the 32 nodes of a pg_node_finish workgroup
+                                       // (batched: [R][ngrp][ceil(Kg / 32)][20], no workgroup holds nodes of two groups)
     double* leafpi;                    // [N][4]: sum_s leaf[s][a] / (pi . leaf[s])
     double* leafterm;                  // [K][4]
     double* terms;                     // [R][K][2]
-    double* out;                       // [2 R + 20]: d_lam_l, d_lam_r, d_pi, d_Q
+    double* out;                       // [ngrp][2 R + 20]: d_lam_l, d_lam_r, d_pi, d_Q of every group's log Z-hat; the batch call appends
+                                       // [ngrp] log Z-hat (pg_reduce's block 2 R + 20)
 };
 
 // ---- small helpers ------------------------------------------------------------------------------
@@ -298,7 +306,7 @@ __global__ __launch_bounds__(256) void pg_copy_words(pg_copy3 a) {
 }
 
 // ---- g1: omega = softmax_k(log w_r) ---------------------------------------------------------------
-// One workgroup per rank event.  exp(log w - lse - log K) alone is a softmax only as far as lse is exact: the sweep stores it as
+// One workgroup per (rank event, group): a batched sweep normalises every group's weights by the group's own lse, log(K / G) and sum.  exp(log w - lse - log K) alone is a softmax only as far as lse is exact: the sweep stores it as
 // one double, so with log-weights of magnitude 1e5 (rates 1e4 apart between rank events: -lambda_r times every earlier branch
 // length) every omega of the event carries the same factor 1 + 1e-11, the sums over particles that should cancel in G and in
 // the rate adjoints do not, and d_lam is off by 2e-9 of its largest entry (tests/test_gpu_grad.py, regime mixed_alternating).
@@ -307,18 +315,18 @@ __global__ __launch_bounds__(256) void pg_copy_words(pg_copy3 a) {
 #define PG_OMEGA_REG 4                                      // elements a thread keeps in registers between the two passes
 __global__ __launch_bounds__(PG_OMEGA_NT) void pg_omega(pg_args a) {
     __shared__ double sh[PG_OMEGA_NT / 64];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const double* lw = a.logw + (size_t)r * a.K;
-    double* om = a.om + (size_t)r * a.K;
-    const double lse = a.lse[r], logK = pm_log((double)a.K);
+    const int r = blockIdx.x, g = blockIdx.y, tid = threadIdx.x, K = a.Kg;
+    const double* lw = a.logw + (size_t)r * a.K + (size_t)g * K;
+    double* om = a.om + (size_t)r * a.K + (size_t)g * K;
+    const double lse = a.lse[(size_t)g * a.lse_stride + r], logK = pm_log((double)K);
     double ev[PG_OMEGA_REG], sum = 0.0;
 #pragma unroll
     for (int i = 0; i < PG_OMEGA_REG; ++i) {
         const int k = tid + i * PG_OMEGA_NT;
-        ev[i] = k < a.K ? pm_exp((lw[k] - lse) - logK) : 0.0;
+        ev[i] = k < K ? pm_exp((lw[k] - lse) - logK) : 0.0;
         sum = sum + ev[i];
     }
-    for (int k = tid + PG_OMEGA_REG * PG_OMEGA_NT; k < a.K; k += PG_OMEGA_NT) sum = sum + pm_exp((lw[k] - lse) - logK);   // (again below)
+    for (int k = tid + PG_OMEGA_REG * PG_OMEGA_NT; k < K; k += PG_OMEGA_NT) sum = sum + pm_exp((lw[k] - lse) - logK);   // (again below)
     sum = pg_wave_sum(sum);
     if ((tid & 63) == 0) sh[tid >> 6] = sum;
     __syncthreads();
@@ -329,9 +337,9 @@ __global__ __launch_bounds__(PG_OMEGA_NT) void pg_omega(pg_args a) {
 #pragma unroll
     for (int i = 0; i < PG_OMEGA_REG; ++i) {
         const int k = tid + i * PG_OMEGA_NT;
-        if (k < a.K) om[k] = ev[i] * inv;
+        if (k < K) om[k] = ev[i] * inv;
     }
-    for (int k = tid + PG_OMEGA_REG * PG_OMEGA_NT; k < a.K; k += PG_OMEGA_NT) om[k] = pm_exp((lw[k] - lse) - logK) * inv;
+    for (int k = tid + PG_OMEGA_REG * PG_OMEGA_NT; k < K; k += PG_OMEGA_NT) om[k] = pm_exp((lw[k] - lse) - logK) * inv;
 }
 
 // ---- g2: G_r[k] = d logZ / d ll_r[k] = omega_r[k] - sum of omega_{r+1} over the particles that adopt k -----
@@ -1178,9 +1186,15 @@ __global__ __launch_bounds__(256) void pg_node_finish(pg_args a) {
     // node) -- 32 nodes per workgroup of 256 threads, grid ceil(R K / 32)
     __shared__ double shw[4][20];
     const int tid = threadIdx.x, row = tid & 3, side = (tid >> 2) & 1;
-    const size_t node0 = (size_t)blockIdx.x * 32 + (tid >> 3);
-    const bool valid = node0 < (size_t)a.R * a.K;
-    const size_t node = valid ? node0 : (size_t)a.R * a.K - 1;
+    size_t node0 = (size_t)blockIdx.x * 32 + (tid >> 3);
+    bool valid = node0 < (size_t)a.R * a.K;
+    size_t node = valid ? node0 : (size_t)a.R * a.K - 1;
+    if (a.ngrp > 1) {                                        // batched: workgroups per (rank event, group), so that fin_part never mixes groups
+        const unsigned nbg = ((unsigned)a.Kg + 31u) / 32u, row_g = (unsigned)blockIdx.x / nbg;   // row_g = r ngrp + g: first node row_g Kg
+        const unsigned kl = ((unsigned)blockIdx.x - row_g * nbg) * 32u + (unsigned)(tid >> 3);
+        valid = kl < (unsigned)a.Kg;
+        node = (size_t)row_g * a.Kg + (valid ? kl : (unsigned)a.Kg - 1u);
+    }
     double pb[16], pib[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < 16; ++q) pb[q] = 0.0;
@@ -1259,13 +1273,31 @@ __global__ __launch_bounds__(256) void pg_scalars(pg_args a) {
 }
 
 // ---- g8: final sums (fixed order): block o < 2R: d_lam; then d_pi[4], d_Q[16] -------------------------------
+// Batched (grid y = group): row g sums group g's particles alone, in the order a context of K / G particles would use (when 32
+// divides K / G, else pg_node_finish's workgroups of that context would be cut elsewhere); block 2 R + 20, launched by the batch
+// call only, hands out the groups' log Z-hat behind the gradients.
 __global__ __launch_bounds__(256) void pg_reduce(pg_args a) {
     __shared__ double sh[4];
-    const int o = blockIdx.x, tid = threadIdx.x;
+    const int o = blockIdx.x, g = blockIdx.y, tid = threadIdx.x, Kg = a.Kg, k0 = g * Kg;
+    double* out = a.out + (size_t)g * (2 * a.R + 20);
+    if (o == 2 * a.R + 20) {
+        if (tid == 0) a.out[(size_t)a.ngrp * (2 * a.R + 20) + g] = a.lse[(size_t)g * a.lse_stride + a.R];
+        return;
+    }
     double acc = 0.0;
     if (o < 2 * a.R) {
         const int side = o / a.R, r = o - side * a.R;
-        for (int k = tid; k < a.K; k += 256) acc = acc + a.terms[((size_t)r * a.K + k) * 2 + side];
+        for (int k = tid; k < Kg; k += 256) acc = acc + a.terms[((size_t)r * a.K + k0 + k) * 2 + side];
+    } else if (a.ngrp > 1) {                                 // (plain proposal only: no twnode)
+        const int q = o - 2 * a.R;
+        const int fcol = q < 4 ? 16 + q : q - 4;
+        const size_t nbg = ((size_t)Kg + 31) / 32, nf = (size_t)a.R * nbg;
+        for (size_t i = tid; i < nf; i += 256) {
+            const size_t r = i / nbg, b = i - r * nbg;
+            acc = acc + a.fin_part[((r * a.ngrp + g) * nbg + b) * 20 + fcol];
+        }
+        if (q < 4)
+            for (int k = tid; k < Kg; k += 256) acc = acc + a.leafterm[(size_t)(k0 + k) * 4 + q];
     } else {
         const int q = o - 2 * a.R;                           // 0..3 pi, 4..19 Q
         const int col = q < 4 ? 18 + q : 2 + (q - 4);
@@ -1292,7 +1324,7 @@ __global__ __launch_bounds__(256) void pg_reduce(pg_args a) {
             for (int k = tid; k < a.K; k += 256) acc = acc + a.leafterm[k * 4 + q];
     }
     const double t = pg_block_sum(acc, sh);
-    if (tid == 0) a.out[o] = t;
+    if (tid == 0) out[o] = t;
 }
 
 

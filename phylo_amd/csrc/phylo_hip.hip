@@ -186,6 +186,8 @@ struct phylo_ctx {
     // host copies of the kept graph's integer records, in pinned memory: copied asynchronously when the sweep ends, so that the
     // reverse pass finds them on the host without a synchronous copy; and the pinned staging area of its packed integer lists
     int64_t* h_anc_p = nullptr;          // [(R-1)][K]
+    std::vector<int64_t> h_anc_glob;     // a batched sweep's ancestors as global indices (host builders of the reverse pass)
+    std::vector<double> h_gout;          // the reverse pass's results on the host: [G][2 R + 20] (+ [G] log Z-hat, batch call)
     double* h_model_p = nullptr;         // pinned image of the model upload (phylo_set_model)
     double* h_leaves_p = nullptr;        // pinned image of the leaf rows and their codes (phylo_set_leaves)
     hipEvent_t ev_leaves = nullptr;
@@ -517,7 +519,7 @@ int ensure_graph_state(phylo_ctx* c) {
     CHK(dalloc(c, &c->d_leafpi, N * 4));
     CHK(dalloc(c, &c->d_leafterm, K * 4));
     CHK(dalloc(c, &c->d_terms, R * K * 2));
-    CHK(dalloc(c, &c->d_gout, 2 * R + 20));
+    CHK(dalloc(c, &c->d_gout, (2 * R + 21) * PK_MAX_GROUPS));   // a batched sweep: a row per group, then the groups' log Z-hat
     {   // the integer lists of the reverse pass live in ONE slab, uploaded with one copy per step
         c->h_csr_cap = pg_lists_ints(R, K);               // (layout: pg_lists_carve, phylo_revlists.h)
         CHK(dalloc(c, &c->d_ad_off, c->h_csr_cap));
@@ -1043,8 +1045,14 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     c->run.active = false;
     if (G < 1 || G > PK_MAX_GROUPS || c->K % G != 0)
         return fail(c, PHYLO_EINVAL, "a batch needs 1 <= G <= %d sweeps and K = %d divisible by G (got %d)", PK_MAX_GROUPS, c->K, G);
-    if (G > 1 && (flags & (PHYLO_TWISTING | PHYLO_KEEP_GRAPH)))
-        return fail(c, PHYLO_EINVAL, "batched sweeps need the plain proposal without PHYLO_KEEP_GRAPH");
+    if (G > 1 && (flags & PHYLO_TWISTING))
+        return fail(c, PHYLO_EINVAL, "batched sweeps need the plain proposal (PHYLO_TWISTING is set)");
+    if (G > 1 && (flags & PHYLO_KEEP_GRAPH)) {             // the graph of G systems: one block-diagonal genealogy, rows form, one GPU
+        if (c->world != 1 || c->comm.transport != 0)
+            return fail(c, PHYLO_EINVAL, "batched sweeps with PHYLO_KEEP_GRAPH need an unsharded context");
+        if (c->S > 4096)
+            return fail(c, PHYLO_EINVAL, "batched sweeps with PHYLO_KEEP_GRAPH need S <= 4096 sites (got %d)", c->S);
+    }
     if (!c->have_leaves || !c->have_model)
         return fail(c, PHYLO_ESTATE, "phylo_set_leaves and phylo_set_model must be called before a sweep");
     if (!c->state_ready) {
@@ -1923,13 +1931,13 @@ static unsigned bit_length(size_t v) { unsigned b = 0; while (v) { ++b; v >>= 1;
 extern "C++" {
 template <int ITEMS>
 static int dev_lists_adopters(phylo_ctx* c, const pg_dl_args& d, hipStream_t s) {
-    const size_t lds = pg_dl_sort<ITEMS>::storage_bytes + (size_t)d.K * 4;
+    const size_t lds = pg_dl_sort<ITEMS>::storage_bytes + (size_t)d.Kg * 4;
     static bool raised = false;                            // (beyond the 64 KB every kernel may ask for: say so once)
     if (lds > 65536 && !raised) {
         HIPCHK(c, hipFuncSetAttribute((const void*)pg_dl_adopters<ITEMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         raised = true;
     }
-    hipLaunchKernelGGL(pg_dl_adopters<ITEMS>, dim3(d.R), dim3(PG_DL_BLOCK), lds, s, d, bit_length((size_t)d.K));
+    hipLaunchKernelGGL(pg_dl_adopters<ITEMS>, dim3(d.R, d.K / d.Kg), dim3(PG_DL_BLOCK), lds, s, d, bit_length((size_t)d.Kg));
     return launch_check(c, "pg_dl_adopters");
 }
 }  // extern "C++"
@@ -1944,6 +1952,7 @@ static int dev_lists_launch(phylo_ctx* c, hipStream_t sL, hipStream_t sS, bool k
     CHK(scratch_get(c, 8, (8 * nn + 4 * nb + meta_ints + 32) * 4, &ws));
     pg_dl_args d{};
     d.N = N; d.R = R; d.K = K;
+    d.Kg = c->last_graph ? K / c->last_G : K;              // (a genealogy given by a test hook: one group)
     d.anc = c->d_anc; d.child = c->d_child;
     int32_t* w = (int32_t*)ws;
     d.cnt_par = w; d.ticket = w + nn; w += nn + 16;
@@ -1963,9 +1972,9 @@ static int dev_lists_launch(phylo_ctx* c, hipStream_t sL, hipStream_t sS, bool k
     void* tp = nullptr;
     CHK(scratch_get(c, 9, c->dl_temp_p + 16, &tp));
     if (kernels) {
-        if (K <= 1024) CHK(dev_lists_adopters<1>(c, d, sL));
-        else if (K <= 2048) CHK(dev_lists_adopters<2>(c, d, sL));
-        else if (K <= 4096) CHK(dev_lists_adopters<4>(c, d, sL));
+        if (d.Kg <= 1024) CHK(dev_lists_adopters<1>(c, d, sL));
+        else if (d.Kg <= 2048) CHK(dev_lists_adopters<2>(c, d, sL));
+        else if (d.Kg <= 4096) CHK(dev_lists_adopters<4>(c, d, sL));
         else CHK(dev_lists_adopters<8>(c, d, sL));
         if (R > 1) {
             hipLaunchKernelGGL(pg_dl_count, dim3(cdiv((long)(2 * nn - 2 * (size_t)K), 256)), dim3(256), 0, sL, d);
@@ -2024,14 +2033,21 @@ static int dev_lists_wait(phylo_ctx* c, pg_list_counts& m) {
     return PHYLO_OK;
 }
 
-static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf);
+static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf, int G);
 // reverse passes in flight in this process (several host threads, each with its own context): a launch that waits inside the GPU for
 // another launch of its own pass (pg_nodes_rows_all beside pg_coeff_all) assumes the two share the GPU with nobody who waits likewise
 static std::atomic<int> g_backward_in_flight{0};
 
-int phylo_sweep_backward(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf) {
+// G = 0: phylo_sweep_backward (one system); G >= 1: phylo_sweep_backward_batch, a row per group of the last sweep
+static int sweep_backward_guarded(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf, int G) {
+    if (c && c->swept && c->last_graph) {                  // the wrong call for the kept graph: refused, the graph stays
+        if (G == 0 && c->last_G > 1)
+            return fail(c, PHYLO_ESTATE, "the last sweep batched %d systems: phylo_sweep_backward_batch returns a gradient per system", c->last_G);
+        if (G != 0 && G != c->last_G)
+            return fail(c, PHYLO_EINVAL, "phylo_sweep_backward_batch: the last sweep batched %d system(s), asked for %d", c->last_G, G);
+    }
     struct in_flight { in_flight() { ++g_backward_in_flight; } ~in_flight() { --g_backward_in_flight; } } guard;
-    const int rc = sweep_backward_impl(c, d_lam_l, d_lam_r, d_pi, d_Q, perf);
+    const int rc = sweep_backward_impl(c, d_lam_l, d_lam_r, d_pi, d_Q, perf, G);
     if (rc != PHYLO_OK && c) {
         // an early return may have left kernels on the side streams that still read the pinned list image and the graph: join them
         // before anything rebuilds or frees those, and drop the graph (the next backward needs a new sweep)
@@ -2041,6 +2057,15 @@ int phylo_sweep_backward(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double*
         c->last_graph = false;
     }
     return rc;
+}
+
+int phylo_sweep_backward(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf) {
+    return sweep_backward_guarded(c, d_lam_l, d_lam_r, d_pi, d_Q, perf, 0);
+}
+
+int phylo_sweep_backward_batch(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, int G, phylo_stats* perf) {
+    if (G < 1) return fail(c, PHYLO_EINVAL, "phylo_sweep_backward_batch needs G >= 1 (got %d)", G);
+    return sweep_backward_guarded(c, d_lam_l, d_lam_r, d_pi, d_Q, perf, G);
 }
 
 // ---- the reverse pass's driver ("driver"): the form is decided in phylo_revlists.h (pg_plan_form before the
@@ -2054,6 +2079,8 @@ struct rev_pass {
     pg_list_counts n;                    // the lists' counts, from the host builders or from pg_dl_lists
     pg_lookahead x;                      // twisted proposal: the look-ahead lists' counts
     pg_lists L{};                        // the pinned image of the device slab (what the host builders write)
+    const int64_t* anc = nullptr;        // the ancestors the host builders read (a batched sweep's: with global indices)
+    bool batch = false;                  // phylo_sweep_backward_batch: a row per group, the groups' log Z-hat behind them
     hipStream_t sB = nullptr;            // the adopted nodes' chain: the second stream (plan.two), else the context's
     int node_launches = 0, tw_launches = 0;
     std::chrono::steady_clock::time_point host_t0;
@@ -2067,6 +2094,7 @@ static pg_plan_in rev_plan_in(const phylo_ctx* c) {
     in.rev_host_lists = c->env.rev_host_lists; in.one_stream = c->env.grad_one_stream; in.two_streams = c->env.grad_two_streams;
     in.rows_chain = c->env.grad_rows_chain; in.coeff_chain = c->env.grad_coeff_chain;
     in.dl_max_k = PG_DL_MAX_K;
+    in.groups = c->last_G;
     return in;
 }
 
@@ -2077,6 +2105,7 @@ static int rev_bind(rev_pass& p) {
     const int N = c->N, K = c->K, S = c->S, R = N - 1;
     const bool whole = p.plan.whole;
     g.N = N; g.S = S; g.K = K; g.R = R; g.T = p.plan.rows_form ? 1 : (S + PG_NT - 1) / PG_NT; g.jc = c->jc;
+    g.ngrp = c->last_G; g.Kg = K / c->last_G; g.lse_stride = c->last_G > 1 ? R + 1 : 0;   // (the batched sweep's lse: [G][R + 1])
     g.twist = p.plan.twist ? 1 : 0;
     g.leaves = c->d_leaves; g.pool = c->d_pool; g.adj = c->d_adj; g.Pmat = whole ? c->d_gPmat : c->d_Pmat;
     g.pool_ptrs = whole ? (const double* const*)c->d_pool_ptrs : nullptr; g.Kloc = c->Kloc;
@@ -2146,7 +2175,7 @@ static int rev_early(rev_pass& p) {
     // The list kernels need the sweep's ancestors and children and nothing else: they are queued right behind the sweep on its own
     // stream, ahead of the early kernels below (they head the longest chain: lists -> sort -> chunk sums -> adopted nodes).
     if (p.plan.dev_lists) CHK(dev_lists_launch(c, c->stream, c->stream, true, false));
-    hipLaunchKernelGGL(pg_omega, dim3(g.R), dim3(PG_OMEGA_NT), 0, c->stream, g);
+    hipLaunchKernelGGL(pg_omega, dim3(g.R, g.ngrp), dim3(PG_OMEGA_NT), 0, c->stream, g);
     CHK(launch_check(c, "pg_omega"));
     hipLaunchKernelGGL(pg_leafpi, dim3(g.N), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_leafpi"));
@@ -2185,6 +2214,11 @@ static int rev_fork(rev_pass& p) {
     CHK(wait_event_spin(c, c->ev_gcopy));
     if (p.plan.bg_free && !p.plan.dev_lists) CHK(rev_bg_free(p));
     p.host_t0 = std::chrono::steady_clock::now();
+    p.anc = c->h_anc_p;
+    if (!p.plan.dev_lists && p.g.ngrp > 1) {               // the host builders take the one genealogy's global indices
+        pg_global_ancestors(R, K, p.g.Kg, c->h_anc_p, c->h_anc_glob);
+        p.anc = c->h_anc_glob.data();
+    }
     p.L = pg_lists_carve(c->h_csr_p, (size_t)R, (size_t)K);     // (phylo_revlists.h: the builders, tested on the CPU)
     if (!p.plan.dev_lists) pg_lists_clear(p.L, R, K);
     p.sB = p.plan.two ? c->gstream : c->stream;
@@ -2208,7 +2242,7 @@ static int rev_fork(rev_pass& p) {
         HIPCHK(c, hipEventRecord(c->ev_gfork, c->stream));                 // everything launched so far (the early kernels)
         HIPCHK(c, hipStreamWaitEvent(p.sB, c->ev_gfork, 0));
     }
-    if (p.plan.early_free && !p.plan.dev_lists) pg_mark_adopted(R, K, c->h_anc_p, p.L);
+    if (p.plan.early_free && !p.plan.dev_lists) pg_mark_adopted(R, K, p.anc, p.L);
     return PHYLO_OK;
 }
 
@@ -2280,7 +2314,9 @@ static int rev_parents(rev_pass& p) {
     g.chunks_free_only = p.plan.early_free ? 1 : 0;
     g.TS = cdiv(S, 256);
     void* fp = nullptr;
-    CHK(scratch_get(c, 2, ((nn + 31) / 32) * 20 * 8, &fp));
+    // (batched: pg_node_finish's workgroups are cut per (rank event, group))
+    const size_t fin_wgs = g.ngrp > 1 ? (size_t)R * g.ngrp * (((size_t)g.Kg + 31) / 32) : (nn + 31) / 32;
+    CHK(scratch_get(c, 2, fin_wgs * 20 * 8, &fp));
     g.fin_part = (double*)fp;
     if (p.plan.rows_form) {
         void* sp = nullptr;
@@ -2312,7 +2348,7 @@ static int rev_adopters(rev_pass& p) {
     pg_args& g = p.g;
     const int K = g.K, R = g.R;
     if (!p.plan.dev_lists) {
-        pg_build_adopters(R, K, c->h_anc_p, p.L, c->h_cur, p.n);
+        pg_build_adopters(R, K, p.anc, p.L, c->h_cur, p.n);
         // the adopters' lists are all the coefficient chain needs: it runs while the host goes on with the parents' lists
         const size_t ad_ints = (size_t)R * (K + 1) + (size_t)R * K;
         HIPCHK(c, hipMemcpyAsync(c->d_ad_off, c->h_csr_p, ad_ints * 4, hipMemcpyHostToDevice, c->stream));
@@ -2470,17 +2506,20 @@ static int rev_finish(rev_pass& p, double* d_lam_l, double* d_lam_r, double* d_p
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_gjoin, 0));
     }
     if (p.plan.bg_free) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_bgdone, 0));
-    hipLaunchKernelGGL(pg_node_finish, dim3(cdiv((long)R * g.K, 32)), dim3(256), 0, c->stream, g);
+    const long fin_wgs = g.ngrp > 1 ? (long)R * g.ngrp * cdiv(g.Kg, 32) : cdiv((long)R * g.K, 32);
+    hipLaunchKernelGGL(pg_node_finish, dim3((unsigned)fin_wgs), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_node_finish"));
     hipLaunchKernelGGL(pg_scalars, dim3(cdiv((long)R * g.K, 256)), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_scalars"));
-    hipLaunchKernelGGL(pg_reduce, dim3(2 * R + 20), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(pg_reduce, dim3(2 * R + 20 + (p.batch ? 1 : 0), g.ngrp), dim3(256), 0, c->stream, g);
     CHK(launch_check(c, "pg_reduce"));
     // sharded: the pass read node rows from the peers' pools; no owner may write its pool again (its next sweep) before every
     // rank's pass is done -- the barrier makes phylo_sweep_backward a collective call
     if (p.plan.whole) CHK(comm_exchange(c, nullptr, 0, 0, 1));
     HIPCHK(c, hipEventRecord(c->evb1, c->stream));
-    std::vector<double> out((size_t)2 * R + 20);
+    const size_t row = (size_t)2 * R + 20, G = (size_t)g.ngrp;
+    std::vector<double>& out = c->h_gout;
+    out.resize(row * G + (p.batch ? G : 0));
     HIPCHK(c, hipMemcpyAsync(out.data(), c->d_gout, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_gjoin, c->stream));     // (free again: the stream has waited for it above)
     CHK(wait_event_spin(c, c->ev_gjoin));
@@ -2490,10 +2529,13 @@ static int rev_finish(rev_pass& p, double* d_lam_l, double* d_lam_r, double* d_p
         return fail(c, PHYLO_EHIP, "reverse pass: a workgroup of pg_nodes_rows_all gave up waiting for a parent's adjoint tile "
                                        "(PHYLO_GRAD_ROWS_CHAIN=1 runs a launch per rank event instead)");
     }
-    if (d_lam_l) memcpy(d_lam_l, out.data(), (size_t)R * 8);
-    if (d_lam_r) memcpy(d_lam_r, out.data() + R, (size_t)R * 8);
-    if (d_pi) memcpy(d_pi, out.data() + 2 * R, 4 * 8);
-    if (d_Q) memcpy(d_Q, out.data() + 2 * R + 4, 16 * 8);
+    for (size_t gi = 0; gi < G; ++gi) {
+        const double* o = out.data() + gi * row;
+        if (d_lam_l) memcpy(d_lam_l + gi * R, o, (size_t)R * 8);
+        if (d_lam_r) memcpy(d_lam_r + gi * R, o + R, (size_t)R * 8);
+        if (d_pi) memcpy(d_pi + gi * 4, o + 2 * R, 4 * 8);
+        if (d_Q) memcpy(d_Q + gi * 16, o + 2 * R + 4, 16 * 8);
+    }
     if (perf) {
         float ms = 0.f;
         HIPCHK(c, hipEventElapsedTime(&ms, c->evb0, c->evb1));
@@ -2508,12 +2550,13 @@ static int rev_finish(rev_pass& p, double* d_lam_l, double* d_lam_r, double* d_p
     return PHYLO_OK;
 }
 
-static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf) {
+static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, double* d_pi, double* d_Q, phylo_stats* perf, int G) {
     CHK(bind(c));
     if (!c->swept || !c->last_graph)
-        return fail(c, PHYLO_ESTATE, "phylo_sweep_backward needs a preceding sweep with PHYLO_KEEP_GRAPH");
+        return fail(c, PHYLO_ESTATE, "%s needs a preceding sweep with PHYLO_KEEP_GRAPH", G ? "phylo_sweep_backward_batch" : "phylo_sweep_backward");
     rev_pass p;
     p.c = c;
+    p.batch = G != 0;
     p.plan = pg_plan_form(rev_plan_in(c));                 // decision point one: before anything is launched
     CHK(rev_bind(p));
     CHK(rev_early(p));
@@ -2547,6 +2590,34 @@ int phylo_vi_gradients(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, int j
     CHK(phylo_sweep_backward(c, raw, raw + R, raw + 2 * R, raw + 2 * R + 4, bwd));
     CHK(phylo_sweep_fetch(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, logZ, fwd));
     pt_chain_rules(R, jc, Q, pi, lam.data(), lam.data() + R, raw, raw + R, raw + 2 * R, raw + 2 * R + 4, grads);
+    return PHYLO_OK;
+}
+
+// ... for G systems behind one set of launches: row g of `grads` is the gradient of log Z-hat_g alone (no mean is taken here)
+int phylo_vi_gradients_batch(phylo_ctx* c, const uint64_t* seeds, int G, uint32_t flags, int jc, const double* vars, double* logZ, double* grads,
+                             phylo_stats* fwd, phylo_stats* bwd) {
+    CHK(bind(c));
+    if (!vars || !grads || !seeds) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients_batch: NULL argument");
+    if (G < 1 || G > PK_MAX_GROUPS) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients_batch: 1 <= G <= %d (got %d)", PK_MAX_GROUPS, G);
+    const int R = c->N - 1;
+    if (R > 64) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients_batch: at most 65 taxa");
+    double Q[16], pi[4];
+    std::vector<double>& lam = c->h_vi_lam;
+    lam.resize((size_t)2 * R);
+    for (int r = 0; r < 2 * R; ++r) lam[r] = std::exp(vars[r]);
+    if (jc) pt_jc_Q(Q); else pt_get_Q(vars + 2 * R, Q);
+    pt_get_pi(vars + 2 * R + 16, pi);
+    CHK(phylo_set_model(c, Q, pi, lam.data(), lam.data() + R, jc));
+    CHK(phylo_sweep_batch_async(c, seeds, G, flags | PHYLO_KEEP_GRAPH));
+    // rows of the driver's own host buffer: d_lam_l, d_lam_r, d_pi, d_Q contiguous per group, the groups' log Z-hat behind them
+    CHK(sweep_backward_guarded(c, nullptr, nullptr, nullptr, nullptr, bwd, G));
+    CHK(phylo_sweep_fetch(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fwd));   // (the timeout word, the sweep's stats)
+    const size_t row = (size_t)2 * R + 20;
+    for (int g = 0; g < G; ++g) {
+        const double* raw = c->h_gout.data() + (size_t)g * row;
+        pt_chain_rules(R, jc, Q, pi, lam.data(), lam.data() + R, raw, raw + R, raw + 2 * R, raw + 2 * R + 4, grads + (size_t)g * row);
+        if (logZ) logZ[g] = c->h_gout[(size_t)G * row + g];
+    }
     return PHYLO_OK;
 }
 
@@ -2643,6 +2714,23 @@ int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int tw
     return PHYLO_OK;
 }
 
+int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,
+                                   int passes_in_flight, uint32_t* mask) {
+    if (N < 2 || K < 1 || G < 1 || K % G != 0 || S < 1 || TS < 1 || n_slow < 0 || coeff_wgs < 0 || !mask)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_reverse_plan_batch: bad arguments");
+    pg_plan_in in{};
+    in.N = N; in.K = K; in.K_local = K; in.S = S; in.world = 1;
+    in.twist = false; in.marks = true;                      // (a batched sweep that keeps its graph: plain proposal, lazy)
+    in.rev_host_lists = switches & 1; in.one_stream = switches & 2; in.two_streams = switches & 4;
+    in.rows_chain = switches & 8; in.coeff_chain = switches & 16;
+    in.dl_max_k = PG_DL_MAX_K;
+    in.groups = G;
+    pg_plan p = pg_plan_form(in);
+    pg_plan_chains(p, (long)n_slow, TS, (long)coeff_wgs, passes_in_flight, N - 1);
+    *mask = pg_plan_mask(p);
+    return PHYLO_OK;
+}
+
 static int debug_device_lists_run(phylo_ctx* c, int32_t* lists, int64_t n_lists, int32_t* meta, int n_meta);
 
 int phylo_debug_device_lists_of(phylo_ctx* c, const int64_t* ancestors, const int32_t* child, int32_t* lists, int64_t n_lists,
@@ -2663,7 +2751,7 @@ int phylo_debug_device_lists_of(phylo_ctx* c, const int64_t* ancestors, const in
 
 int phylo_debug_device_lists(phylo_ctx* c, int32_t* lists, int64_t n_lists, int32_t* meta, int n_meta, int64_t* ancestors, int32_t* child) {
     CHK(bind(c));
-    if (!c->swept || !c->last_graph || !c->last_graph_marks || c->last_graph_twist || c->Kloc != c->K || c->K > PG_DL_MAX_K)
+    if (!c->swept || !c->last_graph || !c->last_graph_marks || c->last_graph_twist || c->Kloc != c->K || c->K / c->last_G > PG_DL_MAX_K)
         return fail(c, PHYLO_ESTATE, "phylo_debug_device_lists needs a preceding lazy sweep with PHYLO_KEEP_GRAPH and the plain proposal, not sharded, K <= %d", PG_DL_MAX_K);
     const int R = c->N - 1, K = c->K;
     CHK(debug_device_lists_run(c, lists, n_lists, meta, n_meta));

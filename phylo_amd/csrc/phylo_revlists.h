@@ -66,8 +66,8 @@ inline void pg_lists_clear(const pg_lists& L, int R, int K) {
     memset(L.slow_flag, 0, nn * 4);
 }
 
-// Adopters of every particle at every rank event (anc[r-1][k'] = the particle k' adopted at rank event r; ascending k' within a
-// list), and the adopted particles (r * K + k), grouped by rank event: adp[ev_adp0[r] .. ev_adp0[r+1]); fills ev_adp0 and n_adp.
+// Adopters of every particle at every rank event (anc[r-1][k'] = the particle k' adopted at rank event r, a GLOBAL index: the
+// caller adds g K / G to the group-local ancestors of a batched sweep (pg_global_ancestors); ascending k' within a list), and the adopted particles (r * K + k), grouped by rank event: adp[ev_adp0[r] .. ev_adp0[r+1]); fills ev_adp0 and n_adp.
 // A few ancestors take nearly all the draws, so counters and cursors are chains of store-to-load forwards on one address: the
 // particles are taken as four contiguous quarters with a counter row each (four independent chains), whose prefix sums give
 // every quarter its own cursor into an ancestor's list.
@@ -107,6 +107,14 @@ inline void pg_build_adopters(int R, int K, const int64_t* anc, const pg_lists& 
     ev_adp0[R] = n_adp;
     if (R == 1) ev_adp0[0] = 0;
     o.n_adp = n_adp;
+}
+
+// The ancestors of a batched sweep are indices inside the adopter's group of Kg particles: as indices of the one K-particle genealogy.
+inline void pg_global_ancestors(int R, int K, int Kg, const int64_t* anc, std::vector<int64_t>& out) {
+    out.resize(R > 1 ? (size_t)(R - 1) * K : 0);
+    for (int r = 0; r + 1 < R; ++r)
+        for (int g = 0, k = 0; k < K; ++g)
+            for (const int end = k + Kg; k < end; ++k) out[(size_t)r * K + k] = anc[(size_t)r * K + k] + (int64_t)g * Kg;
 }
 
 // Bit 2 of slow_flag for every node somebody adopted (r - 1, anc[r-1][k]): what pg_build_parents needs of the adopters when the early
@@ -316,6 +324,7 @@ struct pg_plan_in {
     bool twist, marks;                 // the last sweep: twisted proposal; lazy, left marks of the adopted nodes
     bool rev_host_lists, one_stream, two_streams, rows_chain, coeff_chain;   // the PHYLO_REV_HOST_LISTS / PHYLO_GRAD_* switches
     int dl_max_k;                      // PG_DL_MAX_K of phylo_revlists_dev.h
+    int groups;                        // batched sweep: independent systems of K / groups particles in one genealogy (0 or 1: one sweep)
 };
 struct pg_plan {
     // pg_plan_form
@@ -344,7 +353,10 @@ inline pg_plan pg_plan_form(const pg_plan_in& in) {
     // (never on a sharded context: the device lists are what gates the one-launch chains, pg_coeff_all / pg_nodes_rows_all, which
     //  hand values between workgroups and assume nobody else on the GPU waits likewise -- sharded ranks sharing a GPU run their
     //  passes at once; a sharded pass takes the host lists and a launch per rank event)
-    p.dev_lists = p.early_free && !p.whole && !in.rev_host_lists && in.K_local == in.K && in.K <= in.dl_max_k;
+    // (the one limit that is per group: pg_dl_adopters sorts a group's adopters of one rank event in one workgroup; everything else
+    //  -- the node kernels, the parents' sort, the limits of the one-launch chains in pg_plan_chains -- sees the total K)
+    const int Kg = in.groups > 1 ? in.K / in.groups : in.K;
+    p.dev_lists = p.early_free && !p.whole && !in.rev_host_lists && in.K_local == in.K && Kg <= in.dl_max_k;
     // (the list kernels' sort goes to the second stream as soon as the host has seen the sweep end: queued there behind the lists'
     //  event, it neither waits for the host to read the counts nor holds up the coefficient chain on the context's stream)
     p.sort_early = p.dev_lists && !in.one_stream;

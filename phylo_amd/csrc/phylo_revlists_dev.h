@@ -1,10 +1,10 @@
 // phylo_revlists_dev.h -- the integer lists of the reverse pass built ON THE DEVICE (round 3; phylo_revlists.h is the host form, kept
-// for the twisted proposal, the tile form, sweeps without marks, K > 8192, and as the test reference).  Plain proposal, rows form,
+// for the twisted proposal, the tile form, sweeps without marks, more than 8192 particles per group, and as the test reference).  Plain proposal, rows form,
 // after a lazy sweep (the early pg_nodes_free): who adopted whom per rank event, which nodes have which parents, heavy nodes'
 // chunks, the flagged nodes by rank event -- in the layout pg_lists_carve gives the slab, so the reverse kernels do not care who
 // built it.
 //
-//   pg_dl_adopters one workgroup per rank event: a STABLE block radix sort (rocPRIM's block primitive) of the K adopters by ancestor
+//   pg_dl_adopters one workgroup per (rank event, group of a batched sweep): a STABLE block radix sort (rocPRIM's block primitive) of the K adopters by ancestor
 //                  is ad_idx's row (ascending adopter within an ancestor, like the host's counting sort); the sorted keys, searched
 //                  per ancestor, give ad_off's row and who was adopted at all.  No atomics: a few ancestors take nearly every draw,
 //                  and K increments of one counter are K serial round trips;
@@ -29,8 +29,8 @@
 #include "phylo_revlists.h"
 
 struct pg_dl_args {
-    int N, R, K;
-    const int64_t* anc;                // [R-1][K] ancestors (device)
+    int N, R, K, Kg;                   // Kg: particles per group of a batched sweep (K when there is one)
+    const int64_t* anc;                // [R-1][K] ancestors (device), indices inside the adopter's group
     const int32_t* child;              // [R][K][2] node ids (device)
     int32_t *cnt_par, *ticket;         // [R K], [1]: zeroed by pg_dl_adopters
     int32_t* adopted;                  // [R K]: somebody adopted the node (pg_dl_adopters writes every row)
@@ -41,7 +41,7 @@ struct pg_dl_args {
 };
 #define PG_DL_META_INTS(R) (2 * ((R) + 1) + 4)
 #define PG_DL_BLOCK 1024
-#define PG_DL_MAX_K 8192               // pg_dl_adopters: 1024 threads x 8 adopters
+#define PG_DL_MAX_K 8192               // pg_dl_adopters: 1024 threads x 8 adopters (a batched sweep: per group)
 
 template <int ITEMS>
 struct pg_dl_sort {
@@ -49,28 +49,31 @@ struct pg_dl_sort {
     static constexpr size_t storage_bytes = (sizeof(typename type::storage_type) + 15) & ~(size_t)15;
 };
 
-// grid R (workgroup = rank event), dynamic LDS: the sort's storage, then K sorted keys.  bits = bit length of K (the padding key).
+// grid (R, G) (workgroup = rank event of one group), dynamic LDS: the sort's storage, then Kg sorted keys.  bits = bit length of Kg
+// (the padding key).  The sweep's ancestors are indices inside the adopter's group: keys stay group-local, values and offsets are
+// global (+ g Kg) -- what the host builders give for the block-diagonal genealogy with global ancestors.
 template <int ITEMS>
 __global__ __launch_bounds__(PG_DL_BLOCK) void pg_dl_adopters(const pg_dl_args a, unsigned bits) {
     extern __shared__ __align__(16) unsigned char pg_dl_lds[];
     typedef typename pg_dl_sort<ITEMS>::type sort_t;
     typename sort_t::storage_type& st = *reinterpret_cast<typename sort_t::storage_type*>(pg_dl_lds);
     unsigned int* skeys = reinterpret_cast<unsigned int*>(pg_dl_lds + pg_dl_sort<ITEMS>::storage_bytes);
-    const int r = blockIdx.x, K = a.K, tid = threadIdx.x;
-    for (int x = tid; x < K; x += PG_DL_BLOCK) a.cnt_par[(size_t)r * K + x] = 0;   // what pg_dl_count and pg_dl_lists count into
+    const int r = blockIdx.x, K = a.Kg, k0 = (int)blockIdx.y * K, tid = threadIdx.x;
+    const bool last_group = blockIdx.y + 1 == gridDim.y;
+    for (int x = tid; x < K; x += PG_DL_BLOCK) a.cnt_par[(size_t)r * a.K + k0 + x] = 0;   // what pg_dl_count and pg_dl_lists count into
     if (r == 0) {                                            // nobody adopts at rank event 0, nobody adopts the last rank event's nodes
-        if (tid == 0) *a.ticket = 0;
-        for (int x = tid; x <= K; x += PG_DL_BLOCK) a.L.ad_off[x] = 0;
-        for (int x = tid; x < K; x += PG_DL_BLOCK) a.adopted[(size_t)(a.R - 1) * K + x] = 0;
+        if (tid == 0 && k0 == 0) *a.ticket = 0;
+        for (int x = tid; x < K + (last_group ? 1 : 0); x += PG_DL_BLOCK) a.L.ad_off[k0 + x] = 0;
+        for (int x = tid; x < K; x += PG_DL_BLOCK) a.adopted[(size_t)(a.R - 1) * a.K + k0 + x] = 0;
         return;
     }
-    const int64_t* anc = a.anc + (size_t)(r - 1) * K;
+    const int64_t* anc = a.anc + (size_t)(r - 1) * a.K + k0;
     unsigned int key[ITEMS], val[ITEMS];
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         const int k = tid * ITEMS + j;
         key[j] = k < K ? (unsigned int)anc[k] : (unsigned int)K;
-        val[j] = (unsigned int)k;
+        val[j] = (unsigned int)(k0 + k);
     }
     sort_t().sort(key, val, st, 0u, bits);                  // stable: ascending adopter within an ancestor
 #pragma unroll
@@ -78,18 +81,18 @@ __global__ __launch_bounds__(PG_DL_BLOCK) void pg_dl_adopters(const pg_dl_args a
         const int p = tid * ITEMS + j;
         if (p < K) {
             skeys[p] = key[j];
-            a.L.ad_idx[(size_t)r * K + p] = (int32_t)val[j];
+            a.L.ad_idx[(size_t)r * a.K + k0 + p] = (int32_t)val[j];
         }
     }
     __syncthreads();
-    for (int x = tid; x <= K; x += PG_DL_BLOCK) {            // first position with key >= x
+    for (int x = tid; x < K + (last_group ? 1 : 0); x += PG_DL_BLOCK) {   // first position with key >= x (the next group writes its own first offset)
         int lo = 0, hi = K;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
             if (skeys[mid] < (unsigned int)x) lo = mid + 1; else hi = mid;
         }
-        a.L.ad_off[(size_t)r * (K + 1) + x] = lo;
-        if (x < K) a.adopted[(size_t)(r - 1) * K + x] = lo < K && skeys[lo] == (unsigned int)x;
+        a.L.ad_off[(size_t)r * (a.K + 1) + k0 + x] = k0 + lo;
+        if (x < K) a.adopted[(size_t)(r - 1) * a.K + k0 + x] = lo < K && skeys[lo] == (unsigned int)x;
     }
 }
 

@@ -154,14 +154,24 @@ class Trainer:
     """One device context sized for a minibatch of sites; `step` = sweep + reverse pass + update."""
 
     def __init__(self, genome_NxSxA, K, variables, optimizer, batch_sites, device=0, flags=_ffi.FLAGS_DEFAULT, nested=False, M=1,
-                 native=True, shard_with=None):
+                 native=True, shard_with=None, batched=1):
         """nested: the twisted proposal of vncsmc.py with M sub-samples per pair; its look-ahead potentials are differentiated
         like everything else (vncsmc.py:379-416 has no stop_gradient).  native: the host half of a step (model from the
         variables, chain rules, optimiser update) runs in the library (phylo_vi_gradients / phylo_vi_apply) instead of the NumPy
         statements of this module (~60 small array operations, 65 us of a 0.9 ms step); same formulas.
         shard_with: a context that has joined the ranks (phylo_comm_init): this trainer's context joins its communicator and every
         step trains ONE K-particle system split over the ranks -- every rank must step with the same seeds, in the same order, and
-        every rank gets the same gradient bits (the plain proposal only)."""
+        every rank gets the same gradient bits (the plain proposal only).
+        batched: G > 1 sizes the context for G K particles; a step over G seeds (seed + more_seeds) is then ONE batched sweep and
+        ONE reverse pass over its block-diagonal genealogy (phylo_vi_gradients_batch / phylo_sweep_backward_batch) instead of G
+        sweep-and-reverse-pass pairs one after the other: every system's sweep keeps its bits, the gradients agree to rounding.
+        Plain proposal on one context: ValueError with nested or shard_with."""
+        self.batched = int(batched)
+        if self.batched < 1:
+            raise ValueError("batched must be >= 1")
+        if self.batched > 1 and (nested or shard_with is not None):
+            raise ValueError("a batched trainer (batched=%d) needs the plain proposal on an unsharded context: not with nested=True "
+                             "or shard_with" % self.batched)
         self.native = bool(native)
         self.genome = np.asarray(genome_NxSxA, dtype=np.float64)
         self.v, self.opt = variables, optimizer
@@ -170,7 +180,7 @@ class Trainer:
             self.flags |= _ffi.TWISTING
         self.M = int(M) if nested else 1
         N = self.genome.shape[0]
-        self.ctx = _ffi.Context(K, N, int(batch_sites), device=device)
+        self.ctx = _ffi.Context(K * self.batched, N, int(batch_sites), device=device)
         if shard_with is not None:
             if nested:
                 self.ctx.close()
@@ -207,11 +217,54 @@ class Trainer:
                'backward_lists': 'device' if bwd.merge_launches else 'host', 'backward_launches': bwd.n_launches}
         return logZ, self.v.unpack_grads(g), raw, g
 
+    def _samples_batched(self, sites, seeds):
+        """The (logZ, grads) samples of len(seeds) systems from one batched sweep and one reverse pass, and the raw timings."""
+        sites = np.asarray(sites)
+        if self._sites is None or not np.array_equal(sites, self._sites):
+            self.ctx.set_leaves(self.genome[:, sites, :])
+            self._sites = sites.copy()
+        seeds = [int(s) for s in seeds]
+        if self.native:
+            z, g, fwd, bwd = self.ctx.vi_gradients_batch(seeds, self.flags, self.v.jc, self.v.pack())
+            raw = {'forward_ms': fwd.sweep_ms, 'backward_ms': bwd.sweep_ms, 'backward_host_ms': bwd.merge_ms,
+                   'backward_lists': 'device' if bwd.merge_launches else 'host', 'backward_launches': bwd.n_launches}
+            return [(float(z[i]), self.v.unpack_grads(g[i])) for i in range(len(seeds))], raw
+        Q, pi, lam_l, lam_r = self.v.evaluate()
+        self.ctx.set_model(Q, pi, lam_l, lam_r, jc69_closed_form=self.v.jc)
+        self.ctx.sweep_batch_async(seeds, self.flags)
+        raw = self.ctx.sweep_backward_batch(len(seeds))      # queued right behind the sweep
+        z = self.ctx.sweep_fetch_logz(len(seeds))
+        raw['forward_ms'] = self.ctx.sweep_fetch(arrays=False)['stats']['sweep_ms']
+        samples = []
+        for i in range(len(seeds)):
+            raw_i = {n: raw[n][i] for n in ('d_lam_l', 'd_lam_r', 'd_pi', 'd_Q')}
+            samples.append((float(z[i]), chain_rules(self.v, Q, pi, lam_l, lam_r, raw_i)))
+        return samples, raw
+
+    def _step_batched(self, sites, seed, more_seeds, comm_ctx):
+        seeds = [seed] + list(more_seeds)
+        if len(seeds) != self.batched:
+            raise ValueError("a trainer with batched=%d steps over %d seeds (got %d)" % (self.batched, self.batched, len(seeds)))
+        samples, raw = self._samples_batched(sites, seeds)
+        logZ, grads = mean_of_samples(samples, comm_ctx)    # (the same rows in the same order as the serial path)
+        if self.native:
+            packed = np.concatenate([np.asarray(grads[n], dtype=np.float64).reshape(-1) for n in ('a_l', 'a_r', 'y_q', 'y_station') if n in grads])
+            if packed.shape[0] < self.v.pack().shape[0]:
+                packed = np.concatenate([packed, np.zeros(20)])
+            self.opt.apply_packed(self.v, packed)
+        else:
+            self.opt.apply(self.v, grads)
+        self.last = {'logZ': logZ, 'grads': grads, 'raw': raw}
+        return -logZ
+
     def step(self, sites, seed, more_seeds=(), comm_ctx=None):
         """_, cost = sess.run([self.optimizer, self.cost], feed_dict={self.core: data_batch})  (vcsmc.py:534).
         Data-parallel training: more_seeds = further independent particle systems swept by this process for the same step,
         comm_ctx = a context that has joined the ranks (every rank sweeps its own systems with its own seeds); the optimiser takes
-        ONE step on the mean gradient of all of them (mean_of_samples), the same step on every rank."""
+        ONE step on the mean gradient of all of them (mean_of_samples), the same step on every rank.
+        A trainer built with batched=G takes its G = 1 + len(more_seeds) systems in one batched call."""
+        if self.batched > 1:
+            return self._step_batched(sites, seed, more_seeds, comm_ctx)
         if self.native:
             logZ, grads, raw, packed = self._gradients_native(sites, seed)
         else:

@@ -362,9 +362,12 @@ class VCSMC:
         self.optimizer = train_mod.make_optimizer(getattr(self.args, 'optimizer', ''), self.lr)   # vcsmc.py:488-491
         nested = bool(getattr(self.args, 'nested', False))
         trainer = None
+        # --grad_batched true: the n_local systems of a step share one batched sweep and one reverse pass (train.Trainer, batched)
+        batched = n_local if bool(getattr(self.args, 'grad_batched', False)) and n_local > 1 else 1
         if len(slices) > 1:
             trainer = train_mod.Trainer(self.genome_NxSxA, self.K, self.variables, self.optimizer, len(slices[0]),
-                                        device=self._device, nested=nested, M=self.M, shard_with=ctx if sharded else None)
+                                        device=self._device, nested=nested, M=self.M, shard_with=ctx if sharded else None,
+                                        batched=batched)
         initial = self.sample_phylogenies()
         print('===================\nInitial evaluation of ELBO:', round(initial, 3))
         print('Initial jump chain:')

@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--tree_summary`, `--tree_branches` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -42,6 +42,11 @@ def parse_args(argv=None):
     parser.add_argument('--grad_samples', type=int, default=1,
                         help='independent particle systems swept per optimiser step (and per rank with --train_parallel replicas); the '
                              'step is taken on their mean gradient')
+    parser.add_argument('--grad_batched', default=False, type=lambda x: (str(x).lower() == 'true'),
+                        help='with --grad_samples G > 1: the G particle systems of a step share ONE batched sweep and ONE reverse pass '
+                             '(every rank batches its own G systems under --train_parallel replicas) instead of G sweep-and-reverse-pass '
+                             'pairs one after the other; same seeds, same sweeps, gradients equal to rounding.  Plain proposal, not '
+                             'with --train_parallel sharded')
     parser.add_argument('--ambiguity', choices=('error', 'iupac'), default='error',
                         help="characters outside the dataset's alphabet: KeyError like the reference, or IUPAC indicator rows")
     parser.add_argument('--tree_summary', default=False, type=lambda x: (str(x).lower() == 'true'),
@@ -59,6 +64,12 @@ def parse_args(argv=None):
     if args.train_parallel == 'sharded' and args.nested:
         parser.error('--train_parallel sharded trains the plain proposal only: the reverse pass of a twisted sweep needs the '
                      'whole particle system on one GPU (use --train_parallel replicas or redundant with --nested true)')
+    if args.grad_batched and args.nested:
+        parser.error('--grad_batched true batches the plain proposal only: not with --nested true (the twisted proposal trains '
+                     'its --grad_samples systems one after the other)')
+    if args.grad_batched and args.train_parallel == 'sharded':
+        parser.error('--grad_batched true needs every particle system whole on one GPU: not with --train_parallel sharded (use '
+                     '--train_parallel replicas or redundant)')
     return args
 
 

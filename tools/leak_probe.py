@@ -36,6 +36,8 @@ def cycle(i):
         c.sweep_backward()
         c.sweep_batch_async([1, 2, 3, 4])
         c.sweep_fetch()
+        c.sweep_batch_async([1, 2, 3, 4], _ffi.FLAGS_DEFAULT | _ffi.KEEP_GRAPH)   # the batched graph and its reverse pass
+        c.sweep_backward_batch(4)
 
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 30

@@ -1,5 +1,8 @@
 """Timing of one VI training step (sweep with the graph kept + reverse pass + host update) and a short ELBO
-trajectory.  python tools/train_probe.py [--K 2048] [--sites 898] [--steps 20] [--epochs 0]"""
+trajectory.  python tools/train_probe.py [--K 2048] [--sites 898] [--steps 20] [--epochs 0]
+--batched G: one batched step over G particle systems of K particles each (one batched sweep, one reverse pass) next to G serial
+steps on the same model and seeds in the same process; medians of --steps steps after 3 warm-ups, appended to
+profiles/train_batched_probe.jsonl."""
 import argparse
 import json
 import os
@@ -21,11 +24,49 @@ ap.add_argument('--jcmodel', action='store_true')
 ap.add_argument('--nested', action='store_true')
 ap.add_argument('--phases', action='store_true')
 ap.add_argument('--M', type=int, default=1)
+ap.add_argument('--batched', type=int, default=0)
 a = ap.parse_args()
 
 genome = load_dataset(a.dataset)['genome']
 N, S, _ = genome.shape
 B = a.sites or S
+if a.batched > 1:
+    Gn = a.batched
+    rng = np.random.default_rng(0)
+    sites = np.sort(rng.permutation(S)[:B])                # one minibatch for every step: the leaves stay on the device
+    res = {}
+    for name, batched in (('serial', 1), ('batched', Gn)):
+        # lr = 0: every step sees the same model, so the two runs time the same work on the same seeds
+        tr = T.Trainer(genome, a.K, T.Variables(N, np.log(10.0), a.jcmodel), T.make_optimizer('GradientDescentOptimizer', 0.0), B,
+                       batched=batched)
+        fw, bw, wall = [], [], []
+        for i in range(a.steps + 3):
+            seeds = [i + (g << 32) for g in range(Gn)]
+            t0 = time.perf_counter()
+            if batched > 1:
+                tr.step(sites, seeds[0], seeds[1:])
+                f, b = tr.last['raw']['forward_ms'], tr.last['raw']['backward_ms']
+            else:                                           # G sweep-and-reverse-pass pairs one after the other (what Trainer.step does)
+                f = b = 0.0
+                for sd in seeds:
+                    tr.step(sites, sd)
+                    f += tr.last['raw']['forward_ms']
+                    b += tr.last['raw']['backward_ms']
+            t1 = time.perf_counter()
+            if i >= 3:
+                fw.append(f); bw.append(b); wall.append((t1 - t0) * 1e3)
+        res[name] = {'forward_ms': float(np.median(fw)), 'backward_ms': float(np.median(bw)), 'step_wall_ms': float(np.median(wall)),
+                     'step_wall_ms_min': float(np.min(wall)), 'step_wall_ms_p25': float(np.percentile(wall, 25)),
+                     'step_wall_ms_p75': float(np.percentile(wall, 75)), 'backward_lists': tr.last['raw']['backward_lists']}
+        tr.close()
+    line = {'dataset': a.dataset, 'K_per_system': a.K, 'G': Gn, 'N': N, 'sites': B, 'steps': a.steps, 'serial_G_steps': res['serial'],
+            'batched_step': res['batched'], 'ratio_serial_over_batched': res['serial']['step_wall_ms'] / res['batched']['step_wall_ms']}
+    print(json.dumps(line))
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'train_batched_probe.jsonl')
+    with open(out, 'a') as fh:
+        fh.write(json.dumps(line) + '\n')
+    sys.exit(0)
+
 v = T.Variables(N, np.log(10.0), a.jcmodel)
 tr = T.Trainer(genome, a.K, v, T.make_optimizer('Adam', 0.01), B, nested=a.nested, M=a.M)
 rng = np.random.default_rng(0)
