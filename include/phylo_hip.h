@@ -237,6 +237,8 @@ int phylo_sweep_backward_batch(phylo_ctx* ctx, double* d_lam_l, double* d_lam_r,
  * phylo_vi_gradients: model from the variables (vcsmc.py:133-148; jc != 0: the JC69 constants) -> phylo_set_model -> sweep with
  * PHYLO_KEEP_GRAPH on the context's leaves -> phylo_sweep_backward -> chain rules; grads = d logZ / d variables, packed alike
  * (zeros for y_q, y_station under JC69).  fwd / bwd (may be NULL): phylo_sweep_fetch's and phylo_sweep_backward's stats.
+ * Any number of taxa the context accepts (2 ... 512; the twisted proposal: C(N,2) M <= 2^20); the arguments are checked before
+ * phylo_set_model and the sweep, so a refused call (PHYLO_EINVAL: NULL vars or grads) leaves nothing in flight.
  * On a sharded context phylo_vi_gradients is a collective call like phylo_sweep_backward (every rank passes the same seed and
  * variables: it is ONE particle system) and every rank receives the same gradient bits.
  * phylo_vi_apply: kind 0 tf.train.GradientDescentOptimizer (var += lr d logZ / d var), 1 tf.train.AdamOptimizer (TF 1.15
@@ -244,7 +246,7 @@ int phylo_sweep_backward_batch(phylo_ctx* ctx, double* d_lam_l, double* d_lam_r,
 int phylo_vi_gradients(phylo_ctx* ctx, uint64_t seed, uint32_t flags, int M, int jc, const double* vars, double* logZ, double* grads,
                        phylo_stats* fwd, phylo_stats* bwd);
 /* phylo_vi_gradients for G independent particle systems of K / G particles behind one set of launches (seeds[G]; plain proposal):
- * logZ[G], grads[G][2 (N-1) + 20], row g the gradient of log Z-hat_g with respect to the variables. */
+ * logZ[G], grads[G][2 (N-1) + 20], row g the gradient of log Z-hat_g with respect to the variables.  2 ... 512 taxa alike. */
 int phylo_vi_gradients_batch(phylo_ctx* ctx, const uint64_t* seeds, int G, uint32_t flags, int jc, const double* vars, double* logZ,
                              double* grads, phylo_stats* fwd, phylo_stats* bwd);
 int phylo_vi_apply(int n_taxa, int jc, double* vars, const double* grads, int kind, double lr, double beta1, double beta2, double eps,

@@ -92,8 +92,10 @@ struct pg_args {
     unsigned int row_epoch;            // this reverse pass's value of row_done (never 0)
     unsigned int* row_timeout;         // set when a wait of pg_nodes_rows_all gave up
     unsigned int* coeff_done;          // [R] or NULL: == row_epoch when pg_coeff of that rank event is complete (pg_nodes_rows_all beside the chain)
-    unsigned int* coeff_ticket;        // [R]: workgroups of that launch that have finished (the last one resets it)
-    unsigned long long coeff_mask;     // bit r: rank event r has a pg_coeff launch to wait for
+    unsigned int* coeff_ticket;        // [R]: workgroups of that launch that have finished (pg_G zeroes all R at the head of every pass)
+    const int32_t* ev_adp0;            // [R + 1] (set with coeff_done): pg_dl_lists' starts of every rank event's adopted particles, on the
+                                       // device -- rank event r has a pg_coeff launch to wait for when ev_adp0[r + 1] > ev_adp0[r].  Any R:
+                                       // written before the pass's launches, constant during them (plain loads)
     int TS;
     double *om, *G;                    // [R][K]
     double* C;                         // [R][K][N]: coefficient of sum_s log(pi . X) of every root slot after rank event r
@@ -369,7 +371,8 @@ __global__ __launch_bounds__(64) void pg_G(pg_args a) {
     }
     if (lane == 0) a.G[t] = a.om[t] - sub;
     // (the tickets of the coefficient launches behind this one start at zero whatever an earlier, failed pass left in them)
-    if (a.coeff_ticket && blockIdx.x == 0 && lane < a.R) a.coeff_ticket[lane] = 0u;
+    if (a.coeff_ticket && blockIdx.x == 0)
+        for (int i = lane; i < a.R; i += 64) a.coeff_ticket[i] = 0u;
 }
 
 // ---- g3: root-slot coefficients, one rank event per launch (newest first) ---------------------------------
@@ -518,7 +521,7 @@ __global__ __launch_bounds__(256) void pg_coeff_all(pg_args a, pg_coeff_plan pl)
     const int local = b - pl.first[r], ny = pl.ny[r];
     const int bx = local / ny, by = local - bx * ny;
     const int total = r > 0 ? pl.first[r - 1] - pl.first[r] : (int)gridDim.x - pl.first[r];
-    const bool waits = r + 1 < a.R - 1 && ((a.coeff_mask >> (r + 1)) & 1ull);   // rank event r + 1 has coefficients of its own
+    const bool waits = r + 1 < a.R - 1 && a.ev_adp0[r + 2] > a.ev_adp0[r + 1];   // rank event r + 1 has coefficients of its own
     const unsigned int newer = waits ? (unsigned int)(pl.first[r] - pl.first[r + 1]) : 0u;   // that rank event's workgroups
     pg_coeff_body(a, r, pl.adp0[r], bx, by, (unsigned int)total, waits ? a.coeff_ticket + r + 1 : nullptr, newer);
 }
@@ -876,6 +879,17 @@ __global__ __launch_bounds__(256) void pg_fill_free(pg_args a) {
     for (int slot = 0; slot < a.N - r - 1; ++slot) a.C[t * a.N + slot] = om;
 }
 
+// The marks of a sweep that left none (it stored every node): node (r, a) is marked when a particle k of rank event r + 1 adopted it,
+// a = anc[r][k] inside k's group of Kg particles.  Plain vector stores of the same value; the marks were cleared before.
+__global__ __launch_bounds__(256) void pg_mark_adopted_dev(const int64_t* anc, unsigned int* mark, int R, int K, int Kg) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)(R - 1) * K) return;
+    const int k = (int)(t % (size_t)K);
+    const int64_t a = anc[t];
+    if (a < 0 || a >= Kg) return;                            // (never after a sweep; nothing is written out of bounds whatever anc holds)
+    mark[t - (size_t)k + (size_t)(k / Kg) * Kg + (size_t)a] = 1u;
+}
+
 // Nodes nobody merged again -- all but the few adopted ones, of ALL rank events in one launch: one WAVE per node (grid R K / 4;
 // a flagged node's wave leaves at once: pg_nodes_rows takes it).  Their adjoint is the own term alone, alpha pi / (pi . X), so one
 // pass over the sites does everything.  The node's own row is recomputed from the children, (L P_l) o (R P_r) as in the forward
@@ -1045,7 +1059,7 @@ __device__ __forceinline__ void pg_nodes_rows_body(const pg_args& a, int r_arg, 
     for (int i = 0; i < PG_PART; ++i) acc[i] = 0.0;
     const double lik = pg_dot4(pi[0], x[0], pi[1], x[1], pi[2], x[2], pi[3], x[3]);
     if constexpr (ALL) {                                     // the launch runs beside the coefficient chain: rank event r's must be complete
-        if (a.coeff_done && ((a.coeff_mask >> r) & 1ull)) {  // (uniform)
+        if (a.coeff_done && a.ev_adp0[r + 1] > a.ev_adp0[r]) {   // (uniform; r + 1 <= R)
             if (tid == 0) {
                 unsigned int spins = 0;
                 while (__hip_atomic_load(a.coeff_done + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.row_epoch) {

@@ -170,6 +170,7 @@ struct phylo_ctx {
     size_t htw_rows = 0;                 // rows the history holds
     std::vector<int64_t> h_joff;
     bool last_graph_twist = false, last_graph_marks = false;   // marks: the sweep was lazy, d_mark says which nodes were adopted
+    bool last_graph_eager = false;       // the sweep stored every node and left no marks, and its reverse pass can use them: rev_marks
     int last_M = 1;
     // graph kept for the reverse pass (PHYLO_KEEP_GRAPH; allocated on first use)
     int32_t *d_hroots = nullptr, *d_hcnt = nullptr, *d_pos = nullptr;   // [(R+1)][K][N], [(R+1)][K][N], [R][K][N]
@@ -193,6 +194,7 @@ struct phylo_ctx {
     hipEvent_t ev_leaves = nullptr;
     uint32_t *h_pub = nullptr, *hd_pub = nullptr;
     int32_t *h_dlmeta = nullptr, *hd_dlmeta = nullptr;   // what pg_dl_lists tells the host (phylo_revlists_dev.h), pinned
+    const int32_t* d_dlmeta = nullptr;   // ... and its device original inside scratch 8 (set by dev_lists_launch; pg_args::ev_adp0)
     unsigned int* d_row_done = nullptr;  // [R K][tiles of 256 sites]: pg_nodes_rows_all's "this tile of the adjoint row is complete" words
     unsigned int row_epoch = 0;          // their value in the current reverse pass
     hipEvent_t ev_dl = nullptr;
@@ -206,6 +208,7 @@ struct phylo_ctx {
     hipEvent_t ev_gcopy = nullptr;
     std::vector<int32_t> h_cur;          // scratch of the counting sorts
     std::vector<double> h_vi_lam;        // phylo_vi_gradients: the rates of the step (phylo_set_model copies them)
+    std::vector<double> h_vi_raw;        // ... and the reverse pass's [2 R + 20] gradients ahead of the chain rules
     // sharded PHYLO_KEEP_GRAPH: whole-K copies of the per-rank records the reverse pass reads, made after the last rank event
     // (graph_gather), and their exchange buffer (pk_gx_pack / pk_gx_unpack); node rows stay in their owners' pools
     int32_t* d_gchild = nullptr;         // [R][K][2]
@@ -1766,6 +1769,10 @@ int phylo_sweep_finish(phylo_ctx* c) {
     c->last_graph = graph;
     c->last_graph_twist = graph && twist;
     c->last_graph_marks = graph && c->run.lazy;
+    // (what made the sweep eager with lazy_ok's other conditions met: the flag or the switch alone; one GPU -- a sharded pass keeps
+    //  its own form)
+    // (above PG_KEPT_BITS_TAXA only: up to there every form keeps the bits it had -- phylo_revlists.h)
+    c->last_graph_eager = graph && !c->run.lazy && !twist && S <= 4096 && c->world == 1 && Kl == c->K && N > PG_KEPT_BITS_TAXA;
     c->last_M = c->run.M;
     c->last_G = c->run.G;
     c->last_final_missing = c->run.final_missing;
@@ -1959,6 +1966,7 @@ static int dev_lists_launch(phylo_ctx* c, hipStream_t sL, hipStream_t sS, bool k
     d.adopted = w; w += nn;
     d.bsum = w; w += 4 * nb;
     d.dmeta = w; w += meta_ints;
+    c->d_dlmeta = d.dmeta;
     d.pkey = (uint32_t*)w; d.pval = (uint32_t*)w + 2 * nn; w += 4 * nn;
     uint32_t* pkey_out = (uint32_t*)w;
     d.L = pg_lists_carve(c->d_ad_off, (size_t)R, (size_t)K);
@@ -2082,7 +2090,7 @@ struct rev_pass {
     const int64_t* anc = nullptr;        // the ancestors the host builders read (a batched sweep's: with global indices)
     bool batch = false;                  // phylo_sweep_backward_batch: a row per group, the groups' log Z-hat behind them
     hipStream_t sB = nullptr;            // the adopted nodes' chain: the second stream (plan.two), else the context's
-    int node_launches = 0, tw_launches = 0;
+    int node_launches = 0, tw_launches = 0, mark_launches = 0;
     std::chrono::steady_clock::time_point host_t0;
     double host_ms = 0.0;
 };
@@ -2096,6 +2104,26 @@ static pg_plan_in rev_plan_in(const phylo_ctx* c) {
     in.dl_max_k = PG_DL_MAX_K;
     in.groups = c->last_G;
     return in;
+}
+
+// (0.) After a sweep that stored every node (PHYLO_EAGER_NODES) nothing marked the adopted ones.  The marks say who was adopted and
+// nothing else, and the ancestors say that too: written here, once per sweep, they give such a sweep the reverse pass of a lazy one
+// -- the same launches, the same sums in the same order, the same bits -- instead of the form without marks (which the twisted
+// proposal, S > 4096 and phylo_sweep_node's widened marks still take).
+static int rev_marks(rev_pass& p) {
+    phylo_ctx* c = p.c;
+    if (c->last_graph_marks || !c->last_graph_eager) return PHYLO_OK;
+    const int R = c->N - 1, K = c->K;
+    const size_t mark_words = ((size_t)R * K + R + 3) & ~(size_t)3;
+    HIPCHK(c, hipMemsetAsync(c->d_mark, 0, mark_words * sizeof(unsigned int), c->stream));
+    if (R > 1) {
+        hipLaunchKernelGGL(pg_mark_adopted_dev, dim3(cdiv((long)(R - 1) * K, 256)), dim3(256), 0, c->stream, (const int64_t*)c->d_anc, c->d_mark,
+                           R, K, K / c->last_G);
+        CHK(launch_check(c, "pg_mark_adopted_dev"));
+    }
+    c->last_graph_marks = true;
+    p.mark_launches = 2;
+    return PHYLO_OK;
 }
 
 // 1. the pointer block
@@ -2284,9 +2312,10 @@ static int rev_row_words(rev_pass& p) {
     g.row_timeout = (unsigned int*)(c->hd_dlmeta + PG_DL_META_INTS(R));
     g.coeff_done = c->d_row_done + row_words;
     g.coeff_ticket = g.coeff_done + R;
-    g.coeff_mask = 0ull;
-    for (int r = 0; r + 1 < R; ++r)
-        if (p.n.ev_adp0[r + 1] > p.n.ev_adp0[r]) g.coeff_mask |= 1ull << r;
+    // which rank events have a pg_coeff launch to wait for: read from pg_dl_lists' own starts on the device (rows_all implies
+    // dev_lists; the host has seen those kernels end in dev_lists_wait, ahead of every launch that reads them, on any stream) --
+    // a word per rank event for any R, no upload
+    g.ev_adp0 = c->d_dlmeta;
     return PHYLO_OK;
 }
 
@@ -2305,7 +2334,11 @@ static int rev_parents(rev_pass& p) {
     const int N = g.N, K = g.K, S = g.S, R = g.R;
     const size_t nn = (size_t)R * K;
     if (p.plan.dev_lists) CHK(dev_lists_wait(c, p.n));
-    else pg_build_parents(N, R, K, c->h_child_p, p.plan.rows_form, p.plan.early_free, p.L, c->h_cur, p.n);
+    else {
+        pg_build_parents(N, R, K, c->h_child_p, p.plan.rows_form, p.plan.early_free, p.L, c->h_cur, p.n);
+        // (the order the device builders leave: the same bits -- where no gradient existed before, phylo_revlists.h)
+        if (p.plan.early_free && N > PG_KEPT_BITS_TAXA) pg_flagged_tails_ascending(p.L, p.n.n_slow);
+    }
     void* cpart = nullptr;
     // rows form: the chunk sums of ALL rank events are produced by one launch (free parents only: nothing of the chain is
     // needed for them), so the buffer holds every chunk; else one rank event's at a time
@@ -2543,7 +2576,7 @@ static int rev_finish(rev_pass& p, double* d_lam_l, double* d_lam_r, double* d_p
         perf->sweep_ms = ms;
         // (R + 7 stands for the coefficient chain's launch per rank event and the fixed launches: not a true count under
         //  pg_coeff_all, where that chain is one launch; kept as it is, tools compare it between runs)
-        perf->n_launches = R + 7 + p.node_launches + p.tw_launches;
+        perf->n_launches = R + 7 + p.node_launches + p.tw_launches + p.mark_launches;
         perf->merge_ms = p.host_ms;                        // here: host time of the integer lists (built, or waited for: device lists)
         perf->merge_launches = p.plan.dev_lists ? 1 : 0;   // here: 1 = the lists were built by kernels (phylo_revlists_dev.h)
     }
@@ -2557,6 +2590,7 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
     rev_pass p;
     p.c = c;
     p.batch = G != 0;
+    CHK(rev_marks(p));
     p.plan = pg_plan_form(rev_plan_in(c));                 // decision point one: before anything is launched
     CHK(rev_bind(p));
     CHK(rev_early(p));
@@ -2575,8 +2609,8 @@ static int sweep_backward_impl(phylo_ctx* c, double* d_lam_l, double* d_lam_r, d
 int phylo_vi_gradients(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, int jc, const double* vars, double* logZ, double* grads,
                        phylo_stats* fwd, phylo_stats* bwd) {
     CHK(bind(c));
-    if (!vars || !grads) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients: NULL argument");
-    const int R = c->N - 1;
+    if (!vars || !grads) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients: NULL argument");   // (ahead of phylo_set_model and the sweep:
+    const int R = c->N - 1;                                                                    //  a refused call leaves nothing in flight)
     double Q[16], pi[4];
     std::vector<double>& lam = c->h_vi_lam;
     lam.resize((size_t)2 * R);
@@ -2585,8 +2619,9 @@ int phylo_vi_gradients(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, int j
     pt_get_pi(vars + 2 * R + 16, pi);
     CHK(phylo_set_model(c, Q, pi, lam.data(), lam.data() + R, jc));
     CHK(phylo_sweep_async(c, seed, flags | PHYLO_KEEP_GRAPH, M));
-    double raw[2 * 64 + 20];
-    if (R > 64) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients: at most 65 taxa");
+    std::vector<double>& rawv = c->h_vi_raw;                // d_lam_l[R] | d_lam_r[R] | d_pi[4] | d_Q[16], any R
+    rawv.resize((size_t)2 * R + 20);
+    double* raw = rawv.data();
     CHK(phylo_sweep_backward(c, raw, raw + R, raw + 2 * R, raw + 2 * R + 4, bwd));
     CHK(phylo_sweep_fetch(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, logZ, fwd));
     pt_chain_rules(R, jc, Q, pi, lam.data(), lam.data() + R, raw, raw + R, raw + 2 * R, raw + 2 * R + 4, grads);
@@ -2600,7 +2635,6 @@ int phylo_vi_gradients_batch(phylo_ctx* c, const uint64_t* seeds, int G, uint32_
     if (!vars || !grads || !seeds) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients_batch: NULL argument");
     if (G < 1 || G > PK_MAX_GROUPS) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients_batch: 1 <= G <= %d (got %d)", PK_MAX_GROUPS, G);
     const int R = c->N - 1;
-    if (R > 64) return fail(c, PHYLO_EINVAL, "phylo_vi_gradients_batch: at most 65 taxa");
     double Q[16], pi[4];
     std::vector<double>& lam = c->h_vi_lam;
     lam.resize((size_t)2 * R);

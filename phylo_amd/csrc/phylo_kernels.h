@@ -2067,6 +2067,71 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void
     }
 }
 
+// pk_twist_choose's second half for more than 64 taxa: the form below keeps a root slot / a history entry per lane and forms the
+// contract's sums by readlane, which holds 64 of them.  Here lane 0 forms the same sums in the same order (remaining roots in
+// descending slot order, history entries ascending) from memory, and the lanes stride over the root table for the new one.  Up to 64
+// taxa nothing changes (same code, same bits, same time); above, the twisted sweep works instead of reading lanes that do not exist.
+__device__ __forceinline__ void pk_twist_choose_tail_wide(const pk_twist_args& ta, int jsel, double logq, int il, int ir) {
+    const pk_rank_args& a = ta.a;
+    const int k = blockIdx.x, kg = a.k0 + k, lane = threadIdx.x, n = a.n, N = a.N, J = ta.J;
+    const int32_t* ro = ta.roots_ad + (size_t)kg * N;
+    const int32_t* co = ta.cnt_ad + (size_t)kg * N;
+    const double* rl = ta.rootll_ad + (size_t)kg * N;
+    const double b_l = ta.tw_b[((size_t)k * J + jsel) * 2], b_r = ta.tw_b[((size_t)k * J + jsel) * 2 + 1];
+    const int cnew = co[il] + co[ir];
+    if (lane < 32) ta.Pmat_r[(size_t)k * 32 + lane] = ta.tw_P[((size_t)k * J + jsel) * 32 + lane];
+    if (lane == 0) {
+        double sum_rem = 0.0, fprior = 0.0;
+        int vminus = 0;
+        for (int i = n - 1; i >= 0; --i) {                   // remaining roots, descending slot order
+            if (i == il || i == ir) continue;
+            const int c = co[i];
+            sum_rem = sum_rem + rl[i];
+            fprior = fprior + (-a.ldf[c < a.ldf_n ? c : a.ldf_n]);
+            vminus += c - (c == 1 ? 1 : 0);
+        }
+        fprior = fprior + (-a.ldf[cnew < a.ldf_n ? cnew : a.ldf_n]);
+        vminus += cnew - (cnew == 1 ? 1 : 0);
+        double lp = 0.0, rp = 0.0;
+        for (int j = 0; j <= a.r; ++j) {
+            const double hl = j == a.r ? b_l : a.bl[(size_t)j * a.Kloc + k], hr = j == a.r ? b_r : a.br[(size_t)j * a.Kloc + k];
+            lp = lp + ((-a.lam_l) * hl + a.loglam_l);
+            rp = rp + ((-a.lam_r) * hr + a.loglam_r);
+        }
+        ta.chosen[kg] = (double)jsel;
+        ta.bl_r[k] = b_l;
+        ta.br_r[k] = b_r;
+        double* ax = a.aux + (size_t)k * PK_AUX;
+        ax[AUX_SUM_REM] = sum_rem;
+        ax[AUX_FPRIOR] = fprior;
+        ax[AUX_LPRIOR] = lp;
+        ax[AUX_RPRIOR] = rp;
+        ax[AUX_PAREN] = ((a.loglam_l - a.lam_l * b_l) + a.loglam_r) - a.lam_r * b_r;
+        ax[AUX_LOGV] = pm_log((double)vminus);
+        ax[AUX_Q] = logq;
+        a.child[k * 2] = ro[il];
+        a.child[k * 2 + 1] = ro[ir];
+        a.merges[((size_t)a.r * a.Kloc + k) * 2] = il;
+        a.merges[((size_t)a.r * a.Kloc + k) * 2 + 1] = ir;
+    }
+    if (ta.own_tables) {                                     // (roots_ad and roots_new are different buffers: no slot is read after it is written)
+        for (int i = lane; i < n; i += 64) {
+            const bool merged = i == il || i == ir;
+            const int p = (n - 1 - i) - (il > i ? 1 : 0) - (ir > i ? 1 : 0);
+            if (!merged) {
+                a.roots_new[(size_t)kg * N + p] = ro[i];
+                a.cnt_new[(size_t)kg * N + p] = co[i];
+                a.rootll_new[(size_t)kg * N + p] = rl[i];
+            }
+            if (a.pos_hist) a.pos_hist[(size_t)kg * N + i] = merged ? -1 : p;
+        }
+        if (lane == 0) {
+            a.roots_new[(size_t)kg * N + (n - 2)] = N + a.r * a.K + kg;
+            a.cnt_new[(size_t)kg * N + (n - 2)] = cnew;
+        }
+    }
+}
+
 // one wave per local particle: softmax over its J potentials, one categorical draw (integer CDF), the weight
 // terms of vncsmc.py:472-491 for the chosen pair.
 // (the body is instantiated twice, with w in LDS and with w in global memory: a pointer selected at run time would turn every
@@ -2131,6 +2196,10 @@ __device__ __forceinline__ void pk_twist_choose_body(const pk_twist_args& ta, do
     const int32_t* ro = ta.roots_ad + (size_t)kg * N;
     const int32_t* co = ta.cnt_ad + (size_t)kg * N;
     const double* rl = ta.rootll_ad + (size_t)kg * N;
+    if (N > 64) {                                            // (uniform) more root slots than lanes: see below
+        pk_twist_choose_tail_wide(ta, jsel, logq, il, ir);
+        return;
+    }
     const bool slot = lane < n;                              // (n <= N <= 64)
     const int c_i = slot ? co[lane] : 0, ro_i = slot ? ro[lane] : 0;
     const double rl_i = slot ? rl[lane] : 0.0;

@@ -224,6 +224,23 @@ inline void pg_build_parents(int N, int R, int K, const int32_t* child, bool row
     o.n_chunks = n_chunks; o.max_chunks = max_chunks; o.n_slow = ns; o.n_par = run;
 }
 
+// pg_build_parents with tail_flagged fills a list's flagged entries from the back, which leaves them descending; the device builders
+// (phylo_revlists_dev.h) leave them ascending, and pg_nodes_rows adds them in list order.  The reverse pass turns the host-built
+// tails round, so that a gradient has the same bits whoever built its lists.  Only flagged nodes have parents: n_slow short walks.
+// Both this and the marks of an eager sweep (rev_marks in phylo_hip.hip) apply above PG_KEPT_BITS_TAXA taxa only.  Up to there
+// gradients existed before either, the forms with host-built lists or without marks agreed with the default to the last few bits
+// (the tests hold them to 1e-12), and each keeps the bits it had; above, no reverse pass worked, and all forms give the same bits.
+#define PG_KEPT_BITS_TAXA 65
+inline void pg_flagged_tails_ascending(const pg_lists& L, int32_t n_slow) {
+    for (int32_t i = 0; i < n_slow; ++i) {
+        const size_t x = (size_t)L.slow_idx[i];
+        int32_t *b = L.par_idx + L.par_off[x], *e = L.par_idx + L.par_off[x + 1];
+        int32_t* t = e;
+        while (t > b && !(t[-1] & PG_FREE_PARENT)) --t;
+        for (int32_t* u = e - 1; t < u; ++t, --u) { const int32_t v = *t; *t = *u; *u = v; }
+    }
+}
+
 // ---- twisted proposal: the look-ahead lists --------------------------------------------------------------------------------------
 // The look-ahead merges of rank event r touch every internal node among the adopted roots (rad[r][k][slot], slots 0 .. N - r - 1;
 // rank event 0 adopts leaves only).  Entries (adopter * N + slot) grouped by node (counting sort: ascending adopter, then slot),
@@ -401,7 +418,8 @@ inline void pg_plan_chains(pg_plan& p, long n_slow, long TS, long coeff_wgs, int
     // call, and the adopted nodes' chain queued behind all the coefficient launches would start ~70 us late.
     p.interleave = p.early_free && p.two && p.parents_first && !p.rows_all;
     // with the adopted nodes in one launch, the coefficient chain is one launch too (pg_coeff_all) when all of its workgroups
-    // can be resident (coeff_mask holds a bit per rank event that has a pg_coeff launch: 64)
+    // can be resident (pg_coeff_plan holds 66 rank events; beyond 65 taxa the coefficients run as a launch per rank event, which
+    // ticks the same tickets and completion words for pg_nodes_rows_all -- DESIGN.md section 4b-taxa)
     p.coeff_all = p.rows_all && R - 1 <= 64 && coeff_wgs > 0 && coeff_wgs <= 2048 && !p.coeff_chain;
 }
 

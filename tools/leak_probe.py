@@ -9,6 +9,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from phylo_amd import _ffi, model as M          # noqa: E402
+from phylo_amd import train as T                # noqa: E402
 from phylo_amd.datasets import load_dataset     # noqa: E402
 
 g = load_dataset("primate_data")["genome"][:, :200]
@@ -16,6 +17,10 @@ N, S, _ = g.shape
 Q = M.get_Q(M.init_y_q())
 pi = M.get_stationary_probs(np.zeros(4) + 0.25)
 lam = np.full(N - 1, 10.0)
+# 66 taxa: more rank events than one 64-bit word has bits (the reverse pass's hand-off state, the VI step's buffers)
+N2, S2 = 66, 64
+codes2 = np.random.default_rng(66).integers(0, 5, size=(N2, S2))
+g2 = np.stack([(codes2 == b) | (codes2 == 4) for b in range(4)], axis=-1).astype(np.float64)
 
 
 def used():
@@ -38,6 +43,13 @@ def cycle(i):
         c.sweep_fetch()
         c.sweep_batch_async([1, 2, 3, 4], _ffi.FLAGS_DEFAULT | _ffi.KEEP_GRAPH)   # the batched graph and its reverse pass
         c.sweep_backward_batch(4)
+    v = T.Variables(N2, np.log(10.0), False)            # a context of 66 taxa that trains: two steps, so two passes on one context
+    tr = T.Trainer(g2, 32 + 4 * (i % 8), v, T.make_optimizer('Adam', 0.01), S2)
+    try:
+        tr.step(np.arange(S2), seed=i)
+        tr.step(np.arange(S2), seed=i + 1)
+    finally:
+        tr.close()
 
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 30

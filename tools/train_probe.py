@@ -2,7 +2,10 @@
 trajectory.  python tools/train_probe.py [--K 2048] [--sites 898] [--steps 20] [--epochs 0]
 --batched G: one batched step over G particle systems of K particles each (one batched sweep, one reverse pass) next to G serial
 steps on the same model and seeds in the same process; medians of --steps steps after 3 warm-ups, appended to
-profiles/train_batched_probe.jsonl."""
+profiles/train_batched_probe.jsonl.
+--synthetic N S: a coded alignment (A, C, G, T, gap) of N taxa x S sites drawn here from numpy's default_rng(--synthetic-seed) instead of
+a dataset -- the shipped data stops at 64 taxa (DS8), training does not (2 ... 512).  --out FILE appends the result line to FILE
+(profiles/train_many_taxa_probe.jsonl is where recorded ones go)."""
 import argparse
 import json
 import os
@@ -25,9 +28,17 @@ ap.add_argument('--nested', action='store_true')
 ap.add_argument('--phases', action='store_true')
 ap.add_argument('--M', type=int, default=1)
 ap.add_argument('--batched', type=int, default=0)
+ap.add_argument('--synthetic', type=int, nargs=2, metavar=('N', 'S'), default=None)
+ap.add_argument('--synthetic-seed', type=int, default=20260005)
+ap.add_argument('--out', default='')
 a = ap.parse_args()
 
-genome = load_dataset(a.dataset)['genome']
+if a.synthetic:
+    codes = np.random.default_rng(a.synthetic_seed).integers(0, 5, size=tuple(a.synthetic))
+    genome = np.stack([(codes == b) | (codes == 4) for b in range(4)], axis=-1).astype(np.float64)
+    a.dataset = 'synthetic_%dx%d_seed%d' % (a.synthetic[0], a.synthetic[1], a.synthetic_seed)
+else:
+    genome = load_dataset(a.dataset)['genome']
 N, S, _ = genome.shape
 B = a.sites or S
 if a.batched > 1:
@@ -70,7 +81,7 @@ if a.batched > 1:
 v = T.Variables(N, np.log(10.0), a.jcmodel)
 tr = T.Trainer(genome, a.K, v, T.make_optimizer('Adam', 0.01), B, nested=a.nested, M=a.M)
 rng = np.random.default_rng(0)
-fw, bw, wall, hostms = [], [], [], []
+fw, bw, wall, hostms, launches = [], [], [], [], []
 phases = {}
 if a.phases:                      # wall time of every host call of a step (Trainer.gradients, taken apart)
     orig = {}
@@ -94,9 +105,17 @@ for i in range(a.steps + 3):
         bw.append(tr.last['raw']['backward_ms'])
         hostms.append(tr.last['raw'].get('backward_host_ms', 0.0))
         wall.append((t1 - t0) * 1e3)
+        launches.append(tr.last['raw'].get('backward_launches', 0))
 if a.phases:
     print(json.dumps({'host_call_ms': {k: float(np.mean(v)) for k, v in phases.items()}}))
-print(json.dumps({'dataset': a.dataset, 'nested': a.nested, 'M': a.M, 'K': a.K, 'N': N, 'sites': B, 'steps': a.steps,
-                  'forward_ms': float(np.mean(fw)), 'backward_ms': float(np.mean(bw)), 'backward_host_ms': float(np.mean(hostms)), 'step_wall_ms': float(np.mean(wall)),
-                  'step_wall_ms_min': float(np.min(wall)), 'last_logZ': tr.last['logZ']}))
+line = {'dataset': a.dataset, 'nested': a.nested, 'M': a.M, 'K': a.K, 'N': N, 'sites': B, 'steps': a.steps,
+        'forward_ms': float(np.mean(fw)), 'backward_ms': float(np.mean(bw)), 'backward_host_ms': float(np.mean(hostms)), 'step_wall_ms': float(np.mean(wall)),
+        'step_wall_ms_min': float(np.min(wall)), 'last_logZ': tr.last['logZ'],
+        'forward_ms_median': float(np.median(fw)), 'backward_ms_median': float(np.median(bw)), 'step_wall_ms_median': float(np.median(wall)),
+        'step_wall_ms_p25': float(np.percentile(wall, 25)), 'step_wall_ms_p75': float(np.percentile(wall, 75)),
+        'backward_launches': int(np.median(launches)), 'backward_lists': tr.last['raw'].get('backward_lists', '')}
+print(json.dumps(line))
+if a.out:
+    with open(a.out, 'a') as fh:
+        fh.write(json.dumps(line) + '\n')
 tr.close()
