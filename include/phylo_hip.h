@@ -139,6 +139,27 @@ int phylo_tree_loglik(phylo_ctx* ctx, int n_nodes, int n_leaves, int S, const in
                       const double* leaves_LxSx4, const double* prior4, double* out_loglik,
                       double* root_data_Sx4);
 
+/* The log-likelihood of T explicit rooted binary trees over the context's N taxa under the context's model (Q and
+ * jc69_closed_form of phylo_set_model) and the context's RESIDENT leaves (phylo_set_leaves; nothing is uploaded again) -- what
+ * phylo_tree_loglik computes for one tree, in volume.  Numbering: leaves are nodes 0 .. N-1; row i of a
+ * tree is internal node N + i with children child[t][i][0], child[t][i][1] (a leaf or a node of an earlier row) and branch
+ * lengths blen[t][i][0], blen[t][i][1]; row N-2 is the root.  Every tree is checked on the host before anything is queued: each
+ * leaf and each internal node but the root is a child exactly once, branch lengths are finite and >= 0 (PHYLO_EINVAL naming
+ * tree and row); PHYLO_ESTATE before leaves and model are set; T >= 1.
+ *   loglik_T[t] = sum_s log(prior . x_root[s]) by the arithmetic contract with the context's site tile: bit for bit what
+ *     phylo_tree_loglik returns for the same tree, leaves, prior and site tile.  prior4 == NULL: the context's pi;
+ *   site_lik_TxS[t][s] (may be NULL): the factor prior . x_root[s] that entered the product;
+ *   perf (may be NULL): sweep_ms = device time (hipEvents), n_launches, units = T S (N-1).
+ * Synchronous.  On a sharded context a LOCAL call (every rank holds all leaves), not a collective.  Large T runs in chunks: device
+ * scratch is bounded by 64 MiB (PHYLO_TREES_CHUNK=n in the environment of phylo_create: at most n trees per chunk), not by T.
+ * The sweep's state, a kept graph and a tree summary are left alone. */
+int phylo_trees_loglik(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
+                       double* site_lik_TxS, phylo_stats* perf);
+/* Test hook, no GPU needed: the host half of phylo_trees_loglik on ONE tree -- the checks above (PHYLO_EINVAL, "tree 0, row i")
+ * and the slot schedule the kernel walks: ops[N-1][4] = {destination slot, left source, right source, row}, a source >= 0 a
+ * leaf, a source < 0 the slot ~source; depth = slots in use (<= floor(log2 N) + 1).  tests/test_trees_host.py replays it. */
+int phylo_debug_tree_schedule(int N, const int32_t* child, const double* blen, int32_t* ops, int32_t* depth);
+
 /* VCSMC.resample's index draw (vcsmc.py:284-285) / CSMC.resample (csmc.py:218-228): K iid draws from
  * softmax(logw), by the integer-CDF contract.  idx_K[k] in [0,K). */
 int phylo_resample(phylo_ctx* ctx, const double* logw_K, int K, uint64_t seed, uint32_t step,

@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -199,6 +199,33 @@ def debug_site_product(p, x1, x2):
     return _site_product(None, p, x1, x2)
 
 
+def _tree_rows(child, blen, N):
+    child = np.ascontiguousarray(child, dtype=np.int32)
+    blen = _f64(blen)
+    if child.ndim == 2:
+        child, blen = child[None], blen[None]
+    if child.ndim != 3 or child.shape[1:] != (N - 1, 2) or blen.shape != child.shape:
+        raise ValueError("child and blen must be [T][N-1][2] (or [N-1][2]) for N = %d, got %r and %r" % (N, child.shape, blen.shape))
+    return child, blen
+
+
+def debug_tree_schedule(child, blen):
+    """The host half of phylo_trees_loglik on one tree (no GPU needed): the checks (PhyloError -1 naming the row) and the slot
+    schedule ops [N-1][4] = (destination slot, left source, right source, row), a source >= 0 a leaf, < 0 the slot ~source.
+    Returns (ops, depth)."""
+    lib = load()
+    N = np.asarray(child).shape[-2] + 1
+    child, blen = _tree_rows(child, blen, N)
+    if child.shape[0] != 1:
+        raise ValueError("one tree at a time")
+    ops = np.zeros((N - 1, 4), dtype=np.int32)
+    depth = C.c_int32(0)
+    rc = lib.phylo_debug_tree_schedule(C.c_int(N), _ptr(child), _ptr(blen), _ptr(ops), C.byref(depth))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return ops, depth.value
+
+
 def vi_apply(N, jc, packed_vars, packed_grads, kind, lr, beta1=0.9, beta2=0.999, eps=1e-8, state=None):
     """phylo_vi_apply: the optimiser update on the packed variables IN PLACE (kind 0 gradient descent, 1 Adam with state =
     {'t': int, 'm': array, 'v': array}, updated in place too)."""
@@ -311,6 +338,23 @@ class Context:
                                                 _ptr(bl), _ptr(br), C.c_int(int(root)), _ptr(leaves), _ptr(prior),
                                                 C.byref(out), _ptr(rd)))
         return out.value, rd
+
+    def trees_loglik(self, child, blen, prior=None, want_sites=False):
+        """Log-likelihoods of T explicit trees over the context's resident leaves (phylo_trees_loglik): child, blen [T][N-1][2],
+        leaves 0 .. N-1, row i = internal node N + i, the last row the root; prior None = the model's pi.  Returns loglik [T],
+        or (loglik, site_lik [T][S]) with want_sites; self.last_trees_stats holds the call's stats."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        out = np.empty(T)
+        sites = np.empty((T, self.S)) if want_sites else None
+        st = Stats()
+        self._check(self._lib.phylo_trees_loglik(self._h, C.c_int(T), _ptr(child), _ptr(blen), _ptr(pr), _ptr(out), _ptr(sites),
+                                                 C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return (out, sites) if want_sites else out
 
     def resample(self, logw, seed, step):
         w = _f64(logw).reshape(-1)

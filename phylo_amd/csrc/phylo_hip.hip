@@ -23,6 +23,7 @@
 #include "phylo_revlists_dev.h"
 #include "phylo_train.h"
 #include "phylo_trees.h"
+#include "phylo_treeset.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -64,6 +65,7 @@ struct env_switches {
     int persist_nt = 256;                // PHYLO_PERSIST_NT: threads per workgroup of the one-launch sweep (256 or 512)
     int remote_cache_cap = 0;            // PHYLO_REMOTE_CACHE_CAP: slots of the local cache of remote nodes (0 = 512 MB worth; tests lower it)
     int scan_multi_min = 4096;           // PHYLO_SCAN_MULTI_MIN: groups of more weights than this are scanned by several workgroups
+    int trees_chunk = 0;                 // PHYLO_TREES_CHUNK: trees per chunk of phylo_trees_loglik (0 = what PT2_SCRATCH_BYTES holds; tests lower it)
     void read() {
         eager_nodes = getenv("PHYLO_EAGER_NODES") != nullptr;
         rehearse_sharded = getenv("PHYLO_REHEARSE_SHARDED") != nullptr;
@@ -79,6 +81,7 @@ struct env_switches {
         no_remote_cache = getenv("PHYLO_NO_REMOTE_CACHE") != nullptr;
         { const char* e = getenv("PHYLO_REMOTE_CACHE_CAP"); remote_cache_cap = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_SCAN_MULTI_MIN"); scan_multi_min = e ? atoi(e) : 4096; }
+        { const char* e = getenv("PHYLO_TREES_CHUNK"); trees_chunk = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_P2P"); no_p2p = e && atoi(e) == 0; }
         { const char* e = getenv("PHYLO_P2P_COPY_WORDS"); p2p_copy_words = e ? (size_t)atol(e) : 65536; }
         { const char* e = getenv("PHYLO_P2P_WAIT_S"); p2p_wait_ticks = e && atof(e) > 0 ? (unsigned long long)(atof(e) * 1e8) : PK_P2P_WAIT_TICKS; }
@@ -229,7 +232,8 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[14];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs)
+    DevBuf scratch[15];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+                                         //  14: phylo_trees_loglik's chunk)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -242,6 +246,7 @@ struct phylo_ctx {
     bool tb_done = false;
     unsigned long long sweep_serial = 0, ts_serial = 0;
     hipEvent_t ev_tb0 = nullptr, ev_tb1 = nullptr;
+    hipEvent_t ev_tl0 = nullptr, ev_tl1 = nullptr;   // phylo_trees_loglik's own pair (the sweep's and the summaries' stay theirs)
 };
 
 namespace {
@@ -747,6 +752,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_model) (void)hipEventDestroy(c->ev_model);
     if (c->ev_tb0) (void)hipEventDestroy(c->ev_tb0);
     if (c->ev_tb1) (void)hipEventDestroy(c->ev_tb1);
+    if (c->ev_tl0) (void)hipEventDestroy(c->ev_tl0);
+    if (c->ev_tl1) (void)hipEventDestroy(c->ev_tl1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -1006,6 +1013,112 @@ int phylo_tree_loglik(phylo_ctx* c, int n_nodes, int n_leaves, int S, const int3
     HIPCHK(c, hipMemcpyAsync(out_loglik, dout, 8, hipMemcpyDeviceToHost, c->stream));
     if (root_data) HIPCHK(c, hipMemcpyAsync(root_data, droot, (size_t)S * 4 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PHYLO_OK;
+}
+
+int phylo_trees_loglik(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
+                       double* site_lik_TxS, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!c->have_leaves || !c->have_model)
+        return fail(c, PHYLO_ESTATE, "phylo_trees_loglik needs phylo_set_leaves and phylo_set_model first");
+    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    if (!child || !blen || !loglik_T) return fail(c, PHYLO_EINVAL, "NULL pointer");
+    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
+    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
+        int row = 0;
+        char msg[200];
+        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+    }
+    // one chunk of trees in device scratch: ops | branch lengths | matrices | gap rows | tile values | results | site factors | prior
+    const bool coded = c->leaves_coded;
+    const size_t per_tree = (size_t)R * (16 + 16 + 256 + (coded ? 64 : 0)) + (size_t)ntiles * 8 + 8 + (site_lik_TxS ? (size_t)S * 8 : 0);
+    size_t fit = PT2_SCRATCH_BYTES / per_tree;
+    if (fit < 1) fit = 1;
+    if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);   // one workgroup per (tree, tile)
+    const int chunk = (int)std::min<size_t>((size_t)T, c->env.trees_chunk > 0 ? std::min<size_t>(fit, (size_t)c->env.trees_chunk) : fit);
+    void* slab = nullptr;
+    CHK(scratch_get(c, 14, per_tree * chunk + 32 + 256, &slab));
+    char* p = (char*)slab;
+    auto carve = [&](size_t bytes) { char* q = p; p += (bytes + 15) & ~(size_t)15; return q; };
+    double* d_prior = (double*)carve(32);
+    int32_t* d_ops = (int32_t*)carve((size_t)chunk * R * 16);
+    double* d_P = (double*)carve((size_t)chunk * R * 256);
+    double* d_t = (double*)carve((size_t)chunk * R * 16);
+    double* d_gap = coded ? (double*)carve((size_t)chunk * R * 64) : nullptr;
+    double* d_tilev = (double*)carve((size_t)chunk * ntiles * 8);
+    double* d_out = (double*)carve((size_t)chunk * 8);
+    double* d_site = site_lik_TxS ? (double*)carve((size_t)chunk * S * 8) : nullptr;
+    if (!c->ev_tl0) {
+        HIPCHK(c, hipEventCreate(&c->ev_tl0));
+        HIPCHK(c, hipEventCreate(&c->ev_tl1));
+    }
+    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> ops((size_t)chunk * R * 4);
+    std::vector<double> ts((size_t)chunk * R * 2);
+    double ms_total = 0.0;
+    int launches = 0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int n = std::min(chunk, T - t0);
+        int depth = 1;
+        for (int t = 0; t < n; ++t) {
+            int32_t* o = ops.data() + (size_t)t * R * 4;
+            const int d = pt2_schedule(N, child + (size_t)(t0 + t) * R * 2, o);
+            depth = std::max(depth, d);
+            const double* b = blen + (size_t)(t0 + t) * R * 2;
+            for (int i = 0; i < R; ++i) {                   // branch lengths in schedule order
+                ts[((size_t)t * R + i) * 2] = b[2 * o[4 * i + 3]];
+                ts[((size_t)t * R + i) * 2 + 1] = b[2 * o[4 * i + 3] + 1];
+            }
+        }
+        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_tl0, c->stream));
+        const long n_mat = (long)n * R * 2;
+        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
+        CHK(launch_check(c, "pk_expm_batched"));
+        ++launches;
+        if (coded) {
+            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
+            CHK(launch_check(c, "pt2_gap_rows"));
+            ++launches;
+        }
+        pt2_args a{};
+        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
+        a.prior = prior4 ? d_prior : c->d_pi;
+        a.tilev = d_tilev; a.site_lik = d_site;
+        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
+        pt2_launch(a, n, depth, coded, c->stream);
+        CHK(launch_check(c, "pt2_prune"));
+        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
+        CHK(launch_check(c, "pt2_finish"));
+        launches += 2;
+        HIPCHK(c, hipEventRecord(c->ev_tl1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_site) HIPCHK(c, hipMemcpyAsync(site_lik_TxS + (size_t)t0 * S, d_site, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tl0, c->ev_tl1));
+        ms_total += ms;
+    }
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * R;
+        st.alg_bytes = 96.0 * st.units;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
+int phylo_debug_tree_schedule(int N, const int32_t* child, const double* blen, int32_t* ops, int32_t* depth) {
+    if (N < 2 || N > PK_MAX_TAXA || !child || !blen || !ops || !depth) return fail(nullptr, PHYLO_EINVAL, "bad arguments to phylo_debug_tree_schedule");
+    int row = 0;
+    char msg[200];
+    if (pt2_check_tree(N, child, blen, &row, msg, sizeof msg)) return fail(nullptr, PHYLO_EINVAL, "tree 0, row %d: %s", row, msg);
+    *depth = pt2_schedule(N, child, ops);
     return PHYLO_OK;
 }
 

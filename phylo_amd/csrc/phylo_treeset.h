@@ -1,0 +1,270 @@
+// phylo_treeset.h -- phylo_trees_loglik: the log-likelihood of MANY explicit rooted binary trees over the context's resident
+// alignment.  Host: validation and the slot schedule of one tree; device: the pruning kernel that walks
+// a tree's schedule with the partials of the subtrees in flight in an LDS stack (no partial ever reaches HBM), and the kernel
+// that adds a tree's tile values left to right.  All arithmetic is phylo_math.h's and pk_merge_site's: the bits are those of
+// phylo_tree_loglik (pk_tree_prune + pk_row_loglik) and of the C oracle.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "phylo_kernels.h"
+
+#define PT2_MAX_DEPTH 10                          // floor(log2 PK_MAX_TAXA) + 1 slots
+#define PT2_SLOT_BYTES 2048                       // one slot of one site step: 64 lanes x 4 doubles
+#define PT2_WAVE_LDS (20 * 1024)                  // four site steps per pass while the stack stays within this, else two
+#define PT2_SCRATCH_BYTES ((size_t)64 << 20)      // device scratch of one chunk of trees (phylo_trees_loglik cuts T to fit)
+
+// ------------------------------------------------------------------------------------------------
+// host: one tree = child[N-1][2], blen[N-1][2]; leaves 0 .. N-1, row i = internal node N + i, children from earlier rows
+// ------------------------------------------------------------------------------------------------
+// 0: fine; otherwise the offending row in *bad_row and a message
+inline int pt2_check_tree(int N, const int32_t* child, const double* blen, int* bad_row, char* msg, size_t nmsg) {
+    const int R = N - 1;
+    std::vector<unsigned char> used((size_t)N + R, 0);
+    for (int i = 0; i < R; ++i)
+        for (int sd = 0; sd < 2; ++sd) {
+            const int ch = child[2 * i + sd];
+            const double b = blen[2 * i + sd];
+            *bad_row = i;
+            if (ch < 0 || ch >= N + i) {
+                snprintf(msg, nmsg, "child %d is neither a leaf nor a node of an earlier row (N = %d)", ch, N);
+                return 1;
+            }
+            if (used[ch]) {
+                snprintf(msg, nmsg, "%s %d is a child twice", ch < N ? "leaf" : "node", ch);
+                return 1;
+            }
+            used[ch] = 1;
+            if (!(b >= 0.0) || !std::isfinite(b)) {
+                snprintf(msg, nmsg, "branch length %g above child %d is not a finite number >= 0", b, ch);
+                return 1;
+            }
+        }
+    // 2 (N-1) distinct children out of the 2 N - 2 nodes below the root: every one of them exactly once
+    return 0;
+}
+
+// The schedule of a checked tree: N-1 operations {destination slot, left source, right source, row}; a source >= 0 is a leaf,
+// a source < 0 the slot ~source.  Children-first, the child with the larger slot need first (Sethi-Ullman), the destination
+// takes over the slot of an internal child: a tree of N leaves never holds more than floor(log2 N) + 1 slots.  Returns the depth.
+inline int pt2_schedule(int N, const int32_t* child, int32_t* ops /*[N-1][4]*/) {
+    const int R = N - 1;
+    std::vector<int> need((size_t)R), slot_of((size_t)R, -1), stack, free_slots;
+    for (int i = 0; i < R; ++i) {
+        const int a = child[2 * i], b = child[2 * i + 1];
+        int na = a < N ? 0 : need[a - N], nb = b < N ? 0 : need[b - N];
+        if (na < nb) { const int t = na; na = nb; nb = t; }
+        const int m = nb + (na > 0 ? 1 : 0);
+        need[i] = na > m ? na : (m > 1 ? m : 1);
+    }
+    std::vector<unsigned char> state((size_t)R, 0);
+    int n_ops = 0, depth = 0, next_slot = 0;
+    stack.push_back(R - 1);
+    while (!stack.empty()) {
+        const int i = stack.back();
+        const int a = child[2 * i], b = child[2 * i + 1];
+        if (state[i] == 0) {
+            state[i] = 1;
+            const int na = a < N ? 0 : need[a - N], nb = b < N ? 0 : need[b - N];
+            // (pushed last = visited first: the larger need; ties: the left child)
+            if (na >= nb) { if (b >= N) stack.push_back(b - N); if (a >= N) stack.push_back(a - N); }
+            else { if (a >= N) stack.push_back(a - N); if (b >= N) stack.push_back(b - N); }
+            continue;
+        }
+        stack.pop_back();
+        const int sa = a < N ? -1 : slot_of[a - N], sb = b < N ? -1 : slot_of[b - N];
+        int dst;
+        if (sa >= 0) { dst = sa; if (sb >= 0) free_slots.push_back(sb); }
+        else if (sb >= 0) dst = sb;
+        else if (!free_slots.empty()) {                   // the lowest free slot
+            size_t best = 0;
+            for (size_t j = 1; j < free_slots.size(); ++j) if (free_slots[j] < free_slots[best]) best = j;
+            dst = free_slots[best];
+            free_slots.erase(free_slots.begin() + (long)best);
+        } else dst = next_slot++;
+        slot_of[i] = dst;
+        if (dst + 1 > depth) depth = dst + 1;
+        int32_t* o = ops + 4 * (size_t)n_ops++;
+        o[0] = dst; o[1] = sa >= 0 ? ~sa : a; o[2] = sb >= 0 ? ~sb : b; o[3] = i;
+    }
+    return depth;
+}
+
+// Site steps a wave carries through one pass over the schedule (operations and matrices are read once per pass): four while the
+// stack stays within PT2_WAVE_LDS (depth <= 2: caterpillar-like trees), else two -- at most 40 KiB per wave at depth 10.  (One
+// step per pass holds both matrices and all pointers in scalar registers at once and spills two of them: not built.)
+inline int pt2_unroll(int depth) { return depth * 4 * PT2_SLOT_BYTES <= PT2_WAVE_LDS ? 4 : 2; }
+
+// ------------------------------------------------------------------------------------------------
+// device
+// ------------------------------------------------------------------------------------------------
+struct pt2_args {
+    const int32_t* ops;              // [trees][N-1][4] schedule (wave-uniform)
+    const double* P;                 // [trees][N-1][2][16] matrices in schedule order, left then right
+    const double* gap;               // [trees][N-1][2][4] row 4 of every matrix's leaf table (coded leaves), else NULL
+    const double* leaves;            // [N][S][4]
+    const uint8_t* codes;            // [N][S]
+    const double* prior;             // [4]
+    double* tilev;                   // [trees][ntiles]
+    double* site_lik;                // [trees][S] or NULL
+    int N, S, T, ntiles;
+};
+
+// row 4 of the 5 x 4 leaf table of every matrix (the fma chain over an all-ones row, pk_build_leaf_table); rows 0 .. 3 of the
+// table are the matrix's own rows and are read in place
+__global__ __launch_bounds__(256) void pt2_gap_rows(const double* __restrict__ P, long n_mat, double* __restrict__ gap) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_mat * 4) return;
+    const double* p = P + (t >> 2) * 16;
+    const int j = (int)(t & 3);
+    gap[t] = pm_fma(1.0, p[12 + j], pm_fma(1.0, p[8 + j], pm_fma(1.0, p[4 + j], 1.0 * p[j])));
+}
+
+// Wave-uniform data the launch only reads (operations, matrices, prior) is read through the constant address space: the kernel
+// also stores (site factors, tile values), after which hipcc would no longer prove a plain uniform load invariant and would
+// fetch every matrix once per LANE.
+typedef __attribute__((address_space(4))) const double pt2_cd;
+typedef int pt2_i4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) const pt2_i4 pt2_ci4;
+__device__ __forceinline__ void pt2_uniform16(const double* M, double (&m)[16]) {
+    pt2_cd* q = (pt2_cd*)M;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m[j] = q[j];
+}
+
+// (row . M)[j], the chain of pk_merge_site
+__device__ __forceinline__ void pt2_row_times(const double (&x)[4], const double (&M)[16], double (&out)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double v = x[0] * M[j];
+        v = pm_fma(x[1], M[4 + j], v);
+        v = pm_fma(x[2], M[8 + j], v);
+        out[j] = pm_fma(x[3], M[12 + j], v);
+    }
+}
+
+// One side of one operation for the wave's U site steps: (child row . M) from a coded leaf (table look-up), a generic leaf
+// (resident row) or a slot of the LDS stack.  src and M are wave-uniform.
+template <int U, bool CODED>
+__device__ __forceinline__ void pt2_side(const pt2_args& a, int src, const double* __restrict__ M, const double* __restrict__ gap,
+                                         const pk_d2* stack, const unsigned int (&sc)[U], int lane, double (&out)[U][4]) {
+    if (src >= 0) {
+        if constexpr (CODED) {
+            const uint8_t* cd = a.codes + (size_t)src * a.S;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned int c = *(pk_gu8c*)(cd + sc[u]);
+                const double* row = c < 4u ? M + 4u * c : gap;
+                pk_load4(row, out[u]);
+            }
+        } else {
+            const double* rows = a.leaves + (size_t)src * a.S * 4;
+            double m[16];
+            pt2_uniform16(M, m);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                double x[4];
+                pk_load4(rows + (size_t)sc[u] * 4, x);
+                pt2_row_times(x, m, out[u]);
+            }
+        }
+    } else {
+        const pk_d2* sl = stack + (size_t)(~src) * U * 128 + lane;
+        double m[16];
+        pt2_uniform16(M, m);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const pk_d2 lo = sl[u * 128], hi = sl[u * 128 + 64];
+            const double x[4] = {lo.x, lo.y, hi.x, hi.y};
+            pt2_row_times(x, m, out[u]);
+        }
+    }
+}
+
+// One wave per (tree, site tile), lane = column of the tile, sites in increasing order.  Stack layout: slot d, site step u, half h
+// (states 0,1 | 2,3), lane: 16 bytes each, so a wave's access is one contiguous kilobyte; a lane only ever touches its own
+// column, so the stack needs no fence.  Launched with depth * U * 2048 bytes of dynamic LDS.
+template <int U, bool CODED>
+__global__ __launch_bounds__(64) void pt2_prune(const pt2_args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pt2_lds[];
+    pk_d2* stack = reinterpret_cast<pk_d2*>(pt2_lds);
+    const int lane = threadIdx.x;
+    const int tree = blockIdx.x / a.ntiles, tile = blockIdx.x - tree * a.ntiles;
+    const int R = a.N - 1;
+    const int s0 = tile * a.T, s1 = s0 + a.T < a.S ? s0 + a.T : a.S;
+    pt2_ci4* ops = (pt2_ci4*)(a.ops + (size_t)tree * R * 4);
+    const double* P = a.P + (size_t)tree * R * 32;
+    const double* G = CODED ? a.gap + (size_t)tree * R * 8 : nullptr;
+    pm_lp col = pm_lp_init();
+#pragma unroll 1
+    for (int base = s0; base < s1; base += 64 * U) {       // base: wave-uniform
+        unsigned int sc[U];                                 // a site past the end re-reads the last one; its factor is dropped
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int s = base + 64 * u + lane;
+            sc[u] = (unsigned int)(s < s1 ? s : s1 - 1);
+        }
+        double o[U][4];
+#pragma unroll 1
+        for (int i = 0; i < R; ++i) {
+            const pt2_i4 op = ops[i];
+            double l[U][4], r[U][4];
+            pt2_side<U, CODED>(a, op.y, P + (size_t)i * 32, CODED ? G + (size_t)i * 8 : nullptr, stack, sc, lane, l);
+            pt2_side<U, CODED>(a, op.z, P + (size_t)i * 32 + 16, CODED ? G + (size_t)i * 8 + 4 : nullptr, stack, sc, lane, r);
+            pk_d2* dst = stack + (size_t)op.x * U * 128 + lane;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[u][j] = l[u][j] * r[u][j];
+                const pk_d2 lo = {o[u][0], o[u][1]}, hi = {o[u][2], o[u][3]};
+                dst[u * 128] = lo;
+                dst[u * 128 + 64] = hi;
+            }
+        }
+        pt2_cd* prc = (pt2_cd*)a.prior;                      // (read here, not ahead of the loops: eight scalar registers fewer across them)
+        const double pr[4] = {prc[0], prc[1], prc[2], prc[3]};
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int s = base + 64 * u + lane;
+            if (base + 64 * u < s1) {                       // wave-uniform
+                const double lik = pk_site_lik(pr, o[u]);
+                if (s < s1) {
+                    if (a.site_lik) a.site_lik[(size_t)tree * a.S + s] = lik;
+                    pm_lp_mul(col, lik);
+                }
+            }
+        }
+    }
+    const double t = pk_wave_tree_sum(pm_lp_finish(col));
+    if (lane == 0) a.tilev[(size_t)tree * a.ntiles + tile] = t;
+}
+
+// a tree's tile values, added left to right (as pk_tile_epilogue and pk_row_loglik add them)
+__global__ __launch_bounds__(256) void pt2_finish(const double* __restrict__ tilev, int ntiles, int trees, double* __restrict__ out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= trees) return;
+    const double* tv = tilev + (size_t)t * ntiles;
+    double tot = tv[0];
+    for (int i = 1; i < ntiles; ++i) tot = tot + tv[i];
+    out[t] = tot;
+}
+
+// the launch carries the depth its chunk needs: depth * U * 2048 bytes of LDS per wave
+template <int U, bool CODED>
+inline void pt2_launch_as(const pt2_args& a, int trees, int depth, hipStream_t s) {
+    hipLaunchKernelGGL((pt2_prune<U, CODED>), dim3((unsigned)trees * a.ntiles), dim3(64), (size_t)depth * U * PT2_SLOT_BYTES, s, a);
+}
+inline void pt2_launch(const pt2_args& a, int trees, int depth, bool coded, hipStream_t s) {
+    const int U = pt2_unroll(depth);
+    if (coded) {
+        if (U == 4) pt2_launch_as<4, true>(a, trees, depth, s);
+        else pt2_launch_as<2, true>(a, trees, depth, s);
+    } else {
+        if (U == 4) pt2_launch_as<4, false>(a, trees, depth, s);
+        else pt2_launch_as<2, false>(a, trees, depth, s);
+    }
+}

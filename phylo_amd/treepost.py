@@ -1,6 +1,7 @@
 """Host side of the tree posterior summary (VCSMC.tree_posterior; the device tables come from phylo_tree_summary, DESIGN.md
 section 10): clades in taxon names with their support, topologies with probability, count, representative and Newick, the
-majority-rule consensus tree, credible sets, and a Newick reader that turns a rooted tree back into its clade set."""
+majority-rule consensus tree, credible sets, and a Newick reader that turns a rooted tree back into its clade set; and explicit
+trees as the rows Context.trees_loglik scores: from and to Newick, and from a sweep's final particles."""
 from __future__ import annotations
 
 import json
@@ -177,6 +178,149 @@ def newick_branches(newick, taxa):
     if pos != len(s):
         raise ValueError("trailing characters in Newick: %r" % s[pos:])
     return out
+
+
+def newick_to_rows(newick, taxa):
+    """A rooted Newick tree over `taxa` as the rows Context.trees_loglik takes: (child [N-1][2] int32, blen [N-1][2] float64);
+    leaves are nodes 0 .. N-1 in the order of `taxa`, row i is internal node N + i (numbered as its closing bracket is met, so
+    children come from earlier rows) and the last row is the root.  A node with more than two children is resolved left to
+    right with zero-length branches: (A:a,B:b,C:c) reads ((A:a,B:b):0,C:c).  Every branch needs its ':length' (ValueError
+    otherwise; a length at the root is ignored), every taxon appears exactly once, internal-node labels are skipped."""
+    index = {str(t): i for i, t in enumerate(taxa)}
+    n = len(index)
+    s = newick.strip()
+    if s.endswith(';'):
+        s = s[:-1]
+    pos = 0
+    child, blen, seen = [], [], set()
+
+    def annotation(what, needed):
+        nonlocal pos
+        start = pos
+        while pos < len(s) and s[pos] not in ',()':
+            pos += 1
+        text = s[start:pos]
+        if ':' not in text:
+            if needed:
+                raise ValueError("the branch above %s has no length" % what)
+            return None
+        x = float(text.split(':', 1)[1])
+        if not (x >= 0.0 and x != float('inf')):
+            raise ValueError("the branch above %s has length %r: need a finite number >= 0" % (what, x))
+        return x
+
+    def node(is_root):
+        nonlocal pos
+        if pos < len(s) and s[pos] == '(':
+            pos += 1
+            kids = []
+            while True:
+                kids.append(node(False))
+                if pos < len(s) and s[pos] == ',':
+                    pos += 1
+                    continue
+                if pos < len(s) and s[pos] == ')':
+                    pos += 1
+                    break
+                raise ValueError("malformed Newick at %d: %r" % (pos, s[pos:pos + 20]))
+            if len(kids) < 2:
+                raise ValueError("an internal node with one child at %d" % pos)
+            cur = kids[0]
+            for nxt in kids[1:-1]:                         # a polytomy: join left to right under zero-length branches
+                child.append((cur[0], nxt[0]))
+                blen.append((cur[1], nxt[1]))
+                cur = (n + len(child) - 1, 0.0)
+            child.append((cur[0], kids[-1][0]))
+            blen.append((cur[1], kids[-1][1]))
+            me = n + len(child) - 1
+            return me, annotation("node %d" % me, not is_root)
+        start = pos
+        while pos < len(s) and s[pos] not in ',():':
+            pos += 1
+        name = s[start:pos]
+        if name not in index:
+            raise ValueError("unknown taxon %r in Newick" % name)
+        if name in seen:
+            raise ValueError("taxon %r appears twice" % name)
+        seen.add(name)
+        return index[name], annotation("taxon %r" % name, not is_root)
+
+    node(True)
+    if pos != len(s):
+        raise ValueError("trailing characters in Newick: %r" % s[pos:])
+    if len(seen) != n:
+        raise ValueError("taxa missing from the Newick: %s" % sorted(set(index) - seen))
+    return np.array(child, dtype=np.int32).reshape(n - 1, 2), np.array(blen, dtype=np.float64).reshape(n - 1, 2)
+
+
+def check_rows(child, blen, n=None):
+    """The checks phylo_trees_loglik makes on one tree, in Python: ValueError naming the row."""
+    child, blen = np.asarray(child), np.asarray(blen, dtype=np.float64)
+    n = child.shape[0] + 1 if n is None else n
+    if child.shape != (n - 1, 2) or blen.shape != (n - 1, 2):
+        raise ValueError("child and blen must be [N-1][2]")
+    used = set()
+    for i in range(n - 1):
+        for c, b in zip(child[i], blen[i]):
+            c = int(c)
+            if not 0 <= c < n + i:
+                raise ValueError("row %d: child %d is neither a leaf nor a node of an earlier row" % (i, c))
+            if c in used:
+                raise ValueError("row %d: node %d is a child twice" % (i, c))
+            used.add(c)
+            if not (b >= 0.0 and np.isfinite(b)):
+                raise ValueError("row %d: branch length %r is not a finite number >= 0" % (i, float(b)))
+
+
+def rows_to_newick(child, blen, taxa):
+    """The inverse of newick_to_rows: the Newick string of (child, blen), lengths written so that they read back bit for bit
+    (repr), children in row order, the root bare."""
+    child, blen = np.asarray(child), np.asarray(blen, dtype=np.float64)
+    n = len(taxa)
+    check_rows(child, blen, n)
+    text = [str(t) for t in taxa] + [None] * (n - 1)
+    for i in range(n - 1):                                 # rows are children-first: no recursion
+        (a, b), (x, y) = child[i], blen[i]
+        text[n + i] = '(%s:%s,%s:%s)' % (text[a], repr(float(x)), text[b], repr(float(y)))
+    return text[2 * n - 2] + ';'
+
+
+def particle_trees(merges, ancestors, lbranch, rbranch, remaining=None, seed=None):
+    """The K final particles' trees of a fetched sweep as rows: (child [K][N-1][2] int32, blen [K][N-1][2]).  merges [N-1][K][2]
+    (root-table slots coalesced at each rank event), ancestors [N-2][K] (resampling indices before rank events 1 .. N-2),
+    lbranch / rbranch [N-1][K].  Row r of particle k is the node its lineage created at rank event r, numbered N + r.  The slots
+    that stay move to the front of the table and the new node goes last; their order is `remaining` (one [K][n-2] array of slots
+    per rank event), else the plain proposal's pair-order contract for `seed` (phylo_amd.rng.pair_order), else -- both None --
+    descending slots, the twisted proposal's rule."""
+    merges = np.asarray(merges)
+    R, K = merges.shape[0], merges.shape[1]
+    N = R + 1
+    anc = np.asarray(ancestors).reshape(max(R - 1, 0), K)
+    lb, rb = np.asarray(lbranch, dtype=np.float64), np.asarray(rbranch, dtype=np.float64)
+    tab = np.tile(np.arange(N, dtype=np.int32), (K, 1))
+    child = np.zeros((K, R, 2), dtype=np.int32)
+    blen = np.zeros((K, R, 2), dtype=np.float64)
+    rows = np.arange(K)
+    for r in range(R):
+        if r > 0:
+            idx = anc[r - 1]
+            tab, child, blen = tab[idx], child[idx], blen[idx]
+        n = N - r
+        co = merges[r].astype(np.int64)
+        if remaining is not None:
+            rem = np.asarray(remaining[r], dtype=np.int64).reshape(K, n - 2)
+        elif seed is not None:
+            from . import rng
+            pick, rem = rng.pair_order(K, n, seed, r)
+            if not np.array_equal(pick, merges[r]):
+                raise ValueError("rank event %d: merges are not the pair picks of seed %r" % (r, seed))
+            rem = rem.astype(np.int64)
+        else:
+            rem = np.array([[i for i in range(n - 1, -1, -1) if i != a and i != b] for a, b in co], dtype=np.int64).reshape(K, n - 2)
+        child[:, r, 0], child[:, r, 1] = tab[rows, co[:, 0]], tab[rows, co[:, 1]]
+        blen[:, r, 0], blen[:, r, 1] = lb[r], rb[r]
+        tab = np.concatenate([np.take_along_axis(tab, rem, axis=1), np.full((K, 1), N + r, dtype=np.int32)], axis=1)
+    return child, blen
 
 
 def branch_summary(stats, weight):

@@ -19,7 +19,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _ffi, model, rng
+from . import _ffi, model, rng, treepost
 from . import train as train_mod
 
 
@@ -274,7 +274,6 @@ class VCSMC:
         branch_lengths=True adds (phylo_tree_branches, no particle replayed): clade_branches (mean, sd, min, max of the branch
         above every clade, conditional on the clade), leaf_branches by taxon name, per topology its `clades` rows and mean
         lengths, consensus_bl (the consensus with :mean on every edge) and map_newick (the MAP topology with its mean lengths)."""
-        from . import treepost
         if self._ctx is None or not hasattr(self, '_last_seed'):
             raise RuntimeError("tree_posterior summarises the last sweep: call sample_phylogenies first")
         tab = self._ctx.tree_summary()
@@ -305,6 +304,44 @@ class VCSMC:
             tab = new
         return [row[0] for row in tab]
 
+    def score_trees(self, newicks):
+        """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
+        distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  Returns a list
+        of floats; a local call on every rank when sharded."""
+        rows = [treepost.newick_to_rows(nw, self.taxa) for nw in newicks]
+        if not rows:
+            return []
+        ctx = self._context()
+        ll = ctx.trees_loglik(np.array([r[0] for r in rows]), np.array([r[1] for r in rows]))
+        return [float(x) for x in ll]
+
+    def _tree_scores(self, path):
+        """tree_scores.json of --score_trees: the file's trees, and with branch lengths in the posterior also map.tre,
+        consensus_bl.tre and the ten most probable topologies at their mean lengths (None where a branch has no estimate)"""
+        with open(path) as f:
+            newicks = [line.strip() for line in f if line.strip()]
+        ll = self.score_trees(newicks)
+        out = {'model': {'Q': np.asarray(self.Qmatrix, dtype=np.float64).tolist(),
+                         'pi': np.asarray(self.stationary_probs, dtype=np.float64).reshape(-1).tolist(),
+                         'jc69_closed_form': bool(self.args.jcmodel)},
+               'trees': [{'newick': nw, 'loglik': x} for nw, x in zip(newicks, ll)],
+               'best': int(np.argmax(ll)) if ll else None}
+        post = self.posterior
+        if post is not None and getattr(post, 'map_newick', None) is not None:
+            def scored(nw):
+                try:
+                    return {'newick': nw, 'loglik': self.score_trees([nw])[0]}
+                except ValueError as e:                    # a branch held only by particles of weight 0 has no mean length
+                    return {'newick': nw, 'loglik': None, 'error': str(e)}
+
+            tops = []
+            for i, t in enumerate(post.topologies[:10]):
+                nw = treepost.tree_newick(post.taxa, [(post.clade_sets[j][0], m) for j, m in zip(t['clades'], t['clade_means'])],
+                                          t['leaf_means'])
+                tops.append(dict(scored(nw), rank=i, probability=t['probability']))
+            out['summary'] = {'map': scored(post.map_newick), 'consensus_bl': scored(post.consensus_bl), 'topologies': tops}
+        return out
+
     def _save_results(self, save_dir, initial, history):
         """run_parameters.txt and results.p with the reference's keys (vcsmc.py:503-516, 618-642); no plots."""
         import os
@@ -313,7 +350,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key == 'tree_branches' and not v:       # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))
@@ -417,6 +454,9 @@ class VCSMC:
         self.posterior = None
         if getattr(self.args, 'tree_summary', False):
             self.posterior = self.tree_posterior(branch_lengths=bool(getattr(self.args, 'tree_branches', False)))
+        scores = None
+        if getattr(self.args, 'score_trees', None):        # --score_trees: explicit trees under the final model
+            scores = self._tree_scores(self.args.score_trees)
         if save_dir is not None and getattr(self, '_rank', 0) == 0:   # sharded: every rank holds the same results; rank 0 writes
             if save_dir == 'auto':                   # vcsmc.py:504-507
                 tm = str(datetime.now())
@@ -427,6 +467,11 @@ class VCSMC:
                 self.posterior.write(save_dir)             # tree_posterior.json, consensus.tre
                 if getattr(self.args, 'tree_branches', False):
                     self.posterior.write_branches(save_dir)    # consensus_bl.tre, map.tre, tree_branches.json
+            if scores is not None:
+                import json
+                import os
+                with open(os.path.join(save_dir, 'tree_scores.json'), 'w') as f:
+                    json.dump(scores, f, indent=1)
             self.save_dir = save_dir
             print("Finished...")
         return self.elbos

@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -56,6 +56,12 @@ def parse_args(argv=None):
                         help="with --tree_summary true: also the branch lengths of that posterior (mean, sd, min, max above every "
                              "clade and leaf) into tree_branches.json, consensus_bl.tre (consensus with mean lengths) and map.tre "
                              "(the most probable topology with its mean lengths)")
+    parser.add_argument('--score_trees', default=None, metavar='FILE',
+                        help="a file of rooted Newick trees over the dataset's taxon names, one per line, every branch with its "
+                             "length: after training, their log-likelihoods under the final model (with the model's stationary "
+                             "distribution at the root) go into tree_scores.json in the results directory, with the index of the "
+                             "best one; with --tree_branches true also the scores of map.tre, consensus_bl.tre and the ten most "
+                             "probable topologies at their mean branch lengths")
     args = parser.parse_args(argv)
     if args.tree_branches and not args.tree_summary:
         parser.error('--tree_branches true needs --tree_summary true (it adds branch lengths to that summary)')

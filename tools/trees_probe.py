@@ -1,0 +1,104 @@
+#!/usr/bin/env python
+"""Time phylo_trees_loglik against a loop over phylo_tree_loglik on the same random trees of a shipped dataset, check that the
+two agree bit for bit, and report units/s.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --reps 7 --out profiles/trees_probe.jsonl
+
+The batched call is timed whole (wall, and perf.sweep_ms from hipEvents) `reps` times; the loop is timed over `--loop_trees` of
+the trees (all of them by default) `loop_reps` times.  Medians with the quartiles.  Appends one JSON line to --out."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from phylo_amd import _ffi, model                          # noqa: E402
+from phylo_amd.datasets import load_dataset                # noqa: E402
+
+
+def random_rows(n, rng):
+    roots = list(rng.permutation(n))
+    child = []
+    for i in range(n - 1):
+        a = roots.pop(rng.integers(0, len(roots)))
+        b = roots.pop(rng.integers(0, len(roots)))
+        child.append((a, b))
+        roots.append(n + i)
+    return np.array(child, dtype=np.int32).reshape(n - 1, 2), rng.exponential(0.1, (n - 1, 2))
+
+
+def quartiles(x):
+    q1, q2, q3 = np.percentile(np.asarray(x, dtype=np.float64), [25, 50, 75])
+    return {'median': float(q2), 'q1': float(q1), 'q3': float(q3)}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--dataset', default='hohna_data')
+    ap.add_argument('--trees', type=int, default=4096)
+    ap.add_argument('--reps', type=int, default=7)
+    ap.add_argument('--loop_trees', type=int, default=0, help='trees the loop over tree_loglik takes (0: all)')
+    ap.add_argument('--loop_reps', type=int, default=3)
+    ap.add_argument('--jc', default='false')
+    ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args(argv)
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    pi = np.full(4, 0.25)
+    n_loop = a.trees if a.loop_trees <= 0 else min(a.loop_trees, a.trees)
+    nodes = []
+    for c, b in rows[:n_loop]:
+        left = np.full(2 * N - 1, -1, dtype=np.int32)
+        right = left.copy()
+        bl, br = np.zeros(2 * N - 1), np.zeros(2 * N - 1)
+        left[N:], right[N:], bl[N:], br[N:] = c[:, 0], c[:, 1], b[:, 0], b[:, 1]
+        nodes.append((left, right, bl, br))
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, pi, np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        ll = ctx.trees_loglik(child, blen)                   # warm-up: scratch, code objects
+        wall, dev = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            ll = ctx.trees_loglik(child, blen)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            dev.append(ctx.last_trees_stats['sweep_ms'])
+        stats = dict(ctx.last_trees_stats)
+        ctx.tree_loglik(*nodes[0], 2 * N - 2, g, pi, want_root=False)
+        loop = []
+        for _ in range(a.loop_reps):
+            t0 = time.perf_counter()
+            one = np.array([ctx.tree_loglik(l, r, x, y, 2 * N - 2, g, pi, want_root=False)[0] for l, r, x, y in nodes])
+            loop.append((time.perf_counter() - t0) * 1e3)
+    same = bool(np.array_equal(one.view(np.uint64), ll[:n_loop].view(np.uint64)))
+    w, d, lp = quartiles(wall), quartiles(dev), quartiles(loop)
+    rec = {'probe': 'trees_loglik', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'jc': jc, 'reps': a.reps,
+           'batched_wall_ms': w, 'batched_device_ms': d, 'launches': stats['n_launches'], 'units': stats['units'],
+           'units_per_s_device': stats['units'] / (d['median'] * 1e-3), 'units_per_s_wall': stats['units'] / (w['median'] * 1e-3),
+           'us_per_tree_wall': w['median'] * 1e3 / a.trees,
+           'loop_trees': n_loop, 'loop_reps': a.loop_reps, 'loop_wall_ms': lp, 'loop_us_per_tree': lp['median'] * 1e3 / n_loop,
+           'ratio_loop_over_batched_per_tree': (lp['median'] / n_loop) / (w['median'] / a.trees),
+           'bit_equal': same, 'finite': bool(np.isfinite(ll).all())}
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same else 1
+
+
+if __name__ == '__main__':
+    sys.exit(main())
