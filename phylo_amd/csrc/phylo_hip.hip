@@ -129,6 +129,7 @@ struct phylo_ctx {
     double *d_bl = nullptr, *d_br = nullptr, *d_Pmat = nullptr;   // [(N-1)][Kloc](x32)
     double *d_logw = nullptr, *d_ll = nullptr;                    // [(N-1)][K] (global columns)
     double* d_aux = nullptr;             // [Kloc][PK_AUX]
+    unsigned long long* d_rec = nullptr; // [Kloc][PK_REC] merge records (128-byte lines)
     int tile_override = 0;               // PHYLO_SITE_TILE / phylo_set_site_tile (0: the policy pm_site_tile)
     int site_tile = 0, ntiles = 1;       // contract v5: sites per tile of the canonical sum over sites (multiple of 64), ceil(S / tile)
     double* d_tilev = nullptr;           // [Kloc][ntiles] tile values of the merge (rows longer than one tile)
@@ -395,11 +396,12 @@ void free_sweep_state(phylo_ctx* c) {
     c->d_tilev = nullptr;
     void* ptrs[] = {c->d_pool, c->d_nodell, c->d_bl, c->d_br, c->d_Pmat, c->d_logw, c->d_ll, c->d_aux, c->d_lse, c->d_group_seeds,
                     c->d_tables, (void*)c->d_tab_ptrs, c->d_child, c->d_merges, c->d_anc,
-                    c->d_cdf[0], c->d_cdf[1], c->d_counter, (void*)c->d_pool_ptrs, c->d_mark, c->d_sync, c->d_mirror, c->d_cache};
+                    c->d_cdf[0], c->d_cdf[1], c->d_counter, (void*)c->d_pool_ptrs, c->d_mark, c->d_sync, c->d_mirror, c->d_cache, c->d_rec};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->d_pool = c->d_nodell = c->d_bl = c->d_br = c->d_Pmat = c->d_logw = c->d_ll = c->d_aux = c->d_lse = nullptr;
     c->d_group_seeds = nullptr;
+    c->d_rec = nullptr;
     c->d_roots[0] = c->d_roots[1] = c->d_cnt[0] = c->d_cnt[1] = c->d_child = c->d_merges = nullptr;
     c->d_anc = nullptr;
     c->d_cdf[0] = c->d_cdf[1] = nullptr;
@@ -454,6 +456,7 @@ int alloc_sweep_state(phylo_ctx* c) {
         CHK(dalloc(c, &c->d_ll, R * K));
     }
     CHK(dalloc(c, &c->d_aux, Kl * PK_AUX));
+    CHK(dalloc(c, &c->d_rec, Kl * PK_REC));
     if (c->ntiles > 1) CHK(dalloc(c, &c->d_tilev, Kl * (size_t)c->ntiles));
     CHK(dalloc(c, &c->d_lse, (R + 1) * PK_MAX_GROUPS));
     CHK(dalloc(c, &c->d_group_seeds, PK_MAX_GROUPS));
@@ -1586,6 +1589,10 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
         b.ll_r = c->d_ll + (size_t)r * K;
         b.merges = c->d_merges; b.ancestors = c->d_anc;
         b.child = c->d_child + (size_t)r * Kl * 2; b.aux = c->d_aux;
+        // one rank, plain proposal, a merge that stores nothing: the bookkeeping also leaves a merge record per particle and the
+        // merge starts from it (the storing merge and the sharded and twisted sweeps resolve ids: no record is written for them)
+        const bool use_rec = !twist && Kl == K && (lazy || b.no_store);
+        b.rec = use_rec ? c->d_rec : nullptr;
         b.lazy = lazy ? 1 : 0; b.mark = c->d_mark; b.child_all = c->d_child; b.Pmat_all = c->d_Pmat;
         b.T = c->site_tile; b.ntiles = c->ntiles; b.tilev = c->d_tilev;
         if (twist) {
@@ -1691,11 +1698,21 @@ static int sweep_step_impl(phylo_ctx* c, int phase) {
         const bool nostore = b.lazy || b.no_store;
         const size_t mitems = (size_t)Kl * c->ntiles;                              // one wave per (particle, site tile)
         const dim3 mgrid((unsigned)mitems);
+        // pi by value, from the pinned image of the model upload.  Invariant: phylo_set_model is the only writer of d_Q / d_pi and
+        // of that image, and it rewrites the image only after the previous upload has finished, so for every launch issued after
+        // it returns the image equals the model the other kernels read from d_pi.  A model update made on the device would have
+        // to refresh the image too.
+        pk_pi4 pi4;
+        memcpy(pi4.v, c->h_model_p + 16, sizeof pi4.v);
+        const unsigned long long* mrec = b.rec;
         if (timek && !twist) {  // events stamped with the kernel's own begin/end (what rocprofv3 --kernel-trace reports)
-            if (nostore) hipExtLaunchKernelGGL(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, b);
+            if (nostore && use_rec) hipExtLaunchKernelGGL(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, mrec, b.Pmat, S, b.T, b.ntiles, b.tilev, pi4);
+            else if (nostore) hipExtLaunchKernelGGL(pk_rank_merge_nostore_ids, mgrid, dim3(64), 0, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, b);
             else hipExtLaunchKernelGGL(pk_rank_merge, mgrid, dim3(PK_COLS), (size_t)(c->site_tile < S ? c->site_tile : S) * 8 + 16 + PK_STORE_STAGE_BYTES, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, b);
+        } else if (nostore && use_rec) {
+            hipLaunchKernelGGL(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, mrec, b.Pmat, S, b.T, b.ntiles, b.tilev, pi4);
         } else if (nostore) {
-            hipLaunchKernelGGL(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, b);
+            hipLaunchKernelGGL(pk_rank_merge_nostore_ids, mgrid, dim3(64), 0, c->stream, b);
         } else {
             hipLaunchKernelGGL(pk_rank_merge, mgrid, dim3(PK_COLS), (size_t)(c->site_tile < S ? c->site_tile : S) * 8 + 16 + PK_STORE_STAGE_BYTES, c->stream, b);
         }

@@ -13,6 +13,15 @@
 
 // aux slots
 enum { AUX_SUM_REM = 0, AUX_FPRIOR, AUX_LPRIOR, AUX_RPRIOR, AUX_LL_TILDE, AUX_PAREN, AUX_LOGV, AUX_Q };
+// Merge record: everything one wave of pk_rank_merge_nostore needs about its particle, in one aligned 128-byte line that the
+// bookkeeping writes beside aux / child: the aux row, the two children ALREADY RESOLVED to the address the row loop reads (rows
+// of a node, or the 1-byte codes of a coded leaf), the four addresses the epilogue writes, and a flag word.  One rank only: the
+// address of a child in a peer's pool or in the cache of remote nodes is not known to every particle when its bookkeeping
+// runs (another wave of the same launch may still be fetching it), so sharded sweeps keep the form that resolves ids.
+#define PK_REC 16            // 64-bit slots per record
+enum { REC_BASE_L = PK_AUX, REC_BASE_R, REC_NODELL, REC_ROOTLL, REC_LL, REC_LOGW, REC_FLAGS /* bit 0 / 1: left / right child is a coded leaf */ };
+#define PK_REC_SLOTS (REC_FLAGS + 1)
+static_assert(PK_REC_SLOTS <= PK_REC && PK_REC_SLOTS <= 16, "one lane per slot: pk_rank_book_mat and pk_rank_book write the record with the first 16 lanes of a particle");
 
 // ------------------------------------------------------------------------------------------------
 // Canonical sum over 256 columns of a workgroup (the sum over PARTICLES of the resampling weights: element k
@@ -70,10 +79,20 @@ __device__ __forceinline__ const char* pk_uniform_ptr(const void* p);
         : "=&s"(pk_t0_), "=&s"(pk_t1_), "=&s"(pk_t2_), "=&s"(pk_t3_), "=&s"(pk_t4_), "=&s"(pk_t5_)                             \
         : "s"(pk_uniform_ptr(p256)), "s"(pk_uniform_ptr(q)), "s"(pk_uniform_ptr(r)))   /* (readfirstlane: a uniform value may live in VGPRs) */
 #define PK_TOUCH_END(x) asm("s_waitcnt lgkmcnt(0)" : "+s"(x) : "s"(pk_t0_), "s"(pk_t1_), "s"(pk_t2_), "s"(pk_t3_), "s"(pk_t4_), "s"(pk_t5_))
+// the same for the matrices alone (pk_rank_merge_nostore: pi travels by value, the aux row is part of the record it loads anyway)
+#define PK_TOUCH4_DECL unsigned int pk_t0_, pk_t1_, pk_t2_, pk_t3_
+#define PK_TOUCH4_256(p256)                                                                                                     \
+    asm("s_load_dword %0, %4, 0x0\n\ts_load_dword %1, %4, 0x40\n\ts_load_dword %2, %4, 0x80\n\ts_load_dword %3, %4, 0xc0"          \
+        : "=&s"(pk_t0_), "=&s"(pk_t1_), "=&s"(pk_t2_), "=&s"(pk_t3_)                                                           \
+        : "s"(pk_uniform_ptr(p256)))
+#define PK_TOUCH4_END(x) asm("s_waitcnt lgkmcnt(0)" : "+s"(x) : "s"(pk_t0_), "s"(pk_t1_), "s"(pk_t2_), "s"(pk_t3_))
 #else
 #define PK_TOUCH_DECL
 #define PK_TOUCH_256_2(p256, q, r)
 #define PK_TOUCH_END(x)
+#define PK_TOUCH4_DECL
+#define PK_TOUCH4_256(p256)
+#define PK_TOUCH4_END(x)
 #endif
 
 __device__ __forceinline__ double pk_wave_tree_sum(double v) {
@@ -693,6 +712,7 @@ struct pk_rank_args {
     // value in tilev[k][tile] and pk_tile_epilogue adds them left to right and finishes the particle.
     int T, ntiles;
     double* tilev;                                        // [Kloc][ntiles] or NULL (ntiles == 1)
+    unsigned long long* rec;                              // [Kloc][PK_REC] merge records (one rank, plain proposal) or NULL
 };
 
 // LDS carve of the bookkeeping prologue (arrays of length N rounded up to a multiple of 4)
@@ -721,6 +741,32 @@ __device__ __forceinline__ pk_book_lds pk_book_carve(char* base, int N) {
     L.ord_cnt = L.co + n4;
     L.misc = L.ord_cnt + n4;
     return L;
+}
+
+// slot t < PK_REC_SLOTS of local particle k's merge record, from what the bookkeeping left in LDS (one lane per slot, the lanes
+// that write aux / child).  A child's address is pk_node_ptr's for one rank, or the leaf's codes where the merge reads codes.
+__device__ __forceinline__ void pk_rec_write(const pk_rank_args& a, int k, int kg, int t, const pk_book_lds& L) {
+    const size_t node_sz = (size_t)a.S * 4;
+    unsigned long long v;
+    if (t < PK_AUX) {
+        v = (unsigned long long)__double_as_longlong(L.aux[t]);
+    } else if (t <= REC_BASE_R) {
+        const int id = L.misc[t - REC_BASE_L];
+        if (id >= a.N) v = (unsigned long long)(a.pool + (size_t)(id - a.N) * node_sz);
+        else if (a.leaf_codes) v = (unsigned long long)(a.leaf_codes + (size_t)id * a.S);
+        else v = (unsigned long long)(a.leaves + (size_t)id * node_sz);
+    } else if (t == REC_NODELL) {
+        v = (unsigned long long)(a.nodell + (a.N + a.r * a.K + kg));
+    } else if (t == REC_ROOTLL) {
+        v = (unsigned long long)(a.rootll_new + ((size_t)kg * a.N + (a.n - 2)));
+    } else if (t == REC_LL) {
+        v = (unsigned long long)(a.ll_r + kg);
+    } else if (t == REC_LOGW) {
+        v = (unsigned long long)(a.logw_r + kg);
+    } else {
+        v = a.leaf_codes ? (unsigned long long)((L.misc[0] < a.N ? 1 : 0) | (L.misc[1] < a.N ? 2 : 0)) : 0ull;
+    }
+    a.rec[(size_t)k * PK_REC + t] = v;
 }
 
 // Bookkeeping of one rank event for ONE particle (global index kg), by the first wave of a workgroup;
@@ -1146,6 +1192,10 @@ __global__ __launch_bounds__(64) void pk_rank_book_packed(const pk_rank_args a) 
             if (t < PK_AUX) a.aux[(size_t)k * PK_AUX + t] = L.aux[t];
             else a.child[k * 2 + (t - PK_AUX)] = L.misc[t - PK_AUX];
         }
+        if (a.rec) {
+#pragma unroll
+            for (int t = sl; t < PK_REC_SLOTS; t += LP) pk_rec_write(a, k, kg, t, L);
+        }
     }
     if (a.lazy && a.r > 0 && sl == 0) {
         const int anc = L.misc[3];
@@ -1353,6 +1403,7 @@ __global__ __launch_bounds__(PK_COLS, 5) void pk_rank_book_mat(const pk_rank_arg
         if (sl < PK_AUX) a.aux[(size_t)kg * PK_AUX + sl] = L.aux[sl];
         else a.child[kg * 2 + (sl - PK_AUX)] = L.misc[sl - PK_AUX];
     }
+    if (a.rec && sl < PK_REC_SLOTS) pk_rec_write(a, kg, kg, sl, L);          // (LP >= 16 here)
     if (a.r > 0 && sl == 0) a.mark[(size_t)(a.r - 1) * a.K + L.misc[3]] = 1u;   // the marks stay (phylo_sweep_node reads them)
 }
 
@@ -1370,6 +1421,7 @@ __global__ __launch_bounds__(64) void pk_rank_book(const pk_rank_args a) {
         if (threadIdx.x < PK_AUX) a.aux[(size_t)k * PK_AUX + threadIdx.x] = L.aux[threadIdx.x];
         else a.child[k * 2 + (threadIdx.x - PK_AUX)] = L.misc[threadIdx.x - PK_AUX];
     }
+    if (local && a.rec && threadIdx.x < PK_REC_SLOTS) pk_rec_write(a, kg - a.k0, kg, threadIdx.x, L);
     if (a.lazy && a.r > 0 && threadIdx.x == 0) {
         // this particle adopted the table of `anc`: the node anc created at the previous rank event is now live;
         // pk_materialize_adopted writes the marked nodes of that rank event.
@@ -1735,7 +1787,7 @@ __device__ __forceinline__ void pk_rows_v4(int s0, int s1, const double* Xp, con
 // a workgroup is one wave (two or four independent waves per workgroup measured: 1-3 % slower).  The wave's matrices, pointers
 // and site bounds are wave-uniform (scalar registers).  Row-per-lane form: lane c owns column c of the tile, reads whole 32-byte rows (or 1-byte codes), no DPP
 // moves: about half the instructions per site of the lane-pair form, whose point is the 16-byte-per-lane store.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void pk_rank_merge_nostore(const pk_rank_args a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void pk_rank_merge_nostore_ids(const pk_rank_args a) {
     __shared__ __attribute__((aligned(16))) double tabL[5][4], tabR[5][4];
     __shared__ double lik25[25];
     const int item = (int)blockIdx.x, ntiles = a.ntiles;
@@ -1783,6 +1835,109 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
             ka->rootll_new[(size_t)kg * N + (ka->n - 2)] = tot;
             ka->ll_r[kg] = ll;
             ka->logw_r[kg] = lw;
+        }
+    }
+}
+
+// ---- The same merge started from the particle's merge record (one rank, plain proposal: every launch of the flagship).  The wave's
+//      start-up is then: flat kernel arguments -> ONE line of the record (both row bases resolved, the flag word; the matrices'
+//      lines are touched beside it) -> first rows and matrices.  No child ids, no pointer arithmetic, no sharded branch, and each
+//      variant requests only the matrix registers it uses: none when both children are coded (the 25 lanes that build lik25
+//      read the matrices' rows themselves: one LDS fence), one matrix when one child is coded.  Same fma chains, same bits.
+struct pk_pi4 { double v[4]; };
+typedef __attribute__((address_space(1))) const double pk_gdc;
+typedef __attribute__((address_space(1))) double pk_gd;
+typedef __attribute__((address_space(4))) const unsigned long long pk_cu64;
+typedef __attribute__((address_space(4))) const double pk_cdbl;
+// (leaf row of code c) . P for this lane's c: row c of P, or pk_build_leaf_table's chain over an all-ones row (c == 4: the
+// five lanes that need the other three rows fetch them in a branch of their own, which keeps 24 registers out of the others)
+__device__ __forceinline__ void pk_leaf_vec(const double* __restrict__ P /*16*/, int c, double (&t)[4]) {
+    pk_load4(P + (c < 4 ? c : 0) * 4, t);
+    if (c == 4) {
+        double v[3][4];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pk_load4(P + (i + 1) * 4, v[i]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[j] = pm_fma(1.0, v[2][j], pm_fma(1.0, v[1][j], pm_fma(1.0, v[0][j], 1.0 * t[j])));
+    }
+}
+__device__ __forceinline__ void pk_build_lik25_direct(const double* __restrict__ Pu /*32*/, const double (&pi)[4], double* lik25, int t) {
+    if (t < 25) {
+        const int cl = t / 5, cr = t - cl * 5;
+        double tl[4], tr[4], o[4];
+        pk_leaf_vec(Pu, cl, tl);
+        pk_leaf_vec(Pu + 16, cr, tr);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = tl[j] * tr[j];
+        lik25[t] = pk_site_lik(pi, o);
+    }
+}
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_rows_loop_rec(int s0, int s1, const char* bl, const char* br, const double* Pu, const double (&Pl)[16],
+                                                 const double (&Pr)[16], double (*tabL)[4], double (*tabR)[4], double* lik25,
+                                                 const double (&pi)[4], pm_lp& col) {
+    const int lane = threadIdx.x & 63;
+    pk_rowregs A;
+    pk_rows_load<CL, CR>(A, bl, br, s0 + lane, s1);        // the first rows / codes travel while the tables are built
+    if constexpr (CL && CR) {
+        pk_build_lik25_direct(Pu, pi, lik25, lane);
+        pk_wave_lds_fence();
+    } else if constexpr (CL) {
+        pk_build_leaf_table(Pu, tabL, lane);
+        pk_wave_lds_fence();
+    } else if constexpr (CR) {
+        pk_build_leaf_table(Pu + 16, tabR, lane);
+        pk_wave_lds_fence();
+    }
+    pk_rows_run<CL, CR>(s0, s1, bl, br, A, Pl, Pr, tabL, tabR, lik25, pi, col);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8)))
+void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const double* __restrict__ Pmat, int S, int T, int ntiles,
+                           double* __restrict__ tilev, const pk_pi4 pi4) {
+    __shared__ __attribute__((aligned(16))) double tabL[5][4], tabR[5][4];
+    __shared__ double lik25[25];
+    const int item = (int)blockIdx.x;
+    const int k = ntiles == 1 ? item : item / ntiles, tau = item - k * ntiles;
+    const int s0 = tau * T, s1 = s0 + T < S ? s0 + T : S;
+    // the record and the matrices were written by earlier launches and nothing writes them during this one: read through the
+    // constant address space, a uniform address is a scalar load wherever hipcc places it (a global one only where it proves that
+    // no store of the kernel comes before it, which it does not once it has moved the load into a variant's branch)
+    const pk_cu64* rc = (const pk_cu64*)(rec + (size_t)k * PK_REC);
+    const double* Pu = Pmat + (size_t)k * 32;
+    const pk_cdbl* Pc = (const pk_cdbl*)Pu;
+    PK_TOUCH4_DECL;
+    PK_TOUCH4_256(Pu);
+    unsigned int fl = (unsigned int)rc[REC_FLAGS];
+    const char* bl = pk_uniform_ptr((const void*)rc[REC_BASE_L]);
+    const char* br = pk_uniform_ptr((const void*)rc[REC_BASE_R]);
+    PK_TOUCH4_END(fl);                                     // (before the first use of the flags, on every path)
+    const double pi[4] = {pi4.v[0], pi4.v[1], pi4.v[2], pi4.v[3]};
+    // uniform address, nothing stored yet: scalar loads, which hipcc requests where a matrix is first used -- a coded side's matrix
+    // is never read (pk_rows_out), so a variant requests only what it uses
+    double Pl[16], Pr[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { Pl[u] = Pc[u]; Pr[u] = Pc[16 + u]; }
+    pm_lp col = pm_lp_init();
+    if (fl & 1u) {
+        if (fl & 2u) pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
+        else pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
+    } else {
+        if (fl & 2u) pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
+        else pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
+    }
+    const double tot = pk_wave_tree_sum(pm_lp_finish(col));
+    if (threadIdx.x == 0) {
+        if (ntiles != 1) {
+            tilev[(size_t)k * ntiles + tau] = tot;
+        } else {                                           // the aux row and the four addresses: the record's line again
+            const pk_cdbl* ax = (const pk_cdbl*)rc;
+            const double fl2 = ax[AUX_SUM_REM] + tot;
+            const double ll = ((fl2 + ax[AUX_FPRIOR]) + ax[AUX_LPRIOR]) + ax[AUX_RPRIOR];
+            const double lw = (((ll - ax[AUX_LL_TILDE]) - ax[AUX_PAREN]) + ax[AUX_LOGV]) - ax[AUX_Q];
+            *(pk_gd*)rc[REC_NODELL] = tot;
+            *(pk_gd*)rc[REC_ROOTLL] = tot;
+            *(pk_gd*)rc[REC_LL] = ll;
+            *(pk_gd*)rc[REC_LOGW] = lw;
         }
     }
 }
