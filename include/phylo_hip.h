@@ -306,6 +306,18 @@ int phylo_debug_lookahead_lists(int N, int K, int S, int M, const int32_t* roots
  * 8 rows_all, 9 rows_overlap, 10 chunks_first, 11 interleave, 12 coeff_all.  tests/test_revplan_cpu.py restates the rules. */
 int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int twisted, int marks, uint32_t switches, int64_t n_slow,
                              int TS, int64_t coeff_wgs, int passes_in_flight, uint32_t* mask);
+/* Test hook, no GPU needed: the form the forward sweep's launch path takes (sweep_plan_form + sweep_plan_launches,
+ * phylo_sweep_plan.h; DESIGN.md section 4 "driver") for a shape, a communicator (transport != 0), the flags of phylo_sweep_begin
+ * and the switches: bit 0 PHYLO_EAGER_NODES, 1 PHYLO_REHEARSE_SHARDED, 2 PHYLO_REPLICATED_BOOK (the environment), then three facts
+ * of the context: bit 3 a JC69 model, 4 coded leaves, 5 the device-side exchange.  The site tile is the policy's (phylo_site_tile).
+ * mask: bit 0 twist, 1 graph, 2 timek, 3 lazy, 4 shard_form, 5 replicated_book, 6 local_book, 7 book_mat, 8 mat_by_draws,
+ * 9 want_rdraw, 10 use_rec, 11 sorted_prologue, 12 mat_grouped, 13 mat_draws_grouped, 14 step_a_work, 15 mat_after_book,
+ * 16 mat_barrier, 17 fix_rootll, 18 fold_logz, 19 no_store_last, 20 final_missing, 21 last_graph_eager, 22 one_tile, 23 twist_ll,
+ * 24 twist_tables, 25 tile_epilogue, 26 batched (the scan strides over the groups' log-normalisers); bits 28..31 book_width / 8.
+ * launches[N + 1]: what stats.n_launches counts for the begin ([0]), rank event r ([r + 1]) and the finish ([N]).  Arguments that
+ * phylo_sweep_begin refuses are refused with the same code and message.  tests/test_sweepplan_cpu.py restates the rules. */
+int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
+                           uint32_t* mask, int32_t* launches);
 /* ... after a batched sweep of G groups (K the total): the device lists' limit is per group (K / G <= 8192), every other
  * limit sees the totals.  G = 1 is phylo_debug_reverse_plan. */
 int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,

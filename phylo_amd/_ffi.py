@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -143,6 +143,33 @@ def debug_reverse_plan(N, K, S, K_local=None, world=1, twisted=False, marks=True
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     out = {name: bool(mask.value >> i & 1) for i, name in enumerate(PLAN_BITS)}
     out["mask"] = mask.value
+    return out
+
+
+SWEEP_PLAN_BITS = ("twist", "graph", "timek", "lazy", "shard_form", "replicated_book", "local_book", "book_mat", "mat_by_draws", "want_rdraw",
+                   "use_rec", "sorted_prologue", "mat_grouped", "mat_draws_grouped", "step_a_work", "mat_after_book", "mat_barrier",
+                   "fix_rootll", "fold_logz", "no_store_last", "final_missing", "last_graph_eager", "one_tile", "twist_ll", "twist_tables",
+                   "tile_epilogue", "batched")
+SWEEP_PLAN_SWITCHES = ("eager_nodes", "rehearse_sharded", "replicated_book", "jc", "coded_leaves", "device_exchange")
+
+
+def debug_sweep_plan(N, K, S, K_local=None, G=1, M=1, world=1, transport=False, flags=0, switches=()):
+    """The form the forward sweep's launch path takes for a shape, the flags of a sweep and the switches (names of
+    SWEEP_PLAN_SWITCHES: three environment switches, then three facts of the context) -- no GPU needed: a dict of the booleans of
+    SWEEP_PLAN_BITS, 'book_width', 'mask' and 'launches' (what stats['n_launches'] counts: [0] the begin, [r + 1] rank event r,
+    [N] the finish)."""
+    lib = load()
+    sw = sum(1 << SWEEP_PLAN_SWITCHES.index(name) for name in switches)
+    mask = C.c_uint32(0)
+    launches = (C.c_int32 * (max(N, 1) + 1))()
+    rc = lib.phylo_debug_sweep_plan(C.c_int(N), C.c_int(K), C.c_int(K if K_local is None else K_local), C.c_int(S), C.c_int(G), C.c_int(M),
+                                    C.c_int(world), C.c_int(int(transport)), C.c_uint32(flags), C.c_uint32(sw), C.byref(mask), launches)
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    out = {name: bool(mask.value >> i & 1) for i, name in enumerate(SWEEP_PLAN_BITS)}
+    out["book_width"] = (mask.value >> 28) * 8
+    out["mask"] = mask.value
+    out["launches"] = list(launches)
     return out
 
 

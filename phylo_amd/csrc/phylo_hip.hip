@@ -21,6 +21,7 @@
 #include "phylo_persist.h"
 #include "phylo_grad.h"
 #include "phylo_revlists_dev.h"
+#include "phylo_sweep_plan.h"
 #include "phylo_train.h"
 #include "phylo_trees.h"
 #include "phylo_treeset.h"
@@ -43,14 +44,9 @@ struct sweep_run {                       // a sweep being issued rank event by r
     uint64_t seed = 0;
     uint32_t flags = 0;
     int M = 1, launches = 0, next_r = 0;
-    bool twist = false, graph = false, lazy = false, timek = false, active = false, local_book = false;
-    bool mat_by_draws = false;             // sharded: owners find their adopted nodes from the draws (no pk_all_marks)
-    bool replicated_book = false;          // sharded: every rank advances all K root tables (PHYLO_REPLICATED_BOOK; a kept graph)
-    bool logz_done = false;                // the last scan summed the log-normalisers (no pk_logz_total launch)
-    bool book_mat = false;                 // bookkeeping and the writes of the adopted nodes share one launch (pk_rank_book_mat)
-    int G = 1;                             // independent sweeps batched in this context (phylo_sweep_batch_async)
-    bool final_missing = false;            // the last rank event's nodes were not stored
+    bool active = false;
     int a_done_r = -1;                     // rank event whose first half (sweep_step_a) has been issued
+    sweep_plan plan{};                     // the form, decided by sweep_begin_impl (phylo_sweep_plan.h)
 };
 
 // Switches of DESIGN.md section 6b, read from the environment ONCE (phylo_create): none changes a result bit.  Each one serves a
@@ -598,6 +594,13 @@ int ensure_graph_state(phylo_ctx* c) {
     }
     c->graph_ready = true;
     return PHYLO_OK;
+}
+
+// One launch with the kernel's own begin / end stamped into a pair of events (what rocprofv3 --kernel-trace reports), or without
+template <typename... P, typename... A>
+void launch_stamped(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, A&&... args) {
+    if (e0) hipExtLaunchKernelGGL(kernel, grid, block, lds, s, e0, e1, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
 }
 
 // resampling scan of G groups of Kg log-weights: the LDS form when a group fits (phylo_persist.h), else pk_resample_scan
@@ -1159,177 +1162,208 @@ int phylo_log_zsmc(phylo_ctx* c, const double* logw, int R, int K, double* out) 
     return PHYLO_OK;
 }
 
-static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, const uint64_t* group_seeds, int G) {
+// ---- the forward sweep, launch path ---------------------------------------------------------------------------------------------
+// The form is decided once per sweep (phylo_sweep_plan.h): sweep_begin_impl computes the plan from the facts below and stores it
+// in the run; sweep_step_a, the stages of a rank event and phylo_sweep_finish read it and nothing else (no environment switch, no
+// flag bit).  The order of the HIP calls on the stream is what the measurements in that header's comments paid for.
+static sweep_limits sweep_limits_of() {
+    sweep_limits L{};
+    L.max_groups = PK_MAX_GROUPS; L.twist_max_m = PK_TWIST_MAX_M; L.twist_max_j = PK_TWIST_MAX_J;
+    L.mat_group = PK_MAT_GROUP; L.scan_fold_max_kg = PP_SCAN_KERNEL_MAX_KG; L.kept_bits_taxa = PG_KEPT_BITS_TAXA;
+    L.one_tile_max_s = 4096;
+    L.small_max_kg = 4096; L.small_max_kloc = 8192;
+    L.book_packed8_min = 8192;
+    L.sorted_min_draws = 262144;
+    return L;
+}
+static const sweep_limits k_sweep_limits = sweep_limits_of();
+
+// the flag bits of phylo_sweep_begin as facts (the driver and phylo_debug_sweep_plan decode them here)
+static void sweep_facts_flags(sweep_facts& f, uint32_t flags) {
+    f.twisting = (flags & PHYLO_TWISTING) != 0; f.keep_graph = (flags & PHYLO_KEEP_GRAPH) != 0;
+    f.eager_nodes = (flags & PHYLO_EAGER_NODES) != 0; f.time_kernels = (flags & PHYLO_TIME_KERNELS) != 0;
+}
+
+static sweep_facts sweep_facts_of(const phylo_ctx* c, uint32_t flags, int M, int G) {
+    sweep_facts f{};
+    f.N = c->N; f.K = c->K; f.Kloc = c->Kloc; f.S = c->S; f.G = G; f.M = M; f.world = c->world; f.ntiles = c->ntiles;
+    f.transport = c->comm.transport != 0; f.device_exchange = c->p2p; f.jc = c->jc != 0; f.coded_leaves = c->codes_valid;
+    sweep_facts_flags(f, flags);
+    f.env_eager_nodes = c->env.eager_nodes; f.env_rehearse_sharded = c->env.rehearse_sharded;
+    f.env_replicated_book = c->env.replicated_book;
+    return f;
+}
+
+// What every sweep needs before its first launch, on the launch path and as one launch alike: bind, no run in progress, ...
+static int sweep_bind(phylo_ctx* c) {
     CHK(bind(c));
     c->run.active = false;
-    if (G < 1 || G > PK_MAX_GROUPS || c->K % G != 0)
-        return fail(c, PHYLO_EINVAL, "a batch needs 1 <= G <= %d sweeps and K = %d divisible by G (got %d)", PK_MAX_GROUPS, c->K, G);
-    if (G > 1 && (flags & PHYLO_TWISTING))
-        return fail(c, PHYLO_EINVAL, "batched sweeps need the plain proposal (PHYLO_TWISTING is set)");
-    if (G > 1 && (flags & PHYLO_KEEP_GRAPH)) {             // the graph of G systems: one block-diagonal genealogy, rows form, one GPU
-        if (c->world != 1 || c->comm.transport != 0)
-            return fail(c, PHYLO_EINVAL, "batched sweeps with PHYLO_KEEP_GRAPH need an unsharded context");
-        if (c->S > 4096)
-            return fail(c, PHYLO_EINVAL, "batched sweeps with PHYLO_KEEP_GRAPH need S <= 4096 sites (got %d)", c->S);
-    }
+    return PHYLO_OK;
+}
+// ... leaves and model, the first-use state and the leaves' log-likelihoods
+static int sweep_ready(phylo_ctx* c) {
     if (!c->have_leaves || !c->have_model)
         return fail(c, PHYLO_ESTATE, "phylo_set_leaves and phylo_set_model must be called before a sweep");
     if (!c->state_ready) {
         CHK(ensure_sweep_state(c));
         CHK(refresh_leaf_ll(c));
     }
-    const int N = c->N, K = c->K, Kl = c->Kloc, S = c->S, R = N - 1;
-    const bool twist = (flags & PHYLO_TWISTING) != 0;
-    if (twist) {
-        if (M < 1 || M > PK_TWIST_MAX_M) return fail(c, PHYLO_EINVAL, "twisting needs 1 <= M <= %d (got %d)", PK_TWIST_MAX_M, M);
-        const size_t Jmax = (size_t)(N * (N - 1) / 2) * M;
-        if (Jmax > PK_TWIST_MAX_J) return fail(c, PHYLO_EINVAL, "twisting: C(N,2)*M = %zu exceeds %d", Jmax, PK_TWIST_MAX_J);
-        if (Jmax > PK_TWIST_LDS_J && c->twbuf_cap < (size_t)Kl * Jmax) {     // weights of more sub-samples than LDS holds
-            if (c->d_twbuf) (void)hipFree(c->d_twbuf);
-            c->d_twbuf = nullptr;
-            c->twbuf_cap = 0;
-            CHK(dalloc(c, &c->d_twbuf, (size_t)Kl * Jmax));
-            c->twbuf_cap = (size_t)Kl * Jmax;
-        }
-        if (!c->d_roots_ad) {
-            CHK(dalloc(c, &c->d_roots_ad, (size_t)K * N));
-            CHK(dalloc(c, &c->d_cnt_ad, (size_t)K * N));
-            CHK(dalloc(c, &c->d_rootll_ad, (size_t)K * N));
-            if (!c->p2p) CHK(dalloc(c, &c->d_chosen, (size_t)K));
-        }
-        if (c->tw_capacity < (size_t)Kl * Jmax) {
-            if (c->d_tw_b) { (void)hipFree(c->d_tw_b); (void)hipFree(c->d_tw_P); (void)hipFree(c->d_pot); }
-            c->d_tw_b = c->d_tw_P = c->d_pot = nullptr;
-            c->tw_capacity = 0;
-            CHK(dalloc(c, &c->d_tw_b, (size_t)Kl * Jmax * 2));
-            CHK(dalloc(c, &c->d_tw_P, (size_t)Kl * Jmax * 32));
-            CHK(dalloc(c, &c->d_pot, (size_t)Kl * Jmax));
-            c->tw_capacity = (size_t)Kl * Jmax;
-        }
-    }
-    if (twist && c->codes_valid && !c->hist_ready) {
-        if (!c->d_pair_hist) CHK(dalloc(c, &c->d_pair_hist, (size_t)N * N * 32));
-        hipLaunchKernelGGL(pk_pair_hist, dim3(N, N), dim3(256), 0, c->stream, (const uint8_t*)c->d_leaf_codes, N, S, c->d_pair_hist);
-        CHK(launch_check(c, "pk_pair_hist"));
-        c->hist_ready = true;
-    }
-    const bool timek = (flags & PHYLO_TIME_KERNELS) != 0;
-    if (timek && (int)c->kev.size() < 2 * R) {
-        while ((int)c->kev.size() < 2 * R) {
-            hipEvent_t e;
-            HIPCHK(c, hipEventCreate(&e));
-            c->kev.push_back(e);
-        }
-    }
-    // lazy nodes: dead stores are most of the HBM traffic of the plain sweep (a node is read again only if its
-    // creator survives the next resampling).  Needs every reader on this GPU and the plain proposal.
-    // Pays when a node is large (HBM-bound merges); on small nodes the extra launch costs more than the stores.
-    const bool graph = (flags & PHYLO_KEEP_GRAPH) != 0;
-    if (graph) {
-        if (c->world != 1) {                               // sharded: the plain proposal on nodes of one site tile (graph_gather)
-            if (twist) return fail(c, PHYLO_EINVAL, "PHYLO_KEEP_GRAPH with PHYLO_TWISTING needs an unsharded context");
-            if (S > 4096) return fail(c, PHYLO_EINVAL, "PHYLO_KEEP_GRAPH on a sharded context needs S <= 4096 sites (got %d)", S);
-        }
-        CHK(ensure_graph_state(c));
-        if (twist) {                                       // every rank event keeps its sub-samples: rows [r][k][J_r]
-            c->h_joff.assign((size_t)R + 1, 0);
-            for (int r = 0; r < R; ++r) c->h_joff[r + 1] = c->h_joff[r] + (int64_t)K * (((N - r) * (N - r - 1)) / 2) * M;
-            const size_t rows = (size_t)c->h_joff[R];
-            if (c->htw_rows < rows) {
-                void* old[] = {c->d_htw_b, c->d_htw_P, c->d_hpot, c->d_tau, c->d_twpart};
-                for (void* p : old)
-                    if (p) (void)hipFree(p);
-                c->d_htw_b = c->d_htw_P = c->d_hpot = c->d_tau = c->d_twpart = nullptr;
-                c->htw_rows = 0;
-                CHK(dalloc(c, &c->d_htw_b, rows * 2));
-                CHK(dalloc(c, &c->d_htw_P, rows * 32));
-                CHK(dalloc(c, &c->d_hpot, rows));
-                CHK(dalloc(c, &c->d_tau, rows));
-                CHK(dalloc(c, &c->d_twpart, rows * PG_PART));
-                c->htw_rows = rows;
-            }
-            if (!c->d_hroots_ad) {
-                CHK(dalloc(c, &c->d_hroots_ad, (size_t)R * K * N));
-                CHK(dalloc(c, &c->d_hchosen, (size_t)R * K));
-                CHK(dalloc(c, &c->d_ctw, (size_t)R * K * N));
-                CHK(dalloc(c, &c->d_twnode, (size_t)R * K * PG_NODEG));
-                CHK(dalloc(c, &c->d_joff, (size_t)R + 1));
-                HIPCHK(c, hipHostMalloc((void**)&c->h_rad_p, (size_t)R * K * N * 4));
-                HIPCHK(c, hipHostGetDevicePointer((void**)&c->hd_rad, c->h_rad_p, 0));
-            }
-            HIPCHK(c, hipMemcpyAsync(c->d_joff, c->h_joff.data(), ((size_t)R + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    // A kept graph stays lazy too when its reverse pass reads no node but the adopted ones (rows form, S <= 4096: pg_nodes_free
-    // recomputes a node's row from its children; everything else that is read was somebody's child, i.e. adopted).
-    const bool lazy_ok = !twist && (!graph || S <= 4096) && !(flags & PHYLO_EAGER_NODES) && !c->env.eager_nodes;
-    // marks are plain stores and the extra launch costs less than the dead stores it removes at every size measured.
-    // Sharded, the owner's write needs one more (tiny) collective per rank event (sweep_step_a); rehearsed with a
-    // one-rank RCCL world (PHYLO_REHEARSE_SHARDED=1) the lazy sweep is 0.145 ms against 0.185 ms for the eager one at
-    // primate.p's node size, more than a second collective costs
-    const bool lazy = lazy_ok;
-    int launches = 0;
-    c->swept = false; ++c->sweep_serial;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    // one sweep alone on one GPU with lazy nodes: the adopted nodes are written in the bookkeeping launch (pk_rank_book_mat), found
-    // by the resampling draws, which pk_sweep_prologue then leaves in d_rdraw.  Batched sweeps keep the separate launch (measured:
-    // 2.62e11 against 2.64e11 units/s with the grouped form of the combined launch in round 2; round 3, a launch set alone: 3.57e11 against 3.77e11).
-    const bool book_mat = lazy && c->world == 1 && c->comm.transport == 0 && N <= 64 && S <= 4096 && G == 1 && Kl <= 8192;
-    // sharded with lazy nodes: each owner finds ITS adopted nodes the same way (O(Kloc Kg / 64) comparisons) instead of every rank
-    // searching the ancestors of all K particles (pk_all_marks, O(K) on every rank whatever the number of GPUs)
-    const bool shard_form = c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded);
-    // a sharded sweep that keeps its graph advances all K root tables on every rank: the history planes it writes are then whole
-    // everywhere (the owner-held tables that peers read are the two planes of d_tables, not the history)
-    const bool replicated_book = c->env.replicated_book || (graph && c->world > 1);
-    const bool mat_by_draws = lazy && shard_form && !twist && !replicated_book && S <= 4096 &&
-                              (((K / G) <= 4096 && Kl <= 8192) || ((K / G) % PK_MAT_GROUP == 0 && Kl % PK_MAT_GROUP == 0));
-    const bool want_rdraw = book_mat || mat_by_draws;
-    if (want_rdraw && !c->d_rdraw) CHK(dalloc(c, &c->d_rdraw, (size_t)R * K));
-    const size_t mark_words = ((size_t)R * K + R + 3) & ~(size_t)3;
-    int32_t* t_roots = graph ? c->d_hroots : c->d_roots[0];
-    int32_t* t_cnt = graph ? c->d_hcnt : c->d_cnt[0];
-    double* t_rootll = graph ? c->d_hrootll : c->d_rootll[0];
-    if (!twist) {                                          // draws, initial tables and cleared marks: one launch
-        if (G > 1) HIPCHK(c, hipMemcpyAsync(c->d_group_seeds, group_seeds, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
-        pk_prologue_args pa{};
-        pa.Q = c->d_Q; pa.lam_l = c->d_lam_l; pa.lam_r = c->d_lam_r; pa.jc = c->jc; pa.seed = seed; pa.R = R; pa.Kloc = Kl; pa.k0 = c->k0;
-        pa.bl = c->d_bl; pa.br = c->d_br; pa.Pmat = c->d_Pmat; pa.Kg = K / G;
-        pa.group_seeds = G > 1 ? (const uint64_t*)c->d_group_seeds : (const uint64_t*)nullptr;
-        pa.rdraw = want_rdraw ? c->d_rdraw : (unsigned long long*)nullptr;
-        pa.roots = t_roots; pa.cnt = t_cnt; pa.rootll = t_rootll; pa.nodell = c->d_nodell; pa.K = K; pa.N = N;
-        pa.mark = lazy ? c->d_mark : (unsigned int*)nullptr;
-        pa.mark_words = lazy ? (unsigned int)mark_words : 0u;
-        // large launches (batched sweeps): the matrices sorted by Pade order inside workgroups of 1024 (pk_sweep_draws_sorted)
-        const bool sorted = !c->jc && 2L * R * Kl >= 262144;
-        const int NT = sorted ? 256 : 64;
-        pa.draw_blocks = sorted ? cdiv(2L * R * Kl, PK_DRAW_ITEMS) : cdiv(2L * R * Kl, 64);
-        pa.init_blocks = cdiv((long)K * N, 4 * NT);
-        pa.mark_blocks = lazy ? cdiv((long)mark_words, 4 * NT) : 0;
-        const int rdraw_blocks = want_rdraw ? cdiv((long)(R - 1) * K, NT) : 0;
-        const dim3 pgrid(pa.draw_blocks + pa.init_blocks + pa.mark_blocks + rdraw_blocks);
-        if (sorted) hipLaunchKernelGGL(pk_sweep_prologue_sorted, pgrid, dim3(256), 0, c->stream, pa);
-        else hipLaunchKernelGGL(pk_sweep_prologue, pgrid, dim3(64), 0, c->stream, pa);
-        CHK(launch_check(c, "pk_sweep_prologue"));
-        launches += 1;
-    } else {
-        if (lazy) HIPCHK(c, hipMemsetAsync(c->d_mark, 0, mark_words * sizeof(unsigned int), c->stream));
-        hipLaunchKernelGGL(pk_init_tables, dim3(cdiv((long)K * N, 256)), dim3(256), 0, c->stream, t_roots, t_cnt, t_rootll,
-                           (const double*)c->d_nodell, K, N);
-        launches += 1;
-    }
-    CHK(launch_check(c, "pk_init_tables"));
-    if (c->d_mirror) HIPCHK(c, hipMemsetAsync(c->d_mirror, 0, ((size_t)R * K + 4) * 4, c->stream));   // the cache of remote nodes is per sweep
-    c->run = sweep_run{};
-    c->run.seed = seed; c->run.flags = flags; c->run.M = M;
-    c->run.twist = twist; c->run.graph = graph; c->run.lazy = lazy; c->run.timek = timek;
-    c->run.book_mat = book_mat;
-    c->run.mat_by_draws = mat_by_draws;
-    c->run.replicated_book = replicated_book;
-    c->run.launches = launches; c->run.next_r = 0; c->run.active = true;
-    c->run.G = G;
     return PHYLO_OK;
 }
 
+// ... and what every finished sweep leaves for the calls that follow it
+static void sweep_publish(phylo_ctx* c, bool lazy, bool graph, int G, bool final_missing, int merge_events, int launches, double units) {
+    c->swept = true;
+    c->last_lazy = lazy;                                   // only adopted nodes are in the pool (marks say which)
+    c->last_graph = graph;
+    c->last_G = G;
+    c->last_final_missing = final_missing;
+    c->n_merge_events = merge_events;
+    c->stats.n_launches = launches;
+    c->stats.units = units;
+    c->stats.alg_bytes = 96.0 * units;
+}
+
+// The twisted proposal's buffers (allocated on first use, grow-only) and the code-pair histogram of coded leaves
+static int sweep_alloc_twist(phylo_ctx* c, int M) {
+    const int N = c->N, K = c->K, Kl = c->Kloc;
+    const size_t Jmax = (size_t)(N * (N - 1) / 2) * M;
+    if (Jmax > PK_TWIST_LDS_J && c->twbuf_cap < (size_t)Kl * Jmax) {     // weights of more sub-samples than LDS holds
+        if (c->d_twbuf) (void)hipFree(c->d_twbuf);
+        c->d_twbuf = nullptr;
+        c->twbuf_cap = 0;
+        CHK(dalloc(c, &c->d_twbuf, (size_t)Kl * Jmax));
+        c->twbuf_cap = (size_t)Kl * Jmax;
+    }
+    if (!c->d_roots_ad) {
+        CHK(dalloc(c, &c->d_roots_ad, (size_t)K * N));
+        CHK(dalloc(c, &c->d_cnt_ad, (size_t)K * N));
+        CHK(dalloc(c, &c->d_rootll_ad, (size_t)K * N));
+        if (!c->p2p) CHK(dalloc(c, &c->d_chosen, (size_t)K));
+    }
+    if (c->tw_capacity < (size_t)Kl * Jmax) {
+        if (c->d_tw_b) { (void)hipFree(c->d_tw_b); (void)hipFree(c->d_tw_P); (void)hipFree(c->d_pot); }
+        c->d_tw_b = c->d_tw_P = c->d_pot = nullptr;
+        c->tw_capacity = 0;
+        CHK(dalloc(c, &c->d_tw_b, (size_t)Kl * Jmax * 2));
+        CHK(dalloc(c, &c->d_tw_P, (size_t)Kl * Jmax * 32));
+        CHK(dalloc(c, &c->d_pot, (size_t)Kl * Jmax));
+        c->tw_capacity = (size_t)Kl * Jmax;
+    }
+    if (c->codes_valid && !c->hist_ready) {
+        if (!c->d_pair_hist) CHK(dalloc(c, &c->d_pair_hist, (size_t)N * N * 32));
+        hipLaunchKernelGGL(pk_pair_hist, dim3(N, N), dim3(256), 0, c->stream, (const uint8_t*)c->d_leaf_codes, N, c->S, c->d_pair_hist);
+        CHK(launch_check(c, "pk_pair_hist"));
+        c->hist_ready = true;
+    }
+    return PHYLO_OK;
+}
+
+// The twisted proposal with a kept graph: every rank event keeps its sub-samples, rows [r][k][J_r]
+static int sweep_alloc_twist_history(phylo_ctx* c, int M) {
+    const int N = c->N, K = c->K, R = N - 1;
+    c->h_joff.assign((size_t)R + 1, 0);
+    for (int r = 0; r < R; ++r) c->h_joff[r + 1] = c->h_joff[r] + (int64_t)K * (((N - r) * (N - r - 1)) / 2) * M;
+    const size_t rows = (size_t)c->h_joff[R];
+    if (c->htw_rows < rows) {
+        void* old[] = {c->d_htw_b, c->d_htw_P, c->d_hpot, c->d_tau, c->d_twpart};
+        for (void* p : old)
+            if (p) (void)hipFree(p);
+        c->d_htw_b = c->d_htw_P = c->d_hpot = c->d_tau = c->d_twpart = nullptr;
+        c->htw_rows = 0;
+        CHK(dalloc(c, &c->d_htw_b, rows * 2));
+        CHK(dalloc(c, &c->d_htw_P, rows * 32));
+        CHK(dalloc(c, &c->d_hpot, rows));
+        CHK(dalloc(c, &c->d_tau, rows));
+        CHK(dalloc(c, &c->d_twpart, rows * PG_PART));
+        c->htw_rows = rows;
+    }
+    if (!c->d_hroots_ad) {
+        CHK(dalloc(c, &c->d_hroots_ad, (size_t)R * K * N));
+        CHK(dalloc(c, &c->d_hchosen, (size_t)R * K));
+        CHK(dalloc(c, &c->d_ctw, (size_t)R * K * N));
+        CHK(dalloc(c, &c->d_twnode, (size_t)R * K * PG_NODEG));
+        CHK(dalloc(c, &c->d_joff, (size_t)R + 1));
+        HIPCHK(c, hipHostMalloc((void**)&c->h_rad_p, (size_t)R * K * N * 4));
+        HIPCHK(c, hipHostGetDevicePointer((void**)&c->hd_rad, c->h_rad_p, 0));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_joff, c->h_joff.data(), ((size_t)R + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    return PHYLO_OK;
+}
+
+// First-use and grow-only allocations of the form `p`
+static int sweep_alloc(phylo_ctx* c, const sweep_plan& p, int M) {
+    if (p.twist) CHK(sweep_alloc_twist(c, M));
+    while (p.timek && (int)c->kev.size() < 2 * p.R) {
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreate(&e));
+        c->kev.push_back(e);
+    }
+    if (p.graph) {
+        CHK(ensure_graph_state(c));
+        if (p.twist) CHK(sweep_alloc_twist_history(c, M));
+    }
+    if (p.want_rdraw && !c->d_rdraw) CHK(dalloc(c, &c->d_rdraw, (size_t)p.R * c->K));
+    return PHYLO_OK;
+}
+
+// Draws, initial tables and cleared marks: one launch (the twisted proposal draws per rank event: its tables alone)
+static int sweep_prologue(phylo_ctx* c, const sweep_plan& p, uint64_t seed, const uint64_t* group_seeds) {
+    const int N = c->N, K = c->K, Kl = c->Kloc, R = p.R, G = p.G;
+    const size_t mark_words = ((size_t)R * K + R + 3) & ~(size_t)3;
+    int32_t* t_roots = p.graph ? c->d_hroots : c->d_roots[0];
+    int32_t* t_cnt = p.graph ? c->d_hcnt : c->d_cnt[0];
+    double* t_rootll = p.graph ? c->d_hrootll : c->d_rootll[0];
+    if (!p.twist) {
+        if (G > 1) HIPCHK(c, hipMemcpyAsync(c->d_group_seeds, group_seeds, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+        pk_prologue_args pa{};
+        pa.Q = c->d_Q; pa.lam_l = c->d_lam_l; pa.lam_r = c->d_lam_r; pa.jc = c->jc; pa.seed = seed; pa.R = R; pa.Kloc = Kl; pa.k0 = c->k0;
+        pa.bl = c->d_bl; pa.br = c->d_br; pa.Pmat = c->d_Pmat; pa.Kg = p.Kg;
+        pa.group_seeds = G > 1 ? (const uint64_t*)c->d_group_seeds : (const uint64_t*)nullptr;
+        pa.rdraw = p.want_rdraw ? c->d_rdraw : (unsigned long long*)nullptr;
+        pa.roots = t_roots; pa.cnt = t_cnt; pa.rootll = t_rootll; pa.nodell = c->d_nodell; pa.K = K; pa.N = N;
+        pa.mark = p.lazy ? c->d_mark : (unsigned int*)nullptr;
+        pa.mark_words = p.lazy ? (unsigned int)mark_words : 0u;
+        const int NT = p.sorted_prologue ? 256 : 64;
+        pa.draw_blocks = p.sorted_prologue ? cdiv(2L * R * Kl, PK_DRAW_ITEMS) : cdiv(2L * R * Kl, 64);
+        pa.init_blocks = cdiv((long)K * N, 4 * NT);
+        pa.mark_blocks = p.lazy ? cdiv((long)mark_words, 4 * NT) : 0;
+        const int rdraw_blocks = p.want_rdraw ? cdiv((long)(R - 1) * K, NT) : 0;
+        const dim3 pgrid(pa.draw_blocks + pa.init_blocks + pa.mark_blocks + rdraw_blocks);
+        if (p.sorted_prologue) hipLaunchKernelGGL(pk_sweep_prologue_sorted, pgrid, dim3(256), 0, c->stream, pa);
+        else hipLaunchKernelGGL(pk_sweep_prologue, pgrid, dim3(64), 0, c->stream, pa);
+        CHK(launch_check(c, "pk_sweep_prologue"));
+    } else {
+        if (p.lazy) HIPCHK(c, hipMemsetAsync(c->d_mark, 0, mark_words * sizeof(unsigned int), c->stream));
+        hipLaunchKernelGGL(pk_init_tables, dim3(cdiv((long)K * N, 256)), dim3(256), 0, c->stream, t_roots, t_cnt, t_rootll,
+                           (const double*)c->d_nodell, K, N);
+    }
+    CHK(launch_check(c, "pk_init_tables"));
+    if (c->d_mirror) HIPCHK(c, hipMemsetAsync(c->d_mirror, 0, ((size_t)R * K + 4) * 4, c->stream));   // the cache of remote nodes is per sweep
+    return PHYLO_OK;
+}
+
+// validate (the batch, then -- behind the leaves / model check, as ever -- the proposal and the graph), plan, allocate, prologue,
+// store the run
+static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, const uint64_t* group_seeds, int G) {
+    CHK(sweep_bind(c));
+    const sweep_facts f = sweep_facts_of(c, flags, M, G);
+    char why[160];
+    if (sweep_refuses_batch(f, k_sweep_limits, why, sizeof why)) return fail(c, PHYLO_EINVAL, "%s", why);
+    CHK(sweep_ready(c));
+    if (sweep_refuses_form(f, k_sweep_limits, why, sizeof why)) return fail(c, PHYLO_EINVAL, "%s", why);
+    const sweep_plan p = sweep_plan_form(f, k_sweep_limits);
+    CHK(sweep_alloc(c, p, M));
+    c->swept = false; ++c->sweep_serial;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    CHK(sweep_prologue(c, p, seed, group_seeds));
+    c->run = sweep_run{};
+    c->run.seed = seed; c->run.flags = flags; c->run.M = M;
+    c->run.plan = p;
+    c->run.launches = sweep_plan_launches(p, -1);
+    c->run.active = true;
+    return PHYLO_OK;
+}
 
 // ---- the sweep as ONE launch (phylo_persist.h) ------------------------------------------------------------------
 // Resident-workgroup kernels of different contexts must not be dispatched together: each waits inside the launch for ALL of
@@ -1356,8 +1390,8 @@ static int persist_chain(phylo_ctx* c, bool after_launch) {
 static bool persist_plan(phylo_ctx* c, uint32_t flags, int G, int* Wg_out, int* m_out) {
     if (!(c->env.one_launch || (flags & PHYLO_ONE_LAUNCH))) return false;             // opt-in
     if (c->world != 1 || c->comm.transport != 0) return false;                       // sharded: collectives between launches
-    if (flags & (PHYLO_TWISTING | PHYLO_KEEP_GRAPH | PHYLO_EAGER_NODES | PHYLO_TIME_KERNELS)) return false;   // launch path only
-    if (c->env.eager_nodes) return false;                                           // A/B switch of the launch path
+    if (flags & (PHYLO_TWISTING | PHYLO_KEEP_GRAPH | PHYLO_TIME_KERNELS)) return false;   // launch path only
+    if (sweep_eager_nodes((flags & PHYLO_EAGER_NODES) != 0, c->env.eager_nodes)) return false;   // ... and its A/B switch
     if (c->N > 32 || c->N < 2) return false;                                        // one wave per particle: a lane per root slot, history rows in lanes
     const int Kg = c->K / G;
     if (Kg > PP_MAX_KG) return false;                                               // the group's cdf lives in LDS
@@ -1388,14 +1422,8 @@ static bool persist_plan(phylo_ctx* c, uint32_t flags, int G, int* Wg_out, int* 
 }
 
 static int sweep_persistent(phylo_ctx* c, uint64_t seed, uint32_t flags, const uint64_t* group_seeds, int G, int Wg, int m) {
-    CHK(bind(c));
-    c->run.active = false;
-    if (!c->have_leaves || !c->have_model)
-        return fail(c, PHYLO_ESTATE, "phylo_set_leaves and phylo_set_model must be called before a sweep");
-    if (!c->state_ready) {
-        CHK(ensure_sweep_state(c));
-        CHK(refresh_leaf_ll(c));
-    }
+    CHK(sweep_bind(c));
+    CHK(sweep_ready(c));
     const int N = c->N, K = c->K, S = c->S, R = N - 1, Kg = K / G;
     if (!c->d_rdraw) CHK(dalloc(c, &c->d_rdraw, (size_t)R * K));       // (the launch path's pk_rank_book_mat shares this buffer)
     if (!c->d_pctr) {
@@ -1442,16 +1470,8 @@ static int sweep_persistent(phylo_ctx* c, uint64_t seed, uint32_t flags, const u
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     CHK(persist_chain(c, true));
     c->pctr_base += (unsigned long long)R * Wg;
-    c->swept = true;
-    c->last_lazy = true;                                   // only adopted nodes are in the pool (marks say which)
-    c->last_graph = false;
-    c->last_G = G;
-    c->last_final_missing = false;
+    sweep_publish(c, true, false, G, false, 0, 1, (double)K * S * R);      // lazy: only adopted nodes are in the pool
     c->last_persistent = true;
-    c->n_merge_events = 0;
-    c->stats.n_launches = 1;
-    c->stats.units = (double)K * S * R;
-    c->stats.alg_bytes = 96.0 * c->stats.units;
     return PHYLO_OK;
 }
 
@@ -1493,44 +1513,224 @@ static int comm_exchange(phylo_ctx* c, double* const* arrays, int n_arrays, size
     return launch_check(c, "pk_p2p_exchange");
 }
 
-// Sharded lazy nodes, first half of a rank event: every rank marks the nodes adopted at this resampling (the search
-// of all K particles, no tables), the owner writes its marked nodes, and one tiny collective orders those writes before
-// every rank's merge.  A no-op otherwise.  phylo_sweep_step runs it when the caller has not (phylo_sweep_step_a).
+// The kernel arguments of rank event r, for sweep_step_a's launches and for the stages of the step alike.  (What only the step's kernels read -- tables, weights, records, tiles -- the kernels of
+// sweep_step_a never touch: pk_all_marks reads K, Kg, group_seeds, seed, r, cdf and mark; pk_materialize_adopted(_grouped) and
+// pk_materialize_by_draws read those, rdraw, k0, Kloc, N, S, child_all, Pmat_all, leaves, pool, pool_ptrs, mirror and cache.
+// rdraw is read by pk_materialize_by_draws and pk_rank_book_mat alone, tab_ptrs by the bookkeeping kernels alone.)
+static pk_rank_args rank_args(const phylo_ctx* c, int r) {
+    const sweep_plan& p = c->run.plan;
+    const int N = c->N, K = c->K, Kl = c->Kloc, cur = r & 1, nxt = cur ^ 1;
+    const size_t plane = (size_t)K * N;
+    pk_rank_args b{};
+    b.r = r; b.n = N - r; b.N = N; b.S = c->S; b.K = K; b.Kloc = Kl; b.k0 = c->k0;
+    b.seed = c->run.seed; b.flags = c->run.flags;
+    b.Kg = p.Kg; b.group_seeds = p.G > 1 ? c->d_group_seeds : nullptr;
+    b.no_store = (r == p.R - 1 && p.no_store_last) ? 1 : 0;
+    if (p.graph) {                                         // every rank event keeps its tables: plane r -> plane r + 1
+        b.roots_old = c->d_hroots + plane * r; b.cnt_old = c->d_hcnt + plane * r;
+        b.roots_new = c->d_hroots + plane * (r + 1); b.cnt_new = c->d_hcnt + plane * (r + 1);
+        b.rootll_old = c->d_hrootll + plane * r; b.rootll_new = c->d_hrootll + plane * (r + 1);
+        b.pos_hist = c->d_pos + plane * r;
+    } else {
+        b.roots_old = c->d_roots[cur]; b.cnt_old = c->d_cnt[cur];
+        b.roots_new = c->d_roots[nxt]; b.cnt_new = c->d_cnt[nxt];
+        b.rootll_old = c->d_rootll[cur]; b.rootll_new = c->d_rootll[nxt];
+    }
+    if (p.local_book) {                                    // an ancestor's rows of the previous plane, inside its owner's slab
+        b.tab_ptrs = c->d_tab_ptrs;
+        b.tab_off_rootll = (size_t)cur * K * N * 8;
+        b.tab_off_roots = (size_t)16 * K * N + (size_t)cur * K * N * 4;
+        b.tab_off_cnt = (size_t)24 * K * N + (size_t)cur * K * N * 4;
+    }
+    b.cdf = c->d_cdf[cur];
+    b.rdraw = p.want_rdraw ? c->d_rdraw + (size_t)r * K : nullptr;
+    b.ll_prev = r > 0 ? c->d_ll + (size_t)(r - 1) * K : nullptr;
+    b.nodell = c->d_nodell;
+    b.ldf = c->d_ldf; b.ldf_n = N;
+    b.bl = c->d_bl; b.br = c->d_br;
+    b.lam_l = c->h_lam_l[r]; b.lam_r = c->h_lam_r[r];
+    b.loglam_l = pm_log(b.lam_l); b.loglam_r = pm_log(b.lam_r);
+    b.ll_tilde0 = pm_log(1.0 / (double)p.Kg);              // vcsmc.py:422
+    b.leaves = c->d_leaves; b.pool = c->d_pool; b.pool_ptrs = c->d_pool_ptrs;
+    // the cache of remote nodes is filled by the bookkeeping launch, which must come behind the owners' writes of this rank
+    // event's adopted nodes: not so with replicated bookkeeping (and the twisted proposal reads its roots elsewhere)
+    b.mirror = (p.twist || p.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
+    b.leaf_codes = c->leaves_coded ? c->d_leaf_codes : nullptr;
+    b.Pmat = c->d_Pmat + (size_t)r * Kl * 32;
+    b.pi = c->d_pi;
+    b.logw_r = c->d_logw + (size_t)r * K;
+    b.ll_r = c->d_ll + (size_t)r * K;
+    b.merges = c->d_merges; b.ancestors = c->d_anc;
+    b.child = c->d_child + (size_t)r * Kl * 2; b.aux = c->d_aux;
+    b.rec = p.use_rec ? c->d_rec : nullptr;
+    b.lazy = p.lazy ? 1 : 0; b.mark = c->d_mark; b.child_all = c->d_child; b.Pmat_all = c->d_Pmat;
+    b.T = c->site_tile; b.ntiles = c->ntiles; b.tilev = c->d_tilev;
+    return b;
+}
+
+// The adopted nodes of rank event r - 1, in a launch of their own, and the barrier that orders them before every rank's merge.
+// Once per rank event r > 0: from sweep_step_a with owner-held tables (plan.step_a_work: the owners find their nodes by the draws,
+// or every rank marks the adopted nodes of all K particles first), else from the step behind its bookkeeping (plan.mat_after_book).
+static int step_materialize(phylo_ctx* c, const pk_rank_args& b) {
+    const sweep_plan& p = c->run.plan;
+    const int Kl = c->Kloc, S = c->S;
+    if (p.mat_by_draws) {
+        const int grouped = p.mat_draws_grouped ? 1 : 0;
+        hipLaunchKernelGGL(pk_materialize_by_draws, dim3(grouped ? Kl / PK_MAT_GROUP : Kl), dim3(PK_COLS), 0, c->stream, b, grouped);
+        CHK(launch_check(c, "pk_materialize_by_draws"));
+    } else {
+        if (p.step_a_work) {
+            hipLaunchKernelGGL(pk_all_marks, dim3(cdiv(c->K, 4)), dim3(64), 0, c->stream, b);
+            CHK(launch_check(c, "pk_all_marks"));
+        }
+        if (p.mat_grouped) hipLaunchKernelGGL(pk_materialize_adopted_grouped, dim3(cdiv(Kl, PK_MAT_GROUP)), dim3(PK_COLS), 0, c->stream, b);
+        else hipLaunchKernelGGL(pk_materialize_adopted, dim3(p.one_tile ? 1 : cdiv(S, PK_MAT_TILE), Kl), dim3(PK_COLS), 0, c->stream, b);
+        CHK(launch_check(c, "pk_materialize_adopted"));
+    }
+    if (p.mat_barrier) CHK(comm_exchange(c, nullptr, 0, 0, 1));
+    return PHYLO_OK;
+}
+
+// Sharded lazy nodes, first half of a rank event: the owners write the nodes adopted at this resampling, and one tiny collective
+// orders those writes before every rank's merge (step_materialize).  A no-op otherwise.  phylo_sweep_step runs it when the caller
+// has not (phylo_sweep_step_a).
 static int sweep_step_a(phylo_ctx* c) {
     CHK(bind(c));
     if (!c->run.active) return fail(c, PHYLO_ESTATE, "phylo_sweep_step without phylo_sweep_begin");
-    const int N = c->N, K = c->K, Kl = c->Kloc, S = c->S, R = N - 1, r = c->run.next_r;
+    const int R = c->N - 1, r = c->run.next_r;
     if (r >= R) return fail(c, PHYLO_ESTATE, "all %d rank events of this sweep have been issued", R);
     c->run.a_done_r = r;
-    const bool shard_form = c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded);   // the env: one-rank rehearsal
-    if (!(shard_form && c->run.lazy && !c->run.twist && !c->run.replicated_book) || r == 0) return PHYLO_OK;
-    const int G = c->run.G;
-    pk_rank_args b{};
-    b.r = r; b.n = N - r; b.N = N; b.S = S; b.K = K; b.Kloc = Kl; b.k0 = c->k0;
-    b.seed = c->run.seed; b.flags = c->run.flags;
-    b.cdf = c->d_cdf[r & 1];
-    b.Kg = K / G; b.group_seeds = G > 1 ? c->d_group_seeds : nullptr;
-    b.leaves = c->d_leaves; b.pool = c->d_pool; b.pool_ptrs = c->d_pool_ptrs;
-    b.mirror = (c->run.twist || c->run.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
-    b.leaf_codes = c->leaves_coded ? c->d_leaf_codes : nullptr;
-    b.lazy = 1; b.mark = c->d_mark; b.child_all = c->d_child; b.Pmat_all = c->d_Pmat;
-    if (c->run.mat_by_draws) {
-        b.rdraw = c->d_rdraw + (size_t)r * K;
-        const int grouped = ((K / G) > 4096 || Kl > 8192) ? 1 : 0;     // one workgroup per 64 particles when there are many
-        hipLaunchKernelGGL(pk_materialize_by_draws, dim3(grouped ? Kl / PK_MAT_GROUP : Kl), dim3(PK_COLS), 0, c->stream, b, grouped);
-        CHK(launch_check(c, "pk_materialize_by_draws"));
-        c->run.launches += 1;
-    } else {
-        hipLaunchKernelGGL(pk_all_marks, dim3(cdiv(K, 4)), dim3(64), 0, c->stream, b);
-        CHK(launch_check(c, "pk_all_marks"));
-        // large launches of small nodes (batched sweeps): dispatching one workgroup per particle costs more than the few writes
-        if (S <= 4096 && Kl > 8192) hipLaunchKernelGGL(pk_materialize_adopted_grouped, dim3(cdiv(Kl, PK_MAT_GROUP)), dim3(PK_COLS), 0, c->stream, b);
-        else hipLaunchKernelGGL(pk_materialize_adopted, dim3(S <= 4096 ? 1 : cdiv(S, PK_MAT_TILE), Kl), dim3(PK_COLS), 0, c->stream, b);
-        CHK(launch_check(c, "pk_materialize_adopted"));
-        c->run.launches += 2;
+    if (!c->run.plan.step_a_work || r == 0) return PHYLO_OK;
+    return step_materialize(c, rank_args(c, r));
+}
+
+// The twisted proposal of a rank event: adopt + draws, potentials, choose, the exchange of the choices, tables
+static int step_twist(phylo_ctx* c, const pk_rank_args& b) {
+    const sweep_plan& p = c->run.plan;
+    const int N = c->N, K = c->K, Kl = c->Kloc, r = b.r;
+    pk_twist_args ta{};
+    ta.a = b;
+    ta.M = c->run.M;
+    ta.J = ((N - r) * (N - r - 1) / 2) * ta.M;
+    ta.roots_ad = c->d_roots_ad; ta.cnt_ad = c->d_cnt_ad; ta.rootll_ad = c->d_rootll_ad;
+    ta.tw_b = c->d_tw_b; ta.tw_P = c->d_tw_P; ta.pot = c->d_pot; ta.chosen = c->d_chosen;
+    if (p.graph) {                                         // the reverse pass reads every rank event's sub-samples
+        const size_t j0 = (size_t)c->h_joff[r];
+        ta.tw_b = c->d_htw_b + j0 * 2; ta.tw_P = c->d_htw_P + j0 * 32; ta.pot = c->d_hpot + j0;
+        ta.roots_ad = c->d_hroots_ad + (size_t)K * N * r; ta.chosen = c->d_hchosen + (size_t)r * K;
     }
-    CHK(comm_exchange(c, nullptr, 0, 0, 1));               // barrier: the owners' writes before every rank's merge
+    ta.Pmat_r = c->d_Pmat + (size_t)r * Kl * 32;
+    ta.pair_hist = p.twist_ll ? c->d_pair_hist : nullptr;
+    ta.codes = p.twist_ll ? c->d_leaf_codes : nullptr;
+    ta.bl_r = c->d_bl + (size_t)r * Kl; ta.br_r = c->d_br + (size_t)r * Kl;
+    ta.own_tables = p.twist_tables ? 0 : 1;
+    ta.wbuf = c->d_twbuf;
+    hipLaunchKernelGGL(pk_twist_adopt_draws, dim3(K + cdiv(2L * Kl * ta.J, 64)), dim3(64), 0, c->stream, ta, (const double*)c->d_Q, c->jc);
+    CHK(launch_check(c, "pk_twist_adopt_draws"));
+    if (p.twist_ll) {                                      // coded leaf-leaf pairs: 25 code pairs per row instead of S sites
+        hipLaunchKernelGGL(pk_twist_potentials_ll, dim3((ta.J + 7) / 8, Kl), dim3(256), 0, c->stream, ta);
+        CHK(launch_check(c, "pk_twist_potentials_ll"));
+    }
+    // every other row: one wave each (at rank event 0 of a coded alignment every root is a leaf: nothing is left)
+    const bool any_rows = !(p.twist_ll && r == 0);
+    const dim3 pgrid((unsigned)((((size_t)Kl * ta.J + 7) / 8) * 8));
+    if (p.timek) {   // a twisted sweep's dominant kernel is this one: PHYLO_TIME_KERNELS stamps it instead of the merge
+        if (any_rows) hipExtLaunchKernelGGL(pk_twist_potentials, pgrid, dim3(64), 0, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, ta);
+        else { HIPCHK(c, hipEventRecord(c->kev[2 * r], c->stream)); HIPCHK(c, hipEventRecord(c->kev[2 * r + 1], c->stream)); }
+    } else if (any_rows) {
+        hipLaunchKernelGGL(pk_twist_potentials, pgrid, dim3(64), 0, c->stream, ta);
+    }
+    CHK(launch_check(c, "pk_twist_potentials"));
+    hipLaunchKernelGGL(pk_twist_choose, dim3(Kl), dim3(64), (size_t)(ta.J <= PK_TWIST_LDS_J ? ta.J : 0) * 8, c->stream, ta);
+    CHK(launch_check(c, "pk_twist_choose"));
+    if (p.twist_tables) {
+        double* rows[1] = {c->d_chosen};
+        CHK(comm_exchange(c, rows, 1, (size_t)Kl, 1));
+        hipLaunchKernelGGL(pk_twist_tables, dim3(cdiv(K, 128)), dim3(128), 0, c->stream, ta);
+        CHK(launch_check(c, "pk_twist_tables"));
+    }
     return PHYLO_OK;
+}
+
+// The bookkeeping of a rank event at plan.book_width lanes per particle: with the adopted nodes in the same launch
+// (pk_rank_book_mat, r > 0), else over the root tables this rank advances (pk_rank_book_packed, or pk_rank_book's wave per particle)
+static int step_book(phylo_ctx* c, const pk_rank_args& b) {
+    const sweep_plan& p = c->run.plan;
+    const int K = c->K, w = p.book_width;
+    const size_t lds = pk_book_lds_bytes(c->N);
+    if (p.book_mat && b.r > 0) {
+        const int lp = w < 16 ? 16 : w, per = PK_COLS / lp;   // particles per workgroup; behind them, a workgroup per particle's node
+        const int bb = cdiv(K, per);
+        const dim3 grid(bb + K);
+        if (lp == 16) hipLaunchKernelGGL(pk_rank_book_mat<16>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb);
+        else if (lp == 32) hipLaunchKernelGGL(pk_rank_book_mat<32>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb);
+        else hipLaunchKernelGGL(pk_rank_book_mat<64>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb);
+        return launch_check(c, "pk_rank_book_mat");
+    }
+    const int nbook = p.local_book ? c->Kloc : K;
+    const int per = (w == 8 || w == 16 || w == 32) ? 64 / w : 1;                 // particles per wave
+    const dim3 grid(cdiv(nbook, per));
+    if (w == 8) hipLaunchKernelGGL(pk_rank_book_packed<8>, grid, dim3(64), lds * per, c->stream, b);
+    else if (w == 16) hipLaunchKernelGGL(pk_rank_book_packed<16>, grid, dim3(64), lds * per, c->stream, b);
+    else if (w == 32) hipLaunchKernelGGL(pk_rank_book_packed<32>, grid, dim3(64), lds * per, c->stream, b);
+    else hipLaunchKernelGGL(pk_rank_book, grid, dim3(64), lds * per, c->stream, b);
+    return launch_check(c, "pk_rank_book");
+}
+
+// The merge of a rank event: one wave per (particle, site tile) when nothing is stored -- from the merge records, or resolving
+// ids -- and pk_rank_merge only when the node is stored
+static int step_merge(phylo_ctx* c, const pk_rank_args& b) {
+    const sweep_plan& p = c->run.plan;
+    const int S = c->S;
+    const dim3 mgrid((unsigned)((size_t)c->Kloc * c->ntiles));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (p.timek && !p.twist) { e0 = c->kev[2 * b.r]; e1 = c->kev[2 * b.r + 1]; }
+    if (!(b.lazy || b.no_store)) {
+        const size_t lds = (size_t)(c->site_tile < S ? c->site_tile : S) * 8 + 16 + PK_STORE_STAGE_BYTES;
+        launch_stamped(pk_rank_merge, mgrid, dim3(PK_COLS), lds, c->stream, e0, e1, b);
+    } else if (b.rec) {
+        // pi by value, from the pinned image of the model upload.  Invariant: phylo_set_model is the only writer of d_Q / d_pi and
+        // of that image, and it rewrites the image only after the previous upload has finished, so for every launch issued after
+        // it returns the image equals the model the other kernels read from d_pi.  A model update made on the device would have
+        // to refresh the image too.
+        pk_pi4 pi4;
+        memcpy(pi4.v, c->h_model_p + 16, sizeof pi4.v);
+        launch_stamped(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, e0, e1, (const unsigned long long*)b.rec, b.Pmat, S, b.T,
+                       b.ntiles, b.tilev, pi4);
+    } else {
+        launch_stamped(pk_rank_merge_nostore_ids, mgrid, dim3(64), 0, c->stream, e0, e1, b);
+    }
+    return launch_check(c, "pk_rank_merge");
+}
+
+// rows longer than one tile: tile values left to right, then the particle's weight terms
+static int step_tiles(phylo_ctx* c, const pk_rank_args& b) {
+    hipLaunchKernelGGL(pk_tile_epilogue, dim3(cdiv(c->Kloc, 256)), dim3(256), 0, c->stream, b);
+    return launch_check(c, "pk_tile_epilogue");
+}
+
+// the all-gather of the rank event's three K-vectors (nothing without a communicator)
+static int step_exchange(phylo_ctx* c, int r) {
+    const size_t K = c->K;
+    double* rows[3] = {c->d_logw + r * K, c->d_ll + r * K, c->d_nodell + c->N + r * K};
+    return comm_exchange(c, rows, 3, (size_t)c->Kloc, 0);
+}
+
+// replicated tables: the new roots' log-likelihoods of the other ranks' particles, known since the exchange
+static int step_fix_rootll(phylo_ctx* c, int r) {
+    const int N = c->N, K = c->K;
+    double* rootll_new = c->run.plan.graph ? c->d_hrootll + (size_t)K * N * (r + 1) : c->d_rootll[(r & 1) ^ 1];
+    hipLaunchKernelGGL(pk_fix_rootll, dim3(cdiv(K, 256)), dim3(256), 0, c->stream, rootll_new,
+                       (const double*)(c->d_nodell + N + (size_t)r * K), K, N, N - r, c->k0, c->Kloc);
+    return launch_check(c, "pk_fix_rootll");
+}
+
+// the resampling scan of the rank event's weights, one workgroup set per batched sweep; the last one also sums the log-normalisers
+static int step_scan(phylo_ctx* c, int r) {
+    const sweep_plan& p = c->run.plan;
+    const bool last = r + 1 == p.R;
+    return launch_scan(c, (const double*)(c->d_logw + (size_t)r * c->K), p.Kg, p.G, last ? (uint64_t*)nullptr : c->d_cdf[(r & 1) ^ 1],
+                       c->d_lse + r, p.lse_stride, (last && p.fold_logz) ? p.R : 0);
 }
 
 // phase 0: the whole rank event; 1: up to and including the merge; 2: what follows the all-gather of the rank
@@ -1538,227 +1738,23 @@ static int sweep_step_a(phylo_ctx* c) {
 static int sweep_step_impl(phylo_ctx* c, int phase) {
     CHK(bind(c));
     if (!c->run.active) return fail(c, PHYLO_ESTATE, "phylo_sweep_step without phylo_sweep_begin");
-    const int N = c->N, K = c->K, Kl = c->Kloc, S = c->S, R = N - 1;
-    if (c->run.next_r >= R) return fail(c, PHYLO_ESTATE, "all %d rank events of this sweep have been issued", R);
-    const uint64_t seed = c->run.seed;
-    const uint32_t flags = c->run.flags;
-    const int M = c->run.M;
-    const bool twist = c->run.twist, graph = c->run.graph, lazy = c->run.lazy, timek = c->run.timek;
-    int launches = 0;
-    const size_t lds = pk_book_lds_bytes(N);
-    const size_t plane = (size_t)K * N;
+    const sweep_plan& p = c->run.plan;
     const int r = c->run.next_r;
-    const int G = c->run.G, Kg = K / G;
-    const double ll_tilde0 = pm_log(1.0 / (double)Kg);     // vcsmc.py:422
-    const int cur = r & 1, nxt = cur ^ 1;
-    if (phase != 2 && c->run.a_done_r != r) CHK(sweep_step_a(c));
+    if (r >= p.R) return fail(c, PHYLO_ESTATE, "all %d rank events of this sweep have been issued", p.R);
     if (phase != 2) {
-        pk_rank_args b{};
-        b.r = r; b.n = N - r; b.N = N; b.S = S; b.K = K; b.Kloc = Kl; b.k0 = c->k0;
-        b.seed = seed; b.flags = flags;
-        b.Kg = Kg; b.group_seeds = G > 1 ? c->d_group_seeds : nullptr;
-        // the node of the LAST rank event is never merged again: its log-likelihood is all the sweep needs
-        b.no_store = (r == R - 1 && !graph && !(flags & PHYLO_EAGER_NODES) && !c->env.eager_nodes) ? 1 : 0;
-        if (r == R - 1) c->run.final_missing = b.no_store && !lazy;
-        if (graph) {                                       // every rank event keeps its tables: plane r -> plane r + 1
-            b.roots_old = c->d_hroots + plane * r; b.cnt_old = c->d_hcnt + plane * r;
-            b.roots_new = c->d_hroots + plane * (r + 1); b.cnt_new = c->d_hcnt + plane * (r + 1);
-            b.rootll_old = c->d_hrootll + plane * r; b.rootll_new = c->d_hrootll + plane * (r + 1);
-            b.pos_hist = c->d_pos + plane * r;
-        } else {
-            b.roots_old = c->d_roots[cur]; b.cnt_old = c->d_cnt[cur];
-            b.roots_new = c->d_roots[nxt]; b.cnt_new = c->d_cnt[nxt];
-            b.rootll_old = c->d_rootll[cur]; b.rootll_new = c->d_rootll[nxt];
-        }
-        b.cdf = c->d_cdf[cur];
-        b.ll_prev = r > 0 ? c->d_ll + (size_t)(r - 1) * K : nullptr;
-        b.nodell = c->d_nodell;
-        b.ldf = c->d_ldf; b.ldf_n = N;
-        b.bl = c->d_bl; b.br = c->d_br;
-        b.lam_l = c->h_lam_l[r]; b.lam_r = c->h_lam_r[r];
-        b.loglam_l = pm_log(b.lam_l); b.loglam_r = pm_log(b.lam_r);
-        b.ll_tilde0 = ll_tilde0;
-        b.leaves = c->d_leaves; b.pool = c->d_pool; b.pool_ptrs = c->d_pool_ptrs;
-        // the cache of remote nodes is filled by the bookkeeping launch, which must come behind the owners' writes of this rank
-        // event's adopted nodes: not so with replicated bookkeeping (and the twisted proposal reads its roots elsewhere)
-        b.mirror = (twist || c->run.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
-        b.leaf_codes = c->leaves_coded ? c->d_leaf_codes : nullptr;
-        b.Pmat = c->d_Pmat + (size_t)r * Kl * 32;
-        b.pi = c->d_pi;
-        b.logw_r = c->d_logw + (size_t)r * K;
-        b.ll_r = c->d_ll + (size_t)r * K;
-        b.merges = c->d_merges; b.ancestors = c->d_anc;
-        b.child = c->d_child + (size_t)r * Kl * 2; b.aux = c->d_aux;
-        // one rank, plain proposal, a merge that stores nothing: the bookkeeping also leaves a merge record per particle and the
-        // merge starts from it (the storing merge and the sharded and twisted sweeps resolve ids: no record is written for them)
-        const bool use_rec = !twist && Kl == K && (lazy || b.no_store);
-        b.rec = use_rec ? c->d_rec : nullptr;
-        b.lazy = lazy ? 1 : 0; b.mark = c->d_mark; b.child_all = c->d_child; b.Pmat_all = c->d_Pmat;
-        b.T = c->site_tile; b.ntiles = c->ntiles; b.tilev = c->d_tilev;
-        if (twist) {
-            pk_twist_args ta{};
-            ta.a = b;
-            ta.M = M;
-            ta.J = ((N - r) * (N - r - 1) / 2) * M;
-            ta.roots_ad = c->d_roots_ad; ta.cnt_ad = c->d_cnt_ad; ta.rootll_ad = c->d_rootll_ad;
-            ta.tw_b = c->d_tw_b; ta.tw_P = c->d_tw_P; ta.pot = c->d_pot; ta.chosen = c->d_chosen;
-            if (graph) {                                   // the reverse pass reads every rank event's sub-samples
-                const size_t j0 = (size_t)c->h_joff[r];
-                ta.tw_b = c->d_htw_b + j0 * 2; ta.tw_P = c->d_htw_P + j0 * 32; ta.pot = c->d_hpot + j0;
-                ta.roots_ad = c->d_hroots_ad + plane * r; ta.chosen = c->d_hchosen + (size_t)r * K;
-            }
-            ta.Pmat_r = c->d_Pmat + (size_t)r * Kl * 32;
-            ta.pair_hist = c->codes_valid ? c->d_pair_hist : nullptr;
-            ta.codes = c->codes_valid ? c->d_leaf_codes : nullptr;
-            ta.bl_r = c->d_bl + (size_t)r * Kl; ta.br_r = c->d_br + (size_t)r * Kl;
-            ta.own_tables = c->comm.transport == 0 ? 1 : 0;
-            ta.wbuf = c->d_twbuf;
-            hipLaunchKernelGGL(pk_twist_adopt_draws, dim3(K + cdiv(2L * Kl * ta.J, 64)), dim3(64), 0, c->stream, ta, (const double*)c->d_Q, c->jc);
-            CHK(launch_check(c, "pk_twist_adopt_draws"));
-            if (ta.pair_hist) {                            // coded leaf-leaf pairs: 25 code pairs per row instead of S sites
-                hipLaunchKernelGGL(pk_twist_potentials_ll, dim3((ta.J + 7) / 8, Kl), dim3(256), 0, c->stream, ta);
-                CHK(launch_check(c, "pk_twist_potentials_ll"));
-                ++launches;
-            }
-            // every other row: one wave each (at rank event 0 of a coded alignment every root is a leaf: nothing is left)
-            const bool any_rows = !(ta.pair_hist && r == 0);
-            const dim3 pgrid((unsigned)((((size_t)Kl * ta.J + 7) / 8) * 8));
-            if (timek) {   // a twisted sweep's dominant kernel is this one: PHYLO_TIME_KERNELS stamps it instead of the merge
-                if (any_rows) hipExtLaunchKernelGGL(pk_twist_potentials, pgrid, dim3(64), 0, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, ta);
-                else { HIPCHK(c, hipEventRecord(c->kev[2 * r], c->stream)); HIPCHK(c, hipEventRecord(c->kev[2 * r + 1], c->stream)); }
-            } else if (any_rows) {
-                hipLaunchKernelGGL(pk_twist_potentials, pgrid, dim3(64), 0, c->stream, ta);
-            }
-            CHK(launch_check(c, "pk_twist_potentials"));
-            hipLaunchKernelGGL(pk_twist_choose, dim3(Kl), dim3(64), (size_t)(ta.J <= PK_TWIST_LDS_J ? ta.J : 0) * 8, c->stream, ta);
-            CHK(launch_check(c, "pk_twist_choose"));
-            if (c->comm.transport != 0) {
-                double* rows[1] = {c->d_chosen};
-                CHK(comm_exchange(c, rows, 1, (size_t)Kl, 1));
-            }
-            if (!ta.own_tables) {
-                hipLaunchKernelGGL(pk_twist_tables, dim3(cdiv(K, 128)), dim3(128), 0, c->stream, ta);
-                CHK(launch_check(c, "pk_twist_tables"));
-                ++launches;
-            }
-            launches += 3;                                 // adopt + draws, potentials, choose
-        } else if (c->run.book_mat && r > 0) {
-            b.rdraw = c->d_rdraw + (size_t)r * K;
-            const int mat_blocks = K;
-            if (N <= 16) {
-                const int bb = cdiv(K, PK_COLS / 16);
-                hipLaunchKernelGGL(pk_rank_book_mat<16>, dim3(bb + mat_blocks), dim3(PK_COLS), lds * (PK_COLS / 16), c->stream, b, bb);
-            } else if (N <= 32) {
-                const int bb = cdiv(K, PK_COLS / 32);
-                hipLaunchKernelGGL(pk_rank_book_mat<32>, dim3(bb + mat_blocks), dim3(PK_COLS), lds * (PK_COLS / 32), c->stream, b, bb);
-            } else {                                       // 33..64 taxa (DS3-DS8): one wave per particle, four per workgroup
-                const int bb = cdiv(K, PK_COLS / 64);
-                hipLaunchKernelGGL(pk_rank_book_mat<64>, dim3(bb + mat_blocks), dim3(PK_COLS), lds * (PK_COLS / 64), c->stream, b, bb);
-            }
-            CHK(launch_check(c, "pk_rank_book_mat"));
-            ++launches;
-        } else {
-            // sharded, plain proposal: every rank advances only ITS particles' root tables and reads an
-            // adopted ancestor's row from the owner's slab over the peer mapping (ordered by the all-gather of the
-            // previous rank event, like the node pool) instead of replicating the bookkeeping of all K particles
-            const bool local_book = (c->world > 1 || (c->comm.transport != 0 && c->env.rehearse_sharded)) && !c->run.replicated_book;
-            if (local_book) {
-                b.tab_ptrs = c->d_tab_ptrs;
-                b.tab_off_rootll = (size_t)cur * K * N * 8;
-                b.tab_off_roots = (size_t)16 * K * N + (size_t)cur * K * N * 4;
-                b.tab_off_cnt = (size_t)24 * K * N + (size_t)cur * K * N * 4;
-            }
-            c->run.local_book = local_book;
-            const int nbook = local_book ? Kl : K;
-            // large launches (batched sweeps) are bound by instruction issue: 8 lanes per particle serve 8 particles with one
-            // instruction stream (3.52e11 -> 3.68e11 units/s for a launch set of 20 sweeps; 4 lanes: no further gain); small
-            // launches are latency chains and keep the shorter 16-lane form
-            if (N <= 16 && nbook >= 8192)
-                hipLaunchKernelGGL(pk_rank_book_packed<8>, dim3(cdiv(nbook, 8)), dim3(64), lds * 8, c->stream, b);
-            else if (N <= 16)                              // 4 particles per wave (PK_AUX + 2 = 10 <= 16 lanes)
-                hipLaunchKernelGGL(pk_rank_book_packed<16>, dim3(cdiv(nbook, 4)), dim3(64), lds * 4, c->stream, b);
-            else if (N <= 32)                              // 2 particles per wave
-                hipLaunchKernelGGL(pk_rank_book_packed<32>, dim3(cdiv(nbook, 2)), dim3(64), lds * 2, c->stream, b);
-            else
-                hipLaunchKernelGGL(pk_rank_book, dim3(nbook), dim3(64), lds, c->stream, b);
-            CHK(launch_check(c, "pk_rank_book"));
-            ++launches;
-        }
-        if (lazy && r > 0 && !(c->run.local_book && !twist) && !c->run.book_mat) {   // (sharded with owner-held tables: done in sweep_step_a)
-            // few nodes are marked, almost every workgroup leaves at once: one workgroup per particle for small nodes (a quarter
-            // of the empty workgroups), site tiles for large ones (a marked node is then not limited to one CU's bandwidth)
-            // large launches of small nodes (batched sweeps): dispatching one workgroup per particle costs more than the few writes
-            if (S <= 4096 && Kl > 8192) hipLaunchKernelGGL(pk_materialize_adopted_grouped, dim3(cdiv(Kl, PK_MAT_GROUP)), dim3(PK_COLS), 0, c->stream, b);
-            else hipLaunchKernelGGL(pk_materialize_adopted, dim3(S <= 4096 ? 1 : cdiv(S, PK_MAT_TILE), Kl), dim3(PK_COLS), 0, c->stream, b);
-            CHK(launch_check(c, "pk_materialize_adopted"));
-            ++launches;
-            if (c->comm.transport != 0) CHK(comm_exchange(c, nullptr, 0, 0, 1));   // peers read these nodes in place: order them before every rank's merge
-        }
-        // row-per-lane form when nothing is stored: pk_rank_merge is launched only when the node is stored
-        const bool nostore = b.lazy || b.no_store;
-        const size_t mitems = (size_t)Kl * c->ntiles;                              // one wave per (particle, site tile)
-        const dim3 mgrid((unsigned)mitems);
-        // pi by value, from the pinned image of the model upload.  Invariant: phylo_set_model is the only writer of d_Q / d_pi and
-        // of that image, and it rewrites the image only after the previous upload has finished, so for every launch issued after
-        // it returns the image equals the model the other kernels read from d_pi.  A model update made on the device would have
-        // to refresh the image too.
-        pk_pi4 pi4;
-        memcpy(pi4.v, c->h_model_p + 16, sizeof pi4.v);
-        const unsigned long long* mrec = b.rec;
-        if (timek && !twist) {  // events stamped with the kernel's own begin/end (what rocprofv3 --kernel-trace reports)
-            if (nostore && use_rec) hipExtLaunchKernelGGL(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, mrec, b.Pmat, S, b.T, b.ntiles, b.tilev, pi4);
-            else if (nostore) hipExtLaunchKernelGGL(pk_rank_merge_nostore_ids, mgrid, dim3(64), 0, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, b);
-            else hipExtLaunchKernelGGL(pk_rank_merge, mgrid, dim3(PK_COLS), (size_t)(c->site_tile < S ? c->site_tile : S) * 8 + 16 + PK_STORE_STAGE_BYTES, c->stream, c->kev[2 * r], c->kev[2 * r + 1], 0, b);
-        } else if (nostore && use_rec) {
-            hipLaunchKernelGGL(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, mrec, b.Pmat, S, b.T, b.ntiles, b.tilev, pi4);
-        } else if (nostore) {
-            hipLaunchKernelGGL(pk_rank_merge_nostore_ids, mgrid, dim3(64), 0, c->stream, b);
-        } else {
-            hipLaunchKernelGGL(pk_rank_merge, mgrid, dim3(PK_COLS), (size_t)(c->site_tile < S ? c->site_tile : S) * 8 + 16 + PK_STORE_STAGE_BYTES, c->stream, b);
-        }
-        if (c->ntiles > 1) {    // rows longer than one tile: tile values left to right, then the particle's weight terms
-            CHK(launch_check(c, "pk_rank_merge"));
-            hipLaunchKernelGGL(pk_tile_epilogue, dim3(cdiv(Kl, 256)), dim3(256), 0, c->stream, b);
-            ++launches;
-        }
-        CHK(launch_check(c, "pk_rank_merge"));
-        ++launches;
+        if (c->run.a_done_r != r) CHK(sweep_step_a(c));
+        const pk_rank_args b = rank_args(c, r);
+        if (p.twist) CHK(step_twist(c, b));
+        else CHK(step_book(c, b));
+        if (p.mat_after_book && r > 0) CHK(step_materialize(c, b));
+        CHK(step_merge(c, b));
+        if (p.tile_epilogue) CHK(step_tiles(c, b));
     }
-    if (phase == 0 && c->comm.transport != 0) {
-        double* rows[3] = {c->d_logw + (size_t)r * K, c->d_ll + (size_t)r * K, c->d_nodell + N + (size_t)r * K};
-        CHK(comm_exchange(c, rows, 3, (size_t)Kl, 0));
-    }
-    if (phase == 1) {
-        c->run.launches += launches;
-        return PHYLO_OK;
-    }
-    {
-        {
-            if (c->comm.transport != 0) {
-                if (!c->run.local_book) {
-                    hipLaunchKernelGGL(pk_fix_rootll, dim3(cdiv(K, 256)), dim3(256), 0, c->stream,
-                                       graph ? c->d_hrootll + plane * (r + 1) : c->d_rootll[nxt],
-                                       (const double*)(c->d_nodell + N + (size_t)r * K), K, N, N - r, c->k0, Kl);
-                    CHK(launch_check(c, "pk_fix_rootll"));
-                    ++launches;
-                }
-            }
-            if (G > 1) {                                       // one scan workgroup per batched sweep
-                const bool fold = r + 1 == R && Kg <= PP_SCAN_KERNEL_MAX_KG;   // the last scan also sums the log-normalisers
-                CHK(launch_scan(c, (const double*)(c->d_logw + (size_t)r * K), Kg, G, (r + 1 < R) ? c->d_cdf[nxt] : (uint64_t*)nullptr,
-                                c->d_lse + r, R + 1, fold ? R : 0));
-                if (fold) c->run.logz_done = true;
-                ++launches;
-            } else {
-                const bool fold = r + 1 == R && K <= PP_SCAN_KERNEL_MAX_KG;
-                CHK(launch_scan(c, (const double*)(c->d_logw + (size_t)r * K), K, 1, (r + 1 < R) ? c->d_cdf[nxt] : (uint64_t*)nullptr,
-                                c->d_lse + r, 0, fold ? R : 0));
-                if (fold) c->run.logz_done = true;
-                ++launches;
-            }
-        }
-    }
-    c->run.launches += launches;
+    if (phase == 0) CHK(step_exchange(c, r));
+    if (phase == 1) return PHYLO_OK;
+    if (p.fix_rootll) CHK(step_fix_rootll(c, r));
+    CHK(step_scan(c, r));
+    c->run.launches += sweep_plan_launches(p, r);
     ++c->run.next_r;
     return PHYLO_OK;
 }
@@ -1814,8 +1810,8 @@ int phylo_sweep_step_group(phylo_ctx** ctxs, int n) {
 // ancestors) into whole-K arrays on every rank (pk_gx_pack / pk_gx_unpack).  Node rows are not copied: the reverse pass reads
 // them from their owners' pools over the peer mappings (pg_node_row).  Device-side exchange: barrier, the peers' buffers read
 // over the mappings, barrier (nobody packs again before every reader is done); collective path: the all-gather of the buffers in
-// chunks, then the same tail.  A collective: every rank's sweep ends here.  *launches: kernels this issued.
-static int graph_gather(phylo_ctx* c, int* launches) {
+// chunks, then the same tail.  A collective: every rank's sweep ends here.
+static int graph_gather(phylo_ctx* c) {
     const int K = c->K, Kl = c->Kloc, R = c->N - 1;
     pk_gx_args a{};
     a.world = c->world; a.me = c->rank; a.Kloc = Kl; a.K = K;
@@ -1853,7 +1849,6 @@ static int graph_gather(phylo_ctx* c, int* launches) {
     const size_t total = a.seg * (size_t)c->world;
     hipLaunchKernelGGL(pk_gx_unpack, dim3((unsigned)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096)), dim3(256), 0, c->stream, a);
     CHK(launch_check(c, "pk_gx_unpack"));
-    *launches += c->p2p ? 4 : 2;                           // pack, unpack (+ the two barrier kernels of the device-side exchange)
     return comm_exchange(c, nullptr, 0, 0, 1);
 }
 
@@ -1862,29 +1857,22 @@ int phylo_sweep_finish(phylo_ctx* c) {
     const int N = c->N, Kl = c->Kloc, S = c->S, R = N - 1;
     if (!c->run.active || c->run.next_r != R)
         return fail(c, PHYLO_ESTATE, "phylo_sweep_finish needs phylo_sweep_begin and all %d phylo_sweep_step calls", R);
-    const uint32_t flags = c->run.flags;
-    const int M = c->run.M;
-    const bool twist = c->run.twist, graph = c->run.graph, lazy = c->run.lazy, timek = c->run.timek;
-    int launches = c->run.launches;
-    (void)flags;
-    if (!c->run.logz_done) {
-        if (c->run.G > 1)
-            hipLaunchKernelGGL(pk_logz_total_groups, dim3(c->run.G), dim3(64), 0, c->stream, c->d_lse, R, R + 1);
+    const sweep_plan& p = c->run.plan;
+    if (!p.fold_logz) {
+        if (p.G > 1)
+            hipLaunchKernelGGL(pk_logz_total_groups, dim3(p.G), dim3(64), 0, c->stream, c->d_lse, R, R + 1);
         else
             hipLaunchKernelGGL(pk_logz_total, dim3(1), dim3(64), 0, c->stream, (const double*)c->d_lse, R, c->d_lse + R);
         CHK(launch_check(c, "pk_logz_total"));
-        ++launches;
     }
-    if (graph && c->world > 1) {                           // sharded: the reverse pass reads the whole graph on every rank
-        CHK(graph_gather(c, &launches));
-    }
+    if (p.gather_launches) CHK(graph_gather(c));           // sharded: the reverse pass reads the whole graph on every rank
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    if (graph) {                                           // the reverse pass builds its lists from these on the host
+    if (p.graph) {                                         // the reverse pass builds its lists from these on the host
         pg_copy3 cp{};                                     // (by a kernel into the pinned buffers: pg_copy_words says why)
         const bool whole = c->world > 1;
         cp.src[0] = (const uint32_t*)(whole ? c->d_ganc : c->d_anc); cp.dst[0] = c->hd_anc; cp.n[0] = R > 1 ? (size_t)(R - 1) * c->K * 2 : 0;
         cp.src[1] = (const uint32_t*)(whole ? c->d_gchild : c->d_child); cp.dst[1] = c->hd_child; cp.n[1] = (size_t)R * c->K * 2;
-        if (twist) { cp.src[2] = (const uint32_t*)c->d_hroots_ad; cp.dst[2] = c->hd_rad; cp.n[2] = (size_t)R * c->K * N; }
+        if (p.twist) { cp.src[2] = (const uint32_t*)c->d_hroots_ad; cp.dst[2] = c->hd_rad; cp.n[2] = (size_t)R * c->K * N; }
         // ... and what phylo_sweep_fetch would otherwise copy one by one: log Z-hat, the timeout word of the bounded waits
         cp.src[3] = (const uint32_t*)(c->d_lse + R); cp.dst[3] = c->hd_pub; cp.n[3] = 2;
         cp.src[4] = (const uint32_t*)(c->d_counter + 1); cp.dst[4] = c->hd_pub + 2; cp.n[4] = 1;
@@ -1893,25 +1881,15 @@ int phylo_sweep_finish(phylo_ctx* c) {
         CHK(launch_check(c, "pg_copy_words"));
         HIPCHK(c, hipEventRecord(c->ev_gcopy, c->stream));
     }
-    c->swept = true;
     c->run.active = false;
-    c->last_lazy = lazy;
-    c->last_graph = graph;
-    c->last_graph_twist = graph && twist;
-    c->last_graph_marks = graph && c->run.lazy;
-    // (what made the sweep eager with lazy_ok's other conditions met: the flag or the switch alone; one GPU -- a sharded pass keeps
-    //  its own form)
-    // (above PG_KEPT_BITS_TAXA only: up to there every form keeps the bits it had -- phylo_revlists.h)
-    c->last_graph_eager = graph && !c->run.lazy && !twist && S <= 4096 && c->world == 1 && Kl == c->K && N > PG_KEPT_BITS_TAXA;
+    sweep_publish(c, p.lazy, p.graph, p.G, p.final_missing, p.timek ? R : 0, c->run.launches + sweep_plan_launches(p, R),
+                  (double)Kl * S * R);
+    c->last_graph_twist = p.graph && p.twist;
+    c->last_graph_marks = p.graph && p.lazy;
+    c->last_graph_eager = p.last_graph_eager;
     c->last_M = c->run.M;
-    c->last_G = c->run.G;
-    c->last_final_missing = c->run.final_missing;
-    c->n_merge_events = timek ? R : 0;
-    c->stats.n_launches = launches;
-    c->stats.units = (double)Kl * S * R;
-    c->stats.alg_bytes = 96.0 * c->stats.units;
-    if (twist) {                                           // + K M S C(N+1,3) look-ahead merges, 64 B each (no store)
-        const double ut = (double)Kl * M * S * ((double)(N + 1) * N * (N - 1) / 6.0);
+    if (p.twist) {                                         // + K M S C(N+1,3) look-ahead merges, 64 B each (no store)
+        const double ut = (double)Kl * c->run.M * S * ((double)(N + 1) * N * (N - 1) / 6.0);
         c->stats.units += ut;
         c->stats.alg_bytes += 64.0 * ut;
     }
@@ -2875,6 +2853,26 @@ int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int tw
     pg_plan p = pg_plan_form(in);
     pg_plan_chains(p, (long)n_slow, TS, (long)coeff_wgs, passes_in_flight, N - 1);
     *mask = pg_plan_mask(p);
+    return PHYLO_OK;
+}
+
+int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
+                           uint32_t* mask, int32_t* launches) {
+    if (N < 2 || N > PK_MAX_TAXA || K < 1 || K_local < 1 || K_local > K || S < 1 || world < 1 || !mask || !launches)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_sweep_plan: bad arguments");
+    sweep_facts f{};
+    f.N = N; f.K = K; f.Kloc = K_local; f.S = S; f.G = G; f.M = M; f.world = world;
+    f.ntiles = (S + pm_site_tile(S) - 1) / pm_site_tile(S);
+    f.transport = transport != 0;
+    sweep_facts_flags(f, flags);
+    f.env_eager_nodes = switches & 1; f.env_rehearse_sharded = switches & 2; f.env_replicated_book = switches & 4;
+    f.jc = switches & 8; f.coded_leaves = switches & 16; f.device_exchange = switches & 32;
+    char why[160];
+    if (sweep_refuses_batch(f, k_sweep_limits, why, sizeof why) || sweep_refuses_form(f, k_sweep_limits, why, sizeof why))
+        return fail(nullptr, PHYLO_EINVAL, "%s", why);
+    const sweep_plan p = sweep_plan_form(f, k_sweep_limits);
+    *mask = sweep_plan_mask(p);
+    for (int r = -1; r <= p.R; ++r) launches[r + 1] = sweep_plan_launches(p, r);
     return PHYLO_OK;
 }
 

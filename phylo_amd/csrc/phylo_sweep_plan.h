@@ -1,0 +1,212 @@
+// phylo_sweep_plan.h -- the form of a forward sweep of the launch path (phylo_hip.hip: sweep_begin_impl, the stages of a rank event,
+// phylo_sweep_finish).  Plain C++, no HIP, like phylo_revlists.h: the same functions run in the driver and behind
+// phylo_debug_sweep_plan (tests/test_sweepplan_cpu.py restates the rules).
+//
+// Every form computes the same bits (the parity tests assert that), so a rule that silently picks another form passes every one
+// of them and only shows as a slower sweep.  Which form is issued is therefore decided HERE and nowhere else, once per sweep:
+// sweep_begin_impl computes the plan and stores it in the run, the stages only read it.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+// Constants that live in the kernel headers, and the thresholds of the rules below (the driver fills them by name: sweep_limits_of).
+struct sweep_limits {
+    int max_groups;                    // PK_MAX_GROUPS
+    int twist_max_m, twist_max_j;      // PK_TWIST_MAX_M, PK_TWIST_MAX_J
+    int mat_group;                     // PK_MAT_GROUP: particles per workgroup of the grouped adopted-node launches
+    int scan_fold_max_kg;              // PP_SCAN_KERNEL_MAX_KG: the scan kernels that can also sum the log-normalisers
+    int kept_bits_taxa;                // PG_KEPT_BITS_TAXA
+    int one_tile_max_s;                // 4096: sites of a node that one workgroup writes / of the rows form of the reverse pass
+    int small_max_kg, small_max_kloc;  // 4096, 8192: launches of at most this many particles count as small (latency chains)
+    int book_packed8_min;              // 8192: root tables advanced in one launch from which 8 lanes per particle pay
+    int sorted_min_draws;              // 262144: branch-length draws (2 R Kloc) from which the prologue sorts its matrices
+};
+
+struct sweep_facts {
+    // the shape
+    int N, K, Kloc, S, G, M, world;    // (K: all ranks' particles; Kloc: this rank's; G: sweeps batched in the context)
+    int ntiles;                        // site tiles of a row (the context's site tile decides: 1 unless S exceeds it)
+    bool transport;                    // a communicator is set (phylo_comm_init), whatever the number of ranks
+    bool device_exchange;              // ... and its collectives are the device-side exchange (pk_p2p_exchange)
+    bool jc;                           // the model is JC69 (closed-form matrices)
+    bool coded_leaves;                 // every leaf row is one-hot or all-ones (the twisted proposal's pair histogram)
+    // the flag bits
+    bool twisting, keep_graph, eager_nodes, time_kernels;
+    // the environment switches the launch path reads
+    bool env_eager_nodes, env_rehearse_sharded, env_replicated_book;
+};
+
+struct sweep_plan {
+    int R, G, Kg;                      // rank events; batched sweeps and the particles of one
+    bool twist, graph, timek;
+    bool one_tile;                     // S <= 4096: a node is written by one workgroup
+    bool lazy;                         // nodes are written only when adopted (marks say which)
+    bool shard_form;                   // the sweep is issued as a sharded one (more than one rank, or a one-rank rehearsal)
+    bool replicated_book;              // sharded: every rank advances all K root tables
+    bool local_book;                   // sharded, plain proposal: every rank advances its own particles' tables only
+    bool book_mat;                     // bookkeeping and the writes of the adopted nodes share one launch (pk_rank_book_mat), r > 0
+    bool mat_by_draws;                 // sharded: owners find their adopted nodes from the draws (no pk_all_marks)
+    bool want_rdraw;                   // the prologue leaves the resampling draws in d_rdraw
+    bool use_rec;                      // the bookkeeping leaves a merge record per particle and the merge starts from it
+    bool sorted_prologue;              // pk_sweep_prologue_sorted
+    bool mat_grouped;                  // pk_materialize_adopted_grouped instead of pk_materialize_adopted
+    bool mat_draws_grouped;            // pk_materialize_by_draws: one workgroup per mat_group particles
+    int book_width;                    // lanes per particle of the bookkeeping: 8, 16, 32, 64, or 0 = one wave (pk_rank_book).
+                                       // (pk_rank_book_packed has no 64: one wave then too; pk_rank_book_mat has no 8: 16)
+    bool step_a_work;                  // sweep_step_a issues the adopted-node launches and their barrier for r > 0
+    bool mat_after_book;               // ... else the step does, behind its bookkeeping, for r > 0 (not at all: eager, or book_mat)
+    bool mat_barrier;                  // that launch is followed by a barrier across the ranks
+    bool twist_ll;                     // twisted: coded leaf-leaf pairs go through pk_twist_potentials_ll
+    bool twist_tables;                 // twisted: pk_twist_tables advances the tables (a communicator is set)
+    bool tile_epilogue;                // rows longer than one site tile: pk_tile_epilogue behind the merge
+    bool fix_rootll;                   // sharded without local bookkeeping: pk_fix_rootll behind the exchange
+    bool fold_logz;                    // the last scan also sums the log-normalisers (no pk_logz_total launch)
+    int lse_stride;                    // the scan's stride between the groups' log-normalisers (0: one sweep)
+    bool no_store_last;                // the merge of the last rank event stores no node
+    bool final_missing;                // ... and nothing else wrote it: phylo_sweep_node has to
+    bool last_graph_eager;             // a kept graph whose reverse pass can write the marks itself (rev_marks)
+    int gather_launches;               // kernels of graph_gather behind the last rank event (sharded kept graph)
+};
+
+// PHYLO_EAGER_NODES, as a flag or from the environment: every node is stored by its merge (also read by persist_plan)
+inline bool sweep_eager_nodes(bool flag, bool env) { return flag || env; }
+
+// Lanes per particle of the bookkeeping launch that advances `nbook` root tables of N slots.
+// Large launches (batched sweeps) are bound by instruction issue: 8 lanes per particle serve 8 particles with one instruction
+// stream (3.52e11 -> 3.68e11 units/s for a launch set of 20 sweeps; 4 lanes: no further gain); small launches are latency chains
+// and keep the shorter 16-lane form (4 particles per wave: PK_AUX + 2 = 10 <= 16 lanes).  33..64 taxa (DS3-DS8): 64.
+inline int sweep_book_width(int N, int nbook, const sweep_limits& L) {
+    if (N <= 16) return nbook >= L.book_packed8_min ? 8 : 16;
+    if (N <= 32) return 32;
+    return N <= 64 ? 64 : 0;
+}
+
+// The argument refusals of a sweep, in the order phylo_sweep_begin checks them: true, and the message, when the facts are refused
+// (PHYLO_EINVAL).  First what a batch needs; then, behind the check that leaves and model are set (PHYLO_ESTATE), what the twisted
+// proposal and a kept graph need.
+inline bool sweep_refuses_batch(const sweep_facts& f, const sweep_limits& L, char* msg, size_t n) {
+    const bool sharded = f.world != 1;
+    if (f.G < 1 || f.G > L.max_groups || f.K % f.G != 0)
+        return snprintf(msg, n, "a batch needs 1 <= G <= %d sweeps and K = %d divisible by G (got %d)", L.max_groups, f.K, f.G), true;
+    if (f.G > 1 && f.twisting) return snprintf(msg, n, "batched sweeps need the plain proposal (PHYLO_TWISTING is set)"), true;
+    if (f.G > 1 && f.keep_graph) {     // the graph of G systems: one block-diagonal genealogy, rows form, one GPU
+        if (sharded || f.transport) return snprintf(msg, n, "batched sweeps with PHYLO_KEEP_GRAPH need an unsharded context"), true;
+        if (f.S > L.one_tile_max_s)
+            return snprintf(msg, n, "batched sweeps with PHYLO_KEEP_GRAPH need S <= 4096 sites (got %d)", f.S), true;
+    }
+    return false;
+}
+inline bool sweep_refuses_form(const sweep_facts& f, const sweep_limits& L, char* msg, size_t n) {
+    const bool sharded = f.world != 1;
+    if (f.twisting) {
+        if (f.M < 1 || f.M > L.twist_max_m)
+            return snprintf(msg, n, "twisting needs 1 <= M <= %d (got %d)", L.twist_max_m, f.M), true;
+        const size_t Jmax = (size_t)(f.N * (f.N - 1) / 2) * (size_t)f.M;
+        if (Jmax > (size_t)L.twist_max_j) return snprintf(msg, n, "twisting: C(N,2)*M = %zu exceeds %d", Jmax, L.twist_max_j), true;
+    }
+    if (f.keep_graph && sharded) {     // sharded: the plain proposal on nodes of one site tile (graph_gather)
+        if (f.twisting) return snprintf(msg, n, "PHYLO_KEEP_GRAPH with PHYLO_TWISTING needs an unsharded context"), true;
+        if (f.S > L.one_tile_max_s)
+            return snprintf(msg, n, "PHYLO_KEEP_GRAPH on a sharded context needs S <= 4096 sites (got %d)", f.S), true;
+    }
+    return false;
+}
+
+inline sweep_plan sweep_plan_form(const sweep_facts& f, const sweep_limits& L) {
+    sweep_plan p{};
+    const int N = f.N, K = f.K, Kl = f.Kloc, S = f.S;
+    p.R = N - 1; p.G = f.G; p.Kg = K / f.G;
+    p.twist = f.twisting; p.graph = f.keep_graph; p.timek = f.time_kernels;
+    const bool eager = sweep_eager_nodes(f.eager_nodes, f.env_eager_nodes);
+    const bool one_tile = p.one_tile = S <= L.one_tile_max_s;
+    // lazy nodes: dead stores are most of the HBM traffic of the plain sweep (a node is read again only if its creator survives
+    // the next resampling).  Needs the plain proposal.  Marks are plain stores and the extra launch costs less than the dead
+    // stores it removes at every size measured.
+    // A kept graph stays lazy too when its reverse pass reads no node but the adopted ones (rows form, S <= 4096: pg_nodes_free
+    // recomputes a node's row from its children; everything else that is read was somebody's child, i.e. adopted).
+    // Sharded, the owner's write needs one more (tiny) collective per rank event (sweep_step_a); rehearsed with a one-rank RCCL
+    // world (PHYLO_REHEARSE_SHARDED=1) the lazy sweep is 0.145 ms against 0.185 ms for the eager one at primate.p's node size, more
+    // than a second collective costs.
+    p.lazy = !p.twist && (!p.graph || one_tile) && !eager;
+    p.shard_form = f.world > 1 || (f.transport && f.env_rehearse_sharded);      // (the switch: a one-rank rehearsal)
+    // a sharded sweep that keeps its graph advances all K root tables on every rank: the history planes it writes are then whole
+    // everywhere (the owner-held tables that peers read are the two planes of d_tables, not the history)
+    p.replicated_book = f.env_replicated_book || (p.graph && f.world > 1);
+    // sharded, plain proposal: every rank advances only ITS particles' root tables and reads an adopted ancestor's row from the
+    // owner's slab over the peer mapping (ordered by the all-gather of the previous rank event, like the node pool) instead of
+    // replicating the bookkeeping of all K particles.  (The twisted proposal advances its tables in kernels of its own.)
+    p.local_book = !p.twist && p.shard_form && !p.replicated_book;
+    // one sweep alone on one GPU with lazy nodes: the adopted nodes are written in the bookkeeping launch (pk_rank_book_mat), found
+    // by the resampling draws, which pk_sweep_prologue then leaves in d_rdraw.  Batched sweeps keep the separate launch (measured:
+    // 2.62e11 against 2.64e11 units/s with the grouped form of the combined launch in round 2; round 3, a launch set alone: 3.57e11
+    // against 3.77e11).
+    p.book_mat = p.lazy && f.world == 1 && !f.transport && N <= 64 && one_tile && f.G == 1 && Kl <= L.small_max_kloc;
+    // sharded with lazy nodes: each owner finds ITS adopted nodes the same way (O(Kloc Kg / 64) comparisons) instead of every rank
+    // searching the ancestors of all K particles (pk_all_marks, O(K) on every rank whatever the number of GPUs)
+    const bool mat_small = p.Kg <= L.small_max_kg && Kl <= L.small_max_kloc;
+    p.mat_by_draws = p.lazy && p.local_book && one_tile && (mat_small || (p.Kg % L.mat_group == 0 && Kl % L.mat_group == 0));
+    p.mat_draws_grouped = !mat_small;                      // one workgroup per 64 particles when there are many
+    p.want_rdraw = p.book_mat || p.mat_by_draws;
+    // the node of the LAST rank event is never merged again: its log-likelihood is all the sweep needs
+    p.no_store_last = !p.graph && !eager;
+    p.final_missing = p.no_store_last && !p.lazy;
+    // one rank, plain proposal, a merge that stores nothing: the bookkeeping also leaves a merge record per particle and the merge
+    // starts from it (the storing merge and the sharded and twisted sweeps resolve ids: no record is written for them).
+    // (The last rank event's stores-nothing adds no case: with the plain proposal, no_store_last implies lazy.)
+    p.use_rec = !p.twist && Kl == K && p.lazy;
+    // large launches (batched sweeps): the matrices sorted by Pade order inside workgroups of 1024 (pk_sweep_draws_sorted)
+    p.sorted_prologue = !p.twist && !f.jc && 2L * p.R * Kl >= L.sorted_min_draws;
+    // Adopted nodes in a launch of their own.  Few nodes are marked, almost every workgroup leaves at once: one workgroup per
+    // particle for small nodes (a quarter of the empty workgroups), site tiles for large ones (a marked node is then not limited
+    // to one CU's bandwidth).  Large launches of small nodes (batched sweeps): dispatching one workgroup per particle costs more
+    // than the few writes, one workgroup takes mat_group particles.
+    p.mat_grouped = one_tile && Kl > L.small_max_kloc;
+    p.step_a_work = p.lazy && p.local_book;                // sharded with owner-held tables: ahead of the bookkeeping, in sweep_step_a
+    p.mat_after_book = p.lazy && !p.local_book && !p.book_mat;
+    p.mat_barrier = f.transport;                           // peers read these nodes in place: order them before every rank's merge
+    p.book_width = p.twist ? 0 : sweep_book_width(N, p.local_book ? Kl : K, L);
+    p.twist_ll = p.twist && f.coded_leaves;
+    p.twist_tables = p.twist && f.transport;
+    p.tile_epilogue = f.ntiles > 1;
+    p.fix_rootll = f.transport && !p.local_book;
+    p.fold_logz = p.Kg <= L.scan_fold_max_kg;
+    p.lse_stride = f.G > 1 ? p.R + 1 : 0;
+    // (what made the sweep eager with lazy's other conditions met: the flag or the switch alone; one GPU -- a sharded pass keeps
+    //  its own form; above kept_bits_taxa only: up to there every form keeps the bits it had -- phylo_revlists.h)
+    p.last_graph_eager = p.graph && !p.lazy && !p.twist && one_tile && f.world == 1 && Kl == K && N > L.kept_bits_taxa;
+    // pack, unpack (+ the two barrier kernels of the device-side exchange)
+    p.gather_launches = (p.graph && f.world > 1) ? (f.device_exchange ? 4 : 2) : 0;
+    return p;
+}
+
+// What the driver counts into stats.n_launches: r = -1 the begin, 0 .. R-1 rank event r (sweep_step_a's half included), R the
+// finish.  This is the driver's count as it always was, which is not everywhere the number of kernels: a scan of several
+// workgroups per group counts 1 for its three launches, a twisted rank event counts 3 for adopt + draws, potentials and choose
+// even when pk_twist_potentials has no rows and is not launched, and pk_pair_hist and the kernels of the collectives are not
+// counted.  tests/test_gpu_sweep_forms.py pins the totals.
+inline int sweep_plan_launches(const sweep_plan& p, int r) {
+    if (r < 0) return 1;                                   // pk_sweep_prologue, or pk_init_tables of the twisted proposal
+    if (r >= p.R) return (p.fold_logz ? 0 : 1) + p.gather_launches;
+    int n = 0;
+    if (p.step_a_work && r > 0) n += p.mat_by_draws ? 1 : 2;                     // by the draws, or pk_all_marks + the adopted nodes
+    n += p.twist ? 3 + (p.twist_ll ? 1 : 0) + (p.twist_tables ? 1 : 0) : 1;      // the proposal, or the bookkeeping
+    if (p.mat_after_book && r > 0) n += 1;
+    n += 1 + (p.tile_epilogue ? 1 : 0);                    // the merge
+    n += (p.fix_rootll ? 1 : 0) + 1;                       // behind the exchange: the scan
+    return n;
+}
+
+// The plan as phylo_debug_sweep_plan returns it: the booleans in this order from bit 0 (SWEEP_PLAN_BITS of phylo_amd/_ffi.py names
+// them; `batched` is lse_stride != 0), book_width / 8 in bits 28..31.  gather_launches is the finish's count beyond pk_logz_total.
+inline uint32_t sweep_plan_mask(const sweep_plan& p) {
+    const bool b[] = {p.twist, p.graph, p.timek, p.lazy, p.shard_form, p.replicated_book, p.local_book, p.book_mat, p.mat_by_draws,
+                      p.want_rdraw, p.use_rec, p.sorted_prologue, p.mat_grouped, p.mat_draws_grouped, p.step_a_work, p.mat_after_book,
+                      p.mat_barrier, p.fix_rootll, p.fold_logz, p.no_store_last, p.final_missing, p.last_graph_eager,
+                      p.one_tile, p.twist_ll, p.twist_tables, p.tile_epilogue, p.lse_stride != 0};
+    static_assert(sizeof b / sizeof b[0] <= 28, "bits 28..31 hold book_width / 8");
+    uint32_t m = (uint32_t)(p.book_width / 8) << 28;
+    for (size_t i = 0; i < sizeof b / sizeof b[0]; ++i) m |= b[i] ? 1u << i : 0u;
+    return m;
+}
