@@ -322,6 +322,17 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
  * limit sees the totals.  G = 1 is phylo_debug_reverse_plan. */
 int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,
                                    int passes_in_flight, uint32_t* mask);
+/* No GPU and no context needed: the form of phylo_tree_summary and phylo_tree_branches (pt_plan_form / pb_plan_form of
+ * phylo_trees_plan.h; DESIGN.md section 10 "driver") for a sweep of G groups on `world` ranks, a summary of n_clades and
+ * n_topologies rows, whether the sweep kept whole-K branch lengths, and rocPRIM's temporary-storage bytes of either pass (facts).
+ * scalars[13]: R, L, W, E, Emax, Kg, cbits, tbits, wide, gather, the number of sort passes, the buffers of slot 12, of slot 13.
+ * summary_slab / branches_slab [2 n + 1]: the n buffers' offsets, their bytes, the slab's total (order: TREE_SUMMARY_BUFS /
+ * TREE_BRANCHES_BUFS of phylo_amd/_ffi.py).  sort_bits[17]: the radix bits of the summary's sort passes in issue order.
+ * launches[2]: what stats.n_launches of the two calls counts.  What the calls refuse is refused with the same code and message
+ * (the summary's first).  tests/test_treeplan_cpu.py restates the rules. */
+int phylo_debug_tree_plan(int N, int K, int G, int world, int64_t n_clades, int64_t n_topologies, int kept_whole, int64_t summary_temp,
+                          int64_t branches_temp, int64_t* scalars, int64_t* summary_slab, int64_t* branches_slab, int32_t* sort_bits,
+                          int32_t* launches);
 
 /* The same lists built by the device kernels (phylo_revlists_dev.h) from the graph of the preceding lazy sweep with
  * PHYLO_KEEP_GRAPH, copied back in the same layout (what the builders do not write reads -1; heavy[] holds GLOBAL chunk indices,

@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_tree_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -170,6 +170,40 @@ def debug_sweep_plan(N, K, S, K_local=None, G=1, M=1, world=1, transport=False, 
     out["book_width"] = (mask.value >> 28) * 8
     out["mask"] = mask.value
     out["launches"] = list(launches)
+    return out
+
+
+TREE_SUMMARY_BUFS = ("u", "U", "bits", "kA", "kB", "val", "scan", "weight", "srt", "hp", "o_cbits", "o_cw", "o_tw", "child", "slot", "o_cg",
+                     "o_tn", "o_trep", "o_tg", "o_ptopo", "vA", "vB", "flag", "sid", "cid", "seg_start", "count", "group", "first", "tid", "pos",
+                     "err", "vC", "vD", "temp")
+TREE_BRANCHES_BUFS = ("ebr", "lbr", "gbl", "gbr", "o_cs", "o_ls", "o_ts", "wA", "wB", "cpos", "kA", "kB", "vA", "vB", "cstart", "toff", "o_tc",
+                      "temp")
+
+
+def debug_tree_plan(N, K, G=1, world=1, n_clades=1, n_topologies=1, kept_whole=False, summary_temp=0, branches_temp=0):
+    """The form phylo_tree_summary and phylo_tree_branches take for a sweep of G groups on `world` ranks, a summary of n_clades and
+    n_topologies rows, whether the sweep kept whole-K branch lengths, and rocPRIM's temporary-storage bytes of either pass -- no
+    GPU needed.  A dict: the scalars R, L, W, E, Emax, Kg, cbits, tbits, wide, gather; 'summary_slab' / 'branches_slab' =
+    {'offsets': {name: bytes}, 'sizes': {name: bytes}, 'total'} over TREE_SUMMARY_BUFS / TREE_BRANCHES_BUFS (scratch slots 12 and
+    13); 'sort_bits', the radix bits of the summary's sort passes in issue order; 'summary_launches', 'branches_launches'."""
+    lib = load()
+    ns, nb = len(TREE_SUMMARY_BUFS), len(TREE_BRANCHES_BUFS)
+    sc = (C.c_int64 * 13)()
+    ss, bs = (C.c_int64 * (2 * ns + 1))(), (C.c_int64 * (2 * nb + 1))()
+    bits, launches = (C.c_int32 * 17)(), (C.c_int32 * 2)()
+    rc = lib.phylo_debug_tree_plan(C.c_int(N), C.c_int(K), C.c_int(G), C.c_int(world), C.c_int64(n_clades), C.c_int64(n_topologies),
+                                   C.c_int(int(kept_whole)), C.c_int64(summary_temp), C.c_int64(branches_temp), sc, ss, bs, bits, launches)
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    out = dict(zip(("R", "L", "W", "E", "Emax", "Kg", "cbits", "tbits"), sc[:8]))
+    out["wide"], out["gather"] = bool(sc[8]), bool(sc[9])
+    if (sc[11], sc[12]) != (ns, nb):
+        raise RuntimeError("TREE_SUMMARY_BUFS / TREE_BRANCHES_BUFS do not name the library's buffers")
+    for key, names, a in (("summary_slab", TREE_SUMMARY_BUFS, ss), ("branches_slab", TREE_BRANCHES_BUFS, bs)):
+        n = len(names)
+        out[key] = {"offsets": dict(zip(names, a[:n])), "sizes": dict(zip(names, a[n:2 * n])), "total": a[2 * n]}
+    out["sort_bits"] = list(bits[:sc[10]])
+    out["summary_launches"], out["branches_launches"] = launches[0], launches[1]
     return out
 
 

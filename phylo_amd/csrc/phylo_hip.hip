@@ -24,6 +24,7 @@
 #include "phylo_sweep_plan.h"
 #include "phylo_train.h"
 #include "phylo_trees.h"
+#include "phylo_trees_plan.h"
 #include "phylo_treeset.h"
 
 #include <algorithm>
@@ -2876,6 +2877,35 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
     return PHYLO_OK;
 }
 
+int phylo_debug_tree_plan(int N, int K, int G, int world, int64_t n_clades, int64_t n_topologies, int kept_whole, int64_t summary_temp,
+                          int64_t branches_temp, int64_t* scalars, int64_t* summary_slab, int64_t* branches_slab, int32_t* sort_bits,
+                          int32_t* launches) {
+    if (K < 1 || G < 1 || K % G != 0 || N > PK_MAX_TAXA || world < 1 || summary_temp < 0 || branches_temp < 0 || !scalars || !summary_slab ||
+        !branches_slab || !sort_bits || !launches)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_tree_plan: bad arguments");
+    char why[160];
+    const pt_facts f{N, K, G, world};
+    if (pt_refuses(f, why, sizeof why)) return fail(nullptr, PHYLO_EINVAL, "%s", why);
+    const pb_facts fb{N, K, G, world, n_clades, n_topologies, kept_whole != 0};
+    if (pb_refuses(fb, why, sizeof why)) return fail(nullptr, PHYLO_ESTATE, "%s", why);
+    pt_plan p = pt_plan_form(f);
+    pt_plan_slab(p, (size_t)summary_temp);
+    pb_plan q = pb_plan_form(fb);
+    pb_plan_slab(q, (size_t)branches_temp);
+    unsigned bits[PT_MAX_WORDS + 9];
+    const int n_sorts = pt_plan_sorts(p, bits);
+    for (int i = 0; i < n_sorts; ++i) sort_bits[i] = (int32_t)bits[i];
+    const int64_t sc[] = {p.R, p.L, p.W, p.E, p.Emax, p.Kg, q.cbits, q.tbits, q.wide, q.gather, n_sorts, pt_slab::NBUF, pb_slab::NBUF};
+    memcpy(scalars, sc, sizeof sc);
+    for (int i = 0; i < pt_slab::NBUF; ++i) { summary_slab[i] = (int64_t)p.slab.off[i]; summary_slab[pt_slab::NBUF + i] = (int64_t)p.slab.bytes[i]; }
+    summary_slab[2 * pt_slab::NBUF] = (int64_t)p.slab.total;
+    for (int i = 0; i < pb_slab::NBUF; ++i) { branches_slab[i] = (int64_t)q.slab.off[i]; branches_slab[pb_slab::NBUF + i] = (int64_t)q.slab.bytes[i]; }
+    branches_slab[2 * pb_slab::NBUF] = (int64_t)q.slab.total;
+    launches[0] = pt_plan_launches(p);
+    launches[1] = pb_plan_launches(q);
+    return PHYLO_OK;
+}
+
 int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,
                                    int passes_in_flight, uint32_t* mask) {
     if (N < 2 || K < 1 || G < 1 || K % G != 0 || S < 1 || TS < 1 || n_slow < 0 || coeff_wgs < 0 || !mask)
@@ -2938,389 +2968,385 @@ static int debug_device_lists_run(phylo_ctx* c, int32_t* lists, int64_t n_lists,
     return PHYLO_OK;
 }
 
-// ---- tree posterior of the last sweep (phylo_trees.h) ---------------------------------------------------
+// ---- tree posterior of the last sweep (phylo_trees.h; the form: phylo_trees_plan.h) --------------------
 extern "C++" {
-#define PT_LAUNCH(kern, n, ...)                                                                                     \
-    do {                                                                                                            \
-        hipLaunchKernelGGL(kern, dim3((unsigned)(((n) + PT_NT - 1) / PT_NT)), dim3(PT_NT), 0, c->stream, __VA_ARGS__); \
-        CHK(launch_check(c, #kern));                                                                                \
-        ++launches;                                                                                                 \
+// (key, value) pairs of a stable sort and the buffers it may write: pt_sort leaves the sorted pairs in k / v again
+template <typename KEY>
+struct pt_pairs { KEY *k, *k_alt; uint32_t *v, *v_alt; };
+// the run of a pass: the stages below read the plan and these, nothing else decides
+struct ts_run {
+    phylo_ctx* c; pt_plan plan; int launches;
+    const int32_t* child;                // the children records [R][K][2]: the sweep's, or the gathered ones
+    pt_pairs<unsigned long long> q;      // the current sort buffers
+};
+struct tb_run {
+    phylo_ctx* c; pb_plan plan; int launches;
+    const int32_t* child;
+    const double *bl, *br;               // whole-K branch lengths [R][K]
+    unsigned int* err;                   // this pass's error word: [3] of the summary's
+    pb_seg_args a;
+};
+#define PT_LAUNCH(kern, n, ...)                                                                                       \
+    do {                                                                                                              \
+        hipLaunchKernelGGL(kern, dim3((unsigned)(((n) + PT_NT - 1) / PT_NT)), dim3(PT_NT), 0, p.c->stream, __VA_ARGS__); \
+        CHK(launch_check(p.c, #kern));                                                                                \
+        ++p.launches;                                                                                                 \
     } while (0)
 
-// one stable LSD pass over n (key, value) pairs on bits [0, bits); the sorted pairs end in kin / vin
-static int ts_sort(phylo_ctx* c, unsigned long long*& kin, unsigned long long*& kout, uint32_t*& vin, uint32_t*& vout, long long n,
-                   unsigned bits, int& launches) {
-    size_t bytes = c->ts.temp_bytes;
-    HIPCHK(c, rocprim::radix_sort_pairs(c->ts.temp, bytes, kin, kout, vin, vout, (size_t)n, 0u, bits, c->stream));
-    std::swap(kin, kout);
-    std::swap(vin, vout);
+// one stable LSD pass over n pairs on bits [0, bits)
+template <typename KEY>
+static int pt_sort(phylo_ctx* c, void* temp, size_t temp_bytes, pt_pairs<KEY>& q, long long n, unsigned bits, int& launches) {
+    HIPCHK(c, rocprim::radix_sort_pairs(temp, temp_bytes, q.k, q.k_alt, q.v, q.v_alt, (size_t)n, 0u, bits, c->stream));
+    std::swap(q.k, q.k_alt); std::swap(q.v, q.v_alt);
     ++launches;
     return PHYLO_OK;
 }
 
-static int ts_scan32(phylo_ctx* c, const uint32_t* in, uint32_t* out, long long n, int& launches) {
-    size_t bytes = c->ts.temp_bytes;
-    HIPCHK(c, rocprim::inclusive_scan(c->ts.temp, bytes, in, out, (size_t)n, rocprim::plus<uint32_t>(), c->stream));
-    ++launches;
+// rocPRIM's temporary storage: the largest of what sorts of n32 / n64 pairs with 32- / 64-bit keys, inclusive scans of n_scan u32
+// and u64 and an exclusive scan of n_excl counts need (0: not issued).  The queries launch nothing.
+static int pt_temp_bytes(phylo_ctx* c, size_t n32, size_t n64, size_t n_scan, size_t n_excl, size_t& temp) {
+    uint32_t* const v = nullptr;
+    unsigned long long* const w = nullptr;
+    size_t t[5] = {0, 0, 0, 0, 0};
+    if (n32) HIPCHK(c, rocprim::radix_sort_pairs(nullptr, t[0], v, v, v, v, n32, 0u, 32u, c->stream));
+    if (n64) HIPCHK(c, rocprim::radix_sort_pairs(nullptr, t[1], w, w, v, v, n64, 0u, 64u, c->stream));
+    if (n_scan) HIPCHK(c, rocprim::inclusive_scan(nullptr, t[2], (const uint32_t*)v, v, n_scan, rocprim::plus<uint32_t>(), c->stream));
+    if (n_scan) HIPCHK(c, rocprim::inclusive_scan(nullptr, t[3], (const unsigned long long*)w, w, n_scan, rocprim::plus<unsigned long long>(), c->stream));
+    if (n_excl) HIPCHK(c, rocprim::exclusive_scan(nullptr, t[4], (const int32_t*)nullptr, v, 0u, n_excl, rocprim::plus<uint32_t>(), c->stream));
+    temp = *std::max_element(t, t + 5);
     return PHYLO_OK;
 }
 
-static int ts_scan64(phylo_ctx* c, const unsigned long long* in, unsigned long long* out, long long n, int& launches) {
-    size_t bytes = c->ts.temp_bytes;
-    HIPCHK(c, rocprim::inclusive_scan(c->ts.temp, bytes, in, out, (size_t)n, rocprim::plus<unsigned long long>(), c->stream));
-    ++launches;
-    return PHYLO_OK;
-}
+// the slab of a pass from its scratch slot, its buffers' pointers from the plan's layout (BUFS: the list that made the layout)
+#define PT_SLAB_CARVE(name, T, n) bufs.name = reinterpret_cast<T*>(base + slab.off[slab.name]);
+#define PT_CARVE(BUFS, slot, bufs_)                             \
+    do {                                                        \
+        void* base_ = nullptr;                                  \
+        CHK(scratch_get(p.c, slot, p.plan.slab.total, &base_)); \
+        char* base = (char*)base_;                              \
+        const auto& slab = p.plan.slab;                         \
+        auto& bufs = bufs_;                                     \
+        BUFS(PT_SLAB_CARVE)                                     \
+    } while (0)
 
-// Sharded: every rank's children records [R][Kloc][2] -> whole-K [R][K][2] in b.child, by the host collective in chunks
-static int ts_gather_children(phylo_ctx* c) {
-    const size_t R = (size_t)c->N - 1, K = c->K, Kl = c->Kloc, P = c->world, mine_n = R * Kl * 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<int32_t> mine(mine_n), all(P * mine_n), part, whole(R * K * 2);
-    HIPCHK(c, hipMemcpy(mine.data(), c->d_child, mine_n * 4, hipMemcpyDeviceToHost));
-    const size_t chunk = (size_t)1 << 18;                 // int32 per rank and call: 1 MiB, within the host-mediated transport's slot
+// Sharded: every rank's rows [R][Kloc][width] -> whole-K [R][K][width] in dst, by the host collective in chunks of 1 MiB per rank
+// and call (within the host-mediated transport's slot).  A collective: every rank issues the same calls in the same order.
+template <typename T>
+static int pt_gather_rows(phylo_ctx* c, const T* src, T* dst, size_t width) {
+    const size_t R = (size_t)c->N - 1, K = c->K, Kl = c->Kloc, P = c->world, row = Kl * width, mine_n = R * row;
+    std::vector<T> mine(mine_n), all(P * mine_n), part, whole(R * K * width);
+    HIPCHK(c, hipMemcpy(mine.data(), src, mine_n * sizeof(T), hipMemcpyDeviceToHost));
+    const size_t chunk = ((size_t)1 << 20) / sizeof(T);
     for (size_t o = 0; o < mine_n; o += chunk) {
         const size_t n = std::min(chunk, mine_n - o);
         part.resize(n * P);
-        const int rc = phylo_comm_allgather_host(c->comm, mine.data() + o, n * 4, part.data(), c->stream, &c->err);
+        const int rc = phylo_comm_allgather_host(c->comm, mine.data() + o, n * sizeof(T), part.data(), c->stream, &c->err);
         if (rc != PHYLO_OK) { g_last_error = c->err; return rc; }
-        for (size_t p = 0; p < P; ++p) memcpy(all.data() + p * mine_n + o, part.data() + p * n, n * 4);
+        for (size_t q = 0; q < P; ++q) memcpy(all.data() + q * mine_n + o, part.data() + q * n, n * sizeof(T));
     }
     for (size_t r = 0; r < R; ++r)
-        for (size_t p = 0; p < P; ++p)
-            memcpy(whole.data() + (r * K + p * Kl) * 2, all.data() + p * mine_n + r * Kl * 2, Kl * 2 * 4);
-    HIPCHK(c, hipMemcpy(c->ts.child, whole.data(), whole.size() * 4, hipMemcpyHostToDevice));
+        for (size_t q = 0; q < P; ++q) memcpy(whole.data() + (r * K + q * Kl) * width, all.data() + q * mine_n + r * row, row * sizeof(T));
+    HIPCHK(c, hipMemcpy(dst, whole.data(), whole.size() * sizeof(T), hipMemcpyHostToDevice));
     return PHYLO_OK;
 }
 
-static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topologies, int32_t* n_groups, phylo_stats* perf) {
+// the events of a pass (made at its first call) and the first one's record; its device time and launch count
+static int pt_time_begin(phylo_ctx* c, hipEvent_t& e0, hipEvent_t& e1) {
+    if (!e0) HIPCHK(c, hipEventCreate(&e0));
+    if (!e1) HIPCHK(c, hipEventCreate(&e1));
+    HIPCHK(c, hipEventRecord(e0, c->stream));
+    return PHYLO_OK;
+}
+static int pt_perf(phylo_ctx* c, hipEvent_t e0, hipEvent_t e1, int launches, phylo_stats* perf) {
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
+    if (perf) { *perf = phylo_stats{}; perf->sweep_ms = ms; perf->n_launches = launches; }
+    return PHYLO_OK;
+}
+
+// 1. check: the state, the refusals, the plan
+static int ts_check(ts_run& p, const int64_t* n_clades, const int32_t* n_topologies) {
+    phylo_ctx* c = p.c;
     CHK(bind(c));
     if (!n_clades || !n_topologies) return fail(c, PHYLO_EINVAL, "phylo_tree_summary: NULL count pointer");
     if (!c->swept) return fail(c, PHYLO_ESTATE, "phylo_tree_summary: no sweep has been run");
     if (c->run.active) return fail(c, PHYLO_ESTATE, "phylo_tree_summary: a sweep is being issued (phylo_sweep_finish first)");
-    const int N = c->N, K = c->K, R = N - 1, G = c->last_G, Kg = K / G, W = (N + 63) / 64, L = N - 2;
-    if (N < 3) return fail(c, PHYLO_EINVAL, "phylo_tree_summary needs N >= 3 taxa (got %d)", N);
-    const long long E = (long long)L * K, Emax = E > K ? E : K;
-    if (Emax >= 0xffffffffll) return fail(c, PHYLO_EINVAL, "phylo_tree_summary: (N - 2) K = %lld clade entries exceed 2^32 - 1", E);
-    hipStream_t s = c->stream;
-    pt_bufs& b = c->ts;
-    c->ts_done = false;
-    c->tb_done = false;
+    const pt_facts f{c->N, c->K, c->last_G, c->world};
+    char why[160];
+    if (pt_refuses(f, why, sizeof why)) return fail(c, PHYLO_EINVAL, "%s", why);
+    p.plan = pt_plan_form(f);
+    c->ts_done = c->tb_done = false;
+    return PHYLO_OK;
+}
+
+// 2. carve: every buffer from one grow-only slab (scratch slot 12); 3. gather: sharded, the children records of all K particles
+static int ts_carve_and_gather(ts_run& p) {
+    phylo_ctx* c = p.c;
     size_t temp = 0;
-    {   // rocPRIM's temporary storage: the largest of the sorts and scans below (the queries launch nothing)
-        size_t t = 0;
-        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, t, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
-                                            (uint32_t*)nullptr, (size_t)Emax, 0u, 64u, s));
-        temp = std::max(temp, t);
-        HIPCHK(c, rocprim::inclusive_scan(nullptr, t, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)Emax, rocprim::plus<uint32_t>(), s));
-        temp = std::max(temp, t);
-        HIPCHK(c, rocprim::inclusive_scan(nullptr, t, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)Emax,
-                                          rocprim::plus<unsigned long long>(), s));
-        temp = std::max(temp, t);
+    CHK(pt_temp_bytes(c, 0, (size_t)p.plan.Emax, (size_t)p.plan.Emax, 0, temp));
+    pt_plan_slab(p.plan, temp);
+    PT_CARVE(PT_SLAB_BUFS, 12, c->ts);
+    p.child = c->d_child;
+    if (p.plan.world > 1) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        CHK(pt_gather_rows(c, (const int32_t*)c->d_child, c->ts.child, 2));
+        p.child = c->ts.child;
     }
-    {   // every buffer carved from one grow-only slab (sizes first, then the pointers into it)
-        char* base = nullptr;
-        size_t off = 0;
-        auto take = [&](auto*& p, size_t n) {
-            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
-            off += (n * sizeof(*p) + 255) / 256 * 256;
-        };
-        const size_t Ks = K, Es = E, Em = Emax;
-        for (int pass = 0; pass < 2; ++pass) {
-            off = 0;
-            take(b.u, Ks); take(b.U, G); take(b.bits, (size_t)(R - 1) * W * Ks);
-            take(b.kA, Em); take(b.kB, Em); take(b.val, Em); take(b.scan, Em); take(b.weight, Em); take(b.srt, Es); take(b.hp, Ks);
-            take(b.o_cbits, Es * W); take(b.o_cw, Es); take(b.o_tw, Ks);
-            take(b.child, c->world > 1 ? (size_t)R * Ks * 2 : 0); take(b.slot, (size_t)R * Ks);
-            take(b.o_cg, Es); take(b.o_tn, Ks); take(b.o_trep, Ks); take(b.o_tg, Ks); take(b.o_ptopo, Ks);
-            take(b.vA, Em); take(b.vB, Em); take(b.flag, Em); take(b.sid, Em); take(b.cid, Es); take(b.seg_start, Em);
-            take(b.count, Em); take(b.group, Em); take(b.first, Em); take(b.tid, Ks); take(b.pos, Ks); take(b.err, 4);
-            take(b.vC, Em); take(b.vD, Em);
-            take(b.temp, temp);
-            if (pass == 0) {
-                void* p = nullptr;
-                CHK(scratch_get(c, 12, off, &p));
-                base = (char*)p;
-            }
-        }
-        b.temp_bytes = temp;
-    }
-    const int32_t* child = c->d_child;
-    if (c->world > 1) {
-        CHK(ts_gather_children(c));
-        child = b.child;
-    }
-    if (!c->ev_ts0) {
-        HIPCHK(c, hipEventCreate(&c->ev_ts0));
-        HIPCHK(c, hipEventCreate(&c->ev_ts1));
-    }
-    int launches = 0;
-    HIPCHK(c, hipEventRecord(c->ev_ts0, s));
-    HIPCHK(c, hipMemsetAsync(b.err, 0, 16, s));
-    hipLaunchKernelGGL(pt_weights, dim3(G), dim3(PT_NT), 0, s, (const double*)(c->d_logw + (size_t)(R - 1) * K), Kg, b.u, b.U);
-    CHK(launch_check(c, "pt_weights"));
-    ++launches;
-    PT_LAUNCH(pt_walk, K, child, N, K, W, b.slot, b.bits, (unsigned int*)b.err);
-    unsigned long long *kin = b.kA, *kout = b.kB;
-    uint32_t *vin = b.vA, *vout = b.vB;
-    // clades: stable passes over the bitset words, least significant first, then the group
-    for (int w = 0; w < W; ++w) {
-        PT_LAUNCH(pt_clade_keys, E, (const unsigned long long*)b.bits, w ? (const uint32_t*)vin : nullptr, E, K, W, w, Kg, kin,
-                  w ? nullptr : vin);
-        CHK(ts_sort(c, kin, kout, vin, vout, E, (unsigned)std::min(64, N - 64 * w), launches));
-    }
-    if (G > 1) {
-        PT_LAUNCH(pt_clade_keys, E, (const unsigned long long*)b.bits, (const uint32_t*)vin, E, K, W, -1, Kg, kin, nullptr);
-        CHK(ts_sort(c, kin, kout, vin, vout, E, bit_length((size_t)G - 1), launches));
-    }
-    PT_LAUNCH(pt_clade_heads, E, (const unsigned long long*)b.bits, (const uint32_t*)vin, E, K, W, Kg, (const unsigned long long*)b.u,
+    return PHYLO_OK;
+}
+
+// Keys -> stable sort: one pass over the n current pairs.  TS_WORD: an element's key is word `arg` of its clade's bitset (arg < 0:
+// its group); TS_ORDER: pt_order_keys of mode `arg` (0 weight descending, 1 group, 2 representative).  fresh: the elements are
+// 0 .. n-1 in order and the kernel writes the values; else it reads them.
+enum ts_key { TS_WORD, TS_ORDER };
+static int ts_sort_by(ts_run& p, long long n, ts_key kind, int arg, bool fresh, unsigned bits) {
+    const pt_plan& m = p.plan;
+    const pt_bufs& b = p.c->ts;
+    const uint32_t* cur = fresh ? nullptr : p.q.v;
+    uint32_t* ident = fresh ? p.q.v : nullptr;
+    if (kind == TS_WORD)
+        PT_LAUNCH(pt_clade_keys, n, (const unsigned long long*)b.bits, cur, n, m.K, m.W, arg, m.Kg, p.q.k, ident);
+    else
+        PT_LAUNCH(pt_order_keys, n, cur, n, arg, m.K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
+                  (const uint32_t*)b.first, p.q.k, ident);
+    return pt_sort(p.c, b.temp, m.temp_bytes, p.q, n, bits, p.launches);
+}
+// ... and, for a batch, the stable pass behind it that brings each group's elements together (by content / of an output order)
+static int ts_group_pass(ts_run& p, long long n, bool order) {
+    if (!p.plan.groups) return PHYLO_OK;
+    return order ? ts_sort_by(p, n, TS_ORDER, 1, false, p.plan.order_group_bits) : ts_sort_by(p, n, TS_WORD, -1, false, p.plan.group_bits);
+}
+
+// Group equal keys: the n current pairs are sorted and a heads kernel has left every run's first element in flag, every element's
+// weight in val.  Segment ids (own: per element), each segment's weight, count, group and first element; err[count_word] = segments.
+static int ts_groups(ts_run& p, long long n, uint32_t* own, int count_word) {
+    const pt_plan& m = p.plan;
+    const pt_bufs& b = p.c->ts;
+    size_t bytes = m.temp_bytes;
+    HIPCHK(p.c, rocprim::inclusive_scan(b.temp, bytes, (const uint32_t*)b.flag, b.sid, (size_t)n, rocprim::plus<uint32_t>(), p.c->stream));
+    HIPCHK(p.c, rocprim::inclusive_scan(b.temp, bytes, (const unsigned long long*)b.val, b.scan, (size_t)n, rocprim::plus<unsigned long long>(),
+                                        p.c->stream));
+    p.launches += 2;
+    PT_LAUNCH(pt_seg_ids, n, (const uint32_t*)p.q.v, (const uint32_t*)b.flag, (const uint32_t*)b.sid, n, own, b.seg_start);
+    PT_LAUNCH(pt_seg_sums, n, (const uint32_t*)p.q.v, (const uint32_t*)b.sid, (const uint32_t*)b.seg_start, (const unsigned long long*)b.scan,
+              n, m.K, m.Kg, m.G, b.weight, b.count, b.group, b.first);
+    HIPCHK(p.c, hipMemcpyAsync(b.err + count_word, b.sid + (n - 1), 4, hipMemcpyDeviceToDevice, p.c->stream));
+    return PHYLO_OK;
+}
+
+// 4. - 7. the clade table
+static int ts_clades(ts_run& p) {
+    phylo_ctx* c = p.c;
+    const pt_plan& m = p.plan;
+    pt_bufs& b = c->ts;
+    const long long E = m.E;
+    // 4. weights and walk: integer weights of the particles; every tree walked into node slots and clade bitsets
+    CHK(pt_time_begin(c, c->ev_ts0, c->ev_ts1));
+    HIPCHK(c, hipMemsetAsync(b.err, 0, 16, c->stream));
+    PT_LAUNCH(pt_weights, (long long)m.G * PT_NT, (const double*)(c->d_logw + (size_t)(m.R - 1) * m.K), m.Kg, b.u, b.U);   // (a workgroup per group)
+    PT_LAUNCH(pt_walk, m.K, p.child, m.N, m.K, m.W, b.slot, b.bits, (unsigned int*)b.err);
+    // 5. clade sort: stable passes over the bitset words, least significant first, then the group
+    p.q = {b.kA, b.kB, b.vA, b.vB};
+    for (int w = 0; w < m.W; ++w) CHK(ts_sort_by(p, E, TS_WORD, w, w == 0, m.word_bits[w]));
+    CHK(ts_group_pass(p, E, false));
+    // 6. clade groups: equal bitsets of a group are one clade (cid), with its weight
+    PT_LAUNCH(pt_clade_heads, E, (const unsigned long long*)b.bits, (const uint32_t*)p.q.v, E, m.K, m.W, m.Kg, (const unsigned long long*)b.u,
               b.flag, b.val);
-    CHK(ts_scan32(c, b.flag, b.sid, E, launches));
-    CHK(ts_scan64(c, b.val, b.scan, E, launches));
-    PT_LAUNCH(pt_seg_ids, E, (const uint32_t*)vin, (const uint32_t*)b.flag, (const uint32_t*)b.sid, E, b.cid, b.seg_start);
-    PT_LAUNCH(pt_seg_sums, E, (const uint32_t*)vin, (const uint32_t*)b.sid, (const uint32_t*)b.seg_start, (const unsigned long long*)b.scan,
-              E, K, Kg, G, b.weight, b.count, b.group, b.first);
-    HIPCHK(c, hipMemcpyAsync(b.err + 1, b.sid + (E - 1), 4, hipMemcpyDeviceToDevice, s));
-    // clade order: weight descending (the segments are in bitset order already), then the group
-    PT_LAUNCH(pt_order_keys, E, (const uint32_t*)nullptr, E, 0, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
-              (const uint32_t*)b.first, kin, vin);
-    CHK(ts_sort(c, kin, kout, vin, vout, E, 64u, launches));
-    if (G > 1) {
-        PT_LAUNCH(pt_order_keys, E, (const uint32_t*)vin, E, 1, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
-                  (const uint32_t*)b.first, kin, nullptr);
-        CHK(ts_sort(c, kin, kout, vin, vout, E, bit_length((size_t)G), launches));
-    }
-    b.cord = vin;                                          // (stays: the topology stage sorts in vC / vD)
-    PT_LAUNCH(pt_clade_out, E, (const uint32_t*)vin, (const uint32_t*)b.sid, E, K, W, (const unsigned long long*)b.bits,
+    CHK(ts_groups(p, E, b.cid, 1));
+    // 7. clade order and output: weight descending (the segments are in bitset order already), then the group
+    CHK(ts_sort_by(p, E, TS_ORDER, 0, true, m.weight_bits));
+    CHK(ts_group_pass(p, E, true));
+    b.cord = p.q.v;                                        // final here: vA or vB, by the number of passes so far
+    PT_LAUNCH(pt_clade_out, E, b.cord, (const uint32_t*)b.sid, E, m.K, m.W, (const unsigned long long*)b.bits,
               (const unsigned long long*)b.weight, (const uint32_t*)b.group, (const uint32_t*)b.first, b.o_cbits, b.o_cw, b.o_cg);
-    // topologies: each particle's clade ids sorted inside the particle, then the particles by (group, hash of that vector)
-    PT_LAUNCH(pt_topo_pairs, E, (const uint32_t*)b.cid, E, K, b.kA, b.vC);
-    {
-        size_t bytes = b.temp_bytes;
-        HIPCHK(c, rocprim::radix_sort_pairs(b.temp, bytes, b.kA, b.srt, b.vC, b.vD, (size_t)E, 0u, 32u + bit_length((size_t)K - 1), s));
-        ++launches;
-    }
-    kin = b.kA; kout = b.kB; vin = b.vC; vout = b.vD;
-    PT_LAUNCH(pt_topo_hash, K, (const unsigned long long*)b.srt, K, L, kin, vin, b.hp);
-    CHK(ts_sort(c, kin, kout, vin, vout, K, 64u, launches));
-    if (G > 1) {
-        PT_LAUNCH(pt_clade_keys, K, (const unsigned long long*)b.bits, (const uint32_t*)vin, (long long)K, K, W, -1, Kg, kin, nullptr);
-        CHK(ts_sort(c, kin, kout, vin, vout, K, bit_length((size_t)G - 1), launches));
-    }
-    PT_LAUNCH(pt_topo_heads, K, (const unsigned long long*)b.hp, (const uint32_t*)vin, (const unsigned long long*)b.srt, K, L, Kg,
+    return PHYLO_OK;
+}
+
+// 8. - 10. the topology table.  Live across these stages: u, bits, cid and cord's buffer, which is why they sort their values in
+// vC / vD; kA, kB and the segment arrays (flag .. first) are free again.  Live across the branch pass, which reads them: u, slot,
+// cid, cord, o_tn, o_ptopo, child (sharded), and err[3], its own error word.
+static int ts_topologies(ts_run& p) {
+    const pt_plan& m = p.plan;
+    const pt_bufs& b = p.c->ts;
+    const long long K = m.K;
+    // 8. in-particle sort and hash: each particle's clade ids ascending (the sorted keys stay in srt), the hash of that vector
+    p.q = {b.kA, b.srt, b.vC, b.vD};
+    PT_LAUNCH(pt_topo_pairs, m.E, (const uint32_t*)b.cid, m.E, m.K, p.q.k, p.q.v);
+    CHK(pt_sort(p.c, b.temp, m.temp_bytes, p.q, m.E, m.cid_bits, p.launches));
+    p.q = {b.kA, b.kB, b.vC, b.vD};
+    PT_LAUNCH(pt_topo_hash, K, (const unsigned long long*)b.srt, m.K, m.L, p.q.k, p.q.v, b.hp);
+    // 9. topology groups: the particles by (group, hash); equal vectors of a group are one topology (tid), with its weight
+    CHK(pt_sort(p.c, b.temp, m.temp_bytes, p.q, K, m.weight_bits, p.launches));
+    CHK(ts_group_pass(p, K, false));
+    PT_LAUNCH(pt_topo_heads, K, (const unsigned long long*)b.hp, (const uint32_t*)p.q.v, (const unsigned long long*)b.srt, m.K, m.L, m.Kg,
               (const unsigned long long*)b.u, b.flag, b.val, (unsigned int*)b.err);
-    CHK(ts_scan32(c, b.flag, b.sid, K, launches));
-    CHK(ts_scan64(c, b.val, b.scan, K, launches));
-    PT_LAUNCH(pt_seg_ids, K, (const uint32_t*)vin, (const uint32_t*)b.flag, (const uint32_t*)b.sid, (long long)K, b.tid, b.seg_start);
-    PT_LAUNCH(pt_seg_sums, K, (const uint32_t*)vin, (const uint32_t*)b.sid, (const uint32_t*)b.seg_start, (const unsigned long long*)b.scan,
-              (long long)K, K, Kg, G, b.weight, b.count, b.group, b.first);
-    HIPCHK(c, hipMemcpyAsync(b.err + 2, b.sid + (K - 1), 4, hipMemcpyDeviceToDevice, s));
-    // topology order: representative ascending, then weight descending, then the group
-    PT_LAUNCH(pt_order_keys, K, (const uint32_t*)nullptr, (long long)K, 2, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
-              (const uint32_t*)b.first, kin, vin);
-    CHK(ts_sort(c, kin, kout, vin, vout, K, bit_length((size_t)K), launches));
-    PT_LAUNCH(pt_order_keys, K, (const uint32_t*)vin, (long long)K, 0, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
-              (const uint32_t*)b.first, kin, nullptr);
-    CHK(ts_sort(c, kin, kout, vin, vout, K, 64u, launches));
-    if (G > 1) {
-        PT_LAUNCH(pt_order_keys, K, (const uint32_t*)vin, (long long)K, 1, K, (const unsigned long long*)b.weight, (const uint32_t*)b.group,
-                  (const uint32_t*)b.first, kin, nullptr);
-        CHK(ts_sort(c, kin, kout, vin, vout, K, bit_length((size_t)G), launches));
-    }
-    PT_LAUNCH(pt_topo_out, K, (const uint32_t*)vin, (const uint32_t*)b.sid, K, Kg, (const unsigned long long*)b.weight,
+    CHK(ts_groups(p, K, b.tid, 2));
+    // 10. topology order and output: representative ascending, then weight descending, then the group
+    CHK(ts_sort_by(p, K, TS_ORDER, 2, true, m.rep_bits));
+    CHK(ts_sort_by(p, K, TS_ORDER, 0, false, m.weight_bits));
+    CHK(ts_group_pass(p, K, true));
+    PT_LAUNCH(pt_topo_out, K, (const uint32_t*)p.q.v, (const uint32_t*)b.sid, m.K, m.Kg, (const unsigned long long*)b.weight,
               (const uint32_t*)b.count, (const uint32_t*)b.group, (const uint32_t*)b.first, b.o_tw, b.o_tn, b.o_trep, b.o_tg);
-    PT_LAUNCH(pt_invert, K, (const uint32_t*)vin, (long long)K, b.pos);
-    PT_LAUNCH(pt_particle_topo, K, (const uint32_t*)b.tid, (const uint32_t*)b.pos, K, b.o_ptopo);
-    HIPCHK(c, hipEventRecord(c->ev_ts1, s));
+    PT_LAUNCH(pt_invert, K, (const uint32_t*)p.q.v, K, b.pos);
+    PT_LAUNCH(pt_particle_topo, K, (const uint32_t*)b.tid, (const uint32_t*)b.pos, m.K, b.o_ptopo);
+    return PHYLO_OK;
+}
+
+// 11. finish: the error words, the sweep's own timeout word, the counts
+static int ts_finish(ts_run& p, int64_t* n_clades, int32_t* n_topologies, int32_t* n_groups, phylo_stats* perf) {
+    phylo_ctx* c = p.c;
+    HIPCHK(c, hipEventRecord(c->ev_ts1, c->stream));
     uint32_t hs[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(hs, b.err, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    {   // the summarised sweep's own timeout word (read, not cleared: phylo_sweep_fetch still reports it)
-        unsigned int tmo = 0;
-        if (c->last_graph && c->h_pub) tmo = c->h_pub[2];
-        else HIPCHK(c, hipMemcpy(&tmo, c->d_counter + 1, sizeof tmo, hipMemcpyDeviceToHost));
-        if (tmo) return fail(c, PHYLO_EHIP, "phylo_tree_summary: the sweep timed out in a bounded wait between workgroups; its results are invalid");
-    }
+    HIPCHK(c, hipMemcpyAsync(hs, c->ts.err, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    unsigned int tmo = 0;                                  // the summarised sweep's own timeout word (read, not cleared: the fetch reports it)
+    if (c->last_graph && c->h_pub) tmo = c->h_pub[2];
+    else HIPCHK(c, hipMemcpy(&tmo, c->d_counter + 1, sizeof tmo, hipMemcpyDeviceToHost));
+    if (tmo) return fail(c, PHYLO_EHIP, "phylo_tree_summary: the sweep timed out in a bounded wait between workgroups; its results are invalid");
     if (hs[0] & PT_ERR_TREE) return fail(c, PHYLO_EHIP, "phylo_tree_summary: the sweep's children records do not form one tree per particle");
     if (hs[0] & PT_ERR_COLLISION)
         return fail(c, PHYLO_EHIP, "phylo_tree_summary: two different topologies share a 64-bit routing hash (not merged; summary refused)");
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_ts0, c->ev_ts1));
-    c->ts_nc = hs[1];
-    c->ts_nt = (int)hs[2];
-    c->ts_G = G;
+    CHK(pt_perf(c, c->ev_ts0, c->ev_ts1, p.launches, perf));
+    *n_clades = c->ts_nc = hs[1];
+    *n_topologies = c->ts_nt = (int)hs[2];
+    c->ts_G = p.plan.G;
+    if (n_groups) *n_groups = p.plan.G;
     c->ts_serial = c->sweep_serial;
     c->ts_done = true;
-    *n_clades = hs[1];
-    *n_topologies = (int32_t)hs[2];
-    if (n_groups) *n_groups = G;
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms;
-        st.n_launches = launches;
-        *perf = st;
-    }
     return PHYLO_OK;
 }
 
-// Sharded: every rank's rows [R][Kloc] of one branch-length array -> whole-K [R][K] in dst, by the host collective in chunks
-static int tb_gather_rows(phylo_ctx* c, const double* src, double* dst) {
-    const size_t R = (size_t)c->N - 1, K = c->K, Kl = c->Kloc, P = c->world, mine_n = R * Kl;
-    std::vector<double> mine(mine_n), all(P * mine_n), part, whole(R * K);
-    HIPCHK(c, hipMemcpy(mine.data(), src, mine_n * 8, hipMemcpyDeviceToHost));
-    const size_t chunk = (size_t)1 << 17;                 // doubles per rank and call: 1 MiB, as ts_gather_children
-    for (size_t o = 0; o < mine_n; o += chunk) {
-        const size_t n = std::min(chunk, mine_n - o);
-        part.resize(n * P);
-        const int rc = phylo_comm_allgather_host(c->comm, mine.data() + o, n * 8, part.data(), c->stream, &c->err);
-        if (rc != PHYLO_OK) { g_last_error = c->err; return rc; }
-        for (size_t p = 0; p < P; ++p) memcpy(all.data() + p * mine_n + o, part.data() + p * n, n * 8);
-    }
-    for (size_t r = 0; r < R; ++r)
-        for (size_t p = 0; p < P; ++p) memcpy(whole.data() + r * K + p * Kl, all.data() + p * mine_n + r * Kl, Kl * 8);
-    HIPCHK(c, hipMemcpy(dst, whole.data(), whole.size() * 8, hipMemcpyHostToDevice));
-    return PHYLO_OK;
+static int tree_summary_impl(phylo_ctx* c, int64_t* n_clades, int32_t* n_topologies, int32_t* n_groups, phylo_stats* perf) {
+    ts_run p{c};
+    CHK(ts_check(p, n_clades, n_topologies));
+    CHK(ts_carve_and_gather(p));
+    CHK(ts_clades(p));
+    CHK(ts_topologies(p));
+    return ts_finish(p, n_clades, n_topologies, n_groups, perf);
 }
 
-template <typename KEY>
-static int tb_sort(phylo_ctx* c, KEY* kin, KEY* kout, uint32_t* vin, uint32_t* vout, long long n, unsigned bits, int& launches) {
-    size_t bytes = c->tb.temp_bytes;
-    HIPCHK(c, rocprim::radix_sort_pairs(c->tb.temp, bytes, kin, kout, vin, vout, (size_t)n, 0u, bits, c->stream));
-    ++launches;
-    return PHYLO_OK;
-}
-
-#define PB_SEGS(family, KEY, args, tkey)                                                                                           \
-    do {                                                                                                                           \
-        hipLaunchKernelGGL((pb_seg_sums<family, KEY>), dim3((unsigned)(((args).n_seg + PT_NT / 64 - 1) / (PT_NT / 64))), dim3(PT_NT), 0, \
-                           c->stream, args, tkey);                                                                                 \
-        CHK(launch_check(c, "pb_seg_sums"));                                                                                       \
-        ++launches;                                                                                                                \
-    } while (0)
-
-static int tree_branches_impl(phylo_ctx* c, phylo_stats* perf) {
+// ---- the branch pass over the last summary
+// 1. check: the state (a new sweep makes the summary stale), the refusal, the plan
+static int tb_check(tb_run& p) {
+    phylo_ctx* c = p.c;
     CHK(bind(c));
     if (c->run.active) return fail(c, PHYLO_ESTATE, "phylo_tree_branches: a sweep is being issued (phylo_sweep_finish first)");
     if (!c->swept || !c->ts_done || c->ts_serial != c->sweep_serial)
         return fail(c, PHYLO_ESTATE, "phylo_tree_branches: no phylo_tree_summary of the last sweep (a new sweep needs a new summary)");
-    const int N = c->N, K = c->K, R = N - 1, G = c->ts_G, Kg = K / G, L = N - 2;
-    const long long E = (long long)L * K, nc = c->ts_nc, nt = c->ts_nt, nb = 2LL * N - 2;
-    if (nc < 1 || nt < 1 || nc > E || nt > K) return fail(c, PHYLO_ESTATE, "phylo_tree_branches: the summary holds no rows");
-    const unsigned cbits = std::max(1u, (unsigned)bit_length((size_t)nc - 1)), tbits = std::max(1u, (unsigned)bit_length((size_t)nt - 1));
-    const bool wide = cbits + tbits > 32;                  // (topology, clade) keys: 32 bits hold them on all but huge tables
-    hipStream_t s = c->stream;
-    const pt_bufs& b = c->ts;
-    pb_bufs& t = c->tb;
+    const pb_facts f{c->N, c->K, c->ts_G, c->world, c->ts_nc, c->ts_nt, c->last_graph && c->d_gbl && c->d_gbr};
+    char why[160];
+    if (pb_refuses(f, why, sizeof why)) return fail(c, PHYLO_ESTATE, "%s", why);
+    p.plan = pb_plan_form(f);
     c->tb_done = false;
-    const bool gather = c->world > 1 && !(c->last_graph && c->d_gbl && c->d_gbr);
+    return PHYLO_OK;
+}
+
+// 2. carve: every buffer from one grow-only slab (scratch slot 13); 3. gather: whole-K children records and branch lengths.  Sharded:
+// the summary's gathered children and what a kept graph's graph_gather made whole already, or two collectives here (bl, then br)
+static int tb_carve_and_gather(tb_run& p) {
+    phylo_ctx* c = p.c;
     size_t temp = 0;
-    {
-        size_t q = 0;
-        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, q, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                            (size_t)E, 0u, 32u, s));
-        temp = std::max(temp, q);
-        HIPCHK(c, rocprim::radix_sort_pairs(nullptr, q, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
-                                            (uint32_t*)nullptr, (size_t)E, 0u, 64u, s));
-        if (wide) temp = std::max(temp, q);
-        HIPCHK(c, rocprim::exclusive_scan(nullptr, q, (const int32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)nt, rocprim::plus<uint32_t>(), s));
-        temp = std::max(temp, q);
-    }
-    {
-        char* base = nullptr;
-        size_t off = 0;
-        auto take = [&](auto*& p, size_t n) {
-            p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
-            off += (n * sizeof(*p) + 255) / 256 * 256;
-        };
-        const size_t Ks = K, Es = E;
-        for (int pass = 0; pass < 2; ++pass) {
-            off = 0;
-            take(t.ebr, (size_t)(R - 1) * Ks); take(t.lbr, (size_t)N * Ks);
-            take(t.gbl, gather ? (size_t)R * Ks : 0); take(t.gbr, gather ? (size_t)R * Ks : 0);
-            take(t.o_cs, (size_t)nc * 4); take(t.o_ls, (size_t)G * N * 4); take(t.o_ts, (size_t)nt * nb * 4);
-            take(t.wA, wide ? Es : 0); take(t.wB, wide ? Es : 0);
-            take(t.cpos, Es); take(t.kA, Es); take(t.kB, Es); take(t.vA, Es); take(t.vB, Es);
-            take(t.cstart, (size_t)nc + 1); take(t.toff, (size_t)nt); take(t.o_tc, (size_t)nt * L);
-            take(t.temp, temp);
-            if (pass == 0) {
-                void* p = nullptr;
-                CHK(scratch_get(c, 13, off, &p));
-                base = (char*)p;
-            }
-        }
-        t.temp_bytes = temp;
-    }
-    const int32_t* child = c->world > 1 ? b.child : c->d_child;
-    const double *bl = c->d_bl, *br = c->d_br;
-    if (c->world > 1) {
-        if (gather) {                                      // a collective, like the summary's gather of the children records
-            HIPCHK(c, hipStreamSynchronize(s));
-            CHK(tb_gather_rows(c, c->d_bl, t.gbl));
-            CHK(tb_gather_rows(c, c->d_br, t.gbr));
-            bl = t.gbl; br = t.gbr;
-        } else {                                           // the sweep kept its graph: graph_gather made them whole already
-            bl = c->d_gbl; br = c->d_gbr;
-        }
-    }
-    if (!c->ev_tb0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tb0));
-        HIPCHK(c, hipEventCreate(&c->ev_tb1));
-    }
-    int launches = 0;
-    unsigned int* err = (unsigned int*)b.err + 3;          // the summary's error words: [3] is this pass's
-    HIPCHK(c, hipEventRecord(c->ev_tb0, s));
-    HIPCHK(c, hipMemsetAsync(err, 0, 4, s));
-    PT_LAUNCH(pb_walk, K, child, (const int32_t*)b.slot, bl, br, N, K, t.ebr, t.lbr, err);
-    // clade rows: the entries sorted by their clade's output row (one narrow stable pass over ascending entries)
-    PT_LAUNCH(pt_invert, E, b.cord, E, t.cpos);
-    PT_LAUNCH(pb_entry_keys<uint32_t>, E, (const uint32_t*)b.cid, (const uint32_t*)t.cpos, (const int32_t*)nullptr, E, K, L, 0, t.kA, t.vA);
-    CHK(tb_sort(c, t.kA, t.kB, t.vA, t.vB, E, cbits, launches));
-    t.cperm = t.vB;
-    PT_LAUNCH(pb_clade_starts, E, (const uint32_t*)t.kB, E, (uint32_t)nc, t.cstart);
-    pb_seg_args a{};
-    a.u = b.u; a.ebr = t.ebr; a.lbr = t.lbr; a.cperm = t.cperm; a.cstart = t.cstart; a.toff = t.toff; a.tn = b.o_tn; a.o_tc = t.o_tc;
-    a.N = N; a.K = K; a.Kg = Kg; a.cmask_bits = (int)cbits;
-    a.out = t.o_cs; a.n_seg = nc;
-    PB_SEGS(PB_CLADES, uint32_t, a, (const uint32_t*)nullptr);
-    a.out = t.o_ls; a.n_seg = (long long)G * N;
-    PB_SEGS(PB_LEAVES, uint32_t, a, (const uint32_t*)nullptr);
-    // topology rows: the entries, particle-major, sorted by (topology row, clade row); row t's runs start at (N - 2) toff[t]
-    {
-        size_t bytes = t.temp_bytes;
-        HIPCHK(c, rocprim::exclusive_scan(t.temp, bytes, (const int32_t*)b.o_tn, t.toff, 0u, (size_t)nt, rocprim::plus<uint32_t>(), s));
-        ++launches;
-    }
-    a.out = t.o_ts; a.n_seg = nt * nb;
-    if (wide) {
-        PT_LAUNCH(pb_entry_keys<unsigned long long>, E, (const uint32_t*)b.cid, (const uint32_t*)t.cpos, (const int32_t*)b.o_ptopo, E, K, L,
-                  (int)cbits, t.wA, t.vA);
-        CHK(tb_sort(c, t.wA, t.wB, t.vA, t.kA, E, cbits + tbits, launches));
-        t.tperm = a.tperm = t.kA;
-        PB_SEGS(PB_TOPOS, unsigned long long, a, (const unsigned long long*)t.wB);
-    } else {
-        PT_LAUNCH(pb_entry_keys<uint32_t>, E, (const uint32_t*)b.cid, (const uint32_t*)t.cpos, (const int32_t*)b.o_ptopo, E, K, L, (int)cbits,
-                  t.kA, t.vA);
-        CHK(tb_sort(c, t.kA, t.kB, t.vA, t.cpos, E, cbits + tbits, launches));   // (cpos is free from here: the sorted entries)
-        t.tperm = a.tperm = t.cpos;
-        PB_SEGS(PB_TOPOS, uint32_t, a, (const uint32_t*)t.kB);
-    }
-    HIPCHK(c, hipEventRecord(c->ev_tb1, s));
-    unsigned int herr = 0;
-    HIPCHK(c, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (herr & PT_ERR_TREE) return fail(c, PHYLO_EHIP, "phylo_tree_branches: the sweep's children records do not form one tree per particle");
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tb0, c->ev_tb1));
-    c->tb_done = true;
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms;
-        st.n_launches = launches;
-        *perf = st;
+    CHK(pt_temp_bytes(c, (size_t)p.plan.E, p.plan.wide ? (size_t)p.plan.E : 0, 0, (size_t)p.plan.nt, temp));
+    pb_plan_slab(p.plan, temp);
+    PT_CARVE(PB_SLAB_BUFS, 13, c->tb);
+    p.child = c->d_child; p.bl = c->d_bl; p.br = c->d_br;
+    if (p.plan.world == 1) return PHYLO_OK;
+    p.child = c->ts.child; p.bl = c->d_gbl; p.br = c->d_gbr;
+    if (p.plan.gather) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        CHK(pt_gather_rows(c, (const double*)c->d_bl, c->tb.gbl, 1));
+        CHK(pt_gather_rows(c, (const double*)c->d_br, c->tb.gbr, 1));
+        p.bl = c->tb.gbl; p.br = c->tb.gbr;
     }
     return PHYLO_OK;
 }
-#undef PB_SEGS
+
+template <int family, typename KEY>
+static int tb_seg_sums(tb_run& p, double* out, long long n_seg, const KEY* tkey) {
+    p.a.out = out; p.a.n_seg = n_seg;
+    hipLaunchKernelGGL((pb_seg_sums<family, KEY>), dim3((unsigned)((n_seg + PT_NT / 64 - 1) / (PT_NT / 64))), dim3(PT_NT), 0, p.c->stream, p.a,
+                       tkey);
+    CHK(launch_check(p.c, "pb_seg_sums"));
+    ++p.launches;
+    return PHYLO_OK;
+}
+
+// 4. - 6. the branch above every entry and leaf; the clade rows; the leaf rows
+static int tb_clade_and_leaf_rows(tb_run& p) {
+    phylo_ctx* c = p.c;
+    const pb_plan& m = p.plan;
+    const pt_bufs& b = c->ts;
+    pb_bufs& t = c->tb;
+    p.err = (unsigned int*)b.err + 3;                      // 4. walk
+    CHK(pt_time_begin(c, c->ev_tb0, c->ev_tb1));
+    HIPCHK(c, hipMemsetAsync(p.err, 0, 4, c->stream));
+    PT_LAUNCH(pb_walk, m.K, p.child, (const int32_t*)b.slot, p.bl, p.br, m.N, m.K, t.ebr, t.lbr, p.err);
+    // 5. clade rows: the entries sorted by their clade's output row (one narrow stable pass over ascending entries), then the sums
+    PT_LAUNCH(pt_invert, m.E, b.cord, m.E, t.cpos);
+    pt_pairs<uint32_t> q{t.kA, t.kB, t.vA, t.vB};
+    PT_LAUNCH(pb_entry_keys<uint32_t>, m.E, (const uint32_t*)b.cid, (const uint32_t*)t.cpos, (const int32_t*)nullptr, m.E, m.K, m.L, 0, q.k, q.v);
+    CHK(pt_sort(c, t.temp, m.temp_bytes, q, m.E, m.cbits, p.launches));
+    t.cperm = q.v;
+    PT_LAUNCH(pb_clade_starts, m.E, (const uint32_t*)q.k, m.E, (uint32_t)m.nc, t.cstart);
+    pb_seg_args& a = p.a;
+    a.u = b.u; a.ebr = t.ebr; a.lbr = t.lbr; a.cperm = t.cperm; a.cstart = t.cstart; a.toff = t.toff; a.tn = b.o_tn; a.o_tc = t.o_tc;
+    a.N = m.N; a.K = m.K; a.Kg = m.Kg; a.cmask_bits = (int)m.cbits;
+    CHK(tb_seg_sums<PB_CLADES>(p, t.o_cs, m.nc, (const uint32_t*)nullptr));
+    // 6. leaf rows
+    return tb_seg_sums<PB_LEAVES>(p, t.o_ls, (long long)m.G * m.N, (const uint32_t*)nullptr);
+}
+
+// the entries, particle-major, sorted by (topology row, clade row) keys of one width; tperm = the sorted entries
+template <typename KEY>
+static int tb_topo_sums(tb_run& p, pt_pairs<KEY> q) {
+    const pb_plan& m = p.plan;
+    pb_bufs& t = p.c->tb;
+    PT_LAUNCH(pb_entry_keys<KEY>, m.E, (const uint32_t*)p.c->ts.cid, (const uint32_t*)t.cpos, (const int32_t*)p.c->ts.o_ptopo, m.E, m.K, m.L,
+              (int)m.cbits, q.k, q.v);
+    CHK(pt_sort(p.c, t.temp, m.temp_bytes, q, m.E, m.cbits + m.tbits, p.launches));
+    t.tperm = p.a.tperm = q.v;
+    return tb_seg_sums<PB_TOPOS>(p, t.o_ts, m.nt * m.nb, (const KEY*)q.k);
+}
+
+// 7. topology rows: row t's runs start at (N - 2) toff[t]
+static int tb_topo_rows(tb_run& p) {
+    const pb_plan& m = p.plan;
+    pb_bufs& t = p.c->tb;
+    size_t bytes = m.temp_bytes;
+    HIPCHK(p.c, rocprim::exclusive_scan(t.temp, bytes, (const int32_t*)p.c->ts.o_tn, t.toff, 0u, (size_t)m.nt, rocprim::plus<uint32_t>(),
+                                        p.c->stream));
+    ++p.launches;
+    // Buffers that are free by now take the sorted entries (tperm; cperm in vB stays): cpos in the narrow form, whose last reader is
+    // the key kernel ahead of the sort; kA in the wide form, whose keys are in wA / wB.
+    uint32_t* const tperm_narrow = t.cpos;
+    uint32_t* const tperm_wide = t.kA;
+    if (m.wide) return tb_topo_sums(p, pt_pairs<unsigned long long>{t.wA, t.wB, t.vA, tperm_wide});
+    return tb_topo_sums(p, pt_pairs<uint32_t>{t.kA, t.kB, t.vA, tperm_narrow});
+}
+
+// 8. finish: the error word
+static int tb_finish(tb_run& p, phylo_stats* perf) {
+    phylo_ctx* c = p.c;
+    HIPCHK(c, hipEventRecord(c->ev_tb1, c->stream));
+    unsigned int herr = 0;
+    HIPCHK(c, hipMemcpyAsync(&herr, p.err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (herr & PT_ERR_TREE) return fail(c, PHYLO_EHIP, "phylo_tree_branches: the sweep's children records do not form one tree per particle");
+    CHK(pt_perf(c, c->ev_tb0, c->ev_tb1, p.launches, perf));
+    c->tb_done = true;
+    return PHYLO_OK;
+}
+
+static int tree_branches_impl(phylo_ctx* c, phylo_stats* perf) {
+    tb_run p{c};
+    CHK(tb_check(p));
+    CHK(tb_carve_and_gather(p));
+    CHK(tb_clade_and_leaf_rows(p));
+    CHK(tb_topo_rows(p));
+    return tb_finish(p, perf);
+}
+#undef PT_CARVE
+#undef PT_SLAB_CARVE
 #undef PT_LAUNCH
 }  // extern "C++"
 

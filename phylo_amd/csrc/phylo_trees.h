@@ -18,7 +18,7 @@
 #define PT_NT 256
 enum { PT_ERR_TREE = 1, PT_ERR_COLLISION = 2 };
 
-// device buffers of one summary, carved from one slab (phylo_hip.hip: tree_summary_impl); the o_* tables are what the fetch reads
+// device buffers of one summary, carved from one slab (layout: phylo_trees_plan.h); the o_* tables are what the fetch reads
 struct pt_bufs {
     unsigned long long *u = nullptr, *U = nullptr, *bits = nullptr, *kA = nullptr, *kB = nullptr, *val = nullptr, *scan = nullptr;
     unsigned long long *weight = nullptr, *srt = nullptr, *hp = nullptr, *o_cbits = nullptr, *o_cw = nullptr, *o_tw = nullptr;
@@ -29,7 +29,6 @@ struct pt_bufs {
     const uint32_t* cord = nullptr;          // clade segment of every output row (phylo_tree_branches inverts it)
     uint32_t* err = nullptr;                 // [0] PT_ERR_* bits, [1] clade count, [2] topology count
     unsigned char* temp = nullptr;           // rocPRIM's temporary storage
-    size_t temp_bytes = 0;
 };
 
 // u_k = floor(exp(logw[R-1][k] - max_g) 2^44) per group g of Kg columns (the resampling contract's integer weights, same NaN /
@@ -305,7 +304,6 @@ struct pb_bufs {
     double *o_cs = nullptr, *o_ls = nullptr, *o_ts = nullptr;   // [n_clades][4], [G][N][4], [n_topologies][2N-2][4]
     int32_t* o_tc = nullptr;                 // [n_topologies][N-2] clade rows (over all groups; the fetch subtracts the group's first)
     unsigned char* temp = nullptr;
-    size_t temp_bytes = 0;
 };
 
 // One thread per final particle k: the branch above each child of the node of every rank event of its tree.  slot was validated
