@@ -156,8 +156,8 @@ SWEEP_PLAN_SWITCHES = ("eager_nodes", "rehearse_sharded", "replicated_book", "jc
 def debug_sweep_plan(N, K, S, K_local=None, G=1, M=1, world=1, transport=False, flags=0, switches=()):
     """The form the forward sweep's launch path takes for a shape, the flags of a sweep and the switches (names of
     SWEEP_PLAN_SWITCHES: three environment switches, then three facts of the context) -- no GPU needed: a dict of the booleans of
-    SWEEP_PLAN_BITS, 'book_width', 'mask' and 'launches' (what stats['n_launches'] counts: [0] the begin, [r + 1] rank event r,
-    [N] the finish)."""
+    SWEEP_PLAN_BITS, 'book_width' (lanes per particle of the bookkeeping: 8, 16, 32 or 64; 0 = no bookkeeping launch, the twisted
+    proposal), 'mask' and 'launches' (what stats['n_launches'] counts: [0] the begin, [r + 1] rank event r, [N] the finish)."""
     lib = load()
     sw = sum(1 << SWEEP_PLAN_SWITCHES.index(name) for name in switches)
     mask = C.c_uint32(0)

@@ -1654,7 +1654,7 @@ static int step_twist(phylo_ctx* c, const pk_rank_args& b) {
 }
 
 // The bookkeeping of a rank event at plan.book_width lanes per particle: with the adopted nodes in the same launch
-// (pk_rank_book_mat, r > 0), else over the root tables this rank advances (pk_rank_book_packed, or pk_rank_book's wave per particle)
+// (pk_rank_book_mat, r > 0), else over the root tables this rank advances (pk_rank_book_packed)
 static int step_book(phylo_ctx* c, const pk_rank_args& b) {
     const sweep_plan& p = c->run.plan;
     const int K = c->K, w = p.book_width;
@@ -1663,19 +1663,24 @@ static int step_book(phylo_ctx* c, const pk_rank_args& b) {
         const int lp = w < 16 ? 16 : w, per = PK_COLS / lp;   // particles per workgroup; behind them, a workgroup per particle's node
         const int bb = cdiv(K, per);
         const dim3 grid(bb + K);
-        if (lp == 16) hipLaunchKernelGGL(pk_rank_book_mat<16>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb);
-        else if (lp == 32) hipLaunchKernelGGL(pk_rank_book_mat<32>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb);
-        else hipLaunchKernelGGL(pk_rank_book_mat<64>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb);
+        switch (lp) {
+        case 16: hipLaunchKernelGGL(pk_rank_book_mat<16>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb); break;
+        case 32: hipLaunchKernelGGL(pk_rank_book_mat<32>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb); break;
+        case 64: hipLaunchKernelGGL(pk_rank_book_mat<64>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb); break;
+        default: return fail(c, PHYLO_ESTATE, "step_book: no pk_rank_book_mat of %d lanes", lp);
+        }
         return launch_check(c, "pk_rank_book_mat");
     }
-    const int nbook = p.local_book ? c->Kloc : K;
-    const int per = (w == 8 || w == 16 || w == 32) ? 64 / w : 1;                 // particles per wave
-    const dim3 grid(cdiv(nbook, per));
-    if (w == 8) hipLaunchKernelGGL(pk_rank_book_packed<8>, grid, dim3(64), lds * per, c->stream, b);
-    else if (w == 16) hipLaunchKernelGGL(pk_rank_book_packed<16>, grid, dim3(64), lds * per, c->stream, b);
-    else if (w == 32) hipLaunchKernelGGL(pk_rank_book_packed<32>, grid, dim3(64), lds * per, c->stream, b);
-    else hipLaunchKernelGGL(pk_rank_book, grid, dim3(64), lds * per, c->stream, b);
-    return launch_check(c, "pk_rank_book");
+    const int per = 64 / (w > 0 ? w : 64);                                       // particles per wave
+    const dim3 grid(cdiv(p.local_book ? c->Kloc : K, per));
+    switch (w) {
+    case 8: hipLaunchKernelGGL(pk_rank_book_packed<8>, grid, dim3(64), lds * per, c->stream, b); break;
+    case 16: hipLaunchKernelGGL(pk_rank_book_packed<16>, grid, dim3(64), lds * per, c->stream, b); break;
+    case 32: hipLaunchKernelGGL(pk_rank_book_packed<32>, grid, dim3(64), lds * per, c->stream, b); break;
+    case 64: hipLaunchKernelGGL(pk_rank_book_packed<64>, grid, dim3(64), lds * per, c->stream, b); break;
+    default: return fail(c, PHYLO_ESTATE, "step_book: no pk_rank_book_packed of %d lanes", w);
+    }
+    return launch_check(c, "pk_rank_book_packed");
 }
 
 // The merge of a rank event: one wave per (particle, site tile) when nothing is stored -- from the merge records, or resolving

@@ -21,7 +21,7 @@ enum { AUX_SUM_REM = 0, AUX_FPRIOR, AUX_LPRIOR, AUX_RPRIOR, AUX_LL_TILDE, AUX_PA
 #define PK_REC 16            // 64-bit slots per record
 enum { REC_BASE_L = PK_AUX, REC_BASE_R, REC_NODELL, REC_ROOTLL, REC_LL, REC_LOGW, REC_FLAGS /* bit 0 / 1: left / right child is a coded leaf */ };
 #define PK_REC_SLOTS (REC_FLAGS + 1)
-static_assert(PK_REC_SLOTS <= PK_REC && PK_REC_SLOTS <= 16, "one lane per slot: pk_rank_book_mat and pk_rank_book write the record with the first 16 lanes of a particle");
+static_assert(PK_REC_SLOTS <= PK_REC && PK_REC_SLOTS <= 16, "one lane per slot: with 16 lanes or more per particle the bookkeeping writes the record in one trip (pk_book_tail)");
 
 // ------------------------------------------------------------------------------------------------
 // Canonical sum over 256 columns of a workgroup (the sum over PARTICLES of the resampling weights: element k
@@ -594,33 +594,6 @@ __device__ __forceinline__ int pk_cdf_search(const uint64_t* __restrict__ cdf, i
     return lo < K ? lo : K - 1;
 }
 
-// the same search by one wave: 64 probes per step.  The first round's probe addresses do not depend on the
-// threshold, so `total` and the coarse probes travel together: 2 dependent round trips for K <= 4096.
-__device__ __forceinline__ int pk_cdf_search_wave(const uint64_t* cdf, int K, uint64_t R, int lane) {
-    int lo = 0, hi = K;             // invariant: answer in [lo, hi), cdf[hi-1] > thr
-    int step = (K + 63) >> 6;
-    int p = (lane + 1) * step - 1;
-    if (p > K - 1) p = K - 1;
-    const uint64_t total = cdf[K - 1];
-    uint64_t c = cdf[p];
-    const uint64_t thr = pm_mulhi64(R, total);
-    for (;;) {
-        const unsigned long long mask = __ballot(c > thr);
-        const int f = mask ? __ffsll((long long)mask) - 1 : 63;
-        int pf = lo + (f + 1) * step - 1;
-        if (pf > hi - 1) pf = hi - 1;
-        lo = lo + f * step;
-        hi = pf + 1;
-        if (lo >= hi) lo = hi - 1;
-        if (hi - lo <= 1) break;
-        step = (hi - lo + 63) >> 6;
-        p = lo + (lane + 1) * step - 1;
-        if (p > hi - 1) p = hi - 1;
-        c = cdf[p];
-    }
-    return lo;
-}
-
 __global__ void pk_resample_search(const uint64_t* __restrict__ cdf, int K, int n_draw, int k0, uint64_t seed,
                                    uint32_t step, int64_t* __restrict__ idx) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -769,177 +742,14 @@ __device__ __forceinline__ void pk_rec_write(const pk_rank_args& a, int k, int k
     a.rec[(size_t)k * PK_REC + t] = v;
 }
 
-// Bookkeeping of one rank event for ONE particle (global index kg), by the first wave of a workgroup;
-// every thread of the workgroup must call it (it contains workgroup barriers).
-//   resampling index (vcsmc.py:285) -> adoption of the ancestor's root table (the tf.gather of :286-288, on
-//   integer tables instead of partial likelihoods) -> uniform pair pick (:303-305) -> new root table
-//   (:361-373) -> the scalar terms of the weight that do not depend on the new node (:376-392).
-// `local`: the particle belongs to this rank's shard (float terms and outputs are produced).
-// Dependent global round trips: {cdf total + coarse probes, branch history, ldf table} -> {fine probes}
-// -> {ancestor's table rows, its log-likelihood}; everything after that runs out of LDS.
-__device__ __forceinline__ void pk_book_particle(const pk_rank_args& a, int kg, bool local, const pk_book_lds& L) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const bool w0 = tid < 64;
-    const int n = a.n, N = a.N, k = kg - a.k0;
-    const int grp = a.group_seeds ? kg / a.Kg : 0;       // batched independent sweeps: my group, its seed, my index in it
-    const int gbase = grp * a.Kg;
-    const uint64_t seed = a.group_seeds ? a.group_seeds[grp] : a.seed;
-    const uint32_t kin = (uint32_t)(kg - gbase);
-    if (w0) {
-        // independent of the resampling outcome: issue first (slots >= 64 are copied further down)
-        const double hb_l0 = (local && lane <= a.r) ? a.bl[(size_t)lane * a.Kloc + k] : 0.0;
-        const double hb_r0 = (local && lane <= a.r) ? a.br[(size_t)lane * a.Kloc + k] : 0.0;
-        const double ldf0 = (lane <= a.ldf_n) ? a.ldf[lane] : 0.0;
-        // the pair keys (one Philox block per four slots) and the resampling draw: ONE evaluation for the wave when the
-        // key blocks leave lane 63 free -- lanes 0..nb-1 take the key blocks, lane 63 the resampling counter
-        const int nb = (n + 3) / 4;
-        uint64_t Rdraw = 0;
-        if (nb <= 63) {
-            const bool res = lane == 63;
-            const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, res ? PM_STREAM_RESAMPLE : PM_STREAM_PAIR, res ? 0u : (uint32_t)lane, seed);
-            if (lane < nb) { L.key[lane * 4 + 0] = x.x; L.key[lane * 4 + 1] = x.y; L.key[lane * 4 + 2] = x.z; L.key[lane * 4 + 3] = x.w; }
-            Rdraw = ((uint64_t)(uint32_t)__shfl((int)x.y, 63, 64) << 32) | (uint32_t)__shfl((int)x.x, 63, 64);
-        } else {
-#pragma unroll 1
-            for (int b = lane; b < nb; b += 64) {
-                const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, PM_STREAM_PAIR, (uint32_t)b, seed);
-                L.key[b * 4 + 0] = x.x; L.key[b * 4 + 1] = x.y; L.key[b * 4 + 2] = x.z; L.key[b * 4 + 3] = x.w;
-            }
-            const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, PM_STREAM_RESAMPLE, 0u, seed);
-            Rdraw = ((uint64_t)x.y << 32) | x.x;
-        }
-        int anc = kg;
-        if (a.r > 0) {
-            anc = gbase + pk_cdf_search_wave(a.cdf + gbase, a.group_seeds ? a.Kg : a.K, Rdraw, lane);
-        }
-        const int32_t* ro = a.roots_old + (size_t)anc * N;
-        const int32_t* co = a.cnt_old + (size_t)anc * N;
-        const double* rl = a.rootll_old + (size_t)anc * N;
-        if (a.tab_ptrs) {                              // the owner of the ancestor holds its rows
-            const char* base = a.tab_ptrs[anc / a.Kloc];
-            ro = reinterpret_cast<const int32_t*>(base + a.tab_off_roots) + (size_t)anc * N;
-            co = reinterpret_cast<const int32_t*>(base + a.tab_off_cnt) + (size_t)anc * N;
-            rl = reinterpret_cast<const double*>(base + a.tab_off_rootll) + (size_t)anc * N;
-        }
-        #pragma unroll 1
-        for (int i = lane; i < n; i += 64) { L.ro[i] = ro[i]; L.co[i] = co[i]; L.anc_ll[i] = rl[i]; }
-        if (lane == 0) {
-            L.misc[3] = anc;
-            if (local) L.aux[AUX_LL_TILDE] = (a.r > 0) ? a.ll_prev[anc] : a.ll_tilde0;
-        }
-                if (lane <= a.r) { L.hbl[lane] = hb_l0; L.hbr[lane] = hb_r0; }
-        if (lane <= a.ldf_n) L.ldf[lane] = ldf0;
-        #pragma unroll 1
-        for (int j = lane + 64; j <= a.r; j += 64) {
-            L.hbl[j] = local ? a.bl[(size_t)j * a.Kloc + k] : 0.0;
-            L.hbr[j] = local ? a.br[(size_t)j * a.Kloc + k] : 0.0;
-        }
-        #pragma unroll 1
-        for (int j = lane + 64; j <= a.ldf_n; j += 64) L.ldf[j] = a.ldf[j];
-    }
-    __syncthreads();
-    if (w0) {
-        // largest key (lower slot on ties), then the second largest
-        unsigned long long best = 0ull;
-        #pragma unroll 1
-        for (int i = lane; i < n; i += 64) {
-            const unsigned long long c = ((unsigned long long)L.key[i] << 32) | (0xffffffffu - (uint32_t)i);
-            best = c > best ? c : best;
-        }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned long long o = __shfl_xor(best, off, 64);
-            best = o > best ? o : best;
-        }
-        const int il = (int)(0xffffffffu - (uint32_t)best);
-        best = 0ull;
-        #pragma unroll 1
-        for (int i = lane; i < n; i += 64) {
-            const unsigned long long c = ((unsigned long long)L.key[i] << 32) | (0xffffffffu - (uint32_t)i);
-            if (i != il) best = c > best ? c : best;
-        }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned long long o = __shfl_xor(best, off, 64);
-            best = o > best ? o : best;
-        }
-        const int ir = (int)(0xffffffffu - (uint32_t)best);
-        // position of every remaining slot in ascending (key, slot) order
-        int32_t* rn = a.roots_new + (size_t)kg * N;
-        int32_t* cn = a.cnt_new + (size_t)kg * N;
-        double* rln = a.rootll_new + (size_t)kg * N;
-        #pragma unroll 1
-        for (int i = lane; i < n; i += 64) {
-            if (i == il || i == ir) continue;
-            const unsigned long long mine = ((unsigned long long)L.key[i] << 32) | (uint32_t)i;
-            int rank = 0;
-            #pragma unroll 1
-            for (int j = 0; j < n; ++j) {
-                const unsigned long long cj = ((unsigned long long)L.key[j] << 32) | (uint32_t)j;
-                rank += (j != il && j != ir && cj < mine) ? 1 : 0;
-            }
-            const int node = L.ro[i], c = L.co[i];
-            const double xll = L.anc_ll[i];
-            rn[rank] = node;
-            cn[rank] = c;
-            rln[rank] = xll;
-            if (a.pos_hist) a.pos_hist[(size_t)kg * N + i] = rank;
-            L.ord_cnt[rank] = c;
-            L.ord_ll[rank] = xll;
-            L.ord_ldf[rank] = L.ldf[c < a.ldf_n ? c : a.ldf_n];
-        }
-        if (lane == 0) {
-            const int cnew = L.co[il] + L.co[ir];
-            rn[n - 2] = N + a.r * a.K + kg;           // id of the node this particle creates now
-            cn[n - 2] = cnew;
-            L.ord_cnt[n - 2] = cnew;
-            L.ord_ldf[n - 2] = L.ldf[cnew < a.ldf_n ? cnew : a.ldf_n];
-            L.misc[0] = L.ro[il];
-            L.misc[1] = L.ro[ir];
-            if (a.pos_hist) { a.pos_hist[(size_t)kg * N + il] = -1; a.pos_hist[(size_t)kg * N + ir] = -1; }
-            if (local) {
-                a.merges[((size_t)a.r * a.Kloc + k) * 2 + 0] = il;
-                a.merges[((size_t)a.r * a.Kloc + k) * 2 + 1] = ir;
-                if (a.r > 0) a.ancestors[(size_t)(a.r - 1) * a.Kloc + k] = L.misc[3] - gbase;   // index inside the group
-            }
-        }
-    }
-    __syncthreads();
-    if (tid == 0 && local) {                          // sequential sums, LDS operands only
-        double sum_rem = 0.0, fprior = 0.0;
-        int vminus = 0;
-        #pragma unroll 1
-        for (int p = 0; p < n - 2; ++p) sum_rem = sum_rem + L.ord_ll[p];
-        #pragma unroll 1
-        for (int p = 0; p < n - 1; ++p) {
-            const int c = L.ord_cnt[p];
-            fprior = fprior + (-L.ord_ldf[p]);
-            vminus += c - (c == 1 ? 1 : 0);
-        }
-        double lp = 0.0, rp = 0.0;                    // history rows 0..r with THIS rank's rate (quirk Q3)
-        #pragma unroll 1
-        for (int j = 0; j <= a.r; ++j) {
-            lp = lp + ((-a.lam_l) * L.hbl[j] + a.loglam_l);
-            rp = rp + ((-a.lam_r) * L.hbr[j] + a.loglam_r);
-        }
-        const double b_l = L.hbl[a.r], b_r = L.hbr[a.r];
-        const double q = 1.0 / ((double)((n - 1) * n) / 2.0);      // 1 / ncr(n, 2), vcsmc.py:298
-        L.aux[AUX_SUM_REM] = sum_rem;
-        L.aux[AUX_FPRIOR] = fprior;
-        L.aux[AUX_LPRIOR] = lp;
-        L.aux[AUX_RPRIOR] = rp;
-        L.aux[AUX_PAREN] = ((a.loglam_l - a.lam_l * b_l) + a.loglam_r) - a.lam_r * b_r;
-        L.aux[AUX_LOGV] = pm_log((double)vminus);
-        L.aux[AUX_Q] = (a.flags & 1u) ? q : pm_log(q);
-    }
-    __syncthreads();
-}
-
-// ---- packed bookkeeping: LP lanes per particle, 64 / LP particles per wave ---------------------------------------
+// ---- bookkeeping: LP lanes per particle, 64 / LP particles per wave ------------------------------------------------
 // The bookkeeping of one particle is a few short loops over its n <= N root slots; with one wave per particle most
 // lanes idle and the kernel is bound by instruction issue (profiles/r01_merge_pmc.md: 656 VALU + 620 SALU per
-// particle).  For N <= 32 a particle gets LP = 16 or 32 lanes, so one instruction stream serves 4 or 2 particles.
-// Same arithmetic, same orders (the sequential sums stay sequential, on the first lane of each group).
+// particle).  For N <= 32 a particle gets LP = 8, 16 or 32 lanes, so one instruction stream serves 8, 4 or 2 particles;
+// above that LP = 64, a wave per particle.
+
+// first index with cdf[i] > mulhi64(R, total), by the LP lanes of a group: LP probes per step.  The first round's probe addresses
+// do not depend on the threshold, so `total` and the coarse probes travel together: 2 dependent round trips for K <= LP * LP.
 template <int LP>
 __device__ __forceinline__ int pk_cdf_search_group(const uint64_t* cdf, int K, uint64_t R, int sl, int lane) {
     const int gshift = lane & ~(LP - 1);
@@ -975,7 +785,16 @@ __device__ __forceinline__ int pk_cdf_search_group(const uint64_t* cdf, int K, u
     return lo;
 }
 
-template <int LP>
+// Bookkeeping of one rank event for ONE particle (global index kg), by lane sl of its LP lanes; every thread of the workgroup must
+// call it (it contains workgroup barriers).
+//   resampling index (vcsmc.py:285) -> adoption of the ancestor's root table (the tf.gather of :286-288, on
+//   integer tables instead of partial likelihoods) -> uniform pair pick (:303-305) -> new root table
+//   (:361-373) -> the scalar terms of the weight that do not depend on the new node (:376-392).
+// `local`: the particle belongs to this rank's shard (float terms and outputs are produced).
+// Dependent global round trips: {cdf total + coarse probes, branch history, ldf table} -> {fine probes}
+// -> {ancestor's table rows, its log-likelihood}; everything after that runs out of LDS.
+// KEY_LOOP: the particle may have more pair-key blocks than its group has lanes to spare (see below).
+template <int LP, bool KEY_LOOP>
 __device__ __forceinline__ void pk_book_packed(const pk_rank_args& a, int kg, bool local, const pk_book_lds& L, int sl, int lane) {
     const int n = a.n, N = a.N, k = kg - a.k0;
     const int grp = a.group_seeds ? kg / a.Kg : 0;
@@ -990,13 +809,26 @@ __device__ __forceinline__ void pk_book_packed(const pk_rank_args& a, int kg, bo
         }
         #pragma unroll 1
         for (int j = sl; j <= a.ldf_n; j += LP) L.ldf[j] = a.ldf[j];
-        // pair keys (lanes 0..nb-1 of the group, nb <= LP / 4) and the resampling draw (last lane): one Philox evaluation
+        // pair keys, one Philox block per four slots, and the resampling draw: ONE evaluation for the group when the key blocks
+        // leave its last lane free -- lanes 0..nb-1 take the key blocks, lane LP-1 the resampling counter.  That always holds up
+        // to 64 taxa (nb <= LP / 2); a wave per particle meets more blocks at n >= 253 root slots and then strides over them.
         const int nb = (n + 3) / 4;
-        const bool res = sl == LP - 1;
-        const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, res ? PM_STREAM_RESAMPLE : PM_STREAM_PAIR, res ? 0u : (uint32_t)sl, seed);
-        if (sl < nb) { L.key[sl * 4 + 0] = x.x; L.key[sl * 4 + 1] = x.y; L.key[sl * 4 + 2] = x.z; L.key[sl * 4 + 3] = x.w; }
-        const int src = (lane & ~(LP - 1)) + LP - 1;
-        const uint64_t Rdraw = ((uint64_t)(uint32_t)__shfl((int)x.y, src, 64) << 32) | (uint32_t)__shfl((int)x.x, src, 64);
+        uint64_t Rdraw;
+        if (KEY_LOOP && nb > LP - 1) {
+            #pragma unroll 1
+            for (int b = sl; b < nb; b += LP) {
+                const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, PM_STREAM_PAIR, (uint32_t)b, seed);
+                L.key[b * 4 + 0] = x.x; L.key[b * 4 + 1] = x.y; L.key[b * 4 + 2] = x.z; L.key[b * 4 + 3] = x.w;
+            }
+            const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, PM_STREAM_RESAMPLE, 0u, seed);
+            Rdraw = ((uint64_t)x.y << 32) | x.x;
+        } else {
+            const bool res = sl == LP - 1;
+            const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, res ? PM_STREAM_RESAMPLE : PM_STREAM_PAIR, res ? 0u : (uint32_t)sl, seed);
+            if (sl < nb) { L.key[sl * 4 + 0] = x.x; L.key[sl * 4 + 1] = x.y; L.key[sl * 4 + 2] = x.z; L.key[sl * 4 + 3] = x.w; }
+            const int src = (lane & ~(LP - 1)) + LP - 1;
+            Rdraw = ((uint64_t)(uint32_t)__shfl((int)x.y, src, 64) << 32) | (uint32_t)__shfl((int)x.x, src, 64);
+        }
         int anc = kg;
         if (a.r > 0) anc = gbase + pk_cdf_search_group<LP>(a.cdf + gbase, a.group_seeds ? a.Kg : a.K, Rdraw, sl, lane);
         const int32_t* ro = a.roots_old + (size_t)anc * N;
@@ -1174,17 +1006,12 @@ __device__ __forceinline__ void pk_cache_fill(const pk_rank_args& a, int id, int
     if (lane == 0) __hip_atomic_store(a.mirror + x, slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// What a bookkeeping kernel writes for the particle of each group once pk_book_packed has returned: aux and child for the merge,
+// the merge record, the mark of the adopted ancestor's node (a plain store: every adopter writes the same value; the node's OWNER
+// writes it) and, sharded (`cache`, wave-uniform), its new remote children into the local cache, each copied by the whole wave.
 template <int LP>
-__global__ __launch_bounds__(64) void pk_rank_book_packed(const pk_rank_args a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x, sub = lane / LP, sl = lane & (LP - 1);
-    const int count = a.tab_ptrs ? a.Kloc : a.K;                      // local bookkeeping: this rank's particles only
-    int idx = blockIdx.x * (64 / LP) + sub;
-    if (idx >= count) idx = count - 1;          // a spare group repeats the last particle: identical values, identical writes
-    const int kg = a.tab_ptrs ? a.k0 + idx : idx;
-    const pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
-    const bool local = kg >= a.k0 && kg < a.k0 + a.Kloc;
-    pk_book_packed<LP>(a, kg, local, L, sl, lane);
+__device__ __forceinline__ void pk_book_tail(const pk_rank_args& a, int kg, bool local, bool mark, bool cache, const pk_book_lds& L,
+                                             int sl, int lane) {
     if (local) {
         const int k = kg - a.k0;
 #pragma unroll
@@ -1197,11 +1024,8 @@ __global__ __launch_bounds__(64) void pk_rank_book_packed(const pk_rank_args a) 
             for (int t = sl; t < PK_REC_SLOTS; t += LP) pk_rec_write(a, k, kg, t, L);
         }
     }
-    if (a.lazy && a.r > 0 && sl == 0) {
-        const int anc = L.misc[3];
-        a.mark[(size_t)(a.r - 1) * a.K + anc] = 1u;   // plain store: every adopter writes the same value
-    }
-    if (a.mirror && a.r > 0) {                        // (uniform) sharded: new remote children into the local cache, by the whole wave
+    if (mark && sl == 0) a.mark[(size_t)(a.r - 1) * a.K + L.misc[3]] = 1u;
+    if (cache) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int id = L.misc[c];
@@ -1212,6 +1036,24 @@ __global__ __launch_bounds__(64) void pk_rank_book_packed(const pk_rank_args a) 
             }
         }
     }
+}
+
+// Bookkeeping kernel: one wave per 64 / LP GLOBAL particles.  Particles of this rank's shard also get their child node ids and
+// weight terms written for the merge kernel; for the others only the replicated integer state (root tables) is advanced.
+// A wave per particle is asked to leave room for five waves per SIMD: left alone it takes 97 registers, four waves, and a batch of
+// 40 960 particles of 50 taxa (waves in several rounds) then takes 106.7 us against 93.2 (12 bytes of scratch per lane pay for it).
+template <int LP>
+__global__ __launch_bounds__(64, LP == 64 ? 5 : 1) void pk_rank_book_packed(const pk_rank_args a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x, sub = lane / LP, sl = lane & (LP - 1);
+    const int count = a.tab_ptrs ? a.Kloc : a.K;                      // local bookkeeping: this rank's particles only
+    int idx = blockIdx.x * (64 / LP) + sub;
+    if (idx >= count) idx = count - 1;          // a spare group repeats the last particle: identical values, identical writes
+    const int kg = a.tab_ptrs ? a.k0 + idx : idx;
+    const pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
+    const bool local = kg >= a.k0 && kg < a.k0 + a.Kloc;
+    pk_book_packed<LP, LP == 64>(a, kg, local, L, sl, lane);
+    pk_book_tail<LP>(a, kg, local, a.lazy && a.r > 0, a.mirror && a.r > 0, L, sl, lane);
 }
 
 // Sharded lazy nodes: every rank derives the resampling outcome of ALL K particles (index search only, no tables)
@@ -1398,44 +1240,8 @@ __global__ __launch_bounds__(PK_COLS, 5) void pk_rank_book_mat(const pk_rank_arg
     if (idx >= a.K) idx = a.K - 1;              // a spare group repeats the last particle: identical values, identical writes
     const int kg = idx;                         // one GPU: every particle is local
     const pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
-    pk_book_packed<LP>(a, kg, true, L, sl, lane);
-    if (sl < PK_AUX + 2) {
-        if (sl < PK_AUX) a.aux[(size_t)kg * PK_AUX + sl] = L.aux[sl];
-        else a.child[kg * 2 + (sl - PK_AUX)] = L.misc[sl - PK_AUX];
-    }
-    if (a.rec && sl < PK_REC_SLOTS) pk_rec_write(a, kg, kg, sl, L);          // (LP >= 16 here)
-    if (a.r > 0 && sl == 0) a.mark[(size_t)(a.r - 1) * a.K + L.misc[3]] = 1u;   // the marks stay (phylo_sweep_node reads them)
-}
-
-// Bookkeeping kernel: one 64-thread workgroup (one wave) per GLOBAL particle.  Particles of this rank's
-// shard also get their child node ids and weight terms written for the merge kernel; for the others only the
-// replicated integer state (root tables) is advanced.
-__global__ __launch_bounds__(64) void pk_rank_book(const pk_rank_args a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int kg = a.tab_ptrs ? a.k0 + blockIdx.x : blockIdx.x;      // local bookkeeping: this rank's particles only
-    const pk_book_lds L = pk_book_carve(smem, a.N);
-    const bool local = kg >= a.k0 && kg < a.k0 + a.Kloc;
-    pk_book_particle(a, kg, local, L);
-    if (local && threadIdx.x < PK_AUX + 2) {
-        const int k = kg - a.k0;
-        if (threadIdx.x < PK_AUX) a.aux[(size_t)k * PK_AUX + threadIdx.x] = L.aux[threadIdx.x];
-        else a.child[k * 2 + (threadIdx.x - PK_AUX)] = L.misc[threadIdx.x - PK_AUX];
-    }
-    if (local && a.rec && threadIdx.x < PK_REC_SLOTS) pk_rec_write(a, kg - a.k0, kg, threadIdx.x, L);
-    if (a.lazy && a.r > 0 && threadIdx.x == 0) {
-        // this particle adopted the table of `anc`: the node anc created at the previous rank event is now live;
-        // pk_materialize_adopted writes the marked nodes of that rank event.
-        const int anc = L.misc[3];                    // every rank sees every adoption; the OWNER of the node writes it
-        a.mark[(size_t)(a.r - 1) * a.K + anc] = 1u;  // plain store: every adopter writes the same value (no contended atomics)
-    }
-    if (a.mirror && a.r > 0 && local) {               // (uniform) sharded: new remote children into the local cache
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int id = L.misc[c];
-            const int slot = __shfl(threadIdx.x == 0 ? pk_cache_claim(a, id) : -1, 0, 64);
-            if (slot >= 0) pk_cache_fill(a, id, slot, threadIdx.x);
-        }
-    }
+    pk_book_packed<LP, false>(a, kg, true, L, sl, lane);               // (N <= 64: the key blocks fit one evaluation)
+    pk_book_tail<LP>(a, kg, true, a.r > 0, false, L, sl, lane);        // the marks stay (phylo_sweep_node reads them)
 }
 
 __device__ __forceinline__ const double* pk_node_ptr(const pk_rank_args& a, int id) {
@@ -1547,7 +1353,7 @@ __device__ __forceinline__ void pk_twist_adopt_body(const pk_twist_args& ta, int
     int anc = kg;
     if (a.r > 0) {
         const pm_u32x4 x = pm_philox4x32((uint32_t)kg, (uint32_t)a.r, PM_STREAM_RESAMPLE, 0u, a.seed);
-        anc = pk_cdf_search_wave(a.cdf, a.K, ((uint64_t)x.y << 32) | x.x, lane);
+        anc = pk_cdf_search_group<64>(a.cdf, a.K, ((uint64_t)x.y << 32) | x.x, lane, lane);
     }
     for (int i = lane; i < n; i += 64) {
         ta.roots_ad[(size_t)kg * N + i] = a.roots_old[(size_t)anc * N + i];

@@ -53,8 +53,8 @@ struct sweep_plan {
     bool sorted_prologue;              // pk_sweep_prologue_sorted
     bool mat_grouped;                  // pk_materialize_adopted_grouped instead of pk_materialize_adopted
     bool mat_draws_grouped;            // pk_materialize_by_draws: one workgroup per mat_group particles
-    int book_width;                    // lanes per particle of the bookkeeping: 8, 16, 32, 64, or 0 = one wave (pk_rank_book).
-                                       // (pk_rank_book_packed has no 64: one wave then too; pk_rank_book_mat has no 8: 16)
+    int book_width;                    // lanes per particle of the bookkeeping: 8, 16, 32 or 64; 0 = no bookkeeping launch (twisted).
+                                       // (pk_rank_book_mat has no 8: 16)
     bool step_a_work;                  // sweep_step_a issues the adopted-node launches and their barrier for r > 0
     bool mat_after_book;               // ... else the step does, behind its bookkeeping, for r > 0 (not at all: eager, or book_mat)
     bool mat_barrier;                  // that launch is followed by a barrier across the ranks
@@ -76,11 +76,10 @@ inline bool sweep_eager_nodes(bool flag, bool env) { return flag || env; }
 // Lanes per particle of the bookkeeping launch that advances `nbook` root tables of N slots.
 // Large launches (batched sweeps) are bound by instruction issue: 8 lanes per particle serve 8 particles with one instruction
 // stream (3.52e11 -> 3.68e11 units/s for a launch set of 20 sweeps; 4 lanes: no further gain); small launches are latency chains
-// and keep the shorter 16-lane form (4 particles per wave: PK_AUX + 2 = 10 <= 16 lanes).  33..64 taxa (DS3-DS8): 64.
+// and keep the shorter 16-lane form (4 particles per wave: PK_AUX + 2 = 10 <= 16 lanes).  Above 32 taxa: 64, a wave per particle.
 inline int sweep_book_width(int N, int nbook, const sweep_limits& L) {
     if (N <= 16) return nbook >= L.book_packed8_min ? 8 : 16;
-    if (N <= 32) return 32;
-    return N <= 64 ? 64 : 0;
+    return N <= 32 ? 32 : 64;
 }
 
 // The argument refusals of a sweep, in the order phylo_sweep_begin checks them: true, and the message, when the facts are refused

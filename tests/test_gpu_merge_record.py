@@ -132,7 +132,7 @@ def test_batched_groups_equal_single_sweeps():
 @pytest.mark.parametrize("N,G,Kg,writer", [
     (6, 1, 64, "pk_rank_book_mat"),                        # one sweep, lazy nodes, N <= 64
     (4, 2, 4096, "pk_rank_book_packed<8>"),                # N <= 16 and 8192 particles, batched (no pk_rank_book_mat)
-    (33, 2, 32, "pk_rank_book"),                           # more than 32 taxa, batched
+    (33, 2, 32, "pk_rank_book_packed<64>"),                # more than 32 taxa, batched
 ])
 def test_every_bookkeeping_writer(N, G, Kg, writer):
     """Each kernel that writes the record; lazy nodes equal eager nodes (which merge from ids, with the storing kernel)."""

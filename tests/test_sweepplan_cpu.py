@@ -79,7 +79,7 @@ def _rules(N, K, Kl, S, G, M, world, transport, flags, sw):
         else:
             run_local_book = (world > 1 or (transport and rehearse)) and not replicated
             nbook = Kl if run_local_book else K
-            widths.add(8 if N <= 16 and nbook >= 8192 else 16 if N <= 16 else 32 if N <= 32 else 0)
+            widths.add(8 if N <= 16 and nbook >= 8192 else 16 if N <= 16 else 32 if N <= 32 else 64)
             n += 1
         mat = lazy and r > 0 and not (run_local_book and not twist) and not book_mat
         if r > 0:
@@ -95,12 +95,12 @@ def _rules(N, K, Kl, S, G, M, world, transport, flags, sw):
     p["use_rec"] = use_rec.pop()
     p["mat_after_book"] = mat_after.pop() if mat_after else (lazy and not run_local_book and not book_mat)
     p["fix_rootll"] = fix.pop()
-    # one width per sweep, the two kernel families reading it their own way: pk_rank_book_packed has 8, 16, 32 and else the
-    # one-wave kernel, pk_rank_book_mat has 16 (also where the packed launch of rank event 0 took 8), 32, 64
+    # one width per sweep, 0 only where no bookkeeping is launched (twisted): pk_rank_book_packed has 8, 16, 32 and 64 (a wave per
+    # particle, every N > 32), pk_rank_book_mat has 16 (also where the packed launch of rank event 0 took 8), 32, 64
     wide = N <= 16 and (Kl if run_local_book else K) >= 8192
-    p["book_width"] = 0 if twist else (8 if wide else 16) if N <= 16 else 32 if N <= 32 else 64 if N <= 64 else 0
+    p["book_width"] = 0 if twist else (8 if wide else 16) if N <= 16 else 32 if N <= 32 else 64
     if not twist:
-        packed = {8: 8, 16: 16, 32: 32}.get(p["book_width"], 0)
+        packed = p["book_width"]
         mat = max(p["book_width"], 16)
         assert widths <= {packed, mat} and (packed in widths), (widths, p["book_width"])
     p["fold_logz"] = Kg <= SCAN_KERNEL_MAX_KG
@@ -167,8 +167,10 @@ def test_full_grid_against_the_rules(N, K, S):
 
 def test_each_threshold_flips_its_boolean():
     """the grid compares with the restatement; this states the sides outright"""
-    for (lo, hi), (wlo, whi) in (((16, 17), (16, 32)), ((32, 33), (32, 64)), ((64, 65), (64, 0))):
+    for (lo, hi), (wlo, whi) in (((16, 17), (16, 32)), ((32, 33), (32, 64)), ((64, 65), (64, 64))):
         assert _plan(lo, 64, 64)["book_width"] == wlo and _plan(hi, 64, 64)["book_width"] == whi
+    for N in (65, 66, 130, 252, 253, 257, 512):            # a wave per particle up to PK_MAX_TAXA; 0 is the twisted proposal's alone
+        assert _plan(N, 16, 64)["book_width"] == 64 and _plan(N, 16, 64, flags=TWISTING)["book_width"] == 0
     assert _plan(64, 64, 64)["book_mat"] and not _plan(65, 64, 64)["book_mat"] and _plan(65, 64, 64)["mat_after_book"]
     # S = 4096 / 4097: the combined launch, a lazy kept graph, the owners' search by the draws
     assert _plan(5, 64, 4096)["book_mat"] and not _plan(5, 64, 4097)["book_mat"] and _plan(5, 64, 4097)["lazy"]
