@@ -318,6 +318,11 @@ int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int tw
  * phylo_sweep_begin refuses are refused with the same code and message.  tests/test_sweepplan_cpu.py restates the rules. */
 int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
                            uint32_t* mask, int32_t* launches);
+/* Test hook, no GPU needed: the packed image of byte codes [N][S] as phylo_set_leaves builds it beside them (pk_pack_leaf_codes,
+ * phylo_packed_codes.h): packed[((leaf nC + Jc) 64 + c) 16 + j] = code of site 64 (16 Jc + j) + c with
+ * nC = ceil(ceil(S / 64) / 16), sites >= S hold the pad code 5.  *need = N nC 1024, the image's bytes; with packed NULL only
+ * *need is set, otherwise cap >= *need is required.  tests/test_packed_codes_cpu.py restates the layout. */
+int phylo_debug_pack_leaf_codes(const uint8_t* codes, int N, int S, uint8_t* packed, int64_t cap, int64_t* need);
 /* ... after a batched sweep of G groups (K the total): the device lists' limit is per group (K / G <= 8192), every other
  * limit sees the totals.  G = 1 is phylo_debug_reverse_plan. */
 int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,

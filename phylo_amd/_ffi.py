@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_tree_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_tree_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -171,6 +171,25 @@ def debug_sweep_plan(N, K, S, K_local=None, G=1, M=1, world=1, transport=False, 
     out["mask"] = mask.value
     out["launches"] = list(launches)
     return out
+
+
+def debug_pack_leaf_codes(codes):
+    """The packed image phylo_set_leaves builds beside byte codes [N][S] (no GPU needed): a uint8 array [N][nC][64][16] with
+    [leaf][Jc][c][j] = code of site 64 (16 Jc + j) + c, nC = ceil(ceil(S / 64) / 16), and the pad code 5 at sites >= S."""
+    lib = load()
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.ndim != 2:
+        raise ValueError("codes must be [N][S]")
+    N, S = cd.shape
+    need = C.c_int64(0)
+    rc = lib.phylo_debug_pack_leaf_codes(_ptr(cd), C.c_int(N), C.c_int(S), None, C.c_int64(0), C.byref(need))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    out = np.full(need.value, 0xff, dtype=np.uint8)
+    rc = lib.phylo_debug_pack_leaf_codes(_ptr(cd), C.c_int(N), C.c_int(S), _ptr(out), C.c_int64(out.size), C.byref(need))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return out.reshape(N, -1, 64, 16)
 
 
 TREE_SUMMARY_BUFS = ("u", "U", "bits", "kA", "kB", "val", "scan", "weight", "srt", "hp", "o_cbits", "o_cw", "o_tw", "child", "slot", "o_cg",

@@ -18,6 +18,7 @@
 
 #include "phylo_comm.h"
 #include "phylo_kernels.h"
+#include "phylo_packed_codes.h"
 #include "phylo_persist.h"
 #include "phylo_grad.h"
 #include "phylo_revlists_dev.h"
@@ -117,6 +118,7 @@ struct phylo_ctx {
     double *d_Q = nullptr, *d_pi = nullptr, *d_lam_l = nullptr, *d_lam_r = nullptr, *d_ldf = nullptr;
     double* d_leaves = nullptr;          // [N][S][4]
     uint8_t* d_leaf_codes = nullptr;     // [N][S]; in use only when every leaf row is one-hot or all-ones
+    uint8_t* d_leaf_packed = nullptr;    // the same codes as 16-byte words per lane (phylo_packed_codes.h), behind them in one buffer
     bool leaves_coded = false;
     uint32_t* d_pair_hist = nullptr;     // [N][N][32] code-pair site counts of coded leaves (built on the first twisted sweep)
     bool hist_ready = false, codes_valid = false;
@@ -723,7 +725,8 @@ int phylo_create(const int* device_ids, int n_gpus, int K, int N, int S, int A, 
         c->d_lam_r = c->d_Q + 20 + N;
         if ((rc = dalloc(c, &c->d_ldf, (size_t)N + 1)) != PHYLO_OK) break;
         if ((rc = dalloc(c, &c->d_leaves, (size_t)N * S * 4)) != PHYLO_OK) break;
-        if ((rc = dalloc(c, &c->d_leaf_codes, (size_t)N * S)) != PHYLO_OK) break;
+        if ((rc = dalloc(c, &c->d_leaf_codes, pk_codes_image_bytes(N, S))) != PHYLO_OK) break;
+        c->d_leaf_packed = c->d_leaf_codes + pk_packed_offset(N, S);
         // table of log (2 max(c,2) - 3)!! by leaf count c = 0..N
         c->h_ldf.resize((size_t)N + 1);
         for (int cnt = 0; cnt <= N; ++cnt) c->h_ldf[cnt] = host_log_double_factorial(2 * (cnt > 2 ? cnt : 2) - 3);
@@ -802,16 +805,18 @@ int phylo_set_site_tile(phylo_ctx* c, int T) {
 int phylo_set_leaves(phylo_ctx* c, const double* genome) {
     CHK(bind(c));
     if (!genome) return fail(c, PHYLO_EINVAL, "genome_NxSxA is NULL");
-    // The rows and their 1-byte codes go up from a pinned image that outlives the call, on the context's stream: the call does not
+    // The rows, their 1-byte codes and the codes' packed image (phylo_packed_codes.h; codes and image are one buffer and one copy) go
+    // up from a pinned image that outlives the call, on the context's stream: the call does not
     // wait for the device (a training step on site minibatches sets new leaves every time).  Only a previous upload still in
     // flight has to be over before the image is overwritten.
     const size_t rows = (size_t)c->N * c->S;
-    const bool pinned = rows * 33 <= ((size_t)8 << 20);     // (a large alignment goes up straight from the caller's buffer, and waits)
+    const size_t code_bytes = pk_codes_image_bytes(c->N, c->S);
+    const bool pinned = rows * 32 + code_bytes <= ((size_t)8 << 20);     // (a large alignment goes up straight from the caller's buffer, and waits)
     std::vector<uint8_t> codes_v;
     uint8_t* codes = nullptr;
     if (pinned) {
         if (!c->h_leaves_p) {
-            HIPCHK(c, hipHostMalloc((void**)&c->h_leaves_p, rows * 33));
+            HIPCHK(c, hipHostMalloc((void**)&c->h_leaves_p, rows * 32 + code_bytes));
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_leaves, hipEventDisableTiming));
         } else {
             HIPCHK(c, hipEventSynchronize(c->ev_leaves));
@@ -821,7 +826,7 @@ int phylo_set_leaves(phylo_ctx* c, const double* genome) {
         codes = (uint8_t*)c->h_leaves_p + rows * 32;
     } else {
         HIPCHK(c, hipMemcpyAsync(c->d_leaves, genome, rows * 32, hipMemcpyHostToDevice, c->stream));
-        codes_v.resize(rows);
+        codes_v.resize(code_bytes);
         codes = codes_v.data();
     }
     // one-hot / all-ones rows (the reference's encoding, runner.py:83-96) also get a 1-byte code per site
@@ -841,7 +846,10 @@ int phylo_set_leaves(phylo_ctx* c, const double* genome) {
         c->codes_valid = ok;                                  // a property of the data (the twisting contract uses it)
         c->leaves_coded = ok && !c->env.no_leaf_codes;   // the access-path optimisation can be switched off
         c->hist_ready = false;
-        if (ok) HIPCHK(c, hipMemcpyAsync(c->d_leaf_codes, codes, rows, hipMemcpyHostToDevice, c->stream));
+        if (ok) {
+            pk_pack_leaf_codes(codes, c->N, c->S, codes + pk_packed_offset(c->N, c->S));
+            HIPCHK(c, hipMemcpyAsync(c->d_leaf_codes, codes, code_bytes, hipMemcpyHostToDevice, c->stream));
+        }
     }
     if (pinned) HIPCHK(c, hipEventRecord(c->ev_leaves, c->stream));
     c->have_leaves = true;
@@ -1557,6 +1565,8 @@ static pk_rank_args rank_args(const phylo_ctx* c, int r) {
     // event's adopted nodes: not so with replicated bookkeeping (and the twisted proposal reads its roots elsewhere)
     b.mirror = (p.twist || p.replicated_book) ? nullptr : c->d_mirror; b.cache = c->d_cache; b.cache_cap = c->cache_cap;
     b.leaf_codes = c->leaves_coded ? c->d_leaf_codes : nullptr;
+    b.leaf_packed = c->leaves_coded ? c->d_leaf_packed : nullptr;
+    b.packed_leaf_bytes = pk_packed_leaf_bytes(c->S);
     b.Pmat = c->d_Pmat + (size_t)r * Kl * 32;
     b.pi = c->d_pi;
     b.logw_r = c->d_logw + (size_t)r * K;
@@ -2879,6 +2889,15 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
     const sweep_plan p = sweep_plan_form(f, k_sweep_limits);
     *mask = sweep_plan_mask(p);
     for (int r = -1; r <= p.R; ++r) launches[r + 1] = sweep_plan_launches(p, r);
+    return PHYLO_OK;
+}
+
+int phylo_debug_pack_leaf_codes(const uint8_t* codes, int N, int S, uint8_t* packed, int64_t cap, int64_t* need) {
+    if (N < 1 || S < 1 || !need || (packed && !codes)) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_pack_leaf_codes: bad arguments");
+    *need = (int64_t)pk_packed_bytes(N, S);
+    if (!packed) return PHYLO_OK;
+    if (cap < *need) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_pack_leaf_codes: the image takes %lld bytes (got %lld)", (long long)*need, (long long)cap);
+    pk_pack_leaf_codes(codes, N, S, packed);
     return PHYLO_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "phylo_math.h"
+#include "phylo_packed_codes.h"
 
 #define PK_COLS 256          // canonical site-sum columns == threads per merge workgroup
 #define PK_AUX 8             // per-particle scalars handed from the bookkeeping kernel to the merge epilogue
@@ -15,7 +16,7 @@
 enum { AUX_SUM_REM = 0, AUX_FPRIOR, AUX_LPRIOR, AUX_RPRIOR, AUX_LL_TILDE, AUX_PAREN, AUX_LOGV, AUX_Q };
 // Merge record: everything one wave of pk_rank_merge_nostore needs about its particle, in one aligned 128-byte line that the
 // bookkeeping writes beside aux / child: the aux row, the two children ALREADY RESOLVED to the address the row loop reads (rows
-// of a node, or the 1-byte codes of a coded leaf), the four addresses the epilogue writes, and a flag word.  One rank only: the
+// of a node, or the packed image of a coded leaf's codes), the four addresses the epilogue writes, and a flag word.  One rank only: the
 // address of a child in a peer's pool or in the cache of remote nodes is not known to every particle when its bookkeeping
 // runs (another wave of the same launch may still be fetching it), so sharded sweeps keep the form that resolves ids.
 #define PK_REC 16            // 64-bit slots per record
@@ -650,6 +651,8 @@ struct pk_rank_args {
     double lam_l, lam_r, loglam_l, loglam_r, ll_tilde0;
     const double* leaves;                                 // [N][S][4]
     const uint8_t* leaf_codes;                            // [N][S] 0..3 one-hot state, 4 all-ones; NULL if some row is neither
+    const uint8_t* leaf_packed;                           // [N][packed_leaf_bytes] the same codes, 16 steps per lane and 16-byte word
+    size_t packed_leaf_bytes;                             // (phylo_packed_codes.h); NULL with leaf_codes: what the merge record points to
     double* pool;                                         // [(N-1)][Kloc][S][4]: this rank's nodes
     const double* const* pool_ptrs;                       // [world]: every rank's pool as mapped in this process
     // sharded: remote nodes this rank has merged once are kept in a local cache (pk_pull_remote_children); mirror[node - N] is
@@ -717,7 +720,7 @@ __device__ __forceinline__ pk_book_lds pk_book_carve(char* base, int N) {
 }
 
 // slot t < PK_REC_SLOTS of local particle k's merge record, from what the bookkeeping left in LDS (one lane per slot, the lanes
-// that write aux / child).  A child's address is pk_node_ptr's for one rank, or the leaf's codes where the merge reads codes.
+// that write aux / child).  A child's address is pk_node_ptr's for one rank, or the leaf's packed codes where the merge reads codes.
 __device__ __forceinline__ void pk_rec_write(const pk_rank_args& a, int k, int kg, int t, const pk_book_lds& L) {
     const size_t node_sz = (size_t)a.S * 4;
     unsigned long long v;
@@ -726,7 +729,7 @@ __device__ __forceinline__ void pk_rec_write(const pk_rank_args& a, int k, int k
     } else if (t <= REC_BASE_R) {
         const int id = L.misc[t - REC_BASE_L];
         if (id >= a.N) v = (unsigned long long)(a.pool + (size_t)(id - a.N) * node_sz);
-        else if (a.leaf_codes) v = (unsigned long long)(a.leaf_codes + (size_t)id * a.S);
+        else if (a.leaf_codes) v = (unsigned long long)(a.leaf_packed + (size_t)id * a.packed_leaf_bytes);
         else v = (unsigned long long)(a.leaves + (size_t)id * node_sz);
     } else if (t == REC_NODELL) {
         v = (unsigned long long)(a.nodell + (a.N + a.r * a.K + kg));
@@ -1531,6 +1534,119 @@ __device__ __forceinline__ void pk_rows_run(int s0, int s1, const char* bl, cons
         }
     }
 }
+// ---- a coded side of the record form reads the packed image of its leaf's codes (phylo_packed_codes.h): ONE 16-byte load per lane
+//      serves 16 steps (primate.p, 15 steps: the whole row), requested next to the first rows before the tables are built, so a
+//      leaf x leaf wave has no memory wait inside its row loop.  Chunks are aligned: a tile that starts mid-chunk (T / 64 not a
+//      multiple of 16) begins inside one; with more than 16 steps to go the next chunk travels while the current one is consumed.
+//      Two coded sides: the words are combined once per chunk into (c_l * 5 + c_r) * 8 per BYTE (at most 240 with the pad code 5
+//      on both sides: no carry between bytes), the byte offset of the pair's site likelihood in lik25, so a step is one bit-field
+//      extract and one LDS read; sites past the end hold the pad code on both sides and read lik25[30] = 1.0 exactly: no select.
+struct pk_cstream { pk_u4 nl, nr; unsigned int cur, w1, w2, w3; };   // the quad in use, those after it; the next chunk
+__device__ __forceinline__ pk_u4 pk_chunk_load(const char* b, int Jc) {
+    return *(pk_gu4c*)(b + ((unsigned int)Jc * (unsigned int)PK_CHUNK_BYTES + (threadIdx.x & 63u) * 16u));
+}
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_cs_request(pk_cstream& c, const char* bl, const char* br, int Jc) {
+    if constexpr (CL) c.nl = pk_chunk_load(bl, Jc);
+    if constexpr (CR) c.nr = pk_chunk_load(br, Jc);
+}
+// the requested chunk becomes the current one
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_cs_take(pk_cstream& c) {
+    if constexpr (CL && CR) {
+        c.cur = (c.nl.x * 5u + c.nr.x) * 8u; c.w1 = (c.nl.y * 5u + c.nr.y) * 8u;
+        c.w2 = (c.nl.z * 5u + c.nr.z) * 8u; c.w3 = (c.nl.w * 5u + c.nr.w) * 8u;
+    } else {
+        const pk_u4 n = CL ? c.nl : c.nr;
+        c.cur = n.x; c.w1 = n.y; c.w2 = n.z; c.w3 = n.w;
+    }
+}
+// the next four steps' bytes
+__device__ __forceinline__ void pk_cs_quad(pk_cstream& c) { c.cur = c.w1; c.w1 = c.w2; c.w2 = c.w3; }
+// before the tile's first step (s0, s1: the tile's sites, wave-uniform), its chunk requested: take it, request the next one if the
+// tile reaches it, go to the quad of step s0 / 64
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_cs_start(pk_cstream& c, const char* bl, const char* br, int s0, int s1) {
+    pk_cs_take<CL, CR>(c);
+    if ((s0 | 1023) + 1 < s1) pk_cs_request<CL, CR>(c, bl, br, (s0 >> 10) + 1);
+    #pragma unroll 1
+    for (int i = 0; i < ((s0 >> 8) & 3); ++i) pk_cs_quad(c);
+}
+// the byte (a code, or the pair's offset in lik25) of the step whose first site is u (wave-uniform, a multiple of 64)
+__device__ __forceinline__ unsigned int pk_cs_byte(const pk_cstream& c, int u) { return (c.cur >> ((u >> 3) & 24)) & 0xffu; }
+// before the step whose first site is u, the step after the one just read
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_cs_advance(pk_cstream& c, const char* bl, const char* br, int u, int s1) {
+    if ((u & 1023) == 0) {
+        if (u < s1) {
+            pk_cs_take<CL, CR>(c);
+            if (u + 1024 < s1) pk_cs_request<CL, CR>(c, bl, br, (u >> 10) + 1);
+        }
+    } else if ((u & 255) == 0) {
+        pk_cs_quad(c);
+    }
+}
+// the uncoded sides' rows alone (pk_rows_load's clamp)
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_rows_load_u(pk_rowregs& x, const char* bl, const char* br, int s, int s1) {
+    const unsigned int sc = (unsigned int)(s < s1 ? s : s1 - 1);
+    if constexpr (!CL) { x.l0 = *(pk_gu4c*)(bl + sc * 32u); x.l1 = *(pk_gu4c*)(bl + sc * 32u + 16u); }
+    if constexpr (!CR) { x.r0 = *(pk_gu4c*)(br + sc * 32u); x.r1 = *(pk_gu4c*)(br + sc * 32u + 16u); }
+}
+// pk_rows_run with the coded sides read from the stream: same trips, same pairing (the tile's steps 2 i and 2 i + 1 share one
+// renormalisation, an odd last step is multiplied alone), same factors.  The uncoded side of a mixed merge keeps its two register
+// sets, its clamp and its validity select (the coded side's pad code reads row 5 of its table, which the select discards).
+// Forms of the walk (40 960-particle launch, primate.p; DESIGN.md section 4, profiles/r05_summary.md).  Measured: the one below --
+// the chunk's four words as four scalars per lane, a quad moved up every four steps, one v_bfe_u32 per step with a scalar shift:
+// launch 60.6 -> 56.2 us on average, rank event 0 (all leaf x leaf) 40.0 -> 34.9, 657 -> 588 VALU per wave, but 156 -> 335 SALU
+// (the wave-uniform tests for a new chunk and a new quad and the shift, per step).  Compiled and rejected on their register
+// allocation, not run: the walk indexed by step number beside the site loop (three more live scalars: 42-46 SGPR spills, half a
+// matrix reloaded lane by lane inside the mixed loops); pi and the matrices loaded above the variants (pk_rows_loop_rec).  Not
+// tried: a chunk unrolled with static extracts (pm_lp_mul2's slow path, two logs, would be inlined eight times), SDWA byte selects,
+// a pair-packed image of leaf x leaf.
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_rows_run_packed(int s0, int s1, const char* bl, const char* br, pk_rowregs& A, pk_cstream& c,
+                                                   const double (&Pl)[16], const double (&Pr)[16], const double (*tabL)[4],
+                                                   const double (*tabR)[4], const double* lik25, const double (&pi)[4], pm_lp& col) {
+    static_assert(CL || CR, "a coded side");
+    pk_cs_start<CL, CR>(c, bl, br, s0, s1);
+    if constexpr (CL && CR) {
+        const char* lb = (const char*)lik25;
+        #pragma unroll 1
+        for (int u = s0; u < s1; u += 128) {                // u: wave-uniform
+            const double xa = *(const double*)(lb + pk_cs_byte(c, u));
+            pk_cs_advance<CL, CR>(c, bl, br, u + 64, s1);
+            if (u + 64 < s1) {
+                const double xb = *(const double*)(lb + pk_cs_byte(c, u + 64));
+                pk_cs_advance<CL, CR>(c, bl, br, u + 128, s1);
+                pm_lp_mul2(col, xa, xb);
+            } else {
+                pm_lp_mul(col, xa);
+            }
+        }
+    } else {
+        pk_rowregs B;
+        int s = s0 + (int)(threadIdx.x & 63);
+        #pragma unroll 1
+        for (int u = s0; u < s1; u += 128, s += 128) {
+            pk_rows_load_u<CL, CR>(B, bl, br, s + 64, s1);
+            (CL ? A.cl : A.cr) = pk_cs_byte(c, u);
+            pk_cs_advance<CL, CR>(c, bl, br, u + 64, s1);
+            double xa = pk_rows_lik<CL, CR>(A, Pl, Pr, tabL, tabR, lik25, pi);
+            xa = s < s1 ? xa : 1.0;
+            pk_rows_load_u<CL, CR>(A, bl, br, s + 128, s1);
+            if (u + 64 < s1) {
+                (CL ? B.cl : B.cr) = pk_cs_byte(c, u + 64);
+                pk_cs_advance<CL, CR>(c, bl, br, u + 128, s1);
+                double xb = pk_rows_lik<CL, CR>(B, Pl, Pr, tabL, tabR, lik25, pi);
+                xb = s + 64 < s1 ? xb : 1.0;
+                pm_lp_mul2(col, xa, xb);
+            } else {
+                pm_lp_mul(col, xa);
+            }
+        }
+    }
+}
 // one tile of one merge by one wave; the tables are the wave's own slices of LDS
 template <bool CL, bool CR>
 __device__ __forceinline__ void pk_rows_loop(int s0, int s1, const double* Lp, const double* Rp, const uint8_t* Lc, const uint8_t* Rc,
@@ -1678,15 +1794,32 @@ __device__ __forceinline__ void pk_build_lik25_direct(const double* __restrict__
         lik25[t] = pk_site_lik(pi, o);
     }
 }
+// pi (from the kernel-argument segment) and the matrices of the uncoded sides are requested HERE, inside the variant: uniform
+// addresses in the constant address space, nothing stored yet -- scalar loads.  Loaded above the variants they are one value each
+// for all four, and the register allocator, short of scalar registers only where both matrices are held, then spills them
+// everywhere and reloads them lane by lane inside the mixed variants' row loops.  A coded side's matrix is never read.
 template <bool CL, bool CR>
-__device__ __forceinline__ void pk_rows_loop_rec(int s0, int s1, const char* bl, const char* br, const double* Pu, const double (&Pl)[16],
-                                                 const double (&Pr)[16], double (*tabL)[4], double (*tabR)[4], double* lik25,
-                                                 const double (&pi)[4], pm_lp& col) {
+__device__ __forceinline__ void pk_rows_loop_rec(int s0, int s1, const char* bl, const char* br, const double* Pu, const pk_cdbl* Pc,
+                                                 double (*tabL)[4], double (*tabR)[4], double* lik25, const pk_cdbl* pik, pm_lp& col) {
     const int lane = threadIdx.x & 63;
+    const double pi[4] = {pik[0], pik[1], pik[2], pik[3]};
+    double Pl[16], Pr[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        Pl[u] = CL ? 0.0 : Pc[u];
+        Pr[u] = CR ? 0.0 : Pc[16 + u];
+    }
     pk_rowregs A;
-    pk_rows_load<CL, CR>(A, bl, br, s0 + lane, s1);        // the first rows / codes travel while the tables are built
+    pk_cstream c;
+    if constexpr (CL || CR) {                              // the first rows / the first chunk of codes travel while the tables are built
+        pk_cs_request<CL, CR>(c, bl, br, s0 >> 10);
+        pk_rows_load_u<CL, CR>(A, bl, br, s0 + lane, s1);
+    } else {
+        pk_rows_load<CL, CR>(A, bl, br, s0 + lane, s1);
+    }
     if constexpr (CL && CR) {
         pk_build_lik25_direct(Pu, pi, lik25, lane);
+        if (lane == PK_PAD_CODE * 6) lik25[PK_PAD_CODE * 6] = 1.0;   // pad x pad: a site past the end
         pk_wave_lds_fence();
     } else if constexpr (CL) {
         pk_build_leaf_table(Pu, tabL, lane);
@@ -1695,13 +1828,18 @@ __device__ __forceinline__ void pk_rows_loop_rec(int s0, int s1, const char* bl,
         pk_build_leaf_table(Pu + 16, tabR, lane);
         pk_wave_lds_fence();
     }
-    pk_rows_run<CL, CR>(s0, s1, bl, br, A, Pl, Pr, tabL, tabR, lik25, pi, col);
+    if constexpr (CL || CR) pk_rows_run_packed<CL, CR>(s0, s1, bl, br, A, c, Pl, Pr, tabL, tabR, lik25, pi, col);
+    else pk_rows_run<CL, CR>(s0, s1, bl, br, A, Pl, Pr, tabL, tabR, lik25, pi, col);
 }
+// (the argument segment of the kernel below, as the compiler lays it out)
+struct pk_merge_kernarg { const unsigned long long* rec; const double* Pmat; int S, T, ntiles; double* tilev; pk_pi4 pi4; };
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8)))
 void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const double* __restrict__ Pmat, int S, int T, int ntiles,
                            double* __restrict__ tilev, const pk_pi4 pi4) {
-    __shared__ __attribute__((aligned(16))) double tabL[5][4], tabR[5][4];
-    __shared__ double lik25[25];
+    // (row 5 of a table and lik25[25 .. 29] belong to the pad code beside a real one: never written, read only where the site is
+    // past the end and the factor is replaced; lik25[30] = 1.0 is pad x pad)
+    __shared__ __attribute__((aligned(16))) double tabL[PK_PAD_CODE + 1][4], tabR[PK_PAD_CODE + 1][4];
+    __shared__ double lik25[PK_PAD_CODE * 6 + 1];
     const int item = (int)blockIdx.x;
     const int k = ntiles == 1 ? item : item / ntiles, tau = item - k * ntiles;
     const int s0 = tau * T, s1 = s0 + T < S ? s0 + T : S;
@@ -1717,19 +1855,16 @@ void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const dou
     const char* bl = pk_uniform_ptr((const void*)rc[REC_BASE_L]);
     const char* br = pk_uniform_ptr((const void*)rc[REC_BASE_R]);
     PK_TOUCH4_END(fl);                                     // (before the first use of the flags, on every path)
-    const double pi[4] = {pi4.v[0], pi4.v[1], pi4.v[2], pi4.v[3]};
-    // uniform address, nothing stored yet: scalar loads, which hipcc requests where a matrix is first used -- a coded side's matrix
-    // is never read (pk_rows_out), so a variant requests only what it uses
-    double Pl[16], Pr[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) { Pl[u] = Pc[u]; Pr[u] = Pc[16 + u]; }
+    static_assert(offsetof(pk_merge_kernarg, pi4) == 40 && sizeof(pk_merge_kernarg) == 72, "the kernel's argument segment");
+    const pk_cdbl* pi = (const pk_cdbl*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                         offsetof(pk_merge_kernarg, pi4));
     pm_lp col = pm_lp_init();
     if (fl & 1u) {
-        if (fl & 2u) pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
-        else pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
+        if (fl & 2u) pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        else pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
     } else {
-        if (fl & 2u) pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
-        else pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pl, Pr, tabL, tabR, lik25, pi, col);
+        if (fl & 2u) pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        else pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
     }
     const double tot = pk_wave_tree_sum(pm_lp_finish(col));
     if (threadIdx.x == 0) {
