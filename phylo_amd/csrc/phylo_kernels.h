@@ -1602,8 +1602,15 @@ __device__ __forceinline__ void pk_rows_load_u(pk_rowregs& x, const char* bl, co
 // (the wave-uniform tests for a new chunk and a new quad and the shift, per step).  Compiled and rejected on their register
 // allocation, not run: the walk indexed by step number beside the site loop (three more live scalars: 42-46 SGPR spills, half a
 // matrix reloaded lane by lane inside the mixed loops); pi and the matrices loaded above the variants (pk_rows_loop_rec).  Not
-// tried: a chunk unrolled with static extracts (pm_lp_mul2's slow path, two logs, would be inlined eight times), SDWA byte selects,
-// a pair-packed image of leaf x leaf.
+// tried: SDWA byte selects, a pair-packed image of leaf x leaf.
+// Round 6 (profiles/r06_summary.md): this loop is now the GENERAL path only (pk_rows_general: tiles that start mid-chunk, a special
+// leaf x leaf table entry, the redo of a flagged wave).  Chunk-aligned tiles take pk_rows_fast_cc / pk_rows_fast_mixed below with the
+// speculative update -- measured, 40 960-particle launch: 56.6 -> 49.2 us on average, rank event 0 35.4 -> 25.7, 588 -> 488 VALU
+// and 335 -> 150 SALU per wave.  Compiled and rejected on their register allocation, not run: a mixed chunk unrolled sixteen steps
+// and one word of four steps unrolled (300+ SGPR spills, matrix elements reloaded from spill lanes inside the loop); the general
+// path as a noinline function (v69 in the callee: 71 VGPRs, 7 waves per SIMD); the flag as a boolean (lane masks merged by scalar
+// instructions at every exit of the unrolled loop).  Not measured apart: the speculative update inside this walk, and the static
+// walk with pm_lp_mul2 -- the two were built and measured together and passed together.
 template <bool CL, bool CR>
 __device__ __forceinline__ void pk_rows_run_packed(int s0, int s1, const char* bl, const char* br, pk_rowregs& A, pk_cstream& c,
                                                    const double (&Pl)[16], const double (&Pr)[16], const double (*tabL)[4],
@@ -1783,7 +1790,9 @@ __device__ __forceinline__ void pk_leaf_vec(const double* __restrict__ P /*16*/,
         for (int j = 0; j < 4; ++j) t[j] = pm_fma(1.0, v[2][j], pm_fma(1.0, v[1][j], pm_fma(1.0, v[0][j], 1.0 * t[j])));
     }
 }
-__device__ __forceinline__ void pk_build_lik25_direct(const double* __restrict__ Pu /*32*/, const double (&pi)[4], double* lik25, int t) {
+// (returns whether this lane's entry is outside the positive normal range: what pm_lp_mul2 tests per factor, tested once here)
+__device__ __forceinline__ bool pk_build_lik25_direct(const double* __restrict__ Pu /*32*/, const double (&pi)[4], double* lik25, int t) {
+    bool special = false;
     if (t < 25) {
         const int cl = t / 5, cr = t - cl * 5;
         double tl[4], tr[4], o[4];
@@ -1791,17 +1800,115 @@ __device__ __forceinline__ void pk_build_lik25_direct(const double* __restrict__
         pk_leaf_vec(Pu + 16, cr, tr);
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = tl[j] * tr[j];
-        lik25[t] = pk_site_lik(pi, o);
+        const double x = pk_site_lik(pi, o);
+        lik25[t] = x;
+        special = pm_lp_special(x);
     }
+    return special;
 }
-// pi (from the kernel-argument segment) and the matrices of the uncoded sides are requested HERE, inside the variant: uniform
-// addresses in the constant address space, nothing stored yet -- scalar loads.  Loaded above the variants they are one value each
-// for all four, and the register allocator, short of scalar registers only where both matrices are held, then spills them
-// everywhere and reloads them lane by lane inside the mixed variants' row loops.  A coded side's matrix is never read.
+// ---- The row loops of a tile that starts on a chunk boundary (s0 % 1024 == 0: every tile at the default site tile, a multiple of
+//      the chunk), speculative.  A chunk's steps are walked in statically unrolled pairs: the byte of step j is taken from word
+//      j / 4 at the constant shift 8 (j % 4) -- no quad moved up, no test for a new chunk or a new quad, ONE scalar test per pair
+//      against the steps still to go.  Same trips and pairing as pk_rows_run_packed (the tile's steps 2 i and 2 i + 1 share one
+//      renormalisation, an odd last step is multiplied alone); the next chunk is requested when the current one is taken.  The
+//      running product is updated by pm_lp_mul2_spec / pm_lp_mul_spec (phylo_math.h): no branch, no log; the loops return whether some
+//      lane met what pm_lp_mul2 sends to its per-factor updates, and the kernel then recomputes the tile in pk_rows_general.
+__device__ __forceinline__ unsigned int pk_cw_byte(const unsigned int (&w)[4], int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xffu; }
+// leaf x leaf; every entry of lik25 is a positive normal number (the caller's ballot) and pad x pad is exactly 1.0, so only the
+// pair's product is tested.  A chunk's sixteen steps are unrolled: eight pairs, one test each
+__device__ __forceinline__ bool pk_rows_fast_cc(int s0, int s1, const char* bl, const char* br, pk_cstream& c, const double* lik25,
+                                                pm_lp& col) {
+    const char* lb = (const char*)lik25;
+    pm_lp_flag flag = pm_lp_flag_init();
+    // steps to go from the chunk's first one, the chunk: wave-uniform, and said so (the tile's bounds come out of an integer division,
+    // which the vector pipe computes: without this the trip tests are vector compares)
+    int n = __builtin_amdgcn_readfirstlane((s1 - s0 + 63) >> 6), Jc = __builtin_amdgcn_readfirstlane(s0 >> 10);
+    #pragma unroll 1
+    for (;;) {
+        const unsigned int w[4] = {(c.nl.x * 5u + c.nr.x) * 8u, (c.nl.y * 5u + c.nr.y) * 8u, (c.nl.z * 5u + c.nr.z) * 8u,
+                                   (c.nl.w * 5u + c.nr.w) * 8u};
+        if (n > 16) pk_cs_request<true, true>(c, bl, br, Jc + 1);
+#pragma unroll
+        for (int j = 0; j < 16; j += 2) {
+            if (n < j + 2) {
+                if (n == j + 1) pm_lp_mul_normal(col, *(const double*)(lb + pk_cw_byte(w, j)));
+                break;
+            }
+            const double xa = *(const double*)(lb + pk_cw_byte(w, j));
+            const double xb = *(const double*)(lb + pk_cw_byte(w, j + 1));
+            pm_lp_mul2_spec_q(col, xa, xb, flag);
+        }
+        if (n <= 16) break;
+        n -= 16; ++Jc;
+    }
+    return pm_lp_flag_set(flag);
+}
+// one coded side: the uncoded side keeps its two register sets, its clamp and its validity select (pk_rows_run_packed: dropping them
+// on complete steps was not measured).  One pair per trip of a rolled loop; the chunk's code words are two 64-bit values, the low
+// one shifted down by 16 per pair -- both bytes of a pair at constant positions -- and the high one moves in after four pairs; an
+// odd last step follows the loop.  (A chunk's sixteen steps unrolled as in leaf x leaf, and one word of four steps unrolled:
+// compiled, not run -- next to a matrix and pi in scalar registers the allocator then reloads matrix elements from spill lanes
+// inside the loop.)
 template <bool CL, bool CR>
-__device__ __forceinline__ void pk_rows_loop_rec(int s0, int s1, const char* bl, const char* br, const double* Pu, const pk_cdbl* Pc,
-                                                 double (*tabL)[4], double (*tabR)[4], double* lik25, const pk_cdbl* pik, pm_lp& col) {
-    const int lane = threadIdx.x & 63;
+__device__ __forceinline__ void pk_rows_pair_spec(pk_rowregs& A, pk_rowregs& B, unsigned int ca, unsigned int cb, int s, int s1,
+                                                  const char* bl, const char* br, const double (&Pl)[16], const double (&Pr)[16],
+                                                  const double (*tabL)[4], const double (*tabR)[4], const double (&pi)[4], pm_lp& col,
+                                                  pm_lp_flag& flag) {
+    pk_rows_load_u<CL, CR>(B, bl, br, s + 64, s1);
+    (CL ? A.cl : A.cr) = ca;
+    double xa = pk_rows_lik<CL, CR>(A, Pl, Pr, tabL, tabR, nullptr, pi);
+    xa = s < s1 ? xa : 1.0;
+    pk_rows_load_u<CL, CR>(A, bl, br, s + 128, s1);
+    (CL ? B.cl : B.cr) = cb;
+    double xb = pk_rows_lik<CL, CR>(B, Pl, Pr, tabL, tabR, nullptr, pi);
+    xb = s + 64 < s1 ? xb : 1.0;
+    pm_lp_mul2_spec(col, xa, xb, flag);
+}
+template <bool CL, bool CR>
+__device__ __forceinline__ bool pk_rows_fast_mixed(int s0, int s1, const char* bl, const char* br, pk_rowregs& A, pk_cstream& c,
+                                                   const double (&Pl)[16], const double (&Pr)[16], const double (*tabL)[4],
+                                                   const double (*tabR)[4], const double (&pi)[4], pm_lp& col) {
+    static_assert(CL != CR, "one coded side");
+    pk_rowregs B;
+    pm_lp_flag flag = pm_lp_flag_init();
+    int s = s0 + (int)(threadIdx.x & 63);
+    int n = __builtin_amdgcn_readfirstlane((s1 - s0 + 63) >> 6), Jc = __builtin_amdgcn_readfirstlane(s0 >> 10);
+    #pragma unroll 1
+    for (;;) {
+        const pk_u4 q = CL ? c.nl : c.nr;
+        unsigned long long lo = (unsigned long long)q.x | ((unsigned long long)q.y << 32);
+        unsigned long long hi = (unsigned long long)q.z | ((unsigned long long)q.w << 32);
+        if (n > 16) pk_cs_request<CL, CR>(c, bl, br, Jc + 1);
+        const int m = n < 16 ? n : 16;                     // this chunk's steps
+        #pragma unroll 1
+        for (int t = 0; t < (m >> 1); ++t, s += 128) {
+            if (t == 4) lo = hi;
+            const unsigned int cw = (unsigned int)lo;
+            pk_rows_pair_spec<CL, CR>(A, B, cw & 0xffu, (cw >> 8) & 0xffu, s, s1, bl, br, Pl, Pr, tabL, tabR, pi, col, flag);
+            lo >>= 16;
+        }
+        if (m & 1) {                                       // an odd last step, alone
+            if ((m >> 1) == 4) lo = hi;
+            (CL ? A.cl : A.cr) = (unsigned int)lo & 0xffu;
+            double xa = pk_rows_lik<CL, CR>(A, Pl, Pr, tabL, tabR, nullptr, pi);
+            xa = s < s1 ? xa : 1.0;
+            pm_lp_mul_spec(col, xa, flag);
+        }
+        if (n <= 16) break;
+        n -= 16; ++Jc;
+    }
+    return pm_lp_flag_set(flag);
+}
+// The general path of a coded variant: pk_rows_run_packed from pm_lp_init(), with its own first chunk and rows and its own
+// matrices.  Taken by a tile that starts mid-chunk (a context with an overridden site tile), by a leaf x leaf wave with a lik25
+// entry outside the positive normal range, and as the redo of a wave whose speculative loop raised its flag.  The tables in LDS are
+// the variant's, already built.  ONE copy, below the four variants, so pm_lp_mul2's per-factor updates (two pm_log bodies per
+// loop) are out of the hot loops.  Inlined there and not a call: a device function cannot be given the kernel's register bound
+// (amdgpu_waves_per_eu applies to kernels only), and as a noinline function it compiled to registers up to v69 -- the allocator
+// steps over the callee-saved blocks -- which made the kernel 71 VGPRs and 7 waves per SIMD.
+template <bool CL, bool CR>
+__device__ __forceinline__ pm_lp pk_rows_general_v(int s0, int s1, const char* bl, const char* br, const pk_cdbl* Pc, const pk_cdbl* pik,
+                                                   double (*tabL)[4], double (*tabR)[4], double* lik25) {
     const double pi[4] = {pik[0], pik[1], pik[2], pik[3]};
     double Pl[16], Pr[16];
 #pragma unroll
@@ -1811,16 +1918,61 @@ __device__ __forceinline__ void pk_rows_loop_rec(int s0, int s1, const char* bl,
     }
     pk_rowregs A;
     pk_cstream c;
+    pm_lp col = pm_lp_init();
+    pk_cs_request<CL, CR>(c, bl, br, s0 >> 10);
+    pk_rows_load_u<CL, CR>(A, bl, br, s0 + (int)(threadIdx.x & 63), s1);
+    pk_rows_run_packed<CL, CR>(s0, s1, bl, br, A, c, Pl, Pr, tabL, tabR, lik25, pi, col);
+    return col;
+}
+__device__ __forceinline__ pm_lp pk_rows_general(unsigned int fl, int s0, int s1, const char* bl, const char* br, const double* Pu,
+                                                 const double* pi4, double (*tabL)[4], double (*tabR)[4], double* lik25) {
+    // wave-uniform, and said to be so: the addresses derive from the particle index, which the vector pipe computed
+    fl = (unsigned int)__builtin_amdgcn_readfirstlane((int)fl);
+    s0 = __builtin_amdgcn_readfirstlane(s0);
+    s1 = __builtin_amdgcn_readfirstlane(s1);
+    bl = pk_uniform_ptr(bl);
+    br = pk_uniform_ptr(br);
+    const pk_cdbl* Pc = (const pk_cdbl*)pk_uniform_ptr(Pu);
+    const pk_cdbl* pik = (const pk_cdbl*)pk_uniform_ptr(pi4);
+    if ((fl & 3u) == 3u) return pk_rows_general_v<true, true>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
+    if (fl & 1u) return pk_rows_general_v<true, false>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
+    return pk_rows_general_v<false, true>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
+}
+// pi (from the kernel-argument segment) and the matrices of the uncoded sides are requested HERE, inside the variant: uniform
+// addresses in the constant address space, nothing stored yet -- scalar loads.  Loaded above the variants they are one value each
+// for all four, and the register allocator, short of scalar registers only where both matrices are held, then spills them
+// everywhere and reloads them lane by lane inside the mixed variants' row loops.  A coded side's matrix is never read.
+template <bool CL, bool CR>
+__device__ __forceinline__ bool pk_rows_loop_rec(int s0, int s1, const char* bl, const char* br, const double* Pu, const pk_cdbl* Pc,
+                                                 double (*tabL)[4], double (*tabR)[4], double* lik25, const pk_cdbl* pik, pm_lp& col) {
+    const int lane = threadIdx.x & 63;
+    const double pi[4] = {pik[0], pik[1], pik[2], pik[3]};
+    double Pl[16], Pr[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        Pl[u] = CL ? 0.0 : Pc[u];
+        Pr[u] = CR ? 0.0 : Pc[16 + u];
+    }
+    if constexpr (CL != CR) {
+        // each element in a scalar register pair of its own: as parts of the loads' sixteen-register tuples the allocator splits them
+        // inside the unrolled row loop and reloads elements from spill lanes there
+#pragma unroll
+        for (int u = 0; u < 16; ++u) asm volatile("" : "+s"(CL ? Pr[u] : Pl[u]));
+    }
+    pk_rowregs A;
+    pk_cstream c;
     if constexpr (CL || CR) {                              // the first rows / the first chunk of codes travel while the tables are built
         pk_cs_request<CL, CR>(c, bl, br, s0 >> 10);
         pk_rows_load_u<CL, CR>(A, bl, br, s0 + lane, s1);
     } else {
         pk_rows_load<CL, CR>(A, bl, br, s0 + lane, s1);
     }
+    bool redo = (s0 & 1023) != 0;                          // wave-uniform: a tile that starts mid-chunk takes the general path
     if constexpr (CL && CR) {
-        pk_build_lik25_direct(Pu, pi, lik25, lane);
+        const bool special = pk_build_lik25_direct(Pu, pi, lik25, lane);
         if (lane == PK_PAD_CODE * 6) lik25[PK_PAD_CODE * 6] = 1.0;   // pad x pad: a site past the end
         pk_wave_lds_fence();
+        redo = redo || __any(special);                     // so does a wave whose table holds a factor pm_lp_mul2 would refuse
     } else if constexpr (CL) {
         pk_build_leaf_table(Pu, tabL, lane);
         pk_wave_lds_fence();
@@ -1828,12 +1980,24 @@ __device__ __forceinline__ void pk_rows_loop_rec(int s0, int s1, const char* bl,
         pk_build_leaf_table(Pu + 16, tabR, lane);
         pk_wave_lds_fence();
     }
-    if constexpr (CL || CR) pk_rows_run_packed<CL, CR>(s0, s1, bl, br, A, c, Pl, Pr, tabL, tabR, lik25, pi, col);
-    else pk_rows_run<CL, CR>(s0, s1, bl, br, A, Pl, Pr, tabL, tabR, lik25, pi, col);
+    if constexpr (CL || CR) {
+        if (!redo) {
+            bool flag;
+            if constexpr (CL && CR) flag = pk_rows_fast_cc(s0, s1, bl, br, c, lik25, col);
+            else flag = pk_rows_fast_mixed<CL, CR>(s0, s1, bl, br, A, c, Pl, Pr, tabL, tabR, pi, col);
+            redo = __any(flag);
+        }
+        return redo;                                       // (the kernel's ONE pk_rows_general, below the four variants)
+    } else {
+        pk_rows_run<CL, CR>(s0, s1, bl, br, A, Pl, Pr, tabL, tabR, lik25, pi, col);
+        return false;
+    }
 }
 // (the argument segment of the kernel below, as the compiler lays it out)
 struct pk_merge_kernarg { const unsigned long long* rec; const double* Pmat; int S, T, ntiles; double* tilev; pk_pi4 pi4; };
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8)))
+// (amdgpu_num_vgpr: on gfx90a and later the backend counts it in units of the unified register file, twice the number written, so
+// this caps the allocator at 64 vector registers -- 8 waves per SIMD; the 7-wave bound alone allows it 72, and it used 65)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8), amdgpu_num_vgpr(32)))
 void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const double* __restrict__ Pmat, int S, int T, int ntiles,
                            double* __restrict__ tilev, const pk_pi4 pi4) {
     // (row 5 of a table and lik25[25 .. 29] belong to the pad code beside a real one: never written, read only where the site is
@@ -1841,8 +2005,10 @@ void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const dou
     __shared__ __attribute__((aligned(16))) double tabL[PK_PAD_CODE + 1][4], tabR[PK_PAD_CODE + 1][4];
     __shared__ double lik25[PK_PAD_CODE * 6 + 1];
     const int item = (int)blockIdx.x;
-    const int k = ntiles == 1 ? item : item / ntiles, tau = item - k * ntiles;
-    const int s0 = tau * T, s1 = s0 + T < S ? s0 + T : S;
+    const int k = __builtin_amdgcn_readfirstlane(ntiles == 1 ? item : item / ntiles), tau = item - k * ntiles;
+    // (the tile's bounds come out of an integer division, which the vector pipe computes: said to be wave-uniform here, or every
+    // test on them below is a vector compare)
+    const int s0 = __builtin_amdgcn_readfirstlane(tau * T), s1 = __builtin_amdgcn_readfirstlane(s0 + T < S ? s0 + T : S);
     // the record and the matrices were written by earlier launches and nothing writes them during this one: read through the
     // constant address space, a uniform address is a scalar load wherever hipcc places it (a global one only where it proves that
     // no store of the kernel comes before it, which it does not once it has moved the load into a variant's branch)
@@ -1859,13 +2025,15 @@ void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const dou
     const pk_cdbl* pi = (const pk_cdbl*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() +
                                          offsetof(pk_merge_kernarg, pi4));
     pm_lp col = pm_lp_init();
+    bool redo;
     if (fl & 1u) {
-        if (fl & 2u) pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
-        else pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        if (fl & 2u) redo = pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        else redo = pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
     } else {
-        if (fl & 2u) pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
-        else pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        if (fl & 2u) redo = pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        else redo = pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
     }
+    if (redo) col = pk_rows_general(fl, s0, s1, bl, br, Pu, (const double*)pi, tabL, tabR, lik25);
     const double tot = pk_wave_tree_sum(pm_lp_finish(col));
     if (threadIdx.x == 0) {
         if (ntiles != 1) {

@@ -219,6 +219,51 @@ PM_HD void pm_lp_mul2(pm_lp& a, double x1, double x2) {
     }
 }
 
+// The speculative forms of the two updates: no branch and no pm_log; what pm_lp_mul2 / pm_lp_mul would have sent to their rare
+// paths is ORed into the caller's flag, and (p, E) are taken from the product regardless.  Whenever the flag stays clear,
+// (p, E, extra) are pm_lp_mul2's / pm_lp_mul's bit for bit: the flag's term is exactly `!ok` there (the unsigned compare of
+// pm_lp_mul here), so with the flag clear the reference took its common branch in every update so far, and that branch is these
+// assignments -- by induction over the updates every field is the same, and extra was never touched by either.  With the flag set
+// the fields are garbage (a mantissa in [1, 2) and some exponent: never inf or NaN, so nothing traps later), and the caller
+// discards them and recomputes from pm_lp_init() with pm_lp_mul2 / pm_lp_mul.
+// The flag is kept as two running minima, not as a boolean (on the GPU a boolean per lane is a mask in scalar registers, and
+// ORing it in every update costs the scalar unit and two register pairs inside loops that are short of both; a minimum is one
+// vector instruction): h + 0x80100000 (mod 2^32) of a high word h is >= 0x80200000 iff h is a positive normal number's
+// (0x00100000 <= h < 0x7ff00000: anything from 0x7ff00000 up wraps to below 0x80000000, anything below 0x00100000 stays below
+// 0x80200000), and >= 0x80300000 iff moreover h >= 0x00200000 (q >= 2^-1021).  OR of `!ok` == a minimum under its bound.
+struct pm_lp_flag { uint32_t f, q; };                  // the least key of a factor, of a pair's product
+PM_HD pm_lp_flag pm_lp_flag_init() { pm_lp_flag g = {0xffffffffu, 0xffffffffu}; return g; }
+PM_HD bool pm_lp_flag_set(const pm_lp_flag& g) { return (g.f < 0x80200000u) | (g.q < 0x80300000u); }
+PM_HD uint32_t pm_lp_key(double x) { return (uint32_t)(pm_bits(x) >> 32) + 0x80100000u; }
+PM_HD uint32_t pm_min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+PM_HD bool pm_lp_special(double x) { return pm_bits(x) - 0x0010000000000000ull >= 0x7fe0000000000000ull; }
+// x1, x2 known to be positive normal numbers (checked by the caller where they were made): only q can leave the range
+PM_HD void pm_lp_mul2_spec_q(pm_lp& a, double x1, double x2, pm_lp_flag& flag) {
+    const double q = (a.p * x1) * x2;
+    const uint64_t bq = pm_bits(q);
+    flag.q = pm_min_u32(flag.q, pm_lp_key(q));
+    a.E += (int)((uint32_t)(bq >> 32) >> 20) - 1023;
+    a.p = pm_from_bits((bq & 0x000fffffffffffffull) | 0x3ff0000000000000ull);
+}
+PM_HD void pm_lp_mul2_spec(pm_lp& a, double x1, double x2, pm_lp_flag& flag) {
+    flag.f = pm_min_u32(pm_min_u32(flag.f, pm_lp_key(x1)), pm_lp_key(x2));
+    pm_lp_mul2_spec_q(a, x1, x2, flag);
+}
+// the single-factor twins (an odd last step): pm_lp_mul's common path alone, and the same with its test as the flag
+PM_HD void pm_lp_mul_normal(pm_lp& a, double x) {
+    const uint64_t bx = pm_bits(x);
+    const int ex = (int)((bx >> 52) & 0x7ff);
+    const double mx = pm_from_bits((bx & 0x000fffffffffffffull) | 0x3ff0000000000000ull);
+    a.p = a.p * mx;                                    // [1, 4)
+    const uint64_t bp = pm_bits(a.p);
+    a.E += (ex - 1023) + ((int)((bp >> 52) & 0x7ff) - 1023);
+    a.p = pm_from_bits((bp & 0x000fffffffffffffull) | 0x3ff0000000000000ull);
+}
+PM_HD void pm_lp_mul_spec(pm_lp& a, double x, pm_lp_flag& flag) {
+    flag.f = pm_min_u32(flag.f, pm_lp_key(x));
+    pm_lp_mul_normal(a, x);
+}
+
 PM_HD double pm_lp_finish(const pm_lp& a) {
     const double dE = (double)a.E;
     return ((pm_log(a.p) + dE * 1.90821492927058770002e-10) + dE * 6.93147180369123816490e-01) + a.extra;
