@@ -98,7 +98,7 @@ int phylo_destroy(phylo_ctx* ctx);
  * (vcsmc.py:240-242) is taken tile by tile -- T sites per tile, 64 log-product columns inside a tile, tile values added left to
  * right -- so that one wavefront owns a (row, tile).  phylo_site_tile(S) is the default T for rows of S sites (the CPU oracle
  * uses the same value); phylo_set_site_tile overrides it for this context (T a multiple of 64 in [64, 4096]; 0 = the default),
- * which changes results in the last bits only and drops the sweep state (call it before the first sweep; PHYLO_ESTATE once a
+ * which changes results in the last bits only and drops the sweep state and its tree summary (call it before the first sweep; PHYLO_ESTATE once a
  * communicator is set).  PHYLO_SITE_TILE=T in the environment of phylo_create does the same.  phylo_get_site_tile returns the
  * context's T. */
 int phylo_site_tile(int S);
@@ -221,7 +221,9 @@ int phylo_sweep_finish(phylo_ctx* ctx);
 
 /* Partial-likelihood vector of the node created at rank event r by particle slot k in the last sweep,
  * [S,4] (test surface for the merge kernel inside the sweep).  After a lazy sweep the missing nodes are
- * written first; when sharded that step is a collective: every rank must make the call. */
+ * written first; when sharded that step is a collective: every rank must make the call.
+ * The stored matrices make the call independent of a later phylo_set_model; after phylo_set_leaves it is refused
+ * (PHYLO_ESTATE) until the next sweep: the nodes not yet written would come from the new leaves under the old sweep's records. */
 int phylo_sweep_node(phylo_ctx* ctx, int r, int k, double* out_Sx4);
 
 /* Reverse pass of the last sweep (which must have run with PHYLO_KEEP_GRAPH): the gradient of log Z-hat with

@@ -150,6 +150,7 @@ struct phylo_ctx {
     char** d_xslab_ptrs = nullptr;       // [world] every rank's slab as mapped here
     unsigned long long x_epoch[2] = {0, 0};   // exchanges / barriers issued so far (the same on every rank)
     bool last_lazy = false;
+    bool leaves_newer = false;           // phylo_set_leaves since the last sweep: its unwritten nodes can no longer be written
     int32_t* d_merges = nullptr;         // [(N-1)][Kloc][2]
     int64_t* d_anc = nullptr;            // [(N-2)][Kloc]
     uint64_t* d_cdf[2] = {nullptr, nullptr};   // [K], double-buffered across rank events
@@ -799,6 +800,7 @@ int phylo_set_site_tile(phylo_ctx* c, int T) {
     free_sweep_state(c);                                   // tile values, leaf log-likelihoods: rebuilt by the next sweep
     c->state_ready = false;
     c->swept = false; ++c->sweep_serial;
+    c->ts_done = c->tb_done = false;                       // the summary's tables belong to the dropped sweep: their fetches refuse too
     return PHYLO_OK;
 }
 
@@ -854,6 +856,7 @@ int phylo_set_leaves(phylo_ctx* c, const double* genome) {
     if (pinned) HIPCHK(c, hipEventRecord(c->ev_leaves, c->stream));
     c->have_leaves = true;
     c->last_graph = c->last_graph_twist = false;           // ... and to the leaves
+    c->leaves_newer = true;                                // ... and so do the nodes phylo_sweep_node would still have to write
     CHK(refresh_leaf_ll(c));
     if (!pinned) HIPCHK(c, hipStreamSynchronize(c->stream));
     return PHYLO_OK;
@@ -1223,6 +1226,7 @@ static int sweep_ready(phylo_ctx* c) {
 // ... and what every finished sweep leaves for the calls that follow it
 static void sweep_publish(phylo_ctx* c, bool lazy, bool graph, int G, bool final_missing, int merge_events, int launches, double units) {
     c->swept = true;
+    c->leaves_newer = false;
     c->last_lazy = lazy;                                   // only adopted nodes are in the pool (marks say which)
     c->last_graph = graph;
     c->last_G = G;
@@ -2026,8 +2030,13 @@ int phylo_sweep(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, double* log_
 int phylo_sweep_node(phylo_ctx* c, int r, int k, double* out) {
     CHK(bind(c));
     if (!c->swept) return fail(c, PHYLO_ESTATE, "no sweep has been run");
+    if (c->leaves_newer)                // the nodes not yet written would come from the new leaves under the old sweep's records
+        return fail(c, PHYLO_ESTATE, "phylo_set_leaves has been called since the last sweep: its nodes belong to the old leaves");
     if (r < 0 || r >= c->N - 1 || k < 0 || k >= c->Kloc || !out) return fail(c, PHYLO_EINVAL, "bad (r, k)");
     if (c->last_lazy) {                 // write every node that the lazy sweep skipped, oldest rank event first
+        // a kept graph on one GPU is then what an eager sweep leaves: every node stored, marks that no longer say who was adopted.
+        // rev_marks writes those again from the ancestors, so that the reverse pass has the same bits before and after this call
+        if (c->last_graph && c->last_graph_marks && c->world == 1 && c->Kloc == c->K) c->last_graph_eager = true;
         pk_rank_args b{};
         b.N = c->N; b.S = c->S; b.K = c->K; b.Kloc = c->Kloc; b.k0 = c->k0;
         b.leaves = c->d_leaves; b.pool = c->d_pool; b.pool_ptrs = c->d_pool_ptrs;
@@ -2233,7 +2242,8 @@ static pg_plan_in rev_plan_in(const phylo_ctx* c) {
 // (0.) After a sweep that stored every node (PHYLO_EAGER_NODES) nothing marked the adopted ones.  The marks say who was adopted and
 // nothing else, and the ancestors say that too: written here, once per sweep, they give such a sweep the reverse pass of a lazy one
 // -- the same launches, the same sums in the same order, the same bits -- instead of the form without marks (which the twisted
-// proposal, S > 4096 and phylo_sweep_node's widened marks still take).
+// proposal, S > 4096 and, on a sharded context, phylo_sweep_node's widened marks still take).  phylo_sweep_node on one GPU asks
+// for the same: its widened marks are written again here, and the pass before and after that call has the same bits.
 static int rev_marks(rev_pass& p) {
     phylo_ctx* c = p.c;
     if (c->last_graph_marks || !c->last_graph_eager) return PHYLO_OK;
