@@ -116,6 +116,16 @@ struct pg_args {
 __device__ __forceinline__ double pg_dot4(double a0, double b0, double a1, double b1, double a2, double b2, double a3, double b3) {
     return __builtin_fma(a3, b3, __builtin_fma(a2, b2, __builtin_fma(a1, b1, a0 * b0)));
 }
+// y = x B and y = x B^T for a row x in registers and a 4 x 4 matrix B: four pg_dot4 chains.  (The quad forms -- a state per lane:
+// pg_nodes, pg_parent_quad -- keep their own per-lane chains.)
+__device__ __forceinline__ void pg_rowmat(const double (&x)[4], const double* B, double (&y)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = pg_dot4(x[0], B[j], x[1], B[4 + j], x[2], B[8 + j], x[3], B[12 + j]);
+}
+__device__ __forceinline__ void pg_rowmat_t(const double (&x)[4], const double* B, double (&y)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = pg_dot4(x[0], B[j * 4], x[1], B[j * 4 + 1], x[2], B[j * 4 + 2], x[3], B[j * 4 + 3]);
+}
 // 1 / x for a normal x > 0 (a site likelihood): v_rcp_f64 and two Newton steps -- a quarter of the instructions of the IEEE
 // division and exact to an ulp or two, which is all a pass with a 1e-9 tolerance needs
 __device__ __forceinline__ double pg_rcp(double x) {
@@ -215,15 +225,6 @@ __device__ inline void pg_expm4_frechet(const double* A0, const double* E0, doub
 // product is (row i) x (the right factor), and the right factors of the series are A and E, which every lane holds whole -- the
 // loop needs no exchange and is a quarter as long; only the squarings fetch the other rows (quad broadcasts).  Element by element
 // the arithmetic of pg_expm4_frechet (the same fused chains in the same order).  All four lanes of a quad must be active.
-__device__ __forceinline__ void pg_rowmat(const double (&x)[4], const double* B, double (&y)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        double acc = x[0] * B[j];
-        acc = pm_fma(x[1], B[4 + j], acc);
-        acc = pm_fma(x[2], B[8 + j], acc);
-        y[j] = pm_fma(x[3], B[12 + j], acc);
-    }
-}
 template <int I> __device__ __forceinline__ double pg_quad(double v);
 __device__ __forceinline__ void pg_quad_gather(const double (&rowv)[4], double* full) {      // the whole matrix from the quad's four rows
 #pragma unroll
@@ -750,6 +751,68 @@ __global__ __launch_bounds__(256) void pg_nodes(pg_args a, int r) {
     }
 }
 
+// ---- the row forms' statements of a site (lane = site, all four states in registers); which kernel is which form: DESIGN.md 4b ----
+// The forward merge of a site: u = x1 Pl, v = x2 Pr, y = u o v; returns lik = pi . y.  (pg_rowmat's chains, the two of a column side
+// by side and, in pg_pbar_site, a column's sums at a time: in that order the compiler schedules the site loops of pg_twist_pbar and
+// pg_nodes_free as measured; with whole rows first one multiply-add moved and pg_twist_pbar ran 1.8 % longer.)
+__device__ __forceinline__ double pg_site_merge(const double (&x1)[4], const double (&x2)[4], const double (&Pl)[16], const double (&Pr)[16],
+                                                const double (&pi)[4], double (&u)[4], double (&v)[4], double (&y)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        u[j] = pg_dot4(x1[0], Pl[j], x1[1], Pl[4 + j], x1[2], Pl[8 + j], x1[3], Pl[12 + j]);
+        v[j] = pg_dot4(x2[0], Pr[j], x2[1], Pr[4 + j], x2[2], Pr[8 + j], x2[3], Pr[12 + j]);
+        y[j] = u[j] * v[j];
+    }
+    return pg_dot4(pi[0], y[0], pi[1], y[1], pi[2], y[2], pi[3], y[3]);
+}
+// The matrix adjoints of a site whose adjoint row is known, column j (xbj = xb[j], uj = u[j], vj = v[j]):
+// acc[i * 4 + j] (+)= x1[i] xbj vj, acc[16 + i * 4 + j] (+)= x2[i] xbj uj.  ADD = false writes the products (the sign of a zero
+// product is not that of fma(., ., +0)): for the one site of a thread
+template <bool ADD>
+__device__ __forceinline__ void pg_site_pbar(int j, const double (&x1)[4], const double (&x2)[4], double uj, double vj, double xbj,
+                                             double (&acc)[PG_PART]) {
+    const double tl = xbj * vj, tr = xbj * uj;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        acc[i * 4 + j] = ADD ? __builtin_fma(x1[i], tl, acc[i * 4 + j]) : x1[i] * tl;
+        acc[16 + i * 4 + j] = ADD ? __builtin_fma(x2[i], tr, acc[16 + i * 4 + j]) : x2[i] * tr;
+    }
+}
+// One site of a merge nobody gathers into: the adjoint row is the own term w pi / lik alone, and
+// acc += { X1^T (xb o v),  X2^T (xb o u),  w y / lik }
+__device__ __forceinline__ void pg_pbar_site(const double (&x1)[4], const double (&x2)[4], const double (&Pl)[16],
+                                             const double (&Pr)[16], const double (&pi)[4], double w, double (&acc)[PG_PART]) {
+    double u[4], v[4], y[4];
+    const double lik = pg_site_merge(x1, x2, Pl, Pr, pi, u, v, y);
+    const double inv = w * pg_rcp(lik);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        pg_site_pbar<true>(j, x1, x2, u[j], v[j], pi[j] * inv, acc);
+        acc[32 + j] = __builtin_fma(y[j], inv, acc[32 + j]);
+    }
+}
+// The 36 sums of acc over the wave's 64 lanes (fixed order) through the wave's own LDS rows, twelve at a time: lane (q, part) adds
+// 16 of the 64 values of sum q, two quad steps; the lane that then holds sum i runs store(i, sum).  No workgroup barrier.
+template <class Store>
+__device__ __forceinline__ void pg_wave_sums36(const double (&acc)[PG_PART], double (&red)[12][PG_RED_STRIDE], Store store) {
+    const int lane = threadIdx.x & 63, q = lane >> 2, part = lane & 3;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) red[i][lane] = acc[b * 12 + i];
+        __builtin_amdgcn_wave_barrier();
+        double v = 0.0;
+        if (q < 12) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v = v + red[q][part + 4 * i];
+        }
+        v = v + pg_quad_sum_step<1>(v);
+        v = v + pg_quad_sum_step<2>(v);
+        if (q < 12 && part == 0) store(b * 12 + q, v);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // grid (groups of 64 sites, chunks -- of rank event chunk0's range, or with chunks_free_only of ALL rank events, chunk0 = the first
 // of the launch): cpart[chunk][s] = sum of the chunk's parent contributions (free parents' only with chunks_free_only).
 // Row form: lane = site (all four states: whole 32-byte rows per load, no quad broadcasts -- a quad form spent 24 of its ~50
@@ -846,24 +909,10 @@ struct pg_rows_lds {
     double shW[4][PG_PART];
 };
 __device__ __forceinline__ void pg_rows_reduce(const double (&acc)[PG_PART], pg_rows_lds& sh, double* out) {
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int q = lane >> 2, part = lane & 3;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) sh.red[wv][i][lane] = acc[b * 12 + i];
-        __builtin_amdgcn_wave_barrier();
-        double v = 0.0;
-        if (q < 12) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v = v + sh.red[wv][q][part + 4 * i];
-        }
-        v = v + pg_quad_sum_step<1>(v);
-        v = v + pg_quad_sum_step<2>(v);
-        if (q < 12 && part == 0) sh.shW[wv][b * 12 + q] = v;
-        __builtin_amdgcn_wave_barrier();
-    }
+    double* mine = sh.shW[wv];
+    pg_wave_sums36(acc, sh.red[wv], [mine](int i, double v) { mine[i] = v; });
     __syncthreads();
     if (tid < PG_PART) out[tid] = ((sh.shW[0][tid] + sh.shW[1][tid]) + sh.shW[2][tid]) + sh.shW[3][tid];
 }
@@ -935,7 +984,7 @@ __global__ __launch_bounds__(256, 3) void pg_nodes_free(pg_args a, int phase) {
     }
     #pragma unroll 1
     for (int s = lane; s < a.S; s += 64) {
-        double L[4], Rv[4], u[4], v[4], xb[4];
+        double L[4], Rv[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { L[i] = Ln[i]; Rv[i] = Rn[i]; }
         {
@@ -943,45 +992,10 @@ __global__ __launch_bounds__(256, 3) void pg_nodes_free(pg_args a, int phase) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) { Ln[i] = Lrow[sn + i]; Rn[i] = Rrow[sn + i]; }
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            u[j] = pg_dot4(L[0], Pl[j], L[1], Pl[4 + j], L[2], Pl[8 + j], L[3], Pl[12 + j]);
-            v[j] = pg_dot4(Rv[0], Pr[j], Rv[1], Pr[4 + j], Rv[2], Pr[8 + j], Rv[3], Pr[12 + j]);
-        }
-        const double x0 = u[0] * v[0], x1 = u[1] * v[1], x2 = u[2] * v[2], x3 = u[3] * v[3];
-        const double lik = pg_dot4(pi[0], x0, pi[1], x1, pi[2], x2, pi[3], x3);
-        const double inv = alpha * pg_rcp(lik);
-        acc[32] = __builtin_fma(x0, inv, acc[32]); acc[33] = __builtin_fma(x1, inv, acc[33]);
-        acc[34] = __builtin_fma(x2, inv, acc[34]); acc[35] = __builtin_fma(x3, inv, acc[35]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xb[j] = pi[j] * inv;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double tl = xb[j] * v[j], tr = xb[j] * u[j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                acc[i * 4 + j] = __builtin_fma(L[i], tl, acc[i * 4 + j]);
-                acc[16 + i * 4 + j] = __builtin_fma(Rv[i], tr, acc[16 + i * 4 + j]);
-            }
-        }
+        pg_pbar_site(L, Rv, Pl, Pr, pi, alpha, acc);
     }
-    const int q = lane >> 2, part = lane & 3;
     double* out = a.part + node * PG_PART;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {                            // the 36 sums over the wave's 64 lanes, fixed order, through its LDS rows
-#pragma unroll
-        for (int i = 0; i < 12; ++i) red[wv][i][lane] = acc[b * 12 + i];
-        __builtin_amdgcn_wave_barrier();
-        double v = 0.0;
-        if (q < 12) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v = v + red[wv][q][part + 4 * i];
-        }
-        v = v + pg_quad_sum_step<1>(v);
-        v = v + pg_quad_sum_step<2>(v);
-        if (q < 12 && part == 0) out[b * 12 + q] = v;
-        __builtin_amdgcn_wave_barrier();
-    }
+    pg_wave_sums36(acc, red[wv], [out](int i, double v) { out[i] = v; });
     // nobody adopted (r, k): G = omega, and every root slot's coefficient with it.  (Last: a store ahead of the uniform loads above
     // turns them into vector loads -- 64 more registers, and the kernel four times slower.)
     if (phase == 0) {
@@ -1171,17 +1185,11 @@ __device__ __forceinline__ void pg_nodes_rows_body(const pg_args& a, int r_arg, 
             if constexpr (ALL) pg_st_agent(orow + so + j, xb[j]); else orow[so + j] = xb[j];
             acc[32 + j] = x[j] * inv;
         }
+        double u[4], v[4];
+        pg_rowmat(L, Pl, u);
+        pg_rowmat(Rv, Pr, v);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double u = pg_dot4(L[0], Pl[j], L[1], Pl[4 + j], L[2], Pl[8 + j], L[3], Pl[12 + j]);
-            const double v = pg_dot4(Rv[0], Pr[j], Rv[1], Pr[4 + j], Rv[2], Pr[8 + j], Rv[3], Pr[12 + j]);
-            const double tl = xb[j] * v, tr = xb[j] * u;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                acc[i * 4 + j] = L[i] * tl;
-                acc[16 + i * 4 + j] = Rv[i] * tr;
-            }
-        }
+        for (int j = 0; j < 4; ++j) pg_site_pbar<false>(j, L, Rv, u[j], v[j], xb[j], acc);
     }
     if constexpr (ALL) {                                     // this tile of the adjoint row is complete: release it, then say so
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every wave's agent-scope stores are acknowledged
@@ -1426,34 +1434,8 @@ __device__ __forceinline__ void pg_pair_of(int t, int n, int& il, int& ir) {
     ir = il + 1 + rem;
 }
 
-// One site of a look-ahead merge: acc += w * { X1^T (g o v),  X2^T (g o u),  y / lik }  with u = X1 Pl, v = X2 Pr, y = u o v,
-// lik = pi . y, g = pi / lik  (the factor tau is applied by pg_twist_finish)
-__device__ __forceinline__ void pg_pbar_site(const double (&x1)[4], const double (&x2)[4], const double (&Pl)[16],
-                                             const double (&Pr)[16], const double (&pi)[4], double w, double (&acc)[PG_PART]) {
-    double u[4], v[4], y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        u[j] = pg_dot4(x1[0], Pl[j], x1[1], Pl[4 + j], x1[2], Pl[8 + j], x1[3], Pl[12 + j]);
-        v[j] = pg_dot4(x2[0], Pr[j], x2[1], Pr[4 + j], x2[2], Pr[8 + j], x2[3], Pr[12 + j]);
-        y[j] = u[j] * v[j];
-    }
-    const double lik = pg_dot4(pi[0], y[0], pi[1], y[1], pi[2], y[2], pi[3], y[3]);
-    const double inv = w * pg_rcp(lik);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double g = pi[j] * inv;
-        const double gv = g * v[j], gu = g * u[j];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            acc[i * 4 + j] = __builtin_fma(x1[i], gv, acc[i * 4 + j]);
-            acc[16 + i * 4 + j] = __builtin_fma(x2[i], gu, acc[16 + i * 4 + j]);
-        }
-        acc[32 + j] = __builtin_fma(y[j], inv, acc[32 + j]);
-    }
-}
-
-// one wave per row (4 rows per workgroup).  Rows of two coded leaves are left to pg_twist_pbar_ll.
-// The 36 sums over the wave's 64 lanes go through LDS, 12 at a time: lane (q, part) adds 16 of the 64 values of sum q.
+// one wave per row (4 rows per workgroup): the factor tau is applied by pg_twist_finish.  Rows of two coded leaves are left to
+// pg_twist_pbar_ll.
 __global__ __launch_bounds__(256, 4) void pg_twist_pbar(pg_args a) {
     __shared__ double red[4][12][PG_RED_STRIDE];
     const int lane = threadIdx.x & 63;
@@ -1484,22 +1466,7 @@ __global__ __launch_bounds__(256, 4) void pg_twist_pbar(pg_args a) {
     }
     double* out = a.tw.twpart + (size_t)row;
     const size_t nrows = (size_t)a.tw.joff[a.R];
-    const int q = lane >> 2, part = lane & 3;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {                            // a wave's own LDS rows: no workgroup barrier needed
-#pragma unroll
-        for (int i = 0; i < 12; ++i) red[wv][i][lane] = acc[b * 12 + i];
-        __builtin_amdgcn_wave_barrier();
-        double v = 0.0;
-        if (q < 12) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v = v + red[wv][q][part + 4 * i];
-        }
-        v = v + pg_quad_sum_step<1>(v);
-        v = v + pg_quad_sum_step<2>(v);
-        if (q < 12 && part == 0) out[(size_t)(b * 12 + q) * nrows] = v;
-        __builtin_amdgcn_wave_barrier();
-    }
+    pg_wave_sums36(acc, red[wv], [out, nrows](int i, double v) { out[(size_t)i * nrows] = v; });
 }
 
 // rows of two coded leaves: the site terms take one of 25 values, pair_hist holds how many sites take each.  One thread per
@@ -1646,23 +1613,18 @@ __global__ __launch_bounds__(256) void pg_twist_xchunks(pg_args a, int r, int ch
             const int side = i > i2 ? 1 : 0;                  // x is the right child of the look-ahead merge
             const int tp = side ? pg_pair_index(i2, i, n) : pg_pair_index(i, i2, n);
             const double* sr = pg_row(a, ro[i2]) + soff;
-            const double s0 = sr[0], s1 = sr[1], s2 = sr[2], s3 = sr[3];
+            const double sb[4] = {sr[0], sr[1], sr[2], sr[3]};
             for (int m = 0; m < M; ++m) {
                 const size_t row = row0 + (size_t)tp * M + m;
                 const double tau = a.tw.tau[row];
                 const double* Pme = a.tw.tw_P + row * 32 + side * 16;
                 const double* Psb = a.tw.tw_P + row * 32 + (1 - side) * 16;
                 // with z = Pme (pi o v):  lik = x . z  and the contribution (tau (pi o v) / lik) Pme^T = tau z / lik
-                double z[4];
-                {
-                    double pv[4];
+                double pv[4], z[4];
+                pg_rowmat(sb, Psb, pv);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        pv[j] = pi[j] * pg_dot4(s0, Psb[j], s1, Psb[4 + j], s2, Psb[8 + j], s3, Psb[12 + j]);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        z[q] = pg_dot4(pv[0], Pme[q * 4], pv[1], Pme[q * 4 + 1], pv[2], Pme[q * 4 + 2], pv[3], Pme[q * 4 + 3]);
-                }
+                for (int j = 0; j < 4; ++j) pv[j] = pi[j] * pv[j];
+                pg_rowmat_t(pv, Pme, z);
                 const double lik = pg_dot4(x0, z[0], x1, z[1], x2, z[2], x3, z[3]);
                 const double f = tau * pg_rcp(lik);
 #pragma unroll
