@@ -155,6 +155,22 @@ int phylo_tree_loglik(phylo_ctx* ctx, int n_nodes, int n_leaves, int S, const in
  * The sweep's state, a kept graph and a tree summary are left alone. */
 int phylo_trees_loglik(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
                        double* site_lik_TxS, phylo_stats* perf);
+/* phylo_trees_loglik under among-site rate variation: a mixture of C rate categories (rate_C[c],
+ * weight_C[c]), 1 <= C <= 16 -- discrete Gamma, +I as a category of rate 0 (expm(0) is the identity), or any other.  Bit level:
+ *   the category-c branch lengths are rate_C[c] * blen (one IEEE double multiply, on the host), so the factor f_c[t][s] =
+ *     prior . x_root[s] of category c is bit for bit site_lik of phylo_trees_loglik on (child, rate_C[c] * blen);
+ *   the site value m = weight_C[0] * f_0, then m = fma(weight_C[c], f_c, m) for c = 1 .. C-1 in ascending order;
+ *   loglik_T[t] = sum_s log m[t][s] exactly as phylo_trees_loglik sums log(prior . x_root[s]) (same site tile).
+ * The weights are the caller's: finite and >= 0, NOT normalised here (phylo_amd/rates.py builds normalised ones).
+ *   site_lik_TxS[t][s] (may be NULL) = m;  cat_lik_TxCxS[t][c][s] (may be NULL) = f_c;
+ *   perf (may be NULL): as phylo_trees_loglik, units = T S (N-1) C.
+ * State rules, per-tree checks, chunking (the same 64 MiB slab, PHYLO_TREES_CHUNK) and what is left alone are
+ * phylo_trees_loglik's; a tree's schedule is built once, not once per category.  PHYLO_EINVAL before anything is queued also for
+ * C outside 1 .. 16, a rate or weight that is not finite and >= 0, and a scaled length rate_C[c] * blen that is not finite (the
+ * message names tree, row and category). */
+int phylo_trees_loglik_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate_C,
+                             const double* weight_C, const double* prior4, double* loglik_T, double* site_lik_TxS,
+                             double* cat_lik_TxCxS, phylo_stats* perf);
 /* Test hook, no GPU needed: the host half of phylo_trees_loglik on ONE tree -- the checks above (PHYLO_EINVAL, "tree 0, row i")
  * and the slot schedule the kernel walks: ops[N-1][4] = {destination slot, left source, right source, row}, a source >= 0 a
  * leaf, a source < 0 the slot ~source; depth = slots in use (<= floor(log2 N) + 1).  tests/test_trees_host.py replays it. */

@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -435,6 +435,31 @@ class Context:
                                                  C.byref(st)))
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         return (out, sites) if want_sites else out
+
+    def trees_loglik_rates(self, child, blen, rates, weights, prior=None, want_sites=False, want_cats=False):
+        """trees_loglik under a mixture of C rate categories (phylo_trees_loglik_rates; phylo_amd.rates.rate_model builds discrete
+        Gamma and +I ones): category c scores the tree at rates[c] * blen, a site's value is sum_c weights[c] f_c by the fma chain
+        in ascending c.  The weights are used as given (finite, >= 0, not normalised).  Returns loglik [T], followed by site_lik
+        [T][S] (the mixed value) with want_sites and by cat_lik [T][C][S] (every category's factor) with want_cats;
+        self.last_trees_stats holds the call's stats."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        rates, weights = _f64(rates).reshape(-1), _f64(weights).reshape(-1)
+        if rates.shape != weights.shape:
+            raise ValueError("rates and weights must hold one value per category, got %r and %r" % (rates.shape, weights.shape))
+        nc = rates.size
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        out = np.empty(T)
+        sites = np.empty((T, self.S)) if want_sites else None
+        cats = np.empty((T, nc, self.S)) if want_cats else None
+        st = Stats()
+        self._check(self._lib.phylo_trees_loglik_rates(self._h, C.c_int(T), _ptr(child), _ptr(blen), C.c_int(nc), _ptr(rates),
+                                                       _ptr(weights), _ptr(pr), _ptr(out), _ptr(sites), _ptr(cats), C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        res = (out,) + ((sites,) if want_sites else ()) + ((cats,) if want_cats else ())
+        return res if len(res) > 1 else out
 
     def resample(self, logw, seed, step):
         w = _f64(logw).reshape(-1)

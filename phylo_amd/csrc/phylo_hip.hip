@@ -1034,66 +1034,109 @@ int phylo_tree_loglik(phylo_ctx* c, int n_nodes, int n_leaves, int S, const int3
     return PHYLO_OK;
 }
 
-int phylo_trees_loglik(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
-                       double* site_lik_TxS, phylo_stats* perf) {
+// phylo_trees_loglik (mix false: one set of matrices per tree, pt2_prune) and phylo_trees_loglik_rates (mix true, C rate categories:
+// C sets of lengths, matrices and gap rows per tree behind ONE schedule, pt2_prune_rates)
+static int trees_loglik_run(phylo_ctx* c, const char* who, int T, const int32_t* child, const double* blen, bool mix, int C, const double* rate_C,
+                            const double* weight_C, const double* prior4, double* loglik_T, double* site_lik_TxS,
+                            double* cat_lik_TxCxS, phylo_stats* perf) {
     CHK(bind(c));
-    if (!c->have_leaves || !c->have_model)
-        return fail(c, PHYLO_ESTATE, "phylo_trees_loglik needs phylo_set_leaves and phylo_set_model first");
+    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "%s needs phylo_set_leaves and phylo_set_model first", who);
     if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
-    if (!child || !blen || !loglik_T) return fail(c, PHYLO_EINVAL, "NULL pointer");
+    if (mix && (C < 1 || C > PT2_MAX_CATS)) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
+    if (!child || !blen || !loglik_T || (mix && (!rate_C || !weight_C))) return fail(c, PHYLO_EINVAL, "NULL pointer");
+    static const double one = 1.0;
+    const int nc = mix ? C : 1;                             // sets of lengths per tree; the plain call's set is the tree's own (1.0 * b == b)
+    if (!mix) rate_C = &one;
+    for (int k = 0; mix && k < C; ++k) {
+        if (!(rate_C[k] >= 0.0) || !std::isfinite(rate_C[k]))
+            return fail(c, PHYLO_EINVAL, "rate %g of category %d is not a finite number >= 0", rate_C[k], k);
+        if (!(weight_C[k] >= 0.0) || !std::isfinite(weight_C[k]))
+            return fail(c, PHYLO_EINVAL, "weight %g of category %d is not a finite number >= 0", weight_C[k], k);
+    }
     const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
+    std::vector<int> need, depth_of(mix ? (size_t)T : 0);   // (rates call) every tree's depth: can a chunk take four site steps?
+    for (int t = 0; t < T; ++t) {                          // every tree (and every scaled length) is checked before anything is queued
         int row = 0;
         char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
+        const double* b = blen + (size_t)t * R * 2;
+        if (pt2_check_tree(N, child + (size_t)t * R * 2, b, &row, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+        if (mix) {
+            pt2_needs(N, child + (size_t)t * R * 2, need);
+            depth_of[t] = need[R - 1];
+        }
+        for (int k = 0; mix && k < C; ++k)
+            for (int i = 0; i < 2 * R; ++i)
+                if (!std::isfinite(rate_C[k] * b[i]))
+                    return fail(c, PHYLO_EINVAL, "tree %d, row %d, category %d: branch length %g at rate %g is not finite", t, i / 2, k,
+                                b[i], rate_C[k]);
     }
-    // one chunk of trees in device scratch: ops | branch lengths | matrices | gap rows | tile values | results | site factors | prior
+    // one chunk of trees in device scratch: prior and weights | ops | matrices | branch lengths | gap rows | tile values | results |
+    // site values | category factors.  The rates call's four-step kernels keep the site values in that row between categories
+    // (pt2_prune_rates), so it is there, asked for or not, when a chunk is that shallow: a chunk's depth is its deepest tree's.
     const bool coded = c->leaves_coded;
-    const size_t per_tree = (size_t)R * (16 + 16 + 256 + (coded ? 64 : 0)) + (size_t)ntiles * 8 + 8 + (site_lik_TxS ? (size_t)S * 8 : 0);
-    size_t fit = PT2_SCRATCH_BYTES / per_tree;
-    if (fit < 1) fit = 1;
-    if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);   // one workgroup per (tree, tile)
-    const int chunk = (int)std::min<size_t>((size_t)T, c->env.trees_chunk > 0 ? std::min<size_t>(fit, (size_t)c->env.trees_chunk) : fit);
+    bool sites = site_lik_TxS != nullptr;
+    size_t per_tree = 0;
+    int chunk = 0;
+    for (;;) {
+        per_tree = (size_t)R * 16 + (size_t)nc * R * (16 + 256 + (coded ? 64 : 0)) + (size_t)ntiles * 8 + 8 +
+                   (sites ? (size_t)S * 8 : 0) + (cat_lik_TxCxS ? (size_t)nc * S * 8 : 0);
+        size_t fit = PT2_SCRATCH_BYTES / per_tree;
+        if (fit < 1) fit = 1;
+        if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);   // one workgroup per (tree, tile)
+        chunk = (int)std::min<size_t>((size_t)T, c->env.trees_chunk > 0 ? std::min<size_t>(fit, (size_t)c->env.trees_chunk) : fit);
+        if (!mix || sites) break;
+        for (int t0 = 0; t0 < T && !sites; t0 += chunk)     // the chunks without the row: is one of them that shallow?
+            sites = pt2_unroll(*std::max_element(depth_of.begin() + t0, depth_of.begin() + std::min(T, t0 + chunk))) == 4;
+        if (!sites) break;
+    }
     void* slab = nullptr;
-    CHK(scratch_get(c, 14, per_tree * chunk + 32 + 256, &slab));
+    CHK(scratch_get(c, 14, per_tree * chunk + 32 + PT2_MAX_CATS * 8 + 256, &slab));
     char* p = (char*)slab;
     auto carve = [&](size_t bytes) { char* q = p; p += (bytes + 15) & ~(size_t)15; return q; };
-    double* d_prior = (double*)carve(32);
+    double* d_prior = (double*)carve(32 + PT2_MAX_CATS * 8);   // the prior, then the weights: one pointer for pt2_prune_rates
     int32_t* d_ops = (int32_t*)carve((size_t)chunk * R * 16);
-    double* d_P = (double*)carve((size_t)chunk * R * 256);
-    double* d_t = (double*)carve((size_t)chunk * R * 16);
-    double* d_gap = coded ? (double*)carve((size_t)chunk * R * 64) : nullptr;
+    double* d_P = (double*)carve((size_t)chunk * nc * R * 256);
+    double* d_t = (double*)carve((size_t)chunk * nc * R * 16);
+    double* d_gap = coded ? (double*)carve((size_t)chunk * nc * R * 64) : nullptr;
     double* d_tilev = (double*)carve((size_t)chunk * ntiles * 8);
     double* d_out = (double*)carve((size_t)chunk * 8);
-    double* d_site = site_lik_TxS ? (double*)carve((size_t)chunk * S * 8) : nullptr;
+    double* d_site = sites ? (double*)carve((size_t)chunk * S * 8) : nullptr;
+    double* d_cat = cat_lik_TxCxS ? (double*)carve((size_t)chunk * nc * S * 8) : nullptr;
     if (!c->ev_tl0) {
         HIPCHK(c, hipEventCreate(&c->ev_tl0));
         HIPCHK(c, hipEventCreate(&c->ev_tl1));
     }
     if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    else if (mix) HIPCHK(c, hipMemcpyAsync(d_prior, c->d_pi, 32, hipMemcpyDeviceToDevice, c->stream));
+    if (mix) HIPCHK(c, hipMemcpyAsync(d_prior + 4, weight_C, (size_t)C * 8, hipMemcpyHostToDevice, c->stream));
     std::vector<int32_t> ops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * R * 2);
+    std::vector<double> ts((size_t)chunk * nc * R * 2);
     double ms_total = 0.0;
     int launches = 0;
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int n = std::min(chunk, T - t0);
         int depth = 1;
-        for (int t = 0; t < n; ++t) {
+        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every set of lengths in its order
             int32_t* o = ops.data() + (size_t)t * R * 4;
             const int d = pt2_schedule(N, child + (size_t)(t0 + t) * R * 2, o);
             depth = std::max(depth, d);
             const double* b = blen + (size_t)(t0 + t) * R * 2;
-            for (int i = 0; i < R; ++i) {                   // branch lengths in schedule order
-                ts[((size_t)t * R + i) * 2] = b[2 * o[4 * i + 3]];
-                ts[((size_t)t * R + i) * 2 + 1] = b[2 * o[4 * i + 3] + 1];
+            for (int k = 0; k < nc; ++k) {
+                double* tk = ts.data() + ((size_t)t * nc + k) * R * 2;
+                for (int i = 0; i < R; ++i) {
+                    tk[2 * i] = rate_C[k] * b[2 * o[4 * i + 3]];
+                    tk[2 * i + 1] = rate_C[k] * b[2 * o[4 * i + 3] + 1];
+                }
             }
         }
         if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+        if (mix && !d_site && pt2_unroll(depth) == 4)       // (never: the chunks were looked at above, by pt2_needs' depths)
+            return fail(c, PHYLO_EINVAL, "a chunk of depth %d without the row of site values its kernel needs", depth);
         HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * nc * R * 16, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->ev_tl0, c->stream));
-        const long n_mat = (long)n * R * 2;
+        const long n_mat = (long)n * nc * R * 2;
         hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
         CHK(launch_check(c, "pk_expm_batched"));
         ++launches;
@@ -1102,19 +1145,23 @@ int phylo_trees_loglik(phylo_ctx* c, int T, const int32_t* child, const double* 
             CHK(launch_check(c, "pt2_gap_rows"));
             ++launches;
         }
-        pt2_args a{};
+        pt2_rates_args ra{};
+        pt2_args& a = ra.a;
         a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
+        a.prior = prior4 || mix ? d_prior : c->d_pi;
         a.tilev = d_tilev; a.site_lik = d_site;
         a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        pt2_launch(a, n, depth, coded, c->stream);
-        CHK(launch_check(c, "pt2_prune"));
+        ra.cat_lik = d_cat; ra.C = C;
+        if (mix) pt2_launch_rates(ra, n, depth, coded, c->stream);
+        else pt2_launch(a, n, depth, coded, c->stream);
+        CHK(launch_check(c, mix ? "pt2_prune_rates" : "pt2_prune"));
         hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
         CHK(launch_check(c, "pt2_finish"));
         launches += 2;
         HIPCHK(c, hipEventRecord(c->ev_tl1, c->stream));
         HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-        if (d_site) HIPCHK(c, hipMemcpyAsync(site_lik_TxS + (size_t)t0 * S, d_site, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
+        if (site_lik_TxS) HIPCHK(c, hipMemcpyAsync(site_lik_TxS + (size_t)t0 * S, d_site, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_cat) HIPCHK(c, hipMemcpyAsync(cat_lik_TxCxS + (size_t)t0 * nc * S, d_cat, (size_t)n * nc * S * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
         float ms = 0.f;
         HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tl0, c->ev_tl1));
@@ -1124,11 +1171,22 @@ int phylo_trees_loglik(phylo_ctx* c, int T, const int32_t* child, const double* 
         phylo_stats st{};
         st.sweep_ms = ms_total;
         st.n_launches = launches;
-        st.units = (double)T * S * R;
+        st.units = (double)T * S * R * nc;
         st.alg_bytes = 96.0 * st.units;
         *perf = st;
     }
     return PHYLO_OK;
+}
+
+int phylo_trees_loglik(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
+                       double* site_lik_TxS, phylo_stats* perf) {
+    return trees_loglik_run(c, "phylo_trees_loglik", T, child, blen, false, 0, nullptr, nullptr, prior4, loglik_T, site_lik_TxS, nullptr, perf);
+}
+
+int phylo_trees_loglik_rates(phylo_ctx* c, int T, const int32_t* child, const double* blen, int C, const double* rate_C,
+                             const double* weight_C, const double* prior4, double* loglik_T, double* site_lik_TxS,
+                             double* cat_lik_TxCxS, phylo_stats* perf) {
+    return trees_loglik_run(c, "phylo_trees_loglik_rates", T, child, blen, true, C, rate_C, weight_C, prior4, loglik_T, site_lik_TxS, cat_lik_TxCxS, perf);
 }
 
 int phylo_debug_tree_schedule(int N, const int32_t* child, const double* blen, int32_t* ops, int32_t* depth) {

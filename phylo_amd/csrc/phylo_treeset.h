@@ -16,6 +16,7 @@
 #define PT2_MAX_DEPTH 10                          // floor(log2 PK_MAX_TAXA) + 1 slots
 #define PT2_SLOT_BYTES 2048                       // one slot of one site step: 64 lanes x 4 doubles
 #define PT2_WAVE_LDS (20 * 1024)                  // four site steps per pass while the stack stays within this, else two
+#define PT2_MAX_CATS 16                           // rate categories of phylo_trees_loglik_rates
 #define PT2_SCRATCH_BYTES ((size_t)64 << 20)      // device scratch of one chunk of trees (phylo_trees_loglik cuts T to fit)
 
 // ------------------------------------------------------------------------------------------------
@@ -48,12 +49,11 @@ inline int pt2_check_tree(int N, const int32_t* child, const double* blen, int* 
     return 0;
 }
 
-// The schedule of a checked tree: N-1 operations {destination slot, left source, right source, row}; a source >= 0 is a leaf,
-// a source < 0 the slot ~source.  Children-first, the child with the larger slot need first (Sethi-Ullman), the destination
-// takes over the slot of an internal child: a tree of N leaves never holds more than floor(log2 N) + 1 slots.  Returns the depth.
-inline int pt2_schedule(int N, const int32_t* child, int32_t* ops /*[N-1][4]*/) {
+// the slots every row's subtree needs (Sethi-Ullman); need[N-2], the root's, is the depth pt2_schedule returns
+// (no schedule holds fewer, and pt2_schedule's holds no more: DESIGN.md section 11)
+inline void pt2_needs(int N, const int32_t* child, std::vector<int>& need) {
     const int R = N - 1;
-    std::vector<int> need((size_t)R), slot_of((size_t)R, -1), stack, free_slots;
+    need.resize((size_t)R);
     for (int i = 0; i < R; ++i) {
         const int a = child[2 * i], b = child[2 * i + 1];
         int na = a < N ? 0 : need[a - N], nb = b < N ? 0 : need[b - N];
@@ -61,6 +61,15 @@ inline int pt2_schedule(int N, const int32_t* child, int32_t* ops /*[N-1][4]*/) 
         const int m = nb + (na > 0 ? 1 : 0);
         need[i] = na > m ? na : (m > 1 ? m : 1);
     }
+}
+
+// The schedule of a checked tree: N-1 operations {destination slot, left source, right source, row}; a source >= 0 is a leaf,
+// a source < 0 the slot ~source.  Children-first, the child with the larger slot need first (Sethi-Ullman), the destination
+// takes over the slot of an internal child: a tree of N leaves never holds more than floor(log2 N) + 1 slots.  Returns the depth.
+inline int pt2_schedule(int N, const int32_t* child, int32_t* ops /*[N-1][4]*/) {
+    const int R = N - 1;
+    std::vector<int> need, slot_of((size_t)R, -1), stack, free_slots;
+    pt2_needs(N, child, need);
     std::vector<unsigned char> state((size_t)R, 0);
     int n_ops = 0, depth = 0, next_slot = 0;
     stack.push_back(R - 1);
@@ -241,6 +250,136 @@ __global__ __launch_bounds__(64) void pt2_prune(const pt2_args a) {
     }
     const double t = pk_wave_tree_sum(pm_lp_finish(col));
     if (lane == 0) a.tilev[(size_t)tree * a.ntiles + tile] = t;
+}
+
+// The rates form: C categories of one tree in one wave.  Matrices and gap rows of a tree are laid out
+// [category][op][left|right] (the host scaled the lengths: rate[c] * blen, so the kernel reads no rate), the schedule is the
+// tree's one schedule, read once per category and pass.  Inside a pass the categories run outermost over the same LDS stack; a
+// lane keeps U site values m[u] = weight[0] f_0, then pm_fma(weight[c], f_c, m[u]) in ascending c (in registers at U = 2, in its
+// own entries of site_lik at U = 4: see the kernel), which enter pm_lp_mul where pt2_prune's lik does.  A sibling of pt2_prune over the same pt2_side, so that pt2_prune's code objects stay what they are.
+struct pt2_rates_args {
+    pt2_args a;                      // P [trees][C][N-1][2][16], gap [trees][C][N-1][2][4]; site_lik the mixed value (NULL only at U = 2);
+                                     // prior [4 + C]: the prior, then the weights (wave-uniform, one pointer for both)
+    double* cat_lik;                 // [trees][C][S] the factor of every category, or NULL
+    int C;
+};
+
+// The kernel's own arguments, read again where they are used: what a category's tail and a pass's tail need (prior, weights and
+// the three output pointers) is fetched there by scalar loads from the kernel-argument segment, not held in scalar registers
+// across the operation loop, which already fills them with two matrices (pt2_prune sits at 93 .. 106 of 106).
+typedef __attribute__((address_space(4))) const struct pt2_rates_args pt2_ckarg;
+__device__ __forceinline__ pt2_ckarg* pt2_kernarg_here() {
+    pt2_ckarg* k = (pt2_ckarg*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));                             // (a load through k stays below this point)
+    return k;
+}
+
+template <int U, bool CODED>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(U == 4 ? 4 : (CODED ? 7 : 5)))) void pt2_prune_rates(const pt2_rates_args ra) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pt2_lds[];
+    pk_d2* stack = reinterpret_cast<pk_d2*>(pt2_lds);
+    const pt2_args& a = ra.a;
+    const int lane = threadIdx.x;
+    const int tree = blockIdx.x / a.ntiles, tile = blockIdx.x - tree * a.ntiles;
+    const int R = a.N - 1;
+    const int s0 = tile * a.T, s1 = s0 + a.T < a.S ? s0 + a.T : a.S;
+    pt2_ci4* ops = (pt2_ci4*)(a.ops + (size_t)tree * R * 4);
+    const double* P = a.P + (size_t)tree * ra.C * R * 32;   // category c's matrices and gap rows: stepped, and stepped back per pass
+    const double* G = CODED ? a.gap + (size_t)tree * ra.C * R * 8 : nullptr;
+    // The site values m[u] live in registers across the categories at two site steps.  At four, pt2_prune stands at 116 (coded)
+    // and 128 (generic) VGPRs and 8 more cost a wave per SIMD (130 and 136) or, held to 128, a spill: there a lane keeps them in
+    // its own entries of site_lik (which the host then provides, asked for or not), one 8-byte load and store per site and
+    // category beside N-1 operations.  The bits are the same: a double goes through memory unchanged.
+    constexpr bool VIA_SITE = U == 4;
+    pm_lp col = pm_lp_init();
+#pragma unroll 1
+    for (int base = s0; base < s1; base += 64 * U) {       // base: wave-uniform
+        unsigned int sc[U];                                 // a site past the end re-reads the last one; its factors are dropped
+        double m[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int s = base + 64 * u + lane;
+            sc[u] = (unsigned int)(s < s1 ? s : s1 - 1);
+            m[u] = 0.0;
+        }
+#pragma unroll 1
+        for (int c = 0;;) {                                 // c: wave-uniform, C >= 1
+            double o[U][4];
+#pragma unroll 1
+            for (int i = 0; i < R; ++i) {
+                const pt2_i4 op = ops[i];
+                double l[U][4], r[U][4];
+                pt2_side<U, CODED>(a, op.y, P + (size_t)i * 32, CODED ? G + (size_t)i * 8 : nullptr, stack, sc, lane, l);
+                pt2_side<U, CODED>(a, op.z, P + (size_t)i * 32 + 16, CODED ? G + (size_t)i * 8 + 4 : nullptr, stack, sc, lane, r);
+                pk_d2* dst = stack + (size_t)op.x * U * 128 + lane;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[u][j] = l[u][j] * r[u][j];
+                    const pk_d2 lo = {o[u][0], o[u][1]}, hi = {o[u][2], o[u][3]};
+                    dst[u * 128] = lo;
+                    dst[u * 128 + 64] = hi;
+                }
+            }
+            pt2_ckarg* k = pt2_kernarg_here();
+            const int C = k->C;
+            int e1 = __builtin_amdgcn_readfirstlane(s1);    // (the tail's tests are made here, not kept as masks across the loops)
+            asm volatile("" : "+s"(e1));
+            pt2_cd* prc = (pt2_cd*)k->a.prior;
+            const double pr[4] = {prc[0], prc[1], prc[2], prc[3]};
+            const double w = prc[4 + c];
+            double* F = k->cat_lik;
+            if (F) F += ((size_t)tree * C + c) * a.S;
+            double* sl = k->a.site_lik + (size_t)tree * a.S;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int s = base + 64 * u + lane;
+                if (base + 64 * u < e1) {                   // wave-uniform
+                    const double f = pk_site_lik(pr, o[u]);
+                    if (F && s < e1) F[s] = f;
+                    if constexpr (VIA_SITE) {
+                        if (s < e1) sl[s] = c ? pm_fma(w, f, sl[s]) : w * f;
+                    } else m[u] = c ? pm_fma(w, f, m[u]) : w * f;
+                }
+            }
+            P += (size_t)R * 32;
+            if (CODED) G += (size_t)R * 8;
+            if (++c == C) {
+                P -= (size_t)C * R * 32;
+                if (CODED) G -= (size_t)C * R * 8;
+                break;
+            }
+        }
+        double* sl = pt2_kernarg_here()->a.site_lik;
+        if (sl) sl += (size_t)tree * a.S;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int s = base + 64 * u + lane;
+            if (s < s1) {
+                if constexpr (VIA_SITE) m[u] = sl[s];
+                else if (sl) sl[s] = m[u];
+                pm_lp_mul(col, m[u]);
+            }
+        }
+    }
+    const double t = pk_wave_tree_sum(pm_lp_finish(col));
+    pt2_ckarg* k = pt2_kernarg_here();
+    if (lane == 0) k->a.tilev[(size_t)blockIdx.x] = t;       // [tree][tile]: the workgroup's own index
+}
+
+template <int U, bool CODED>
+inline void pt2_launch_rates_as(const pt2_rates_args& ra, int trees, int depth, hipStream_t s) {
+    hipLaunchKernelGGL((pt2_prune_rates<U, CODED>), dim3((unsigned)trees * ra.a.ntiles), dim3(64), (size_t)depth * U * PT2_SLOT_BYTES, s, ra);
+}
+inline void pt2_launch_rates(const pt2_rates_args& ra, int trees, int depth, bool coded, hipStream_t s) {
+    const int U = pt2_unroll(depth);
+    if (coded) {
+        if (U == 4) pt2_launch_rates_as<4, true>(ra, trees, depth, s);
+        else pt2_launch_rates_as<2, true>(ra, trees, depth, s);
+    } else {
+        if (U == 4) pt2_launch_rates_as<4, false>(ra, trees, depth, s);
+        else pt2_launch_rates_as<2, false>(ra, trees, depth, s);
+    }
 }
 
 // a tree's tile values, added left to right (as pk_tile_epilogue and pk_row_loglik add them)

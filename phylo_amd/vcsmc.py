@@ -304,33 +304,44 @@ class VCSMC:
             tab = new
         return [row[0] for row in tab]
 
-    def score_trees(self, newicks):
+    def score_trees(self, newicks, rates=None):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
-        distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  Returns a list
-        of floats; a local call on every rank when sharded."""
+        distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
+        (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
+        rates (phylo_trees_loglik_rates).  Returns a list of floats; a local call on every rank when sharded."""
         rows = [treepost.newick_to_rows(nw, self.taxa) for nw in newicks]
         if not rows:
             return []
         ctx = self._context()
-        ll = ctx.trees_loglik(np.array([r[0] for r in rows]), np.array([r[1] for r in rows]))
+        child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+        ll = ctx.trees_loglik(child, blen) if rates is None else ctx.trees_loglik_rates(child, blen, rates[0], rates[1])
         return [float(x) for x in ll]
 
     def _tree_scores(self, path):
         """tree_scores.json of --score_trees: the file's trees, and with branch lengths in the posterior also map.tre,
-        consensus_bl.tre and the ten most probable topologies at their mean lengths (None where a branch has no estimate)"""
+        consensus_bl.tre and the ten most probable topologies at their mean lengths (None where a branch has no estimate);
+        with --score_rates every one of these scores is under that rate model, which the file then names"""
         with open(path) as f:
             newicks = [line.strip() for line in f if line.strip()]
-        ll = self.score_trees(newicks)
+        spec = getattr(self.args, 'score_rates', None)
+        rm = None
+        if spec:
+            from . import rates as rates_mod
+            rm = rates_mod.parse_spec(spec)
+        mix = None if rm is None else (rm['rates'], rm['weights'])
+        ll = self.score_trees(newicks, rates=mix)
         out = {'model': {'Q': np.asarray(self.Qmatrix, dtype=np.float64).tolist(),
                          'pi': np.asarray(self.stationary_probs, dtype=np.float64).reshape(-1).tolist(),
                          'jc69_closed_form': bool(self.args.jcmodel)},
                'trees': [{'newick': nw, 'loglik': x} for nw, x in zip(newicks, ll)],
                'best': int(np.argmax(ll)) if ll else None}
+        if rm is not None:                                 # (absent without --score_rates: the file is what it was before the flag)
+            out['rates'] = {'spec': rm['spec'], 'rates': rm['rates'].tolist(), 'weights': rm['weights'].tolist()}
         post = self.posterior
         if post is not None and getattr(post, 'map_newick', None) is not None:
             def scored(nw):
                 try:
-                    return {'newick': nw, 'loglik': self.score_trees([nw])[0]}
+                    return {'newick': nw, 'loglik': self.score_trees([nw], rates=mix)[0]}
                 except ValueError as e:                    # a branch held only by particles of weight 0 has no mean length
                     return {'newick': nw, 'loglik': None, 'error': str(e)}
 
@@ -350,7 +361,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))

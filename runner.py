@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -62,7 +62,20 @@ def parse_args(argv=None):
                              "distribution at the root) go into tree_scores.json in the results directory, with the index of the "
                              "best one; with --tree_branches true also the scores of map.tre, consensus_bl.tre and the ten most "
                              "probable topologies at their mean branch lengths")
+    parser.add_argument('--score_rates', default=None, metavar='gamma:ALPHA:C[:PINV]',
+                        help="with --score_trees: score under among-site rate variation -- C discrete Gamma categories of shape "
+                             "ALPHA (Yang 1994, mean rates), and with PINV > 0 a class of invariant sites of that proportion (the "
+                             "rates of the variable sites are not rescaled); every score in tree_scores.json is then under that "
+                             "model, and the file names its rates and weights")
     args = parser.parse_args(argv)
+    if args.score_rates is not None:
+        if not args.score_trees:
+            parser.error('--score_rates needs --score_trees FILE (it is the rate model those trees are scored under)')
+        from phylo_amd import rates
+        try:
+            rates.parse_spec(args.score_rates)
+        except ValueError as e:
+            parser.error('--score_rates: %s' % e)
     if args.tree_branches and not args.tree_summary:
         parser.error('--tree_branches true needs --tree_summary true (it adds branch lengths to that summary)')
     if args.twisting is not None:

@@ -5,7 +5,13 @@ two agree bit for bit, and report units/s.
     python tools/trees_probe.py --dataset hohna_data --trees 4096 --reps 7 --out profiles/trees_probe.jsonl
 
 The batched call is timed whole (wall, and perf.sweep_ms from hipEvents) `reps` times; the loop is timed over `--loop_trees` of
-the trees (all of them by default) `loop_reps` times.  Medians with the quartiles.  Appends one JSON line to --out."""
+the trees (all of them by default) `loop_reps` times.  Medians with the quartiles.  Appends one JSON line to --out.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --rates 4 --reps 7 --out profiles/trees_probe.jsonl
+
+--rates C times phylo_trees_loglik_rates under C discrete Gamma categories (--alpha) instead, against C
+plain phylo_trees_loglik calls on the scaled trees in the same run: device and wall times of both, their ratios, and whether
+cat_lik carries the plain calls' site factors bit for bit."""
 import argparse
 import json
 import os
@@ -38,6 +44,58 @@ def quartiles(x):
     return {'median': float(q2), 'q1': float(q1), 'q3': float(q3)}
 
 
+def rates_probe(a):
+    """the rates call against C plain calls on the scaled trees: same trees, same context, same run"""
+    from phylo_amd import rates as R
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    rates, weights = R.rate_model(a.alpha, a.rates)
+    C = rates.size
+    scaled = [rates[c] * blen for c in range(C)]             # (outside the timed region: the caller of C plain calls holds them)
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        ll, cats = ctx.trees_loglik_rates(child, blen, rates, weights, want_cats=True)     # warm-up, and the factors to compare
+        same = True
+        for c in range(C):
+            _, f = ctx.trees_loglik(child, scaled[c], want_sites=True)                     # warm-up of the plain call too
+            same = same and bool(np.array_equal(f.view(np.uint64), np.ascontiguousarray(cats[:, c]).view(np.uint64)))
+        del cats
+        wall, dev, pwall, pdev = [], [], [], []
+        for _ in range(a.reps):                              # interleaved: both see the same machine
+            t0 = time.perf_counter()
+            ll = ctx.trees_loglik_rates(child, blen, rates, weights)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            dev.append(ctx.last_trees_stats['sweep_ms'])
+            stats = dict(ctx.last_trees_stats)
+            t0 = time.perf_counter()
+            d = 0.0
+            for c in range(C):
+                ctx.trees_loglik(child, scaled[c])
+                d += ctx.last_trees_stats['sweep_ms']
+            pwall.append((time.perf_counter() - t0) * 1e3)
+            pdev.append(d)
+    w, d, pw, pd = quartiles(wall), quartiles(dev), quartiles(pwall), quartiles(pdev)
+    rec = {'probe': 'trees_loglik_rates', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'jc': jc, 'reps': a.reps,
+           'C': int(C), 'alpha': a.alpha, 'rates': rates.tolist(),
+           'rates_wall_ms': w, 'rates_device_ms': d, 'plain_x_C_wall_ms': pw, 'plain_x_C_device_ms': pd,
+           'device_ratio_rates_over_plain_x_C': d['median'] / pd['median'], 'wall_ratio_rates_over_plain_x_C': w['median'] / pw['median'],
+           'launches': stats['n_launches'], 'units': stats['units'], 'units_per_s_device': stats['units'] / (d['median'] * 1e-3),
+           'cat_lik_bit_equal': same, 'finite': bool(np.isfinite(ll).all())}
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -48,7 +106,11 @@ def main(argv=None):
     ap.add_argument('--jc', default='false')
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--rates', type=int, default=0, help='C > 0: probe phylo_trees_loglik_rates under C Gamma categories')
+    ap.add_argument('--alpha', type=float, default=0.5)
     a = ap.parse_args(argv)
+    if a.rates > 0:
+        return rates_probe(a)
     jc = a.jc.lower() == 'true'
     g = load_dataset(a.dataset)['genome']
     N, S, _ = g.shape
