@@ -341,6 +341,20 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
  * nC = ceil(ceil(S / 64) / 16), sites >= S hold the pad code 5.  *need = N nC 1024, the image's bytes; with packed NULL only
  * *need is set, otherwise cap >= *need is required.  tests/test_packed_codes_cpu.py restates the layout. */
 int phylo_debug_pack_leaf_codes(const uint8_t* codes, int N, int S, uint8_t* packed, int64_t cap, int64_t* need);
+/* Test hooks of the merge's site-pattern form (phylo_site_patterns.h), the first two without a GPU.
+ * phylo_debug_site_patterns: the tables phylo_set_leaves builds from byte codes [N][S].  *U = the number of distinct columns,
+ * numbered by first occurrence; rep[u], u < *U: the first site with column u (room for S); image (16 bits per site, room for
+ * 2048 ceil(ceil(S / 64) / 16) bytes, written when *U <= 8191): image[((Jc 2 + h) 64 + c) 8 + j] = 8 (column number of site
+ * 64 (16 Jc + 8 h + j) + c), 8 *U at sites >= S; rep_off (1024 words, written when *U <= 512): 32 rep[u], 0 from *U on; rep_leaf
+ * (written when *U <= 512, rep_leaf_cap >= N 1024 always suffices): the codes [N][*U] of the representative sites as
+ * phylo_debug_pack_leaf_codes packs them.  Each output may be NULL.
+ * phylo_debug_site_patterns_rule: 1 if a context of S sites in ntiles site tiles whose leaves have U distinct columns and are coded
+ * (coded != 0) takes the form under PHYLO_SITE_PATTERNS = 0 (sw 0), unset (1) or force (2), else 0; -1 for bad arguments.
+ * phylo_debug_site_patterns_of: *U of the context's current leaves (0: not coded) and whether its record-form merges take the form. */
+int phylo_debug_site_patterns(const uint8_t* codes, int N, int S, int32_t* U, int32_t* rep, uint16_t* image, uint32_t* rep_off,
+                              uint8_t* rep_leaf, int64_t rep_leaf_cap);
+int phylo_debug_site_patterns_rule(int S, int U, int coded, int ntiles, int sw);
+int phylo_debug_site_patterns_of(phylo_ctx* ctx, int32_t* U, int32_t* taken);
 /* ... after a batched sweep of G groups (K the total): the device lists' limit is per group (K / G <= 8192), every other
  * limit sees the totals.  G = 1 is phylo_debug_reverse_plan. */
 int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,

@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_tree_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -190,6 +190,44 @@ def debug_pack_leaf_codes(codes):
     if rc:
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     return out.reshape(N, -1, 64, 16)
+
+
+SITE_PATTERN_SWITCH = {"0": 0, None: 1, "force": 2}        # PHYLO_SITE_PATTERNS
+
+
+def debug_site_patterns(codes):
+    """The site-pattern tables phylo_set_leaves builds from byte codes [N][S] (phylo_site_patterns.h; no GPU needed): a dict with U,
+    rep [U], image (uint16 [nC][2][64][8]: [Jc][h][c][j] = 8 * the column number of site 64 (16 Jc + 8 h + j) + c, 8 U at sites >= S;
+    None when U > 8191), rep_off (uint32 [1024]) and rep_leaf (uint8 [N][1][64][16], the packed codes of the representative sites);
+    the last two None when U > 512."""
+    lib = load()
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.ndim != 2:
+        raise ValueError("codes must be [N][S]")
+    N, S = cd.shape
+    nC = -(-(-(-S // 64)) // 16)
+    U = C.c_int32(0)
+    rep = np.full(S, -1, dtype=np.int32)
+    image = np.full(nC * 1024, 0xffff, dtype=np.uint16)
+    rep_off = np.full(1024, 0xffffffff, dtype=np.uint32)
+    rep_leaf = np.full(N * 1024, 0xff, dtype=np.uint8)
+    rc = lib.phylo_debug_site_patterns(_ptr(cd), C.c_int(N), C.c_int(S), C.byref(U), _ptr(rep), _ptr(image), _ptr(rep_off), _ptr(rep_leaf),
+                                       C.c_int64(rep_leaf.size))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    u = U.value
+    return {"U": u, "rep": rep[:u].copy(), "image": image.reshape(nC, 2, 64, 8) if u <= 8191 else None,
+            "rep_off": rep_off if u <= 512 else None,
+            "rep_leaf": rep_leaf[:N * 1024 * (-(-(-(-u // 64)) // 16))].reshape(N, -1, 64, 16) if u <= 512 else None}
+
+
+def debug_site_patterns_rule(S, U, coded=True, ntiles=1, switch=None):
+    """Does a context take the merge's site-pattern form (no GPU needed)?  switch: PHYLO_SITE_PATTERNS' value, "0", None or "force"."""
+    lib = load()
+    rc = lib.phylo_debug_site_patterns_rule(C.c_int(S), C.c_int(U), C.c_int(int(coded)), C.c_int(ntiles), C.c_int(SITE_PATTERN_SWITCH[switch]))
+    if rc < 0:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return bool(rc)
 
 
 TREE_SUMMARY_BUFS = ("u", "U", "bits", "kA", "kB", "val", "scan", "weight", "srt", "hp", "o_cbits", "o_cw", "o_tw", "child", "slot", "o_cg",
@@ -728,6 +766,13 @@ class Context:
         used, cap = C.c_int(0), C.c_int(0)
         self._check(self._lib.phylo_debug_remote_cache(self._h, C.byref(used), C.byref(cap)))
         return used.value, cap.value
+
+    def debug_site_patterns(self):
+        """(U, taken): the distinct columns of the current leaves (0: not coded) and whether the record-form merge takes the
+        site-pattern form for them (phylo_site_patterns.h)"""
+        U, taken = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.phylo_debug_site_patterns_of(self._h, C.byref(U), C.byref(taken)))
+        return U.value, bool(taken.value)
 
     def comm_exchange_kind(self):
         """'none' | 'rccl' | 'hostshm' | 'p2p': how the K-vectors of a rank event reach the other ranks"""

@@ -19,6 +19,7 @@
 #include "phylo_comm.h"
 #include "phylo_kernels.h"
 #include "phylo_packed_codes.h"
+#include "phylo_site_patterns.h"
 #include "phylo_persist.h"
 #include "phylo_grad.h"
 #include "phylo_revlists_dev.h"
@@ -63,6 +64,7 @@ struct env_switches {
     int persist_nt = 256;                // PHYLO_PERSIST_NT: threads per workgroup of the one-launch sweep (256 or 512)
     int remote_cache_cap = 0;            // PHYLO_REMOTE_CACHE_CAP: slots of the local cache of remote nodes (0 = 512 MB worth; tests lower it)
     int scan_multi_min = 4096;           // PHYLO_SCAN_MULTI_MIN: groups of more weights than this are scanned by several workgroups
+    int site_patterns = PK_PAT_AUTO;     // PHYLO_SITE_PATTERNS: 0 = never the pattern form of the merge, force = wherever it is valid
     int trees_chunk = 0;                 // PHYLO_TREES_CHUNK: trees per chunk of phylo_trees_loglik (0 = what PT2_SCRATCH_BYTES holds; tests lower it)
     void read() {
         eager_nodes = getenv("PHYLO_EAGER_NODES") != nullptr;
@@ -78,6 +80,7 @@ struct env_switches {
         rev_host_lists = getenv("PHYLO_REV_HOST_LISTS") != nullptr;
         no_remote_cache = getenv("PHYLO_NO_REMOTE_CACHE") != nullptr;
         { const char* e = getenv("PHYLO_REMOTE_CACHE_CAP"); remote_cache_cap = e ? atoi(e) : 0; }
+        { const char* e = getenv("PHYLO_SITE_PATTERNS"); site_patterns = !e ? PK_PAT_AUTO : !strcmp(e, "force") ? PK_PAT_FORCE : atoi(e) == 0 ? PK_PAT_OFF : PK_PAT_AUTO; }
         { const char* e = getenv("PHYLO_SCAN_MULTI_MIN"); scan_multi_min = e ? atoi(e) : 4096; }
         { const char* e = getenv("PHYLO_TREES_CHUNK"); trees_chunk = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_P2P"); no_p2p = e && atoi(e) == 0; }
@@ -119,6 +122,8 @@ struct phylo_ctx {
     double* d_leaves = nullptr;          // [N][S][4]
     uint8_t* d_leaf_codes = nullptr;     // [N][S]; in use only when every leaf row is one-hot or all-ones
     uint8_t* d_leaf_packed = nullptr;    // the same codes as 16-byte words per lane (phylo_packed_codes.h), behind them in one buffer
+    uint8_t* d_pat = nullptr;            // behind both, the site-pattern tables (phylo_site_patterns.h): pattern image, representatives,
+    int pat_U = 0;                       // representative leaf image; pat_U: distinct columns of the current leaves (0: not coded)
     bool leaves_coded = false;
     uint32_t* d_pair_hist = nullptr;     // [N][N][32] code-pair site counts of coded leaves (built on the first twisted sweep)
     bool hist_ready = false, codes_valid = false;
@@ -726,8 +731,9 @@ int phylo_create(const int* device_ids, int n_gpus, int K, int N, int S, int A, 
         c->d_lam_r = c->d_Q + 20 + N;
         if ((rc = dalloc(c, &c->d_ldf, (size_t)N + 1)) != PHYLO_OK) break;
         if ((rc = dalloc(c, &c->d_leaves, (size_t)N * S * 4)) != PHYLO_OK) break;
-        if ((rc = dalloc(c, &c->d_leaf_codes, pk_codes_image_bytes(N, S))) != PHYLO_OK) break;
+        if ((rc = dalloc(c, &c->d_leaf_codes, pk_leaf_image_bytes(N, S))) != PHYLO_OK) break;
         c->d_leaf_packed = c->d_leaf_codes + pk_packed_offset(N, S);
+        c->d_pat = c->d_leaf_codes + pk_pat_offset(N, S);
         // table of log (2 max(c,2) - 3)!! by leaf count c = 0..N
         c->h_ldf.resize((size_t)N + 1);
         for (int cnt = 0; cnt <= N; ++cnt) c->h_ldf[cnt] = host_log_double_factorial(2 * (cnt > 2 ? cnt : 2) - 3);
@@ -812,7 +818,7 @@ int phylo_set_leaves(phylo_ctx* c, const double* genome) {
     // wait for the device (a training step on site minibatches sets new leaves every time).  Only a previous upload still in
     // flight has to be over before the image is overwritten.
     const size_t rows = (size_t)c->N * c->S;
-    const size_t code_bytes = pk_codes_image_bytes(c->N, c->S);
+    const size_t code_bytes = pk_leaf_image_bytes(c->N, c->S);
     const bool pinned = rows * 32 + code_bytes <= ((size_t)8 << 20);     // (a large alignment goes up straight from the caller's buffer, and waits)
     std::vector<uint8_t> codes_v;
     uint8_t* codes = nullptr;
@@ -848,9 +854,13 @@ int phylo_set_leaves(phylo_ctx* c, const double* genome) {
         c->codes_valid = ok;                                  // a property of the data (the twisting contract uses it)
         c->leaves_coded = ok && !c->env.no_leaf_codes;   // the access-path optimisation can be switched off
         c->hist_ready = false;
+        c->pat_U = 0;
         if (ok) {
             pk_pack_leaf_codes(codes, c->N, c->S, codes + pk_packed_offset(c->N, c->S));
-            HIPCHK(c, hipMemcpyAsync(c->d_leaf_codes, codes, code_bytes, hipMemcpyHostToDevice, c->stream));
+            // the site-pattern tables go up only where a launch can read them (U within the table's cap)
+            c->pat_U = pk_pat_build(codes, c->N, c->S, codes + pk_pat_offset(c->N, c->S));
+            const size_t up_bytes = c->pat_U <= PK_PAT_MAX_U ? code_bytes : pk_codes_image_bytes(c->N, c->S);
+            HIPCHK(c, hipMemcpyAsync(c->d_leaf_codes, codes, up_bytes, hipMemcpyHostToDevice, c->stream));
         }
     }
     if (pinned) HIPCHK(c, hipEventRecord(c->ev_leaves, c->stream));
@@ -1588,6 +1598,9 @@ static int comm_exchange(phylo_ctx* c, double* const* arrays, int n_arrays, size
 // sweep_step_a never touch: pk_all_marks reads K, Kg, group_seeds, seed, r, cdf and mark; pk_materialize_adopted(_grouped) and
 // pk_materialize_by_draws read those, rdraw, k0, Kloc, N, S, child_all, Pmat_all, leaves, pool, pool_ptrs, mirror and cache.
 // rdraw is read by pk_materialize_by_draws and pk_rank_book_mat alone, tab_ptrs by the bookkeeping kernels alone.)
+// does the record-form merge of the current leaves take the pattern form (phylo_site_patterns.h: the rule)?
+static bool pat_on(const phylo_ctx* c) { return pk_pat_take(c->S, c->pat_U, c->leaves_coded, c->ntiles, c->env.site_patterns); }
+
 static pk_rank_args rank_args(const phylo_ctx* c, int r) {
     const sweep_plan& p = c->run.plan;
     const int N = c->N, K = c->K, Kl = c->Kloc, cur = r & 1, nxt = cur ^ 1;
@@ -1773,8 +1786,18 @@ static int step_merge(phylo_ctx* c, const pk_rank_args& b) {
         // to refresh the image too.
         pk_pi4 pi4;
         memcpy(pi4.v, c->h_model_p + 16, sizeof pi4.v);
-        launch_stamped(pk_rank_merge_nostore, mgrid, dim3(64), 0, c->stream, e0, e1, (const unsigned long long*)b.rec, b.Pmat, S, b.T,
-                       b.ntiles, b.tilev, pi4);
+        // the pattern form: the table's LDS and U go with the launch; U = 0 is today's form
+        pk_pat_args pat = {nullptr, nullptr, 0, 0};
+        size_t lds = 0;
+        if (pat_on(c)) {
+            pat.pimg = (const char*)c->d_pat;
+            pat.roff = (const char*)c->d_pat + pk_pat_image_bytes(S);
+            pat.rep_delta = (long long)((c->d_pat + pk_pat_image_bytes(S) + pk_pat_rep_bytes()) - c->d_leaf_packed);
+            pat.U = c->pat_U;
+            lds = pk_pat_lds_bytes(c->pat_U);
+        }
+        launch_stamped(pk_rank_merge_nostore, mgrid, dim3(64), lds, c->stream, e0, e1, (const unsigned long long*)b.rec, b.Pmat, S, b.T,
+                       b.ntiles, b.tilev, pi4, pat);
     } else {
         launch_stamped(pk_rank_merge_nostore_ids, mgrid, dim3(64), 0, c->stream, e0, e1, b);
     }
@@ -2966,6 +2989,39 @@ int phylo_debug_pack_leaf_codes(const uint8_t* codes, int N, int S, uint8_t* pac
     if (!packed) return PHYLO_OK;
     if (cap < *need) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_pack_leaf_codes: the image takes %lld bytes (got %lld)", (long long)*need, (long long)cap);
     pk_pack_leaf_codes(codes, N, S, packed);
+    return PHYLO_OK;
+}
+
+int phylo_debug_site_patterns(const uint8_t* codes, int N, int S, int32_t* U, int32_t* rep, uint16_t* image, uint32_t* rep_off,
+                              uint8_t* rep_leaf, int64_t rep_leaf_cap) {
+    if (N < 1 || S < 1 || !codes || !U) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_site_patterns: bad arguments");
+    std::vector<int32_t> pat((size_t)S), rp((size_t)S);
+    *U = pk_pat_columns(codes, N, S, pat.data(), rp.data());
+    if (rep) memcpy(rep, rp.data(), (size_t)*U * sizeof(int32_t));
+    if (image && *U <= PK_PAT_IMAGE_MAX_U) pk_pat_pack_image(pat.data(), S, *U, image);
+    if (rep_off && *U <= PK_PAT_MAX_U) pk_pat_rep_offsets(rp.data(), *U, rep_off);
+    if (rep_leaf && *U <= PK_PAT_MAX_U) {
+        if (rep_leaf_cap < (int64_t)pk_packed_bytes(N, *U))
+            return fail(nullptr, PHYLO_EINVAL, "phylo_debug_site_patterns: the representative leaf image takes %lld bytes (got %lld)",
+                        (long long)pk_packed_bytes(N, *U), (long long)rep_leaf_cap);
+        pk_pat_rep_leaf_image(codes, N, S, rp.data(), *U, rep_leaf, pk_packed_leaf_bytes(*U));
+    }
+    return PHYLO_OK;
+}
+
+int phylo_debug_site_patterns_rule(int S, int U, int coded, int ntiles, int sw) {
+    if (S < 1 || U < 0 || ntiles < 1 || sw < PK_PAT_OFF || sw > PK_PAT_FORCE) {
+        (void)fail(nullptr, PHYLO_EINVAL, "phylo_debug_site_patterns_rule: bad arguments");
+        return -1;
+    }
+    return pk_pat_take(S, U, coded != 0, ntiles, sw) ? 1 : 0;
+}
+
+int phylo_debug_site_patterns_of(phylo_ctx* c, int32_t* U, int32_t* taken) {
+    if (!c || !U || !taken) return fail(c, PHYLO_EINVAL, "phylo_debug_site_patterns_of: NULL argument");
+    if (!c->have_leaves) return fail(c, PHYLO_ESTATE, "phylo_debug_site_patterns_of needs leaves");
+    *U = c->pat_U;
+    *taken = pat_on(c) ? 1 : 0;
     return PHYLO_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include "phylo_math.h"
 #include "phylo_packed_codes.h"
+#include "phylo_site_patterns.h"
 
 #define PK_COLS 256          // canonical site-sum columns == threads per merge workgroup
 #define PK_AUX 8             // per-particle scalars handed from the bookkeeping kernel to the merge epilogue
@@ -1899,6 +1900,113 @@ __device__ __forceinline__ bool pk_rows_fast_mixed(int s0, int s1, const char* b
     }
     return pm_lp_flag_set(flag);
 }
+// ---- Site patterns (phylo_site_patterns.h): a wave with an uncoded child computes the site likelihood once per DISTINCT column of
+//      the alignment and takes the product over all sites by looking the factors up.  Two sites with the same column carry the same
+//      bits in every node (every kernel that writes a node row runs the same operations per site), so the factor of a site IS the
+//      factor of its column's representative site: only where a factor comes from changes, not one bit of it.
+//      Phase 1: lane l computes the columns u = l + 64 j < U -- the uncoded rows gathered at the representative site (32-byte rows,
+//      the same `saddr` form; the row offset read one and two steps ahead, 0 behind the last column: always a site of the row), the
+//      coded side's code from the representative leaf image (it lies at a fixed distance behind the leaf's packed image, which the
+//      record holds: nothing new in the record), walked like pk_rows_fast_mixed's (U <= 512: eight steps, the chunk's low two words)
+//      -- through the same pk_rows_lik, and stores the value in the table ulik[u]; a column past U stores exactly 1.0
+//      (the same select as a site past the end), and entry U, the pad, is 1.0.  No running product; the least key of a stored value
+//      is the flag's factor term, as pm_lp_mul2_spec keeps it.
+//      Phase 2, behind the wave's LDS fence: pk_rows_fast_cc's walk over ALL sites -- a chunk's sixteen steps unrolled in eight
+//      pairs, a pair's two table offsets the halves of ONE 32-bit word of the pattern image, one LDS read per site,
+//      pm_lp_mul2_spec_q per pair, pm_lp_mul_normal for an odd last step, the next chunk requested when the current one is taken.
+//      Same lanes, steps, pairing and updates as the loops it replaces.  A set flag from either phase sends the wave to what it
+//      replaces (pk_rows_general; pk_rows_run for two internal children), which recomputes from pm_lp_init() over all sites.
+typedef __attribute__((address_space(1))) const unsigned int pk_gu32c;
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_pat_rows(pk_rowregs& x, const char* bl, const char* br, unsigned int off) {
+    if constexpr (!CL) { x.l0 = *(pk_gu4c*)(bl + off); x.l1 = *(pk_gu4c*)(bl + off + 16u); }
+    if constexpr (!CR) { x.r0 = *(pk_gu4c*)(br + off); x.r1 = *(pk_gu4c*)(br + off + 16u); }
+}
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_pat_entry(pk_rowregs& X, unsigned int code, unsigned int u, unsigned int U, const double (&Pl)[16],
+                                             const double (&Pr)[16], const double (*tabL)[4], const double (*tabR)[4],
+                                             const double (&pi)[4], double* ulik, pm_lp_flag& flag) {
+    if constexpr (CL) X.cl = code;
+    if constexpr (CR) X.cr = code;
+    double x = pk_rows_lik<CL, CR>(X, Pl, Pr, tabL, tabR, nullptr, pi);
+    x = u < U ? x : 1.0;
+    flag.f = pm_min_u32(flag.f, pm_lp_key(x));
+    ulik[u] = x;
+}
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_pat_phase1(int U, const char* bl, const char* br, const char* rl, const char* roff,
+                                              const double (&Pl)[16], const double (&Pr)[16], const double (*tabL)[4],
+                                              const double (*tabR)[4], const double (&pi)[4], double* ulik, pm_lp_flag& flag) {
+    static_assert(!(CL && CR), "an uncoded side");
+    const int nU = __builtin_amdgcn_readfirstlane((U + 63) >> 6);
+    unsigned int u = threadIdx.x & 63u;
+    unsigned long long lo = 0;                             // the codes of my columns: one byte per step
+    if constexpr (CL || CR) {
+        const pk_u4 q = *(pk_gu4c*)(rl + u * 16u);
+        lo = (unsigned long long)q.x | ((unsigned long long)q.y << 32);
+    }
+    pk_rowregs A, B;
+    unsigned int ro = *(pk_gu32c*)(roff + u * 4u);
+    pk_pat_rows<CL, CR>(A, bl, br, ro);
+    ro = *(pk_gu32c*)(roff + (u + 64u) * 4u);
+    #pragma unroll 1
+    for (int t = 0; t < (nU >> 1); ++t, u += 128u) {
+        pk_pat_rows<CL, CR>(B, bl, br, ro);
+        ro = *(pk_gu32c*)(roff + (u + 128u) * 4u);
+        const unsigned int cw = (unsigned int)lo;
+        pk_pat_entry<CL, CR>(A, cw & 0xffu, u, (unsigned int)U, Pl, Pr, tabL, tabR, pi, ulik, flag);
+        pk_pat_rows<CL, CR>(A, bl, br, ro);
+        ro = *(pk_gu32c*)(roff + (u + 192u) * 4u);
+        pk_pat_entry<CL, CR>(B, (cw >> 8) & 0xffu, u + 64u, (unsigned int)U, Pl, Pr, tabL, tabR, pi, ulik, flag);
+        lo >>= 16;
+    }
+    if (nU & 1) pk_pat_entry<CL, CR>(A, (unsigned int)lo & 0xffu, u, (unsigned int)U, Pl, Pr, tabL, tabR, pi, ulik, flag);
+    if (threadIdx.x == 0) ulik[U] = 1.0;                   // the pad entry (U a multiple of 64: no select wrote it)
+}
+__device__ __forceinline__ void pk_pat_request(pk_u4& n0, pk_u4& n1, const char* pimg, int Jc) {
+    const unsigned int o = (unsigned int)Jc * (2u * PK_PAT_HALF_BYTES) + (threadIdx.x & 63u) * 16u;
+    n0 = *(pk_gu4c*)(pimg + o);
+    n1 = *(pk_gu4c*)(pimg + o + (unsigned int)PK_PAT_HALF_BYTES);
+}
+// (n0, n1: chunk 0 of the pattern image, requested by the caller; the tile is the whole row and starts at site 0)
+__device__ __forceinline__ void pk_pat_walk(int s1, const char* pimg, pk_u4 n0, pk_u4 n1, const double* ulik, pm_lp& col, pm_lp_flag& flag) {
+    const char* ub = (const char*)ulik;
+    int n = __builtin_amdgcn_readfirstlane((s1 + 63) >> 6), Jc = 0;
+    #pragma unroll 1
+    for (;;) {
+        const unsigned int w[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+        if (n > 16) pk_pat_request(n0, n1, pimg, Jc + 1);
+#pragma unroll
+        for (int j = 0; j < 16; j += 2) {
+            if (n < j + 2) {
+                if (n == j + 1) pm_lp_mul_normal(col, *(const double*)(ub + (w[j >> 1] & 0xffffu)));
+                break;
+            }
+            const double xa = *(const double*)(ub + (w[j >> 1] & 0xffffu));
+            const double xb = *(const double*)(ub + (w[j >> 1] >> 16));
+            pm_lp_mul2_spec_q(col, xa, xb, flag);
+        }
+        if (n <= 16) break;
+        n -= 16; ++Jc;
+    }
+}
+// the kernel's arguments behind pi (pk_merge_kernarg): read from the argument segment where they are used
+struct pk_pat_args { const char* pimg; const char* roff; long long rep_delta /* representative leaf image - packed image */; int U; };
+typedef __attribute__((address_space(4))) const pk_pat_args pk_pat_kargs;
+template <bool CL, bool CR>
+__device__ __forceinline__ bool pk_rows_pat(int s1, const char* bl, const char* br, const char* rl, pk_pat_kargs* pa, const double (&Pl)[16],
+                                            const double (&Pr)[16], const double (*tabL)[4], const double (*tabR)[4],
+                                            const double (&pi)[4], double* ulik, pm_lp& col) {
+    pm_lp_flag flag = pm_lp_flag_init();
+    const char* pimg = pa->pimg;
+    pk_u4 n0, n1;
+    if constexpr (CL || CR) pk_pat_request(n0, n1, pimg, 0);   // (two internal children: behind phase 1, whose rows fill the registers)
+    pk_pat_phase1<CL, CR>(pa->U, bl, br, rl, pa->roff, Pl, Pr, tabL, tabR, pi, ulik, flag);
+    if constexpr (!(CL || CR)) pk_pat_request(n0, n1, pimg, 0);
+    pk_wave_lds_fence();
+    pk_pat_walk(s1, pimg, n0, n1, ulik, col, flag);
+    return pm_lp_flag_set(flag);
+}
 // The general path of a coded variant: pk_rows_run_packed from pm_lp_init(), with its own first chunk and rows and its own
 // matrices.  Taken by a tile that starts mid-chunk (a context with an overridden site tile), by a leaf x leaf wave with a lik25
 // entry outside the positive normal range, and as the redo of a wave whose speculative loop raised its flag.  The tables in LDS are
@@ -1917,11 +2025,16 @@ __device__ __forceinline__ pm_lp pk_rows_general_v(int s0, int s1, const char* b
         Pr[u] = CR ? 0.0 : Pc[16 + u];
     }
     pk_rowregs A;
-    pk_cstream c;
     pm_lp col = pm_lp_init();
-    pk_cs_request<CL, CR>(c, bl, br, s0 >> 10);
-    pk_rows_load_u<CL, CR>(A, bl, br, s0 + (int)(threadIdx.x & 63), s1);
-    pk_rows_run_packed<CL, CR>(s0, s1, bl, br, A, c, Pl, Pr, tabL, tabR, lik25, pi, col);
+    if constexpr (CL || CR) {
+        pk_cstream c;
+        pk_cs_request<CL, CR>(c, bl, br, s0 >> 10);
+        pk_rows_load_u<CL, CR>(A, bl, br, s0 + (int)(threadIdx.x & 63), s1);
+        pk_rows_run_packed<CL, CR>(s0, s1, bl, br, A, c, Pl, Pr, tabL, tabR, lik25, pi, col);
+    } else {                                               // no coded side: the loop of two internal children as it is
+        pk_rows_load<CL, CR>(A, bl, br, s0 + (int)(threadIdx.x & 63), s1);
+        pk_rows_run<CL, CR>(s0, s1, bl, br, A, Pl, Pr, tabL, tabR, lik25, pi, col);
+    }
     return col;
 }
 __device__ __forceinline__ pm_lp pk_rows_general(unsigned int fl, int s0, int s1, const char* bl, const char* br, const double* Pu,
@@ -1936,7 +2049,35 @@ __device__ __forceinline__ pm_lp pk_rows_general(unsigned int fl, int s0, int s1
     const pk_cdbl* pik = (const pk_cdbl*)pk_uniform_ptr(pi4);
     if ((fl & 3u) == 3u) return pk_rows_general_v<true, true>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
     if (fl & 1u) return pk_rows_general_v<true, false>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
-    return pk_rows_general_v<false, true>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
+    if (fl & 2u) return pk_rows_general_v<false, true>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
+    // two internal children, the pattern form flagged: today's loop.  (A copy down here and not a way on into the variant's own loop:
+    // with the two loops in one variant the allocator reloads a matrix element from a spill lane in every trip of today's.)
+    return pk_rows_general_v<false, false>(s0, s1, bl, br, Pc, pik, tabL, tabR, lik25);
+}
+// A variant with an uncoded side in the pattern form: its own loads of pi and the matrices (values of its own to the register
+// allocator: what it spills here it does not reload in the loops of today's form), the coded side's table, the two phases.
+template <bool CL, bool CR>
+__device__ __forceinline__ bool pk_rows_loop_pat(int s1, const char* bl, const char* br, const double* Pu, const pk_cdbl* Pc,
+                                                 double (*tabL)[4], double (*tabR)[4], const pk_cdbl* pik, pm_lp& col, pk_pat_kargs* pa,
+                                                 double* ulik) {
+    static_assert(!(CL && CR), "an uncoded side");
+    const double pi[4] = {pik[0], pik[1], pik[2], pik[3]};
+    double Pl[16], Pr[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        Pl[u] = CL ? 0.0 : Pc[u];
+        Pr[u] = CR ? 0.0 : Pc[16 + u];
+    }
+    const char* rl = nullptr;
+    if constexpr (CL != CR) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) asm volatile("" : "+s"(CL ? Pr[u] : Pl[u]));   // (pk_rows_loop_rec)
+        rl = (CL ? bl : br) + pa->rep_delta;
+        if constexpr (CL) pk_build_leaf_table(Pu, tabL, (int)(threadIdx.x & 63));
+        else pk_build_leaf_table(Pu + 16, tabR, (int)(threadIdx.x & 63));
+        pk_wave_lds_fence();
+    }
+    return __any(pk_rows_pat<CL, CR>(s1, bl, br, rl, pa, Pl, Pr, tabL, tabR, pi, ulik, col));
 }
 // pi (from the kernel-argument segment) and the matrices of the uncoded sides are requested HERE, inside the variant: uniform
 // addresses in the constant address space, nothing stored yet -- scalar loads.  Loaded above the variants they are one value each
@@ -1944,7 +2085,13 @@ __device__ __forceinline__ pm_lp pk_rows_general(unsigned int fl, int s0, int s1
 // everywhere and reloads them lane by lane inside the mixed variants' row loops.  A coded side's matrix is never read.
 template <bool CL, bool CR>
 __device__ __forceinline__ bool pk_rows_loop_rec(int s0, int s1, const char* bl, const char* br, const double* Pu, const pk_cdbl* Pc,
-                                                 double (*tabL)[4], double (*tabR)[4], double* lik25, const pk_cdbl* pik, pm_lp& col) {
+                                                 double (*tabL)[4], double (*tabR)[4], double* lik25, const pk_cdbl* pik, pm_lp& col,
+                                                 pk_pat_kargs* pa, double* ulik) {
+    // the pattern form (wave-uniform: a kernel argument; the host sets U only where the row is one tile, so s0 == 0)
+    // (a flagged wave of two internal children: pk_rows_general's variant without a coded side)
+    if constexpr (!(CL && CR)) {
+        if (pa->U != 0) return pk_rows_loop_pat<CL, CR>(s1, bl, br, Pu, Pc, tabL, tabR, pik, col, pa, ulik);
+    }
     const int lane = threadIdx.x & 63;
     const double pi[4] = {pik[0], pik[1], pik[2], pik[3]};
     double Pl[16], Pr[16];
@@ -1994,16 +2141,18 @@ __device__ __forceinline__ bool pk_rows_loop_rec(int s0, int s1, const char* bl,
     }
 }
 // (the argument segment of the kernel below, as the compiler lays it out)
-struct pk_merge_kernarg { const unsigned long long* rec; const double* Pmat; int S, T, ntiles; double* tilev; pk_pi4 pi4; };
+struct pk_merge_kernarg { const unsigned long long* rec; const double* Pmat; int S, T, ntiles; double* tilev; pk_pi4 pi4; pk_pat_args pat; };
 // (amdgpu_num_vgpr: on gfx90a and later the backend counts it in units of the unified register file, twice the number written, so
 // this caps the allocator at 64 vector registers -- 8 waves per SIMD; the 7-wave bound alone allows it 72, and it used 65)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8), amdgpu_num_vgpr(32)))
 void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const double* __restrict__ Pmat, int S, int T, int ntiles,
-                           double* __restrict__ tilev, const pk_pi4 pi4) {
+                           double* __restrict__ tilev, const pk_pi4 pi4, const pk_pat_args pat) {
     // (row 5 of a table and lik25[25 .. 29] belong to the pad code beside a real one: never written, read only where the site is
     // past the end and the factor is replaced; lik25[30] = 1.0 is pad x pad)
     __shared__ __attribute__((aligned(16))) double tabL[PK_PAD_CODE + 1][4], tabR[PK_PAD_CODE + 1][4];
     __shared__ double lik25[PK_PAD_CODE * 6 + 1];
+    // the pattern form's table of site likelihoods, sized by the launch (pk_pat_lds_bytes; nothing where the form is not taken)
+    extern __shared__ __attribute__((aligned(16))) double pk_ulik[];
     const int item = (int)blockIdx.x;
     const int k = __builtin_amdgcn_readfirstlane(ntiles == 1 ? item : item / ntiles), tau = item - k * ntiles;
     // (the tile's bounds come out of an integer division, which the vector pipe computes: said to be wave-uniform here, or every
@@ -2021,17 +2170,20 @@ void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const dou
     const char* bl = pk_uniform_ptr((const void*)rc[REC_BASE_L]);
     const char* br = pk_uniform_ptr((const void*)rc[REC_BASE_R]);
     PK_TOUCH4_END(fl);                                     // (before the first use of the flags, on every path)
-    static_assert(offsetof(pk_merge_kernarg, pi4) == 40 && sizeof(pk_merge_kernarg) == 72, "the kernel's argument segment");
+    static_assert(offsetof(pk_merge_kernarg, pi4) == 40 && offsetof(pk_merge_kernarg, pat) == 72 && sizeof(pk_merge_kernarg) == 104,
+                  "the kernel's argument segment");
+    pk_pat_kargs* pa = (pk_pat_kargs*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                       offsetof(pk_merge_kernarg, pat));
     const pk_cdbl* pi = (const pk_cdbl*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() +
                                          offsetof(pk_merge_kernarg, pi4));
     pm_lp col = pm_lp_init();
     bool redo;
     if (fl & 1u) {
-        if (fl & 2u) redo = pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
-        else redo = pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        if (fl & 2u) redo = pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
+        else redo = pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
     } else {
-        if (fl & 2u) redo = pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
-        else redo = pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col);
+        if (fl & 2u) redo = pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
+        else redo = pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
     }
     if (redo) col = pk_rows_general(fl, s0, s1, bl, br, Pu, (const double*)pi, tabL, tabR, lik25);
     const double tot = pk_wave_tree_sum(pm_lp_finish(col));
