@@ -423,6 +423,32 @@ int phylo_tree_summary_fetch(phylo_ctx* ctx, uint64_t* clade_bits, uint64_t* cla
 int phylo_tree_branches(phylo_ctx* ctx, phylo_stats* perf);
 int phylo_tree_branches_fetch(phylo_ctx* ctx, double* clade_stats, double* leaf_stats, int32_t* topo_clades, double* topo_stats);
 
+/* RELL bootstrap over the per-site factors of a scored tree set: which of T trees are significantly worse
+ * than the best one?  site_lik_TxS is what phylo_trees_loglik / phylo_trees_loglik_rates return (every entry finite and > 0); S is
+ * the call's own (no leaves are read, it need not be the context's).  Bit level:
+ *   x[t][s] = log(site_lik[t][s]) (the contract's log, phylo_math_probe op 1);
+ *   replicate b (its GLOBAL index, whatever the chunking) draws S sites: draw j is word j & 3 of the Philox4x32-10 block with key
+ *     seed and counter (b, 0, 4, j >> 2) -- stream 4 --, the site is (word * S) >> 32 as a 64-bit product; cnt[b][s] counts them;
+ *   rl[t][b]: acc = +0.0, then acc = fma((double)cnt[b][s], x[t][s], acc) for s = 0 .. S-1 in ascending order, ONE chain;
+ *   obs[t]: the same chain with every count 1 (last bits off loglik_T of the scoring call, which multiplies site factors: the
+ *     statistics use obs, which is consistent with the replicates);
+ *   best[b] = the t of the greatest rl[t][b], ties to the lowest t;  wins[t] = #{b : best[b] = t}.
+ * Outputs: obs_T [T], best_B [B], wins_T [T]; may be NULL: rep_loglik_TxB [T][B] = rl, counts_BxS [B][S] = cnt, site_loglik_TxS
+ * [T][S] = x, perf (sweep_ms = device time by hipEvents, n_launches, units = T S B).
+ * Synchronous; on a sharded context a local call, not a collective.  x stays on the device for the call (PHYLO_ENOMEM if it cannot
+ * be allocated); replicates run in chunks whose counts (uint16) and scores stay within 256 MiB (PHYLO_RELL_CHUNK=n in the
+ * environment of phylo_create caps the replicates per chunk; no bit depends on it).  The call has its own scratch and events,
+ * released with the context, and leaves alone the sweep's state, a kept graph, a tree summary and phylo_trees_loglik's scratch.
+ * PHYLO_EINVAL, before anything is queued: a NULL required pointer, T < 1, S outside 1 .. 65535, B outside 1 .. 2^20, an entry of
+ * site_lik that is not finite and > 0 (the message names tree and site). */
+int phylo_rell(phylo_ctx* ctx, int T, int S, const double* site_lik_TxS, int B, uint64_t seed, double* obs_T, int32_t* best_B,
+               int64_t* wins_T, double* rep_loglik_TxB, int32_t* counts_BxS, double* site_loglik_TxS, phylo_stats* perf);
+/* Test hook, no GPU and no context needed: phylo_rell's contract as a loop on the host over the same functions the kernels call,
+ * for replicates b0 .. b0 + nB - 1: counts [nB][S], x [T][S], rl [T][nB]; any output may be NULL (site_lik too when only counts
+ * are asked for). */
+int phylo_debug_rell_host(int T, int S, const double* site_lik_TxS, int b0, int nB, uint64_t seed, int32_t* counts, double* x,
+                          double* rl);
+
 /* Bit-level probe of the device arithmetic contract: op 0 exp(x), 1 log(x), 2 x/y, 3 fma(x,y,x), 4 exp(x) for x <= 0 (the scan's);
  * op 5 is outside that contract: the reverse pass's reciprocal of a site likelihood (pg_rcp, an ulp or two off 1/x). */
 int phylo_math_probe(phylo_ctx* ctx, int op, const double* x, const double* y, int n, double* out);

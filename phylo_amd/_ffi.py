@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -344,6 +344,29 @@ def debug_tree_schedule(child, blen):
     return ops, depth.value
 
 
+def debug_rell_host(site_lik, b0, nB, seed, S=None, want_counts=True, want_logs=True, want_reps=True):
+    """phylo_rell's contract as a host loop (no GPU needed) for replicates b0 .. b0 + nB - 1 of site_lik [T][S]: a dict with
+    'counts' [nB][S] int32, 'site_loglik' [T][S] and 'rep_loglik' [T][nB].  site_lik None (then give S): the counts alone."""
+    lib = load()
+    if site_lik is None:
+        T, S = 1, int(S)
+        sl, want_logs, want_reps = None, False, False
+    else:
+        sl = _f64(site_lik)
+        if sl.ndim != 2:
+            raise ValueError("site_lik must be [T][S], got %r" % (sl.shape,))
+        T, S = sl.shape
+    nB = int(nB)
+    cnt = np.zeros((nB, S), dtype=np.int32) if want_counts else None
+    x = np.empty((T, S)) if want_logs else None
+    rl = np.empty((T, nB)) if want_reps else None
+    rc = lib.phylo_debug_rell_host(C.c_int(T), C.c_int(S), _ptr(sl), C.c_int(int(b0)), C.c_int(nB), C.c_uint64(int(seed)), _ptr(cnt),
+                                   _ptr(x), _ptr(rl))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return {'counts': cnt, 'site_loglik': x, 'rep_loglik': rl}
+
+
 def vi_apply(N, jc, packed_vars, packed_grads, kind, lr, beta1=0.9, beta2=0.999, eps=1e-8, state=None):
     """phylo_vi_apply: the optimiser update on the packed variables IN PLACE (kind 0 gradient descent, 1 Adam with state =
     {'t': int, 'm': array, 'v': array}, updated in place too)."""
@@ -498,6 +521,33 @@ class Context:
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         res = (out,) + ((sites,) if want_sites else ()) + ((cats,) if want_cats else ())
         return res if len(res) > 1 else out
+
+    def rell(self, site_lik, B, seed, want_reps=False, want_counts=False, want_logs=False):
+        """RELL bootstrap over the site factors site_lik [T][S] of a scored tree set (phylo_rell; what trees_loglik and
+        trees_loglik_rates return with want_sites): B replicates from `seed`.  Returns a dict: 'obs' [T] the observed scores (the
+        contract's chain over log site factors), 'best' [B] the best tree of every replicate, 'wins' [T] their histogram, and on
+        request 'rep_loglik' [T][B], 'counts' [B][S], 'site_loglik' [T][S]; 'stats' holds the call's stats.
+        phylo_amd.treetests.tree_tests turns them into bootstrap proportions and KH / SH / c-ELW values."""
+        sl = _f64(site_lik)
+        if sl.ndim != 2:
+            raise ValueError("site_lik must be [T][S], got %r" % (sl.shape,))
+        T, S = sl.shape
+        B = int(B)
+        obs, best, wins = np.empty(T), np.empty(max(B, 0), dtype=np.int32), np.empty(T, dtype=np.int64)
+        reps = np.empty((T, B)) if want_reps and B > 0 else None
+        counts = np.empty((B, S), dtype=np.int32) if want_counts and B > 0 else None
+        logs = np.empty((T, S)) if want_logs else None
+        st = Stats()
+        self._check(self._lib.phylo_rell(self._h, C.c_int(T), C.c_int(S), _ptr(sl), C.c_int(B), C.c_uint64(int(seed)), _ptr(obs),
+                                         _ptr(best), _ptr(wins), _ptr(reps), _ptr(counts), _ptr(logs), C.byref(st)))
+        out = {'obs': obs, 'best': best, 'wins': wins, 'stats': {f: getattr(st, f) for f, _ in Stats._fields_}}
+        if want_reps:
+            out['rep_loglik'] = reps
+        if want_counts:
+            out['counts'] = counts
+        if want_logs:
+            out['site_loglik'] = logs
+        return out
 
     def resample(self, logw, seed, step):
         w = _f64(logw).reshape(-1)

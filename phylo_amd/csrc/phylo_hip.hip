@@ -28,6 +28,7 @@
 #include "phylo_trees.h"
 #include "phylo_trees_plan.h"
 #include "phylo_treeset.h"
+#include "phylo_rell.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -66,6 +67,7 @@ struct env_switches {
     int scan_multi_min = 4096;           // PHYLO_SCAN_MULTI_MIN: groups of more weights than this are scanned by several workgroups
     int site_patterns = PK_PAT_AUTO;     // PHYLO_SITE_PATTERNS: 0 = never the pattern form of the merge, force = wherever it is valid
     int trees_chunk = 0;                 // PHYLO_TREES_CHUNK: trees per chunk of phylo_trees_loglik (0 = what PT2_SCRATCH_BYTES holds; tests lower it)
+    int rell_chunk = 0;                  // PHYLO_RELL_CHUNK: replicates per chunk of phylo_rell (0 = what PR_CHUNK_BYTES holds; tests lower it)
     void read() {
         eager_nodes = getenv("PHYLO_EAGER_NODES") != nullptr;
         rehearse_sharded = getenv("PHYLO_REHEARSE_SHARDED") != nullptr;
@@ -83,6 +85,7 @@ struct env_switches {
         { const char* e = getenv("PHYLO_SITE_PATTERNS"); site_patterns = !e ? PK_PAT_AUTO : !strcmp(e, "force") ? PK_PAT_FORCE : atoi(e) == 0 ? PK_PAT_OFF : PK_PAT_AUTO; }
         { const char* e = getenv("PHYLO_SCAN_MULTI_MIN"); scan_multi_min = e ? atoi(e) : 4096; }
         { const char* e = getenv("PHYLO_TREES_CHUNK"); trees_chunk = e ? atoi(e) : 0; }
+        { const char* e = getenv("PHYLO_RELL_CHUNK"); rell_chunk = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_P2P"); no_p2p = e && atoi(e) == 0; }
         { const char* e = getenv("PHYLO_P2P_COPY_WORDS"); p2p_copy_words = e ? (size_t)atol(e) : 65536; }
         { const char* e = getenv("PHYLO_P2P_WAIT_S"); p2p_wait_ticks = e && atof(e) > 0 ? (unsigned long long)(atof(e) * 1e8) : PK_P2P_WAIT_TICKS; }
@@ -238,8 +241,8 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[15];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
-                                         //  14: phylo_trees_loglik's chunk)
+    DevBuf scratch[16];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+                                         //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -253,6 +256,7 @@ struct phylo_ctx {
     unsigned long long sweep_serial = 0, ts_serial = 0;
     hipEvent_t ev_tb0 = nullptr, ev_tb1 = nullptr;
     hipEvent_t ev_tl0 = nullptr, ev_tl1 = nullptr;   // phylo_trees_loglik's own pair (the sweep's and the summaries' stay theirs)
+    hipEvent_t ev_rl0 = nullptr, ev_rl1 = nullptr;   // phylo_rell's own pair
 };
 
 namespace {
@@ -771,6 +775,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_tb1) (void)hipEventDestroy(c->ev_tb1);
     if (c->ev_tl0) (void)hipEventDestroy(c->ev_tl0);
     if (c->ev_tl1) (void)hipEventDestroy(c->ev_tl1);
+    if (c->ev_rl0) (void)hipEventDestroy(c->ev_rl0);
+    if (c->ev_rl1) (void)hipEventDestroy(c->ev_rl1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -1205,6 +1211,124 @@ int phylo_debug_tree_schedule(int N, const int32_t* child, const double* blen, i
     char msg[200];
     if (pt2_check_tree(N, child, blen, &row, msg, sizeof msg)) return fail(nullptr, PHYLO_EINVAL, "tree 0, row %d: %s", row, msg);
     *depth = pt2_schedule(N, child, ops);
+    return PHYLO_OK;
+}
+
+// ---- RELL bootstrap over a scored tree set's site factors (phylo_rell.h) ----
+int phylo_rell(phylo_ctx* c, int T, int S, const double* site_lik_TxS, int B, uint64_t seed, double* obs_T, int32_t* best_B, int64_t* wins_T,
+               double* rep_loglik_TxB, int32_t* counts_BxS, double* site_loglik_TxS, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!site_lik_TxS || !obs_T || !best_B || !wins_T) return fail(c, PHYLO_EINVAL, "phylo_rell: site_lik, obs, best and wins must be given (NULL pointer)");
+    {
+        char msg[200];                                     // everything is checked before anything is queued
+        if (pr_check_shape(T, S, B, msg, sizeof msg) || pr_check_factors(T, S, site_lik_TxS, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "phylo_rell: %s", msg);
+    }
+    // one slab: logs [T][S] (resident for the call) | counts [chunk + 1][Sp] uint16 | scores [T][chunk + 1] | observed [T] |
+    // best [chunk] | wins [T] | flag.  Counts and scores of a chunk of replicates stay within PR_CHUNK_BYTES (while one replicate
+    // does); the first chunk carries one more column, the row of ones whose chain is the observed score.
+    const size_t Sp = pr_count_stride(S), n_x = (size_t)T * S;
+    const size_t per_rep = Sp * 2 + (size_t)T * 8;
+    size_t fit = PR_CHUNK_BYTES / per_rep;
+    if (fit < 1) fit = 1;
+    if (c->env.rell_chunk > 0 && (size_t)c->env.rell_chunk < fit) fit = (size_t)c->env.rell_chunk;
+    const int chunk = (int)std::min<size_t>((size_t)B, fit);
+    const size_t ldr = (size_t)chunk + 1;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_cnt = up(n_x * 8), o_rl = o_cnt + up(ldr * Sp * 2), o_obs = o_rl + up((size_t)T * ldr * 8), o_best = o_obs + up((size_t)T * 8),
+                 o_wins = o_best + up((size_t)chunk * 4), o_flag = o_wins + up((size_t)T * 8), total = o_flag + 256;
+    void* slab = nullptr;
+    CHK(scratch_get(c, 15, total, &slab));
+    char* base = (char*)slab;
+    double* d_x = (double*)base;
+    uint16_t* d_cnt = (uint16_t*)(base + o_cnt);
+    double* d_rl = (double*)(base + o_rl);
+    double* d_obs = (double*)(base + o_obs);
+    int32_t* d_best = (int32_t*)(base + o_best);
+    unsigned long long* d_wins = (unsigned long long*)(base + o_wins);
+    unsigned int* d_flag = (unsigned int*)(base + o_flag);
+    if (!c->ev_rl0) {
+        HIPCHK(c, hipEventCreate(&c->ev_rl0));
+        HIPCHK(c, hipEventCreate(&c->ev_rl1));
+    }
+    HIPCHK(c, hipMemcpyAsync(d_x, site_lik_TxS, n_x * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_wins, 0, (size_t)T * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, 4, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_rl0, c->stream));
+    hipLaunchKernelGGL(pr_log, dim3((unsigned)((n_x + 255) / 256)), dim3(256), 0, c->stream, d_x, n_x, d_flag);
+    CHK(launch_check(c, "pr_log"));
+    HIPCHK(c, hipEventRecord(c->ev_rl1, c->stream));
+    unsigned int flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    if (site_loglik_TxS) HIPCHK(c, hipMemcpyAsync(site_loglik_TxS, d_x, n_x * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag) return fail(c, PHYLO_EINVAL, "phylo_rell: the device met a site factor that is not a finite number > 0");
+    double ms_total = 0.0;
+    int launches = 1;
+    {
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_rl0, c->ev_rl1));
+        ms_total += ms;
+    }
+    std::vector<uint16_t> h_cnt(counts_BxS ? (size_t)chunk * Sp : 0);
+    const uint32_t nblk = (uint32_t)(Sp / 4);
+    for (int r0 = 0; r0 < B; r0 += chunk) {
+        const int n = std::min(chunk, B - r0);
+        const int ncols = n + (r0 == 0 ? 1 : 0);
+        HIPCHK(c, hipMemsetAsync(d_cnt, 0, (size_t)ncols * Sp * 2, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_rl0, c->stream));
+        const size_t n_threads = (size_t)n * nblk;
+        hipLaunchKernelGGL(pr_counts, dim3((unsigned)((n_threads + 255) / 256)), dim3(256), 0, c->stream, (unsigned int*)d_cnt, S, Sp, (uint32_t)r0,
+                           n_threads, nblk, seed);
+        CHK(launch_check(c, "pr_counts"));
+        ++launches;
+        if (r0 == 0) {
+            hipLaunchKernelGGL(pr_ones, dim3(cdiv(S, 256)), dim3(256), 0, c->stream, d_cnt + (size_t)n * Sp, S);
+            CHK(launch_check(c, "pr_ones"));
+            ++launches;
+        }
+        hipLaunchKernelGGL(pr_replicates, dim3((unsigned)cdiv(T, PR_TT), (unsigned)cdiv(ncols, PR_TB)), dim3(256), 0, c->stream, (const double*)d_x,
+                           (const uint16_t*)d_cnt, T, S, Sp, ncols, d_rl, ldr);
+        CHK(launch_check(c, "pr_replicates"));
+        hipLaunchKernelGGL(pr_best, dim3(cdiv(n, 64)), dim3(1024), 0, c->stream, (const double*)d_rl, ldr, T, n, d_best, d_wins);
+        CHK(launch_check(c, "pr_best"));
+        launches += 2;
+        if (r0 == 0) {
+            hipLaunchKernelGGL(pr_column, dim3(cdiv(T, 256)), dim3(256), 0, c->stream, (const double*)d_rl, ldr, (size_t)n, T, d_obs);
+            CHK(launch_check(c, "pr_column"));
+            ++launches;
+        }
+        HIPCHK(c, hipEventRecord(c->ev_rl1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(best_B + r0, d_best, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (r0 == 0) HIPCHK(c, hipMemcpyAsync(obs_T, d_obs, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
+        if (rep_loglik_TxB)
+            HIPCHK(c, hipMemcpy2DAsync(rep_loglik_TxB + r0, (size_t)B * 8, d_rl, ldr * 8, (size_t)n * 8, (size_t)T, hipMemcpyDeviceToHost, c->stream));
+        if (counts_BxS) HIPCHK(c, hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)n * Sp * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's buffers are reused by the next one
+        if (counts_BxS)
+            for (int b = 0; b < n; ++b)
+                for (int s = 0; s < S; ++s) counts_BxS[(size_t)(r0 + b) * S + s] = h_cnt[(size_t)b * Sp + s];
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_rl0, c->ev_rl1));
+        ms_total += ms;
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "wins are copied as they are");
+    HIPCHK(c, hipMemcpyAsync(wins_T, d_wins, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * B;
+        st.alg_bytes = 8.0 * (double)T * S + 8.0 * (double)T * B;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
+int phylo_debug_rell_host(int T, int S, const double* site_lik_TxS, int b0, int nB, uint64_t seed, int32_t* counts, double* x, double* rl) {
+    char msg[200];
+    if (pr_rell_host(T, S, site_lik_TxS, b0, nB, seed, counts, x, rl, msg, sizeof msg)) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_rell_host: %s", msg);
     return PHYLO_OK;
 }
 

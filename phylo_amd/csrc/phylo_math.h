@@ -292,7 +292,7 @@ PM_HD pm_u32x4 pm_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
     return r;
 }
 
-enum { PM_STREAM_PAIR = 0, PM_STREAM_BRANCH = 1, PM_STREAM_RESAMPLE = 2, PM_STREAM_TWIST = 3 };
+enum { PM_STREAM_PAIR = 0, PM_STREAM_BRANCH = 1, PM_STREAM_RESAMPLE = 2, PM_STREAM_TWIST = 3, PM_STREAM_BOOT = 4 };
 #define PM_CDF_SCALE 17592186044416.0 /* 2^44 */
 
 // 64 random bits -> double in (0,1]

@@ -7,6 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 STREAM_PAIR, STREAM_BRANCH, STREAM_RESAMPLE, STREAM_TWIST = 0, 1, 2, 3
+STREAM_BOOT = 4                         # phylo_rell's site draws: counter (replicate, 0, 4, draw >> 2)
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
 _MASK = np.uint64(0xFFFFFFFF)

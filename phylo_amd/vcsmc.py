@@ -304,18 +304,33 @@ class VCSMC:
             tab = new
         return [row[0] for row in tab]
 
-    def score_trees(self, newicks, rates=None):
+    def score_trees(self, newicks, rates=None, want_sites=False):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
         distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
         (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
-        rates (phylo_trees_loglik_rates).  Returns a list of floats; a local call on every rank when sharded."""
+        rates (phylo_trees_loglik_rates).  Returns a list of floats -- with want_sites, that list and the site factors [T][S] the
+        call returned --; a local call on every rank when sharded."""
         rows = [treepost.newick_to_rows(nw, self.taxa) for nw in newicks]
         if not rows:
-            return []
+            return ([], np.empty((0, self.S))) if want_sites else []
         ctx = self._context()
         child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
-        ll = ctx.trees_loglik(child, blen) if rates is None else ctx.trees_loglik_rates(child, blen, rates[0], rates[1])
-        return [float(x) for x in ll]
+        if rates is None:
+            res = ctx.trees_loglik(child, blen, want_sites=want_sites)
+        else:
+            res = ctx.trees_loglik_rates(child, blen, rates[0], rates[1], want_sites=want_sites)
+        if want_sites:
+            return [float(x) for x in res[0]], res[1]
+        return [float(x) for x in res]
+
+    def tree_tests(self, site_lik, B, seed):
+        """tree_tests.json of --tree_tests: the RELL bootstrap (phylo_rell) over the site factors of the scored trees and the
+        statistics phylo_amd.treetests reads off it"""
+        from . import treetests
+        out = self._context().rell(site_lik, B, seed, want_reps=True)
+        st = treetests.tree_tests(out['obs'], out['wins'], B, reps=out['rep_loglik'])
+        return {'B': int(B), 'seed': int(seed), 'best': int(st['best']), 'obs': out['obs'].tolist(), 'bp': st['bp'].tolist(),
+                'p_kh': st['p_kh'].tolist(), 'p_sh': st['p_sh'].tolist(), 'c_elw': st['c_elw'].tolist()}
 
     def _tree_scores(self, path):
         """tree_scores.json of --score_trees: the file's trees, and with branch lengths in the posterior also map.tre,
@@ -329,7 +344,14 @@ class VCSMC:
             from . import rates as rates_mod
             rm = rates_mod.parse_spec(spec)
         mix = None if rm is None else (rm['rates'], rm['weights'])
-        ll = self.score_trees(newicks, rates=mix)
+        tests = getattr(self.args, 'tree_tests', None)
+        self.tree_test_results = None
+        if tests and newicks:                              # --tree_tests: from the site factors of this very scoring call
+            from . import treetests
+            ll, sites = self.score_trees(newicks, rates=mix, want_sites=True)
+            self.tree_test_results = self.tree_tests(sites, *treetests.parse_spec(tests))
+        else:
+            ll = self.score_trees(newicks, rates=mix)
         out = {'model': {'Q': np.asarray(self.Qmatrix, dtype=np.float64).tolist(),
                          'pi': np.asarray(self.stationary_probs, dtype=np.float64).reshape(-1).tolist(),
                          'jc69_closed_form': bool(self.args.jcmodel)},
@@ -361,7 +383,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))
@@ -483,6 +505,9 @@ class VCSMC:
                 import os
                 with open(os.path.join(save_dir, 'tree_scores.json'), 'w') as f:
                     json.dump(scores, f, indent=1)
+                if getattr(self, 'tree_test_results', None) is not None:
+                    with open(os.path.join(save_dir, 'tree_tests.json'), 'w') as f:
+                        json.dump(self.tree_test_results, f, indent=1)
             self.save_dir = save_dir
             print("Finished...")
         return self.elbos

@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -67,7 +67,20 @@ def parse_args(argv=None):
                              "ALPHA (Yang 1994, mean rates), and with PINV > 0 a class of invariant sites of that proportion (the "
                              "rates of the variable sites are not rescaled); every score in tree_scores.json is then under that "
                              "model, and the file names its rates and weights")
+    parser.add_argument('--tree_tests', default=None, metavar='B[:SEED]',
+                        help="with --score_trees: which of those trees are significantly worse than the best one?  A RELL bootstrap "
+                             "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
+                             "--score_rates if given) writes tree_tests.json beside tree_scores.json: per tree the observed score, "
+                             "the bootstrap proportion, the p-values of the KH and SH tests and the expected likelihood weight")
     args = parser.parse_args(argv)
+    if args.tree_tests is not None:
+        if not args.score_trees:
+            parser.error('--tree_tests needs --score_trees FILE (it tests the trees scored there)')
+        from phylo_amd import treetests
+        try:
+            treetests.parse_spec(args.tree_tests)
+        except ValueError as e:
+            parser.error('--tree_tests: %s' % e)
     if args.score_rates is not None:
         if not args.score_trees:
             parser.error('--score_rates needs --score_trees FILE (it is the rate model those trees are scored under)')

@@ -43,6 +43,7 @@ def cycle(i):
         c.sweep_fetch()
         c.sweep_batch_async([1, 2, 3, 4], _ffi.FLAGS_DEFAULT | _ffi.KEEP_GRAPH)   # the batched graph and its reverse pass
         c.sweep_backward_batch(4)
+        c.rell(np.full((40 + i % 8, 300), 0.25), 64, i)     # the bootstrap's own slab (logs, counts, replicate scores)
     v = T.Variables(N2, np.log(10.0), False)            # a context of 66 taxa that trains: two steps, so two passes on one context
     tr = T.Trainer(g2, 32 + 4 * (i % 8), v, T.make_optimizer('Adam', 0.01), S2)
     try:
