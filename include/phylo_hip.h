@@ -171,6 +171,21 @@ int phylo_trees_loglik(phylo_ctx* ctx, int T, const int32_t* child, const double
 int phylo_trees_loglik_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate_C,
                              const double* weight_C, const double* prior4, double* loglik_T, double* site_lik_TxS,
                              double* cat_lik_TxCxS, phylo_stats* perf);
+/* The derivatives of phylo_trees_loglik's log-likelihood with respect to every branch length: for T trees
+ * given as phylo_trees_loglik takes them (same numbering, same checks, same state rules),
+ *   loglik_T[t]      bit for bit phylo_trees_loglik's value for the same tree, prior and site tile;
+ *   grad[t][i][side] = d loglik_T[t] / d blen[t][i][side] = sum_s L'_s / L_s;
+ *   curv[t][i][side] (may be NULL) = d^2 loglik_T[t] / d blen[t][i][side]^2 = sum_s (L''_s / L_s - (L'_s / L_s)^2),
+ * both shaped [T][N-1][2] as blen.  The sums run in a fixed order (64 sites by the wave's adjacent-pair tree, the steps of a
+ * site tile in ascending order, the tiles left to right; no atomics): a call repeats its own bits, and chunking changes none.
+ * Against a restatement the derivatives carry a tolerance, not a bit contract.  A tree whose loglik is not finite gets NaN in
+ * every derivative entry.  perf (may be NULL): sweep_ms = device time, n_launches, units = T S (N-1).
+ * Synchronous; on a sharded context a LOCAL call.  PHYLO_EINVAL before anything is queued for a bad tree (naming tree and row) and
+ * for child, blen, loglik_T or grad == NULL.  Large T runs in chunks (64 MiB; PHYLO_TREES_CHUNK caps the trees of a chunk); the
+ * node stores of the resident workgroups take at most 256 MiB more.  Own scratch and events, released with the context: the
+ * sweep's state, a pending phylo_sweep_backward, a tree summary and the scratch of phylo_trees_loglik and phylo_rell are left alone. */
+int phylo_trees_grad(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
+                     double* grad, double* curv, phylo_stats* perf);
 /* Test hook, no GPU needed: the host half of phylo_trees_loglik on ONE tree -- the checks above (PHYLO_EINVAL, "tree 0, row i")
  * and the slot schedule the kernel walks: ops[N-1][4] = {destination slot, left source, right source, row}, a source >= 0 a
  * leaf, a source < 0 the slot ~source; depth = slots in use (<= floor(log2 N) + 1).  tests/test_trees_host.py replays it. */

@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -521,6 +521,25 @@ class Context:
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         res = (out,) + ((sites,) if want_sites else ()) + ((cats,) if want_cats else ())
         return res if len(res) > 1 else out
+
+    def trees_grad(self, child, blen, prior=None, want_curv=False):
+        """Derivatives of trees_loglik with respect to every branch length (phylo_trees_grad): returns (loglik [T], grad
+        [T][N-1][2]) or, with want_curv, (loglik, grad, curv) -- curv the own second derivative of every length.  loglik is bit
+        for bit trees_loglik's; a tree whose loglik is not finite has NaN derivatives.  self.last_trees_stats holds the call's
+        stats.  phylo_amd.treeopt.optimize_branches climbs with it."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        out = np.empty(T)
+        grad = np.empty(blen.shape)
+        curv = np.empty(blen.shape) if want_curv else None
+        st = Stats()
+        self._check(self._lib.phylo_trees_grad(self._h, C.c_int(T), _ptr(child), _ptr(blen), _ptr(pr), _ptr(out), _ptr(grad), _ptr(curv),
+                                               C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return (out, grad, curv) if want_curv else (out, grad)
 
     def rell(self, site_lik, B, seed, want_reps=False, want_counts=False, want_logs=False):
         """RELL bootstrap over the site factors site_lik [T][S] of a scored tree set (phylo_rell; what trees_loglik and

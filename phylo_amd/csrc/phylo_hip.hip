@@ -29,6 +29,7 @@
 #include "phylo_trees_plan.h"
 #include "phylo_treeset.h"
 #include "phylo_rell.h"
+#include "phylo_treegrad.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -241,8 +242,9 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[16];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
-                                         //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates)
+    DevBuf scratch[17];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+                                         //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates;
+                                         //  16: phylo_trees_grad's chunk and node stores)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -257,6 +259,7 @@ struct phylo_ctx {
     hipEvent_t ev_tb0 = nullptr, ev_tb1 = nullptr;
     hipEvent_t ev_tl0 = nullptr, ev_tl1 = nullptr;   // phylo_trees_loglik's own pair (the sweep's and the summaries' stay theirs)
     hipEvent_t ev_rl0 = nullptr, ev_rl1 = nullptr;   // phylo_rell's own pair
+    hipEvent_t ev_tg0 = nullptr, ev_tg1 = nullptr;   // phylo_trees_grad's own pair
 };
 
 namespace {
@@ -777,6 +780,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_tl1) (void)hipEventDestroy(c->ev_tl1);
     if (c->ev_rl0) (void)hipEventDestroy(c->ev_rl0);
     if (c->ev_rl1) (void)hipEventDestroy(c->ev_rl1);
+    if (c->ev_tg0) (void)hipEventDestroy(c->ev_tg0);
+    if (c->ev_tg1) (void)hipEventDestroy(c->ev_tg1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -1321,6 +1326,118 @@ int phylo_rell(phylo_ctx* c, int T, int S, const double* site_lik_TxS, int B, ui
         st.n_launches = launches;
         st.units = (double)T * S * B;
         st.alg_bytes = 8.0 * (double)T * S + 8.0 * (double)T * B;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
+// ---- branch-length derivatives of a scored tree set (phylo_treegrad.h) ----
+int phylo_trees_grad(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T, double* grad,
+                     double* curv, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_grad needs phylo_set_leaves and phylo_set_model first");
+    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    if (!child || !blen || !loglik_T || !grad) return fail(c, PHYLO_EINVAL, "phylo_trees_grad: child, blen, loglik and grad must be given (NULL pointer)");
+    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
+    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
+        int row = 0;
+        char msg[200];
+        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+    }
+    const bool coded = c->leaves_coded, want_curv = curv != nullptr;
+    ptg_plan pl;
+    if (ptg_make_plan(N, ntiles, T, coded, want_curv, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+        return fail(c, PHYLO_EINVAL, "phylo_trees_grad: no plan for N=%d, %d tiles, T=%d", N, ntiles, T);
+    const int chunk = pl.chunk, nq = pl.nq;
+    void* slab = nullptr;
+    CHK(scratch_get(c, 16, pl.total, &slab));
+    char* base = (char*)slab;
+    double* d_prior = (double*)(base + pl.o_prior);
+    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
+    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
+    double* d_P = (double*)(base + pl.o_P);
+    double* d_t = (double*)(base + pl.o_t);
+    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
+    double* d_tilev = (double*)(base + pl.o_tilev);
+    double* d_out = (double*)(base + pl.o_out);
+    double* d_dtile = (double*)(base + pl.o_dtile);
+    double* d_dout = (double*)(base + pl.o_dout);
+    if (!c->ev_tg0) {
+        HIPCHK(c, hipEventCreate(&c->ev_tg0));
+        HIPCHK(c, hipEventCreate(&c->ev_tg1));
+    }
+    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
+    std::vector<double> ts((size_t)chunk * R * 2);
+    double ms_total = 0.0;
+    int launches = 0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int n = std::min(chunk, T - t0);
+        int depth = 1;
+        for (int t = 0; t < n; ++t) {
+            int32_t* o = ops.data() + (size_t)t * R * 4;
+            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
+            depth = std::max(depth, pt2_schedule(N, ch, o));
+            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
+                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
+            const double* b = blen + (size_t)(t0 + t) * R * 2;
+            double* tk = ts.data() + (size_t)t * R * 2;
+            for (int i = 0; i < R; ++i) {
+                tk[2 * i] = b[2 * o[4 * i + 3]];
+                tk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
+            }
+        }
+        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_tg0, c->stream));
+        const long n_mat = (long)n * R * 2;                 // M | M' | M'' packed by this chunk's count
+        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
+        CHK(launch_check(c, "pk_expm_batched"));
+        hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_P, n_mat,
+                           d_P + n_mat * 16, d_P + 2 * n_mat * 16);
+        CHK(launch_check(c, "ptg_dmats"));
+        launches += 2;
+        if (coded) {
+            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
+            CHK(launch_check(c, "pt2_gap_rows"));
+            ++launches;
+        }
+        ptg_args g{};
+        pt2_args& a = g.a;
+        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
+        a.prior = prior4 ? d_prior : c->d_pi;
+        a.tilev = d_tilev; a.site_lik = nullptr;
+        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
+        g.dops = d_dops; g.dtile = d_dtile; g.store = (pk_d2*)(base + pl.o_store);
+        g.mat_plane = n_mat * 16;
+        g.n_items = n * ntiles; g.depth = depth;
+        ptg_launch(g, std::min(pl.grid, g.n_items), coded, want_curv, c->stream);
+        CHK(launch_check(c, "ptg_updown"));
+        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
+        CHK(launch_check(c, "pt2_finish"));
+        hipLaunchKernelGGL(ptg_finish, dim3(cdiv((long)n * nq * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)d_ops,
+                           (const double*)d_out, ntiles, n, R, nq, d_dout);
+        CHK(launch_check(c, "ptg_finish"));
+        launches += 3;
+        HIPCHK(c, hipEventRecord(c->ev_tg1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(grad + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
+        if (want_curv)
+            HIPCHK(c, hipMemcpyAsync(curv + (size_t)t0 * 2 * R, d_dout + (size_t)n * 2 * R, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tg0, c->ev_tg1));
+        ms_total += ms;
+    }
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * R;
+        st.alg_bytes = 96.0 * st.units;
         *perf = st;
     }
     return PHYLO_OK;

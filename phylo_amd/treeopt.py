@@ -1,0 +1,123 @@
+"""Maximum-likelihood branch lengths of a set of trees: a driver in plain NumPy over a function that returns
+the log-likelihood of every tree with its gradient and own second derivatives (Context.trees_grad on the device, any restatement
+of it in the tests).  No device code here."""
+import numpy as np
+
+EPS_CURV = 1e-6          # a curvature above -EPS_CURV (flat or convex along the branch) is taken for -EPS_CURV
+ARMIJO = 1e-4            # a step is accepted when the log-likelihood rises by at least this share of what the gradient promises
+NOISE = 2.0 ** -46       # two log-likelihoods closer than this share of their size are told apart by their gradients (see below)
+MEMORY = 8               # pairs (change of lengths, change of gradient) a tree keeps for its quasi-Newton correction
+MIN_FACTOR = 2.0 ** -4   # a tree whose step factor falls below this forgets its pairs: the plain diagonal step is an ascent direction
+
+
+def _free(b, g, lo, hi):
+    """branches that may move: not at a bound with the gradient pointing outward"""
+    return ~(((b <= lo) & (g < 0)) | ((b >= hi) & (g > 0)))
+
+
+def _converged(b, g, lo, hi, gtol):
+    """per tree: every branch has |g| <= gtol, or sits at a bound with the gradient pointing outward"""
+    ok = (np.abs(g) <= gtol) | ~_free(b, g, lo, hi)
+    return ok.all(axis=1)
+
+
+def _direction(g, c, free, mem, b):
+    """Per tree the ascent direction: the diagonal Newton step -g / min(c, -EPS_CURV) of every free branch, corrected by the
+    tree's remembered pairs (the two-loop recursion of L-BFGS with the diagonal Newton matrix as its initial matrix; with no
+    pair remembered it IS the diagonal step).  g, c, free, b [T][n]; mem a list of (s, y, rho) with rho [T] (0 = pair not held)."""
+    h0 = -1.0 / np.minimum(c, -EPS_CURV)
+    q = np.where(free, g, 0.0)
+    alphas = []
+    for s, y, rho in reversed(mem):
+        a = rho * (s * q).sum(axis=1)
+        q = q - a[:, None] * y
+        alphas.append(a)
+    d = h0 * q
+    for (s, y, rho), a in zip(mem, reversed(alphas)):
+        beta = rho * (y * d).sum(axis=1)
+        d = d + (a - beta)[:, None] * s
+    d = np.where(free, d, 0.0)
+    plain = np.where(free, h0 * g, 0.0)
+    bad = ~np.isfinite(d).all(axis=1) | ((g * d).sum(axis=1) <= 0)
+    d[bad] = plain[bad]
+    cap = np.maximum(1.0, b)                                # no branch moves by more than its own length (or 1) in one step: a flat or
+    return np.clip(d, -cap, cap), bad                       # convex branch (curvature taken for -EPS_CURV) would otherwise jump to a bound
+
+
+def optimize_branches(grad_fn, child, blen, lo=1e-8, hi=100.0, max_iter=50, gtol=1e-6):
+    """Climb the log-likelihood of T trees over their branch lengths.  grad_fn(blen [T][N-1][2]) -> (loglik [T], grad, curv) for
+    all trees at once; child is carried for the caller (grad_fn knows the topologies).
+
+    All trees advance in lockstep, one call of grad_fn per iteration.  A tree's trial point is its current lengths plus its
+    step factor times its direction, projected onto [lo, hi].  The direction is the diagonal Newton step -g / min(curv,
+    -EPS_CURV) of every branch; because branches that share a degree of freedom (the two at the root under a reversible model,
+    the branches round an internal branch of length zero) make that step alone swing about the optimum or crawl, a tree also
+    remembers its last MEMORY accepted steps and corrects the direction by them (L-BFGS over the diagonal Newton matrix).  The
+    trial is accepted when the tree's log-likelihood does not fall and rises by ARMIJO of the first-order promise (a promise
+    below the rounding of the log-likelihood is not asked for); otherwise the tree keeps its lengths and its factor is halved.
+    After an accepted step the factor is 1 again.  A tree's lengths change on accepted steps only: its sequence of
+    log-likelihoods never falls.  A tree is converged when every branch has |g| <= gtol or sits at a bound with the gradient
+    pointing outward.
+
+    Returns a dict: 'blen' [T][N-1][2], 'loglik' [T], 'iterations' [T] (calls of grad_fn while the tree was not converged),
+    'converged' [T] bool, 'grad' [T][N-1][2] at the returned lengths, 'history' [calls + 1][T] the log-likelihood of every tree
+    at the start and after every call."""
+    del child
+    b = np.clip(np.array(blen, dtype=np.float64), lo, hi)
+    if b.ndim == 2:
+        b = b[None]
+    shape = b.shape
+    T = shape[0]
+    b = b.reshape(T, -1)
+
+    def call(x):
+        ll, g, c = grad_fn(x.reshape(shape))
+        return np.array(ll, dtype=np.float64), np.array(g, dtype=np.float64).reshape(T, -1), np.array(c, dtype=np.float64).reshape(T, -1)
+
+    ll, g, c = call(b)
+    if not np.isfinite(ll).all():
+        raise ValueError("optimize_branches: a tree's log-likelihood is not finite at the starting lengths")
+    factor = np.ones(T)
+    iters = np.zeros(T, dtype=np.int64)
+    history = [ll.copy()]
+    mem = []
+    free_was = _free(b, g, lo, hi)
+    done = _converged(b, g, lo, hi, gtol)
+    for _ in range(max_iter):
+        if done.all():
+            break
+        free = _free(b, g, lo, hi)
+        d, bad = _direction(g, c, free, mem, b)
+        forget = bad | (factor < MIN_FACTOR) | (free != free_was).any(axis=1)      # (pairs made with another set of moving branches mislead)
+        free_was = free
+        if forget.any():
+            for _, _, rho in mem:
+                rho[forget] = 0.0
+            plain, _ = _direction(g, c, free, [], b)
+            d[forget] = plain[forget]
+        trial = np.clip(b + factor[:, None] * d, lo, hi)
+        trial[done] = b[done]
+        promise = (g * (trial - b)).sum(axis=1)
+        ll_t, g_t, c_t = call(trial)
+        iters[~done] += 1
+        with np.errstate(invalid='ignore'):
+            # Inside the rounding of the sum over sites the difference of two log-likelihoods says nothing, while the gradients at
+            # both ends still do: there the rise is judged by the trapezoid (g + g_t) . step / 2, and the tree's log-likelihood
+            # keeps the larger of the two computed values (they differ by less than NOISE |loglik|).
+            near = np.abs(ll_t - ll) <= NOISE * np.abs(ll)
+            rise = 0.5 * ((g + g_t) * (trial - b)).sum(axis=1)
+            take = ~done & np.isfinite(ll_t) & np.where(near, rise >= 0, (ll_t >= ll) & (ll_t - ll >= ARMIJO * promise))
+        ll_t = np.where(near, np.maximum(ll, ll_t), ll_t)
+        s, y = trial - b, g - g_t                           # (y of -loglik: positive curvature).  Accepted steps only: a refused trial
+        sy = (s * y).sum(axis=1)                            # may lie where the surface is nothing like it is here
+        keep = take & (sy > 1e-300)
+        s, y = np.where(keep[:, None], s, 0.0), np.where(keep[:, None], y, 0.0)
+        rho = np.where(keep, 1.0 / np.where(keep, sy, 1.0), 0.0)
+        mem = (mem + [(s, y, rho)])[-MEMORY:]
+        b[take], ll[take], g[take], c[take] = trial[take], ll_t[take], g_t[take], c_t[take]
+        factor[take] = 1.0
+        factor[~take & ~done] *= 0.5
+        history.append(ll.copy())
+        done = _converged(b, g, lo, hi, gtol)
+    return {'blen': b.reshape(shape), 'loglik': ll, 'iterations': iters, 'converged': done, 'grad': g.reshape(shape),
+            'history': np.array(history)}

@@ -304,18 +304,34 @@ class VCSMC:
             tab = new
         return [row[0] for row in tab]
 
-    def score_trees(self, newicks, rates=None, want_sites=False):
+    def score_trees(self, newicks, rates=None, want_sites=False, optimize=False):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
         distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
         (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
         rates (phylo_trees_loglik_rates).  Returns a list of floats -- with want_sites, that list and the site factors [T][S] the
-        call returned --; a local call on every rank when sharded."""
+        call returned --; a local call on every rank when sharded.
+        optimize=True (not with rates): the branch lengths of every tree are first climbed to their maximum-likelihood values
+        (phylo_amd.treeopt.optimize_branches over phylo_trees_grad); the scores, and the site factors of one final
+        trees_loglik(want_sites=True), are at those lengths, and self.last_tree_opt holds 'newicks' (the trees at those
+        lengths), 'loglik_given', 'iterations' and 'converged' per tree."""
+        if optimize and rates is not None:
+            raise ValueError("score_trees: optimize=True is not built for rate mixtures (phylo_trees_grad has no rates form)")
         rows = [treepost.newick_to_rows(nw, self.taxa) for nw in newicks]
         if not rows:
             return ([], np.empty((0, self.S))) if want_sites else []
         ctx = self._context()
         child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
-        if rates is None:
+        if optimize:
+            from . import treeopt
+            given = ctx.trees_loglik(child, blen)
+            opt = treeopt.optimize_branches(lambda b: ctx.trees_grad(child, b, want_curv=True), child, blen)
+            blen = opt['blen']
+            self.last_tree_opt = {'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(child, blen)],
+                                  'loglik_given': [float(x) for x in given], 'iterations': [int(i) for i in opt['iterations']],
+                                  'converged': [bool(v) for v in opt['converged']]}
+            res = ctx.trees_loglik(child, blen, want_sites=True)
+            res = res if want_sites else res[0]
+        elif rates is None:
             res = ctx.trees_loglik(child, blen, want_sites=want_sites)
         else:
             res = ctx.trees_loglik_rates(child, blen, rates[0], rates[1], want_sites=want_sites)
@@ -345,18 +361,29 @@ class VCSMC:
             rm = rates_mod.parse_spec(spec)
         mix = None if rm is None else (rm['rates'], rm['weights'])
         tests = getattr(self.args, 'tree_tests', None)
+        ml = bool(getattr(self.args, 'score_opt', False)) and bool(newicks)   # --score_opt: at maximum-likelihood branch lengths
         self.tree_test_results = None
-        if tests and newicks:                              # --tree_tests: from the site factors of this very scoring call
-            from . import treetests
+        self.trees_ml = None
+        if ml:
+            ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True)
+            opt = self.last_tree_opt
+            ll = opt['loglik_given']
+            self.trees_ml = opt['newicks']
+        elif tests and newicks:                            # --tree_tests: from the site factors of this very scoring call
             ll, sites = self.score_trees(newicks, rates=mix, want_sites=True)
-            self.tree_test_results = self.tree_tests(sites, *treetests.parse_spec(tests))
         else:
             ll = self.score_trees(newicks, rates=mix)
+        if tests and newicks:                              # (with --score_opt: the site factors at the ML lengths)
+            from . import treetests
+            self.tree_test_results = self.tree_tests(sites, *treetests.parse_spec(tests))
         out = {'model': {'Q': np.asarray(self.Qmatrix, dtype=np.float64).tolist(),
                          'pi': np.asarray(self.stationary_probs, dtype=np.float64).reshape(-1).tolist(),
                          'jc69_closed_form': bool(self.args.jcmodel)},
                'trees': [{'newick': nw, 'loglik': x} for nw, x in zip(newicks, ll)],
                'best': int(np.argmax(ll)) if ll else None}
+        if ml:                                             # (absent without --score_opt: the file is what it was before the flag)
+            for t, x, it, cv in zip(out['trees'], ll_ml, opt['iterations'], opt['converged']):
+                t.update(loglik_ml=x, iterations=it, converged=cv)
         if rm is not None:                                 # (absent without --score_rates: the file is what it was before the flag)
             out['rates'] = {'spec': rm['spec'], 'rates': rm['rates'].tolist(), 'weights': rm['weights'].tolist()}
         post = self.posterior
@@ -383,7 +410,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))
@@ -505,6 +532,9 @@ class VCSMC:
                 import os
                 with open(os.path.join(save_dir, 'tree_scores.json'), 'w') as f:
                     json.dump(scores, f, indent=1)
+                if getattr(self, 'trees_ml', None) is not None:
+                    with open(os.path.join(save_dir, 'trees_ml.nwk'), 'w') as f:
+                        f.write('\n'.join(self.trees_ml) + '\n')
                 if getattr(self, 'tree_test_results', None) is not None:
                     with open(os.path.join(save_dir, 'tree_tests.json'), 'w') as f:
                         json.dump(self.tree_test_results, f, indent=1)

@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -67,6 +67,11 @@ def parse_args(argv=None):
                              "ALPHA (Yang 1994, mean rates), and with PINV > 0 a class of invariant sites of that proportion (the "
                              "rates of the variable sites are not rescaled); every score in tree_scores.json is then under that "
                              "model, and the file names its rates and weights")
+    parser.add_argument('--score_opt', default=False, type=lambda x: (str(x).lower() == 'true'),
+                        help="with --score_trees: first climb every tree's branch lengths to their maximum-likelihood values "
+                             "(phylo_trees_grad on the device, phylo_amd/treeopt.py); writes trees_ml.nwk (the trees at those "
+                             "lengths), adds loglik_ml, iterations and converged to every tree of tree_scores.json, and gives "
+                             "--tree_tests the site likelihoods at those lengths.  Not with --score_rates")
     parser.add_argument('--tree_tests', default=None, metavar='B[:SEED]',
                         help="with --score_trees: which of those trees are significantly worse than the best one?  A RELL bootstrap "
                              "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
@@ -89,6 +94,11 @@ def parse_args(argv=None):
             rates.parse_spec(args.score_rates)
         except ValueError as e:
             parser.error('--score_rates: %s' % e)
+    if args.score_opt:
+        if not args.score_trees:
+            parser.error('--score_opt true needs --score_trees FILE (it optimises the branch lengths of the trees scored there)')
+        if args.score_rates is not None:
+            parser.error('--score_opt true: the branch-length gradient is not built for rate mixtures (not with --score_rates)')
     if args.tree_branches and not args.tree_summary:
         parser.error('--tree_branches true needs --tree_summary true (it adds branch lengths to that summary)')
     if args.twisting is not None:

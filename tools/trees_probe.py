@@ -11,7 +11,13 @@ the trees (all of them by default) `loop_reps` times.  Medians with the quartile
 
 --rates C times phylo_trees_loglik_rates under C discrete Gamma categories (--alpha) instead, against C
 plain phylo_trees_loglik calls on the scaled trees in the same run: device and wall times of both, their ratios, and whether
-cat_lik carries the plain calls' site factors bit for bit."""
+cat_lik carries the plain calls' site factors bit for bit.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --grad --reps 7 --out profiles/trees_probe.jsonl
+
+--grad times phylo_trees_grad, with and without curvature, against the plain phylo_trees_loglik on the
+same trees in the same run: device and wall times, their ratios, the 4 (N-1) + 1 plain calls a central-difference gradient would
+cost, and whether loglik carries the plain call's bits."""
 import argparse
 import json
 import os
@@ -96,6 +102,53 @@ def rates_probe(a):
     return 0 if same else 1
 
 
+def grad_probe(a):
+    """phylo_trees_grad, with and without curvature, against the plain call: same trees, same context, same run"""
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        ll = ctx.trees_loglik(child, blen)                   # warm-up of all three
+        lg, grad = ctx.trees_grad(child, blen)
+        lc, grad2, curv = ctx.trees_grad(child, blen, want_curv=True)
+        same = bool(np.array_equal(ll.view(np.uint64), lg.view(np.uint64)) and np.array_equal(ll.view(np.uint64), lc.view(np.uint64))
+                    and np.array_equal(grad.view(np.uint64), grad2.view(np.uint64)))
+        t = {k: ([], []) for k in ('plain', 'grad', 'curv')}
+        for _ in range(a.reps):                              # interleaved: all three see the same machine
+            for k, call in (('plain', lambda: ctx.trees_loglik(child, blen)), ('grad', lambda: ctx.trees_grad(child, blen)),
+                            ('curv', lambda: ctx.trees_grad(child, blen, want_curv=True))):
+                t0 = time.perf_counter()
+                call()
+                t[k][0].append((time.perf_counter() - t0) * 1e3)
+                t[k][1].append(ctx.last_trees_stats['sweep_ms'])
+            stats = dict(ctx.last_trees_stats)
+    q = {k: (quartiles(v[0]), quartiles(v[1])) for k, v in t.items()}
+    n_fd = 4 * (N - 1) + 1
+    rec = {'probe': 'trees_grad', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'jc': jc, 'reps': a.reps,
+           'plain_wall_ms': q['plain'][0], 'plain_device_ms': q['plain'][1], 'grad_wall_ms': q['grad'][0], 'grad_device_ms': q['grad'][1],
+           'curv_wall_ms': q['curv'][0], 'curv_device_ms': q['curv'][1],
+           'device_ratio_grad_over_plain': q['grad'][1]['median'] / q['plain'][1]['median'],
+           'device_ratio_curv_over_plain': q['curv'][1]['median'] / q['plain'][1]['median'],
+           'wall_ratio_grad_over_plain': q['grad'][0]['median'] / q['plain'][0]['median'],
+           'wall_ratio_curv_over_plain': q['curv'][0]['median'] / q['plain'][0]['median'],
+           'central_difference_calls': n_fd, 'central_difference_device_ms': n_fd * q['plain'][1]['median'],
+           'launches': stats['n_launches'], 'units': stats['units'], 'units_per_s_device_grad': stats['units'] / (q['grad'][1]['median'] * 1e-3),
+           'loglik_and_grad_bit_equal': same, 'finite': bool(np.isfinite(grad).all() and np.isfinite(curv).all())}
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -108,7 +161,10 @@ def main(argv=None):
     ap.add_argument('--out', default=None)
     ap.add_argument('--rates', type=int, default=0, help='C > 0: probe phylo_trees_loglik_rates under C Gamma categories')
     ap.add_argument('--alpha', type=float, default=0.5)
+    ap.add_argument('--grad', action='store_true', help='probe phylo_trees_grad (with and without curvature) against the plain call')
     a = ap.parse_args(argv)
+    if a.grad:
+        return grad_probe(a)
     if a.rates > 0:
         return rates_probe(a)
     jc = a.jc.lower() == 'true'
