@@ -179,7 +179,8 @@ int phylo_trees_loglik_rates(phylo_ctx* ctx, int T, const int32_t* child, const 
  * both shaped [T][N-1][2] as blen.  The sums run in a fixed order (64 sites by the wave's adjacent-pair tree, the steps of a
  * site tile in ascending order, the tiles left to right; no atomics): a call repeats its own bits, and chunking changes none.
  * Against a restatement the derivatives carry a tolerance, not a bit contract.  A tree whose loglik is not finite gets NaN in
- * every derivative entry.  perf (may be NULL): sweep_ms = device time, n_launches, units = T S (N-1).
+ * every derivative entry, and so does a tree with any site factor L_s below 2^-1020 (partials are not rescaled; 1 / L_s is no
+ * double there), whose loglik_T stays what phylo_trees_loglik gives.  perf (may be NULL): sweep_ms = device time, n_launches, units = T S (N-1).
  * Synchronous; on a sharded context a LOCAL call.  PHYLO_EINVAL before anything is queued for a bad tree (naming tree and row) and
  * for child, blen, loglik_T or grad == NULL.  Large T runs in chunks (64 MiB; PHYLO_TREES_CHUNK caps the trees of a chunk); the
  * node stores of the resident workgroups take at most 256 MiB more.  Own scratch and events, released with the context: the

@@ -525,7 +525,8 @@ class Context:
     def trees_grad(self, child, blen, prior=None, want_curv=False):
         """Derivatives of trees_loglik with respect to every branch length (phylo_trees_grad): returns (loglik [T], grad
         [T][N-1][2]) or, with want_curv, (loglik, grad, curv) -- curv the own second derivative of every length.  loglik is bit
-        for bit trees_loglik's; a tree whose loglik is not finite has NaN derivatives.  self.last_trees_stats holds the call's
+        for bit trees_loglik's; a tree whose loglik is not finite, or which has a site factor below 2^-1020 (a finite loglik
+        then), has NaN derivatives.  self.last_trees_stats holds the call's
         stats.  phylo_amd.treeopt.optimize_branches climbs with it."""
         child, blen = _tree_rows(child, blen, self.N)
         T = child.shape[0]

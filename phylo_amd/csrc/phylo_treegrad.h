@@ -14,6 +14,7 @@
 #define PTG_CHUNK_BYTES ((size_t)64 << 20)        // device scratch of one chunk of trees, the node store apart
 #define PTG_STORE_BYTES ((size_t)256 << 20)       // the node stores of all resident workgroups
 #define PTG_WG_PER_CU 8                           // workgroups (= waves) per compute unit the grid is capped at
+#define PTG_LIK_FLOOR 0x1p-1020                   // a site factor below this (or not finite) has no usable reciprocal: NaN derivatives
 
 // ------------------------------------------------------------------------------------------------
 // host: the plan of one call -- no HIP, so that a plain host program can run it under sanitizers (tests/treegrad_asan_main.cpp)
@@ -164,7 +165,8 @@ __device__ __forceinline__ double ptg_xDg(const double (&x)[4], const double (&D
 // bits) with every non-root node also stored to the workgroup's node store [row][site step][half][lane]; then the schedule in
 // reverse: the outer partial of the node (the prior at the root, else what its parent left in the node's slot), both children's
 // partials (ptg_child) and both messages again (the upward chain), g, and per branch L' / L (and L'' / L - (L' / L)^2) in the
-// contract's order (ptg_xDg; M' and M'' wave-uniform), reduced over the wave by pk_wave_tree_sum and added by lane 0 into its
+// contract's order (ptg_xDg; M' and M'' wave-uniform; 1 / L is NaN where L lies below PTG_LIK_FLOOR or is not finite), reduced
+// over the wave by pk_wave_tree_sum and added by lane 0 into its
 // entry of the LDS array acc[nq][2 (N-1)]; the outer partial of an internal child overwrites the child's partial.  A lane only
 // ever touches its own column of the store, and lane 0 alone the array: neither needs a fence inside an item.
 // Launched with depth * U * 2048 + nq * 2 (N-1) * 8 bytes of dynamic LDS.
@@ -230,7 +232,9 @@ __global__ __launch_bounds__(64) void ptg_updown(const ptg_args g) {
                 inv[u] = 0.0;
                 if (base + 64 * u < s1) {                   // wave-uniform
                     const double lik = pk_site_lik(pr, o[u]);
-                    inv[u] = 1.0 / lik;
+                    // below the floor 1 / lik overflows (lik < 2^-1024) or is made from a subnormal's few bits: NaN, which the
+                    // wave reduction carries into every sum of the tile and ptg_finish into every entry of the tree
+                    inv[u] = lik >= PTG_LIK_FLOOR && lik < pm_inf() ? 1.0 / lik : pm_nan();
                     if (s < s1) pm_lp_mul(col, lik);
                 }
             }
@@ -323,7 +327,8 @@ __global__ __launch_bounds__(64) void ptg_updown(const ptg_args g) {
 }
 
 // Per (tree, quantity, branch of the schedule): the tiles added left to right; written to the caller's row (op.w) and side.  A tree
-// whose log-likelihood is not finite gets NaN in every entry.  out [nq][trees][N-1][2].
+// whose log-likelihood is not finite gets NaN in every entry (one with a site factor below PTG_LIK_FLOOR already carries it).
+// out [nq][trees][N-1][2].
 __global__ __launch_bounds__(256) void ptg_finish(const double* __restrict__ dtile, const int32_t* __restrict__ ops, const double* __restrict__ loglik,
                                                   int ntiles, int trees, int R, int nq, double* __restrict__ out) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -10,6 +10,10 @@ MEMORY = 8               # pairs (change of lengths, change of gradient) a tree 
 MIN_FACTOR = 2.0 ** -4   # a tree whose step factor falls below this forgets its pairs: the plain diagonal step is an ascent direction
 
 
+class OutOfRangeError(ValueError):
+    """a tree cannot be climbed from its starting lengths: its log-likelihood or its derivatives are not finite there"""
+
+
 def _free(b, g, lo, hi):
     """branches that may move: not at a bound with the gradient pointing outward"""
     return ~(((b <= lo) & (g < 0)) | ((b >= hi) & (g > 0)))
@@ -55,6 +59,9 @@ def optimize_branches(grad_fn, child, blen, lo=1e-8, hi=100.0, max_iter=50, gtol
     remembers its last MEMORY accepted steps and corrects the direction by them (L-BFGS over the diagonal Newton matrix).  The
     trial is accepted when the tree's log-likelihood does not fall and rises by ARMIJO of the first-order promise (a promise
     below the rounding of the log-likelihood is not asked for); otherwise the tree keeps its lengths and its factor is halved.
+    A trial whose log-likelihood, gradient or curvature is not finite is refused like one that falls: phylo_trees_grad gives NaN
+    derivatives beside a finite log-likelihood to a tree with a site factor below 2^-1020, and there is
+    nothing to climb on there.  A tree in that state at the STARTING lengths raises OutOfRangeError (a ValueError) naming it.
     After an accepted step the factor is 1 again.  A tree's lengths change on accepted steps only: its sequence of
     log-likelihoods never falls.  A tree is converged when every branch has |g| <= gtol or sits at a bound with the gradient
     pointing outward.
@@ -75,8 +82,12 @@ def optimize_branches(grad_fn, child, blen, lo=1e-8, hi=100.0, max_iter=50, gtol
         return np.array(ll, dtype=np.float64), np.array(g, dtype=np.float64).reshape(T, -1), np.array(c, dtype=np.float64).reshape(T, -1)
 
     ll, g, c = call(b)
-    if not np.isfinite(ll).all():
-        raise ValueError("optimize_branches: a tree's log-likelihood is not finite at the starting lengths")
+    for t in range(T):
+        if not np.isfinite(ll[t]):
+            raise OutOfRangeError("optimize_branches: the log-likelihood of tree %d is not finite at the starting lengths" % t)
+        if not (np.isfinite(g[t]).all() and np.isfinite(c[t]).all()):
+            raise OutOfRangeError("optimize_branches: the gradient of tree %d is not finite at the starting lengths (log-likelihood "
+                                  "%.17g): a site likelihood lies below 2^-1020, outside the range of phylo_trees_grad" % (t, ll[t]))
     factor = np.ones(T)
     iters = np.zeros(T, dtype=np.int64)
     history = [ll.copy()]
@@ -106,8 +117,9 @@ def optimize_branches(grad_fn, child, blen, lo=1e-8, hi=100.0, max_iter=50, gtol
             # keeps the larger of the two computed values (they differ by less than NOISE |loglik|).
             near = np.abs(ll_t - ll) <= NOISE * np.abs(ll)
             rise = 0.5 * ((g + g_t) * (trial - b)).sum(axis=1)
-            take = ~done & np.isfinite(ll_t) & np.where(near, rise >= 0, (ll_t >= ll) & (ll_t - ll >= ARMIJO * promise))
-        ll_t = np.where(near, np.maximum(ll, ll_t), ll_t)
+            ok_t = np.isfinite(ll_t) & np.isfinite(g_t).all(axis=1) & np.isfinite(c_t).all(axis=1)
+            take = ~done & ok_t & np.where(near, rise >= 0, (ll_t >= ll) & (ll_t - ll >= ARMIJO * promise))
+        ll_t = np.where(near & ok_t, np.maximum(ll, ll_t), ll_t)
         s, y = trial - b, g - g_t                           # (y of -loglik: positive curvature).  Accepted steps only: a refused trial
         sy = (s * y).sum(axis=1)                            # may lie where the surface is nothing like it is here
         keep = take & (sy > 1e-300)

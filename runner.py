@@ -8,6 +8,7 @@ Same flags and defaults.  Differences: datasets come from an 
 encodes them) are new.
 """
 import argparse
+import sys
 
 import numpy as np
 
@@ -121,8 +122,13 @@ def main(argv=None):
     from phylo_amd.vcsmc import VCSMC
     datadict = load_dataset(args.dataset, ambiguity=args.ambiguity)
     vcsmc = VCSMC(datadict, K=args.n_particles, args=args)
-    return vcsmc.train(epochs=args.num_epoch, batch_size=args.batch_size, learning_rate=args.learning_rate,
-                       memory_optimization=args.memory_optimization)
+    from phylo_amd.treeopt import OutOfRangeError
+    try:
+        return vcsmc.train(epochs=args.num_epoch, batch_size=args.batch_size, learning_rate=args.learning_rate,
+                           memory_optimization=args.memory_optimization)
+    except OutOfRangeError as e:                           # --score_opt on a tree that cannot be climbed: a message, no traceback
+        sys.exit("runner.py --score_opt: %s (trees are numbered from 0 in the order of %s; score it without --score_opt true, "
+                 "or give it branch lengths under which every site has a likelihood above 2^-1020)" % (e, args.score_trees))
 
 
 if __name__ == "__main__":

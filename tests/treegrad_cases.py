@@ -6,6 +6,10 @@ from scipy.linalg import expm
 # Measured by test_treegrad_cpu.py::test_reference_against_mpmath (N = 5, S = 8, gaps; grad and curv, GTR and JC69): the worst
 # |reference - 50-digit value| / ((scale + |value|) 2^-53) is 8.59; the test asserts that it stays at or below E_REF.
 E_REF = 8.6
+# Measured by test_trees_edges_cpu.py::test_reference_against_mpmath_at_the_floor (the same 40 trees, every site factor scaled into
+# [2^-1020, 2^-1000] through two leaves): 8.59 in the same units -- the floor costs the restatement nothing, so 2^-1020, the bound
+# the sweep's reverse pass states, is the bound below which phylo_trees_grad gives NaN, and TOL holds down to it.
+E_REF_FLOOR = 8.6
 TOL = 8 * E_REF * 2.0 ** -53         # device against reference: |difference| <= TOL (scale + |value|)
 
 

@@ -7,8 +7,13 @@ row order, M[i][side] the matrix of the branch above child[i][side]), so that wh
     L'_s(b) = sum_k x_child[k] sum_j M'_b[k][j] g_b[j],  M' = M Q,  M'' = M' Q
     grad = sum_s L'/L,  curv = sum_s (L''/L - (L'/L)^2),  scale = sum_s |L'/L|
 
+The range: a tree with a site factor L_s below FLOOR = 2^-1020, or not finite, gets NaN in every derivative entry (1 / L_s is
+no double below 2^-1024, and a subnormal L_s holds a handful of bits); its loglik is what it is.
+
 `site_terms` is the same for ONE site over any number type (floats, mpmath's mpf): the high-precision yardstick of the tests."""
 import numpy as np
+
+FLOOR = 2.0 ** -1020     # the smallest site factor whose tree still gets derivatives (DESIGN.md section 13)
 
 
 def dmat(M, Q):
@@ -23,7 +28,10 @@ def dmat(M, Q):
 def fma(a, b, c):
     """round(a b + c) with ONE rounding, as the device's fma: the product exactly as p + e (Veltkamp's split, Dekker's product),
     p + c exactly as s + t (Knuth's sum), then s + (t + e).  Exact unless a b + c lies within 2^-106 of its size of a rounding
-    boundary, or a value is near the ends of the double range (|a|, |b| < 1e300, |a b| > 1e-290: every partial here is)."""
+    boundary, or a value is near the ends of the double range (|a|, |b| < 1e300, |a b| > 1e-290).  Partials of alignments whose
+    site factors stay above 1e-290 are inside; towards FLOOR they are not: there the error term e of the product underflows and
+    this is an ordinary chain of rounded operations, within an ulp or so of the device's fma and no longer its bits.  Nothing
+    is claimed bit for bit per site down there; the tolerance of the tests covers it (treegrad_cases.E_REF_FLOOR)."""
     a, b, c = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(c, dtype=np.float64))
     p = a * b
     ah = a * 134217729.0
@@ -47,23 +55,42 @@ def _row_times(x, M):
     return out
 
 
-def tree_grad(child, M, Q, prior, leaves):
-    """child [N-1][2], M [N-1][2][4][4], leaves [N][S][4]  ->  loglik, grad, curv, scale (the last three [N-1][2])"""
+def _upward(child, M, prior, leaves):
+    """the upward pass: every node's partial x [N + R] of [S][4], the messages [R][2][S][4] and the site factors L [S]"""
+    N, S = leaves.shape[0], leaves.shape[1]
+    R = N - 1
+    x = [leaves[i] for i in range(N)] + [None] * R
+    msg = np.empty((R, 2, S, 4))
+    with np.errstate(all='ignore'):
+        for i in range(R):
+            for sd in range(2):
+                msg[i, sd] = _row_times(x[child[i, sd]], M[i, sd])
+            x[N + i] = msg[i, 0] * msg[i, 1]
+        xr = x[N + R - 1]
+        L = fma(prior[3], xr[:, 3], fma(prior[2], xr[:, 2], fma(prior[1], xr[:, 1], prior[0] * xr[:, 0])))     # pk_site_lik's chain
+    return x, msg, L
+
+
+def site_factors(child, M, prior, leaves):
+    """L_s [S] of one tree: what the preconditions of the tests are read from"""
+    return _upward(np.asarray(child), np.asarray(M, dtype=np.float64), np.asarray(prior, dtype=np.float64).reshape(4), leaves)[2]
+
+
+def trees_site_factors(child, M, prior, leaves):
+    return np.array([site_factors(c, m, prior, leaves) for c, m in zip(child, M)])
+
+
+def tree_grad(child, M, Q, prior, leaves, want_sites=False):
+    """child [N-1][2], M [N-1][2][4][4], leaves [N][S][4]  ->  loglik, grad, curv, scale (the last three [N-1][2]); with
+    want_sites the site factors L [S] as a fifth"""
     child = np.asarray(child)
     N, S = leaves.shape[0], leaves.shape[1]
     R = N - 1
     M = np.asarray(M, dtype=np.float64)
     M1 = dmat(M, Q)
     M2 = dmat(M1, Q)
-    x = [leaves[i] for i in range(N)] + [None] * R
-    msg = np.empty((R, 2, S, 4))
-    for i in range(R):
-        for sd in range(2):
-            msg[i, sd] = _row_times(x[child[i, sd]], M[i, sd])
-        x[N + i] = msg[i, 0] * msg[i, 1]
     prior = np.asarray(prior, dtype=np.float64).reshape(4)
-    xr = x[N + R - 1]
-    L = fma(prior[3], xr[:, 3], fma(prior[2], xr[:, 2], fma(prior[1], xr[:, 1], prior[0] * xr[:, 0])))     # pk_site_lik's chain
+    x, msg, L = _upward(child, M, prior, leaves)
     abar = [None] * (N + R)
     abar[N + R - 1] = np.broadcast_to(prior, (S, 4))
     grad, curv, scale = np.empty((R, 2)), np.empty((R, 2)), np.empty((R, 2))
@@ -89,15 +116,15 @@ def tree_grad(child, M, Q, prior, leaves):
                         a[:, k] = ((M[i, sd, k, 0] * g[:, 0] + M[i, sd, k, 1] * g[:, 1]) + M[i, sd, k, 2] * g[:, 2]) + M[i, sd, k, 3] * g[:, 3]
                     abar[ch] = a
         loglik = float(np.sum(np.log(L)))
-    if not np.isfinite(loglik):
+    if not (np.isfinite(loglik) and np.isfinite(L).all() and (L >= FLOOR).all()):
         grad[:], curv[:] = np.nan, np.nan
-    return loglik, grad, curv, scale
+    return (loglik, grad, curv, scale, L) if want_sites else (loglik, grad, curv, scale)
 
 
-def trees_grad(child, M, Q, prior, leaves):
-    """T trees: child [T][N-1][2], M [T][N-1][2][4][4]  ->  loglik [T], grad, curv, scale [T][N-1][2]"""
-    res = [tree_grad(c, m, Q, prior, leaves) for c, m in zip(child, M)]
-    return tuple(np.array([r[k] for r in res]) for k in range(4))
+def trees_grad(child, M, Q, prior, leaves, want_sites=False):
+    """T trees: child [T][N-1][2], M [T][N-1][2][4][4]  ->  loglik [T], grad, curv, scale [T][N-1][2] (and L [T][S])"""
+    res = [tree_grad(c, m, Q, prior, leaves, want_sites) for c, m in zip(child, M)]
+    return tuple(np.array([r[k] for r in res]) for k in range(5 if want_sites else 4))
 
 
 def site_terms(child, M, Q, prior, rows, zero):
