@@ -187,6 +187,25 @@ int phylo_trees_loglik_rates(phylo_ctx* ctx, int T, const int32_t* child, const 
  * sweep's state, a pending phylo_sweep_backward, a tree summary and the scratch of phylo_trees_loglik and phylo_rell are left alone. */
 int phylo_trees_grad(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
                      double* grad, double* curv, phylo_stats* perf);
+/* phylo_trees_grad under a mixture of C rate categories: the derivatives of phylo_trees_loglik_rates'
+ * MIXTURE log-likelihood.  rate and weight are [C] with per_tree == 0 (one mixture for all trees) and [T][C] with per_tree == 1
+ * (tree t under its own row), 1 <= C <= 16.  With r = rate[t][c], w = weight[t][c], f_c the factor of category c, m = the site
+ * value of phylo_trees_loglik_rates, D1_c (D2_c) the L' (L'') of phylo_trees_grad inside category c (a derivative with respect to
+ * the SCALED length r * blen), u_c = w r, v_c = u_c r, a1 = sum_c u_c D1_c and a2 = sum_c v_c D2_c (c ascending from +0.0):
+ *   loglik_T[t]      bit for bit phylo_trees_loglik_rates' value for that tree under that tree's mixture (same prior and tile);
+ *   grad[t][i][side] = sum_s a1 / m;   curv[t][i][side] (may be NULL) = sum_s (a2 / m - (a1 / m)^2);
+ *   drate_TxC[t][c]  (may be NULL) = sum_s sum_b blen_b w D1_{c,b} / m, d loglik / d rate[t][c] at fixed blen;
+ *   dweight_TxC[t][c] (may be NULL) = sum_s f_c / m.
+ * A rate-0 category, a zero weight and a site with some f_c == 0 are ordinary.  Fixed order of summation, no atomics: a call
+ * repeats its own bits; chunking, the grid cap, a tree's place, shared against per-tree passing of the same numbers and the
+ * optional outputs change none of grad's.  NaN rule: phylo_trees_grad's, on m.  perf: units = T S (N-1) C.
+ * Synchronous; a LOCAL call on a sharded context; state rules, per-tree checks and chunking as phylo_trees_loglik_rates.
+ * PHYLO_EINVAL before anything is queued for a bad tree, C outside 1 .. 16, a bad rate, weight or scaled length (the message names
+ * tree, row and category), per_tree outside {0, 1}, and for child, blen, rate, weight, loglik_T or grad == NULL.  Own scratch and
+ * events, released with the context; everything phylo_trees_grad leaves alone, and phylo_trees_grad's own scratch, is left alone. */
+int phylo_trees_grad_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate,
+                           const double* weight, int per_tree, const double* prior4, double* loglik_T, double* grad, double* curv,
+                           double* drate_TxC, double* dweight_TxC, phylo_stats* perf);
 /* Test hook, no GPU needed: the host half of phylo_trees_loglik on ONE tree -- the checks above (PHYLO_EINVAL, "tree 0, row i")
  * and the slot schedule the kernel walks: ops[N-1][4] = {destination slot, left source, right source, row}, a source >= 0 a
  * leaf, a source < 0 the slot ~source; depth = slots in use (<= floor(log2 N) + 1).  tests/test_trees_host.py replays it. */

@@ -30,6 +30,7 @@
 #include "phylo_treeset.h"
 #include "phylo_rell.h"
 #include "phylo_treegrad.h"
+#include "phylo_treegrad_rates.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -242,9 +243,9 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[17];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+    DevBuf scratch[18];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
                                          //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates;
-                                         //  16: phylo_trees_grad's chunk and node stores)
+                                         //  16: phylo_trees_grad's chunk and node stores; 17: phylo_trees_grad_rates's)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -260,6 +261,7 @@ struct phylo_ctx {
     hipEvent_t ev_tl0 = nullptr, ev_tl1 = nullptr;   // phylo_trees_loglik's own pair (the sweep's and the summaries' stay theirs)
     hipEvent_t ev_rl0 = nullptr, ev_rl1 = nullptr;   // phylo_rell's own pair
     hipEvent_t ev_tg0 = nullptr, ev_tg1 = nullptr;   // phylo_trees_grad's own pair
+    hipEvent_t ev_tr0 = nullptr, ev_tr1 = nullptr;   // phylo_trees_grad_rates' own pair
 };
 
 namespace {
@@ -782,6 +784,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_rl1) (void)hipEventDestroy(c->ev_rl1);
     if (c->ev_tg0) (void)hipEventDestroy(c->ev_tg0);
     if (c->ev_tg1) (void)hipEventDestroy(c->ev_tg1);
+    if (c->ev_tr0) (void)hipEventDestroy(c->ev_tr0);
+    if (c->ev_tr1) (void)hipEventDestroy(c->ev_tr1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -1437,6 +1441,143 @@ int phylo_trees_grad(phylo_ctx* c, int T, const int32_t* child, const double* bl
         st.sweep_ms = ms_total;
         st.n_launches = launches;
         st.units = (double)T * S * R;
+        st.alg_bytes = 96.0 * st.units;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
+// ---- the same under a mixture of rate categories (phylo_treegrad_rates.h) ----
+int phylo_trees_grad_rates(phylo_ctx* c, int T, const int32_t* child, const double* blen, int C, const double* rate, const double* weight,
+                           int per_tree, const double* prior4, double* loglik_T, double* grad, double* curv, double* drate_TxC,
+                           double* dweight_TxC, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_grad_rates needs phylo_set_leaves and phylo_set_model first");
+    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    if (C < 1 || C > PT2_MAX_CATS) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
+    if (per_tree != 0 && per_tree != 1) return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: per_tree must be 0 or 1 (per_tree=%d)", per_tree);
+    if (!child || !blen || !rate || !weight || !loglik_T || !grad)
+        return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: child, blen, rate, weight, loglik and grad must be given (NULL pointer)");
+    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
+    const size_t mix_stride = per_tree ? (size_t)C : 0;    // tree t's mixture: row t, or the one row
+    for (int t = 0; t < T; ++t) {                          // every tree and its mixture are checked before anything is queued
+        int row = 0;
+        char msg[200];
+        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+        if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
+    }
+    const bool coded = c->leaves_coded, want_curv = curv != nullptr, want_params = drate_TxC != nullptr || dweight_TxC != nullptr;
+    ptgr_plan pl;
+    if (ptgr_make_plan(N, ntiles, T, C, coded, want_curv, want_params, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+        return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: no plan for N=%d, %d tiles, T=%d, C=%d", N, ntiles, T, C);
+    const int chunk = pl.chunk, nq = pl.nq, np = pl.np;
+    void* slab = nullptr;
+    CHK(scratch_get(c, 17, pl.total, &slab));
+    char* base = (char*)slab;
+    double* d_prior = (double*)(base + pl.o_prior);
+    double* d_coef = (double*)(base + pl.o_coef);
+    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
+    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
+    double* d_P = (double*)(base + pl.o_P);
+    double* d_t = (double*)(base + pl.o_t);
+    double* d_b = (double*)(base + pl.o_b);
+    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
+    double* d_tilev = (double*)(base + pl.o_tilev);
+    double* d_out = (double*)(base + pl.o_out);
+    double* d_dtile = (double*)(base + pl.o_dtile);
+    double* d_dout = (double*)(base + pl.o_dout);
+    double* d_ptile = want_params ? (double*)(base + pl.o_ptile) : nullptr;
+    double* d_pout = want_params ? (double*)(base + pl.o_pout) : nullptr;
+    if (!c->ev_tr0) {
+        HIPCHK(c, hipEventCreate(&c->ev_tr0));
+        HIPCHK(c, hipEventCreate(&c->ev_tr1));
+    }
+    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
+    std::vector<double> ts((size_t)chunk * C * R * 2), bs((size_t)chunk * R * 2), coef((size_t)chunk * pl.ncoef);
+    double ms_total = 0.0;
+    int launches = 0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int n = std::min(chunk, T - t0);
+        int depth = 1;
+        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every set of lengths in its order
+            int32_t* o = ops.data() + (size_t)t * R * 4;
+            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
+            depth = std::max(depth, pt2_schedule(N, ch, o));
+            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
+                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
+            const double* b = blen + (size_t)(t0 + t) * R * 2;
+            const double* rt = rate + (t0 + t) * mix_stride;
+            double* bk = bs.data() + (size_t)t * R * 2;
+            for (int i = 0; i < R; ++i) {
+                bk[2 * i] = b[2 * o[4 * i + 3]];
+                bk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
+            }
+            for (int k = 0; k < C; ++k) {
+                double* tk = ts.data() + ((size_t)t * C + k) * R * 2;
+                for (int i = 0; i < 2 * R; ++i) tk[i] = rt[k] * bk[i];
+            }
+            ptgr_coefficients(C, rt, weight + (t0 + t) * mix_stride, coef.data() + (size_t)t * pl.ncoef);
+        }
+        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+        if (ptgr_lds_bytes(N, depth, C, want_curv, want_params) > PTGR_MAX_LDS)
+            return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: %zu bytes of LDS for a wave exceed %zu (depth %d, N=%d, C=%d)",
+                        ptgr_lds_bytes(N, depth, C, want_curv, want_params), PTGR_MAX_LDS, depth, N, C);
+        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * C * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_b, bs.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_coef, coef.data(), (size_t)n * pl.ncoef * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_tr0, c->stream));
+        const long n_mat = (long)n * C * R * 2;             // M | M' | M'' packed by this chunk's count
+        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
+        CHK(launch_check(c, "pk_expm_batched"));
+        hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_P, n_mat,
+                           d_P + n_mat * 16, d_P + 2 * n_mat * 16);
+        CHK(launch_check(c, "ptg_dmats"));
+        launches += 2;
+        if (coded) {
+            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
+            CHK(launch_check(c, "pt2_gap_rows"));
+            ++launches;
+        }
+        ptgr_args g{};
+        pt2_args& a = g.a;
+        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
+        a.prior = prior4 ? d_prior : c->d_pi;
+        a.tilev = d_tilev; a.site_lik = nullptr;
+        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
+        g.dops = d_dops; g.coef = d_coef; g.blen = d_b; g.dtile = d_dtile; g.ptile = d_ptile; g.store = (pk_d2*)(base + pl.o_store);
+        g.mat_plane = n_mat * 16;
+        g.n_items = n * ntiles; g.depth = depth; g.C = C;
+        ptgr_launch(g, std::min(pl.grid, g.n_items), coded, want_curv, want_params, c->stream);
+        CHK(launch_check(c, "ptgr_updown"));
+        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
+        CHK(launch_check(c, "pt2_finish"));
+        hipLaunchKernelGGL(ptgr_finish, dim3(cdiv((long)n * (nq * 2 * R + np * C), 256)), dim3(256), 0, c->stream, (const double*)d_dtile,
+                           (const double*)d_ptile, (const int32_t*)d_ops, (const double*)d_out, ntiles, n, R, nq, np, C, d_dout, d_pout);
+        CHK(launch_check(c, "ptgr_finish"));
+        launches += 3;
+        HIPCHK(c, hipEventRecord(c->ev_tr1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(grad + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
+        if (want_curv)
+            HIPCHK(c, hipMemcpyAsync(curv + (size_t)t0 * 2 * R, d_dout + (size_t)n * 2 * R, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
+        if (drate_TxC) HIPCHK(c, hipMemcpyAsync(drate_TxC + (size_t)t0 * C, d_pout, (size_t)n * C * 8, hipMemcpyDeviceToHost, c->stream));
+        if (dweight_TxC)
+            HIPCHK(c, hipMemcpyAsync(dweight_TxC + (size_t)t0 * C, d_pout + (size_t)n * C, (size_t)n * C * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tr0, c->ev_tr1));
+        ms_total += ms;
+    }
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * R * C;
         st.alg_bytes = 96.0 * st.units;
         *perf = st;
     }

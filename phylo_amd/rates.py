@@ -136,27 +136,56 @@ def discrete_gamma(alpha, C, kind='mean'):
     return np.array([C * (cut[k + 1] - cut[k]) for k in range(C)])
 
 
-def rate_model(alpha=None, C=4, pinv=0.0):
+def rate_model(alpha=None, C=4, pinv=0.0, keep_invariant=False):
     """(rates, weights) of a rate mixture for Context.trees_loglik_rates: C discrete Gamma categories of shape alpha (alpha None:
     the single rate 1), each of weight (1 - pinv) / C, and with pinv > 0 an invariant class first: rate 0, weight pinv.
 
     The rates of the variable sites are NOT rescaled by 1 / (1 - pinv): their mean stays 1 and the mean rate over all sites is
     1 - pinv, so a branch length counts substitutions per VARIABLE site -- the convention of PAML and PhyML, and the one under
-    which a tree inferred by them under +I+G carries its branch lengths."""
+    which a tree inferred by them under +I+G carries its branch lengths.  keep_invariant: the invariant class is there at
+    pinv = 0 too (weight 0: an ordinary category), so that a fit of pinv keeps one layout."""
     pinv = float(pinv)
     if not 0.0 <= pinv < 1.0:
         raise ValueError("rate_model needs 0 <= pinv < 1 (pinv=%r)" % pinv)
     gam = np.array([1.0]) if alpha is None else discrete_gamma(alpha, C)
     w = np.full(gam.size, (1.0 - pinv) / gam.size)
-    if pinv > 0.0:
+    if pinv > 0.0 or keep_invariant:
         gam, w = np.concatenate([[0.0], gam]), np.concatenate([[pinv], w])
     if gam.size > MAX_CATS:
         raise ValueError("%d rate categories; at most %d" % (gam.size, MAX_CATS))
     return gam, w
 
 
+JAC_STEP = 1e-4            # the step in log alpha of rate_model_jacobian's central difference
+
+
+def rate_model_jacobian(alpha, C=4, pinv=0.0, keep_invariant=False):
+    """(d rates / d alpha, d weights / d pinv) in rate_model's layout for the same arguments (the invariant class first when
+    pinv > 0 or keep_invariant).  d weights / d pinv is exact: +1 for the invariant class, -1 / C for every other.  d rates /
+    d alpha is the central difference of discrete_gamma in log alpha, (r(alpha e^h) - r(alpha e^-h)) / (2 h alpha) with h =
+    JAC_STEP = 1e-4: the truncation term is of the order h^2 = 1e-8 of the rates' size and the rounding of discrete_gamma
+    (about 1e-14) enters as 1e-14 / h = 1e-10; the invariant class has derivative 0."""
+    alpha, C, pinv = float(alpha), int(C), float(pinv)
+    if not 0.0 <= pinv < 1.0:
+        raise ValueError("rate_model_jacobian needs 0 <= pinv < 1 (pinv=%r)" % pinv)
+    up, dn = discrete_gamma(alpha * math.exp(JAC_STEP), C), discrete_gamma(alpha * math.exp(-JAC_STEP), C)
+    dr = (up - dn) / (2.0 * JAC_STEP * alpha)
+    dw = np.full(C, -1.0 / C)
+    if pinv > 0.0 or keep_invariant:
+        dr, dw = np.concatenate([[0.0], dr]), np.concatenate([[1.0], dw])
+    return dr, dw
+
+
+def chain(drate, dweight, jac):
+    """(d loglik / d alpha, d loglik / d pinv) from Context.trees_grad_rates' drate and dweight [..., C] and rate_model_jacobian's
+    pair, each [C] or [..., C] (one Jacobian per tree): the sums over the categories."""
+    dr, dw = np.asarray(jac[0], dtype=np.float64), np.asarray(jac[1], dtype=np.float64)
+    return (np.asarray(drate, dtype=np.float64) * dr).sum(axis=-1), (np.asarray(dweight, dtype=np.float64) * dw).sum(axis=-1)
+
+
 def parse_spec(spec):
-    """'gamma:ALPHA:C[:PINV]' (runner.py --score_rates) -> {'spec', 'rates', 'weights'}; ValueError on anything else."""
+    """'gamma:ALPHA:C[:PINV]' (runner.py --score_rates) -> {'spec', 'rates', 'weights', 'alpha', 'C', 'pinv'}; ValueError on
+    anything else."""
     parts = str(spec).split(':')
     if parts[0] != 'gamma' or len(parts) not in (3, 4):
         raise ValueError("a rate model is gamma:ALPHA:C or gamma:ALPHA:C:PINV, not %r" % (spec,))
@@ -166,7 +195,7 @@ def parse_spec(spec):
     except ValueError:
         raise ValueError("a rate model is gamma:ALPHA:C or gamma:ALPHA:C:PINV with numbers, not %r" % (spec,)) from None
     rates, weights = rate_model(alpha, C, pinv)
-    return {'spec': str(spec), 'rates': rates, 'weights': weights}
+    return {'spec': str(spec), 'rates': rates, 'weights': weights, 'alpha': alpha, 'C': C, 'pinv': pinv}
 
 
 def site_rates(cat_lik, rates, weights):

@@ -304,24 +304,53 @@ class VCSMC:
             tab = new
         return [row[0] for row in tab]
 
-    def score_trees(self, newicks, rates=None, want_sites=False, optimize=False):
+    def score_trees(self, newicks, rates=None, want_sites=False, optimize=False, fit=()):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
         distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
         (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
         rates (phylo_trees_loglik_rates).  Returns a list of floats -- with want_sites, that list and the site factors [T][S] the
         call returned --; a local call on every rank when sharded.
-        optimize=True (not with rates): the branch lengths of every tree are first climbed to their maximum-likelihood values
-        (phylo_amd.treeopt.optimize_branches over phylo_trees_grad); the scores, and the site factors of one final
-        trees_loglik(want_sites=True), are at those lengths, and self.last_tree_opt holds 'newicks' (the trees at those
-        lengths), 'loglik_given', 'iterations' and 'converged' per tree."""
-        if optimize and rates is not None:
-            raise ValueError("score_trees: optimize=True is not built for rate mixtures (phylo_trees_grad has no rates form)")
+        optimize=True: the branch lengths of every tree are first climbed to their maximum-likelihood values
+        (phylo_amd.treeopt.optimize_branches over phylo_trees_grad, or with rates over phylo_trees_grad_rates under that
+        mixture); the scores, and the site factors of a final scoring call, are at those lengths, and self.last_tree_opt holds
+        'newicks' (the trees at those lengths), 'loglik_given', 'iterations' and 'converged' per tree.
+        fit (with optimize and rates): ('alpha',) or ('alpha', 'pinv') -- every tree also climbs its own Gamma shape (and share
+        of invariant sites) from the model's values (phylo_amd.treeopt.optimize_rates); rates is then what
+        phylo_amd.rates.parse_spec returns (it knows alpha, C and p_inv), the final scores come from one trees_loglik_rates per
+        tree under that tree's fitted mixture, and self.last_tree_opt also holds 'alpha' and 'pinv' (None without the class)."""
+        fit = tuple(fit)
+        spec = rates if isinstance(rates, dict) else None
+        if spec is not None:
+            rates = (spec['rates'], spec['weights'])
+        if fit and not (optimize and spec is not None):
+            raise ValueError("score_trees: fit=%r needs optimize=True and rates as phylo_amd.rates.parse_spec gives them" % (fit,))
         rows = [treepost.newick_to_rows(nw, self.taxa) for nw in newicks]
         if not rows:
             return ([], np.empty((0, self.S))) if want_sites else []
         ctx = self._context()
         child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
-        if optimize:
+        if optimize and rates is not None:
+            from . import treeopt
+            given = ctx.trees_loglik_rates(child, blen, rates[0], rates[1])
+            if fit:
+                opt = treeopt.optimize_rates(lambda b, r, w: ctx.trees_grad_rates(child, b, r, w, want_curv=True, want_params=True),
+                                             child, blen, spec['alpha'], spec['C'], pinv0=spec['pinv'], fit=fit)
+            else:
+                opt = treeopt.optimize_branches(lambda b: ctx.trees_grad_rates(child, b, rates[0], rates[1], want_curv=True), child, blen)
+            blen = opt['blen']
+            self.last_tree_opt = {'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(child, blen)],
+                                  'loglik_given': [float(x) for x in given], 'iterations': [int(i) for i in opt['iterations']],
+                                  'converged': [bool(v) for v in opt['converged']]}
+            if fit:
+                self.last_tree_opt['alpha'] = [float(a) for a in opt['alpha']]
+                self.last_tree_opt['pinv'] = None if opt['pinv'] is None else [float(p) for p in opt['pinv']]
+                per = [ctx.trees_loglik_rates(child[t], blen[t], opt['rates'][t], opt['weights'][t], want_sites=True)
+                       for t in range(child.shape[0])]
+                res = (np.array([p[0][0] for p in per]), np.array([p[1][0] for p in per]))
+            else:
+                res = ctx.trees_loglik_rates(child, blen, rates[0], rates[1], want_sites=True)
+            res = res if want_sites else res[0]
+        elif optimize:
             from . import treeopt
             given = ctx.trees_loglik(child, blen)
             opt = treeopt.optimize_branches(lambda b: ctx.trees_grad(child, b, want_curv=True), child, blen)
@@ -362,6 +391,8 @@ class VCSMC:
         mix = None if rm is None else (rm['rates'], rm['weights'])
         tests = getattr(self.args, 'tree_tests', None)
         ml = bool(getattr(self.args, 'score_opt', False)) and bool(newicks)   # --score_opt: at maximum-likelihood branch lengths
+        mode = getattr(self.args, 'score_fit', None)       # --score_fit: the same under the rate model, and its parameters fitted
+        fit = tuple(mode.split('+')[1:]) if mode and newicks else None
         self.tree_test_results = None
         self.trees_ml = None
         if ml:
@@ -369,6 +400,12 @@ class VCSMC:
             opt = self.last_tree_opt
             ll = opt['loglik_given']
             self.trees_ml = opt['newicks']
+        elif fit is not None:
+            ll_ml, sites = self.score_trees(newicks, rates=rm, want_sites=True, optimize=True, fit=fit)
+            opt = self.last_tree_opt
+            ll = opt['loglik_given']
+            self.trees_ml = opt['newicks']
+            ml = True
         elif tests and newicks:                            # --tree_tests: from the site factors of this very scoring call
             ll, sites = self.score_trees(newicks, rates=mix, want_sites=True)
         else:
@@ -384,6 +421,11 @@ class VCSMC:
         if ml:                                             # (absent without --score_opt: the file is what it was before the flag)
             for t, x, it, cv in zip(out['trees'], ll_ml, opt['iterations'], opt['converged']):
                 t.update(loglik_ml=x, iterations=it, converged=cv)
+            if fit:                                        # --score_fit with a fitted model: every tree's own values
+                for i, t in enumerate(out['trees']):
+                    t['alpha'] = opt['alpha'][i]
+                    if opt['pinv'] is not None:
+                        t['pinv'] = opt['pinv'][i]
         if rm is not None:                                 # (absent without --score_rates: the file is what it was before the flag)
             out['rates'] = {'spec': rm['spec'], 'rates': rm['rates'].tolist(), 'weights': rm['weights'].tolist()}
         post = self.posterior
@@ -410,7 +452,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))

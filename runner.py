@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -72,7 +72,15 @@ def parse_args(argv=None):
                         help="with --score_trees: first climb every tree's branch lengths to their maximum-likelihood values "
                              "(phylo_trees_grad on the device, phylo_amd/treeopt.py); writes trees_ml.nwk (the trees at those "
                              "lengths), adds loglik_ml, iterations and converged to every tree of tree_scores.json, and gives "
-                             "--tree_tests the site likelihoods at those lengths.  Not with --score_rates")
+                             "--tree_tests the site likelihoods at those lengths.  Not with --score_rates: under a rate model "
+                             "--score_fit does this")
+    parser.add_argument('--score_fit', default=None, choices=['branches', 'branches+alpha', 'branches+alpha+pinv'],
+                        help="with --score_trees and --score_rates: climb every tree's branch lengths to their maximum-likelihood "
+                             "values UNDER that rate model (phylo_trees_grad_rates on the device), and with +alpha (+pinv) also "
+                             "every tree's own Gamma shape (and share of invariant sites), starting from the model's values; "
+                             "writes trees_ml.nwk, adds loglik_ml, iterations, converged (and alpha, pinv where fitted) to every "
+                             "tree of tree_scores.json, and gives --tree_tests the site likelihoods at the fitted values.  Not "
+                             "with --score_opt true")
     parser.add_argument('--tree_tests', default=None, metavar='B[:SEED]',
                         help="with --score_trees: which of those trees are significantly worse than the best one?  A RELL bootstrap "
                              "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
@@ -99,7 +107,16 @@ def parse_args(argv=None):
         if not args.score_trees:
             parser.error('--score_opt true needs --score_trees FILE (it optimises the branch lengths of the trees scored there)')
         if args.score_rates is not None:
-            parser.error('--score_opt true: the branch-length gradient is not built for rate mixtures (not with --score_rates)')
+            parser.error('--score_opt true: the one-rate branch-length gradient is not built for rate mixtures (not with '
+                         '--score_rates); --score_fit branches climbs the lengths under the rate model')
+    if args.score_fit is not None:
+        if not args.score_trees or args.score_rates is None:
+            parser.error('--score_fit needs --score_trees FILE and --score_rates gamma:ALPHA:C[:PINV] (it fits the trees scored there '
+                         'under that rate model, from its values)')
+        if args.score_opt:
+            parser.error('--score_fit and --score_opt true exclude one another (--score_fit branches is --score_opt under the rate model)')
+        if 'alpha' in args.score_fit and rates.parse_spec(args.score_rates)['C'] < 2:
+            parser.error('--score_fit %s: one category has no shape to fit (--score_rates with C >= 2)' % args.score_fit)
     if args.tree_branches and not args.tree_summary:
         parser.error('--tree_branches true needs --tree_summary true (it adds branch lengths to that summary)')
     if args.twisting is not None:
@@ -126,9 +143,11 @@ def main(argv=None):
     try:
         return vcsmc.train(epochs=args.num_epoch, batch_size=args.batch_size, learning_rate=args.learning_rate,
                            memory_optimization=args.memory_optimization)
-    except OutOfRangeError as e:                           # --score_opt on a tree that cannot be climbed: a message, no traceback
-        sys.exit("runner.py --score_opt: %s (trees are numbered from 0 in the order of %s; score it without --score_opt true, "
-                 "or give it branch lengths under which every site has a likelihood above 2^-1020)" % (e, args.score_trees))
+    except OutOfRangeError as e:                           # --score_opt / --score_fit on a tree that cannot be climbed: a message, no traceback
+        flag = '--score_fit' if args.score_fit else '--score_opt'
+        sys.exit("runner.py %s: %s (trees are numbered from 0 in the order of %s; score it without %s, "
+                 "or give it branch lengths under which every site has a likelihood above 2^-1020)"
+                 % (flag, e, args.score_trees, '--score_fit' if args.score_fit else '--score_opt true'))
 
 
 if __name__ == "__main__":

@@ -17,7 +17,13 @@ cat_lik carries the plain calls' site factors bit for bit.
 
 --grad times phylo_trees_grad, with and without curvature, against the plain phylo_trees_loglik on the
 same trees in the same run: device and wall times, their ratios, the 4 (N-1) + 1 plain calls a central-difference gradient would
-cost, and whether loglik carries the plain call's bits."""
+cost, and whether loglik carries the plain call's bits.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --grad --rates 4 --reps 7 --out profiles/trees_probe.jsonl
+
+--grad --rates C times phylo_trees_grad_rates under C discrete Gamma categories: the gradient alone,
+with curvature, and with curvature and the rate and weight sums, against C calls of phylo_trees_grad (with curvature) on the
+scaled trees, interleaved in the same run; the number of chunks, and whether loglik carries phylo_trees_loglik_rates' bits."""
 import argparse
 import json
 import os
@@ -149,6 +155,66 @@ def grad_probe(a):
     return 0 if same else 1
 
 
+def grad_rates_probe(a):
+    """phylo_trees_grad_rates against C calls of phylo_trees_grad on the scaled trees: same trees, same context, same run"""
+    from phylo_amd import rates as R
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    rates, weights = R.rate_model(a.alpha, a.rates)
+    C = rates.size
+    scaled = [rates[c] * blen for c in range(C)]             # (outside the timed region: the caller of C plain calls holds them)
+    forms = {'grad': {}, 'curv': dict(want_curv=True), 'all': dict(want_curv=True, want_params=True)}
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        ll = ctx.trees_loglik_rates(child, blen, rates, weights)                           # warm-up of every form
+        outs = {k: ctx.trees_grad_rates(child, blen, rates, weights, **kw) for k, kw in forms.items()}
+        per_chunk = 6 if ctx.last_trees_stats['n_launches'] % 6 == 0 else 5
+        chunks = ctx.last_trees_stats['n_launches'] // per_chunk
+        for c in range(C):
+            ctx.trees_grad(child, scaled[c], want_curv=True)
+        same = all(bool(np.array_equal(o[0].view(np.uint64), ll.view(np.uint64)) and
+                        np.array_equal(o[1].view(np.uint64), outs['grad'][1].view(np.uint64))) for o in outs.values())
+        t = {k: ([], []) for k in list(forms) + ['plain_x_C']}
+        for _ in range(a.reps):                              # interleaved: all see the same machine
+            for k, kw in forms.items():
+                t0 = time.perf_counter()
+                ctx.trees_grad_rates(child, blen, rates, weights, **kw)
+                t[k][0].append((time.perf_counter() - t0) * 1e3)
+                t[k][1].append(ctx.last_trees_stats['sweep_ms'])
+                stats = dict(ctx.last_trees_stats)
+            t0 = time.perf_counter()
+            d = 0.0
+            for c in range(C):
+                ctx.trees_grad(child, scaled[c], want_curv=True)
+                d += ctx.last_trees_stats['sweep_ms']
+            t['plain_x_C'][0].append((time.perf_counter() - t0) * 1e3)
+            t['plain_x_C'][1].append(d)
+    q = {k: (quartiles(v[0]), quartiles(v[1])) for k, v in t.items()}
+    rec = {'probe': 'trees_grad_rates', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'jc': jc, 'reps': a.reps,
+           'C': int(C), 'alpha': a.alpha, 'chunks': int(chunks)}
+    for k in t:
+        rec[k + '_wall_ms'], rec[k + '_device_ms'] = q[k]
+    for k in forms:
+        rec['device_ratio_%s_over_plain_x_C' % k] = q[k][1]['median'] / q['plain_x_C'][1]['median']
+        rec['wall_ratio_%s_over_plain_x_C' % k] = q[k][0]['median'] / q['plain_x_C'][0]['median']
+    rec.update({'launches': stats['n_launches'], 'units': stats['units'],
+                'units_per_s_device_curv': stats['units'] / (q['curv'][1]['median'] * 1e-3), 'loglik_and_grad_bit_equal': same,
+                'finite': bool(all(np.isfinite(x).all() for x in outs['all']))})
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -163,6 +229,8 @@ def main(argv=None):
     ap.add_argument('--alpha', type=float, default=0.5)
     ap.add_argument('--grad', action='store_true', help='probe phylo_trees_grad (with and without curvature) against the plain call')
     a = ap.parse_args(argv)
+    if a.grad and a.rates > 0:
+        return grad_rates_probe(a)
     if a.grad:
         return grad_probe(a)
     if a.rates > 0:
