@@ -371,6 +371,12 @@ int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int tw
  * phylo_sweep_begin refuses are refused with the same code and message.  tests/test_sweepplan_cpu.py restates the rules. */
 int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
                            uint32_t* mask, int32_t* launches);
+/* Test hook, no GPU needed: the form the resampling scan takes for groups of Kg log-weights (sweep_scan_form_of, phylo_sweep_plan.h;
+ * DESIGN.md section 6b): 0 the scan of several workgroups per group (pp_scan_multi_*), 1 pp_resample_scan<512>, 2
+ * pp_resample_scan<1024>, 3 pk_resample_scan(_groups); -1 for Kg < 1.  ctx NULL: under PHYLO_SCAN_MULTI_MIN = multi_min; else under
+ * the value the context read when it was created (multi_min is ignored).  wanted: the caller asks for a cdf or a log-normaliser
+ * (phylo_resample, phylo_log_zsmc and every scan of a sweep do).  tests/test_sweepplan_cpu.py restates the rule. */
+int phylo_debug_scan_form(phylo_ctx* ctx, int Kg, int multi_min, int wanted);
 /* Test hook, no GPU needed: the packed image of byte codes [N][S] as phylo_set_leaves builds it beside them (pk_pack_leaf_codes,
  * phylo_packed_codes.h): packed[((leaf nC + Jc) 64 + c) 16 + j] = code of site 64 (16 Jc + j) + c with
  * nC = ceil(ceil(S / 64) / 16), sites >= S hold the pad code 5.  *need = N nC 1024, the image's bytes; with packed NULL only
@@ -396,15 +402,19 @@ int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches
                                    int passes_in_flight, uint32_t* mask);
 /* No GPU and no context needed: the form of phylo_tree_summary and phylo_tree_branches (pt_plan_form / pb_plan_form of
  * phylo_trees_plan.h; DESIGN.md section 10 "driver") for a sweep of G groups on `world` ranks, a summary of n_clades and
- * n_topologies rows, whether the sweep kept whole-K branch lengths, and rocPRIM's temporary-storage bytes of either pass (facts).
+ * n_topologies rows, whether the sweep kept whole-K branch lengths, whether PHYLO_TREE_WIDE_KEYS is set (force_wide: the 64-bit
+ * keys of the branch pass at any size), and rocPRIM's temporary-storage bytes of either pass (facts).
  * scalars[13]: R, L, W, E, Emax, Kg, cbits, tbits, wide, gather, the number of sort passes, the buffers of slot 12, of slot 13.
  * summary_slab / branches_slab [2 n + 1]: the n buffers' offsets, their bytes, the slab's total (order: TREE_SUMMARY_BUFS /
  * TREE_BRANCHES_BUFS of phylo_amd/_ffi.py).  sort_bits[17]: the radix bits of the summary's sort passes in issue order.
  * launches[2]: what stats.n_launches of the two calls counts.  What the calls refuse is refused with the same code and message
- * (the summary's first).  tests/test_treeplan_cpu.py restates the rules. */
-int phylo_debug_tree_plan(int N, int K, int G, int world, int64_t n_clades, int64_t n_topologies, int kept_whole, int64_t summary_temp,
-                          int64_t branches_temp, int64_t* scalars, int64_t* summary_slab, int64_t* branches_slab, int32_t* sort_bits,
-                          int32_t* launches);
+ * (the summary's first).  tests/test_treeplan_cpu.py restates the rules.
+ * phylo_debug_tree_branches_of: the plan the context's last phylo_tree_branches took: *wide (1: the 64-bit keys), *cbits, *tbits.
+ * PHYLO_ESTATE when no branch pass has run on the context. */
+int phylo_debug_tree_plan(int N, int K, int G, int world, int64_t n_clades, int64_t n_topologies, int kept_whole, int force_wide,
+                          int64_t summary_temp, int64_t branches_temp, int64_t* scalars, int64_t* summary_slab, int64_t* branches_slab,
+                          int32_t* sort_bits, int32_t* launches);
+int phylo_debug_tree_branches_of(phylo_ctx* ctx, int32_t* wide, int32_t* cbits, int32_t* tbits);
 
 /* The same lists built by the device kernels (phylo_revlists_dev.h) from the graph of the preceding lazy sweep with
  * PHYLO_KEEP_GRAPH, copied back in the same layout (what the builders do not write reads -1; heavy[] holds GLOBAL chunk indices,

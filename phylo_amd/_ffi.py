@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -237,10 +237,10 @@ TREE_BRANCHES_BUFS = ("ebr", "lbr", "gbl", "gbr", "o_cs", "o_ls", "o_ts", "wA", 
                       "temp")
 
 
-def debug_tree_plan(N, K, G=1, world=1, n_clades=1, n_topologies=1, kept_whole=False, summary_temp=0, branches_temp=0):
+def debug_tree_plan(N, K, G=1, world=1, n_clades=1, n_topologies=1, kept_whole=False, summary_temp=0, branches_temp=0, force_wide=False):
     """The form phylo_tree_summary and phylo_tree_branches take for a sweep of G groups on `world` ranks, a summary of n_clades and
-    n_topologies rows, whether the sweep kept whole-K branch lengths, and rocPRIM's temporary-storage bytes of either pass -- no
-    GPU needed.  A dict: the scalars R, L, W, E, Emax, Kg, cbits, tbits, wide, gather; 'summary_slab' / 'branches_slab' =
+    n_topologies rows, whether the sweep kept whole-K branch lengths, rocPRIM's temporary-storage bytes of either pass and whether
+    PHYLO_TREE_WIDE_KEYS is set (force_wide) -- no GPU needed.  A dict: the scalars R, L, W, E, Emax, Kg, cbits, tbits, wide, gather; 'summary_slab' / 'branches_slab' =
     {'offsets': {name: bytes}, 'sizes': {name: bytes}, 'total'} over TREE_SUMMARY_BUFS / TREE_BRANCHES_BUFS (scratch slots 12 and
     13); 'sort_bits', the radix bits of the summary's sort passes in issue order; 'summary_launches', 'branches_launches'."""
     lib = load()
@@ -249,7 +249,8 @@ def debug_tree_plan(N, K, G=1, world=1, n_clades=1, n_topologies=1, kept_whole=F
     ss, bs = (C.c_int64 * (2 * ns + 1))(), (C.c_int64 * (2 * nb + 1))()
     bits, launches = (C.c_int32 * 17)(), (C.c_int32 * 2)()
     rc = lib.phylo_debug_tree_plan(C.c_int(N), C.c_int(K), C.c_int(G), C.c_int(world), C.c_int64(n_clades), C.c_int64(n_topologies),
-                                   C.c_int(int(kept_whole)), C.c_int64(summary_temp), C.c_int64(branches_temp), sc, ss, bs, bits, launches)
+                                   C.c_int(int(kept_whole)), C.c_int(int(force_wide)), C.c_int64(summary_temp), C.c_int64(branches_temp),
+                                   sc, ss, bs, bits, launches)
     if rc:
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     out = dict(zip(("R", "L", "W", "E", "Emax", "Kg", "cbits", "tbits"), sc[:8]))
@@ -262,6 +263,19 @@ def debug_tree_plan(N, K, G=1, world=1, n_clades=1, n_topologies=1, kept_whole=F
     out["sort_bits"] = list(bits[:sc[10]])
     out["summary_launches"], out["branches_launches"] = launches[0], launches[1]
     return out
+
+
+SCAN_FORMS = ("multi", "lds512", "lds1024", "in_place")   # pp_scan_multi_*, pp_resample_scan<512>, <1024>, pk_resample_scan(_groups)
+
+
+def debug_scan_form(Kg, multi_min=4096, wanted=True):
+    """The form launch_scan takes for groups of Kg log-weights under PHYLO_SCAN_MULTI_MIN = multi_min (sweep_scan_form_of; no GPU
+    and no context needed): a name of SCAN_FORMS.  wanted: the caller asks for a cdf or a log-normaliser."""
+    lib = load()
+    rc = lib.phylo_debug_scan_form(None, C.c_int(Kg), C.c_int(multi_min), C.c_int(int(wanted)))
+    if rc < 0:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return SCAN_FORMS[rc]
 
 
 def debug_reverse_plan_batch(N, K, G, S, switches=(), n_slow=0, TS=None, coeff_wgs=0, passes_in_flight=1):
@@ -880,6 +894,19 @@ class Context:
         U, taken = C.c_int32(0), C.c_int32(0)
         self._check(self._lib.phylo_debug_site_patterns_of(self._h, C.byref(U), C.byref(taken)))
         return U.value, bool(taken.value)
+
+    def debug_tree_branches(self):
+        """The plan the last tree_branches() of this context took: {'wide': 64-bit (topology, clade) keys, 'cbits', 'tbits'}"""
+        wide, cbits, tbits = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.phylo_debug_tree_branches_of(self._h, C.byref(wide), C.byref(cbits), C.byref(tbits)))
+        return {'wide': bool(wide.value), 'cbits': cbits.value, 'tbits': tbits.value}
+
+    def debug_scan_form(self, Kg, wanted=True):
+        """debug_scan_form with the PHYLO_SCAN_MULTI_MIN this context read when it was created"""
+        rc = self._lib.phylo_debug_scan_form(self._h, C.c_int(Kg), C.c_int(0), C.c_int(int(wanted)))
+        if rc < 0:
+            raise PhyloError(rc, self._lib.phylo_last_error(self._h).decode())
+        return SCAN_FORMS[rc]
 
     def comm_exchange_kind(self):
         """'none' | 'rccl' | 'hostshm' | 'p2p': how the K-vectors of a rank event reach the other ranks"""

@@ -60,7 +60,7 @@ struct sweep_run {                       // a sweep being issued rank event by r
 struct env_switches {
     bool eager_nodes = false, rehearse_sharded = false, replicated_book = false, no_leaf_codes = false, one_launch = false,
          persist_stamps = false, grad_one_stream = false, grad_two_streams = false, rev_host_lists = false, no_remote_cache = false,
-         no_p2p = false, grad_rows_chain = false, grad_coeff_chain = false;
+         no_p2p = false, grad_rows_chain = false, grad_coeff_chain = false, tree_wide_keys = false;
     int persist_wgs = 0;                 // PHYLO_PERSIST_WGS: resident workgroups of the one-launch sweep (0 = default)
     unsigned long long p2p_wait_ticks = PK_P2P_WAIT_TICKS;   // PHYLO_P2P_WAIT_S: bound of a flag wait of the device-side exchange
     size_t p2p_copy_words = 65536;       // PHYLO_P2P_COPY_WORDS: exchanges beyond this many doubles copy with many workgroups (tests lower it)
@@ -83,6 +83,7 @@ struct env_switches {
         grad_two_streams = getenv("PHYLO_GRAD_TWO_STREAMS") != nullptr;
         rev_host_lists = getenv("PHYLO_REV_HOST_LISTS") != nullptr;
         no_remote_cache = getenv("PHYLO_NO_REMOTE_CACHE") != nullptr;
+        { const char* e = getenv("PHYLO_TREE_WIDE_KEYS"); tree_wide_keys = e && atoi(e) != 0; }
         { const char* e = getenv("PHYLO_REMOTE_CACHE_CAP"); remote_cache_cap = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_SITE_PATTERNS"); site_patterns = !e ? PK_PAT_AUTO : !strcmp(e, "force") ? PK_PAT_FORCE : atoi(e) == 0 ? PK_PAT_OFF : PK_PAT_AUTO; }
         { const char* e = getenv("PHYLO_SCAN_MULTI_MIN"); scan_multi_min = e ? atoi(e) : 4096; }
@@ -256,6 +257,7 @@ struct phylo_ctx {
     // the last phylo_tree_branches of that summary (scratch slot 13); a sweep begun since the summary makes both stale for it
     pb_bufs tb;
     bool tb_done = false;
+    int tb_wide = -1, tb_cbits = 0, tb_tbits = 0;   // the plan the last finished branch pass took (-1: none yet; phylo_debug_tree_branches_of)
     unsigned long long sweep_serial = 0, ts_serial = 0;
     hipEvent_t ev_tb0 = nullptr, ev_tb1 = nullptr;
     hipEvent_t ev_tl0 = nullptr, ev_tl1 = nullptr;   // phylo_trees_loglik's own pair (the sweep's and the summaries' stay theirs)
@@ -621,9 +623,27 @@ void launch_stamped(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hip
     else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
 }
 
-// resampling scan of G groups of Kg log-weights: the LDS form when a group fits (phylo_persist.h), else pk_resample_scan
+// the constants of the kernel headers and the thresholds that the plans read (phylo_sweep_plan.h)
+static sweep_limits sweep_limits_of() {
+    sweep_limits L{};
+    L.max_groups = PK_MAX_GROUPS; L.twist_max_m = PK_TWIST_MAX_M; L.twist_max_j = PK_TWIST_MAX_J;
+    L.mat_group = PK_MAT_GROUP; L.scan_fold_max_kg = PP_SCAN_KERNEL_MAX_KG; L.kept_bits_taxa = PG_KEPT_BITS_TAXA;
+    L.scan_lds512_max_kg = 4096;
+    L.one_tile_max_s = 4096;
+    L.small_max_kg = 4096; L.small_max_kloc = 8192;
+    L.book_packed8_min = 8192;
+    L.sorted_min_draws = 262144;
+    return L;
+}
+static const sweep_limits k_sweep_limits = sweep_limits_of();
+
+// Resampling scan of G groups of Kg log-weights, in the form sweep_scan_form_of decides (phylo_sweep_plan.h): several workgroups per
+// group above PHYLO_SCAN_MULTI_MIN weights (three launches); else one workgroup per group, with the cdf in LDS by 512 threads up to
+// 4096 weights and by 1024 threads up to PP_SCAN_KERNEL_MAX_KG (phylo_persist.h), and beyond that staged in the cdf buffer itself
+// (pk_resample_scan(_groups), phylo_kernels.h).
 int launch_scan(phylo_ctx* c, const double* logw, int Kg, int G, uint64_t* cdf, double* lse, int lse_stride, int logz_R = 0) {
-    if (Kg > c->env.scan_multi_min && (cdf || lse)) {      // large groups: several workgroups per group, three small launches
+    const sweep_scan_form form = sweep_scan_form_of(Kg, c->env.scan_multi_min, cdf || lse, k_sweep_limits);
+    if (form == SCAN_MULTI) {
         pp_scan_multi_args a{};
         a.logw = logw; a.Kg = Kg; a.B = (Kg + PP_SCAN_TILE - 1) / PP_SCAN_TILE;
         void* ws = nullptr;
@@ -640,16 +660,23 @@ int launch_scan(phylo_ctx* c, const double* logw, int Kg, int G, uint64_t* cdf, 
         else { a.lse_only = 1; hipLaunchKernelGGL(pp_scan_multi_cdf, dim3(1, G), dim3(512), 0, c->stream, a); }
         return launch_check(c, "pp_scan_multi_cdf");
     }
-    if (Kg <= 4096) {
+    if (form == SCAN_LDS_512) {
         hipLaunchKernelGGL(pp_resample_scan<512>, dim3(G), dim3(512), pp_resample_scan_lds(Kg), c->stream, logw, Kg, cdf, lse, lse_stride, logz_R);
         return launch_check(c, "pp_resample_scan");
     }
-    if (Kg <= PP_SCAN_KERNEL_MAX_KG) {      // large groups (the replicated scan of a sharded sweep): 16 waves, 128 KiB of LDS
-        hipLaunchKernelGGL(pp_resample_scan<1024>, dim3(G), dim3(1024), pp_resample_scan_lds(Kg), c->stream, logw, Kg, cdf, lse, lse_stride, logz_R);
+    if (form == SCAN_LDS_1024) {
+        const size_t lds = pp_resample_scan_lds(Kg);
+        static bool raised = false;                        // (beyond the 64 KB every kernel may ask for: say so once, like dev_lists_adopters)
+        if (lds > 65536 && !raised) {
+            HIPCHK(c, hipFuncSetAttribute((const void*)pp_resample_scan<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)pp_resample_scan_lds(PP_SCAN_KERNEL_MAX_KG)));
+            raised = true;
+        }
+        hipLaunchKernelGGL(pp_resample_scan<1024>, dim3(G), dim3(1024), lds, c->stream, logw, Kg, cdf, lse, lse_stride, logz_R);
         return launch_check(c, "pp_resample_scan");
     }
-    if (G > 1) hipLaunchKernelGGL(pk_resample_scan_groups, dim3(G), dim3(PK_COLS), pk_scan_lds_bytes(Kg), c->stream, logw, Kg, cdf, lse, lse_stride);
-    else hipLaunchKernelGGL(pk_resample_scan, dim3(1), dim3(PK_COLS), pk_scan_lds_bytes(Kg), c->stream, logw, Kg, cdf, lse);
+    if (G > 1) hipLaunchKernelGGL(pk_resample_scan_groups, dim3(G), dim3(PK_COLS), 0, c->stream, logw, Kg, cdf, lse, lse_stride);
+    else hipLaunchKernelGGL(pk_resample_scan, dim3(1), dim3(PK_COLS), 0, c->stream, logw, Kg, cdf, lse);
     return launch_check(c, "pk_resample_scan");
 }
 
@@ -1628,18 +1655,6 @@ int phylo_log_zsmc(phylo_ctx* c, const double* logw, int R, int K, double* out) 
 // The form is decided once per sweep (phylo_sweep_plan.h): sweep_begin_impl computes the plan from the facts below and stores it
 // in the run; sweep_step_a, the stages of a rank event and phylo_sweep_finish read it and nothing else (no environment switch, no
 // flag bit).  The order of the HIP calls on the stream is what the measurements in that header's comments paid for.
-static sweep_limits sweep_limits_of() {
-    sweep_limits L{};
-    L.max_groups = PK_MAX_GROUPS; L.twist_max_m = PK_TWIST_MAX_M; L.twist_max_j = PK_TWIST_MAX_J;
-    L.mat_group = PK_MAT_GROUP; L.scan_fold_max_kg = PP_SCAN_KERNEL_MAX_KG; L.kept_bits_taxa = PG_KEPT_BITS_TAXA;
-    L.one_tile_max_s = 4096;
-    L.small_max_kg = 4096; L.small_max_kloc = 8192;
-    L.book_packed8_min = 8192;
-    L.sorted_min_draws = 262144;
-    return L;
-}
-static const sweep_limits k_sweep_limits = sweep_limits_of();
-
 // the flag bits of phylo_sweep_begin as facts (the driver and phylo_debug_sweep_plan decode them here)
 static void sweep_facts_flags(sweep_facts& f, uint32_t flags) {
     f.twisting = (flags & PHYLO_TWISTING) != 0; f.keep_graph = (flags & PHYLO_KEEP_GRAPH) != 0;
@@ -3407,16 +3422,16 @@ int phylo_debug_site_patterns_of(phylo_ctx* c, int32_t* U, int32_t* taken) {
     return PHYLO_OK;
 }
 
-int phylo_debug_tree_plan(int N, int K, int G, int world, int64_t n_clades, int64_t n_topologies, int kept_whole, int64_t summary_temp,
-                          int64_t branches_temp, int64_t* scalars, int64_t* summary_slab, int64_t* branches_slab, int32_t* sort_bits,
-                          int32_t* launches) {
+int phylo_debug_tree_plan(int N, int K, int G, int world, int64_t n_clades, int64_t n_topologies, int kept_whole, int force_wide,
+                          int64_t summary_temp, int64_t branches_temp, int64_t* scalars, int64_t* summary_slab, int64_t* branches_slab,
+                          int32_t* sort_bits, int32_t* launches) {
     if (K < 1 || G < 1 || K % G != 0 || N > PK_MAX_TAXA || world < 1 || summary_temp < 0 || branches_temp < 0 || !scalars || !summary_slab ||
         !branches_slab || !sort_bits || !launches)
         return fail(nullptr, PHYLO_EINVAL, "phylo_debug_tree_plan: bad arguments");
     char why[160];
     const pt_facts f{N, K, G, world};
     if (pt_refuses(f, why, sizeof why)) return fail(nullptr, PHYLO_EINVAL, "%s", why);
-    const pb_facts fb{N, K, G, world, n_clades, n_topologies, kept_whole != 0};
+    const pb_facts fb{N, K, G, world, n_clades, n_topologies, kept_whole != 0, force_wide != 0};
     if (pb_refuses(fb, why, sizeof why)) return fail(nullptr, PHYLO_ESTATE, "%s", why);
     pt_plan p = pt_plan_form(f);
     pt_plan_slab(p, (size_t)summary_temp);
@@ -3433,6 +3448,21 @@ int phylo_debug_tree_plan(int N, int K, int G, int world, int64_t n_clades, int6
     branches_slab[2 * pb_slab::NBUF] = (int64_t)q.slab.total;
     launches[0] = pt_plan_launches(p);
     launches[1] = pb_plan_launches(q);
+    return PHYLO_OK;
+}
+
+int phylo_debug_scan_form(phylo_ctx* c, int Kg, int multi_min, int wanted) {
+    if (Kg < 1) {
+        (void)fail(c, PHYLO_EINVAL, "phylo_debug_scan_form: bad arguments");
+        return -1;
+    }
+    return (int)sweep_scan_form_of(Kg, c ? c->env.scan_multi_min : multi_min, wanted != 0, k_sweep_limits);
+}
+
+int phylo_debug_tree_branches_of(phylo_ctx* c, int32_t* wide, int32_t* cbits, int32_t* tbits) {
+    if (!c || !wide || !cbits || !tbits) return fail(c, PHYLO_EINVAL, "phylo_debug_tree_branches_of: NULL argument");
+    if (c->tb_wide < 0) return fail(c, PHYLO_ESTATE, "phylo_debug_tree_branches_of: no phylo_tree_branches has run");
+    *wide = c->tb_wide; *cbits = c->tb_cbits; *tbits = c->tb_tbits;
     return PHYLO_OK;
 }
 
@@ -3763,7 +3793,7 @@ static int tb_check(tb_run& p) {
     if (c->run.active) return fail(c, PHYLO_ESTATE, "phylo_tree_branches: a sweep is being issued (phylo_sweep_finish first)");
     if (!c->swept || !c->ts_done || c->ts_serial != c->sweep_serial)
         return fail(c, PHYLO_ESTATE, "phylo_tree_branches: no phylo_tree_summary of the last sweep (a new sweep needs a new summary)");
-    const pb_facts f{c->N, c->K, c->ts_G, c->world, c->ts_nc, c->ts_nt, c->last_graph && c->d_gbl && c->d_gbr};
+    const pb_facts f{c->N, c->K, c->ts_G, c->world, c->ts_nc, c->ts_nt, c->last_graph && c->d_gbl && c->d_gbr, c->env.tree_wide_keys};
     char why[160];
     if (pb_refuses(f, why, sizeof why)) return fail(c, PHYLO_ESTATE, "%s", why);
     p.plan = pb_plan_form(f);
@@ -3864,6 +3894,7 @@ static int tb_finish(tb_run& p, phylo_stats* perf) {
     if (herr & PT_ERR_TREE) return fail(c, PHYLO_EHIP, "phylo_tree_branches: the sweep's children records do not form one tree per particle");
     CHK(pt_perf(c, c->ev_tb0, c->ev_tb1, p.launches, perf));
     c->tb_done = true;
+    c->tb_wide = p.plan.wide ? 1 : 0; c->tb_cbits = (int)p.plan.cbits; c->tb_tbits = (int)p.plan.tbits;
     return PHYLO_OK;
 }
 

@@ -467,10 +467,10 @@ __device__ __forceinline__ void pk_scan_tile(const double* logw, int K, int base
         if (base + (int)threadIdx.x + PK_COLS * j >= K) v[j] = pm_nan();
 }
 
-// `stage`: K-element scratch for the integer weights between the two passes: LDS when it fits, else cdf[].
+// The integer weights are staged between the two passes in cdf[] itself (the groups this form takes do not fit LDS).
 __device__ __forceinline__ void pk_scan_block(const double* logw, int K, uint64_t* __restrict__ cdf,
-                                              double* __restrict__ lse_out, pk_scan_lds* sh,
-                                              unsigned long long* stage) {
+                                              double* __restrict__ lse_out, pk_scan_lds* sh) {
+    unsigned long long* const stage = reinterpret_cast<unsigned long long*>(cdf);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const bool one_tile = K <= 8 * PK_COLS;
     double v[8];
@@ -563,28 +563,18 @@ __device__ __forceinline__ void pk_scan_block(const double* logw, int K, uint64_
     }
 }
 
-#define PK_SCAN_LDS_MAX_K 8192
 __global__ __launch_bounds__(PK_COLS) void pk_resample_scan(const double* logw, int K, uint64_t* __restrict__ cdf,
                                                              double* __restrict__ lse_out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];     // [pk_scan_lds][K x u64 when K fits]
-    pk_scan_lds* sh = reinterpret_cast<pk_scan_lds*>(smem);
-    unsigned long long* stage = (K <= PK_SCAN_LDS_MAX_K) ? reinterpret_cast<unsigned long long*>(smem + sizeof(pk_scan_lds))
-                                                         : reinterpret_cast<unsigned long long*>(cdf);
-    pk_scan_block(logw, K, cdf, lse_out, sh, stage);
+    __shared__ pk_scan_lds sh;
+    pk_scan_block(logw, K, cdf, lse_out, &sh);
 }
 // G independent sweeps batched in one context: one workgroup per group scans its own K-segment
 __global__ __launch_bounds__(PK_COLS) void pk_resample_scan_groups(const double* logw, int K, uint64_t* __restrict__ cdf,
                                                                     double* __restrict__ lse_out, int lse_stride) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    pk_scan_lds* sh = reinterpret_cast<pk_scan_lds*>(smem);
+    __shared__ pk_scan_lds sh;
     const int g = blockIdx.x;
     uint64_t* cg = cdf ? cdf + (size_t)g * K : nullptr;
-    unsigned long long* stage = (K <= PK_SCAN_LDS_MAX_K) ? reinterpret_cast<unsigned long long*>(smem + sizeof(pk_scan_lds))
-                                                         : reinterpret_cast<unsigned long long*>(cg);
-    pk_scan_block(logw + (size_t)g * K, K, cg, lse_out + (size_t)g * lse_stride, sh, stage);
-}
-__host__ inline size_t pk_scan_lds_bytes(int K) {
-    return sizeof(pk_scan_lds) + (K <= PK_SCAN_LDS_MAX_K ? (size_t)K * 8 : 0);
+    pk_scan_block(logw + (size_t)g * K, K, cg, lse_out + (size_t)g * lse_stride, &sh);
 }
 
 __device__ __forceinline__ int pk_cdf_search(const uint64_t* __restrict__ cdf, int K, uint64_t thr) {

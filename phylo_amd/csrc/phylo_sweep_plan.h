@@ -17,6 +17,7 @@ struct sweep_limits {
     int twist_max_m, twist_max_j;      // PK_TWIST_MAX_M, PK_TWIST_MAX_J
     int mat_group;                     // PK_MAT_GROUP: particles per workgroup of the grouped adopted-node launches
     int scan_fold_max_kg;              // PP_SCAN_KERNEL_MAX_KG: the scan kernels that can also sum the log-normalisers
+    int scan_lds512_max_kg;            // 4096: groups that pp_resample_scan<512> takes (32 KiB of cdf in LDS)
     int kept_bits_taxa;                // PG_KEPT_BITS_TAXA
     int one_tile_max_s;                // 4096: sites of a node that one workgroup writes / of the rows form of the reverse pass
     int small_max_kg, small_max_kloc;  // 4096, 8192: launches of at most this many particles count as small (latency chains)
@@ -178,6 +179,22 @@ inline sweep_plan sweep_plan_form(const sweep_facts& f, const sweep_limits& L) {
     // pack, unpack (+ the two barrier kernels of the device-side exchange)
     p.gather_launches = (p.graph && f.world > 1) ? (f.device_exchange ? 4 : 2) : 0;
     return p;
+}
+
+// The form of a resampling scan of groups of Kg log-weights (launch_scan; phylo_resample, phylo_log_zsmc and every rank event of a
+// sweep): decided here, from the group size, PHYLO_SCAN_MULTI_MIN as the context read it (default 4096) and whether the caller
+// wants anything written (a cdf or a log-normaliser).  All four compute the same bits (tests/test_gpu_scan_forms.py).
+enum sweep_scan_form {
+    SCAN_MULTI = 0,                    // pp_scan_multi_max / _exp / _cdf: several workgroups per group, a tile of 2048 weights each
+    SCAN_LDS_512 = 1,                  // pp_resample_scan<512>: one workgroup per group, the cdf in LDS
+    SCAN_LDS_1024 = 2,                 // pp_resample_scan<1024>: 16 waves, up to 128 KiB of LDS
+    SCAN_IN_PLACE = 3                  // pk_resample_scan(_groups): one workgroup per group, staged in the cdf buffer itself
+};
+inline sweep_scan_form sweep_scan_form_of(int Kg, int multi_min, bool wanted, const sweep_limits& L) {
+    if (Kg > multi_min && wanted) return SCAN_MULTI;
+    if (Kg <= L.scan_lds512_max_kg) return SCAN_LDS_512;
+    if (Kg <= L.scan_fold_max_kg) return SCAN_LDS_1024;
+    return SCAN_IN_PLACE;
 }
 
 // What the driver counts into stats.n_launches: r = -1 the begin, 0 .. R-1 rank event r (sweep_step_a's half included), R the

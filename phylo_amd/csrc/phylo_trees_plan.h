@@ -134,6 +134,7 @@ struct pb_facts {
     int N, K, G, world;                // (G: the summary's)
     long long nc, nt;                  // the summary's rows: clades and topologies, over all groups
     bool kept_whole;                   // the sweep kept its graph and left whole-K branch lengths (graph_gather)
+    bool force_wide;                   // PHYLO_TREE_WIDE_KEYS (tests): the 64-bit keys at any size
 };
 
 struct pb_plan {
@@ -161,7 +162,7 @@ inline pb_plan pb_plan_form(const pb_facts& f) {
     p.E = (long long)p.L * f.K; p.nc = f.nc; p.nt = f.nt; p.nb = 2LL * f.N - 2;
     p.cbits = pt_bit_length((size_t)f.nc - 1);
     p.tbits = pt_bit_length((size_t)f.nt - 1);
-    p.wide = p.cbits + p.tbits > 32;                       // 32 bits hold the keys on all but huge tables
+    p.wide = f.force_wide || p.cbits + p.tbits > 32;       // 32 bits hold the keys on all but huge tables
     p.gather = f.world > 1 && !f.kept_whole;
     return p;
 }

@@ -1,5 +1,6 @@
 """One rank of a sharded sweep followed by its tree posterior summary and branch pass (helper process of
-tests/test_gpu_tree_branches.py).
+tests/test_gpu_tree_branches.py and tests/test_gpu_tree_branches_wide.py; the saved 'branch_plan' is (wide, cbits, tbits) of the
+pass, phylo_debug_tree_branches_of).
 usage: python tests/_tree_branches_worker.py RANK WORLD K DATASET SEED KEEP_GRAPH OUT.npz"""
 import os
 import sys
@@ -27,6 +28,8 @@ def main():
     ctx.sweep(seed, flags=_ffi.FLAGS_DEFAULT | (_ffi.KEEP_GRAPH if keep else 0))
     tab = ctx.tree_summary()
     tab.update(ctx.tree_branches(tab))
+    plan = ctx.debug_tree_branches()
+    tab['branch_plan'] = np.array([int(plan['wide']), plan['cbits'], plan['tbits']], dtype=np.int32)
     np.savez(out, **{k: v for k, v in tab.items() if isinstance(v, np.ndarray)})
     ctx.close()
 

@@ -288,3 +288,44 @@ def test_bad_arguments_are_refused():
         args.update(kw)
         with pytest.raises(_ffi.PhyloError):
             _ffi.debug_sweep_plan(**args)
+
+
+def _scan_form(Kg, multi_min, wanted):
+    """launch_scan as it was spelled before sweep_scan_form_of: the scan of several workgroups per group above the switch when
+    anything is wanted; else one workgroup per group: the cdf in LDS by 512 threads up to 4096 weights, by 1024 threads up to
+    PP_SCAN_KERNEL_MAX_KG, beyond that staged in the cdf buffer itself"""
+    if Kg > multi_min and wanted:
+        return "multi"
+    if Kg <= 4096:
+        return "lds512"
+    return "lds1024" if Kg <= SCAN_KERNEL_MAX_KG else "in_place"
+
+
+def test_scan_form_and_its_three_thresholds():
+    sizes = (1, 2, 63, 64, 65, 100, 2048, 2049, 4095, 4096, 4097, 5000, 8192, 16383, 16384, 16385, 20003, 100001, 1 << 30, (1 << 31) - 1)
+    for multi_min, Kg, wanted in itertools.product((0, 64, 4096, 5000, 16384, 20000, 1 << 30), sizes, (True, False)):
+        assert _ffi.debug_scan_form(Kg, multi_min, wanted) == _scan_form(Kg, multi_min, wanted), (Kg, multi_min, wanted)
+    # the default switch: nothing above 4096 weights is scanned by one workgroup
+    assert [_ffi.debug_scan_form(Kg) for Kg in (4096, 4097, 16384, 16385)] == ["lds512", "multi", "multi", "multi"]
+    # the switch out of reach: 4096 and PP_SCAN_KERNEL_MAX_KG are the last sizes of the two LDS forms
+    assert [_ffi.debug_scan_form(Kg, 1 << 30) for Kg in (4096, 4097, 16384, 16385)] == ["lds512", "lds1024", "lds1024", "in_place"]
+    # the switch itself: the first size beyond it
+    assert [_ffi.debug_scan_form(Kg, 64) for Kg in (64, 65)] == ["lds512", "multi"]
+    assert [_ffi.debug_scan_form(Kg, 5000) for Kg in (5000, 5001)] == ["lds1024", "multi"]
+    assert [_ffi.debug_scan_form(Kg, 20000) for Kg in (20000, 20001)] == ["in_place", "multi"]
+    # nothing wanted (no cdf, no log-normaliser): never the three launches
+    assert _ffi.debug_scan_form(9000, wanted=False) == "lds1024" and _ffi.debug_scan_form(20000, wanted=False) == "in_place"
+    assert _ffi.SCAN_FORMS == ("multi", "lds512", "lds1024", "in_place")
+    with pytest.raises(_ffi.PhyloError) as e:
+        _ffi.debug_scan_form(0)
+    assert e.value.code == EINVAL
+
+
+def test_fold_logz_is_a_size_rule_not_a_scan_form():
+    """the last scan sums the log-normalisers in both LDS kernels and in the scan of several workgroups; pk_resample_scan(_groups)
+    cannot, and is only reached beyond PP_SCAN_KERNEL_MAX_KG whatever the switch: fold_logz never names a form that cannot fold"""
+    for multi_min, Kg in itertools.product((64, 4096, 1 << 30), (4096, 4097, 16384, 16385, 33282)):
+        folds = _plan(5, Kg, 8)["fold_logz"]
+        assert folds == (Kg <= SCAN_KERNEL_MAX_KG)
+        if _ffi.debug_scan_form(Kg, multi_min) == "in_place":
+            assert not folds

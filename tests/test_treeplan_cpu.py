@@ -1,8 +1,9 @@
 """The form of the tree posterior's two passes (phylo_amd/csrc/phylo_trees_plan.h: pt_plan_form / pb_plan_form, the layouts of
 scratch slots 12 and 13, pt_plan_launches / pb_plan_launches) against a restatement in Python of the rules as tree_summary_impl and
 tree_branches_impl spelled them before there was a plan: the take() sequence line by line, each sort's bit count, wide, gather,
-the refusals and the launch counts.  The wide form needs n_clades * n_topologies near 2^32, which no GPU test reaches: its
-selection and its buffers are pinned here.  No GPU: phylo_debug_tree_plan calls the functions the driver calls."""
+the refusals and the launch counts.  The wide form needs n_clades * n_topologies near 2^32 or PHYLO_TREE_WIDE_KEYS (force_wide):
+its selection and its buffers are pinned here, for both (tests/test_gpu_tree_branches_wide.py runs it).  No GPU:
+phylo_debug_tree_plan calls the functions the driver calls."""
 import itertools
 import json
 import os
@@ -80,11 +81,11 @@ def summary_rules(N, K, G, world, temp):
             "summary_launches": launches}
 
 
-def branches_rules(N, K, G, world, nc, nt, kept_whole, temp):
+def branches_rules(N, K, G, world, nc, nt, kept_whole, temp, force_wide=False):
     R, L = N - 1, N - 2
     E, nb = L * K, 2 * N - 2
     cbits, tbits = max(1, bit_length(nc - 1)), max(1, bit_length(nt - 1))
-    wide = cbits + tbits > 32
+    wide = force_wide or cbits + tbits > 32
     gather = world > 1 and not kept_whole
     Ks, Es = K, E
     takes = [("ebr", 8, (R - 1) * Ks), ("lbr", 8, N * Ks)]
@@ -136,6 +137,10 @@ def test_plan_equals_the_rules(N):
             assert got["gather"] == (world > 1 and not kept_whole)
             wide_seen += got["wide"]
             narrow32_seen += got["cbits"] + got["tbits"] == 32
+            forced = _ffi.debug_tree_plan(N, K, force_wide=True, **args)
+            want.update(branches_rules(N, K, G, world, nc, nt, kept_whole, TEMP_B, force_wide=True))
+            assert forced == want and forced["wide"], (N, K, G, world, nc, nt, kept_whole)
+            check_slab(forced["branches_slab"], _ffi.TREE_BRANCHES_BUFS)
     if N == 512:                                           # (the grid does reach both sides of the threshold)
         assert wide_seen and narrow32_seen
 
@@ -150,6 +155,37 @@ def test_wide_keys_start_at_33_bits():
     assert narrow["branches_slab"]["sizes"]["wA"] == narrow["branches_slab"]["sizes"]["wB"] == 0
     assert wide["branches_slab"]["sizes"]["wA"] == wide["branches_slab"]["sizes"]["wB"] == 8 * E
     assert wide["branches_slab"]["total"] - narrow["branches_slab"]["total"] == 2 * 8 * E + 256   # (and one more block of o_cs)
+
+
+def test_forced_wide_changes_the_two_key_buffers_and_nothing_else():
+    """PHYLO_TREE_WIDE_KEYS as a fact: wide is set, wA / wB get E elements of 8 bytes each, the temporary storage counts the 64-bit
+    sort (the caller's fact: a larger branches_temp lands in the slab), and every other word of the plan is the narrow plan's"""
+    for N, K, G, world, nc, nt, kept in ((9, 16, 1, 1, 20, 3, False), (9, 100, 1, 1, 61, 7, False), (3, 96, 1, 1, 1, 1, False),
+                                         (12, 256, 4, 1, 300, 40, False), (70, 64, 1, 1, 900, 64, False), (9, 64, 1, 2, 30, 5, False),
+                                         (9, 64, 1, 2, 30, 5, True)):
+        args = dict(G=G, world=world, n_clades=nc, n_topologies=nt, kept_whole=kept, summary_temp=TEMP_S)
+        narrow = _ffi.debug_tree_plan(N, K, branches_temp=TEMP_B, **args)
+        forced = _ffi.debug_tree_plan(N, K, branches_temp=TEMP_B + 5000, force_wide=True, **args)   # (the 64-bit sort asks for more)
+        E = (N - 2) * K
+        assert not narrow["wide"] and forced["wide"] and narrow["cbits"] + narrow["tbits"] <= 32
+        ns, fs = narrow["branches_slab"], forced["branches_slab"]
+        assert ns["sizes"]["wA"] == ns["sizes"]["wB"] == 0 and fs["sizes"]["wA"] == fs["sizes"]["wB"] == 8 * E
+        assert ns["sizes"]["temp"] == TEMP_B and fs["sizes"]["temp"] == TEMP_B + 5000
+        for name in _ffi.TREE_BRANCHES_BUFS:
+            if name not in ("wA", "wB", "temp"):
+                assert fs["sizes"][name] == ns["sizes"][name], name
+        one = (8 * E + 255) // 256 * 256
+        shift = 2 * one
+        for i, name in enumerate(_ffi.TREE_BRANCHES_BUFS):  # wB moves by wA's bytes, the buffers behind it by those of both
+            moved = min(2, max(0, i - _ffi.TREE_BRANCHES_BUFS.index("wA"))) * one
+            assert fs["offsets"][name] - ns["offsets"][name] == moved, name
+        assert fs["total"] - ns["total"] == shift + ((TEMP_B + 5000 + 255) // 256 - (TEMP_B + 255) // 256) * 256
+        for key in narrow:                                  # key layout, radix bits, launch counts, the summary: untouched
+            if key not in ("wide", "branches_slab"):
+                assert forced[key] == narrow[key], key
+    # a plan that is wide by size is the same plan with and without the fact
+    args = dict(n_clades=(1 << 16) + 1, n_topologies=40960, branches_temp=TEMP_B)
+    assert _ffi.debug_tree_plan(512, 40960, force_wide=True, **args) == _ffi.debug_tree_plan(512, 40960, **args)
 
 
 def test_refusals():
