@@ -377,6 +377,18 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
  * the value the context read when it was created (multi_min is ignored).  wanted: the caller asks for a cdf or a log-normaliser
  * (phylo_resample, phylo_log_zsmc and every scan of a sweep do).  tests/test_sweepplan_cpu.py restates the rule. */
 int phylo_debug_scan_form(phylo_ctx* ctx, int Kg, int multi_min, int wanted);
+/* Test hooks of the one-launch sweep's grid (persist_plan_of, phylo_sweep_plan.h; DESIGN.md sections 4c and 6b).
+ * phylo_debug_persist_plan, no GPU needed: the rule for a shape (K: all G groups' particles, K divisible by G), the flags of a sweep,
+ * the switches (bit 0 PHYLO_EAGER_NODES, 1 PHYLO_ONE_LAUNCH: the environment), a communicator (transport != 0) and the facts the
+ * driver asks the device for: n_cus compute units, blocks_per_cu workgroups the planner may place on one (0: the kernel is not
+ * admitted; 1; 2), and the two switches as a context reads them: persist_wgs (PHYLO_PERSIST_WGS, <= 0: unset) and persist_nt
+ * (PHYLO_PERSIST_NT: 512, everything else is 256).  out[5]: taken (0: the launch path runs, the rest is 0), Wg workgroups per group,
+ * m = K / G / Wg particles per workgroup, threads per workgroup, dynamic LDS bytes per workgroup.
+ * phylo_debug_persist_of: threads, Wg, m and LDS bytes of the context's last sweep if it was a one-launch sweep, else PHYLO_ESTATE.
+ * tests/test_one_launch_plan_cpu.py restates the rule; tests/test_gpu_one_launch_forms.py asserts the grid before it compares. */
+int phylo_debug_persist_plan(int N, int K, int S, int G, uint32_t flags, uint32_t switches, int world, int transport, int n_cus,
+                             int blocks_per_cu, int persist_wgs, int persist_nt, int64_t* out);
+int phylo_debug_persist_of(phylo_ctx* ctx, int32_t* nt, int32_t* Wg, int32_t* m, int64_t* lds);
 /* Test hook, no GPU needed: the packed image of byte codes [N][S] as phylo_set_leaves builds it beside them (pk_pack_leaf_codes,
  * phylo_packed_codes.h): packed[((leaf nC + Jc) 64 + c) 16 + j] = code of site 64 (16 Jc + j) + c with
  * nC = ceil(ceil(S / 64) / 16), sites >= S hold the pad code 5.  *need = N nC 1024, the image's bytes; with packed NULL only

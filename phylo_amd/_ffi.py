@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_persist_plan", "phylo_debug_persist_of", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -276,6 +276,26 @@ def debug_scan_form(Kg, multi_min=4096, wanted=True):
     if rc < 0:
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     return SCAN_FORMS[rc]
+
+
+PERSIST_PLAN_SWITCHES = ("eager_nodes", "one_launch")      # PHYLO_EAGER_NODES, PHYLO_ONE_LAUNCH in the environment
+
+
+def debug_persist_plan(N, K, S, G=1, flags=FLAGS_DEFAULT | ONE_LAUNCH, switches=(), world=1, transport=False, n_cus=256, blocks_per_cu=1,
+                       persist_wgs=0, persist_nt=256):
+    """The grid the one-launch sweep takes (persist_plan_of; no GPU and no context needed) for a shape (K: all G groups' particles),
+    the flags of a sweep, the switches (names of PERSIST_PLAN_SWITCHES) and the facts of a device and a context: its compute units,
+    the workgroups the planner may place on one (0, 1 or 2), PHYLO_PERSIST_WGS (0: unset) and PHYLO_PERSIST_NT.  None when the
+    launch path runs instead, else {'nt', 'Wg', 'm', 'lds'}."""
+    lib = load()
+    sw = sum(1 << PERSIST_PLAN_SWITCHES.index(name) for name in switches)
+    out = (C.c_int64 * 5)()
+    rc = lib.phylo_debug_persist_plan(C.c_int(N), C.c_int(K), C.c_int(S), C.c_int(G), C.c_uint32(flags), C.c_uint32(sw), C.c_int(world),
+                                      C.c_int(int(transport)), C.c_int(n_cus), C.c_int(blocks_per_cu), C.c_int(persist_wgs),
+                                      C.c_int(persist_nt), out)
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return {'nt': out[3], 'Wg': out[1], 'm': out[2], 'lds': out[4]} if out[0] else None
 
 
 def debug_reverse_plan_batch(N, K, G, S, switches=(), n_slow=0, TS=None, coeff_wgs=0, passes_in_flight=1):
@@ -907,6 +927,13 @@ class Context:
         if rc < 0:
             raise PhyloError(rc, self._lib.phylo_last_error(self._h).decode())
         return SCAN_FORMS[rc]
+
+    def debug_persist(self):
+        """The grid the last sweep of this context took as ONE launch: {'nt', 'Wg', 'm', 'lds'} (threads per workgroup, workgroups
+        per group, particles per workgroup, dynamic LDS bytes); PhyloError (PHYLO_ESTATE) when it ran on the launch path."""
+        nt, Wg, m, lds = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._check(self._lib.phylo_debug_persist_of(self._h, C.byref(nt), C.byref(Wg), C.byref(m), C.byref(lds)))
+        return {'nt': nt.value, 'Wg': Wg.value, 'm': m.value, 'lds': lds.value}
 
     def comm_exchange_kind(self):
         """'none' | 'rccl' | 'hostshm' | 'p2p': how the K-vectors of a rank event reach the other ranks"""

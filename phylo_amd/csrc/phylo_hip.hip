@@ -95,7 +95,7 @@ struct env_switches {
         const char* w = getenv("PHYLO_PERSIST_WGS");
         persist_wgs = w ? atoi(w) : 0;
         const char* t = getenv("PHYLO_PERSIST_NT");
-        persist_nt = (t && atoi(t) == 512) ? 512 : 256;
+        persist_nt = persist_nt_of(t ? atoi(t) : 0);
     }
 };
 
@@ -111,6 +111,8 @@ struct phylo_ctx {
     bool pctr_dirty = false;                 // a bounded wait timed out: the counters hold partial arrivals
     int persist_blocks_per_cu = -1;          // occupancy of pp_sweep (-1: not asked yet)
     bool last_persistent = false;
+    int last_pp_nt = 0, last_pp_Wg = 0, last_pp_m = 0;   // the grid the last one-launch sweep took (phylo_debug_persist_of)
+    size_t last_pp_lds = 0;
     unsigned long long* d_stamps = nullptr;  // phase stamps of the one-launch sweep (PHYLO_PERSIST_STAMPS=1)
     int K = 0, N = 0, S = 0, A = 4;      // K = global particle count
     int Kloc = 0, k0 = 0;                // this rank's shard
@@ -1840,6 +1842,7 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     c->run.plan = p;
     c->run.launches = sweep_plan_launches(p, -1);
     c->run.active = true;
+    c->last_persistent = false;
     return PHYLO_OK;
 }
 
@@ -1863,18 +1866,26 @@ static int persist_chain(phylo_ctx* c, bool after_launch) {
     return PHYLO_OK;
 }
 
+static size_t persist_lds_bytes(int N, int m, int Kg) { return pp_layout(N, m, Kg).total; }
+static const persist_limits k_persist_limits = {32, PP_MAX_KG, PP_MAX_M, 8192, (size_t)150 * 1024, persist_lds_bytes};
+
+static persist_facts persist_facts_flags(int N, int K, int S, int G, int world, bool transport, uint32_t flags, bool env_one_launch,
+                                         bool env_eager_nodes) {
+    persist_facts f{};
+    f.N = N; f.K = K; f.S = S; f.G = G; f.world = world; f.transport = transport;
+    f.one_launch = env_one_launch || (flags & PHYLO_ONE_LAUNCH);
+    f.twisting = (flags & PHYLO_TWISTING) != 0; f.keep_graph = (flags & PHYLO_KEEP_GRAPH) != 0;
+    f.time_kernels = (flags & PHYLO_TIME_KERNELS) != 0; f.eager_nodes = (flags & PHYLO_EAGER_NODES) != 0;
+    f.env_eager_nodes = env_eager_nodes;
+    return f;
+}
+
 // Plan: G groups x Wg resident workgroups, m = Kg / Wg particles each.  Returns false when this context / sweep is
 // not eligible (the launch-per-rank-event path runs instead).
+// The rule is persist_plan_of (phylo_sweep_plan.h); here only the facts of this context and device.
 static bool persist_plan(phylo_ctx* c, uint32_t flags, int G, int* Wg_out, int* m_out) {
-    if (!(c->env.one_launch || (flags & PHYLO_ONE_LAUNCH))) return false;             // opt-in
-    if (c->world != 1 || c->comm.transport != 0) return false;                       // sharded: collectives between launches
-    if (flags & (PHYLO_TWISTING | PHYLO_KEEP_GRAPH | PHYLO_TIME_KERNELS)) return false;   // launch path only
-    if (sweep_eager_nodes((flags & PHYLO_EAGER_NODES) != 0, c->env.eager_nodes)) return false;   // ... and its A/B switch
-    if (c->N > 32 || c->N < 2) return false;                                        // one wave per particle: a lane per root slot, history rows in lanes
-    const int Kg = c->K / G;
-    if (Kg > PP_MAX_KG) return false;                                               // the group's cdf lives in LDS
-    // large nodes: the launch path spreads one node over several workgroups and its launches are long enough
-    if ((double)c->S * 32.0 > 256.0 * 1024.0) return false;
+    persist_facts f = persist_facts_flags(c->N, c->K, c->S, G, c->world, c->comm.transport != 0, flags, c->env.one_launch, c->env.eager_nodes);
+    if (persist_refuses_shape(f, k_persist_limits)) return false;
     if (c->persist_blocks_per_cu < 0) {
         // residency of ONE workgroup per CU is all the kernel needs; ask the runtime whether it is admitted at all
         int nb = 0;
@@ -1884,18 +1895,12 @@ static bool persist_plan(phylo_ctx* c, uint32_t flags, int G, int* Wg_out, int* 
             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pp_sweep<256>, 256, lds);
         c->persist_blocks_per_cu = (e == hipSuccess && nb >= 1) ? (nb >= 3 ? 2 : 1) : 0;   // one workgroup per CU by default; two only with a block of margin
     }
-    if (c->persist_blocks_per_cu < 1 || c->n_cus < 1) return false;
-    int Wt = c->env.persist_wgs > 0 ? c->env.persist_wgs : c->n_cus;                // default: one workgroup per CU
-    if (Wt > c->n_cus * c->persist_blocks_per_cu) Wt = c->n_cus * c->persist_blocks_per_cu;
-    if (Wt < G) return false;
-    int Wg = Wt / G;
-    if (Wg > Kg) Wg = Kg;
-    while (Wg > 1 && Kg % Wg) --Wg;
-    const int m = Kg / Wg;
-    if (m > PP_MAX_M) return false;
-    if (pp_layout(c->N, m, Kg).total > 150 * 1024) return false;
-    *Wg_out = Wg;
-    *m_out = m;
+    f.n_cus = c->n_cus; f.blocks_per_cu = c->persist_blocks_per_cu;
+    f.persist_wgs = c->env.persist_wgs; f.persist_nt = c->env.persist_nt;
+    const persist_grid p = persist_plan_of(f, k_persist_limits);
+    if (!p.taken) return false;
+    *Wg_out = p.Wg;
+    *m_out = p.m;
     return true;
 }
 
@@ -1950,6 +1955,7 @@ static int sweep_persistent(phylo_ctx* c, uint64_t seed, uint32_t flags, const u
     c->pctr_base += (unsigned long long)R * Wg;
     sweep_publish(c, true, false, G, false, 0, 1, (double)K * S * R);      // lazy: only adopted nodes are in the pool
     c->last_persistent = true;
+    c->last_pp_nt = c->env.persist_nt; c->last_pp_Wg = Wg; c->last_pp_m = m; c->last_pp_lds = lds;
     return PHYLO_OK;
 }
 
@@ -3457,6 +3463,24 @@ int phylo_debug_scan_form(phylo_ctx* c, int Kg, int multi_min, int wanted) {
         return -1;
     }
     return (int)sweep_scan_form_of(Kg, c ? c->env.scan_multi_min : multi_min, wanted != 0, k_sweep_limits);
+}
+
+int phylo_debug_persist_plan(int N, int K, int S, int G, uint32_t flags, uint32_t switches, int world, int transport, int n_cus,
+                             int blocks_per_cu, int persist_wgs, int persist_nt, int64_t* out) {
+    if (N < 1 || K < 1 || S < 1 || G < 1 || K % G != 0 || world < 1 || !out)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_persist_plan: bad arguments");
+    persist_facts f = persist_facts_flags(N, K, S, G, world, transport != 0, flags, (switches & 2) != 0, (switches & 1) != 0);
+    f.n_cus = n_cus; f.blocks_per_cu = blocks_per_cu; f.persist_wgs = persist_wgs; f.persist_nt = persist_nt_of(persist_nt);
+    const persist_grid p = persist_plan_of(f, k_persist_limits);
+    out[0] = p.taken ? 1 : 0; out[1] = p.Wg; out[2] = p.m; out[3] = p.nt; out[4] = (int64_t)p.lds;
+    return PHYLO_OK;
+}
+
+int phylo_debug_persist_of(phylo_ctx* c, int32_t* nt, int32_t* Wg, int32_t* m, int64_t* lds) {
+    if (!c || !nt || !Wg || !m || !lds) return fail(c, PHYLO_EINVAL, "phylo_debug_persist_of: NULL argument");
+    if (!c->last_persistent) return fail(c, PHYLO_ESTATE, "phylo_debug_persist_of: the last sweep was not a one-launch sweep");
+    *nt = c->last_pp_nt; *Wg = c->last_pp_Wg; *m = c->last_pp_m; *lds = (int64_t)c->last_pp_lds;
+    return PHYLO_OK;
 }
 
 int phylo_debug_tree_branches_of(phylo_ctx* c, int32_t* wide, int32_t* cbits, int32_t* tbits) {

@@ -214,6 +214,72 @@ inline int sweep_plan_launches(const sweep_plan& p, int r) {
     return n;
 }
 
+// ---- the one-launch sweep (phylo_persist.h: pp_sweep<NT>) --------------------------------------------------
+// Whether a sweep is issued as ONE launch of resident workgroups, and on which grid: G groups x Wg workgroups of nt threads,
+// m = Kg / Wg particles each.  Every grid computes the launch path's bits, so a rule that silently picks another grid (or the launch
+// path) passes every comparison: the rule is stated here once, persist_plan (phylo_hip.hip) feeds it the facts it queried, and
+// phylo_debug_persist_plan the facts a test names (tests/test_one_launch_plan_cpu.py restates it).
+struct persist_limits {
+    int max_taxa;                      // 32: one wave per particle, a lane per root slot, history rows in lanes
+    int max_kg;                        // PP_MAX_KG: the group's cdf lives in LDS
+    int max_m;                         // PP_MAX_M: adoption flags and own ancestors live in LDS
+    int max_s;                         // 8192: larger nodes (256 KiB) are spread over several workgroups by the launch path
+    size_t max_lds;                    // 150 KiB of the CU's 160
+    size_t (*lds_bytes)(int N, int m, int Kg);   // pp_layout(N, m, Kg).total
+};
+
+struct persist_facts {
+    int N, K, S, G, world;
+    bool transport;                    // a communicator is set
+    bool one_launch;                   // PHYLO_ONE_LAUNCH, as a flag or from the environment: the form is opt-in
+    bool twisting, keep_graph, time_kernels, eager_nodes, env_eager_nodes;
+    int n_cus;                         // compute units of the device
+    int blocks_per_cu;                 // workgroups of pp_sweep<nt> the planner may place on a CU: 0 (not admitted), 1 or 2
+    int persist_wgs;                   // PHYLO_PERSIST_WGS: resident workgroups of the whole launch (<= 0: one per CU)
+    int persist_nt;                    // PHYLO_PERSIST_NT as persist_nt_of read it: 256 or 512
+};
+
+struct persist_grid {
+    bool taken;                        // false: the launch path runs (the other fields are 0)
+    int Wg, m, nt;
+    size_t lds;                        // dynamic LDS bytes of a workgroup
+};
+
+// PHYLO_PERSIST_NT: 512 selects pp_sweep<512>, everything else (unset included: 0) the 256-thread form
+inline int persist_nt_of(int requested) { return requested == 512 ? 512 : 256; }
+
+// The refusals that need no fact of the device (persist_plan asks the runtime for the occupancy only behind them).
+inline bool persist_refuses_shape(const persist_facts& f, const persist_limits& L) {
+    if (!f.one_launch) return true;                                                  // opt-in
+    if (f.world != 1 || f.transport) return true;                                    // sharded: collectives between launches
+    if (f.twisting || f.keep_graph || f.time_kernels) return true;                   // launch path only
+    if (sweep_eager_nodes(f.eager_nodes, f.env_eager_nodes)) return true;            // ... and its A/B switch
+    if (f.N > L.max_taxa || f.N < 2) return true;
+    if (f.K / f.G > L.max_kg) return true;
+    if (f.S > L.max_s) return true;
+    return false;
+}
+
+inline persist_grid persist_plan_of(const persist_facts& f, const persist_limits& L) {
+    const persist_grid no{};
+    if (persist_refuses_shape(f, L)) return no;
+    if (f.blocks_per_cu < 1 || f.n_cus < 1) return no;
+    const int Kg = f.K / f.G;
+    int Wt = f.persist_wgs > 0 ? f.persist_wgs : f.n_cus;                            // default: one workgroup per CU
+    if (Wt > f.n_cus * f.blocks_per_cu) Wt = f.n_cus * f.blocks_per_cu;              // residency: never more than the device admits
+    if (Wt < f.G) return no;
+    int Wg = Wt / f.G;
+    if (Wg > Kg) Wg = Kg;
+    while (Wg > 1 && Kg % Wg) --Wg;                                                  // every workgroup owns the same number of particles
+    const int m = Kg / Wg;
+    if (m > L.max_m) return no;
+    // (no admissible shape reaches this refusal: with N <= 32, m <= 1024 and Kg <= 8192 the layout takes at most 94 240 bytes.
+    //  It stays as the guard of the launch's LDS request should a limit above move; tests/test_one_launch_plan_cpu.py pins the maximum.)
+    const size_t lds = L.lds_bytes(f.N, m, Kg);
+    if (lds > L.max_lds) return no;
+    return persist_grid{true, Wg, m, f.persist_nt, lds};
+}
+
 // The plan as phylo_debug_sweep_plan returns it: the booleans in this order from bit 0 (SWEEP_PLAN_BITS of phylo_amd/_ffi.py names
 // them; `batched` is lse_stride != 0), book_width / 8 in bits 28..31.  gather_launches is the finish's count beyond pk_logz_total.
 inline uint32_t sweep_plan_mask(const sweep_plan& p) {
