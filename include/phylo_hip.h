@@ -206,6 +206,24 @@ int phylo_trees_grad(phylo_ctx* ctx, int T, const int32_t* child, const double* 
 int phylo_trees_grad_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate,
                            const double* weight, int per_tree, const double* prior4, double* loglik_T, double* grad, double* curv,
                            double* drate_TxC, double* dweight_TxC, phylo_stats* perf);
+/* The NNI neighbourhood of every tree of a set, at the tree's current branch lengths: for T trees given as
+ * phylo_trees_loglik takes them (same numbering, same checks, same state rules),
+ *   loglik_T[t]        bit for bit phylo_trees_loglik's value for the same tree, prior and site tile;
+ *   delta[t][i][side]  = sum_s log(L'_s / L_s), L'_s the site factor of one nearest-neighbour interchange, shaped [T][N-1][2] as blen:
+ *     row i < N-2 (node v = N + i, parent p, sibling c): v's child on `side` and c change places, every subtree keeping its own
+ *       length -- v = (v's other child, c), p = (v, that child); with p the root the move only shifts the root along its edge;
+ *     row N-2 (the root, children v = child[N-2][0] and c = child[N-2][1], both internal): v's side-1 child and c's child on `side`
+ *       change places -- the two interchanges across the root's edge; NaN in both entries when v or c is a leaf.
+ * The neighbour's log-likelihood at the current lengths is loglik_T[t] + delta.  An impossible neighbour (L'_s = 0 at a site)
+ * gets -inf.  Fixed order of summation, no atomics: a call repeats its own bits, and chunking changes none; against a
+ * restatement delta carries a tolerance, not a bit contract.  A tree whose loglik is not finite, or with a site factor below
+ * 2^-1020, gets NaN in every entry (phylo_trees_grad's rule).  perf (may be NULL): sweep_ms = device time, n_launches, units =
+ * T S (N-1).  Synchronous; on a sharded context a LOCAL call.  PHYLO_EINVAL before anything is queued for a bad tree (naming tree and
+ * row), T < 1, and for child, blen, loglik_T or delta == NULL; PHYLO_ESTATE before phylo_set_leaves and phylo_set_model.  Chunks
+ * and node stores as phylo_trees_grad (PHYLO_TREES_CHUNK).  Own scratch and events, released with the context: the sweep's state
+ * and the scratch of phylo_trees_loglik, phylo_rell, phylo_trees_grad and phylo_trees_grad_rates are left alone. */
+int phylo_trees_nni(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
+                    double* delta, phylo_stats* perf);
 /* Test hook, no GPU needed: the host half of phylo_trees_loglik on ONE tree -- the checks above (PHYLO_EINVAL, "tree 0, row i")
  * and the slot schedule the kernel walks: ops[N-1][4] = {destination slot, left source, right source, row}, a source >= 0 a
  * leaf, a source < 0 the slot ~source; depth = slots in use (<= floor(log2 N) + 1).  tests/test_trees_host.py replays it. */

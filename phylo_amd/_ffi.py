@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_nni", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -612,6 +612,25 @@ class Context:
                                                      _ptr(dweight), C.byref(st)))
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         return (out, grad) + ((curv,) if want_curv else ()) + ((drate, dweight) if want_params else ())
+
+    def trees_nni(self, child, blen, prior=None):
+        """The NNI neighbourhood of every tree at its current lengths (phylo_trees_nni): returns (loglik [T], delta [T][N-1][2]).
+        delta[t][i][side], i < N-2: the change of tree t's log-likelihood when node N + i's child on `side` and the node's sibling
+        change places (every subtree keeps its length); delta[t][N-2][side]: node child[N-2][0]'s side-1 child and node
+        child[N-2][1]'s child on `side` change places (NaN when a root child is a leaf).  -inf: an impossible neighbour; NaN in
+        every entry: trees_grad's rule.  loglik is bit for bit trees_loglik's.  self.last_trees_stats holds the call's stats.
+        phylo_amd.treesearch has the moves as rows (apply_nni) and a hill-climber over this call (nni_search)."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        out = np.empty(T)
+        delta = np.empty(blen.shape)
+        st = Stats()
+        self._check(self._lib.phylo_trees_nni(self._h, C.c_int(T), _ptr(child), _ptr(blen), _ptr(pr), _ptr(out), _ptr(delta), C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return out, delta
 
     def rell(self, site_lik, B, seed, want_reps=False, want_counts=False, want_logs=False):
         """RELL bootstrap over the site factors site_lik [T][S] of a scored tree set (phylo_rell; what trees_loglik and

@@ -304,7 +304,7 @@ class VCSMC:
             tab = new
         return [row[0] for row in tab]
 
-    def score_trees(self, newicks, rates=None, want_sites=False, optimize=False, fit=()):
+    def score_trees(self, newicks, rates=None, want_sites=False, optimize=False, fit=(), search=None, search_rounds=20):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
         distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
         (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
@@ -317,8 +317,14 @@ class VCSMC:
         fit (with optimize and rates): ('alpha',) or ('alpha', 'pinv') -- every tree also climbs its own Gamma shape (and share
         of invariant sites) from the model's values (phylo_amd.treeopt.optimize_rates); rates is then what
         phylo_amd.rates.parse_spec returns (it knows alpha, C and p_inv), the final scores come from one trees_loglik_rates per
-        tree under that tree's fitted mixture, and self.last_tree_opt also holds 'alpha' and 'pinv' (None without the class)."""
+        tree under that tree's fitted mixture, and self.last_tree_opt also holds 'alpha' and 'pinv' (None without the class).
+        search='nni' (with optimize, without rates): after the climb every tree is hill-climbed over nearest-neighbour
+        interchanges (phylo_amd.treesearch.nni_search over phylo_trees_nni and phylo_trees_grad, at most search_rounds rounds);
+        the scores and site factors are those of the trees found, and self.last_tree_search holds 'newicks' (those trees),
+        'loglik_ml' (of the given topologies at their ML lengths), 'nni_moves', 'rounds' and 'converged' per tree."""
         fit = tuple(fit)
+        if search is not None and (search != 'nni' or not optimize or rates is not None):
+            raise ValueError("score_trees: search=%r needs search='nni', optimize=True and no rates" % (search,))
         spec = rates if isinstance(rates, dict) else None
         if spec is not None:
             rates = (spec['rates'], spec['weights'])
@@ -358,6 +364,14 @@ class VCSMC:
             self.last_tree_opt = {'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(child, blen)],
                                   'loglik_given': [float(x) for x in given], 'iterations': [int(i) for i in opt['iterations']],
                                   'converged': [bool(v) for v in opt['converged']]}
+            if search:
+                from . import treesearch
+                found = treesearch.nni_search(lambda c, b: ctx.trees_grad(c, b, want_curv=True), ctx.trees_nni, child, blen,
+                                              max_rounds=search_rounds)
+                self.last_tree_search = {'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(found['child'], found['blen'])],
+                                         'loglik_ml': [float(x) for x in opt['loglik']], 'nni_moves': [len(m) for m in found['moves']],
+                                         'rounds': [int(r) for r in found['rounds']], 'converged': [bool(v) for v in found['converged']]}
+                child, blen = found['child'], found['blen']
             res = ctx.trees_loglik(child, blen, want_sites=True)
             res = res if want_sites else res[0]
         elif rates is None:
@@ -395,7 +409,14 @@ class VCSMC:
         fit = tuple(mode.split('+')[1:]) if mode and newicks else None
         self.tree_test_results = None
         self.trees_ml = None
-        if ml:
+        self.trees_search = None
+        srch = getattr(self.args, 'score_search', None) if ml else None     # --score_search nni[:ROUNDS]: then an NNI search from there
+        if srch:
+            ll_search, sites = self.score_trees(newicks, want_sites=True, optimize=True, search=srch[0], search_rounds=srch[1])
+            opt, found = self.last_tree_opt, self.last_tree_search
+            ll, ll_ml = opt['loglik_given'], found['loglik_ml']
+            self.trees_ml, self.trees_search = opt['newicks'], found['newicks']
+        elif ml:
             ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True)
             opt = self.last_tree_opt
             ll = opt['loglik_given']
@@ -421,6 +442,9 @@ class VCSMC:
         if ml:                                             # (absent without --score_opt: the file is what it was before the flag)
             for t, x, it, cv in zip(out['trees'], ll_ml, opt['iterations'], opt['converged']):
                 t.update(loglik_ml=x, iterations=it, converged=cv)
+            if srch:                                       # (absent without --score_search)
+                for t, x, nm, rd in zip(out['trees'], ll_search, found['nni_moves'], found['rounds']):
+                    t.update(loglik_search=x, nni_moves=nm, search_rounds=rd)
             if fit:                                        # --score_fit with a fitted model: every tree's own values
                 for i, t in enumerate(out['trees']):
                     t['alpha'] = opt['alpha'][i]
@@ -452,7 +476,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit', 'score_search') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))
@@ -577,6 +601,9 @@ class VCSMC:
                 if getattr(self, 'trees_ml', None) is not None:
                     with open(os.path.join(save_dir, 'trees_ml.nwk'), 'w') as f:
                         f.write('\n'.join(self.trees_ml) + '\n')
+                if getattr(self, 'trees_search', None) is not None:
+                    with open(os.path.join(save_dir, 'trees_search.nwk'), 'w') as f:
+                        f.write('\n'.join(self.trees_search) + '\n')
                 if getattr(self, 'tree_test_results', None) is not None:
                     with open(os.path.join(save_dir, 'tree_tests.json'), 'w') as f:
                         json.dump(self.tree_test_results, f, indent=1)

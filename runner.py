@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -81,6 +81,12 @@ def parse_args(argv=None):
                              "writes trees_ml.nwk, adds loglik_ml, iterations, converged (and alpha, pinv where fitted) to every "
                              "tree of tree_scores.json, and gives --tree_tests the site likelihoods at the fitted values.  Not "
                              "with --score_opt true")
+    parser.add_argument('--score_search', default=None, metavar='nni[:ROUNDS]',
+                        help="with --score_trees and --score_opt true: after the climb, hill-climb every tree over nearest-neighbour "
+                             "interchanges (phylo_trees_nni on the device, phylo_amd/treesearch.py), at most ROUNDS rounds (default "
+                             "20); writes trees_search.nwk (the trees found), adds loglik_search, nni_moves and search_rounds to "
+                             "every tree of tree_scores.json, and gives --tree_tests the site likelihoods of the trees found.  Not "
+                             "with --score_rates or --score_fit")
     parser.add_argument('--tree_tests', default=None, metavar='B[:SEED]',
                         help="with --score_trees: which of those trees are significantly worse than the best one?  A RELL bootstrap "
                              "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
@@ -103,6 +109,17 @@ def parse_args(argv=None):
             rates.parse_spec(args.score_rates)
         except ValueError as e:
             parser.error('--score_rates: %s' % e)
+    if args.score_search is not None:
+        kind, _, rounds = str(args.score_search).partition(':')
+        if kind != 'nni' or (rounds and not (rounds.isdigit() and int(rounds) >= 1)):
+            parser.error('--score_search: nni or nni:ROUNDS with ROUNDS >= 1, not %r' % args.score_search)
+        if args.score_rates is not None or args.score_fit is not None:
+            parser.error('--score_search nni: the NNI neighbourhood is not built for rate mixtures (not with --score_rates or '
+                         '--score_fit)')
+        if not args.score_trees or not args.score_opt:
+            parser.error('--score_search needs --score_trees and --score_opt true (it searches from the trees scored there, at '
+                         'their maximum-likelihood lengths)')
+        args.score_search = ('nni', int(rounds) if rounds else 20)
     if args.score_opt:
         if not args.score_trees:
             parser.error('--score_opt true needs --score_trees FILE (it optimises the branch lengths of the trees scored there)')

@@ -47,6 +47,7 @@ def cycle(i):
         child = np.array([[j - 1 + N if j else 0, j + 1] for j in range(N - 1)], dtype=np.int32)   # a caterpillar, 30 .. 37 times
         n = 30 + i % 8
         c.trees_grad(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1), want_curv=True)   # the gradient's own slab and node stores
+        c.trees_nni(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1))   # the NNI neighbourhood's own slab and node stores
         c.trees_grad_rates(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1), np.linspace(0.0, 2.0, 2 + i % 4), np.full(2 + i % 4, 0.25),
                            want_curv=True, want_params=True)   # ... and the mixture gradient's: a slab that grows with the categories
     v = T.Variables(N2, np.log(10.0), False)            # a context of 66 taxa that trains: two steps, so two passes on one context

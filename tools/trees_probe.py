@@ -23,7 +23,14 @@ cost, and whether loglik carries the plain call's bits.
 
 --grad --rates C times phylo_trees_grad_rates under C discrete Gamma categories: the gradient alone,
 with curvature, and with curvature and the rate and weight sums, against C calls of phylo_trees_grad (with curvature) on the
-scaled trees, interleaved in the same run; the number of chunks, and whether loglik carries phylo_trees_loglik_rates' bits."""
+scaled trees, interleaved in the same run; the number of chunks, and whether loglik carries phylo_trees_loglik_rates' bits.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --nni --reps 7 --out profiles/trees_probe.jsonl
+
+--nni times phylo_trees_nni against phylo_trees_loglik on the explicitly built NNI neighbours of the first
+--explicit_trees trees (and phylo_trees_nni on those trees alone), the plain call and phylo_trees_grad with and without
+curvature, interleaved in the same run: device and wall times, their ratios, whether loglik carries the plain call's bits, and
+the worst relative difference of loglik + delta to the explicit neighbour's log-likelihood."""
 import argparse
 import json
 import os
@@ -215,6 +222,75 @@ def grad_rates_probe(a):
     return 0 if same else 1
 
 
+def nni_probe(a):
+    """phylo_trees_nni against phylo_trees_loglik on the explicitly built neighbours of the same trees, and against
+    phylo_trees_grad: same trees, same context, same run.  The neighbours of the first --explicit_trees trees are built as rows
+    (phylo_amd.treesearch.apply_nni, outside the timed region: 2 (N-2) or 2 (N-1) trees each) and compared per tree of the set."""
+    from phylo_amd.treesearch import apply_nni, nni_moves
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    n_x = min(a.explicit_trees, a.trees) if a.explicit_trees > 0 else a.trees
+    at, cs, bs = [], [], []
+    for t in range(n_x):
+        for mv in nni_moves(child[t]):
+            c2, b2 = apply_nni(child[t], blen[t], *mv)
+            at.append((t,) + mv)
+            cs.append(c2)
+            bs.append(b2)
+    xc, xb, at = np.array(cs), np.array(bs), np.array(at)
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        ll = ctx.trees_loglik(child, blen)                   # warm-up of every call
+        ln, delta = ctx.trees_nni(child, blen)
+        ctx.trees_nni(child[:n_x], blen[:n_x])
+        ctx.trees_grad(child, blen)
+        ctx.trees_grad(child, blen, want_curv=True)
+        lx = ctx.trees_loglik(xc, xb)
+        same = bool(np.array_equal(ll.view(np.uint64), ln.view(np.uint64)))
+        with np.errstate(invalid='ignore'):
+            diff = np.abs((ll[at[:, 0]] + delta[at[:, 0], at[:, 1], at[:, 2]]) - lx) / np.abs(lx)
+        worst = float(np.nanmax(diff))
+        calls = (('plain', lambda: ctx.trees_loglik(child, blen)), ('nni', lambda: ctx.trees_nni(child, blen)),
+                 ('nni_subset', lambda: ctx.trees_nni(child[:n_x], blen[:n_x])), ('explicit_subset', lambda: ctx.trees_loglik(xc, xb)),
+                 ('grad', lambda: ctx.trees_grad(child, blen)), ('curv', lambda: ctx.trees_grad(child, blen, want_curv=True)))
+        t = {k: ([], []) for k, _ in calls}
+        stats = {}
+        for _ in range(a.reps):                              # interleaved: every call sees the same machine
+            for k, call in calls:
+                t0 = time.perf_counter()
+                call()
+                t[k][0].append((time.perf_counter() - t0) * 1e3)
+                t[k][1].append(ctx.last_trees_stats['sweep_ms'])
+                stats[k] = dict(ctx.last_trees_stats)
+    q = {k: (quartiles(v[0]), quartiles(v[1])) for k, v in t.items()}
+    rec = {'probe': 'trees_nni', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'jc': jc, 'reps': a.reps,
+           'explicit_trees': int(n_x), 'neighbours': int(xc.shape[0])}
+    for k in t:
+        rec[k + '_wall_ms'], rec[k + '_device_ms'] = q[k]
+    rec.update({'device_ratio_nni_over_plain': q['nni'][1]['median'] / q['plain'][1]['median'],
+                'device_ratio_nni_over_grad': q['nni'][1]['median'] / q['grad'][1]['median'],
+                'device_ratio_nni_over_curv': q['nni'][1]['median'] / q['curv'][1]['median'],
+                'device_ratio_explicit_over_nni_same_trees': q['explicit_subset'][1]['median'] / q['nni_subset'][1]['median'],
+                'wall_ratio_explicit_over_nni_same_trees': q['explicit_subset'][0]['median'] / q['nni_subset'][0]['median'],
+                'launches': stats['nni']['n_launches'], 'units': stats['nni']['units'],
+                'units_per_s_device_nni': stats['nni']['units'] / (q['nni'][1]['median'] * 1e-3),
+                'loglik_bit_equal': same, 'worst_relative_difference_to_explicit': worst,
+                'finite': bool(np.isfinite(delta[at[:, 0], at[:, 1], at[:, 2]]).all())})
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same and worst < 1e-9 else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -228,7 +304,11 @@ def main(argv=None):
     ap.add_argument('--rates', type=int, default=0, help='C > 0: probe phylo_trees_loglik_rates under C Gamma categories')
     ap.add_argument('--alpha', type=float, default=0.5)
     ap.add_argument('--grad', action='store_true', help='probe phylo_trees_grad (with and without curvature) against the plain call')
+    ap.add_argument('--nni', action='store_true', help='probe phylo_trees_nni against phylo_trees_loglik on the explicit neighbours, and phylo_trees_grad')
+    ap.add_argument('--explicit_trees', type=int, default=512, help='with --nni: trees whose neighbours are built and scored explicitly (0: all)')
     a = ap.parse_args(argv)
+    if a.nni:
+        return nni_probe(a)
     if a.grad and a.rates > 0:
         return grad_rates_probe(a)
     if a.grad:
