@@ -38,16 +38,18 @@ def reference(ctx, child, blen, prior, g):
     return NR.trees_nni(child, device_matrices(ctx, blen), prior, g)
 
 
-def close(name, got, ref, absd, S):
-    """NaN where the restatement has NaN, -inf where it has -inf, elsewhere within TOL_NNI (S + sum |d_s| + |value|)"""
+def close(name, got, ref, absd, S, tol=TOL_NNI):
+    """NaN where the restatement has NaN, -inf where it has -inf, elsewhere within TOL_NNI (S + sum |d_s| + |value|) (tol: the
+    bound of the deep trees, treenni_cases.TOL_NNI_BIG).  Returns the worst ratio to the bound."""
     np.testing.assert_array_equal(np.isnan(got), np.isnan(ref), err_msg=name + ": NaN entries")
     np.testing.assert_array_equal(np.isneginf(got), np.isneginf(ref), err_msg=name + ": -inf entries")
     at = np.isfinite(ref)
     assert np.isfinite(got[at]).all(), name
     err = np.abs(got[at] - ref[at]) / (S + absd[at] + np.abs(ref[at]))
-    print("%s: worst |device - restatement| / (S + sum |d_s| + |value|) = %.3g (TOL_NNI %.3g) over %d entries, %d -inf, %d NaN"
-          % (name, err.max() if err.size else 0.0, TOL_NNI, err.size, np.isneginf(ref).sum(), np.isnan(ref).sum()))
-    assert (err <= TOL_NNI).all(), (name, float(err.max()), TOL_NNI)
+    print("%s: worst |device - restatement| / (S + sum |d_s| + |value|) = %.3g (bound %.3g) over %d entries, %d -inf, %d NaN"
+          % (name, err.max() if err.size else 0.0, tol, err.size, np.isneginf(ref).sum(), np.isnan(ref).sum()))
+    assert (err <= tol).all(), (name, float(err.max()), tol)
+    return float(err.max()) / tol if err.size else 0.0
 
 
 def missing_moves(child):
@@ -59,20 +61,21 @@ def missing_moves(child):
     return out
 
 
-def explicit(name, ctx, child, blen, ll, delta, prior, S):
-    """loglik + delta against phylo_trees_loglik of every explicitly built neighbour"""
+def explicit(name, ctx, child, blen, ll, delta, prior, S, tol=TOL_EXPL, moves=nni_moves):
+    """loglik + delta against phylo_trees_loglik of every explicitly built neighbour (moves: which of a tree's moves; tol: the
+    bound of the deep trees, treenni_cases.TOL_EXPL_BIG).  Returns the worst ratio to the bound."""
     _, sites = ctx.trees_loglik(child, blen, prior=prior, want_sites=True)
     with np.errstate(divide='ignore'):
         a0 = np.abs(np.log(sites)).sum(axis=1)
     cs, bs, at = [], [], []
     for t in range(child.shape[0]):
-        for mv in nni_moves(child[t]):
+        for mv in moves(child[t]):
             c2, b2 = apply_nni(child[t], blen[t], *mv)
             cs.append(c2)
             bs.append(b2)
             at.append((t,) + mv)
     if not cs:
-        return
+        return 0.0
     ll2, sites2 = ctx.trees_loglik(np.array(cs), np.array(bs), prior=prior, want_sites=True)
     worst = 0.0
     for (t, r, sd), x, s2 in zip(at, ll2, sites2):
@@ -82,9 +85,10 @@ def explicit(name, ctx, child, blen, ll, delta, prior, S):
             continue
         err = abs(lhs - x) / (S + a0[t] + np.abs(np.log(s2)).sum())
         worst = max(worst, err)
-        assert err <= TOL_EXPL, (name, t, r, sd, lhs, x, err, TOL_EXPL)
-    print("%s: worst |(loglik + delta) - loglik of the neighbour| / (S + sum |log L| + sum |log L'|) = %.3g (TOL_EXPL %.3g) over %d moves"
-          % (name, worst, TOL_EXPL, len(at)))
+        assert err <= tol, (name, t, r, sd, lhs, x, err, tol)
+    print("%s: worst |(loglik + delta) - loglik of the neighbour| / (S + sum |log L| + sum |log L'|) = %.3g (bound %.3g) over %d moves"
+          % (name, worst, tol, len(at)))
+    return worst / tol
 
 
 # ---- 1. shapes and conditions ------------------------------------------------------------------------------------------------

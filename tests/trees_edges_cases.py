@@ -1,4 +1,4 @@
-"""Shared inputs of the edge tests of scored tree sets (DESIGN.md sections 11, 11b, 13): alignments simulated along trees of 129
+"""Shared inputs of the edge tests of scored tree sets (DESIGN.md sections 11, 11b, 13, 14): alignments simulated along trees of 129
 to 512 taxa with that tree and nearest-neighbour interchanges of it as the set; sets with more work items than ptg_updown has
 workgroups; generic leaves scaled by exact powers of two so that chosen site factors land near the floor of the double range;
 random columns over 300 and 310 taxa, which reach that floor by themselves.  test_trees_edges_cpu.py holds every case to its
@@ -60,6 +60,20 @@ def big_case(name, n=5):
         g[rng.integers(0, N), rng.integers(0, S)] = [0.5, 0.25, 0.0, 1.0]       # one row that is no indicator: no codes at all
     for a in (g, child, blen):
         a.setflags(write=False)
+    return g, child, blen, Q
+
+
+@functools.lru_cache(maxsize=None)
+def two_strip_case(S=200):
+    """(g, child, blen, Q): balanced-N257's tree set on an alignment of S sites simulated along the same generating tree (the
+    case's seed gives the tree and its lengths, SEEDS['two-strips'] the columns): with a site tile of 256 one tile whose second
+    strip of 128 sites holds S - 128 live ones"""
+    name = 'balanced-N257'
+    _, child, blen, Q = big_case(name)
+    c0, b0 = SHAPES['balanced'](257, np.random.default_rng(SEEDS.get(name, 12)))
+    assert c0.tobytes() == child[0].tobytes()
+    g = simulate(c0, b0 + 0.05, Q, PRIOR, S, np.random.default_rng(SEEDS.get('two-strips', 200)))
+    g.setflags(write=False)
     return g, child, blen, Q
 
 
