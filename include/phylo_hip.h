@@ -224,6 +224,25 @@ int phylo_trees_grad_rates(phylo_ctx* ctx, int T, const int32_t* child, const do
  * and the scratch of phylo_trees_loglik, phylo_rell, phylo_trees_grad and phylo_trees_grad_rates are left alone. */
 int phylo_trees_nni(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
                     double* delta, phylo_stats* perf);
+/* phylo_trees_nni under a mixture of C rate categories: trees, numbering, checks, prior, state rules, moves,
+ * rows, sides and the NaN of a missing root move as phylo_trees_nni; rate, weight [C] (per_tree == 0) or [T][C] (per_tree == 1),
+ * 1 <= C <= 16, checked as phylo_trees_grad_rates checks them.  Category c of tree t is the tree (child, rate[t][c] blen), one
+ * multiply per length on the host; inside it everything is phylo_trees_nni's under that category's matrices, giving the tree's
+ * factor f_c and every neighbour's f'_c per site.  m_s = w_0 f_0, then fma(w_c, f_c, m) in ascending c (phylo_trees_loglik_rates'
+ * value); m'_s the same chain over f'_c;
+ *   loglik_T[t]        bit for bit phylo_trees_loglik_rates' value for that tree under that tree's mixture (same prior and tile);
+ *   delta[t][i][side]  = sum_s log(m'_s (1 / m_s)), shaped [T][N-1][2].
+ * The neighbour's mixture log-likelihood at the current lengths is loglik_T[t] + delta.  A neighbour with m'_s = 0 at a site gets
+ * -inf; a single f'_c = 0 with m'_s > 0, a zero weight and a rate-0 category are ordinary.  A tree whose loglik is not finite, or
+ * with an m_s below 2^-1020 or not finite, gets NaN in every entry.  Fixed order of summation, no atomics: a call repeats its own
+ * bits; chunking, the grid cap, a tree's place and shared against per-tree passing of the same numbers change none; against a
+ * restatement delta carries a tolerance.  perf (may be NULL): units = T S (N-1) C.  Synchronous; a LOCAL call on a sharded context.
+ * PHYLO_EINVAL before anything is queued for a bad tree, C outside 1 .. 16, a bad rate, weight or scaled length (the message names
+ * tree, row and category), per_tree outside {0, 1}, T < 1, a tree whose wave would need more than 64 KiB of LDS, and for child,
+ * blen, rate, weight, loglik_T or delta == NULL; PHYLO_ESTATE before phylo_set_leaves and phylo_set_model.  Own scratch and events,
+ * released with the context: the sweep's state and the scratch of every other tree-set call are left alone. */
+int phylo_trees_nni_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate,
+                          const double* weight, int per_tree, const double* prior4, double* loglik_T, double* delta, phylo_stats* perf);
 /* Test hook, no GPU needed: the host half of phylo_trees_loglik on ONE tree -- the checks above (PHYLO_EINVAL, "tree 0, row i")
  * and the slot schedule the kernel walks: ops[N-1][4] = {destination slot, left source, right source, row}, a source >= 0 a
  * leaf, a source < 0 the slot ~source; depth = slots in use (<= floor(log2 N) + 1).  tests/test_trees_host.py replays it. */

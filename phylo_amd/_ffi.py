@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_nni", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -629,6 +629,37 @@ class Context:
         delta = np.empty(blen.shape)
         st = Stats()
         self._check(self._lib.phylo_trees_nni(self._h, C.c_int(T), _ptr(child), _ptr(blen), _ptr(pr), _ptr(out), _ptr(delta), C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return out, delta
+
+    def trees_nni_rates(self, child, blen, rates, weights, prior=None):
+        """trees_nni under a mixture of C rate categories (phylo_trees_nni_rates): returns (loglik [T], delta [T][N-1][2]), the
+        change of trees_loglik_rates' mixture log-likelihood under every NNI move of every tree at its current lengths; moves,
+        rows and sides as trees_nni.  rates and weights are [C] (one mixture for all trees) or [T][C] (tree t under row t).
+        loglik is bit for bit trees_loglik_rates'; -inf: a neighbour whose mixed site value is 0 at a site; NaN in every entry:
+        trees_grad's rule on the mixed site value.  self.last_trees_stats holds the call's stats."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        rates, weights = _f64(rates), _f64(weights)
+        if rates.shape != weights.shape:
+            raise ValueError("rates and weights must have one shape, got %r and %r" % (rates.shape, weights.shape))
+        if rates.ndim == 2:
+            if rates.shape[0] != T:
+                raise ValueError("per-tree rates must be [T][C] with T = %d, got %r" % (T, rates.shape))
+            per_tree = 1
+        elif rates.ndim == 1:
+            per_tree = 0
+        else:
+            raise ValueError("rates must be [C] or [T][C], got %r" % (rates.shape,))
+        nc = rates.shape[-1]
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        out = np.empty(T)
+        delta = np.empty(blen.shape)
+        st = Stats()
+        self._check(self._lib.phylo_trees_nni_rates(self._h, C.c_int(T), _ptr(child), _ptr(blen), C.c_int(nc), _ptr(rates), _ptr(weights),
+                                                    C.c_int(per_tree), _ptr(pr), _ptr(out), _ptr(delta), C.byref(st)))
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         return out, delta
 

@@ -32,6 +32,7 @@
 #include "phylo_treegrad.h"
 #include "phylo_treegrad_rates.h"
 #include "phylo_treenni.h"
+#include "phylo_treenni_rates.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -247,9 +248,10 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[19];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+    DevBuf scratch[20];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
                                          //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates;
-                                         //  16: phylo_trees_grad's chunk and node stores; 17: phylo_trees_grad_rates's; 18: phylo_trees_nni's)
+                                         //  16: phylo_trees_grad's chunk and node stores; 17: phylo_trees_grad_rates's; 18: phylo_trees_nni's;
+                                         //  19: phylo_trees_nni_rates's)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -268,6 +270,7 @@ struct phylo_ctx {
     hipEvent_t ev_tg0 = nullptr, ev_tg1 = nullptr;   // phylo_trees_grad's own pair
     hipEvent_t ev_tr0 = nullptr, ev_tr1 = nullptr;   // phylo_trees_grad_rates' own pair
     hipEvent_t ev_tn0 = nullptr, ev_tn1 = nullptr;   // phylo_trees_nni's own pair
+    hipEvent_t ev_tm0 = nullptr, ev_tm1 = nullptr;   // phylo_trees_nni_rates' own pair
 };
 
 namespace {
@@ -819,6 +822,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_tr1) (void)hipEventDestroy(c->ev_tr1);
     if (c->ev_tn0) (void)hipEventDestroy(c->ev_tn0);
     if (c->ev_tn1) (void)hipEventDestroy(c->ev_tn1);
+    if (c->ev_tm0) (void)hipEventDestroy(c->ev_tm0);
+    if (c->ev_tm1) (void)hipEventDestroy(c->ev_tm1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -1760,6 +1765,134 @@ int phylo_trees_nni(phylo_ctx* c, int T, const int32_t* child, const double* ble
         st.sweep_ms = ms_total;
         st.n_launches = launches;
         st.units = (double)T * S * R;
+        st.alg_bytes = 96.0 * st.units;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
+// ---- the same under a mixture of rate categories (phylo_treenni_rates.h) ----
+int phylo_trees_nni_rates(phylo_ctx* c, int T, const int32_t* child, const double* blen, int C, const double* rate, const double* weight,
+                          int per_tree, const double* prior4, double* loglik_T, double* delta, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_nni_rates needs phylo_set_leaves and phylo_set_model first");
+    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    if (C < 1 || C > PT2_MAX_CATS) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
+    if (per_tree != 0 && per_tree != 1) return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: per_tree must be 0 or 1 (per_tree=%d)", per_tree);
+    if (!child || !blen || !rate || !weight || !loglik_T || !delta)
+        return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: child, blen, rate, weight, loglik and delta must be given (NULL pointer)");
+    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
+    const size_t mix_stride = per_tree ? (size_t)C : 0;    // tree t's mixture: row t, or the one row
+    for (int t = 0; t < T; ++t) {                          // every tree and its mixture are checked before anything is queued
+        int row = 0;
+        char msg[200];
+        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+        if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
+    }
+    const bool coded = c->leaves_coded;
+    ptnr_plan pl;
+    if (ptnr_make_plan(N, ntiles, T, C, coded, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+        return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: no plan for N=%d, %d tiles, T=%d, C=%d", N, ntiles, T, C);
+    const int chunk = pl.chunk;
+    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4), nops((size_t)chunk * R * 4);
+    std::vector<double> ts((size_t)chunk * C * R * 2), ws((size_t)chunk * C);
+    for (int t = 0; t < T; ++t) {                          // the LDS of every tree's schedule, too, before anything is queued
+        const int depth = pt2_schedule(N, child + (size_t)t * R * 2, ops.data());
+        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+        if (ptnr_lds_bytes(N, depth) > PTGR_MAX_LDS)
+            return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: %zu bytes of LDS for a wave exceed %zu (tree %d, depth %d, N=%d)",
+                        ptnr_lds_bytes(N, depth), PTGR_MAX_LDS, t, depth, N);
+    }
+    void* slab = nullptr;
+    CHK(scratch_get(c, 19, pl.total, &slab));
+    char* base = (char*)slab;
+    double* d_prior = (double*)(base + pl.o_prior);
+    double* d_w = (double*)(base + pl.o_w);
+    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
+    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
+    int32_t* d_nops = (int32_t*)(base + pl.o_nops);
+    double* d_P = (double*)(base + pl.o_P);
+    double* d_t = (double*)(base + pl.o_t);
+    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
+    double* d_tilev = (double*)(base + pl.o_tilev);
+    double* d_out = (double*)(base + pl.o_out);
+    double* d_dtile = (double*)(base + pl.o_dtile);
+    double* d_dout = (double*)(base + pl.o_dout);
+    if (!c->ev_tm0) {
+        HIPCHK(c, hipEventCreate(&c->ev_tm0));
+        HIPCHK(c, hipEventCreate(&c->ev_tm1));
+    }
+    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    double ms_total = 0.0;
+    int launches = 0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int n = std::min(chunk, T - t0);
+        int depth = 1;
+        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every category's lengths in its order
+            int32_t* o = ops.data() + (size_t)t * R * 4;
+            int32_t* d = dops.data() + (size_t)t * R * 4;
+            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
+            depth = std::max(depth, pt2_schedule(N, ch, o));
+            if (ptg_down_ops(N, ch, o, d) || ptn_nni_ops(N, o, d, nops.data() + (size_t)t * R * 4))
+                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
+            const double* b = blen + (size_t)(t0 + t) * R * 2;
+            const double* rt = rate + (t0 + t) * mix_stride;
+            const double* wt = weight + (t0 + t) * mix_stride;
+            for (int k = 0; k < C; ++k) {
+                double* tk = ts.data() + ((size_t)t * C + k) * R * 2;
+                for (int i = 0; i < R; ++i) {
+                    tk[2 * i] = rt[k] * b[2 * o[4 * i + 3]];
+                    tk[2 * i + 1] = rt[k] * b[2 * o[4 * i + 3] + 1];
+                }
+                ws[(size_t)t * C + k] = wt[k];
+            }
+        }
+        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_nops, nops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * C * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_w, ws.data(), (size_t)n * C * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_tm0, c->stream));
+        const long n_mat = (long)n * C * R * 2;
+        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
+        CHK(launch_check(c, "pk_expm_batched"));
+        ++launches;
+        if (coded) {
+            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
+            CHK(launch_check(c, "pt2_gap_rows"));
+            ++launches;
+        }
+        ptnr_args g{};
+        pt2_args& a = g.a;
+        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
+        a.prior = prior4 ? d_prior : c->d_pi;
+        a.tilev = d_tilev; a.site_lik = nullptr;
+        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
+        g.dops = d_dops; g.nops = d_nops; g.w = d_w; g.dtile = d_dtile; g.store = (pk_d2*)(base + pl.o_store);
+        g.n_items = n * ntiles; g.depth = depth; g.C = C;
+        ptnr_launch(g, std::min(pl.grid, g.n_items), coded, c->stream);
+        CHK(launch_check(c, "ptnr_updown"));
+        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
+        CHK(launch_check(c, "pt2_finish"));
+        hipLaunchKernelGGL(ptnr_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)d_ops,
+                           (const double*)d_out, ntiles, n, R, d_dout);
+        CHK(launch_check(c, "ptnr_finish"));
+        launches += 3;
+        HIPCHK(c, hipEventRecord(c->ev_tm1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(delta + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tm0, c->ev_tm1));
+        ms_total += ms;
+    }
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * R * C;
         st.alg_bytes = 96.0 * st.units;
         *perf = st;
     }

@@ -66,10 +66,12 @@ def apply_nni(child, blen, row, side):
     return _renumber(kids, lens, N + R - 1, N)
 
 
-def nni_search(grad_fn, nni_fn, child, blen, max_rounds=20, eps=1e-6, **optimize_kw):
+def nni_search(grad_fn, nni_fn, child, blen, max_rounds=20, eps=1e-6, with_index=False, **optimize_kw):
     """Hill-climb T trees over NNI moves, all trees in lockstep.  grad_fn(child [n][N-1][2], blen) -> (loglik [n], grad, curv) and
     nni_fn(child, blen) -> (loglik [n], delta [n][N-1][2]) score any set of trees at once (Context.trees_grad with want_curv and
-    Context.trees_nni, or restatements of them); optimize_kw goes to optimize_branches.
+    Context.trees_nni, or restatements of them); optimize_kw goes to optimize_branches.  With with_index=True both are called as
+    grad_fn(child, blen, idx) and nni_fn(child, blen, idx), idx [n] the indices, into the T trees given, of the trees in that
+    call: what belongs to a tree (its own rate mixture, say) can follow it through the subsets the search passes.
 
     Every tree's lengths are climbed first.  Then, per round: one nni_fn call on all unfinished trees; per tree the move with the
     largest finite delta above eps that is not barred is applied (apply_nni); the changed trees are re-optimised in ONE lockstep
@@ -85,7 +87,13 @@ def nni_search(grad_fn, nni_fn, child, blen, max_rounds=20, eps=1e-6, **optimize
     if child.ndim == 2:
         child, b = child[None], b[None]
     T = child.shape[0]
-    opt = optimize_branches(lambda x: grad_fn(child, x), child, b, **optimize_kw)
+    if with_index:
+        grad_of = lambda c, x, i: grad_fn(c, x, np.array(i, dtype=np.int64))     # noqa: E731
+        nni_of = lambda c, x, i: nni_fn(c, x, np.array(i, dtype=np.int64))       # noqa: E731
+    else:
+        grad_of = lambda c, x, i: grad_fn(c, x)                                   # noqa: E731
+        nni_of = lambda c, x, i: nni_fn(c, x)                                     # noqa: E731
+    opt = optimize_branches(lambda x: grad_of(child, x, np.arange(T)), child, b, **optimize_kw)
     b, ll = opt['blen'], np.array(opt['loglik'], dtype=np.float64)
     history = [[float(v)] for v in ll]
     moves = [[] for _ in range(T)]
@@ -96,7 +104,7 @@ def nni_search(grad_fn, nni_fn, child, blen, max_rounds=20, eps=1e-6, **optimize
         idx = np.flatnonzero(active)
         if idx.size == 0:
             break
-        _, delta = nni_fn(child[idx], b[idx])
+        _, delta = nni_of(child[idx], b[idx], idx)
         tried, new_child, new_blen = [], [], []
         for k, t in enumerate(idx):
             d = np.array(delta[k], dtype=np.float64)
@@ -115,7 +123,8 @@ def nni_search(grad_fn, nni_fn, child, blen, max_rounds=20, eps=1e-6, **optimize
         if not tried:
             break
         new_child = np.array(new_child)
-        o = optimize_branches(lambda x: grad_fn(new_child, x), new_child, np.array(new_blen), **optimize_kw)
+        who = [t for t, _ in tried]
+        o = optimize_branches(lambda x: grad_of(new_child, x, who), new_child, np.array(new_blen), **optimize_kw)
         for k, (t, mv) in enumerate(tried):
             rounds[t] += 1
             if o['loglik'][k] > ll[t]:

@@ -318,13 +318,17 @@ class VCSMC:
         of invariant sites) from the model's values (phylo_amd.treeopt.optimize_rates); rates is then what
         phylo_amd.rates.parse_spec returns (it knows alpha, C and p_inv), the final scores come from one trees_loglik_rates per
         tree under that tree's fitted mixture, and self.last_tree_opt also holds 'alpha' and 'pinv' (None without the class).
-        search='nni' (with optimize, without rates): after the climb every tree is hill-climbed over nearest-neighbour
-        interchanges (phylo_amd.treesearch.nni_search over phylo_trees_nni and phylo_trees_grad, at most search_rounds rounds);
-        the scores and site factors are those of the trees found, and self.last_tree_search holds 'newicks' (those trees),
-        'loglik_ml' (of the given topologies at their ML lengths), 'nni_moves', 'rounds' and 'converged' per tree."""
+        search='nni' (with optimize): after the climb every tree is hill-climbed over nearest-neighbour interchanges
+        (phylo_amd.treesearch.nni_search over phylo_trees_nni and phylo_trees_grad, at most search_rounds rounds); the scores and
+        site factors are those of the trees found, and self.last_tree_search holds 'newicks' (those trees), 'loglik_ml' (of the
+        given topologies at their ML lengths), 'nni_moves', 'rounds' and 'converged' per tree.  With rates the search runs under
+        the mixture (phylo_trees_nni_rates and phylo_trees_grad_rates).  With fit as well, every tree is searched with ITS fitted
+        alpha (and p_inv) held fixed -- a mixture per tree, which follows its tree through the search --, then one more
+        optimize_rates runs on the trees found from the found lengths and those values; self.last_tree_search then also holds
+        the final 'alpha' and 'pinv' (self.last_tree_opt keeps those of the given topologies)."""
         fit = tuple(fit)
-        if search is not None and (search != 'nni' or not optimize or rates is not None):
-            raise ValueError("score_trees: search=%r needs search='nni', optimize=True and no rates" % (search,))
+        if search is not None and (search != 'nni' or not optimize):
+            raise ValueError("score_trees: search=%r needs search='nni' and optimize=True" % (search,))
         spec = rates if isinstance(rates, dict) else None
         if spec is not None:
             rates = (spec['rates'], spec['weights'])
@@ -350,6 +354,31 @@ class VCSMC:
             if fit:
                 self.last_tree_opt['alpha'] = [float(a) for a in opt['alpha']]
                 self.last_tree_opt['pinv'] = None if opt['pinv'] is None else [float(p) for p in opt['pinv']]
+            if search:
+                from . import treesearch
+                if fit:                                     # every tree under its own fitted mixture, held fixed while it is searched
+                    r_t, w_t = np.array(opt['rates'], dtype=np.float64), np.array(opt['weights'], dtype=np.float64)
+                    found = treesearch.nni_search(lambda c, b, i: ctx.trees_grad_rates(c, b, r_t[i], w_t[i], want_curv=True),
+                                                  lambda c, b, i: ctx.trees_nni_rates(c, b, r_t[i], w_t[i]), child, blen,
+                                                  max_rounds=search_rounds, with_index=True)
+                else:
+                    found = treesearch.nni_search(lambda c, b: ctx.trees_grad_rates(c, b, rates[0], rates[1], want_curv=True),
+                                                  lambda c, b: ctx.trees_nni_rates(c, b, rates[0], rates[1]), child, blen,
+                                                  max_rounds=search_rounds)
+                ml_scores = [float(x) for x in opt['loglik']]
+                child, blen = found['child'], found['blen']
+                if fit:                                     # the model of the trees found, from the found lengths and the values held
+                    opt = treeopt.optimize_rates(lambda b, r, w: ctx.trees_grad_rates(child, b, r, w, want_curv=True, want_params=True),
+                                                 child, blen, opt['alpha'], spec['C'],
+                                                 pinv0=spec['pinv'] if opt['pinv'] is None else opt['pinv'], fit=fit)
+                    blen = opt['blen']
+                self.last_tree_search = {'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(child, blen)],
+                                         'loglik_ml': ml_scores, 'nni_moves': [len(m) for m in found['moves']],
+                                         'rounds': [int(r) for r in found['rounds']], 'converged': [bool(v) for v in found['converged']]}
+                if fit:
+                    self.last_tree_search['alpha'] = [float(a) for a in opt['alpha']]
+                    self.last_tree_search['pinv'] = None if opt['pinv'] is None else [float(p) for p in opt['pinv']]
+            if fit:
                 per = [ctx.trees_loglik_rates(child[t], blen[t], opt['rates'][t], opt['weights'][t], want_sites=True)
                        for t in range(child.shape[0])]
                 res = (np.array([p[0][0] for p in per]), np.array([p[1][0] for p in per]))
@@ -411,7 +440,15 @@ class VCSMC:
         self.trees_ml = None
         self.trees_search = None
         srch = getattr(self.args, 'score_search', None) if ml else None     # --score_search nni[:ROUNDS]: then an NNI search from there
-        if srch:
+        fsrch = getattr(self.args, 'score_fit_search', None) if fit is not None else None   # --score_fit_search: the same under the rate model
+        if fsrch:
+            ll_search, sites = self.score_trees(newicks, rates=rm, want_sites=True, optimize=True, fit=fit, search=fsrch[0],
+                                                search_rounds=fsrch[1])
+            opt, found = self.last_tree_opt, self.last_tree_search
+            ll, ll_ml = opt['loglik_given'], found['loglik_ml']
+            self.trees_ml, self.trees_search = opt['newicks'], found['newicks']
+            srch, ml = fsrch, True
+        elif srch:
             ll_search, sites = self.score_trees(newicks, want_sites=True, optimize=True, search=srch[0], search_rounds=srch[1])
             opt, found = self.last_tree_opt, self.last_tree_search
             ll, ll_ml = opt['loglik_given'], found['loglik_ml']
@@ -450,6 +487,10 @@ class VCSMC:
                     t['alpha'] = opt['alpha'][i]
                     if opt['pinv'] is not None:
                         t['pinv'] = opt['pinv'][i]
+                    if fsrch:                              # (absent without --score_fit_search) the values of the tree found
+                        t['alpha_search'] = found['alpha'][i]
+                        if found['pinv'] is not None:
+                            t['pinv_search'] = found['pinv'][i]
         if rm is not None:                                 # (absent without --score_rates: the file is what it was before the flag)
             out['rates'] = {'spec': rm['spec'], 'rates': rm['rates'].tolist(), 'weights': rm['weights'].tolist()}
         post = self.posterior
@@ -476,7 +517,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit', 'score_search') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit', 'score_search', 'score_fit_search') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))

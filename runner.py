@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -86,13 +86,28 @@ def parse_args(argv=None):
                              "interchanges (phylo_trees_nni on the device, phylo_amd/treesearch.py), at most ROUNDS rounds (default "
                              "20); writes trees_search.nwk (the trees found), adds loglik_search, nni_moves and search_rounds to "
                              "every tree of tree_scores.json, and gives --tree_tests the site likelihoods of the trees found.  Not "
-                             "with --score_rates or --score_fit")
+                             "with --score_rates or --score_fit: --score_fit_search does this under a rate model")
+    parser.add_argument('--score_fit_search', default=None, metavar='nni[:ROUNDS]',
+                        help="with --score_trees, --score_rates and --score_fit: after the fit, hill-climb every tree over "
+                             "nearest-neighbour interchanges UNDER the rate model (phylo_trees_nni_rates on the device), every tree "
+                             "with its own fitted alpha (and p_inv) held fixed, at most ROUNDS rounds (default 20), then fit the "
+                             "trees found once more; writes trees_search.nwk, adds loglik_search, nni_moves and search_rounds (and "
+                             "alpha_search, pinv_search where fitted) to every tree of tree_scores.json, and gives --tree_tests the "
+                             "site likelihoods of the trees found")
     parser.add_argument('--tree_tests', default=None, metavar='B[:SEED]',
                         help="with --score_trees: which of those trees are significantly worse than the best one?  A RELL bootstrap "
                              "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
                              "--score_rates if given) writes tree_tests.json beside tree_scores.json: per tree the observed score, "
                              "the bootstrap proportion, the p-values of the KH and SH tests and the expected likelihood weight")
     args = parser.parse_args(argv)
+    if args.score_fit_search is not None:
+        kind, _, rounds = str(args.score_fit_search).partition(':')
+        if kind != 'nni' or (rounds and not (rounds.isdigit() and int(rounds) >= 1)):
+            parser.error('--score_fit_search: nni or nni:ROUNDS with ROUNDS >= 1, not %r' % args.score_fit_search)
+        if not args.score_trees or args.score_rates is None or args.score_fit is None:
+            parser.error('--score_fit_search needs --score_trees, --score_rates and --score_fit (it searches from the trees fitted '
+                         'there, under their fitted rate models)')
+        args.score_fit_search = ('nni', int(rounds) if rounds else 20)
     if args.tree_tests is not None:
         if not args.score_trees:
             parser.error('--tree_tests needs --score_trees FILE (it tests the trees scored there)')
@@ -115,7 +130,7 @@ def parse_args(argv=None):
             parser.error('--score_search: nni or nni:ROUNDS with ROUNDS >= 1, not %r' % args.score_search)
         if args.score_rates is not None or args.score_fit is not None:
             parser.error('--score_search nni: the NNI neighbourhood is not built for rate mixtures (not with --score_rates or '
-                         '--score_fit)')
+                         '--score_fit); --score_fit_search nni searches under the rate model')
         if not args.score_trees or not args.score_opt:
             parser.error('--score_search needs --score_trees and --score_opt true (it searches from the trees scored there, at '
                          'their maximum-likelihood lengths)')

@@ -30,7 +30,14 @@ scaled trees, interleaved in the same run; the number of chunks, and whether log
 --nni times phylo_trees_nni against phylo_trees_loglik on the explicitly built NNI neighbours of the first
 --explicit_trees trees (and phylo_trees_nni on those trees alone), the plain call and phylo_trees_grad with and without
 curvature, interleaved in the same run: device and wall times, their ratios, whether loglik carries the plain call's bits, and
-the worst relative difference of loglik + delta to the explicit neighbour's log-likelihood."""
+the worst relative difference of loglik + delta to the explicit neighbour's log-likelihood.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --nni --rates 4 --reps 7 --out profiles/trees_probe.jsonl
+
+--nni --rates C times phylo_trees_nni_rates under C discrete Gamma categories against C calls of
+phylo_trees_nni on the scaled trees and, for the first --explicit_trees trees, against phylo_trees_loglik_rates on their explicitly
+built neighbours, interleaved in the same run: device and wall times, their ratios, the number of chunks, whether loglik carries
+phylo_trees_loglik_rates' bits, and the worst relative difference of loglik + delta to the explicit neighbour's log-likelihood."""
 import argparse
 import json
 import os
@@ -291,6 +298,87 @@ def nni_probe(a):
     return 0 if same and worst < 1e-9 else 1
 
 
+def nni_rates_probe(a):
+    """phylo_trees_nni_rates against C calls of phylo_trees_nni on the scaled trees and against phylo_trees_loglik_rates on the
+    explicitly built neighbours of the first --explicit_trees trees: same trees, same context, same run"""
+    from phylo_amd import rates as R
+    from phylo_amd.treesearch import apply_nni, nni_moves
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    rates, weights = R.rate_model(a.alpha, a.rates)
+    C = rates.size
+    scaled = [rates[c] * blen for c in range(C)]             # (outside the timed region: the caller of C plain calls holds them)
+    n_x = min(a.explicit_trees, a.trees) if a.explicit_trees > 0 else a.trees
+    at, cs, bs = [], [], []
+    for t in range(n_x):
+        for mv in nni_moves(child[t]):
+            c2, b2 = apply_nni(child[t], blen[t], *mv)
+            at.append((t,) + mv)
+            cs.append(c2)
+            bs.append(b2)
+    xc, xb, at = np.array(cs), np.array(bs), np.array(at)
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        ll = ctx.trees_loglik_rates(child, blen, rates, weights)          # warm-up of every call
+        ln, delta = ctx.trees_nni_rates(child, blen, rates, weights)
+        per_chunk = 5 if ctx.last_trees_stats['n_launches'] % 5 == 0 else 4
+        chunks = ctx.last_trees_stats['n_launches'] // per_chunk
+        ctx.trees_nni_rates(child[:n_x], blen[:n_x], rates, weights)
+        for c in range(C):
+            ctx.trees_nni(child, scaled[c])
+        lx = ctx.trees_loglik_rates(xc, xb, rates, weights)
+        same = bool(np.array_equal(ll.view(np.uint64), ln.view(np.uint64)))
+        with np.errstate(invalid='ignore'):
+            diff = np.abs((ll[at[:, 0]] + delta[at[:, 0], at[:, 1], at[:, 2]]) - lx) / np.abs(lx)
+        worst = float(np.nanmax(diff))
+
+        def plain_x_C():
+            d = 0.0
+            for c in range(C):
+                ctx.trees_nni(child, scaled[c])
+                d += ctx.last_trees_stats['sweep_ms']
+            ctx.last_trees_stats['sweep_ms'] = d
+
+        calls = (('nni_rates', lambda: ctx.trees_nni_rates(child, blen, rates, weights)), ('plain_x_C', plain_x_C),
+                 ('nni_rates_subset', lambda: ctx.trees_nni_rates(child[:n_x], blen[:n_x], rates, weights)),
+                 ('explicit_subset', lambda: ctx.trees_loglik_rates(xc, xb, rates, weights)))
+        t = {k: ([], []) for k, _ in calls}
+        stats = {}
+        for _ in range(a.reps):                              # interleaved: every call sees the same machine
+            for k, call in calls:
+                t0 = time.perf_counter()
+                call()
+                t[k][0].append((time.perf_counter() - t0) * 1e3)
+                t[k][1].append(ctx.last_trees_stats['sweep_ms'])
+                stats[k] = dict(ctx.last_trees_stats)
+    q = {k: (quartiles(v[0]), quartiles(v[1])) for k, v in t.items()}
+    rec = {'probe': 'trees_nni_rates', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'jc': jc, 'reps': a.reps,
+           'C': int(C), 'alpha': a.alpha, 'chunks': int(chunks), 'explicit_trees': int(n_x), 'neighbours': int(xc.shape[0])}
+    for k in t:
+        rec[k + '_wall_ms'], rec[k + '_device_ms'] = q[k]
+    rec.update({'device_ratio_nni_rates_over_plain_x_C': q['nni_rates'][1]['median'] / q['plain_x_C'][1]['median'],
+                'wall_ratio_nni_rates_over_plain_x_C': q['nni_rates'][0]['median'] / q['plain_x_C'][0]['median'],
+                'device_ratio_explicit_over_nni_rates_same_trees': q['explicit_subset'][1]['median'] / q['nni_rates_subset'][1]['median'],
+                'wall_ratio_explicit_over_nni_rates_same_trees': q['explicit_subset'][0]['median'] / q['nni_rates_subset'][0]['median'],
+                'launches': stats['nni_rates']['n_launches'], 'units': stats['nni_rates']['units'],
+                'units_per_s_device_nni_rates': stats['nni_rates']['units'] / (q['nni_rates'][1]['median'] * 1e-3),
+                'loglik_bit_equal': same, 'worst_relative_difference_to_explicit': worst,
+                'finite': bool(np.isfinite(delta[at[:, 0], at[:, 1], at[:, 2]]).all())})
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same and worst < 1e-9 else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -307,6 +395,8 @@ def main(argv=None):
     ap.add_argument('--nni', action='store_true', help='probe phylo_trees_nni against phylo_trees_loglik on the explicit neighbours, and phylo_trees_grad')
     ap.add_argument('--explicit_trees', type=int, default=512, help='with --nni: trees whose neighbours are built and scored explicitly (0: all)')
     a = ap.parse_args(argv)
+    if a.nni and a.rates > 0:
+        return nni_rates_probe(a)
     if a.nni:
         return nni_probe(a)
     if a.grad and a.rates > 0:
