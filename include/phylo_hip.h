@@ -408,6 +408,22 @@ int phylo_debug_reverse_plan(int N, int K, int K_local, int S, int world, int tw
  * phylo_sweep_begin refuses are refused with the same code and message.  tests/test_sweepplan_cpu.py restates the rules. */
 int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
                            uint32_t* mask, int32_t* launches);
+/* Test hooks of the chain form of a rank event (sweep_chain_form_of, phylo_sweep_plan.h; DESIGN.md sections 4 and 6b): the scan
+ * hands out every particle's ancestor and the list of adopted particles, the bookkeeping reads its ancestor, the adopted nodes are
+ * written from the list by item waves inside the bookkeeping's launch.  A decision of its own beside the plan: phylo_debug_sweep_plan's output does not depend on it.
+ * phylo_debug_sweep_chain, no GPU needed: the arguments of phylo_debug_sweep_plan, then PHYLO_SCAN_MULTI_MIN and
+ * PHYLO_SCAN_ANCESTORS as a context reads them (unset: 4096 and 1).  out[3]: taken (0: the rest is 0), item waves per group, the
+ * parts a node's sites are cut into.
+ * phylo_debug_sweep_chain_of: 1 if the rank events of the context's last sweep took the chain form, else 0.
+ * phylo_debug_scan_ancestors: the scan's tail alone, on G groups of Kg log-weights (host, [G][Kg]) with the groups' seeds for the
+ * resampling draws of rank event r_next: anc [G][Kg] (index inside the group), list [G][Kg] (the first cnt[g] entries of a row:
+ * the adopted particles, ascending; the rest -1) and cnt [G].  Needs a scan form that keeps the cdf in LDS (else PHYLO_ESTATE).
+ * tests/test_sweepchain_cpu.py restates the rule, tests/test_gpu_scan_ancestors.py the tail. */
+int phylo_debug_sweep_chain(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
+                            int multi_min, int scan_ancestors, int32_t* out);
+int phylo_debug_sweep_chain_of(phylo_ctx* ctx, int32_t* taken);
+int phylo_debug_scan_ancestors(phylo_ctx* ctx, const double* logw, int Kg, int G, const uint64_t* seeds, uint32_t r_next, int32_t* anc,
+                               int32_t* list, int32_t* cnt);
 /* Test hook, no GPU needed: the form the resampling scan takes for groups of Kg log-weights (sweep_scan_form_of, phylo_sweep_plan.h;
  * DESIGN.md section 6b): 0 the scan of several workgroups per group (pp_scan_multi_*), 1 pp_resample_scan<512>, 2
  * pp_resample_scan<1024>, 3 pk_resample_scan(_groups); -1 for Kg < 1.  ctx NULL: under PHYLO_SCAN_MULTI_MIN = multi_min; else under

@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_persist_plan", "phylo_debug_persist_of", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_sweep_chain", "phylo_debug_sweep_chain_of", "phylo_debug_scan_ancestors", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_persist_plan", "phylo_debug_persist_of", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -171,6 +171,21 @@ def debug_sweep_plan(N, K, S, K_local=None, G=1, M=1, world=1, transport=False, 
     out["mask"] = mask.value
     out["launches"] = list(launches)
     return out
+
+
+def debug_sweep_chain(N, K, S, K_local=None, G=1, M=1, world=1, transport=False, flags=0, switches=(), multi_min=4096, scan_ancestors=1):
+    """Whether the rank events of a sweep take the chain form (sweep_chain_form_of; no GPU needed): the arguments of debug_sweep_plan,
+    then PHYLO_SCAN_MULTI_MIN and PHYLO_SCAN_ANCESTORS as a context reads them.  A dict: 'taken', 'item_waves' (per group) and
+    'parts' (of a node's sites, one per item)."""
+    lib = load()
+    sw = sum(1 << SWEEP_PLAN_SWITCHES.index(name) for name in switches)
+    out = (C.c_int32 * 3)()
+    rc = lib.phylo_debug_sweep_chain(C.c_int(N), C.c_int(K), C.c_int(K if K_local is None else K_local), C.c_int(S), C.c_int(G), C.c_int(M),
+                                     C.c_int(world), C.c_int(int(transport)), C.c_uint32(flags), C.c_uint32(sw), C.c_int(multi_min),
+                                     C.c_int(scan_ancestors), out)
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return {"taken": bool(out[0]), "item_waves": out[1], "parts": out[2]}
 
 
 def debug_pack_leaf_codes(codes):
@@ -977,6 +992,29 @@ class Context:
         if rc < 0:
             raise PhyloError(rc, self._lib.phylo_last_error(self._h).decode())
         return SCAN_FORMS[rc]
+
+    def debug_sweep_chain(self):
+        """Did the rank events of this context's last sweep take the chain form (sweep_chain_form_of)?"""
+        taken = C.c_int32(0)
+        self._check(self._lib.phylo_debug_sweep_chain_of(self._h, C.byref(taken)))
+        return bool(taken.value)
+
+    def debug_scan_ancestors(self, logw, seeds, r_next):
+        """The tail of the resampling scan alone (pp_scan_ancestors) on log-weights [G][Kg] with the groups' seeds, for the draws of rank
+        event r_next: (anc [G][Kg] int32, list [G][Kg] int32 with -1 behind the first cnt[g] entries, cnt [G] int32)."""
+        w = np.ascontiguousarray(logw, dtype=np.float64)
+        if w.ndim != 2:
+            raise ValueError("logw must be [G][Kg]")
+        G, Kg = w.shape
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd.shape != (G,):
+            raise ValueError("one seed per group")
+        anc = np.full((G, Kg), -2, dtype=np.int32)
+        lst = np.full((G, Kg), -2, dtype=np.int32)
+        cnt = np.full(G, -2, dtype=np.int32)
+        self._check(self._lib.phylo_debug_scan_ancestors(self._h, _ptr(w), C.c_int(Kg), C.c_int(G), _ptr(sd), C.c_uint32(r_next), _ptr(anc),
+                                                         _ptr(lst), _ptr(cnt)))
+        return anc, lst, cnt
 
     def debug_persist(self):
         """The grid the last sweep of this context took as ONE launch: {'nt', 'Wg', 'm', 'lds'} (threads per workgroup, workgroups

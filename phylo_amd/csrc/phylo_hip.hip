@@ -55,6 +55,7 @@ struct sweep_run {                       // a sweep being issued rank event by r
     bool active = false;
     int a_done_r = -1;                     // rank event whose first half (sweep_step_a) has been issued
     sweep_plan plan{};                     // the form, decided by sweep_begin_impl (phylo_sweep_plan.h)
+    sweep_chain_form chain{};              // ... and the chain form of its rank events (sweep_chain_form_of), beside the plan
 };
 
 // Switches of DESIGN.md section 6b, read from the environment ONCE (phylo_create): none changes a result bit.  Each one serves a
@@ -69,6 +70,7 @@ struct env_switches {
     int persist_nt = 256;                // PHYLO_PERSIST_NT: threads per workgroup of the one-launch sweep (256 or 512)
     int remote_cache_cap = 0;            // PHYLO_REMOTE_CACHE_CAP: slots of the local cache of remote nodes (0 = 512 MB worth; tests lower it)
     int scan_multi_min = 4096;           // PHYLO_SCAN_MULTI_MIN: groups of more weights than this are scanned by several workgroups
+    int scan_ancestors = 1;              // PHYLO_SCAN_ANCESTORS: 0 = no chain form of a rank event (sweep_chain_form_of)
     int site_patterns = PK_PAT_AUTO;     // PHYLO_SITE_PATTERNS: 0 = never the pattern form of the merge, force = wherever it is valid
     int trees_chunk = 0;                 // PHYLO_TREES_CHUNK: trees per chunk of phylo_trees_loglik (0 = what PT2_SCRATCH_BYTES holds; tests lower it)
     int rell_chunk = 0;                  // PHYLO_RELL_CHUNK: replicates per chunk of phylo_rell (0 = what PR_CHUNK_BYTES holds; tests lower it)
@@ -89,6 +91,7 @@ struct env_switches {
         { const char* e = getenv("PHYLO_REMOTE_CACHE_CAP"); remote_cache_cap = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_SITE_PATTERNS"); site_patterns = !e ? PK_PAT_AUTO : !strcmp(e, "force") ? PK_PAT_FORCE : atoi(e) == 0 ? PK_PAT_OFF : PK_PAT_AUTO; }
         { const char* e = getenv("PHYLO_SCAN_MULTI_MIN"); scan_multi_min = e ? atoi(e) : 4096; }
+        { const char* e = getenv("PHYLO_SCAN_ANCESTORS"); scan_ancestors = e ? atoi(e) : 1; }
         { const char* e = getenv("PHYLO_TREES_CHUNK"); trees_chunk = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_RELL_CHUNK"); rell_chunk = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_P2P"); no_p2p = e && atoi(e) == 0; }
@@ -169,6 +172,12 @@ struct phylo_ctx {
     int32_t* d_merges = nullptr;         // [(N-1)][Kloc][2]
     int64_t* d_anc = nullptr;            // [(N-2)][Kloc]
     uint64_t* d_cdf[2] = {nullptr, nullptr};   // [K], double-buffered across rank events
+    // the chain form of a rank event: what the scan of rank event r leaves for rank event r + 1 (every count is written by every
+    // scan that writes any: nothing to clear between rank events, sweeps or batch sizes)
+    int32_t* d_anc_next = nullptr;       // [K] ancestor of each particle, index inside its group
+    int32_t* d_adopt_list = nullptr;     // [K] the adopted particles of each group, ascending
+    int32_t* d_adopt_cnt = nullptr;      // [PK_MAX_GROUPS]
+    int last_chain = 0;                  // the last sweep's rank events took the chain form (phylo_debug_sweep_chain_of)
     unsigned int* d_counter = nullptr;   // [1] timeout word of the bounded waits between workgroups ([0] unused)
     const double** d_pool_ptrs = nullptr; // [world] pool base of every rank (peer mappings)
     // sharded: remote nodes merged by this rank, fetched once per sweep (pk_pull_remote_children)
@@ -419,7 +428,7 @@ void free_sweep_state(phylo_ctx* c) {
     c->d_tilev = nullptr;
     void* ptrs[] = {c->d_pool, c->d_nodell, c->d_bl, c->d_br, c->d_Pmat, c->d_logw, c->d_ll, c->d_aux, c->d_lse, c->d_group_seeds,
                     c->d_tables, (void*)c->d_tab_ptrs, c->d_child, c->d_merges, c->d_anc,
-                    c->d_cdf[0], c->d_cdf[1], c->d_counter, (void*)c->d_pool_ptrs, c->d_mark, c->d_sync, c->d_mirror, c->d_cache, c->d_rec};
+                    c->d_cdf[0], c->d_cdf[1], c->d_anc_next, c->d_adopt_list, c->d_adopt_cnt, c->d_counter, (void*)c->d_pool_ptrs, c->d_mark, c->d_sync, c->d_mirror, c->d_cache, c->d_rec};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->d_pool = c->d_nodell = c->d_bl = c->d_br = c->d_Pmat = c->d_logw = c->d_ll = c->d_aux = c->d_lse = nullptr;
@@ -428,6 +437,7 @@ void free_sweep_state(phylo_ctx* c) {
     c->d_roots[0] = c->d_roots[1] = c->d_cnt[0] = c->d_cnt[1] = c->d_child = c->d_merges = nullptr;
     c->d_anc = nullptr;
     c->d_cdf[0] = c->d_cdf[1] = nullptr;
+    c->d_anc_next = c->d_adopt_list = c->d_adopt_cnt = nullptr;
     c->d_counter = nullptr;
     c->d_rootll[0] = c->d_rootll[1] = nullptr;
     c->d_tables = nullptr;
@@ -496,6 +506,12 @@ int alloc_sweep_state(phylo_ctx* c) {
     CHK(dalloc(c, &c->d_anc, (R > 0 ? R - 1 : 0) * Kl));
     CHK(dalloc(c, &c->d_cdf[0], K));
     CHK(dalloc(c, &c->d_cdf[1], K));
+    CHK(dalloc(c, &c->d_anc_next, K));
+    CHK(dalloc(c, &c->d_adopt_list, K));
+    CHK(dalloc(c, &c->d_adopt_cnt, (size_t)PK_MAX_GROUPS));
+    HIPCHK(c, hipMemset(c->d_anc_next, 0, K * 4));         // (indices: never read before a scan wrote them, and in range even so)
+    HIPCHK(c, hipMemset(c->d_adopt_list, 0, K * 4));
+    HIPCHK(c, hipMemset(c->d_adopt_cnt, 0, (size_t)PK_MAX_GROUPS * 4));
     CHK(dalloc(c, &c->d_counter, ((size_t)N + 3) & ~(size_t)3));
     HIPCHK(c, hipMemset(c->d_counter, 0, (((size_t)N + 3) & ~(size_t)3) * sizeof(unsigned int)));
     CHK(dalloc(c, &c->d_pool_ptrs, (size_t)c->world));
@@ -648,8 +664,13 @@ static const sweep_limits k_sweep_limits = sweep_limits_of();
 // group above PHYLO_SCAN_MULTI_MIN weights (three launches); else one workgroup per group, with the cdf in LDS by 512 threads up to
 // 4096 weights and by 1024 threads up to PP_SCAN_KERNEL_MAX_KG (phylo_persist.h), and beyond that staged in the cdf buffer itself
 // (pk_resample_scan(_groups), phylo_kernels.h).
-int launch_scan(phylo_ctx* c, const double* logw, int Kg, int G, uint64_t* cdf, double* lse, int lse_stride, int logz_R = 0) {
+// `anc` (the chain form of a rank event; the LDS forms alone): the scan also writes the resampling outcome (pp_scan_ancestors).
+int launch_scan(phylo_ctx* c, const double* logw, int Kg, int G, uint64_t* cdf, double* lse, int lse_stride, int logz_R = 0,
+                const pp_anc_out* anc = nullptr) {
+    const pp_anc_out ao = anc ? *anc : pp_anc_out{};
     const sweep_scan_form form = sweep_scan_form_of(Kg, c->env.scan_multi_min, cdf || lse, k_sweep_limits);
+    if (ao.anc && (!cdf || logz_R > 0 || (form != SCAN_LDS_512 && form != SCAN_LDS_1024)))
+        return fail(c, PHYLO_ESTATE, "launch_scan: the resampling outcome needs a cdf and a scan that holds it in LDS (Kg = %d)", Kg);
     if (form == SCAN_MULTI) {
         pp_scan_multi_args a{};
         a.logw = logw; a.Kg = Kg; a.B = (Kg + PP_SCAN_TILE - 1) / PP_SCAN_TILE;
@@ -668,16 +689,26 @@ int launch_scan(phylo_ctx* c, const double* logw, int Kg, int G, uint64_t* cdf, 
         return launch_check(c, "pp_scan_multi_cdf");
     }
     if (form == SCAN_LDS_512) {
-        hipLaunchKernelGGL(pp_resample_scan<512>, dim3(G), dim3(512), pp_resample_scan_lds(Kg), c->stream, logw, Kg, cdf, lse, lse_stride, logz_R);
+        if (ao.anc) hipLaunchKernelGGL(pp_resample_scan_anc<512>, dim3(G), dim3(512), pp_resample_scan_lds(Kg, true), c->stream, logw, Kg, cdf, lse, lse_stride, ao);
+        else hipLaunchKernelGGL(pp_resample_scan<512>, dim3(G), dim3(512), pp_resample_scan_lds(Kg), c->stream, logw, Kg, cdf, lse, lse_stride, logz_R);
         return launch_check(c, "pp_resample_scan");
     }
     if (form == SCAN_LDS_1024) {
-        const size_t lds = pp_resample_scan_lds(Kg);
-        static bool raised = false;                        // (beyond the 64 KB every kernel may ask for: say so once, like dev_lists_adopters)
-        if (lds > 65536 && !raised) {
+        const size_t lds = pp_resample_scan_lds(Kg, ao.anc != nullptr);
+        static bool raised = false, raised_anc = false;                        // (beyond the 64 KB every kernel may ask for: say so once, like dev_lists_adopters)
+        if (lds > 65536 && !raised && !ao.anc) {
             HIPCHK(c, hipFuncSetAttribute((const void*)pp_resample_scan<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)pp_resample_scan_lds(PP_SCAN_KERNEL_MAX_KG)));
             raised = true;
+        }
+        if (ao.anc) {
+            if (lds > 65536 && !raised_anc) {
+                HIPCHK(c, hipFuncSetAttribute((const void*)pp_resample_scan_anc<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)pp_resample_scan_lds(PP_SCAN_KERNEL_MAX_KG, true)));
+                raised_anc = true;
+            }
+            hipLaunchKernelGGL(pp_resample_scan_anc<1024>, dim3(G), dim3(1024), lds, c->stream, logw, Kg, cdf, lse, lse_stride, ao);
+            return launch_check(c, "pp_resample_scan_anc");
         }
         hipLaunchKernelGGL(pp_resample_scan<1024>, dim3(G), dim3(1024), lds, c->stream, logw, Kg, cdf, lse, lse_stride, logz_R);
         return launch_check(c, "pp_resample_scan");
@@ -2086,6 +2117,8 @@ static int sweep_begin_impl(phylo_ctx* c, uint64_t seed, uint32_t flags, int M, 
     c->run = sweep_run{};
     c->run.seed = seed; c->run.flags = flags; c->run.M = M;
     c->run.plan = p;
+    c->run.chain = sweep_chain_form_of(p, c->S, c->env.scan_multi_min, c->env.scan_ancestors, k_sweep_limits);
+    c->last_chain = c->run.chain.taken ? 1 : 0;
     c->run.launches = sweep_plan_launches(p, -1);
     c->run.active = true;
     c->last_persistent = false;
@@ -2201,6 +2234,7 @@ static int sweep_persistent(phylo_ctx* c, uint64_t seed, uint32_t flags, const u
     c->pctr_base += (unsigned long long)R * Wg;
     sweep_publish(c, true, false, G, false, 0, 1, (double)K * S * R);      // lazy: only adopted nodes are in the pool
     c->last_persistent = true;
+    c->last_chain = 0;
     c->last_pp_nt = c->env.persist_nt; c->last_pp_Wg = Wg; c->last_pp_m = m; c->last_pp_lds = lds;
     return PHYLO_OK;
 }
@@ -2300,6 +2334,10 @@ static pk_rank_args rank_args(const phylo_ctx* c, int r) {
     b.rec = p.use_rec ? c->d_rec : nullptr;
     b.lazy = p.lazy ? 1 : 0; b.mark = c->d_mark; b.child_all = c->d_child; b.Pmat_all = c->d_Pmat;
     b.T = c->site_tile; b.ntiles = c->ntiles; b.tilev = c->d_tilev;
+    if (c->run.chain.taken && r > 0) {
+        b.anc_in = c->d_anc_next; b.adopt_list = c->d_adopt_list; b.adopt_cnt = c->d_adopt_cnt;
+        b.item_waves = c->run.chain.item_waves; b.item_parts = c->run.chain.parts;
+    }
     return b;
 }
 
@@ -2309,6 +2347,7 @@ static pk_rank_args rank_args(const phylo_ctx* c, int r) {
 static int step_materialize(phylo_ctx* c, const pk_rank_args& b) {
     const sweep_plan& p = c->run.plan;
     const int Kl = c->Kloc, S = c->S;
+    if (c->run.chain.taken) return PHYLO_OK;               // the chain form: written from the scan's list inside the bookkeeping's launch
     if (p.mat_by_draws) {
         const int grouped = p.mat_draws_grouped ? 1 : 0;
         hipLaunchKernelGGL(pk_materialize_by_draws, dim3(grouped ? Kl / PK_MAT_GROUP : Kl), dim3(PK_COLS), 0, c->stream, b, grouped);
@@ -2406,6 +2445,19 @@ static int step_book(phylo_ctx* c, const pk_rank_args& b) {
         return launch_check(c, "pk_rank_book_mat");
     }
     const int per = 64 / (w > 0 ? w : 64);                                       // particles per wave
+    const sweep_chain_form& ch = c->run.chain;
+    if (ch.taken) {                                        // the ancestors from the scan; the item waves of the adopted nodes lead the grid
+        const int items = b.r > 0 ? p.G * ch.item_waves : 0;
+        const dim3 grid(items + cdiv(K, per));
+        switch (w) {
+        case 8: hipLaunchKernelGGL(pk_rank_book_chain<8>, grid, dim3(64), lds * per, c->stream, b, items); break;
+        case 16: hipLaunchKernelGGL(pk_rank_book_chain<16>, grid, dim3(64), lds * per, c->stream, b, items); break;
+        case 32: hipLaunchKernelGGL(pk_rank_book_chain<32>, grid, dim3(64), lds * per, c->stream, b, items); break;
+        case 64: hipLaunchKernelGGL(pk_rank_book_chain<64>, grid, dim3(64), lds * per, c->stream, b, items); break;
+        default: return fail(c, PHYLO_ESTATE, "step_book: no pk_rank_book_chain of %d lanes", w);
+        }
+        return launch_check(c, "pk_rank_book_chain");
+    }
     const dim3 grid(cdiv(p.local_book ? c->Kloc : K, per));
     switch (w) {
     case 8: hipLaunchKernelGGL(pk_rank_book_packed<8>, grid, dim3(64), lds * per, c->stream, b); break;
@@ -2479,8 +2531,13 @@ static int step_fix_rootll(phylo_ctx* c, int r) {
 static int step_scan(phylo_ctx* c, int r) {
     const sweep_plan& p = c->run.plan;
     const bool last = r + 1 == p.R;
+    pp_anc_out ao{};
+    if (c->run.chain.taken && !last) {                     // the resampling outcome of rank event r + 1
+        ao.anc = c->d_anc_next; ao.list = c->d_adopt_list; ao.cnt = c->d_adopt_cnt;
+        ao.group_seeds = p.G > 1 ? c->d_group_seeds : nullptr; ao.seed = c->run.seed; ao.r_next = (uint32_t)(r + 1);
+    }
     return launch_scan(c, (const double*)(c->d_logw + (size_t)r * c->K), p.Kg, p.G, last ? (uint64_t*)nullptr : c->d_cdf[(r & 1) ^ 1],
-                       c->d_lse + r, p.lse_stride, (last && p.fold_logz) ? p.R : 0);
+                       c->d_lse + r, p.lse_stride, (last && p.fold_logz) ? p.R : 0, ao.anc ? &ao : nullptr);
 }
 
 // phase 0: the whole rank event; 1: up to and including the merge; 2: what follows the all-gather of the rank
@@ -3629,6 +3686,56 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
     const sweep_plan p = sweep_plan_form(f, k_sweep_limits);
     *mask = sweep_plan_mask(p);
     for (int r = -1; r <= p.R; ++r) launches[r + 1] = sweep_plan_launches(p, r);
+    return PHYLO_OK;
+}
+
+int phylo_debug_sweep_chain(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
+                            int multi_min, int scan_ancestors, int32_t* out) {
+    if (N < 2 || N > PK_MAX_TAXA || K < 1 || K_local < 1 || K_local > K || S < 1 || world < 1 || !out)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_sweep_chain: bad arguments");
+    sweep_facts f{};
+    f.N = N; f.K = K; f.Kloc = K_local; f.S = S; f.G = G; f.M = M; f.world = world;
+    f.ntiles = (S + pm_site_tile(S) - 1) / pm_site_tile(S);
+    f.transport = transport != 0;
+    sweep_facts_flags(f, flags);
+    f.env_eager_nodes = switches & 1; f.env_rehearse_sharded = switches & 2; f.env_replicated_book = switches & 4;
+    f.jc = switches & 8; f.coded_leaves = switches & 16; f.device_exchange = switches & 32;
+    char why[160];
+    if (sweep_refuses_batch(f, k_sweep_limits, why, sizeof why) || sweep_refuses_form(f, k_sweep_limits, why, sizeof why))
+        return fail(nullptr, PHYLO_EINVAL, "%s", why);
+    const sweep_chain_form ch = sweep_chain_form_of(sweep_plan_form(f, k_sweep_limits), S, multi_min, scan_ancestors, k_sweep_limits);
+    out[0] = ch.taken ? 1 : 0; out[1] = ch.item_waves; out[2] = ch.parts;
+    return PHYLO_OK;
+}
+
+int phylo_debug_sweep_chain_of(phylo_ctx* c, int32_t* taken) {
+    if (!c || !taken) return fail(c, PHYLO_EINVAL, "phylo_debug_sweep_chain_of: NULL argument");
+    *taken = c->last_chain;
+    return PHYLO_OK;
+}
+
+int phylo_debug_scan_ancestors(phylo_ctx* c, const double* logw, int Kg, int G, const uint64_t* seeds, uint32_t r_next, int32_t* anc,
+                               int32_t* list, int32_t* cnt) {
+    CHK(bind(c));
+    if (!logw || !seeds || !anc || !list || !cnt || Kg < 1 || G < 1 || G > PK_MAX_GROUPS)
+        return fail(c, PHYLO_EINVAL, "phylo_debug_scan_ancestors: bad arguments");
+    const size_t K = (size_t)Kg * G;
+    void *dw, *dcdf, *dout, *dseed;
+    CHK(scratch_get(c, 0, K * 8, &dw));
+    CHK(scratch_get(c, 1, K * 8, &dcdf));
+    CHK(scratch_get(c, 2, (2 * K + (size_t)G) * 4, &dout));
+    CHK(scratch_get(c, 3, (size_t)G * 8, &dseed));
+    HIPCHK(c, hipMemcpyAsync(dw, logw, K * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dseed, seeds, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dout, 0xff, (2 * K + (size_t)G) * 4, c->stream));      // (what the scan does not write shows as -1)
+    pp_anc_out ao{};
+    ao.anc = (int32_t*)dout; ao.list = ao.anc + K; ao.cnt = ao.list + K;
+    ao.group_seeds = (const uint64_t*)dseed; ao.r_next = r_next;
+    CHK(launch_scan(c, (const double*)dw, Kg, G, (uint64_t*)dcdf, (double*)nullptr, 0, 0, &ao));
+    HIPCHK(c, hipMemcpyAsync(anc, ao.anc, K * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(list, ao.list, K * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt, ao.cnt, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PHYLO_OK;
 }
 

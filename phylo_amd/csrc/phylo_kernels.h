@@ -680,6 +680,11 @@ struct pk_rank_args {
     int T, ntiles;
     double* tilev;                                        // [Kloc][ntiles] or NULL (ntiles == 1)
     unsigned long long* rec;                              // [Kloc][PK_REC] merge records (one rank, plain proposal) or NULL
+    // the chain form of a rank event (phylo_sweep_plan.h), r > 0: what the scan of rank event r - 1 left (pp_scan_ancestors)
+    const int32_t* anc_in;                                // [K] ancestor of particle kg, index inside its group
+    const int32_t* adopt_list;                            // [K] group g's adopted particles at [g Kg, g Kg + adopt_cnt[g]), ascending
+    const int32_t* adopt_cnt;                             // [G]
+    int item_waves, item_parts;                           // pk_mat_listed: waves per group, parts of a node's sites
 };
 
 // LDS carve of the bookkeeping prologue (arrays of length N rounded up to a multiple of 4)
@@ -788,7 +793,9 @@ __device__ __forceinline__ int pk_cdf_search_group(const uint64_t* cdf, int K, u
 // Dependent global round trips: {cdf total + coarse probes, branch history, ldf table} -> {fine probes}
 // -> {ancestor's table rows, its log-likelihood}; everything after that runs out of LDS.
 // KEY_LOOP: the particle may have more pair-key blocks than its group has lanes to spare (see below).
-template <int LP, bool KEY_LOOP>
+// ANC_IN (the chain form of a rank event): the ancestor is read from a.anc_in, which the previous rank event's scan wrote, in the
+// place of the resampling draw and the index search -- one round trip for the search's two to four, and no lane draws for it.
+template <int LP, bool KEY_LOOP, bool ANC_IN = false>
 __device__ __forceinline__ void pk_book_packed(const pk_rank_args& a, int kg, bool local, const pk_book_lds& L, int sl, int lane) {
     const int n = a.n, N = a.N, k = kg - a.k0;
     const int grp = a.group_seeds ? kg / a.Kg : 0;
@@ -808,23 +815,29 @@ __device__ __forceinline__ void pk_book_packed(const pk_rank_args& a, int kg, bo
         // to 64 taxa (nb <= LP / 2); a wave per particle meets more blocks at n >= 253 root slots and then strides over them.
         const int nb = (n + 3) / 4;
         uint64_t Rdraw;
+        if (ANC_IN) Rdraw = 0;                             // (not drawn: the ancestor is read)
         if (KEY_LOOP && nb > LP - 1) {
             #pragma unroll 1
             for (int b = sl; b < nb; b += LP) {
                 const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, PM_STREAM_PAIR, (uint32_t)b, seed);
                 L.key[b * 4 + 0] = x.x; L.key[b * 4 + 1] = x.y; L.key[b * 4 + 2] = x.z; L.key[b * 4 + 3] = x.w;
             }
-            const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, PM_STREAM_RESAMPLE, 0u, seed);
-            Rdraw = ((uint64_t)x.y << 32) | x.x;
+            if (!ANC_IN) {
+                const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, PM_STREAM_RESAMPLE, 0u, seed);
+                Rdraw = ((uint64_t)x.y << 32) | x.x;
+            }
         } else {
-            const bool res = sl == LP - 1;
+            const bool res = !ANC_IN && sl == LP - 1;      // (ANC_IN: no lane draws for the resampling, the select folds away)
             const pm_u32x4 x = pm_philox4x32(kin, (uint32_t)a.r, res ? PM_STREAM_RESAMPLE : PM_STREAM_PAIR, res ? 0u : (uint32_t)sl, seed);
             if (sl < nb) { L.key[sl * 4 + 0] = x.x; L.key[sl * 4 + 1] = x.y; L.key[sl * 4 + 2] = x.z; L.key[sl * 4 + 3] = x.w; }
-            const int src = (lane & ~(LP - 1)) + LP - 1;
-            Rdraw = ((uint64_t)(uint32_t)__shfl((int)x.y, src, 64) << 32) | (uint32_t)__shfl((int)x.x, src, 64);
+            if (!ANC_IN) {
+                const int src = (lane & ~(LP - 1)) + LP - 1;
+                Rdraw = ((uint64_t)(uint32_t)__shfl((int)x.y, src, 64) << 32) | (uint32_t)__shfl((int)x.x, src, 64);
+            }
         }
         int anc = kg;
-        if (a.r > 0) anc = gbase + pk_cdf_search_group<LP>(a.cdf + gbase, a.group_seeds ? a.Kg : a.K, Rdraw, sl, lane);
+        if (ANC_IN) { if (a.r > 0) anc = gbase + a.anc_in[kg]; }
+        else if (a.r > 0) anc = gbase + pk_cdf_search_group<LP>(a.cdf + gbase, a.group_seeds ? a.Kg : a.K, Rdraw, sl, lane);
         const int32_t* ro = a.roots_old + (size_t)anc * N;
         const int32_t* co = a.cnt_old + (size_t)anc * N;
         const double* rl = a.rootll_old + (size_t)anc * N;
@@ -1251,6 +1264,85 @@ __device__ __forceinline__ const double* pk_node_ptr(const pk_rank_args& a, int 
         if (slot > 0) return a.cache + (size_t)(slot - 1) * node_sz;
     }
     return a.pool_ptrs[owner] + ((size_t)rho * a.Kloc + (kap - owner * a.Kloc)) * node_sz;
+}
+
+// ---- The chain form of a rank event (phylo_sweep_plan.h: sweep_chain_form_of; one rank, plain proposal, lazy nodes) --------------
+// The adopted nodes of rank event r - 1 from the list the scan left (pp_scan_ancestors), a wave per item = (list entry, part of
+// the sites).  Nothing here waits for the bookkeeping: the list was ready before the launch.  Wave w of the W waves of group g
+// strides over the group's cnt x Q items (Q parts) and leaves after one scalar load when it has none.  The entry, the child ids and the
+// node's two matrices are wave-uniform and were written by earlier launches: scalar loads through the constant address space,
+// ids and matrices requested together; two rows per lane in flight (the waves share the bookkeeping's kernel, whose registers
+// the rows must not raise: with four, pk_rank_book_chain<8> would take 95 registers for pk_rank_book_packed<8>'s 66 -- the rule
+// cuts a node into up to eight parts instead).  Every part stores the node's mark behind its rows (a
+// plain store of 1, like the bookkeeping's: d_mark keeps meaning "the node is in the pool").  Same operations per row as
+// pk_materialize_node: same bits.
+typedef __attribute__((address_space(4))) const int32_t pk_ci32;
+#define PK_ITEM_ROWS 2
+__device__ __forceinline__ void pk_mat_listed(const pk_rank_args& a, int wg, int lane) {
+    typedef __attribute__((address_space(4))) const double cdbl;
+    constexpr int U = PK_ITEM_ROWS;
+    const int W = a.item_waves, Q = a.item_parts, rho = a.r - 1;
+    const int g = __builtin_amdgcn_readfirstlane(wg / W), w = wg - g * W;
+    const int n = ((pk_ci32*)a.adopt_cnt)[g] * Q;
+    if (w >= n) return;
+    pk_ci32* list = (pk_ci32*)(a.adopt_list + (size_t)g * a.Kg);
+    const size_t node_sz = (size_t)a.S * 4;
+    const int qlen = (a.S + Q - 1) / Q;
+    for (int item = w; item < n; item += W) {              // wave-uniform
+        const int e = __builtin_amdgcn_readfirstlane(item / Q), q = item - e * Q;
+        const int kap = g * a.Kg + list[e];
+        const size_t slot = (size_t)rho * a.K + kap;       // (one rank: local slot == global particle)
+        pk_ci32* ch = (pk_ci32*)(a.child_all + slot * 2);
+        const cdbl* P = (const cdbl*)(a.Pmat_all + slot * 32);
+        const int c0 = ch[0], c1 = ch[1];
+        double Pl[16], Pr[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) { Pl[j] = P[j]; Pr[j] = P[16 + j]; }
+        const double* Lp = c0 < a.N ? a.leaves + (size_t)c0 * node_sz : a.pool + (size_t)(c0 - a.N) * node_sz;
+        const double* Rp = c1 < a.N ? a.leaves + (size_t)c1 * node_sz : a.pool + (size_t)(c1 - a.N) * node_sz;
+        double* out = a.pool + slot * node_sz;
+        const int s0 = q * qlen, s1 = s0 + qlen < a.S ? s0 + qlen : a.S;
+        for (int s = s0 + lane; s < s1; s += U * 64) {
+            double Lv[U][4], Rv[U][4];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int su = s + u * 64 < s1 ? s + u * 64 : s;               // (a row past the end re-reads this lane's first)
+                pk_load4(Lp + (size_t)su * 4, Lv[u]);
+                pk_load4(Rp + (size_t)su * 4, Rv[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                double o[4];
+                pk_merge_site(Lv[u], Rv[u], Pl, Pr, o);
+                if (s + u * 64 < s1) pk_store4(out + (size_t)(s + u * 64) * 4, o);
+            }
+        }
+        if (lane == 0) a.mark[(size_t)rho * a.K + kap] = 1u;
+    }
+}
+
+// The chain form's bookkeeping: pk_rank_book_packed with the ancestor read from a.anc_in and no mark store (the item waves store
+// the marks).  The adopted nodes share the launch -- workgroups [0, item_wgs) are the item waves, FIRST in the grid
+// (they start their chains of round trips while the bookkeeping's waves are still being dispatched), the bookkeeping behind them.
+// The two parts touch no common address: the items read rows r - 1 of child_all / Pmat_all and write pool rows and marks of rank
+// event r - 1, the bookkeeping writes row r and reads neither pool nor marks.
+// Rank event 0 has no item waves (item_wgs = 0).
+template <int LP>
+__global__ __launch_bounds__(64, LP == 64 ? 5 : 1) void pk_rank_book_chain(const pk_rank_args a, int item_wgs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if ((int)blockIdx.x < item_wgs) {
+        pk_mat_listed(a, (int)blockIdx.x, (int)threadIdx.x);
+        return;
+    }
+    const int lane = threadIdx.x, sub = lane / LP, sl = lane & (LP - 1);
+    const int count = a.tab_ptrs ? a.Kloc : a.K;
+    int idx = ((int)blockIdx.x - item_wgs) * (64 / LP) + sub;
+    if (idx >= count) idx = count - 1;          // a spare group repeats the last particle: identical values, identical writes
+    const int kg = a.tab_ptrs ? a.k0 + idx : idx;
+    const pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
+    const bool local = kg >= a.k0 && kg < a.k0 + a.Kloc;
+    pk_book_packed<LP, LP == 64, true>(a, kg, local, L, sl, lane);
+    pk_book_tail<LP>(a, kg, local, false, a.mirror && a.r > 0, L, sl, lane);
 }
 
 // Leaf children whose rows are one-hot / all-ones (the reference's encoding, runner.py:83-96) are read as a

@@ -312,6 +312,83 @@ __device__ __forceinline__ void pp_scan(const double* logw, int Kg, unsigned lon
     }
 }
 
+// ---- The resampling OUTCOME of the next rank event, behind the cdf in LDS (the chain form of a rank event, phylo_sweep_plan.h).
+//      The scan's workgroup holds the whole cdf and sits on the chain of dependent launches with an otherwise idle GPU: it also
+//      evaluates every particle's resampling draw of rank event r_next -- the counter, stream and seed of pk_book_packed -- finds
+//      the ancestor by a binary search in LDS (the first i with cdf[i] > mulhi64(draw, total): pk_cdf_search_group's answer) and
+//      writes the ascending list of the adopted particles, so that the bookkeeping needs no search and the writes of the adopted
+//      nodes need no marks.  Integers only: same bits as the search.  Called by pp_resample_scan_anc alone (pp_scan is shared
+//      with pp_sweep, whose code must not move).
+struct pp_anc_out {
+    int32_t* anc;                      // [G][Kg] ancestor of particle k, index inside the group; NULL: no tail
+    int32_t* list;                     // [G][Kg] the adopted particles of the group, ascending, cnt[g] entries
+    int32_t* cnt;                      // [G]
+    const uint64_t* group_seeds;       // [G] or NULL (use `seed`)
+    uint64_t seed;
+    uint32_t r_next;                   // the rank event whose resampling this is (the scan's own + 1)
+};
+template <int NT>
+__device__ __forceinline__ void pp_scan_ancestors(const unsigned long long* cdf, int Kg, int g, const pp_anc_out& o, unsigned char* flag,
+                                                  pp_scan_lds* sh) {
+    constexpr int NW = NT / 64, ME = NT == 512 ? 8 : 16;   // ME: 64-lane rows of a wave's span (Kg <= 4096 / <= PP_SCAN_KERNEL_MAX_KG)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int k = tid; k < Kg; k += NT) flag[k] = 0;
+    __syncthreads();                                       // the cdf is whole, the flags are clear
+    const uint64_t seed = o.group_seeds ? o.group_seeds[g] : o.seed;
+    const unsigned long long total = cdf[Kg - 1];
+    int32_t* anc = o.anc + (size_t)g * Kg;
+    for (int base = 0; base < Kg; base += 4 * NT) {        // four searches per thread side by side: a fixed trip count, no branch
+        unsigned long long thr[4];
+        int lo[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = base + tid + NT * j;
+            const pm_u32x4 x = pm_philox4x32((uint32_t)(k < Kg ? k : Kg - 1), o.r_next, PM_STREAM_RESAMPLE, 0u, seed);
+            thr[j] = pm_mulhi64(((uint64_t)x.y << 32) | x.x, total);
+            lo[j] = 0;
+        }
+        for (int n = Kg; n > 1;) {                         // invariant: the answer lies in [lo, lo + n)
+            const int half = n >> 1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) lo[j] = cdf[lo[j] + half - 1] > thr[j] ? lo[j] : lo[j] + half;
+            n -= half;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = base + tid + NT * j;
+            if (k < Kg) { anc[k] = lo[j]; flag[lo[j]] = 1; }   // (a plain store: every adopter writes the same value)
+        }
+    }
+    __syncthreads();
+    // the flags in ascending order: wave wv owns the indices [wv E 64, (wv + 1) E 64), a ballot per row of 64, the waves' counts
+    // through LDS -- no atomics, one order
+    const int E = (Kg + NT - 1) / NT;
+    unsigned long long b[ME];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < ME; ++j) {
+        const int i = (wv * E + j) * 64 + lane;
+        b[j] = __ballot(j < E && i < Kg && flag[i < Kg ? i : 0] != 0);
+        mine += __popcll(b[j]);
+    }
+    if (lane == 0) sh->u[wv] = (unsigned long long)mine;
+    __syncthreads();
+    int off = 0, all = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int u = (int)sh->u[i];
+        if (i < wv) off += u;
+        all += u;
+    }
+    int32_t* list = o.list + (size_t)g * Kg;
+#pragma unroll
+    for (int j = 0; j < ME; ++j) {
+        if ((b[j] >> lane) & 1ull) list[off + __popcll(b[j] & ((1ull << lane) - 1ull))] = (wv * E + j) * 64 + lane;
+        off += __popcll(b[j]);
+    }
+    if (tid == 0) o.cnt[g] = all;
+}
+
 // The same scan as a launch of its own (launches-per-rank-event path, phylo_resample, phylo_log_zsmc): one workgroup of 512
 // threads per group, cdf built in LDS and copied out.  Replaces pk_resample_scan(_groups) whenever the group fits LDS.
 // logz_R > 0: lse_out is element logz_R - 1 of a row of logz_R log-normalisers; their left-to-right sum (compute_log_ZSMC,
@@ -333,6 +410,22 @@ __global__ __launch_bounds__(NT) void pp_resample_scan(const double* logw, int K
     if (!cdf) return;
     __syncthreads();
     unsigned long long* out = reinterpret_cast<unsigned long long*>(cdf) + (size_t)g * Kg;
+    for (int k = threadIdx.x; k < Kg; k += NT) out[k] = lcdf[k];
+}
+// The scan of a rank event in the chain form: the same, then the resampling outcome (pp_scan_ancestors) behind the cdf in LDS, with
+// Kg flag bytes of LDS behind the cdf.  A kernel of its own: every other caller's scan keeps its code (a single sweep is a chain of
+// eleven such launches, and the longer argument list and code measured 0.5 % on it).  Never the last rank event's scan: a cdf is
+// always wanted, and the log-normalisers are not summed here.
+template <int NT>
+__global__ __launch_bounds__(NT) void pp_resample_scan_anc(const double* logw, int Kg, uint64_t* __restrict__ cdf, double* lse_out, int lse_stride,
+                                                           const pp_anc_out ao) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    pp_scan_lds* sh = reinterpret_cast<pp_scan_lds*>(smem);
+    unsigned long long* lcdf = reinterpret_cast<unsigned long long*>(smem + ((sizeof(pp_scan_lds) + 15) & ~(size_t)15));
+    const int g = blockIdx.x;
+    pp_scan<NT>(logw + (size_t)g * Kg, Kg, lcdf, lse_out ? lse_out + (size_t)g * lse_stride : (double*)nullptr, sh, true);
+    pp_scan_ancestors<NT>(lcdf, Kg, g, ao, reinterpret_cast<unsigned char*>(lcdf + Kg), sh);
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(cdf) + (size_t)g * Kg;     // (pp_scan_ancestors ends behind a barrier)
     for (int k = threadIdx.x; k < Kg; k += NT) out[k] = lcdf[k];
 }
 // ---- The same scan by SEVERAL workgroups per group (large groups: the replicated scan of a sharded sweep -- 8 GPUs x 2048 particles
@@ -485,7 +578,9 @@ __global__ __launch_bounds__(512) void pp_scan_multi_cdf(const pp_scan_multi_arg
         if (lo + j < a.Kg) out[lo + j] = run + e[j];
 }
 #define PP_SCAN_KERNEL_MAX_KG 16384    // 128 KiB of cdf in LDS, 1024 threads: the replicated scan of 8 GPUs x 2048 particles
-__host__ inline size_t pp_resample_scan_lds(int Kg) { return ((sizeof(pp_scan_lds) + 15) & ~(size_t)15) + (size_t)Kg * 8; }
+__host__ inline size_t pp_resample_scan_lds(int Kg, bool ancestors = false) {      // (ancestors: a flag byte per particle behind the cdf)
+    return ((sizeof(pp_scan_lds) + 15) & ~(size_t)15) + (size_t)Kg * 8 + (ancestors ? ((size_t)Kg + 15) & ~(size_t)15 : 0);
+}
 
 // ---- part A of a particle's rank event, by ONE wave, BEFORE the wait (nothing here depends on the resampling): the pair
 //      pick of extend_partial_state (vcsmc.py:303-305: Gumbel top-2 restated on the keys, remaining slots by ascending key),

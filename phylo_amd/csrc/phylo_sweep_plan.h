@@ -197,11 +197,46 @@ inline sweep_scan_form sweep_scan_form_of(int Kg, int multi_min, bool wanted, co
     return SCAN_IN_PLACE;
 }
 
+// ---- the chain form of a rank event -------------------------------------------------------------------------
+// A rank event of a batched sweep is scan -> bookkeeping -> adopted nodes -> merge on one stream, and the three short launches are
+// latency chains.  Which ancestor a particle adopts, hence which nodes must be written, is known to the scan's workgroup (the whole
+// cdf is in its LDS): in the chain form the scan of rank event r also writes every particle's ancestor of rank event r + 1 and the
+// ascending list of the adopted particles of each group (pp_scan_ancestors); the bookkeeping reads its ancestor instead of searching
+// the cdf and stores no mark; and the adopted nodes are written from the list by item waves that LEAD the bookkeeping's grid, a wave
+// per (list entry, part of the node's sites), which also store the marks (pk_rank_book_chain, pk_mat_listed): they no longer wait
+// for the bookkeeping, they run beside it.  Same bits as the launches it replaces (tests/test_gpu_chain_forms.py).
+// The rule is a decision of its own beside the plan: sweep_plan, its mask and its launch counts do not know it.
+struct sweep_chain_form {
+    bool taken;                        // false: the launches of the plan exactly (the other fields are 0)
+    int item_waves;                    // W: waves per group that walk the group's list
+    int parts;                         // the parts a node's sites are cut into, one per item
+};
+// `scan_ancestors`: PHYLO_SCAN_ANCESTORS as the context read it (0 = off; unset: 1).  `multi_min`: PHYLO_SCAN_MULTI_MIN likewise.
+inline sweep_chain_form sweep_chain_form_of(const sweep_plan& p, int S, int multi_min, int scan_ancestors, const sweep_limits& L) {
+    const sweep_chain_form no{};
+    if (scan_ancestors == 0) return no;
+    if (!(p.use_rec && p.mat_after_book)) return no;       // one rank, plain proposal, lazy nodes, the separate adopted-nodes launch
+    if (p.mat_barrier) return no;                          // a communicator is set: peers read these nodes, the launch and its barrier stay
+    if (p.R < 2) return no;                                // (no resampling at all)
+    const sweep_scan_form s = sweep_scan_form_of(p.Kg, multi_min, true, L);
+    if (s != SCAN_LDS_512 && s != SCAN_LDS_1024) return no;
+    sweep_chain_form f{};
+    f.taken = true;
+    // two rows per lane in flight (more would raise the registers of the bookkeeping that shares the kernel): a node is cut so that
+    // a part is ONE round trip of its wave where it can be, into at most eight; short rows need no cut
+    f.parts = (S + 127) / 128 < 8 ? (S + 127) / 128 : 8;
+    // few particles are adopted on real data (about 40 of 2048 at primate.p): 128 waves meet at most three items each there, and the
+    // waves without an item leave after one scalar load.  Many adopted nodes (flat weights): the waves stride over the list.
+    f.item_waves = p.Kg * f.parts < 128 ? p.Kg * f.parts : 128;
+    return f;
+}
+
 // What the driver counts into stats.n_launches: r = -1 the begin, 0 .. R-1 rank event r (sweep_step_a's half included), R the
 // finish.  This is the driver's count as it always was, which is not everywhere the number of kernels: a scan of several
 // workgroups per group counts 1 for its three launches, a twisted rank event counts 3 for adopt + draws, potentials and choose
 // even when pk_twist_potentials has no rows and is not launched, and pk_pair_hist and the kernels of the collectives are not
-// counted.  tests/test_gpu_sweep_forms.py pins the totals.
+// counted.  Where the chain form puts two stages into one launch (bookkeeping and adopted nodes), the count stays that of the
+// stages.  tests/test_gpu_sweep_forms.py pins the totals.
 inline int sweep_plan_launches(const sweep_plan& p, int r) {
     if (r < 0) return 1;                                   // pk_sweep_prologue, or pk_init_tables of the twisted proposal
     if (r >= p.R) return (p.fold_logz ? 0 : 1) + p.gather_launches;
