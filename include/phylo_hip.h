@@ -206,6 +206,27 @@ int phylo_trees_grad(phylo_ctx* ctx, int T, const int32_t* child, const double* 
 int phylo_trees_grad_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate,
                            const double* weight, int per_tree, const double* prior4, double* loglik_T, double* grad, double* curv,
                            double* drate_TxC, double* dweight_TxC, phylo_stats* perf);
+/* The derivatives of phylo_trees_loglik's log-likelihood with respect to the substitution model: along P
+ * directions in the space of generators (dirs_Px16, row-major 4 x 4 each, 1 <= P <= 16, every entry finite) and with respect to the
+ * root distribution.  Trees, prior, state rules and per-tree checks as phylo_trees_grad; one rate only.  With Q_eff the context's Q
+ * (under jc69_closed_form the generator 1/4, diagonal -3/4), t_b a branch's length and D_{p,b} = L(Q_eff t_b, dirs[p] t_b) the
+ * Frechet derivative of expm (one multiply per entry of either argument; D indexed like the branch's matrix; a zero length gives 0):
+ *   loglik_T[t]      bit for bit phylo_trees_loglik's value for the same tree, prior and site tile;
+ *   grad[t][i][side] (may be NULL) bit for bit phylo_trees_grad's grad;
+ *   dtheta_TxP[t][p] = sum_s sum_b (x_child . D_{p,b} . g_b) / L_s, the derivative of loglik_T[t] along dirs[p] at fixed lengths
+ *                      and prior (x_child, g_b and the order of the product as in phylo_trees_grad's L'_s, D in the place of M');
+ *   dprior_Tx4[t][j] (may be NULL) = sum_s x_root[s][j] / L_s, the partial derivative with respect to prior[j] at fixed Q.
+ * Fixed order of summation, no atomics: per lane and direction the terms of every operation (last to first), side and site step
+ * from +0.0, the 64 lanes by the wave's adjacent-pair tree once per (tree, tile), the tiles left to right.  A call repeats its own
+ * bits; chunking, the grid cap, a tree's place, the optional outputs and P itself (which other directions ride along) change
+ * none.  Against a restatement dtheta and dprior carry a tolerance, not a bit contract.  NaN rule: phylo_trees_grad's, on every
+ * entry of grad, dtheta and dprior of the tree.  perf (may be NULL): units = T S (N-1) (1 + P).
+ * Synchronous; a LOCAL call on a sharded context.  PHYLO_EINVAL before anything is queued for a bad tree, P outside 1 .. 16, a
+ * direction entry that is not finite, and for child, blen, dirs, loglik_T or dtheta == NULL.  Own scratch and events, released
+ * with the context; everything phylo_trees_grad leaves alone, and the scratch of its siblings, is left alone. */
+int phylo_trees_grad_model(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int P, const double* dirs_Px16,
+                           const double* prior4, double* loglik_T, double* grad, double* dtheta_TxP, double* dprior_Tx4,
+                           phylo_stats* perf);
 /* The NNI neighbourhood of every tree of a set, at the tree's current branch lengths: for T trees given as
  * phylo_trees_loglik takes them (same numbering, same checks, same state rules),
  *   loglik_T[t]        bit for bit phylo_trees_loglik's value for the same tree, prior and site tile;

@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_grad_model", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -590,6 +590,37 @@ class Context:
                                                C.byref(st)))
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         return (out, grad, curv) if want_curv else (out, grad)
+
+    def trees_grad_model(self, child, blen, dirs, prior=None, want_grad=False, want_prior=True):
+        """Derivatives of trees_loglik with respect to the substitution model (phylo_trees_grad_model): dirs [P][4][4] are P
+        directions in the space of generators (1 <= P <= 16; phylo_amd.modelfit.q_directions builds the twelve of the project's
+        row-softmax Q).  Returns (loglik [T], dtheta [T][P]), then grad [T][N-1][2] with want_grad (trees_grad's bits), then
+        dprior [T][4] with want_prior (the partial derivatives with respect to the root distribution at fixed Q;
+        phylo_amd.modelfit.chain_prior turns them into d / d y_station).  dtheta[t][p] is the derivative of loglik[t] along
+        dirs[p] at fixed lengths and prior; a column does not depend on which other directions ride in the call.  loglik is bit
+        for bit trees_loglik's; the NaN rule is trees_grad's.  self.last_trees_stats holds the call's stats.
+        phylo_amd.treeopt.optimize_model climbs with it."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        dirs = _f64(dirs)
+        if dirs.ndim == 2 and dirs.shape == (4, 4):
+            dirs = dirs[None]
+        if dirs.ndim != 3 or dirs.shape[1:] != (4, 4):
+            raise ValueError("dirs must be [P][4][4], got %r" % (dirs.shape,))
+        dirs = np.ascontiguousarray(dirs)
+        npd = dirs.shape[0]
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        out = np.empty(T)
+        dtheta = np.empty((T, npd))
+        grad = np.empty(blen.shape) if want_grad else None
+        dprior = np.empty((T, 4)) if want_prior else None
+        st = Stats()
+        self._check(self._lib.phylo_trees_grad_model(self._h, C.c_int(T), _ptr(child), _ptr(blen), C.c_int(npd), _ptr(dirs), _ptr(pr),
+                                                     _ptr(out), _ptr(grad), _ptr(dtheta), _ptr(dprior), C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return (out, dtheta) + ((grad,) if want_grad else ()) + ((dprior,) if want_prior else ())
 
     def trees_grad_rates(self, child, blen, rates, weights, prior=None, want_curv=False, want_params=False):
         """trees_grad under a mixture of C rate categories (phylo_trees_grad_rates): the derivatives of trees_loglik_rates'

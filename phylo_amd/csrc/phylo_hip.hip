@@ -33,6 +33,7 @@
 #include "phylo_treegrad_rates.h"
 #include "phylo_treenni.h"
 #include "phylo_treenni_rates.h"
+#include "phylo_treegrad_model.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -257,10 +258,10 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[20];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+    DevBuf scratch[21];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
                                          //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates;
                                          //  16: phylo_trees_grad's chunk and node stores; 17: phylo_trees_grad_rates's; 18: phylo_trees_nni's;
-                                         //  19: phylo_trees_nni_rates's)
+                                         //  19: phylo_trees_nni_rates's; 20: phylo_trees_grad_model's)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -280,6 +281,7 @@ struct phylo_ctx {
     hipEvent_t ev_tr0 = nullptr, ev_tr1 = nullptr;   // phylo_trees_grad_rates' own pair
     hipEvent_t ev_tn0 = nullptr, ev_tn1 = nullptr;   // phylo_trees_nni's own pair
     hipEvent_t ev_tm0 = nullptr, ev_tm1 = nullptr;   // phylo_trees_nni_rates' own pair
+    hipEvent_t ev_tq0 = nullptr, ev_tq1 = nullptr;   // phylo_trees_grad_model's own pair
 };
 
 namespace {
@@ -855,6 +857,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_tn1) (void)hipEventDestroy(c->ev_tn1);
     if (c->ev_tm0) (void)hipEventDestroy(c->ev_tm0);
     if (c->ev_tm1) (void)hipEventDestroy(c->ev_tm1);
+    if (c->ev_tq0) (void)hipEventDestroy(c->ev_tq0);
+    if (c->ev_tq1) (void)hipEventDestroy(c->ev_tq1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -1511,6 +1515,150 @@ int phylo_trees_grad(phylo_ctx* c, int T, const int32_t* child, const double* bl
         st.n_launches = launches;
         st.units = (double)T * S * R;
         st.alg_bytes = 96.0 * st.units;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
+// ---- derivatives along directions of the generator and with respect to the prior (phylo_treegrad_model.h) ----
+int phylo_trees_grad_model(phylo_ctx* c, int T, const int32_t* child, const double* blen, int P, const double* dirs_Px16, const double* prior4,
+                           double* loglik_T, double* grad, double* dtheta_TxP, double* dprior_Tx4, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_grad_model needs phylo_set_leaves and phylo_set_model first");
+    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    if (!child || !blen || !dirs_Px16 || !loglik_T || !dtheta_TxP)
+        return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: child, blen, dirs, loglik and dtheta must be given (NULL pointer)");
+    if (P < 1 || P > PTM_MAX_DIRS) return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: need 1 <= P <= %d directions (P=%d)", PTM_MAX_DIRS, P);
+    for (int i = 0; i < P * 16; ++i)
+        if (!std::isfinite(dirs_Px16[i]))
+            return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: direction %d, entry %d is not finite (%g)", i / 16, i % 16, dirs_Px16[i]);
+    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
+    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
+        int row = 0;
+        char msg[200];
+        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+    }
+    const bool coded = c->leaves_coded, want_grad = grad != nullptr;
+    ptm_plan pl;
+    if (ptm_make_plan(N, ntiles, T, P, coded, want_grad, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+        return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: no plan for N=%d, %d tiles, T=%d, P=%d", N, ntiles, T, P);
+    // From the deepest schedule there is, not a chunk's own, so that nothing is queued before it; with N <= 512, P <= 16 that is
+    // 56 KiB, so the refusal cannot fire today: it guards a larger PT2_MAX_DEPTH or PTM_MAX_DIRS (the arithmetic is in the sanitizer program)
+    if (ptm_lds_bytes(N, PT2_MAX_DEPTH, P, want_grad) > PTM_MAX_LDS)
+        return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: %zu bytes of LDS for a wave exceed %zu (N=%d, P=%d)",
+                    ptm_lds_bytes(N, PT2_MAX_DEPTH, P, want_grad), PTM_MAX_LDS, N, P);
+    const int chunk = pl.chunk, nm = pl.nm;
+    void* slab = nullptr;
+    CHK(scratch_get(c, 20, pl.total, &slab));
+    char* base = (char*)slab;
+    double* d_prior = (double*)(base + pl.o_prior);
+    double* d_dirs = (double*)(base + pl.o_dirs);
+    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
+    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
+    double* d_P = (double*)(base + pl.o_P);
+    double* d_D = (double*)(base + pl.o_D);
+    double* d_t = (double*)(base + pl.o_t);
+    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
+    double* d_tilev = (double*)(base + pl.o_tilev);
+    double* d_out = (double*)(base + pl.o_out);
+    double* d_dtile = want_grad ? (double*)(base + pl.o_dtile) : nullptr;
+    double* d_dout = want_grad ? (double*)(base + pl.o_dout) : nullptr;
+    double* d_mtile = (double*)(base + pl.o_mtile);
+    double* d_mout = (double*)(base + pl.o_mout);          // dtheta [n][P] | dprior [n][4]
+    if (!c->ev_tq0) {
+        HIPCHK(c, hipEventCreate(&c->ev_tq0));
+        HIPCHK(c, hipEventCreate(&c->ev_tq1));
+    }
+    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_dirs, dirs_Px16, (size_t)P * 128, hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
+    std::vector<double> ts((size_t)chunk * R * 2);
+    double ms_total = 0.0;
+    int launches = 0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int n = std::min(chunk, T - t0);
+        int depth = 1;
+        for (int t = 0; t < n; ++t) {
+            int32_t* o = ops.data() + (size_t)t * R * 4;
+            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
+            depth = std::max(depth, pt2_schedule(N, ch, o));
+            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
+                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
+            const double* b = blen + (size_t)(t0 + t) * R * 2;
+            double* tk = ts.data() + (size_t)t * R * 2;
+            for (int i = 0; i < R; ++i) {
+                tk[2 * i] = b[2 * o[4 * i + 3]];
+                tk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
+            }
+        }
+        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_tq0, c->stream));
+        const long n_mat = (long)n * R * 2;                 // M | M' packed by this chunk's count
+        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
+        CHK(launch_check(c, "pk_expm_batched"));
+        ++launches;
+        if (want_grad) {                                    // M'' is ptg_dmats' second output: it goes where D is built next
+            hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_P, n_mat,
+                               d_P + n_mat * 16, d_D);
+            CHK(launch_check(c, "ptg_dmats"));
+            ++launches;
+        }
+        hipLaunchKernelGGL(ptm_dirmats, dim3(cdiv(n_mat * P, 64)), dim3(64), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_dirs, P,
+                           (const double*)d_t, n_mat, d_D);
+        CHK(launch_check(c, "ptm_dirmats"));
+        ++launches;
+        if (coded) {
+            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
+            CHK(launch_check(c, "pt2_gap_rows"));
+            ++launches;
+        }
+        ptm_args m{};
+        ptg_args& g = m.g;
+        pt2_args& a = g.a;
+        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
+        a.prior = prior4 ? d_prior : c->d_pi;
+        a.tilev = d_tilev; a.site_lik = nullptr;
+        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
+        g.dops = d_dops; g.dtile = d_dtile; g.store = (pk_d2*)(base + pl.o_store);
+        g.mat_plane = n_mat * 16;
+        g.n_items = n * ntiles; g.depth = depth;
+        m.D = d_D; m.mtile = d_mtile; m.P = P;
+        ptm_launch(m, std::min(pl.grid, g.n_items), coded, want_grad, c->stream);
+        CHK(launch_check(c, "ptm_updown"));
+        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
+        CHK(launch_check(c, "pt2_finish"));
+        launches += 2;
+        if (want_grad) {
+            hipLaunchKernelGGL(ptg_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)d_ops,
+                               (const double*)d_out, ntiles, n, R, 1, d_dout);
+            CHK(launch_check(c, "ptg_finish"));
+            ++launches;
+        }
+        hipLaunchKernelGGL(ptm_finish, dim3(cdiv((long)n * nm, 256)), dim3(256), 0, c->stream, (const double*)d_mtile, (const double*)d_out, ntiles, n, P,
+                           d_mout, d_mout + (size_t)n * P);
+        CHK(launch_check(c, "ptm_finish"));
+        ++launches;
+        HIPCHK(c, hipEventRecord(c->ev_tq1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (want_grad) HIPCHK(c, hipMemcpyAsync(grad + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dtheta_TxP + (size_t)t0 * P, d_mout, (size_t)n * P * 8, hipMemcpyDeviceToHost, c->stream));
+        if (dprior_Tx4)
+            HIPCHK(c, hipMemcpyAsync(dprior_Tx4 + (size_t)t0 * 4, d_mout + (size_t)n * P, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tq0, c->ev_tq1));
+        ms_total += ms;
+    }
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * R * (1 + P);
+        st.alg_bytes = 96.0 * (double)T * S * R;
         *perf = st;
     }
     return PHYLO_OK;

@@ -219,3 +219,169 @@ def optimize_rates(grad_fn, child, blen, alpha0, C, pinv0=None, fit=('alpha',), 
     out.update(blen=x[:, :nb].reshape(b0.shape), grad=g[:, :nb].reshape(b0.shape), grad_model=g[:, nb:],
                alpha=np.array(a), pinv=np.array(p) if has_inv else None, rates=rt, weights=wt)
     return out
+
+
+MODEL_ITER = 200                 # quasi-Newton steps of one model fit at fixed lengths
+MODEL_HALVINGS = 40              # step halvings of one line search before the fit gives up
+
+
+def _climb_bfgs(fun, x0, gtol, max_iter=MODEL_ITER):
+    """Maximise fun(x) -> (f, g) from x0 by BFGS with backtracking: the inverse matrix starts as the identity scaled so that the
+    first step is of order FIRST_STEP and takes the usual scaling s.y / y.y after the first accepted step.  A trial is taken when
+    f does not fall and rises by ARMIJO of the first-order promise; two values closer than NOISE of their size are told apart
+    by the trapezoid of their gradients (optimize_branches' rule).  Returns the point of the largest f seen, its f and g, the
+    steps taken and the list of f."""
+    x = np.array(x0, dtype=np.float64)
+    f, g = fun(x)
+    if not (np.isfinite(f) and np.isfinite(g).all()):
+        raise OutOfRangeError("optimize_model: the objective or its gradient is not finite at the starting model")
+    n = x.size
+    H = np.eye(n) * (FIRST_STEP / max(np.abs(g).max(), 1.0))
+    fs, steps, first = [f], 0, True
+    best = (x, f, g)                                        # inside NOISE a step judged by its gradients may lower f: the best point is returned
+    for _ in range(max_iter):
+        if np.abs(g).max() <= gtol:
+            break
+        d = H @ g
+        if not np.isfinite(d).all() or g @ d <= 0:
+            H = np.eye(n) * (FIRST_STEP / max(np.abs(g).max(), 1.0))
+            d = H @ g
+        step, taken = 1.0, False
+        for _ in range(MODEL_HALVINGS):
+            xt = x + step * d
+            ft, gt = fun(xt)
+            if np.isfinite(ft) and np.isfinite(gt).all():
+                if abs(ft - f) <= NOISE * abs(f):
+                    ok = 0.5 * ((g + gt) @ (xt - x)) >= 0
+                else:
+                    ok = ft >= f and ft - f >= ARMIJO * step * (g @ d)
+                if ok:
+                    taken = True
+                    break
+            step *= 0.5
+        if not taken:
+            break
+        s, y = xt - x, g - gt
+        sy = s @ y
+        if sy > 1e-300:
+            if first:
+                H = np.eye(n) * (sy / (y @ y))
+                first = False
+            rho = 1.0 / sy
+            V = np.eye(n) - rho * np.outer(s, y)
+            H = V @ H @ V.T + rho * np.outer(s, s)
+        moved = np.abs(s).max()
+        x, f, g = xt, ft, gt
+        if f >= best[1]:
+            best = (x, f, g)
+        fs.append(f)
+        steps += 1
+        if moved == 0.0:
+            break
+    return best[0], best[1], best[2], steps, fs
+
+
+def optimize_model(grad_model_fn, grad_fn, child, blen, y_q0, y_station0, fit=('q',), fit_on=None, max_rounds=20, tol=1e-6,
+                   lo=1e-8, hi=100.0, branch_iter=50, gtol=1e-6):
+    """Fit ONE substitution model shared by T trees, and every tree's branch lengths under it, by climbing the log-likelihood
+    grad_fn and grad_model_fn compute.  CAVEAT: on the device that function is the project's, whose pruning step is x . M (SURVEY.md
+    quirk Q2); for an asymmetric Q its site factors are not probabilities, it has no interior maximum over Q, and the climb ends on
+    the boundary of the softmax -- the result is then NOT a maximum-likelihood estimate of a substitution model (DESIGN.md section
+    13c).  Over functions whose factors are probabilities (the textbook convention) it is one.  The model: the
+    project's row-softmax Q (phylo_amd.model.get_Q of y_q; 'q' in fit, always) and the root distribution softmax(y_station)
+    ('pi' in fit).  Block-coordinate ascent:
+
+      (a) every tree's lengths are climbed by optimize_branches under the current model;
+      (b) with the lengths fixed, BFGS with backtracking climbs the twelve off-diagonal entries of y_q (and the four of
+          y_station, whose gradient has no component along (1, 1, 1, 1): fifteen free coordinates at most) on the objective
+          sum over t in fit_on of loglik[t].
+
+    fit_on defaults to the single best tree after the first (a) -- the usual practice before topology tests; several trees sum
+    their objectives.  One round is (b) then (a); the fit stops when a round raises the objective by less than tol, or after
+    max_rounds.  The objective never falls: both halves take a step only if it does not lower it.
+
+    The row-softmax fixes the scale of every row of Q (its off-diagonal entries sum to 1), so no direction of the model space
+    rescales Q as a whole: branch lengths and Q are not confounded, and (a) and (b) do not chase one another along a ridge.
+
+    grad_fn(blen [T][N-1][2], Q [4][4], pi [4]) -> (loglik [T], grad, curv): Context.trees_grad(want_curv=True) after set_model,
+    or a restatement.  grad_model_fn(idx, blen [n][N-1][2], Q, pi, dirs [P][4][4]) -> (loglik [n], dtheta [n][P], dprior [n][4])
+    for the trees idx: Context.trees_grad_model, or a restatement.
+
+    Returns a dict: 'y_q' [4][4], 'y_station' [4], 'Q', 'pi', 'blen' [T][N-1][2] and 'loglik' [T] (every tree at its climbed
+    lengths under the fitted model), 'fit_on', 'rounds', 'objective_start' (after the first (a): the objective under the
+    starting model) and 'objective', 'history' (the objective after every half round, starting with objective_start),
+    'grad_model' (the gradient of the fitted coordinates at the returned model and lengths), 'converged'."""
+    from . import model as model_mod
+    from . import modelfit
+    fit = tuple(fit)
+    if 'q' not in fit or any(f not in ('q', 'pi') for f in fit):
+        raise ValueError("optimize_model: fit is ('q',) or ('q', 'pi'), not %r" % (fit,))
+    fit_pi = 'pi' in fit
+    b = np.array(blen, dtype=np.float64)
+    if b.ndim == 2:
+        b = b[None]
+    T = b.shape[0]
+    y_q = modelfit.unpack_q(modelfit.pack_q(y_q0))
+    y_st = np.array(y_station0, dtype=np.float64).reshape(4)
+
+    def model_of(yq, ys):
+        return model_mod.get_Q(yq), model_mod.get_stationary_probs(ys).reshape(4)
+
+    def lengths(bb, yq, ys):
+        Q, pi = model_of(yq, ys)
+        return optimize_branches(lambda x: grad_fn(x, Q, pi), child, bb, lo=lo, hi=hi, max_iter=branch_iter, gtol=gtol)
+
+    out = lengths(b, y_q, y_st)
+    b, ll = out['blen'], np.array(out['loglik'], dtype=np.float64)
+    if fit_on is None:
+        fit_on = [int(np.argmax(ll))]
+    fit_on = [int(t) for t in np.atleast_1d(fit_on)]
+    if not fit_on or min(fit_on) < 0 or max(fit_on) >= T:
+        raise ValueError("optimize_model: fit_on names trees 0 .. %d, got %r" % (T - 1, fit_on))
+    idx = np.array(fit_on)
+
+    def value(v, bb):
+        """the objective at model coordinates v and lengths bb: its value, the trees' terms and the gradient in v"""
+        yq = modelfit.unpack_q(v[:12])
+        ys = v[12:] if fit_pi else y_st
+        Q, pi = model_of(yq, ys)
+        l, dth, dpr = grad_model_fn(idx, bb[idx], Q, pi, modelfit.q_directions(yq))
+        l = np.array(l, dtype=np.float64)
+        g = np.asarray(dth, dtype=np.float64).sum(axis=0)
+        if fit_pi:
+            g = np.concatenate([g, modelfit.chain_prior(np.asarray(dpr, dtype=np.float64).sum(axis=0), ys)])
+        return float(np.sum(l)), l, g
+
+    def coords():
+        return np.concatenate([modelfit.pack_q(y_q)] + ([y_st] if fit_pi else []))
+
+    # Every recorded objective is value() at the point that is kept: optimize_branches records, of two log-likelihoods it cannot
+    # tell apart, the larger, which need not be the value at the lengths it returns.
+    obj, l_cur, gm = value(coords(), b)
+    ll[idx] = l_cur
+    start, history, rounds, converged = obj, [obj], 0, False
+    for _ in range(max_rounds):
+        v, f_b, _, _, _ = _climb_bfgs(lambda x: value(x, b)[::2], coords(), gtol)      # (b): starts at obj, returns its best point
+        if f_b >= obj:                                      # taken only if it does not lower the objective
+            y_q = modelfit.unpack_q(v[:12])
+            if fit_pi:
+                y_st = v[12:].copy()
+        f_b, l_cur, gm = value(coords(), b)
+        history.append(f_b)
+        out = lengths(b, y_q, y_st)                         # (a)
+        new, l_new, g_new = value(coords(), out['blen'])
+        if new >= f_b:                                      # ... and so is (a)
+            b, ll, l_cur, gm = out['blen'], np.array(out['loglik'], dtype=np.float64), l_new, g_new
+        else:                                               # the lengths stay; every tree's value is that of its start under this model
+            ll, new = np.array(out['history'][0], dtype=np.float64), f_b
+        ll[idx] = l_cur
+        history.append(new)
+        rounds += 1
+        rise, obj = new - obj, new
+        if rise < tol:
+            converged = True
+            break
+    Q, pi = model_of(y_q, y_st)
+    return {'y_q': y_q, 'y_station': y_st, 'Q': Q, 'pi': pi, 'blen': b, 'loglik': ll, 'fit_on': fit_on, 'rounds': rounds,
+            'objective_start': start, 'objective': obj, 'history': np.array(history), 'grad_model': gm, 'converged': converged,
+            'branches': out}

@@ -304,7 +304,8 @@ class VCSMC:
             tab = new
         return [row[0] for row in tab]
 
-    def score_trees(self, newicks, rates=None, want_sites=False, optimize=False, fit=(), search=None, search_rounds=20):
+    def score_trees(self, newicks, rates=None, want_sites=False, optimize=False, fit=(), search=None, search_rounds=20, fit_model=(),
+                    fit_on=None, fit_rounds=20):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
         distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
         (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
@@ -325,8 +326,20 @@ class VCSMC:
         the mixture (phylo_trees_nni_rates and phylo_trees_grad_rates).  With fit as well, every tree is searched with ITS fitted
         alpha (and p_inv) held fixed -- a mixture per tree, which follows its tree through the search --, then one more
         optimize_rates runs on the trees found from the found lengths and those values; self.last_tree_search then also holds
-        the final 'alpha' and 'pinv' (self.last_tree_opt keeps those of the given topologies)."""
+        the final 'alpha' and 'pinv' (self.last_tree_opt keeps those of the given topologies).
+        fit_model (with optimize; one rate, no search): ('q',) or ('q', 'pi') -- ONE substitution model shared by all trees is
+        fitted (at most fit_rounds rounds; CAVEAT: under the project's pruning convention the fitted function has no interior
+        maximum over an asymmetric Q, so this is not a maximum-likelihood model estimate: DESIGN.md section 13c) on the trees fit_on (default: the best tree at its ML lengths under the current model)
+        together with every tree's lengths (phylo_amd.treeopt.optimize_model over phylo_trees_grad_model and phylo_trees_grad,
+        from y_q and y_station; never the JC69 closed form).  The fit calls set_model between device calls; the context's
+        model is put back before this returns, and the fitted one is handed to the caller in self.last_model_fit ('Q', 'pi',
+        'y_q', 'y_station', 'fit_on', 'rounds', 'objective_start', 'objective', 'history').  The scores and site factors come
+        from one trees_loglik under the fitted model; self.last_tree_opt is as with optimize alone ('loglik_given' under the
+        model given, 'newicks' at the lengths climbed under the fitted model)."""
         fit = tuple(fit)
+        fit_model = tuple(fit_model)
+        if fit_model and (not optimize or rates is not None or fit or search is not None):
+            raise ValueError("score_trees: fit_model=%r needs optimize=True and neither rates, fit nor search" % (fit_model,))
         if search is not None and (search != 'nni' or not optimize):
             raise ValueError("score_trees: search=%r needs search='nni' and optimize=True" % (search,))
         spec = rates if isinstance(rates, dict) else None
@@ -385,6 +398,40 @@ class VCSMC:
             else:
                 res = ctx.trees_loglik_rates(child, blen, rates[0], rates[1], want_sites=True)
             res = res if want_sites else res[0]
+        elif optimize and fit_model:
+            from . import treeopt
+            given = ctx.trees_loglik(child, blen)
+            lam_l, lam_r = self.left_branches_param, self.right_branches_param
+
+            def under(Q, pi):
+                ctx.set_model(Q, pi, lam_l, lam_r, jc69_closed_form=False)
+
+            def grad_fn(b, Q, pi):
+                under(Q, pi)
+                return ctx.trees_grad(child, b, want_curv=True)
+
+            def grad_model_fn(idx, b, Q, pi, dirs):
+                under(Q, pi)
+                return ctx.trees_grad_model(child[idx], b, dirs)
+
+            try:
+                mf = treeopt.optimize_model(grad_model_fn, grad_fn, child, blen, self.y_q, np.asarray(self.y_station).reshape(-1),
+                                            fit=fit_model, fit_on=fit_on, max_rounds=fit_rounds)
+                blen = mf['blen']
+                under(mf['Q'], mf['pi'])
+                res = ctx.trees_loglik(child, blen, want_sites=True)
+            finally:
+                self._context()                             # the context's model again, from the same numbers: the same bits
+            opt = mf['branches']
+            self.last_tree_opt = {'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(child, blen)],
+                                  'loglik_given': [float(x) for x in given], 'iterations': [int(i) for i in opt['iterations']],
+                                  'converged': [bool(v) for v in opt['converged']]}
+            self.last_model_fit = {'Q': mf['Q'].tolist(), 'pi': mf['pi'].tolist(), 'y_q': mf['y_q'].tolist(),
+                                   'y_station': mf['y_station'].tolist(), 'fit': list(fit_model), 'fit_on': mf['fit_on'],
+                                   'rounds': int(mf['rounds']), 'objective_start': float(mf['objective_start']),
+                                   'objective': float(mf['objective']), 'history': [float(h) for h in mf['history']],
+                                   'converged': bool(mf['converged'])}
+            res = res if want_sites else res[0]
         elif optimize:
             from . import treeopt
             given = ctx.trees_loglik(child, blen)
@@ -439,6 +486,9 @@ class VCSMC:
         self.tree_test_results = None
         self.trees_ml = None
         self.trees_search = None
+        self.model_ml = None
+        mfit = getattr(self.args, 'score_model_fit', None) if ml else None  # --score_model_fit q | q+pi: one ML model for all trees
+        mfit = tuple(mfit.split('+')) if mfit else None
         srch = getattr(self.args, 'score_search', None) if ml else None     # --score_search nni[:ROUNDS]: then an NNI search from there
         fsrch = getattr(self.args, 'score_fit_search', None) if fit is not None else None   # --score_fit_search: the same under the rate model
         if fsrch:
@@ -453,6 +503,12 @@ class VCSMC:
             opt, found = self.last_tree_opt, self.last_tree_search
             ll, ll_ml = opt['loglik_given'], found['loglik_ml']
             self.trees_ml, self.trees_search = opt['newicks'], found['newicks']
+        elif ml and mfit:
+            ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True, fit_model=mfit)
+            opt = self.last_tree_opt
+            ll = opt['loglik_given']
+            self.trees_ml = opt['newicks']
+            self.model_ml = self.last_model_fit
         elif ml:
             ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True)
             opt = self.last_tree_opt
@@ -517,7 +573,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit', 'score_search', 'score_fit_search') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit', 'score_search', 'score_fit_search', 'score_model_fit') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))
@@ -642,6 +698,9 @@ class VCSMC:
                 if getattr(self, 'trees_ml', None) is not None:
                     with open(os.path.join(save_dir, 'trees_ml.nwk'), 'w') as f:
                         f.write('\n'.join(self.trees_ml) + '\n')
+                if getattr(self, 'model_ml', None) is not None:
+                    with open(os.path.join(save_dir, 'model_ml.json'), 'w') as f:
+                        json.dump(self.model_ml, f, indent=1)
                 if getattr(self, 'trees_search', None) is not None:
                     with open(os.path.join(save_dir, 'trees_search.nwk'), 'w') as f:
                         f.write('\n'.join(self.trees_search) + '\n')

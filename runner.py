@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--score_model_fit`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -87,6 +87,16 @@ def parse_args(argv=None):
                              "20); writes trees_search.nwk (the trees found), adds loglik_search, nni_moves and search_rounds to "
                              "every tree of tree_scores.json, and gives --tree_tests the site likelihoods of the trees found.  Not "
                              "with --score_rates or --score_fit: --score_fit_search does this under a rate model")
+    parser.add_argument('--score_model_fit', default=None, choices=['q', 'q+pi'],
+                        help="with --score_trees and --score_opt true: fit ONE substitution model for all trees by climbing the "
+                             "log-likelihood -- the row-softmax Q (q), and the root distribution too (q+pi) -- on the best tree, "
+                             "together with every tree's branch lengths (phylo_trees_grad_model).  Writes model_ml.json (Q, pi, "
+                             "y_q, y_station, fit_on, rounds, the objective before and after); loglik_ml of tree_scores.json, "
+                             "trees_ml.nwk and the site likelihoods of --tree_tests are then under the fitted model.  Not with "
+                             "--score_rates, --score_fit or --score_search.  CAVEAT: under the project's pruning convention (a message is x.M) the "
+                             "site factors of an asymmetric Q are not probabilities and the climb ends on the boundary of the "
+                             "softmax: the fitted model is NOT a maximum-likelihood estimate of a substitution model, and tree tests "
+                             "under it are tests under a degenerate model (DESIGN.md section 13c)")
     parser.add_argument('--score_fit_search', default=None, metavar='nni[:ROUNDS]',
                         help="with --score_trees, --score_rates and --score_fit: after the fit, hill-climb every tree over "
                              "nearest-neighbour interchanges UNDER the rate model (phylo_trees_nni_rates on the device), every tree "
@@ -141,6 +151,14 @@ def parse_args(argv=None):
         if args.score_rates is not None:
             parser.error('--score_opt true: the one-rate branch-length gradient is not built for rate mixtures (not with '
                          '--score_rates); --score_fit branches climbs the lengths under the rate model')
+    if args.score_model_fit is not None:
+        if args.score_rates is not None or args.score_fit is not None:
+            parser.error('--score_model_fit: the model gradient is not built for rate mixtures (not with --score_rates or --score_fit)')
+        if args.score_search is not None:
+            parser.error('--score_model_fit: the NNI search runs under the model given, not a fitted one (not with --score_search)')
+        if not args.score_trees or not args.score_opt:
+            parser.error('--score_model_fit needs --score_trees and --score_opt true (it fits the model on the trees scored there, '
+                         'at their maximum-likelihood branch lengths)')
     if args.score_fit is not None:
         if not args.score_trees or args.score_rates is None:
             parser.error('--score_fit needs --score_trees FILE and --score_rates gamma:ALPHA:C[:PINV] (it fits the trees scored there '

@@ -37,7 +37,14 @@ the worst relative difference of loglik + delta to the explicit neighbour's log-
 --nni --rates C times phylo_trees_nni_rates under C discrete Gamma categories against C calls of
 phylo_trees_nni on the scaled trees and, for the first --explicit_trees trees, against phylo_trees_loglik_rates on their explicitly
 built neighbours, interleaved in the same run: device and wall times, their ratios, the number of chunks, whether loglik carries
-phylo_trees_loglik_rates' bits, and the worst relative difference of loglik + delta to the explicit neighbour's log-likelihood."""
+phylo_trees_loglik_rates' bits, and the worst relative difference of loglik + delta to the explicit neighbour's log-likelihood.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --model --dirs 12 --reps 7 --out profiles/trees_probe.jsonl
+
+--model times phylo_trees_grad_model along --dirs P directions of the row-softmax Q (and with P = 1)
+against phylo_trees_grad without curvature, phylo_trees_loglik, and the central-difference yardstick it replaces -- 2 P pairs of
+set_model and phylo_trees_loglik --, interleaved in the same run: device and wall times, their ratios, the number of chunks, and
+whether loglik and grad carry the siblings' bits."""
 import argparse
 import json
 import os
@@ -113,6 +120,86 @@ def rates_probe(a):
            'device_ratio_rates_over_plain_x_C': d['median'] / pd['median'], 'wall_ratio_rates_over_plain_x_C': w['median'] / pw['median'],
            'launches': stats['n_launches'], 'units': stats['units'], 'units_per_s_device': stats['units'] / (d['median'] * 1e-3),
            'cat_lik_bit_equal': same, 'finite': bool(np.isfinite(ll).all())}
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same else 1
+
+
+def model_probe(a):
+    """phylo_trees_grad_model along P directions (and along one) against phylo_trees_grad, the plain call and the 2 P
+    set_model + phylo_trees_loglik pairs of a central difference: same trees, same context, same run"""
+    from phylo_amd import modelfit
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    y_q = model.init_y_q()
+    Q, pi, lam = model.get_Q(y_q), np.full(4, 0.25), np.full(N - 1, 10.0)
+    P = a.dirs
+    dirs = np.concatenate([modelfit.q_directions(y_q), rng.normal(size=(4, 4, 4))])[:P]
+    h = 1e-6
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, pi, lam, lam)
+        ll = ctx.trees_loglik(child, blen)                   # warm-up of all
+        lg, grad = ctx.trees_grad(child, blen)
+        lm, dth, mgrad, dpr = ctx.trees_grad_model(child, blen, dirs, want_grad=True)
+        ctx.trees_grad_model(child, blen, dirs[:1], want_grad=True)
+        same = bool(np.array_equal(ll.view(np.uint64), lm.view(np.uint64)) and np.array_equal(grad.view(np.uint64), mgrad.view(np.uint64)))
+        t = {k: ([], []) for k in ('model', 'model1', 'model_only', 'grad', 'plain', 'fd')}
+
+        def timed(key, fn):
+            t0 = time.perf_counter()
+            dev = fn()
+            t[key][0].append((time.perf_counter() - t0) * 1e3)
+            t[key][1].append(dev)
+
+        def one(fn):
+            fn()
+            return ctx.last_trees_stats['sweep_ms']
+
+        def central():
+            dev, fd = 0.0, np.empty((a.trees, P))
+            for p in range(P):
+                pair = []
+                for sgn in (1.0, -1.0):
+                    ctx.set_model(Q + sgn * h * dirs[p], pi, lam, lam)
+                    pair.append(ctx.trees_loglik(child, blen))
+                    dev += ctx.last_trees_stats['sweep_ms']
+                fd[:, p] = (pair[0] - pair[1]) / (2 * h)
+            ctx.set_model(Q, pi, lam, lam)
+            central.fd = fd
+            return dev
+
+        for _ in range(a.reps):                              # interleaved: all see the same machine
+            timed('model', lambda: one(lambda: ctx.trees_grad_model(child, blen, dirs, want_grad=True)))
+            stats = dict(ctx.last_trees_stats)
+            timed('model1', lambda: one(lambda: ctx.trees_grad_model(child, blen, dirs[:1], want_grad=True)))
+            timed('model_only', lambda: one(lambda: ctx.trees_grad_model(child, blen, dirs, want_prior=False)))
+            timed('grad', lambda: one(lambda: ctx.trees_grad(child, blen)))
+            timed('plain', lambda: one(lambda: ctx.trees_loglik(child, blen)))
+            timed('fd', central)
+    q = {k: (quartiles(v[0]), quartiles(v[1])) for k, v in t.items()}
+    fd_off = float(np.max(np.abs(central.fd - dth) / (1.0 + np.abs(dth))))
+    rec = {'probe': 'trees_grad_model', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'reps': a.reps, 'P': int(P),
+           'model_wall_ms': q['model'][0], 'model_device_ms': q['model'][1], 'model_P1_wall_ms': q['model1'][0], 'model_P1_device_ms': q['model1'][1],
+           'model_without_grad_device_ms': q['model_only'][1],
+           'grad_wall_ms': q['grad'][0], 'grad_device_ms': q['grad'][1], 'plain_wall_ms': q['plain'][0], 'plain_device_ms': q['plain'][1],
+           'central_2P_wall_ms': q['fd'][0], 'central_2P_device_ms': q['fd'][1],
+           'device_ratio_model_over_grad': q['model'][1]['median'] / q['grad'][1]['median'],
+           'device_ratio_model_P1_over_grad': q['model1'][1]['median'] / q['grad'][1]['median'],
+           'device_ratio_model_over_plain': q['model'][1]['median'] / q['plain'][1]['median'],
+           'device_ratio_model_over_central_2P': q['model'][1]['median'] / q['fd'][1]['median'],
+           'wall_ratio_model_over_grad': q['model'][0]['median'] / q['grad'][0]['median'],
+           'wall_ratio_model_over_central_2P': q['model'][0]['median'] / q['fd'][0]['median'],
+           'launches': stats['n_launches'], 'chunks': stats['n_launches'] // 8, 'units': stats['units'],
+           'units_per_s_device': stats['units'] / (q['model'][1]['median'] * 1e-3),
+           'central_difference_off': fd_off, 'loglik_and_grad_bit_equal': same, 'finite': bool(np.isfinite(dth).all() and np.isfinite(dpr).all())}
     line = json.dumps(rec)
     print(line)
     if a.out:
@@ -394,7 +481,11 @@ def main(argv=None):
     ap.add_argument('--grad', action='store_true', help='probe phylo_trees_grad (with and without curvature) against the plain call')
     ap.add_argument('--nni', action='store_true', help='probe phylo_trees_nni against phylo_trees_loglik on the explicit neighbours, and phylo_trees_grad')
     ap.add_argument('--explicit_trees', type=int, default=512, help='with --nni: trees whose neighbours are built and scored explicitly (0: all)')
+    ap.add_argument('--model', action='store_true', help='probe phylo_trees_grad_model against phylo_trees_grad, the plain call and central differences')
+    ap.add_argument('--dirs', type=int, default=12, help='with --model: directions of a call (1 .. 16)')
     a = ap.parse_args(argv)
+    if a.model:
+        return model_probe(a)
     if a.nni and a.rates > 0:
         return nni_rates_probe(a)
     if a.nni:
