@@ -579,6 +579,30 @@ int phylo_rell(phylo_ctx* ctx, int T, int S, const double* site_lik_TxS, int B, 
  * are asked for). */
 int phylo_debug_rell_host(int T, int S, const double* site_lik_TxS, int b0, int nB, uint64_t seed, int32_t* counts, double* x,
                           double* rl);
+/* The multiscale RELL bootstrap behind Shimodaira's approximately unbiased (AU) test: K scales, B
+ * replicates each; replicate b of scale k draws draws[k] sites, not S.  x and obs_T are phylo_rell's, bit for bit.  Counts: draw j
+ * (0 <= j < draws[k]) is word j & 3 of the Philox4x32-10 block with key = seed and counter (b, k, 4, j >> 2) -- counter word 1,
+ * which is 0 in phylo_rell, carries the scale --, the site (word * S) >> 32; cnt[k][b][s] is uint16 and a row sums to draws[k]; b
+ * and k are global indices, chunking changes no bit.  rl[k][t][b] is phylo_rell's single fma chain over ascending s with these
+ * counts; it is NOT rescaled by S / draws[k] (the factor is the same for every tree of a column).  best[k][b] is the lexicographic
+ * maximum of (rl[k][t][b], -t) over t: the greatest score, ties to the lowest t, in any order of reduction.  wins[k][t] =
+ * #{b : best[k][b] = t}; every row of wins sums to B.  K = 1 with draws = {S} returns phylo_rell's obs, best and wins bit for bit
+ * for the same seed and B: scale 0 shares its Philox stream with phylo_rell, so samples of the two calls are not independent.
+ * The score matrix is never stored unless rep_loglik_KxTxB is given (tests and probes); best_KxB and counts_KxBxS may be NULL too.
+ * perf (may be NULL): sweep_ms = device time by events, n_launches, units = T S K B.  Synchronous; on a sharded context a LOCAL
+ * call.  Columns (k, b) run in chunks whose counts, partial maxima and, when asked for, scores stay within 256 MiB; a chunk may
+ * straddle scales (PHYLO_RELL_CHUNK=n caps its columns; no bit depends on it).  Own scratch and events, released with the context:
+ * the sweep's state, a kept graph, a tree summary and every other call's scratch are left alone.  PHYLO_EINVAL, before anything is
+ * queued: phylo_rell's refusals (T < 1, S outside 1 .. 65535, B outside 1 .. 2^20 per scale, a site factor that is not finite and
+ * > 0), K outside 1 .. 64, draws, obs or wins == NULL, a draws[k] outside 1 .. 65535, the uint16 count bound (the message names k). */
+int phylo_rell_multiscale(phylo_ctx* ctx, int T, int S, const double* site_lik_TxS, int K, const int32_t* draws_K, int B, uint64_t seed,
+                          double* obs_T, int64_t* wins_KxT, int32_t* best_KxB, double* rep_loglik_KxTxB, int32_t* counts_KxBxS,
+                          phylo_stats* perf);
+/* Test hook, no GPU and no context needed: phylo_rell_multiscale's contract as a loop on the host over the same functions the
+ * kernels call, for scale k0 and replicates b0 .. b0 + nB - 1: counts [nB][S], rl [T][nB], best [nB]; any output may be NULL
+ * (site_lik too when only counts are asked for). */
+int phylo_debug_rell_multiscale_host(int T, int S, const double* site_lik_TxS, int K, const int32_t* draws_K, int k0, int b0, int nB,
+                                     uint64_t seed, int32_t* counts, double* rl, int32_t* best);
 
 /* Bit-level probe of the device arithmetic contract: op 0 exp(x), 1 log(x), 2 x/y, 3 fma(x,y,x), 4 exp(x) for x <= 0 (the scan's);
  * op 5 is outside that contract: the reverse pass's reciprocal of a site likelihood (pg_rcp, an ulp or two off 1/x). */

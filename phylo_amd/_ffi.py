@@ -26,7 +26,7 @@ COMM_ID_BYTES = 128
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_grad_model", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_grad_model", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_rell_multiscale", "phylo_debug_rell_multiscale_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -416,6 +416,30 @@ def debug_rell_host(site_lik, b0, nB, seed, S=None, want_counts=True, want_logs=
     return {'counts': cnt, 'site_loglik': x, 'rep_loglik': rl}
 
 
+def debug_rell_multiscale_host(site_lik, draws, k0, b0, nB, seed, S=None, want_counts=True, want_reps=True, want_best=True):
+    """phylo_rell_multiscale's contract as a host loop (no GPU needed) for scale k0 of `draws` and its replicates b0 .. b0 + nB - 1:
+    a dict with 'counts' [nB][S] int32, 'rep_loglik' [T][nB] and 'best' [nB].  site_lik None (then give S): the counts alone."""
+    lib = load()
+    if site_lik is None:
+        T, S = 1, int(S)
+        sl, want_reps, want_best = None, False, False
+    else:
+        sl = _f64(site_lik)
+        if sl.ndim != 2:
+            raise ValueError("site_lik must be [T][S], got %r" % (sl.shape,))
+        T, S = sl.shape
+    dr = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1)
+    nB = int(nB)
+    cnt = np.zeros((nB, S), dtype=np.int32) if want_counts else None
+    rl = np.empty((T, nB)) if want_reps else None
+    best = np.empty(nB, dtype=np.int32) if want_best else None
+    rc = lib.phylo_debug_rell_multiscale_host(C.c_int(T), C.c_int(S), _ptr(sl), C.c_int(dr.size), _ptr(dr), C.c_int(int(k0)), C.c_int(int(b0)),
+                                              C.c_int(nB), C.c_uint64(int(seed)), _ptr(cnt), _ptr(rl), _ptr(best))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return {'counts': cnt, 'rep_loglik': rl, 'best': best}
+
+
 def vi_apply(N, jc, packed_vars, packed_grads, kind, lr, beta1=0.9, beta2=0.999, eps=1e-8, state=None):
     """phylo_vi_apply: the optimiser update on the packed variables IN PLACE (kind 0 gradient descent, 1 Adam with state =
     {'t': int, 'm': array, 'v': array}, updated in place too)."""
@@ -734,6 +758,37 @@ class Context:
             out['counts'] = counts
         if want_logs:
             out['site_loglik'] = logs
+        return out
+
+    def rell_multiscale(self, site_lik, draws, B, seed, want_best=False, want_reps=False, want_counts=False):
+        """Multiscale RELL bootstrap over the site factors site_lik [T][S] (phylo_rell_multiscale): B replicates at each of the
+        K scales, scale k drawing draws[k] sites.  Returns a dict: 'obs' [T] (phylo_rell's observed scores), 'wins' [K][T] the
+        number of replicates of scale k in which tree t scores highest (ties to the lowest t), 'stats', and on request 'best'
+        [K][B], 'rep_loglik' [K][T][B] (not rescaled by S / draws[k]) and 'counts' [K][B][S].  The score matrix is not stored
+        on the device unless want_reps asks for it.  treetests.au_scales gives draws, treetests.au_test reads the AU p-values
+        off wins.  Scale 0 shares its random stream with rell(): the two calls' samples are not independent."""
+        sl = _f64(site_lik)
+        if sl.ndim != 2:
+            raise ValueError("site_lik must be [T][S], got %r" % (sl.shape,))
+        T, S = sl.shape
+        dr = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1)
+        K, B = dr.size, int(B)
+        nb = max(B, 0)
+        obs, wins = np.empty(T), np.empty((K, T), dtype=np.int64)
+        best = np.empty((K, nb), dtype=np.int32) if want_best else None
+        reps = np.empty((K, T, nb)) if want_reps else None
+        counts = np.empty((K, nb, S), dtype=np.int32) if want_counts else None
+        st = Stats()
+        self._check(self._lib.phylo_rell_multiscale(self._h, C.c_int(T), C.c_int(S), _ptr(sl), C.c_int(K), _ptr(dr), C.c_int(B),
+                                                    C.c_uint64(int(seed)), _ptr(obs), _ptr(wins), _ptr(best), _ptr(reps), _ptr(counts),
+                                                    C.byref(st)))
+        out = {'obs': obs, 'wins': wins, 'stats': {f: getattr(st, f) for f, _ in Stats._fields_}}
+        if want_best:
+            out['best'] = best
+        if want_reps:
+            out['rep_loglik'] = reps
+        if want_counts:
+            out['counts'] = counts
         return out
 
     def resample(self, logw, seed, step):

@@ -29,6 +29,7 @@
 #include "phylo_trees_plan.h"
 #include "phylo_treeset.h"
 #include "phylo_rell.h"
+#include "phylo_rell_ms.h"
 #include "phylo_treegrad.h"
 #include "phylo_treegrad_rates.h"
 #include "phylo_treenni.h"
@@ -74,7 +75,7 @@ struct env_switches {
     int scan_ancestors = 1;              // PHYLO_SCAN_ANCESTORS: 0 = no chain form of a rank event (sweep_chain_form_of)
     int site_patterns = PK_PAT_AUTO;     // PHYLO_SITE_PATTERNS: 0 = never the pattern form of the merge, force = wherever it is valid
     int trees_chunk = 0;                 // PHYLO_TREES_CHUNK: trees per chunk of phylo_trees_loglik (0 = what PT2_SCRATCH_BYTES holds; tests lower it)
-    int rell_chunk = 0;                  // PHYLO_RELL_CHUNK: replicates per chunk of phylo_rell (0 = what PR_CHUNK_BYTES holds; tests lower it)
+    int rell_chunk = 0;                  // PHYLO_RELL_CHUNK: replicates per chunk of phylo_rell, columns per chunk of phylo_rell_multiscale (0 = what PR_CHUNK_BYTES holds; tests lower it)
     void read() {
         eager_nodes = getenv("PHYLO_EAGER_NODES") != nullptr;
         rehearse_sharded = getenv("PHYLO_REHEARSE_SHARDED") != nullptr;
@@ -258,10 +259,10 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[21];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+    DevBuf scratch[22];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
                                          //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates;
                                          //  16: phylo_trees_grad's chunk and node stores; 17: phylo_trees_grad_rates's; 18: phylo_trees_nni's;
-                                         //  19: phylo_trees_nni_rates's; 20: phylo_trees_grad_model's)
+                                         //  19: phylo_trees_nni_rates's; 20: phylo_trees_grad_model's; 21: phylo_rell_multiscale's logs and chunk)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -277,6 +278,7 @@ struct phylo_ctx {
     hipEvent_t ev_tb0 = nullptr, ev_tb1 = nullptr;
     hipEvent_t ev_tl0 = nullptr, ev_tl1 = nullptr;   // phylo_trees_loglik's own pair (the sweep's and the summaries' stay theirs)
     hipEvent_t ev_rl0 = nullptr, ev_rl1 = nullptr;   // phylo_rell's own pair
+    hipEvent_t ev_rm0 = nullptr, ev_rm1 = nullptr;   // phylo_rell_multiscale's own pair
     hipEvent_t ev_tg0 = nullptr, ev_tg1 = nullptr;   // phylo_trees_grad's own pair
     hipEvent_t ev_tr0 = nullptr, ev_tr1 = nullptr;   // phylo_trees_grad_rates' own pair
     hipEvent_t ev_tn0 = nullptr, ev_tn1 = nullptr;   // phylo_trees_nni's own pair
@@ -849,6 +851,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_tl1) (void)hipEventDestroy(c->ev_tl1);
     if (c->ev_rl0) (void)hipEventDestroy(c->ev_rl0);
     if (c->ev_rl1) (void)hipEventDestroy(c->ev_rl1);
+    if (c->ev_rm0) (void)hipEventDestroy(c->ev_rm0);
+    if (c->ev_rm1) (void)hipEventDestroy(c->ev_rm1);
     if (c->ev_tg0) (void)hipEventDestroy(c->ev_tg0);
     if (c->ev_tg1) (void)hipEventDestroy(c->ev_tg1);
     if (c->ev_tr0) (void)hipEventDestroy(c->ev_tr0);
@@ -1408,6 +1412,126 @@ int phylo_rell(phylo_ctx* c, int T, int S, const double* site_lik_TxS, int B, ui
     return PHYLO_OK;
 }
 
+// ---- multiscale RELL bootstrap, the resampling behind the AU test (phylo_rell_ms.h) ----
+int phylo_rell_multiscale(phylo_ctx* c, int T, int S, const double* site_lik_TxS, int K, const int32_t* draws_K, int B, uint64_t seed, double* obs_T,
+                          int64_t* wins_KxT, int32_t* best_KxB, double* rep_loglik_KxTxB, int32_t* counts_KxBxS, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!site_lik_TxS || !draws_K || !obs_T || !wins_KxT)
+        return fail(c, PHYLO_EINVAL, "phylo_rell_multiscale: site_lik, draws, obs and wins must be given (NULL pointer)");
+    {
+        char msg[200];                                     // everything is checked before anything is queued
+        if (prm_check_shape(T, S, K, draws_K, B, msg, sizeof msg) || pr_check_factors(T, S, site_lik_TxS, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "phylo_rell_multiscale: %s", msg);
+    }
+    // one slab: logs [T][S] (resident for the call) | counts [chunk + 1][Sp] uint16 | partial values, indices [tiles][chunk] |
+    // scores [T][chunk] when asked for | observed [T] | best [chunk] | wins [K][T] | draws [K] | flag.  A column is one replicate
+    // of one scale, c = k B + b; the first chunk carries one more, the row of ones whose chain is the observed score.
+    const bool scores = rep_loglik_KxTxB != nullptr;
+    const size_t Sp = pr_count_stride(S), n_x = (size_t)T * S, n_all = (size_t)K * B;
+    const int chunk = prm_chunk_cols(T, S, K, B, scores, c->env.rell_chunk);
+    const int ntiles = cdiv(T, PR_TT);
+    const size_t ld = (size_t)chunk;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_cnt = up(n_x * 8), o_pv = o_cnt + up((ld + 1) * Sp * 2), o_pi = o_pv + up((size_t)ntiles * ld * 8),
+                 o_rl = o_pi + up((size_t)ntiles * ld * 4), o_obs = o_rl + up(scores ? (size_t)T * ld * 8 : 0), o_best = o_obs + up((size_t)T * 8),
+                 o_wins = o_best + up(ld * 4), o_draws = o_wins + up((size_t)K * T * 8), o_flag = o_draws + up((size_t)K * 4), total = o_flag + 256;
+    void* slab = nullptr;
+    CHK(scratch_get(c, 21, total, &slab));
+    char* base = (char*)slab;
+    double* d_x = (double*)base;
+    uint16_t* d_cnt = (uint16_t*)(base + o_cnt);
+    double* d_pv = (double*)(base + o_pv);
+    int32_t* d_pi = (int32_t*)(base + o_pi);
+    double* d_rl = scores ? (double*)(base + o_rl) : nullptr;
+    double* d_obs = (double*)(base + o_obs);
+    int32_t* d_best = (int32_t*)(base + o_best);
+    unsigned long long* d_wins = (unsigned long long*)(base + o_wins);
+    int32_t* d_draws = (int32_t*)(base + o_draws);
+    unsigned int* d_flag = (unsigned int*)(base + o_flag);
+    if (!c->ev_rm0) {
+        HIPCHK(c, hipEventCreate(&c->ev_rm0));
+        HIPCHK(c, hipEventCreate(&c->ev_rm1));
+    }
+    HIPCHK(c, hipMemcpyAsync(d_x, site_lik_TxS, n_x * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_draws, draws_K, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_wins, 0, (size_t)K * T * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, 4, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_rm0, c->stream));
+    hipLaunchKernelGGL(pr_log, dim3((unsigned)((n_x + 255) / 256)), dim3(256), 0, c->stream, d_x, n_x, d_flag);
+    CHK(launch_check(c, "pr_log"));
+    HIPCHK(c, hipEventRecord(c->ev_rm1, c->stream));
+    unsigned int flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag) return fail(c, PHYLO_EINVAL, "phylo_rell_multiscale: the device met a site factor that is not a finite number > 0");
+    double ms_total = 0.0;
+    int launches = 1;
+    {
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_rm0, c->ev_rm1));
+        ms_total += ms;
+    }
+    std::vector<uint16_t> h_cnt(counts_KxBxS ? (size_t)chunk * Sp : 0);
+    for (size_t c0 = 0; c0 < n_all; c0 += (size_t)chunk) {
+        const int n = (int)std::min<size_t>((size_t)chunk, n_all - c0);
+        const int ncols = n + (c0 == 0 ? 1 : 0);
+        const uint32_t nblk = (uint32_t)((prm_max_draws(draws_K, B, c0, (size_t)n) + 3) / 4);
+        HIPCHK(c, hipMemsetAsync(d_cnt, 0, (size_t)ncols * Sp * 2, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_rm0, c->stream));
+        const size_t n_threads = (size_t)n * nblk;
+        hipLaunchKernelGGL(prm_counts, dim3((unsigned)((n_threads + 255) / 256)), dim3(256), 0, c->stream, (unsigned int*)d_cnt, S, Sp, (uint32_t)c0,
+                           (uint32_t)B, (const int32_t*)d_draws, n_threads, nblk, seed);
+        CHK(launch_check(c, "prm_counts"));
+        ++launches;
+        if (c0 == 0) {
+            hipLaunchKernelGGL(pr_ones, dim3(cdiv(S, 256)), dim3(256), 0, c->stream, d_cnt + (size_t)n * Sp, S);
+            CHK(launch_check(c, "pr_ones"));
+            ++launches;
+        }
+        const dim3 grid((unsigned)ntiles, (unsigned)cdiv(ncols, PR_TB));
+        if (scores)
+            hipLaunchKernelGGL(prm_product<true>, grid, dim3(256), 0, c->stream, (const double*)d_x, (const uint16_t*)d_cnt, T, S, Sp, ncols, n, d_pv,
+                               d_pi, ld, d_obs, d_rl, ld);
+        else
+            hipLaunchKernelGGL(prm_product<false>, grid, dim3(256), 0, c->stream, (const double*)d_x, (const uint16_t*)d_cnt, T, S, Sp, ncols, n, d_pv,
+                               d_pi, ld, d_obs, d_rl, ld);
+        CHK(launch_check(c, "prm_product"));
+        hipLaunchKernelGGL(prm_join, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_pv, (const int32_t*)d_pi, ld, ntiles, n, (uint32_t)c0,
+                           (uint32_t)B, T, d_best, d_wins);
+        CHK(launch_check(c, "prm_join"));
+        launches += 2;
+        HIPCHK(c, hipEventRecord(c->ev_rm1, c->stream));
+        if (best_KxB) HIPCHK(c, hipMemcpyAsync(best_KxB + c0, d_best, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (c0 == 0) HIPCHK(c, hipMemcpyAsync(obs_T, d_obs, (size_t)T * 8, hipMemcpyDeviceToHost, c->stream));
+        if (scores)                                        // a chunk may straddle scales: one strided copy per scale it touches
+            for (size_t a = c0; a < c0 + (size_t)n;) {
+                const size_t k = a / (size_t)B, b = a % (size_t)B, w = std::min<size_t>((size_t)B - b, c0 + (size_t)n - a);
+                HIPCHK(c, hipMemcpy2DAsync(rep_loglik_KxTxB + k * (size_t)T * B + b, (size_t)B * 8, d_rl + (a - c0), ld * 8, w * 8, (size_t)T,
+                                           hipMemcpyDeviceToHost, c->stream));
+                a += w;
+            }
+        if (counts_KxBxS) HIPCHK(c, hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)n * Sp * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's buffers are reused by the next one
+        if (counts_KxBxS)
+            for (int b = 0; b < n; ++b)
+                for (int s = 0; s < S; ++s) counts_KxBxS[(c0 + (size_t)b) * S + s] = h_cnt[(size_t)b * Sp + s];
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_rm0, c->ev_rm1));
+        ms_total += ms;
+    }
+    HIPCHK(c, hipMemcpyAsync(wins_KxT, d_wins, (size_t)K * T * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * K * B;
+        st.alg_bytes = 8.0 * (double)T * S + 12.0 * (double)ntiles * K * B;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
 // ---- branch-length derivatives of a scored tree set (phylo_treegrad.h) ----
 int phylo_trees_grad(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T, double* grad,
                      double* curv, phylo_stats* perf) {
@@ -1804,6 +1928,14 @@ int phylo_trees_grad_rates(phylo_ctx* c, int T, const int32_t* child, const doub
 int phylo_debug_rell_host(int T, int S, const double* site_lik_TxS, int b0, int nB, uint64_t seed, int32_t* counts, double* x, double* rl) {
     char msg[200];
     if (pr_rell_host(T, S, site_lik_TxS, b0, nB, seed, counts, x, rl, msg, sizeof msg)) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_rell_host: %s", msg);
+    return PHYLO_OK;
+}
+
+int phylo_debug_rell_multiscale_host(int T, int S, const double* site_lik_TxS, int K, const int32_t* draws_K, int k0, int b0, int nB, uint64_t seed,
+                                     int32_t* counts, double* rl, int32_t* best) {
+    char msg[200];
+    if (prm_rell_host(T, S, site_lik_TxS, K, draws_K, k0, b0, nB, seed, counts, rl, best, msg, sizeof msg))
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_rell_multiscale_host: %s", msg);
     return PHYLO_OK;
 }
 

@@ -113,19 +113,16 @@ __device__ __forceinline__ void pr_panel_store(const pr_panel& p, double* xs, do
     }
 }
 
-// rl[t][b] for a chunk's columns.  Workgroup = 64 trees x 128 columns, four waves of 32 x 64 = 2 x 4 MFMA tiles each; every wave
-// walks ALL sites in steps of 4 with its eight accumulators in registers.  Operand lanes (the probe's): A[row l & 15][k l >> 4],
+// A workgroup's walk over ALL sites for its 64 trees x 128 columns (t0, b0), four waves of 32 x 64 = 2 x 4 MFMA tiles each, in
+// steps of 4 sites with a wave's eight accumulators in registers: the body of pr_replicates and of prm_product (phylo_rell_ms.h),
+// which differ in their epilogues alone.  xs, cs: the workgroup's panels.  Operand lanes (the probe's): A[row l & 15][k l >> 4],
 // B[k l >> 4][col l & 15], D col l & 15, row (l >> 4) + 4 reg.  Trees, columns and sites past the end enter as 0.0 / count 0
 // (fma(0, x, acc) == acc bit for bit: acc starts at +0.0, x is finite), so no MFMA sits under a divergent guard.
-__global__ __launch_bounds__(256) void pr_replicates(const double* __restrict__ x, const uint16_t* __restrict__ cnt, int T, int S, size_t Sp, int ncols,
-                                                     double* __restrict__ rl, size_t ldr) {
-    __shared__ __attribute__((aligned(16))) double xs[PR_KP * PR_XS];
-    __shared__ __attribute__((aligned(16))) double cs[PR_KP * PR_CS];
+__device__ __forceinline__ void pr_walk(pr_d4 (&acc)[2][4], const double* __restrict__ x, const uint16_t* __restrict__ cnt, int T, int S, size_t Sp,
+                                        int ncols, int t0, int b0, double* xs, double* cs) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t0 = blockIdx.x * PR_TT, b0 = blockIdx.y * PR_TB;
     const int wt = (wave & 1) * 32, wb = (wave >> 1) * 64;
     const int r = lane & 15, kk = lane >> 4;
-    pr_d4 acc[2][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -152,6 +149,19 @@ __global__ __launch_bounds__(256) void pr_replicates(const double* __restrict__ 
                 for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     }
+}
+
+// rl[t][b] for a chunk's columns: the walk, then every score stored
+__global__ __launch_bounds__(256) void pr_replicates(const double* __restrict__ x, const uint16_t* __restrict__ cnt, int T, int S, size_t Sp, int ncols,
+                                                     double* __restrict__ rl, size_t ldr) {
+    __shared__ __attribute__((aligned(16))) double xs[PR_KP * PR_XS];
+    __shared__ __attribute__((aligned(16))) double cs[PR_KP * PR_CS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t0 = blockIdx.x * PR_TT, b0 = blockIdx.y * PR_TB;
+    const int wt = (wave & 1) * 32, wb = (wave >> 1) * 64;
+    const int r = lane & 15, kk = lane >> 4;
+    pr_d4 acc[2][4];
+    pr_walk(acc, x, cnt, T, S, Sp, ncols, t0, b0, xs, cs);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll

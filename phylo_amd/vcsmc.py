@@ -458,14 +458,25 @@ class VCSMC:
             return [float(x) for x in res[0]], res[1]
         return [float(x) for x in res]
 
-    def tree_tests(self, site_lik, B, seed):
+    def tree_tests(self, site_lik, B, seed, au=None):
         """tree_tests.json of --tree_tests: the RELL bootstrap (phylo_rell) over the site factors of the scored trees and the
-        statistics phylo_amd.treetests reads off it"""
+        statistics phylo_amd.treetests reads off it; with au (--tree_tests_au: 'default' or r1,r2,...) also the AU test, from
+        the multiscale bootstrap (phylo_rell_multiscale) on the same site factors, B and seed"""
         from . import treetests
         out = self._context().rell(site_lik, B, seed, want_reps=True)
         st = treetests.tree_tests(out['obs'], out['wins'], B, reps=out['rep_loglik'])
-        return {'B': int(B), 'seed': int(seed), 'best': int(st['best']), 'obs': out['obs'].tolist(), 'bp': st['bp'].tolist(),
-                'p_kh': st['p_kh'].tolist(), 'p_sh': st['p_sh'].tolist(), 'c_elw': st['c_elw'].tolist()}
+        res = {'B': int(B), 'seed': int(seed), 'best': int(st['best']), 'obs': out['obs'].tolist(), 'bp': st['bp'].tolist(),
+               'p_kh': st['p_kh'].tolist(), 'p_sh': st['p_sh'].tolist(), 'c_elw': st['c_elw'].tolist()}
+        if au:                                             # (absent without the flag: the file is what it was before it existed)
+            sc = treetests.au_scales(np.asarray(site_lik).shape[1], au)
+            ms = self._context().rell_multiscale(site_lik, sc['draws'], B, seed)
+            fit = treetests.au_test(ms['wins'], sc['sigma2'], B)
+            nn = lambda a: [None if x != x else float(x) for x in a]       # NaN (no fit for that tree) is null in JSON
+            res.update(p_au=fit['p_au'].tolist(), se_au=nn(fit['se_au']), au_d=nn(fit['d']), au_c=nn(fit['c']),
+                       au_ok=[bool(x) for x in fit['au_ok']],
+                       au_scales={'r': sc['r'].tolist(), 'draws': sc['draws'].tolist(), 'sigma2': sc['sigma2'].tolist()},
+                       bp_scales=fit['bp'].tolist())
+        return res
 
     def _tree_scores(self, path):
         """tree_scores.json of --score_trees: the file's trees, and with branch lengths in the posterior also map.tre,
@@ -526,7 +537,7 @@ class VCSMC:
             ll = self.score_trees(newicks, rates=mix)
         if tests and newicks:                              # (with --score_opt: the site factors at the ML lengths)
             from . import treetests
-            self.tree_test_results = self.tree_tests(sites, *treetests.parse_spec(tests))
+            self.tree_test_results = self.tree_tests(sites, *treetests.parse_spec(tests), au=getattr(self.args, 'tree_tests_au', None))
         out = {'model': {'Q': np.asarray(self.Qmatrix, dtype=np.float64).tolist(),
                          'pi': np.asarray(self.stationary_probs, dtype=np.float64).reshape(-1).tolist(),
                          'jc69_closed_form': bool(self.args.jcmodel)},
@@ -573,7 +584,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'score_opt', 'score_fit', 'score_search', 'score_fit_search', 'score_model_fit') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'tree_tests_au', 'score_opt', 'score_fit', 'score_search', 'score_fit_search', 'score_model_fit') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))

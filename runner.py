@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--score_model_fit`, `--tree_tests` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--score_model_fit`, `--tree_tests`, `--tree_tests_au` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -109,7 +109,20 @@ def parse_args(argv=None):
                              "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
                              "--score_rates if given) writes tree_tests.json beside tree_scores.json: per tree the observed score, "
                              "the bootstrap proportion, the p-values of the KH and SH tests and the expected likelihood weight")
+    parser.add_argument('--tree_tests_au', default=None, metavar='default|r1,r2,...',
+                        help="with --tree_tests: also Shimodaira's approximately unbiased (AU) test, from a multiscale RELL bootstrap "
+                             "on the same site likelihoods, B and SEED -- B replicates of r_k S sites at every scale r_k "
+                             "('default': 0.5, 0.6, ..., 1.4); adds p_au, se_au, au_d, au_c, au_ok, au_scales and bp_scales to "
+                             "tree_tests.json")
     args = parser.parse_args(argv)
+    if args.tree_tests_au is not None:
+        if args.tree_tests is None:
+            parser.error('--tree_tests_au needs --tree_tests B[:SEED] (it adds the AU test to the tests made there)')
+        from phylo_amd import treetests
+        try:
+            treetests.au_ratios(args.tree_tests_au)
+        except ValueError as e:
+            parser.error('--tree_tests_au: %s' % e)
     if args.score_fit_search is not None:
         kind, _, rounds = str(args.score_fit_search).partition(':')
         if kind != 'nni' or (rounds and not (rounds.isdigit() and int(rounds) >= 1)):

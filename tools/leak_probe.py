@@ -44,6 +44,7 @@ def cycle(i):
         c.sweep_batch_async([1, 2, 3, 4], _ffi.FLAGS_DEFAULT | _ffi.KEEP_GRAPH)   # the batched graph and its reverse pass
         c.sweep_backward_batch(4)
         c.rell(np.full((40 + i % 8, 300), 0.25), 64, i)     # the bootstrap's own slab (logs, counts, replicate scores)
+        c.rell_multiscale(np.full((40 + i % 8, 300), 0.25), (150, 300, 420), 64, i, want_reps=i % 2 == 1)   # ... and the multiscale one's
         child = np.array([[j - 1 + N if j else 0, j + 1] for j in range(N - 1)], dtype=np.int32)   # a caterpillar, 30 .. 37 times
         n = 30 + i % 8
         c.trees_grad(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1), want_curv=True)   # the gradient's own slab and node stores

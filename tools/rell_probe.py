@@ -8,7 +8,11 @@ wall time of the same product in NumPy, `x @ counts.T`, on the threads the proce
 The site factors are those of phylo_trees_loglik on random trees.  The call is timed whole `--runs` times after a warm-up (wall,
 and perf.sweep_ms from hipEvents: the kernels, without the upload of the factors and the copies back); medians with the
 quartiles.  A few replicates at both ends are checked bit for bit against the host loop (phylo_debug_rell_host).  Appends one
-JSON line to --out."""
+JSON line to --out.
+
+    python tools/rell_probe.py --multiscale --dataset hohna_data --trees 4096 --reps 1000 --out profiles/rell_probe.jsonl
+
+times phylo_rell_multiscale at the scales of --scales against one phylo_rell call per scale."""
 import argparse
 import json
 import os
@@ -43,6 +47,56 @@ def quartiles(x):
     return {'median': float(q2), 'q1': float(q1), 'q3': float(q3)}
 
 
+def multiscale(a, ctx, sites, N, S):
+    """--multiscale: phylo_rell_multiscale at the scales of --scales against the parent's path to the same replicates, K calls of
+    phylo_rell at the same B (which can only draw S sites: nearly the same multiply-adds, not the same samples).  Interleaved, one
+    warm-up each; medians with quartiles of --runs."""
+    from phylo_amd import treetests
+    T, B = a.trees, a.reps
+    sc = treetests.au_scales(S, a.scales)
+    K = len(sc['draws'])
+    ms = ctx.rell_multiscale(sites, sc['draws'], B, a.seed)                 # warm-ups
+    ctx.rell(sites, B, a.seed)
+    dev, wall, dev_plain, wall_plain = [], [], [], []
+    for _ in range(a.runs):
+        t0 = time.perf_counter()
+        ms = ctx.rell_multiscale(sites, sc['draws'], B, a.seed)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        dev.append(ms['stats']['sweep_ms'])
+        t0 = time.perf_counter()
+        d = 0.0
+        for k in range(K):
+            d += ctx.rell(sites, B, a.seed + k)['stats']['sweep_ms']
+        wall_plain.append((time.perf_counter() - t0) * 1e3)
+        dev_plain.append(d)
+    # a few replicates at both ends of the first and the last scale against the host loop, through the instance that stores nothing
+    full = ctx.rell_multiscale(sites, sc['draws'], B, a.seed, want_best=True)
+    n = min(4, B)
+    same = bool(np.array_equal(full['wins'], ms['wins'])) and bool((full['wins'].sum(axis=1) == B).all())
+    for k in sorted({0, K - 1}):
+        for b0 in sorted({0, B - n}):
+            host = _ffi.debug_rell_multiscale_host(sites, sc['draws'], k, b0, n, a.seed, want_counts=False, want_reps=False)
+            same = same and bool(np.array_equal(host['best'], full['best'][k, b0:b0 + n]))
+    same = same and bool(np.array_equal(np.stack([np.bincount(r, minlength=T) for r in full['best']]), full['wins']))
+    fit = treetests.au_test(ms['wins'], sc['sigma2'], B)
+    order = np.argsort(-ctx.rell(sites, 1, a.seed)['obs'])[:5]              # the five best trees by observed score
+    d, w, dp, wp = quartiles(dev), quartiles(wall), quartiles(dev_plain), quartiles(wall_plain)
+    units = float(T) * S * B * float(np.sum(sc['draws'])) / S               # multiply-adds that carry a draw: T B sum_k n_k
+    sp, tiles = (S + 3) // 4 * 4, (T + 63) // 64
+    rec = {'probe': 'rell_multiscale', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': T, 'B': B, 'K': K, 'runs': a.runs,
+           'r': sc['r'].tolist(), 'draws': sc['draws'].tolist(), 'device_ms': d, 'wall_ms': w, 'launches': ms['stats']['n_launches'],
+           'plain_calls_device_ms': dp, 'plain_calls_wall_ms': wp, 'ratio_plain_over_multiscale_device': dp['median'] / d['median'],
+           'ratio_plain_over_multiscale_wall': wp['median'] / w['median'], 'units_T_S_K_B': ms['stats']['units'],
+           'units_per_s_device': ms['stats']['units'] / (d['median'] * 1e-3), 'drawn_units': units,
+           'columns_per_chunk': min((256 << 20) // (sp * 2 + tiles * 12 + 4), 1 << 20, K * B),
+           'columns_per_chunk_limit': min((256 << 20) // (sp * 2 + tiles * 12 + 4), 1 << 20),
+           'bit_equal_host_loop': same,
+           'au_of_best_trees': [{'tree': int(t), 'p_au': float(fit['p_au'][t]), 'se_au': float(fit['se_au'][t]) if fit['au_ok'][t] else None, 'rss': float(fit['rss'][t]),
+                                 'df': int(fit['df'][t]), 'au_ok': bool(fit['au_ok'][t]), 'bp': float(fit['bp'][int(np.argmin(np.abs(sc['sigma2'] - 1)))][t])}
+                                for t in order]}
+    return rec, same
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -52,6 +106,9 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--numpy_runs', type=int, default=3, help='timed x @ counts.T products (0: skip the yardstick)')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--multiscale', action='store_true',
+                    help='time phylo_rell_multiscale (the AU test\'s resampling) against one phylo_rell call per scale instead')
+    ap.add_argument('--scales', default='default', help="with --multiscale: 'default' (r = 0.5 .. 1.4) or r1,r2,...")
     a = ap.parse_args(argv)
     g = load_dataset(a.dataset)['genome']
     N, S, _ = g.shape
@@ -63,6 +120,15 @@ def main(argv=None):
         ctx.set_leaves(g)
         ctx.set_model(model.get_Q(model.init_y_q()), np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0))
         ll, sites = ctx.trees_loglik(child, blen, want_sites=True)
+        if a.multiscale:
+            rec, same = multiscale(a, ctx, sites, N, S)
+            line = json.dumps(rec)
+            print(line)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, 'a') as f:
+                    f.write(line + '\n')
+            return 0 if same else 1
         full = ctx.rell(sites, B, a.seed, want_reps=True, want_counts=True, want_logs=True)      # warm-up, and the arrays to compare
         wall, dev, wall_reps = [], [], []
         for _ in range(a.runs):
