@@ -79,20 +79,22 @@ def missing_moves(child):
     return out
 
 
-def explicit(name, ctx, child, blen, ll, delta, prior, S, rates, weights, tol=TOL_EXPL_RATES):
-    """loglik + delta against phylo_trees_loglik_rates of every explicitly built neighbour"""
+def explicit(name, ctx, child, blen, ll, delta, prior, S, rates, weights, tol=TOL_EXPL_RATES, moves=nni_moves):
+    """loglik + delta against phylo_trees_loglik_rates of every explicitly built neighbour (moves: which of a tree's moves, every
+    one by default; tol: the bound of the deep trees, treenni_rates_edges_cases.TOL_EXPL_RATES_BIG).  Returns the worst ratio to
+    the bound."""
     _, sites = ctx.trees_loglik_rates(child, blen, rates, weights, prior=prior, want_sites=True)
     with np.errstate(divide='ignore'):
         a0 = np.abs(np.log(sites)).sum(axis=1)
     cs, bs, at = [], [], []
     for t in range(child.shape[0]):
-        for mv in nni_moves(child[t]):
+        for mv in moves(child[t]):
             c2, b2 = apply_nni(child[t], blen[t], *mv)
             cs.append(c2)
             bs.append(b2)
             at.append((t,) + mv)
     if not cs:
-        return
+        return 0.0
     ll2, sites2 = ctx.trees_loglik_rates(np.array(cs), np.array(bs), rates, weights, prior=prior, want_sites=True)
     worst = 0.0
     for (t, r, sd), x, s2 in zip(at, ll2, sites2):
@@ -105,6 +107,7 @@ def explicit(name, ctx, child, blen, ll, delta, prior, S, rates, weights, tol=TO
         assert err <= tol, (name, t, r, sd, lhs, x, err, tol)
     print("%s: worst |(loglik + delta) - loglik of the neighbour| / (S + sum |log m| + sum |log m'|) = %.3g (bound %.3g) over %d moves"
           % (name, worst, tol, len(at)))
+    return worst / tol
 
 
 # ---- 1. shapes, conditions and mixtures -------------------------------------------------------------------------------------------

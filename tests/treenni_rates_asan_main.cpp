@@ -1,6 +1,7 @@
 // Stand-alone host program for tests/test_treenni_rates_cpu.py: the host half of phylo_amd/csrc/phylo_treenni_rates.h -- the plan of
 // a call (chunk of trees, slab layout, capped grid) and the LDS of a launch with its refusal -- every output checked against its
-// definition (built with -fsanitize=address,undefined).  No GPU, nothing of the library.
+// definition (built with -fsanitize=address,undefined).  No GPU, nothing of the library.  With six arguments (N, site tiles, T, C,
+// coded, compute units) it prints that call's chunk and grid instead.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -38,7 +39,13 @@ static long check_plan(int N, int ntiles, int T, int C, bool coded, int n_cus, i
     return bad;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc == 7) {               // N ntiles T C coded cus: the plan's chunk and grid, for tests/test_treenni_rates_edges_cpu.py
+        ptnr_plan q;
+        if (ptnr_make_plan(atoi(argv[1]), atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]) != 0, atoi(argv[6]), 0, &q)) return 2;
+        printf("chunk %d grid %d per_tree %zu wg_store %zu\n", q.chunk, q.grid, q.per_tree, q.wg_store);
+        return 0;
+    }
     long bad = 0;
     const int Ns[] = {2, 3, 4, 5, 12, 33, 70, 128, 511, 512};
     const int tiles[] = {1, 2, 3, 64};
