@@ -482,6 +482,21 @@ int phylo_debug_site_patterns(const uint8_t* codes, int N, int S, int32_t* U, in
                               uint8_t* rep_leaf, int64_t rep_leaf_cap);
 int phylo_debug_site_patterns_rule(int S, int U, int coded, int ntiles, int sw);
 int phylo_debug_site_patterns_of(phylo_ctx* ctx, int32_t* U, int32_t* taken);
+/* Test hooks of the clade tables of the site-pattern form (phylo_site_patterns.h), the first two without a GPU.
+ * phylo_debug_clade_patterns_rule: 1 if leaves of N taxa, S sites and U distinct columns whose merges take the pattern form
+ * (pat_taken != 0) get clade tables under PHYLO_CLADE_PATTERNS = 0 (sw 0), unset (1) or force (2), else 0; -1 for bad arguments.
+ * *bytes (may be NULL) = the tables' size.
+ * phylo_debug_clade_tables: the tables of byte codes [N][S], N <= 12.  *U as above; layout[5] = the bytes of the strided byte
+ * codes, of a block's representatives, of its site image, a block's stride, the whole buffer.  With tables NULL nothing else is
+ * written; otherwise cap >= layout[4] and U <= 512 are required, block Z lies at layout[0] + Z layout[3] (header word 0 = U_Z at
+ * +0, representatives at +256, image behind them; blocks of fewer than three leaves are not written) and cls, if given, receives
+ * [2^N][U] 16-bit class numbers (every bitset, the small ones included).
+ * phylo_debug_clade_patterns_of: whether the context's current leaves have tables that a record-form sweep would use, whether the
+ * last sweep begun on the launch path took them (the plan's clade_pat), and the tables' bytes (0: none).
+ * phylo_debug_sweep_plan: bit 6 of `switches` states that the tables are there; the plan's clade_pat is bit 27 of *mask. */
+int phylo_debug_clade_patterns_rule(int pat_taken, int N, int S, int U, int sw, int64_t* bytes);
+int phylo_debug_clade_tables(const uint8_t* codes, int N, int S, int32_t* U, int64_t* layout, uint8_t* tables, int64_t cap, uint16_t* cls);
+int phylo_debug_clade_patterns_of(phylo_ctx* ctx, int32_t* eligible, int32_t* taken, int64_t* bytes);
 /* ... after a batched sweep of G groups (K the total): the device lists' limit is per group (K / G <= 8192), every other
  * limit sees the totals.  G = 1 is phylo_debug_reverse_plan. */
 int phylo_debug_reverse_plan_batch(int N, int K, int G, int S, uint32_t switches, int64_t n_slow, int TS, int64_t coeff_wgs,

@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_sweep_chain", "phylo_debug_sweep_chain_of", "phylo_debug_scan_ancestors", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_persist_plan", "phylo_debug_persist_of", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_sweep_chain", "phylo_debug_sweep_chain_of", "phylo_debug_scan_ancestors", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_clade_patterns_rule", "phylo_debug_clade_tables", "phylo_debug_clade_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_persist_plan", "phylo_debug_persist_of", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -243,6 +243,69 @@ def debug_site_patterns_rule(S, U, coded=True, ntiles=1, switch=None):
     if rc < 0:
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     return bool(rc)
+
+
+CLADE_MAX_TAXA = 12                                        # PK_CLADE_MAX_N
+CLADE_MAX_BYTES = 32 << 20                                 # PK_CLADE_MAX_BYTES
+
+
+def debug_clade_patterns_rule(N, S, U, pat_taken=True, switch=None):
+    """(taken, bytes): do leaves of N taxa, S sites and U distinct columns get the clade tables of the pattern form, and the
+    tables' size (no GPU needed)?  switch: PHYLO_CLADE_PATTERNS' value, "0", None or "force"."""
+    lib = load()
+    nbytes = C.c_int64(0)
+    rc = lib.phylo_debug_clade_patterns_rule(C.c_int(int(pat_taken)), C.c_int(N), C.c_int(S), C.c_int(U), C.c_int(SITE_PATTERN_SWITCH[switch]),
+                                             C.byref(nbytes))
+    if rc < 0:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return bool(rc), nbytes.value
+
+
+def debug_clade_tables(codes):
+    """The clade tables phylo_set_leaves builds from byte codes [N][S], N <= 12 (phylo_site_patterns.h; no GPU needed): a dict with U,
+    'codes' (uint8 [N][leaf stride], the strided byte codes), 'cls' (uint16 [2^N][U], the class of every global pattern in every
+    leaf bitset) and 'blocks': {Z: {'U': U_Z, 'rep_off': uint32 [64 (ceil(U / 64) + 2)], 'image': uint16 [nC][2][64][8]}} for
+    every bitset Z of at least three leaves."""
+    lib = load()
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.ndim != 2:
+        raise ValueError("codes must be [N][S]")
+    N, S = cd.shape
+    U = C.c_int32(0)
+    lay = (C.c_int64 * 5)()
+    rc = lib.phylo_debug_clade_tables(_ptr(cd), C.c_int(N), C.c_int(S), C.byref(U), lay, None, C.c_int64(0), None)
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    codes_bytes, rep_bytes, image_bytes, stride, total = (int(x) for x in lay)
+    buf = np.full(total, 0xff, dtype=np.uint8)
+    cls = np.full((1 << N) * U.value, 0xffff, dtype=np.uint16)
+    rc = lib.phylo_debug_clade_tables(_ptr(cd), C.c_int(N), C.c_int(S), C.byref(U), lay, _ptr(buf), C.c_int64(total), _ptr(cls))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    blocks = {}
+    for Z in range(1 << N):
+        if bin(Z).count("1") < 3:
+            continue
+        b = buf[codes_bytes + Z * stride: codes_bytes + (Z + 1) * stride]
+        blocks[Z] = {"U": int(b[:4].view(np.uint32)[0]), "rep_off": b[256:256 + rep_bytes].view(np.uint32).copy(),
+                     "image": b[256 + rep_bytes:].view(np.uint16).reshape(-1, 2, 64, 8).copy()}
+    return {"U": U.value, "codes": buf[:codes_bytes].reshape(N, -1).copy(), "cls": cls.reshape(1 << N, U.value), "blocks": blocks,
+            "layout": {"codes_bytes": codes_bytes, "rep_bytes": rep_bytes, "image_bytes": image_bytes, "stride": stride, "total": total}}
+
+
+def debug_sweep_plan_clade(N, K, S, clade_tables=True, **kw):
+    """The plan's clade_pat (bit 27 of the mask) for debug_sweep_plan's arguments, with the clade tables of the leaves there or not."""
+    lib = load()
+    sw = sum(1 << SWEEP_PLAN_SWITCHES.index(name) for name in kw.get("switches", ())) | (64 if clade_tables else 0)
+    mask = C.c_uint32(0)
+    launches = (C.c_int32 * (max(N, 1) + 1))()
+    K_local = kw.get("K_local")
+    rc = lib.phylo_debug_sweep_plan(C.c_int(N), C.c_int(K), C.c_int(K if K_local is None else K_local), C.c_int(S), C.c_int(kw.get("G", 1)),
+                                    C.c_int(kw.get("M", 1)), C.c_int(kw.get("world", 1)), C.c_int(int(kw.get("transport", False))),
+                                    C.c_uint32(kw.get("flags", 0)), C.c_uint32(sw), C.byref(mask), launches)
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return bool(mask.value >> 27 & 1)
 
 
 TREE_SUMMARY_BUFS = ("u", "U", "bits", "kA", "kB", "val", "scan", "weight", "srt", "hp", "o_cbits", "o_cw", "o_tw", "child", "slot", "o_cg",
@@ -1065,6 +1128,13 @@ class Context:
         U, taken = C.c_int32(0), C.c_int32(0)
         self._check(self._lib.phylo_debug_site_patterns_of(self._h, C.byref(U), C.byref(taken)))
         return U.value, bool(taken.value)
+
+    def debug_clade_patterns(self):
+        """(eligible, taken, bytes): the current leaves have clade tables that a record-form sweep would use; the last sweep begun on
+        the launch path took them (its plan's clade_pat); the tables' size (0: none)"""
+        el, taken, nbytes = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._check(self._lib.phylo_debug_clade_patterns_of(self._h, C.byref(el), C.byref(taken), C.byref(nbytes)))
+        return bool(el.value), bool(taken.value), nbytes.value
 
     def debug_tree_branches(self):
         """The plan the last tree_branches() of this context took: {'wide': 64-bit (topology, clade) keys, 'cbits', 'tbits'}"""

@@ -74,6 +74,7 @@ struct env_switches {
     int scan_multi_min = 4096;           // PHYLO_SCAN_MULTI_MIN: groups of more weights than this are scanned by several workgroups
     int scan_ancestors = 1;              // PHYLO_SCAN_ANCESTORS: 0 = no chain form of a rank event (sweep_chain_form_of)
     int site_patterns = PK_PAT_AUTO;     // PHYLO_SITE_PATTERNS: 0 = never the pattern form of the merge, force = wherever it is valid
+    int clade_patterns = PK_CLADE_AUTO;  // PHYLO_CLADE_PATTERNS: 0 = never the clade tables of the pattern form, force = wherever they are eligible
     int trees_chunk = 0;                 // PHYLO_TREES_CHUNK: trees per chunk of phylo_trees_loglik (0 = what PT2_SCRATCH_BYTES holds; tests lower it)
     int rell_chunk = 0;                  // PHYLO_RELL_CHUNK: replicates per chunk of phylo_rell, columns per chunk of phylo_rell_multiscale (0 = what PR_CHUNK_BYTES holds; tests lower it)
     void read() {
@@ -92,6 +93,7 @@ struct env_switches {
         { const char* e = getenv("PHYLO_TREE_WIDE_KEYS"); tree_wide_keys = e && atoi(e) != 0; }
         { const char* e = getenv("PHYLO_REMOTE_CACHE_CAP"); remote_cache_cap = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_SITE_PATTERNS"); site_patterns = !e ? PK_PAT_AUTO : !strcmp(e, "force") ? PK_PAT_FORCE : atoi(e) == 0 ? PK_PAT_OFF : PK_PAT_AUTO; }
+        { const char* e = getenv("PHYLO_CLADE_PATTERNS"); clade_patterns = !e ? PK_CLADE_AUTO : !strcmp(e, "force") ? PK_CLADE_FORCE : atoi(e) == 0 ? PK_CLADE_OFF : PK_CLADE_AUTO; }
         { const char* e = getenv("PHYLO_SCAN_MULTI_MIN"); scan_multi_min = e ? atoi(e) : 4096; }
         { const char* e = getenv("PHYLO_SCAN_ANCESTORS"); scan_ancestors = e ? atoi(e) : 1; }
         { const char* e = getenv("PHYLO_TREES_CHUNK"); trees_chunk = e ? atoi(e) : 0; }
@@ -140,6 +142,15 @@ struct phylo_ctx {
     uint8_t* d_pat = nullptr;            // behind both, the site-pattern tables (phylo_site_patterns.h): pattern image, representatives,
     int pat_U = 0;                       // representative leaf image; pat_U: distinct columns of the current leaves (0: not coded)
     bool leaves_coded = false;
+    // clade patterns (phylo_site_patterns.h): the strided byte codes and one block per leaf bitset, built by phylo_set_leaves where
+    // the rule takes them; first-use, grow-only, uploaded from a pinned image of their own
+    uint8_t* d_clade = nullptr;
+    uint8_t* h_clade_p = nullptr;
+    size_t clade_cap = 0;                // bytes both buffers hold
+    pk_clade_layout clade_layout{};      // of the current leaves (clade_ready)
+    bool clade_ready = false;            // the tables of the current leaves are on the device (or on their way, on the stream)
+    hipEvent_t ev_clade = nullptr;
+    int32_t* d_bits[2] = {nullptr, nullptr};   // [K][N] leaf bitset of every root, two planes (allocated by the first sweep that takes the form)
     uint32_t* d_pair_hist = nullptr;     // [N][N][32] code-pair site counts of coded leaves (built on the first twisted sweep)
     bool hist_ready = false, codes_valid = false;
     // sweep state
@@ -430,6 +441,8 @@ void free_sweep_state(phylo_ctx* c) {
     c->pctr_dirty = false;
     if (c->d_tilev) (void)hipFree(c->d_tilev);
     c->d_tilev = nullptr;
+    if (c->d_bits[0]) (void)hipFree(c->d_bits[0]);
+    c->d_bits[0] = c->d_bits[1] = nullptr;
     void* ptrs[] = {c->d_pool, c->d_nodell, c->d_bl, c->d_br, c->d_Pmat, c->d_logw, c->d_ll, c->d_aux, c->d_lse, c->d_group_seeds,
                     c->d_tables, (void*)c->d_tab_ptrs, c->d_child, c->d_merges, c->d_anc,
                     c->d_cdf[0], c->d_cdf[1], c->d_anc_next, c->d_adopt_list, c->d_adopt_cnt, c->d_counter, (void*)c->d_pool_ptrs, c->d_mark, c->d_sync, c->d_mirror, c->d_cache, c->d_rec};
@@ -834,7 +847,7 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->bgstream) (void)hipStreamSynchronize(c->bgstream);
     phylo_comm_destroy(&c->comm);
     free_sweep_state(c);
-    void* ptrs[] = {c->d_Q, c->d_ldf, c->d_leaves, c->d_leaf_codes};
+    void* ptrs[] = {c->d_Q, c->d_ldf, c->d_leaves, c->d_leaf_codes, c->d_clade};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& b : c->scratch)
@@ -877,6 +890,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->h_model_p) (void)hipHostFree(c->h_model_p);
     if (c->ev_leaves) (void)hipEventDestroy(c->ev_leaves);
     if (c->h_leaves_p) (void)hipHostFree(c->h_leaves_p);
+    if (c->ev_clade) (void)hipEventDestroy(c->ev_clade);
+    if (c->h_clade_p) (void)hipHostFree(c->h_clade_p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return PHYLO_OK;
@@ -947,12 +962,33 @@ int phylo_set_leaves(phylo_ctx* c, const double* genome) {
         c->leaves_coded = ok && !c->env.no_leaf_codes;   // the access-path optimisation can be switched off
         c->hist_ready = false;
         c->pat_U = 0;
+        c->clade_ready = false;
         if (ok) {
             pk_pack_leaf_codes(codes, c->N, c->S, codes + pk_packed_offset(c->N, c->S));
             // the site-pattern tables go up only where a launch can read them (U within the table's cap)
-            c->pat_U = pk_pat_build(codes, c->N, c->S, codes + pk_pat_offset(c->N, c->S));
+            std::vector<int32_t> pat, rep;
+            c->pat_U = pk_pat_build(codes, c->N, c->S, codes + pk_pat_offset(c->N, c->S), pat, rep);
             const size_t up_bytes = c->pat_U <= PK_PAT_MAX_U ? code_bytes : pk_codes_image_bytes(c->N, c->S);
             HIPCHK(c, hipMemcpyAsync(c->d_leaf_codes, codes, up_bytes, hipMemcpyHostToDevice, c->stream));
+            // the clade tables, where the rule takes them (the site tile may still change: the sweep's plan asks pat_on again)
+            if (pk_clade_take(pk_pat_take(c->S, c->pat_U, c->leaves_coded, 1, c->env.site_patterns), c->N, c->S, c->pat_U, c->env.clade_patterns)) {
+                const pk_clade_layout L = pk_clade_layout_of(c->N, c->S, c->pat_U);
+                if (L.total > c->clade_cap) {
+                    if (c->d_clade) HIPCHK(c, hipFree(c->d_clade));
+                    if (c->h_clade_p) HIPCHK(c, hipHostFree(c->h_clade_p));
+                    c->d_clade = nullptr; c->h_clade_p = nullptr; c->clade_cap = 0;
+                    HIPCHK(c, hipMalloc((void**)&c->d_clade, L.total));
+                    HIPCHK(c, hipHostMalloc((void**)&c->h_clade_p, L.total));
+                    c->clade_cap = L.total;
+                }
+                if (!c->ev_clade) HIPCHK(c, hipEventCreateWithFlags(&c->ev_clade, hipEventDisableTiming));
+                else HIPCHK(c, hipEventSynchronize(c->ev_clade));
+                pk_clade_build(codes, c->N, c->S, pat.data(), rep.data(), c->pat_U, c->h_clade_p, nullptr);
+                HIPCHK(c, hipMemcpyAsync(c->d_clade, c->h_clade_p, L.total, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipEventRecord(c->ev_clade, c->stream));
+                c->clade_layout = L;
+                c->clade_ready = true;
+            }
         }
     }
     if (pinned) HIPCHK(c, hipEventRecord(c->ev_leaves, c->stream));
@@ -2227,6 +2263,7 @@ static sweep_facts sweep_facts_of(const phylo_ctx* c, uint32_t flags, int M, int
     sweep_facts_flags(f, flags);
     f.env_eager_nodes = c->env.eager_nodes; f.env_rehearse_sharded = c->env.rehearse_sharded;
     f.env_replicated_book = c->env.replicated_book;
+    f.clade_tables = c->clade_ready && pk_pat_take(c->S, c->pat_U, c->leaves_coded, c->ntiles, c->env.site_patterns);
     return f;
 }
 
@@ -2341,6 +2378,10 @@ static int sweep_alloc(phylo_ctx* c, const sweep_plan& p, int M) {
         if (p.twist) CHK(sweep_alloc_twist_history(c, M));
     }
     if (p.want_rdraw && !c->d_rdraw) CHK(dalloc(c, &c->d_rdraw, (size_t)p.R * c->K));
+    if (p.clade_pat && !c->d_bits[0]) {
+        CHK(dalloc(c, &c->d_bits[0], 2 * (size_t)c->K * c->N));
+        c->d_bits[1] = c->d_bits[0] + (size_t)c->K * c->N;
+    }
     return PHYLO_OK;
 }
 
@@ -2359,6 +2400,7 @@ static int sweep_prologue(phylo_ctx* c, const sweep_plan& p, uint64_t seed, cons
         pa.group_seeds = G > 1 ? (const uint64_t*)c->d_group_seeds : (const uint64_t*)nullptr;
         pa.rdraw = p.want_rdraw ? c->d_rdraw : (unsigned long long*)nullptr;
         pa.roots = t_roots; pa.cnt = t_cnt; pa.rootll = t_rootll; pa.nodell = c->d_nodell; pa.K = K; pa.N = N;
+        pa.bits = p.clade_pat ? c->d_bits[0] : (int32_t*)nullptr;
         pa.mark = p.lazy ? c->d_mark : (unsigned int*)nullptr;
         pa.mark_words = p.lazy ? (unsigned int)mark_words : 0u;
         const int NT = p.sorted_prologue ? 256 : 64;
@@ -2582,6 +2624,7 @@ static pk_rank_args rank_args(const phylo_ctx* c, int r) {
         b.roots_old = c->d_roots[cur]; b.cnt_old = c->d_cnt[cur];
         b.roots_new = c->d_roots[nxt]; b.cnt_new = c->d_cnt[nxt];
         b.rootll_old = c->d_rootll[cur]; b.rootll_new = c->d_rootll[nxt];
+        if (p.clade_pat) { b.bits_old = c->d_bits[cur]; b.bits_new = c->d_bits[nxt]; }   // (never with a kept graph: the plan)
     }
     if (p.local_book) {                                    // an ancestor's rows of the previous plane, inside its owner's slab
         b.tab_ptrs = c->d_tab_ptrs;
@@ -2711,11 +2754,16 @@ static int step_twist(phylo_ctx* c, const pk_rank_args& b) {
 static int step_book(phylo_ctx* c, const pk_rank_args& b) {
     const sweep_plan& p = c->run.plan;
     const int K = c->K, w = p.book_width;
-    const size_t lds = pk_book_lds_bytes(c->N);
+    const size_t lds = pk_book_lds_bytes(c->N) + (p.clade_pat ? pk_book_bits_lds_bytes(c->N) : 0);   // (per group; pk_book_carve_sub)
     if (p.book_mat && b.r > 0) {
         const int lp = w < 16 ? 16 : w, per = PK_COLS / lp;   // particles per workgroup; behind them, a workgroup per particle's node
         const int bb = cdiv(K, per);
         const dim3 grid(bb + K);
+        if (p.clade_pat) {                                 // (N <= 12: 16 lanes)
+            if (lp != 16) return fail(c, PHYLO_ESTATE, "step_book: clade patterns at %d lanes", lp);
+            hipLaunchKernelGGL(pk_rank_book_mat_clade<16>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb);
+            return launch_check(c, "pk_rank_book_mat");
+        }
         switch (lp) {
         case 16: hipLaunchKernelGGL(pk_rank_book_mat<16>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb); break;
         case 32: hipLaunchKernelGGL(pk_rank_book_mat<32>, grid, dim3(PK_COLS), lds * per, c->stream, b, bb); break;
@@ -2729,6 +2777,12 @@ static int step_book(phylo_ctx* c, const pk_rank_args& b) {
     if (ch.taken) {                                        // the ancestors from the scan; the item waves of the adopted nodes lead the grid
         const int items = b.r > 0 ? p.G * ch.item_waves : 0;
         const dim3 grid(items + cdiv(K, per));
+        if (p.clade_pat) {
+            if (w == 8) hipLaunchKernelGGL(pk_rank_book_chain_clade<8>, grid, dim3(64), lds * per, c->stream, b, items);
+            else if (w == 16) hipLaunchKernelGGL(pk_rank_book_chain_clade<16>, grid, dim3(64), lds * per, c->stream, b, items);
+            else return fail(c, PHYLO_ESTATE, "step_book: clade patterns at %d lanes", w);
+            return launch_check(c, "pk_rank_book_chain");
+        }
         switch (w) {
         case 8: hipLaunchKernelGGL(pk_rank_book_chain<8>, grid, dim3(64), lds * per, c->stream, b, items); break;
         case 16: hipLaunchKernelGGL(pk_rank_book_chain<16>, grid, dim3(64), lds * per, c->stream, b, items); break;
@@ -2739,6 +2793,12 @@ static int step_book(phylo_ctx* c, const pk_rank_args& b) {
         return launch_check(c, "pk_rank_book_chain");
     }
     const dim3 grid(cdiv(p.local_book ? c->Kloc : K, per));
+    if (p.clade_pat) {
+        if (w == 8) hipLaunchKernelGGL(pk_rank_book_packed_clade<8>, grid, dim3(64), lds * per, c->stream, b);
+        else if (w == 16) hipLaunchKernelGGL(pk_rank_book_packed_clade<16>, grid, dim3(64), lds * per, c->stream, b);
+        else return fail(c, PHYLO_ESTATE, "step_book: clade patterns at %d lanes", w);
+        return launch_check(c, "pk_rank_book_packed");
+    }
     switch (w) {
     case 8: hipLaunchKernelGGL(pk_rank_book_packed<8>, grid, dim3(64), lds * per, c->stream, b); break;
     case 16: hipLaunchKernelGGL(pk_rank_book_packed<16>, grid, dim3(64), lds * per, c->stream, b); break;
@@ -2768,9 +2828,16 @@ static int step_merge(phylo_ctx* c, const pk_rank_args& b) {
         pk_pi4 pi4;
         memcpy(pi4.v, c->h_model_p + 16, sizeof pi4.v);
         // the pattern form: the table's LDS and U go with the launch; U = 0 is today's form
-        pk_pat_args pat = {nullptr, nullptr, 0, 0};
+        pk_pat_args pat = {nullptr, nullptr, 0, 0, 0u, 0u, nullptr};
         size_t lds = 0;
-        if (pat_on(c)) {
+        if (p.clade_pat) {                                 // (implies pat_on: sweep_facts_of)
+            const pk_clade_layout& L = c->clade_layout;
+            pat.clade = (const char*)c->d_clade + L.codes_bytes;
+            pat.cstride = (unsigned int)L.stride; pat.crep = (unsigned int)L.rep_bytes;
+            pat.rep_delta = (long long)(c->d_clade - c->d_leaf_packed);
+            pat.U = c->pat_U;
+            lds = pk_pat_lds_bytes(c->pat_U);
+        } else if (pat_on(c)) {
             pat.pimg = (const char*)c->d_pat;
             pat.roff = (const char*)c->d_pat + pk_pat_image_bytes(S);
             pat.rep_delta = (long long)((c->d_pat + pk_pat_image_bytes(S) + pk_pat_rep_bytes()) - c->d_leaf_packed);
@@ -3959,7 +4026,7 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
     f.transport = transport != 0;
     sweep_facts_flags(f, flags);
     f.env_eager_nodes = switches & 1; f.env_rehearse_sharded = switches & 2; f.env_replicated_book = switches & 4;
-    f.jc = switches & 8; f.coded_leaves = switches & 16; f.device_exchange = switches & 32;
+    f.jc = switches & 8; f.coded_leaves = switches & 16; f.device_exchange = switches & 32; f.clade_tables = switches & 64;
     char why[160];
     if (sweep_refuses_batch(f, k_sweep_limits, why, sizeof why) || sweep_refuses_form(f, k_sweep_limits, why, sizeof why))
         return fail(nullptr, PHYLO_EINVAL, "%s", why);
@@ -4058,6 +4125,41 @@ int phylo_debug_site_patterns_of(phylo_ctx* c, int32_t* U, int32_t* taken) {
     if (!c->have_leaves) return fail(c, PHYLO_ESTATE, "phylo_debug_site_patterns_of needs leaves");
     *U = c->pat_U;
     *taken = pat_on(c) ? 1 : 0;
+    return PHYLO_OK;
+}
+
+int phylo_debug_clade_patterns_rule(int pat_taken, int N, int S, int U, int sw, int64_t* bytes) {
+    if (N < 1 || S < 1 || U < 0 || sw < PK_CLADE_OFF || sw > PK_CLADE_FORCE) {
+        (void)fail(nullptr, PHYLO_EINVAL, "phylo_debug_clade_patterns_rule: bad arguments");
+        return -1;
+    }
+    if (bytes) *bytes = (int64_t)pk_clade_layout_of(N, S, U).total;
+    return pk_clade_take(pat_taken != 0, N, S, U, sw) ? 1 : 0;
+}
+
+// The clade tables of byte codes [N][S] (N <= PK_CLADE_MAX_N) as phylo_set_leaves builds them: layout[5] = codes_bytes, rep_bytes,
+// image_bytes, stride, total; with `tables` (cap >= total bytes) the buffer, with `cls` ([2^N][U] uint16) every bitset's classes.
+int phylo_debug_clade_tables(const uint8_t* codes, int N, int S, int32_t* U, int64_t* layout, uint8_t* tables, int64_t cap, uint16_t* cls) {
+    if (N < 1 || N > PK_CLADE_MAX_N || S < 1 || !codes || !U || !layout) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_clade_tables: bad arguments");
+    std::vector<int32_t> pat((size_t)S), rp((size_t)S);
+    *U = pk_pat_columns(codes, N, S, pat.data(), rp.data());
+    const pk_clade_layout L = pk_clade_layout_of(N, S, *U);
+    layout[0] = (int64_t)L.codes_bytes; layout[1] = (int64_t)L.rep_bytes; layout[2] = (int64_t)L.image_bytes;
+    layout[3] = (int64_t)L.stride; layout[4] = (int64_t)L.total;
+    if (!tables) return PHYLO_OK;
+    if (*U > PK_PAT_MAX_U) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_clade_tables: U = %d exceeds %d", *U, PK_PAT_MAX_U);
+    if (cap < (int64_t)L.total) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_clade_tables: the tables take %lld bytes (got %lld)", (long long)L.total, (long long)cap);
+    pk_clade_build(codes, N, S, pat.data(), rp.data(), *U, tables, cls);
+    return PHYLO_OK;
+}
+
+// eligible: the tables of the current leaves are built and the pattern form is taken; taken: the last sweep begun took the form
+int phylo_debug_clade_patterns_of(phylo_ctx* c, int32_t* eligible, int32_t* taken, int64_t* bytes) {
+    if (!c || !eligible || !taken || !bytes) return fail(c, PHYLO_EINVAL, "phylo_debug_clade_patterns_of: NULL argument");
+    if (!c->have_leaves) return fail(c, PHYLO_ESTATE, "phylo_debug_clade_patterns_of needs leaves");
+    *eligible = (c->clade_ready && pat_on(c)) ? 1 : 0;
+    *taken = c->run.plan.clade_pat ? 1 : 0;
+    *bytes = c->clade_ready ? (int64_t)c->clade_layout.total : 0;
     return PHYLO_OK;
 }
 

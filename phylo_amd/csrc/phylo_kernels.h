@@ -21,7 +21,7 @@ enum { AUX_SUM_REM = 0, AUX_FPRIOR, AUX_LPRIOR, AUX_RPRIOR, AUX_LL_TILDE, AUX_PA
 // address of a child in a peer's pool or in the cache of remote nodes is not known to every particle when its bookkeeping
 // runs (another wave of the same launch may still be fetching it), so sharded sweeps keep the form that resolves ids.
 #define PK_REC 16            // 64-bit slots per record
-enum { REC_BASE_L = PK_AUX, REC_BASE_R, REC_NODELL, REC_ROOTLL, REC_LL, REC_LOGW, REC_FLAGS /* bit 0 / 1: left / right child is a coded leaf */ };
+enum { REC_BASE_L = PK_AUX, REC_BASE_R, REC_NODELL, REC_ROOTLL, REC_LL, REC_LOGW, REC_FLAGS /* bit 0 / 1: left / right child is a coded leaf; from bit 2: the new node's leaf bitset (clade patterns) */ };
 #define PK_REC_SLOTS (REC_FLAGS + 1)
 static_assert(PK_REC_SLOTS <= PK_REC && PK_REC_SLOTS <= 16, "one lane per slot: with 16 lanes or more per particle the bookkeeping writes the record in one trip (pk_book_tail)");
 
@@ -212,6 +212,7 @@ struct pk_prologue_args {
     double* rootll;
     const double* nodell;
     int K, N;
+    int32_t* bits;                      // [K][N] leaf bitset of every root, or NULL (clade patterns: phylo_site_patterns.h)
     unsigned int* mark;                 // NULL: no marks to clear
     unsigned int mark_words;            // multiple of 4
     int draw_blocks, init_blocks, mark_blocks;   // then the blocks that fill rdraw
@@ -314,6 +315,7 @@ __device__ __forceinline__ void pk_sweep_prologue_body(const pk_prologue_args& p
                 p.roots[i] = i % p.N;
                 p.cnt[i] = 1;
                 p.rootll[i] = p.nodell[i % p.N];
+                if (p.bits) p.bits[i] = 1 << (i % p.N);
             }
         }
     } else if (b < p.draw_blocks + p.init_blocks + p.mark_blocks) {
@@ -685,13 +687,17 @@ struct pk_rank_args {
     const int32_t* adopt_list;                            // [K] group g's adopted particles at [g Kg, g Kg + adopt_cnt[g]), ascending
     const int32_t* adopt_cnt;                             // [G]
     int item_waves, item_parts;                           // pk_mat_listed: waves per group, parts of a node's sites
+    // clade patterns (phylo_site_patterns.h; the plan's clade_pat): the leaf bitset of every root, adopted with the ancestor's row,
+    // OR-ed for the new node and handed to the merge in the record's flag word from bit 2 on.  NULL: not taken, nothing is touched.
+    const int32_t* bits_old; int32_t* bits_new;           // [K][N]
 };
 
 // LDS carve of the bookkeeping prologue (arrays of length N rounded up to a multiple of 4)
 struct pk_book_lds {
     double *ord_ll, *ord_ldf, *hbl, *hbr, *anc_ll, *ldf;   // ldf: N+1 entries (n4 + 4 reserved)
     uint32_t* key; int32_t *ro, *co, *ord_cnt;
-    double* aux; int32_t* misc;   // misc: [0] child l, [1] child r, [2] is_last, [3] ancestor
+    double* aux; int32_t* misc;   // misc: [0] child l, [1] child r, [2] the new node's leaf bitset (clade patterns), [3] ancestor
+    int32_t* bo;                  // the adopted roots' leaf bitsets (clade patterns: behind ALL groups' carves, pk_book_carve_sub)
 };
 __host__ __device__ inline size_t pk_book_lds_bytes(int N) {
     const size_t n4 = ((size_t)N + 3) & ~(size_t)3;
@@ -712,11 +718,21 @@ __device__ __forceinline__ pk_book_lds pk_book_carve(char* base, int N) {
     L.co = L.ro + n4;
     L.ord_cnt = L.co + n4;
     L.misc = L.ord_cnt + n4;
+    L.bo = nullptr;
+    return L;
+}
+// group `sub` of the `groups` of a workgroup: its carve, and its bitset row behind the last group's carve (the launch asks for
+// pk_book_bits_lds_bytes more per group where the plan takes clade patterns: the BITS kernels alone use it)
+__host__ __device__ inline size_t pk_book_bits_lds_bytes(int N) { return (((size_t)N + 3) & ~(size_t)3) * 4; }
+__device__ __forceinline__ pk_book_lds pk_book_carve_sub(char* smem, int sub, int groups, int N) {
+    pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(N), N);
+    L.bo = (int32_t*)(smem + (size_t)groups * pk_book_lds_bytes(N) + (size_t)sub * pk_book_bits_lds_bytes(N));
     return L;
 }
 
 // slot t < PK_REC_SLOTS of local particle k's merge record, from what the bookkeeping left in LDS (one lane per slot, the lanes
 // that write aux / child).  A child's address is pk_node_ptr's for one rank, or the leaf's packed codes where the merge reads codes.
+template <bool BITS = false>
 __device__ __forceinline__ void pk_rec_write(const pk_rank_args& a, int k, int kg, int t, const pk_book_lds& L) {
     const size_t node_sz = (size_t)a.S * 4;
     unsigned long long v;
@@ -737,6 +753,7 @@ __device__ __forceinline__ void pk_rec_write(const pk_rank_args& a, int k, int k
         v = (unsigned long long)(a.logw_r + kg);
     } else {
         v = a.leaf_codes ? (unsigned long long)((L.misc[0] < a.N ? 1 : 0) | (L.misc[1] < a.N ? 2 : 0)) : 0ull;
+        if constexpr (BITS) v |= (unsigned long long)(unsigned int)L.misc[2] << 2;
     }
     a.rec[(size_t)k * PK_REC + t] = v;
 }
@@ -795,7 +812,9 @@ __device__ __forceinline__ int pk_cdf_search_group(const uint64_t* cdf, int K, u
 // KEY_LOOP: the particle may have more pair-key blocks than its group has lanes to spare (see below).
 // ANC_IN (the chain form of a rank event): the ancestor is read from a.anc_in, which the previous rank event's scan wrote, in the
 // place of the resampling draw and the index search -- one round trip for the search's two to four, and no lane draws for it.
-template <int LP, bool KEY_LOOP, bool ANC_IN = false>
+// BITS (clade patterns, the plan's clade_pat; compiled for 8 and 16 lanes only -- the form needs N <= 12): the roots' leaf bitsets
+// travel with the tables.  Without it the code is what it was: an alignment outside the form pays nothing for it.
+template <int LP, bool KEY_LOOP, bool ANC_IN = false, bool BITS = false>
 __device__ __forceinline__ void pk_book_packed(const pk_rank_args& a, int kg, bool local, const pk_book_lds& L, int sl, int lane) {
     const int n = a.n, N = a.N, k = kg - a.k0;
     const int grp = a.group_seeds ? kg / a.Kg : 0;
@@ -849,6 +868,11 @@ __device__ __forceinline__ void pk_book_packed(const pk_rank_args& a, int kg, bo
         }
         #pragma unroll 1
         for (int i = sl; i < n; i += LP) { L.ro[i] = ro[i]; L.co[i] = co[i]; L.anc_ll[i] = rl[i]; }
+        if constexpr (BITS) {                          // (one rank: the ancestor's row is in this plane)
+            const int32_t* bo = a.bits_old + (size_t)anc * N;
+            #pragma unroll 1
+            for (int i = sl; i < n; i += LP) L.bo[i] = bo[i];
+        }
         if (sl == 0) {
             L.misc[3] = anc;
             if (local) L.aux[AUX_LL_TILDE] = (a.r > 0) ? a.ll_prev[anc] : a.ll_tilde0;
@@ -904,8 +928,14 @@ __device__ __forceinline__ void pk_book_packed(const pk_rank_args& a, int kg, bo
             L.ord_cnt[rank] = c;
             L.ord_ll[rank] = xll;
             L.ord_ldf[rank] = L.ldf[c < a.ldf_n ? c : a.ldf_n];
+            if constexpr (BITS) a.bits_new[(size_t)kg * N + rank] = L.bo[i];
         }
         if (sl == 0) {
+            if constexpr (BITS) {
+                const int bnew = L.bo[il] | L.bo[ir];
+                a.bits_new[(size_t)kg * N + (n - 2)] = bnew;
+                L.misc[2] = bnew;
+            }
             const int cnew = L.co[il] + L.co[ir];
             rn[n - 2] = N + a.r * a.K + kg;           // id of the node this particle creates now
             cn[n - 2] = cnew;
@@ -1016,7 +1046,7 @@ __device__ __forceinline__ void pk_cache_fill(const pk_rank_args& a, int id, int
 // What a bookkeeping kernel writes for the particle of each group once pk_book_packed has returned: aux and child for the merge,
 // the merge record, the mark of the adopted ancestor's node (a plain store: every adopter writes the same value; the node's OWNER
 // writes it) and, sharded (`cache`, wave-uniform), its new remote children into the local cache, each copied by the whole wave.
-template <int LP>
+template <int LP, bool BITS = false>
 __device__ __forceinline__ void pk_book_tail(const pk_rank_args& a, int kg, bool local, bool mark, bool cache, const pk_book_lds& L,
                                              int sl, int lane) {
     if (local) {
@@ -1028,7 +1058,7 @@ __device__ __forceinline__ void pk_book_tail(const pk_rank_args& a, int kg, bool
         }
         if (a.rec) {
 #pragma unroll
-            for (int t = sl; t < PK_REC_SLOTS; t += LP) pk_rec_write(a, k, kg, t, L);
+            for (int t = sl; t < PK_REC_SLOTS; t += LP) pk_rec_write<BITS>(a, k, kg, t, L);
         }
     }
     if (mark && sl == 0) a.mark[(size_t)(a.r - 1) * a.K + L.misc[3]] = 1u;
@@ -1049,18 +1079,28 @@ __device__ __forceinline__ void pk_book_tail(const pk_rank_args& a, int kg, bool
 // weight terms written for the merge kernel; for the others only the replicated integer state (root tables) is advanced.
 // A wave per particle is asked to leave room for five waves per SIMD: left alone it takes 97 registers, four waves, and a batch of
 // 40 960 particles of 50 taxa (waves in several rounds) then takes 106.7 us against 93.2 (12 bytes of scratch per lane pay for it).
-template <int LP>
-__global__ __launch_bounds__(64, LP == 64 ? 5 : 1) void pk_rank_book_packed(const pk_rank_args a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <int LP, bool BITS>
+__device__ __forceinline__ void pk_rank_book_packed_body(const pk_rank_args& a, char* smem) {
     const int lane = threadIdx.x, sub = lane / LP, sl = lane & (LP - 1);
     const int count = a.tab_ptrs ? a.Kloc : a.K;                      // local bookkeeping: this rank's particles only
     int idx = blockIdx.x * (64 / LP) + sub;
     if (idx >= count) idx = count - 1;          // a spare group repeats the last particle: identical values, identical writes
     const int kg = a.tab_ptrs ? a.k0 + idx : idx;
-    const pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
+    const pk_book_lds L = BITS ? pk_book_carve_sub(smem, sub, 64 / LP, a.N) : pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
     const bool local = kg >= a.k0 && kg < a.k0 + a.Kloc;
-    pk_book_packed<LP, LP == 64>(a, kg, local, L, sl, lane);
-    pk_book_tail<LP>(a, kg, local, a.lazy && a.r > 0, a.mirror && a.r > 0, L, sl, lane);
+    pk_book_packed<LP, LP == 64, false, BITS>(a, kg, local, L, sl, lane);
+    pk_book_tail<LP, BITS>(a, kg, local, a.lazy && a.r > 0, a.mirror && a.r > 0, L, sl, lane);
+}
+template <int LP>
+__global__ __launch_bounds__(64, LP == 64 ? 5 : 1) void pk_rank_book_packed(const pk_rank_args a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    pk_rank_book_packed_body<LP, false>(a, smem);
+}
+// ... with the roots' leaf bitsets (clade patterns)
+template <int LP>
+__global__ __launch_bounds__(64, 1) void pk_rank_book_packed_clade(const pk_rank_args a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    pk_rank_book_packed_body<LP, true>(a, smem);
 }
 
 // Sharded lazy nodes: every rank derives the resampling outcome of ALL K particles (index search only, no tables)
@@ -1235,9 +1275,8 @@ __global__ __launch_bounds__(PK_COLS) void pk_materialize_by_draws(const pk_rank
     else pk_mat_by_thresholds(a, a.k0 + (int)blockIdx.x);
 }
 
-template <int LP>
-__global__ __launch_bounds__(PK_COLS, 5) void pk_rank_book_mat(const pk_rank_args a, int book_blocks) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <int LP, bool BITS>
+__device__ __forceinline__ void pk_rank_book_mat_body(const pk_rank_args& a, int book_blocks, char* smem) {
     if ((int)blockIdx.x >= book_blocks) {                 // (one workgroup per particle: the launch is a single sweep's)
         pk_mat_by_thresholds(a, (int)blockIdx.x - book_blocks);
         return;
@@ -1246,9 +1285,19 @@ __global__ __launch_bounds__(PK_COLS, 5) void pk_rank_book_mat(const pk_rank_arg
     int idx = blockIdx.x * (PK_COLS / LP) + sub;
     if (idx >= a.K) idx = a.K - 1;              // a spare group repeats the last particle: identical values, identical writes
     const int kg = idx;                         // one GPU: every particle is local
-    const pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
-    pk_book_packed<LP, false>(a, kg, true, L, sl, lane);               // (N <= 64: the key blocks fit one evaluation)
-    pk_book_tail<LP>(a, kg, true, a.r > 0, false, L, sl, lane);        // the marks stay (phylo_sweep_node reads them)
+    const pk_book_lds L = BITS ? pk_book_carve_sub(smem, sub, PK_COLS / LP, a.N) : pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
+    pk_book_packed<LP, false, false, BITS>(a, kg, true, L, sl, lane);  // (N <= 64: the key blocks fit one evaluation)
+    pk_book_tail<LP, BITS>(a, kg, true, a.r > 0, false, L, sl, lane);        // the marks stay (phylo_sweep_node reads them)
+}
+template <int LP>
+__global__ __launch_bounds__(PK_COLS, 5) void pk_rank_book_mat(const pk_rank_args a, int book_blocks) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    pk_rank_book_mat_body<LP, false>(a, book_blocks, smem);
+}
+template <int LP>
+__global__ __launch_bounds__(PK_COLS, 5) void pk_rank_book_mat_clade(const pk_rank_args a, int book_blocks) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    pk_rank_book_mat_body<LP, true>(a, book_blocks, smem);
 }
 
 __device__ __forceinline__ const double* pk_node_ptr(const pk_rank_args& a, int id) {
@@ -1327,9 +1376,8 @@ __device__ __forceinline__ void pk_mat_listed(const pk_rank_args& a, int wg, int
 // The two parts touch no common address: the items read rows r - 1 of child_all / Pmat_all and write pool rows and marks of rank
 // event r - 1, the bookkeeping writes row r and reads neither pool nor marks.
 // Rank event 0 has no item waves (item_wgs = 0).
-template <int LP>
-__global__ __launch_bounds__(64, LP == 64 ? 5 : 1) void pk_rank_book_chain(const pk_rank_args a, int item_wgs) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <int LP, bool BITS>
+__device__ __forceinline__ void pk_rank_book_chain_body(const pk_rank_args& a, int item_wgs, char* smem) {
     if ((int)blockIdx.x < item_wgs) {
         pk_mat_listed(a, (int)blockIdx.x, (int)threadIdx.x);
         return;
@@ -1339,10 +1387,20 @@ __global__ __launch_bounds__(64, LP == 64 ? 5 : 1) void pk_rank_book_chain(const
     int idx = ((int)blockIdx.x - item_wgs) * (64 / LP) + sub;
     if (idx >= count) idx = count - 1;          // a spare group repeats the last particle: identical values, identical writes
     const int kg = a.tab_ptrs ? a.k0 + idx : idx;
-    const pk_book_lds L = pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
+    const pk_book_lds L = BITS ? pk_book_carve_sub(smem, sub, 64 / LP, a.N) : pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
     const bool local = kg >= a.k0 && kg < a.k0 + a.Kloc;
-    pk_book_packed<LP, LP == 64, true>(a, kg, local, L, sl, lane);
-    pk_book_tail<LP>(a, kg, local, false, a.mirror && a.r > 0, L, sl, lane);
+    pk_book_packed<LP, LP == 64, true, BITS>(a, kg, local, L, sl, lane);
+    pk_book_tail<LP, BITS>(a, kg, local, false, a.mirror && a.r > 0, L, sl, lane);
+}
+template <int LP>
+__global__ __launch_bounds__(64, LP == 64 ? 5 : 1) void pk_rank_book_chain(const pk_rank_args a, int item_wgs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    pk_rank_book_chain_body<LP, false>(a, item_wgs, smem);
+}
+template <int LP>
+__global__ __launch_bounds__(64, 1) void pk_rank_book_chain_clade(const pk_rank_args a, int item_wgs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    pk_rank_book_chain_body<LP, true>(a, item_wgs, smem);
 }
 
 // Leaf children whose rows are one-hot / all-ones (the reference's encoding, runner.py:83-96) are read as a
@@ -2073,18 +2131,79 @@ __device__ __forceinline__ void pk_pat_walk(int s1, const char* pimg, pk_u4 n0, 
     }
 }
 // the kernel's arguments behind pi (pk_merge_kernarg): read from the argument segment where they are used
-struct pk_pat_args { const char* pimg; const char* roff; long long rep_delta /* representative leaf image - packed image */; int U; };
+// (clade: the blocks of the clade tables, NULL = the form above over the whole alignment's columns; rep_delta is then the distance
+// from a leaf's packed image to its strided byte codes)
+struct pk_pat_args {
+    const char* pimg; const char* roff; long long rep_delta /* representative leaf image - packed image */; int U;
+    unsigned int cstride, crep;          // clade patterns: a block's stride, the bytes of its representatives
+    const char* clade;
+};
 typedef __attribute__((address_space(4))) const pk_pat_args pk_pat_kargs;
+// ---- Clade patterns (phylo_site_patterns.h): phase 1 over the distinct columns of the MERGED CLADE.  The block of the clade's leaf
+//      bitset Z (the record's flag word from bit 2 on) holds U_Z, the representatives' row offsets and a site image in the global
+//      image's layout; U_Z is requested beside the first offsets (a scalar load: nothing waits for it before the first rows are
+//      under way).  A coded side's code is gathered from the leaf's byte codes at the representative site, offset >> 5, with the
+//      rows.  Same pk_rows_lik, same select behind U_Z, same key / minimum, same pad entry; phase 2 is pk_pat_walk over the block's
+//      image.  The factor of a site is that of a site with the same column on Z's leaves: the same bits.
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_clade_rows(pk_rowregs& x, const char* bl, const char* br, const char* cb, unsigned int off) {
+    pk_pat_rows<CL, CR>(x, bl, br, off);
+    if constexpr (CL) x.cl = *(pk_gu8c*)(cb + (off >> 5));
+    if constexpr (CR) x.cr = *(pk_gu8c*)(cb + (off >> 5));
+}
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_clade_entry(const pk_rowregs& X, unsigned int u, unsigned int U, const double (&Pl)[16],
+                                               const double (&Pr)[16], const double (*tabL)[4], const double (*tabR)[4],
+                                               const double (&pi)[4], double* ulik, pm_lp_flag& flag) {
+    double x = pk_rows_lik<CL, CR>(X, Pl, Pr, tabL, tabR, nullptr, pi);
+    x = u < U ? x : 1.0;
+    flag.f = pm_min_u32(flag.f, pm_lp_key(x));
+    ulik[u] = x;
+}
+template <bool CL, bool CR>
+__device__ __forceinline__ void pk_clade_phase1(const char* blk, const char* bl, const char* br, const char* cb, const double (&Pl)[16],
+                                                const double (&Pr)[16], const double (*tabL)[4], const double (*tabR)[4],
+                                                const double (&pi)[4], double* ulik, pm_lp_flag& flag) {
+    static_assert(!(CL && CR), "an uncoded side");
+    const char* roff = blk + PK_CLADE_HDR_BYTES;
+    unsigned int u = threadIdx.x & 63u;
+    pk_rowregs A, B;
+    unsigned int ro = *(pk_gu32c*)(roff + u * 4u);
+    const int U = *(__attribute__((address_space(4))) const int*)blk;
+    pk_clade_rows<CL, CR>(A, bl, br, cb, ro);
+    ro = *(pk_gu32c*)(roff + (u + 64u) * 4u);
+    const int nU = (U + 63) >> 6;
+    #pragma unroll 1
+    for (int t = 0; t < (nU >> 1); ++t, u += 128u) {
+        pk_clade_rows<CL, CR>(B, bl, br, cb, ro);
+        ro = *(pk_gu32c*)(roff + (u + 128u) * 4u);
+        pk_clade_entry<CL, CR>(A, u, (unsigned int)U, Pl, Pr, tabL, tabR, pi, ulik, flag);
+        pk_clade_rows<CL, CR>(A, bl, br, cb, ro);
+        ro = *(pk_gu32c*)(roff + (u + 192u) * 4u);
+        pk_clade_entry<CL, CR>(B, u + 64u, (unsigned int)U, Pl, Pr, tabL, tabR, pi, ulik, flag);
+    }
+    if (nU & 1) pk_clade_entry<CL, CR>(A, u, (unsigned int)U, Pl, Pr, tabL, tabR, pi, ulik, flag);
+    if (threadIdx.x == 0) ulik[U] = 1.0;                   // the pad entry
+}
 template <bool CL, bool CR>
 __device__ __forceinline__ bool pk_rows_pat(int s1, const char* bl, const char* br, const char* rl, pk_pat_kargs* pa, const double (&Pl)[16],
                                             const double (&Pr)[16], const double (*tabL)[4], const double (*tabR)[4],
-                                            const double (&pi)[4], double* ulik, pm_lp& col) {
+                                            const double (&pi)[4], double* ulik, pm_lp& col, unsigned int Z) {
     pm_lp_flag flag = pm_lp_flag_init();
-    const char* pimg = pa->pimg;
+    const char* pimg;
     pk_u4 n0, n1;
-    if constexpr (CL || CR) pk_pat_request(n0, n1, pimg, 0);   // (two internal children: behind phase 1, whose rows fill the registers)
-    pk_pat_phase1<CL, CR>(pa->U, bl, br, rl, pa->roff, Pl, Pr, tabL, tabR, pi, ulik, flag);
-    if constexpr (!(CL || CR)) pk_pat_request(n0, n1, pimg, 0);
+    if (pa->clade != nullptr) {                            // (wave-uniform: a kernel argument)
+        const char* blk = pa->clade + (size_t)(Z * pa->cstride);
+        pimg = blk + PK_CLADE_HDR_BYTES + pa->crep;
+        if constexpr (CL || CR) pk_pat_request(n0, n1, pimg, 0);
+        pk_clade_phase1<CL, CR>(blk, bl, br, rl, Pl, Pr, tabL, tabR, pi, ulik, flag);
+        if constexpr (!(CL || CR)) pk_pat_request(n0, n1, pimg, 0);
+    } else {
+        pimg = pa->pimg;
+        if constexpr (CL || CR) pk_pat_request(n0, n1, pimg, 0);   // (two internal children: behind phase 1, whose rows fill the registers)
+        pk_pat_phase1<CL, CR>(pa->U, bl, br, rl, pa->roff, Pl, Pr, tabL, tabR, pi, ulik, flag);
+        if constexpr (!(CL || CR)) pk_pat_request(n0, n1, pimg, 0);
+    }
     pk_wave_lds_fence();
     pk_pat_walk(s1, pimg, n0, n1, ulik, col, flag);
     return pm_lp_flag_set(flag);
@@ -2141,7 +2260,7 @@ __device__ __forceinline__ pm_lp pk_rows_general(unsigned int fl, int s0, int s1
 template <bool CL, bool CR>
 __device__ __forceinline__ bool pk_rows_loop_pat(int s1, const char* bl, const char* br, const double* Pu, const pk_cdbl* Pc,
                                                  double (*tabL)[4], double (*tabR)[4], const pk_cdbl* pik, pm_lp& col, pk_pat_kargs* pa,
-                                                 double* ulik) {
+                                                 double* ulik, unsigned int Z) {
     static_assert(!(CL && CR), "an uncoded side");
     const double pi[4] = {pik[0], pik[1], pik[2], pik[3]};
     double Pl[16], Pr[16];
@@ -2159,7 +2278,7 @@ __device__ __forceinline__ bool pk_rows_loop_pat(int s1, const char* bl, const c
         else pk_build_leaf_table(Pu + 16, tabR, (int)(threadIdx.x & 63));
         pk_wave_lds_fence();
     }
-    return __any(pk_rows_pat<CL, CR>(s1, bl, br, rl, pa, Pl, Pr, tabL, tabR, pi, ulik, col));
+    return __any(pk_rows_pat<CL, CR>(s1, bl, br, rl, pa, Pl, Pr, tabL, tabR, pi, ulik, col, Z));
 }
 // pi (from the kernel-argument segment) and the matrices of the uncoded sides are requested HERE, inside the variant: uniform
 // addresses in the constant address space, nothing stored yet -- scalar loads.  Loaded above the variants they are one value each
@@ -2168,11 +2287,11 @@ __device__ __forceinline__ bool pk_rows_loop_pat(int s1, const char* bl, const c
 template <bool CL, bool CR>
 __device__ __forceinline__ bool pk_rows_loop_rec(int s0, int s1, const char* bl, const char* br, const double* Pu, const pk_cdbl* Pc,
                                                  double (*tabL)[4], double (*tabR)[4], double* lik25, const pk_cdbl* pik, pm_lp& col,
-                                                 pk_pat_kargs* pa, double* ulik) {
+                                                 pk_pat_kargs* pa, double* ulik, unsigned int Z) {
     // the pattern form (wave-uniform: a kernel argument; the host sets U only where the row is one tile, so s0 == 0)
     // (a flagged wave of two internal children: pk_rows_general's variant without a coded side)
     if constexpr (!(CL && CR)) {
-        if (pa->U != 0) return pk_rows_loop_pat<CL, CR>(s1, bl, br, Pu, Pc, tabL, tabR, pik, col, pa, ulik);
+        if (pa->U != 0) return pk_rows_loop_pat<CL, CR>(s1, bl, br, Pu, Pc, tabL, tabR, pik, col, pa, ulik, Z);
     }
     const int lane = threadIdx.x & 63;
     const double pi[4] = {pik[0], pik[1], pik[2], pik[3]};
@@ -2252,7 +2371,7 @@ void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const dou
     const char* bl = pk_uniform_ptr((const void*)rc[REC_BASE_L]);
     const char* br = pk_uniform_ptr((const void*)rc[REC_BASE_R]);
     PK_TOUCH4_END(fl);                                     // (before the first use of the flags, on every path)
-    static_assert(offsetof(pk_merge_kernarg, pi4) == 40 && offsetof(pk_merge_kernarg, pat) == 72 && sizeof(pk_merge_kernarg) == 104,
+    static_assert(offsetof(pk_merge_kernarg, pi4) == 40 && offsetof(pk_merge_kernarg, pat) == 72 && sizeof(pk_merge_kernarg) == 120,
                   "the kernel's argument segment");
     pk_pat_kargs* pa = (pk_pat_kargs*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() +
                                        offsetof(pk_merge_kernarg, pat));
@@ -2261,11 +2380,11 @@ void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const dou
     pm_lp col = pm_lp_init();
     bool redo;
     if (fl & 1u) {
-        if (fl & 2u) redo = pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
-        else redo = pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
+        if (fl & 2u) redo = pk_rows_loop_rec<true, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik, fl >> 2);
+        else redo = pk_rows_loop_rec<true, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik, fl >> 2);
     } else {
-        if (fl & 2u) redo = pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
-        else redo = pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik);
+        if (fl & 2u) redo = pk_rows_loop_rec<false, true>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik, fl >> 2);
+        else redo = pk_rows_loop_rec<false, false>(s0, s1, bl, br, Pu, Pc, tabL, tabR, lik25, pi, col, pa, pk_ulik, fl >> 2);
     }
     if (redo) col = pk_rows_general(fl, s0, s1, bl, br, Pu, (const double*)pi, tabL, tabR, lik25);
     const double tot = pk_wave_tree_sum(pm_lp_finish(col));

@@ -110,8 +110,9 @@ static inline void pk_pat_rep_leaf_image(const uint8_t* codes, int N, int S, con
 }
 // Everything at once, as phylo_set_leaves calls it: `tables` is the image buffer from pk_pat_offset(N, S) on.  Returns U; the tables
 // are written only when U <= PK_PAT_MAX_U (no launch reads them otherwise).
-static inline int pk_pat_build(const uint8_t* codes, int N, int S, uint8_t* tables) {
-    std::vector<int32_t> pat((size_t)S), rep((size_t)S);
+// (pat, rep: the columns as pk_pat_columns leaves them, for what is built from them next)
+static inline int pk_pat_build(const uint8_t* codes, int N, int S, uint8_t* tables, std::vector<int32_t>& pat, std::vector<int32_t>& rep) {
+    pat.resize((size_t)S); rep.resize((size_t)S);
     const int U = pk_pat_columns(codes, N, S, pat.data(), rep.data());
     if (U <= PK_PAT_MAX_U) {
         pk_pat_pack_image(pat.data(), S, U, (uint16_t*)tables);
@@ -119,6 +120,10 @@ static inline int pk_pat_build(const uint8_t* codes, int N, int S, uint8_t* tabl
         pk_pat_rep_leaf_image(codes, N, S, rep.data(), U, tables + pk_pat_image_bytes(S) + pk_pat_rep_bytes(), pk_packed_leaf_bytes(S));
     }
     return U;
+}
+static inline int pk_pat_build(const uint8_t* codes, int N, int S, uint8_t* tables) {
+    std::vector<int32_t> pat, rep;
+    return pk_pat_build(codes, N, S, tables, pat, rep);
 }
 
 // ---- The rule: does pk_rank_merge_nostore take the pattern form for these leaves?
@@ -155,4 +160,110 @@ static inline bool pk_pat_take(int S, int U, bool coded, int ntiles, int sw) {
     if (sw == PK_PAT_FORCE) return true;
     const long nS = (S + 63) / 64, nU = (U + 63) / 64;
     return 10 * (nU * PK_PAT_C_PHASE1 + nS * PK_PAT_C_WALK + PK_PAT_C_FIXED) <= 8 * nS * PK_PAT_C_STEP;
+}
+
+// ---- Clade patterns: one site likelihood per distinct column of the MERGED CLADE.
+// The factor of a merge at a site depends only on the column restricted to the leaves below the new node: the induction above holds
+// clade by clade (two sites whose columns agree on the leaves of Z = L u R carry bit-identical rows in L and in R).  Most merges
+// build small clades, whose restricted columns are few, so phase 1 of the pattern form runs ceil(U_Z / 64) steps and not
+// ceil(U / 64).  What a wave needs is one BLOCK per clade, found from the clade's leaf bitset alone (the bookkeeping hands the
+// bitset to the merge in the high bits of the record's flag word): blocks are indexed directly by the bitset, all 2^N of them at one
+// stride -- no directory, no dependent load in the wave's start-up.  The buffer (pk_clade_layout):
+//
+//   byte codes          [N][pk_packed_leaf_bytes(S)]: the one-byte codes again, leaf by leaf at the stride of the packed image, so a
+//                       coded child's codes lie a fixed distance from its packed image (which the record holds) and a lane gathers
+//                       the code of its representative site at (row offset >> 5).  Bytes past S are 0 and never read.
+//   block Z             for every bitset Z < 2^N with at least three leaves (the others are never merged into by an uncoded child):
+//       header          256 bytes, word 0 = U_Z, the distinct columns of the alignment restricted to Z's leaves
+//       representatives off[c] = 32 * (first site of class c), c < U_Z, 0 behind them: 64 (ceil(U / 64) + 2) words (phase 1 reads
+//                       one and two steps ahead).  Classes are numbered by first occurrence, so the representatives ascend.
+//       site image      pk_pat_pack_image's layout exactly, 8 * class of every site, pad entry 8 U_Z.
+//
+// Built incrementally: the classes of Z are the classes of Z minus its highest leaf, refined by that leaf's code -- over the U
+// global patterns, not the S sites (global patterns are numbered by first occurrence, so first occurrence among patterns IS first
+// occurrence among sites).
+#define PK_CLADE_MAX_N 12                // 2^N blocks, and the bitset's 12 bits in the flag word
+#define PK_CLADE_MAX_BYTES ((size_t)32 << 20)   // the buffer's cap; primate.p (12 x 898, U = 413): 18 886 656 bytes
+#define PK_CLADE_HDR_BYTES 256
+#define PK_CLADE_DEFAULT 1               // PHYLO_CLADE_PATTERNS unset: the form is taken where it is eligible
+
+enum { PK_CLADE_OFF = 0, PK_CLADE_AUTO = 1, PK_CLADE_FORCE = 2 };   // PHYLO_CLADE_PATTERNS = 0, unset, force
+
+struct pk_clade_layout { size_t codes_bytes, rep_bytes, image_bytes, stride, total; };
+static inline pk_clade_layout pk_clade_layout_of(int N, int S, int U) {
+    pk_clade_layout L;
+    L.codes_bytes = pk_packed_bytes(N, S);
+    L.rep_bytes = (size_t)((U + 63) / 64 + 2) * 256;
+    L.image_bytes = pk_pat_image_bytes(S);
+    L.stride = PK_CLADE_HDR_BYTES + L.rep_bytes + L.image_bytes;
+    L.total = L.codes_bytes + (N <= 30 ? ((size_t)1 << N) : ((size_t)1 << 30)) * L.stride;
+    return L;
+}
+// The rule: the pattern form is taken (pk_pat_take), at least three and at most PK_CLADE_MAX_N taxa, the buffer within its cap.
+static inline bool pk_clade_take(bool pat_taken, int N, int S, int U, int sw) {
+    if (sw == PK_CLADE_OFF || (sw == PK_CLADE_AUTO && !PK_CLADE_DEFAULT)) return false;
+    if (!pat_taken || N < 3 || N > PK_CLADE_MAX_N) return false;
+    return pk_clade_layout_of(N, S, U).total <= PK_CLADE_MAX_BYTES;
+}
+// The buffer (pk_clade_layout_of(N, S, U).total bytes) of byte codes [N][S] with their global patterns pat[S], rep[U] (pk_pat_columns).
+// Blocks of fewer than three leaves are not written.  cls_out, if given: [2^N][U], the class of every global pattern in every
+// bitset (bitset 0: one class).
+static inline void pk_clade_build(const uint8_t* codes, int N, int S, const int32_t* pat, const int32_t* rep, int U, uint8_t* out,
+                                  uint16_t* cls_out) {
+    const pk_clade_layout L = pk_clade_layout_of(N, S, U);
+    const size_t leaf_bytes = pk_packed_leaf_bytes(S);
+    memset(out, 0, L.codes_bytes);
+    for (int leaf = 0; leaf < N; ++leaf) memcpy(out + (size_t)leaf * leaf_bytes, codes + (size_t)leaf * S, (size_t)S);
+    std::vector<uint8_t> cu((size_t)N * U);                // the representatives' codes
+    for (int leaf = 0; leaf < N; ++leaf)
+        for (int u = 0; u < U; ++u) cu[(size_t)leaf * U + u] = codes[(size_t)leaf * S + rep[u]];
+    // the global pattern of every entry of a site image, U for the pad
+    const size_t nimg = L.image_bytes / 2;
+    std::vector<uint16_t> pidx(nimg, (uint16_t)U);
+    std::vector<uint16_t> off8((size_t)U + 1);             // 8 * class of every global pattern in the current bitset, then the pad
+    for (int s = 0; s < S; ++s) {
+        const int q = s / 64, c = s % 64;
+        pidx[((size_t)(q / PK_CHUNK_STEPS) * 2 + (q % PK_CHUNK_STEPS) / 8) * (PK_PAT_HALF_BYTES / 2) + (size_t)c * 8 + q % 8] = (uint16_t)pat[s];
+    }
+    const size_t nZ = (size_t)1 << N;
+    std::vector<uint16_t> cls_own;
+    uint16_t* cls = cls_out;
+    if (!cls) { cls_own.resize(nZ * U); cls = cls_own.data(); }
+    for (int u = 0; u < U; ++u) cls[u] = 0;
+    std::vector<int32_t> stamp((size_t)U * 6, 0);          // the bitset that last saw (class of Z minus its highest leaf, code)
+    std::vector<uint16_t> id((size_t)U * 6);
+    std::vector<uint32_t> first((size_t)U + 1);            // the representatives' row offsets of the current bitset
+    const size_t rep_words = L.rep_bytes / 4;
+    for (size_t Z = 1; Z < nZ; ++Z) {
+        int h = 0, leaves = 0;
+        for (int b = 0; b < N; ++b)
+            if (Z >> b & 1) { h = b; ++leaves; }
+        const uint16_t* cp = cls + (Z ^ ((size_t)1 << h)) * U;
+        uint16_t* cz = cls + Z * U;
+        const uint8_t* ch = cu.data() + (size_t)h * U;
+        // (no branch on "a new class": it is unpredictable and would cost more than everything else here -- the class number and
+        // the representative are written every time and kept only where the count moves on)
+        int n = 0;
+        for (int u = 0; u < U; ++u) {
+            const size_t key = (size_t)cp[u] * 6 + ch[u];
+            const unsigned int fresh = stamp[key] != (int32_t)Z, keep = fresh - 1u;   // (keep: all ones where the class is known)
+            stamp[key] = (int32_t)Z;
+            const uint16_t k = (uint16_t)(((unsigned int)n & ~keep) | (id[key] & keep));
+            id[key] = k;
+            first[n] = 32u * (uint32_t)rep[u];
+            n += fresh;
+            cz[u] = k;
+        }
+        if (leaves < 3) continue;
+        uint8_t* blk = out + L.codes_bytes + Z * L.stride;
+        uint32_t* ro = (uint32_t*)(blk + PK_CLADE_HDR_BYTES);
+        memcpy(ro, first.data(), (size_t)n * 4);
+        for (size_t w = (size_t)n; w < rep_words; ++w) ro[w] = 0u;
+        memset(blk, 0, PK_CLADE_HDR_BYTES);
+        *(uint32_t*)blk = (uint32_t)n;
+        uint16_t* img = (uint16_t*)(blk + PK_CLADE_HDR_BYTES + L.rep_bytes);
+        for (int u = 0; u < U; ++u) off8[u] = (uint16_t)(8 * cz[u]);
+        off8[U] = (uint16_t)(8 * n);
+        for (size_t i = 0; i < nimg; ++i) img[i] = off8[pidx[i]];
+    }
 }

@@ -37,6 +37,9 @@ struct sweep_facts {
     bool twisting, keep_graph, eager_nodes, time_kernels;
     // the environment switches the launch path reads
     bool env_eager_nodes, env_rehearse_sharded, env_replicated_book;
+    // the clade tables of the current leaves are built and the merge's pattern form is taken (phylo_site_patterns.h: pk_clade_take,
+    // pk_pat_take -- the rule and PHYLO_CLADE_PATTERNS were applied when the leaves were set)
+    bool clade_tables;
 };
 
 struct sweep_plan {
@@ -69,6 +72,8 @@ struct sweep_plan {
     bool final_missing;                // ... and nothing else wrote it: phylo_sweep_node has to
     bool last_graph_eager;             // a kept graph whose reverse pass can write the marks itself (rev_marks)
     int gather_launches;               // kernels of graph_gather behind the last rank event (sharded kept graph)
+    bool clade_pat;                    // clade patterns: the root tables carry leaf bitsets, the record's flag word the new clade's,
+                                       // and the merge's phase 1 runs over the clade's block
 };
 
 // PHYLO_EAGER_NODES, as a flag or from the environment: every node is stored by its merge (also read by persist_plan)
@@ -178,6 +183,9 @@ inline sweep_plan sweep_plan_form(const sweep_facts& f, const sweep_limits& L) {
     p.last_graph_eager = p.graph && !p.lazy && !p.twist && one_tile && f.world == 1 && Kl == K && N > L.kept_bits_taxa;
     // pack, unpack (+ the two barrier kernels of the device-side exchange)
     p.gather_launches = (p.graph && f.world > 1) ? (f.device_exchange ? 4 : 2) : 0;
+    // clade patterns: the record-form merge of one site tile, root tables in the two planes (a kept graph writes history planes,
+    // which carry no bitsets).  Sharded, twisted and eager sweeps write no record.
+    p.clade_pat = f.clade_tables && p.use_rec && !p.graph && f.ntiles == 1;
     return p;
 }
 
@@ -321,7 +329,7 @@ inline uint32_t sweep_plan_mask(const sweep_plan& p) {
     const bool b[] = {p.twist, p.graph, p.timek, p.lazy, p.shard_form, p.replicated_book, p.local_book, p.book_mat, p.mat_by_draws,
                       p.want_rdraw, p.use_rec, p.sorted_prologue, p.mat_grouped, p.mat_draws_grouped, p.step_a_work, p.mat_after_book,
                       p.mat_barrier, p.fix_rootll, p.fold_logz, p.no_store_last, p.final_missing, p.last_graph_eager,
-                      p.one_tile, p.twist_ll, p.twist_tables, p.tile_epilogue, p.lse_stride != 0};
+                      p.one_tile, p.twist_ll, p.twist_tables, p.tile_epilogue, p.lse_stride != 0, p.clade_pat};
     static_assert(sizeof b / sizeof b[0] <= 28, "bits 28..31 hold book_width / 8");
     uint32_t m = (uint32_t)(p.book_width / 8) << 28;
     for (size_t i = 0; i < sizeof b / sizeof b[0]; ++i) m |= b[i] ? 1u << i : 0u;
