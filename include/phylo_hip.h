@@ -443,6 +443,19 @@ int phylo_debug_sweep_plan(int N, int K, int K_local, int S, int G, int M, int w
 int phylo_debug_sweep_chain(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
                             int multi_min, int scan_ancestors, int32_t* out);
 int phylo_debug_sweep_chain_of(phylo_ctx* ctx, int32_t* taken);
+/* Test hooks of how the record-form merge and the chain bookkeeping are launched (phylo_launch_map.h; the plan's launch_xcd and
+ * book_xcd; DESIGN.md sections 6b and 8).  Neither changes a bit of a result.
+ * phylo_debug_launch_map, no GPU needed: for a launch of n items at W (1, 2 or 4) waves per workgroup, with or without the XCD
+ * remap, *grid = the workgroups and, if items is not NULL (cap >= grid W entries), items[b W + w] = the item that wave w of
+ * workgroup b takes; an entry >= n is a wave without work.
+ * phylo_debug_sweep_launch, no GPU needed: the arguments of phylo_debug_sweep_plan, then PHYLO_LAUNCH_XCD as a context reads it
+ * (0 = unset, -1 = off, 1 = on, 2 = the merge alone, 3 = the bookkeeping alone).  out[2]: launch_xcd, book_xcd.
+ * phylo_debug_sweep_launch_of: the same two of the context's last sweep.
+ * tests/test_launch_map_cpu.py checks the map. */
+int phylo_debug_launch_map(int n, int W, int xcd, int32_t* grid, int32_t* items, int64_t cap);
+int phylo_debug_sweep_launch(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
+                             int launch_xcd, int32_t* out);
+int phylo_debug_sweep_launch_of(phylo_ctx* ctx, int32_t* out);
 int phylo_debug_scan_ancestors(phylo_ctx* ctx, const double* logw, int Kg, int G, const uint64_t* seeds, uint32_t r_next, int32_t* anc,
                                int32_t* list, int32_t* cnt);
 /* Test hook, no GPU needed: the form the resampling scan takes for groups of Kg log-weights (sweep_scan_form_of, phylo_sweep_plan.h;

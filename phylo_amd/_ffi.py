@@ -30,7 +30,7 @@ EXPORTS = [
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
-    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_sweep_chain", "phylo_debug_sweep_chain_of", "phylo_debug_scan_ancestors", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_clade_patterns_rule", "phylo_debug_clade_tables", "phylo_debug_clade_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_persist_plan", "phylo_debug_persist_of", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
+    "phylo_math_probe", "phylo_debug_frechet", "phylo_debug_stamps", "phylo_debug_reverse_lists", "phylo_debug_lookahead_lists", "phylo_debug_reverse_plan", "phylo_debug_reverse_plan_batch", "phylo_debug_sweep_plan", "phylo_debug_sweep_chain", "phylo_debug_sweep_chain_of", "phylo_debug_launch_map", "phylo_debug_sweep_launch", "phylo_debug_sweep_launch_of", "phylo_debug_scan_ancestors", "phylo_debug_pack_leaf_codes", "phylo_debug_site_patterns", "phylo_debug_site_patterns_rule", "phylo_debug_site_patterns_of", "phylo_debug_clade_patterns_rule", "phylo_debug_clade_tables", "phylo_debug_clade_patterns_of", "phylo_debug_tree_plan", "phylo_debug_tree_branches_of", "phylo_debug_scan_form", "phylo_debug_persist_plan", "phylo_debug_persist_of", "phylo_debug_device_lists", "phylo_debug_device_lists_of", "phylo_debug_remote_cache", "phylo_debug_site_product",
     "phylo_vi_gradients", "phylo_vi_gradients_batch", "phylo_vi_apply",
     "phylo_site_tile", "phylo_set_site_tile", "phylo_get_site_tile",
     "phylo_comm_unique_id", "phylo_comm_init", "phylo_comm_share", "phylo_comm_allgather", "phylo_comm_max", "phylo_comm_barrier",
@@ -186,6 +186,37 @@ def debug_sweep_chain(N, K, S, K_local=None, G=1, M=1, world=1, transport=False,
     if rc:
         raise PhyloError(rc, lib.phylo_last_error(None).decode())
     return {"taken": bool(out[0]), "item_waves": out[1], "parts": out[2]}
+
+
+def debug_launch_map(n, W, xcd):
+    """Which wave takes which item in a launch of n items at W waves per workgroup (phylo_launch_map.h; no GPU needed): the grid and
+    an int32 array [grid][W] of items; an entry >= n is a wave without work."""
+    lib = load()
+    grid = C.c_int32(0)
+    rc = lib.phylo_debug_launch_map(C.c_int(n), C.c_int(W), C.c_int(int(xcd)), C.byref(grid), None, C.c_int64(0))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    items = np.zeros((grid.value, W), dtype=np.int32)
+    rc = lib.phylo_debug_launch_map(C.c_int(n), C.c_int(W), C.c_int(int(xcd)), C.byref(grid), _ptr(items), C.c_int64(items.size))
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return grid.value, items
+
+
+def debug_sweep_launch(N, K, S, K_local=None, G=1, M=1, world=1, transport=False, flags=0, switches=(), launch_xcd=0):
+    """How the plan launches the record-form merge and the chain bookkeeping (no GPU needed): the arguments of debug_sweep_plan
+    (switches may also name 'clade_tables'), then PHYLO_LAUNCH_XCD as a context reads it (0 = unset, -1 = off, 1 = on, 2 = the
+    merge alone, 3 = the bookkeeping alone).  A dict: 'launch_xcd', 'book_xcd'."""
+    lib = load()
+    names = SWEEP_PLAN_SWITCHES + ("clade_tables",)
+    sw = sum(1 << names.index(name) for name in switches)
+    out = (C.c_int32 * 2)()
+    rc = lib.phylo_debug_sweep_launch(C.c_int(N), C.c_int(K), C.c_int(K if K_local is None else K_local), C.c_int(S), C.c_int(G),
+                                      C.c_int(M), C.c_int(world), C.c_int(int(transport)), C.c_uint32(flags), C.c_uint32(sw),
+                                      C.c_int(launch_xcd), out)
+    if rc:
+        raise PhyloError(rc, lib.phylo_last_error(None).decode())
+    return {"launch_xcd": bool(out[0]), "book_xcd": bool(out[1])}
 
 
 def debug_pack_leaf_codes(codes):
@@ -1154,6 +1185,12 @@ class Context:
         taken = C.c_int32(0)
         self._check(self._lib.phylo_debug_sweep_chain_of(self._h, C.byref(taken)))
         return bool(taken.value)
+
+    def debug_sweep_launch(self):
+        """How this context's last sweep launched its record-form merge and chain bookkeeping: debug_sweep_launch's dict"""
+        out = (C.c_int32 * 2)()
+        self._check(self._lib.phylo_debug_sweep_launch_of(self._h, out))
+        return {"launch_xcd": bool(out[0]), "book_xcd": bool(out[1])}
 
     def debug_scan_ancestors(self, logw, seeds, r_next):
         """The tail of the resampling scan alone (pp_scan_ancestors) on log-weights [G][Kg] with the groups' seeds, for the draws of rank

@@ -76,6 +76,7 @@ struct env_switches {
     int site_patterns = PK_PAT_AUTO;     // PHYLO_SITE_PATTERNS: 0 = never the pattern form of the merge, force = wherever it is valid
     int clade_patterns = PK_CLADE_AUTO;  // PHYLO_CLADE_PATTERNS: 0 = never the clade tables of the pattern form, force = wherever they are eligible
     int trees_chunk = 0;                 // PHYLO_TREES_CHUNK: trees per chunk of phylo_trees_loglik (0 = what PT2_SCRATCH_BYTES holds; tests lower it)
+    int launch_xcd = 0;                  // PHYLO_LAUNCH_XCD: 1 / 0 = an XCD owns a contiguous range of particles, or not (unset: the plan's rule)
     int rell_chunk = 0;                  // PHYLO_RELL_CHUNK: replicates per chunk of phylo_rell, columns per chunk of phylo_rell_multiscale (0 = what PR_CHUNK_BYTES holds; tests lower it)
     void read() {
         eager_nodes = getenv("PHYLO_EAGER_NODES") != nullptr;
@@ -98,6 +99,7 @@ struct env_switches {
         { const char* e = getenv("PHYLO_SCAN_ANCESTORS"); scan_ancestors = e ? atoi(e) : 1; }
         { const char* e = getenv("PHYLO_TREES_CHUNK"); trees_chunk = e ? atoi(e) : 0; }
         { const char* e = getenv("PHYLO_RELL_CHUNK"); rell_chunk = e ? atoi(e) : 0; }
+        { const char* e = getenv("PHYLO_LAUNCH_XCD"); launch_xcd = !e ? 0 : atoi(e) > 0 ? atoi(e) : -1; }
         { const char* e = getenv("PHYLO_P2P"); no_p2p = e && atoi(e) == 0; }
         { const char* e = getenv("PHYLO_P2P_COPY_WORDS"); p2p_copy_words = e ? (size_t)atol(e) : 65536; }
         { const char* e = getenv("PHYLO_P2P_WAIT_S"); p2p_wait_ticks = e && atof(e) > 0 ? (unsigned long long)(atof(e) * 1e8) : PK_P2P_WAIT_TICKS; }
@@ -2263,6 +2265,7 @@ static sweep_facts sweep_facts_of(const phylo_ctx* c, uint32_t flags, int M, int
     sweep_facts_flags(f, flags);
     f.env_eager_nodes = c->env.eager_nodes; f.env_rehearse_sharded = c->env.rehearse_sharded;
     f.env_replicated_book = c->env.replicated_book;
+    f.env_launch_xcd = c->env.launch_xcd;
     f.clade_tables = c->clade_ready && pk_pat_take(c->S, c->pat_U, c->leaves_coded, c->ntiles, c->env.site_patterns);
     return f;
 }
@@ -2661,6 +2664,7 @@ static pk_rank_args rank_args(const phylo_ctx* c, int r) {
         b.anc_in = c->d_anc_next; b.adopt_list = c->d_adopt_list; b.adopt_cnt = c->d_adopt_cnt;
         b.item_waves = c->run.chain.item_waves; b.item_parts = c->run.chain.parts;
     }
+    b.book_xcd = c->run.chain.taken && p.book_xcd;
     return b;
 }
 
@@ -2776,7 +2780,7 @@ static int step_book(phylo_ctx* c, const pk_rank_args& b) {
     const sweep_chain_form& ch = c->run.chain;
     if (ch.taken) {                                        // the ancestors from the scan; the item waves of the adopted nodes lead the grid
         const int items = b.r > 0 ? p.G * ch.item_waves : 0;
-        const dim3 grid(items + cdiv(K, per));
+        const dim3 grid(items + pk_launch_grid(cdiv(K, per), 1, p.book_xcd));
         if (p.clade_pat) {
             if (w == 8) hipLaunchKernelGGL(pk_rank_book_chain_clade<8>, grid, dim3(64), lds * per, c->stream, b, items);
             else if (w == 16) hipLaunchKernelGGL(pk_rank_book_chain_clade<16>, grid, dim3(64), lds * per, c->stream, b, items);
@@ -2844,8 +2848,10 @@ static int step_merge(phylo_ctx* c, const pk_rank_args& b) {
             pat.U = c->pat_U;
             lds = pk_pat_lds_bytes(c->pat_U);
         }
-        launch_stamped(pk_rank_merge_nostore, mgrid, dim3(64), lds, c->stream, e0, e1, (const unsigned long long*)b.rec, b.Pmat, S, b.T,
-                       b.ntiles, b.tilev, pi4, pat);
+        // which wave takes which item: phylo_launch_map.h, by the plan's launch_xcd (the kernel reads it off the sign of the count)
+        const int n = (int)mgrid.x, grid = pk_launch_grid(n, 1, p.launch_xcd), n_xcd = p.launch_xcd ? -n : n;
+        launch_stamped(pk_rank_merge_nostore, dim3((unsigned)grid), dim3(64), lds, c->stream, e0, e1, (const unsigned long long*)b.rec, b.Pmat,
+                       S, b.T, b.ntiles, n_xcd, b.tilev, pi4, pat);
     } else {
         launch_stamped(pk_rank_merge_nostore_ids, mgrid, dim3(64), 0, c->stream, e0, e1, b);
     }
@@ -4052,6 +4058,45 @@ int phylo_debug_sweep_chain(int N, int K, int K_local, int S, int G, int M, int 
         return fail(nullptr, PHYLO_EINVAL, "%s", why);
     const sweep_chain_form ch = sweep_chain_form_of(sweep_plan_form(f, k_sweep_limits), S, multi_min, scan_ancestors, k_sweep_limits);
     out[0] = ch.taken ? 1 : 0; out[1] = ch.item_waves; out[2] = ch.parts;
+    return PHYLO_OK;
+}
+
+int phylo_debug_sweep_launch(int N, int K, int K_local, int S, int G, int M, int world, int transport, uint32_t flags, uint32_t switches,
+                             int launch_xcd, int32_t* out) {
+    if (N < 2 || N > PK_MAX_TAXA || K < 1 || K_local < 1 || K_local > K || S < 1 || world < 1 || !out)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_sweep_launch: bad arguments");
+    sweep_facts f{};
+    f.N = N; f.K = K; f.Kloc = K_local; f.S = S; f.G = G; f.M = M; f.world = world;
+    f.ntiles = (S + pm_site_tile(S) - 1) / pm_site_tile(S);
+    f.transport = transport != 0;
+    sweep_facts_flags(f, flags);
+    f.env_eager_nodes = switches & 1; f.env_rehearse_sharded = switches & 2; f.env_replicated_book = switches & 4;
+    f.jc = switches & 8; f.coded_leaves = switches & 16; f.device_exchange = switches & 32; f.clade_tables = switches & 64;
+    f.env_launch_xcd = launch_xcd;
+    char why[160];
+    if (sweep_refuses_batch(f, k_sweep_limits, why, sizeof why) || sweep_refuses_form(f, k_sweep_limits, why, sizeof why))
+        return fail(nullptr, PHYLO_EINVAL, "%s", why);
+    const sweep_plan p = sweep_plan_form(f, k_sweep_limits);
+    out[0] = p.launch_xcd ? 1 : 0; out[1] = p.book_xcd ? 1 : 0;
+    return PHYLO_OK;
+}
+
+int phylo_debug_sweep_launch_of(phylo_ctx* c, int32_t* out) {
+    if (!c || !out) return fail(c, PHYLO_EINVAL, "phylo_debug_sweep_launch_of: NULL argument");
+    const sweep_plan& p = c->run.plan;
+    out[0] = p.launch_xcd ? 1 : 0; out[1] = p.book_xcd ? 1 : 0;
+    return PHYLO_OK;
+}
+
+int phylo_debug_launch_map(int n, int W, int xcd, int32_t* grid, int32_t* items, int64_t cap) {
+    if (n < 1 || (W != 1 && W != 2 && W != 4) || !grid)
+        return fail(nullptr, PHYLO_EINVAL, "phylo_debug_launch_map: bad arguments");
+    const int g = pk_launch_grid(n, W, xcd != 0);
+    *grid = g;
+    if (!items) return PHYLO_OK;
+    if (cap < (int64_t)g * W) return fail(nullptr, PHYLO_EINVAL, "phylo_debug_launch_map: items needs %lld entries", (long long)g * W);
+    for (int b = 0; b < g; ++b)
+        for (int w = 0; w < W; ++w) items[(size_t)b * W + w] = pk_launch_item(b, g, W, w, xcd != 0);
     return PHYLO_OK;
 }
 

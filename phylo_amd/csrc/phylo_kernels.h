@@ -7,6 +7,7 @@
 #include "phylo_math.h"
 #include "phylo_packed_codes.h"
 #include "phylo_site_patterns.h"
+#include "phylo_launch_map.h"
 
 #define PK_COLS 256          // canonical site-sum columns == threads per merge workgroup
 #define PK_AUX 8             // per-particle scalars handed from the bookkeeping kernel to the merge epilogue
@@ -687,6 +688,7 @@ struct pk_rank_args {
     const int32_t* adopt_list;                            // [K] group g's adopted particles at [g Kg, g Kg + adopt_cnt[g]), ascending
     const int32_t* adopt_cnt;                             // [G]
     int item_waves, item_parts;                           // pk_mat_listed: waves per group, parts of a node's sites
+    int book_xcd;                                         // the particle waves behind them: an XCD owns a contiguous range (the plan's book_xcd)
     // clade patterns (phylo_site_patterns.h; the plan's clade_pat): the leaf bitset of every root, adopted with the ancestor's row,
     // OR-ed for the new node and handed to the merge in the record's flag word from bit 2 on.  NULL: not taken, nothing is touched.
     const int32_t* bits_old; int32_t* bits_new;           // [K][N]
@@ -1384,7 +1386,11 @@ __device__ __forceinline__ void pk_rank_book_chain_body(const pk_rank_args& a, i
     }
     const int lane = threadIdx.x, sub = lane / LP, sl = lane & (LP - 1);
     const int count = a.tab_ptrs ? a.Kloc : a.K;
-    int idx = ((int)blockIdx.x - item_wgs) * (64 / LP) + sub;
+    // the waves behind the item waves, each 64 / LP particles (phylo_launch_map.h: with a.book_xcd an XCD owns a contiguous range)
+    const int nwg = (int)gridDim.x - item_wgs;
+    const int first = pk_launch_item((int)blockIdx.x - item_wgs, nwg, 64 / LP, 0, a.book_xcd != 0);
+    if (first >= count) return;                 // (a surplus wave of the rounded grid: one wave, no barrier)
+    int idx = first + sub;
     if (idx >= count) idx = count - 1;          // a spare group repeats the last particle: identical values, identical writes
     const int kg = a.tab_ptrs ? a.k0 + idx : idx;
     const pk_book_lds L = BITS ? pk_book_carve_sub(smem, sub, 64 / LP, a.N) : pk_book_carve(smem + (size_t)sub * pk_book_lds_bytes(a.N), a.N);
@@ -2342,19 +2348,24 @@ __device__ __forceinline__ bool pk_rows_loop_rec(int s0, int s1, const char* bl,
     }
 }
 // (the argument segment of the kernel below, as the compiler lays it out)
-struct pk_merge_kernarg { const unsigned long long* rec; const double* Pmat; int S, T, ntiles; double* tilev; pk_pi4 pi4; pk_pat_args pat; };
+// (n_xcd sits in the padding behind ntiles: the items of the launch, negated where an XCD owns a contiguous range of them)
+struct pk_merge_kernarg { const unsigned long long* rec; const double* Pmat; int S, T, ntiles, n_xcd; double* tilev; pk_pi4 pi4; pk_pat_args pat; };
 // (amdgpu_num_vgpr: on gfx90a and later the backend counts it in units of the unified register file, twice the number written, so
 // this caps the allocator at 64 vector registers -- 8 waves per SIMD; the 7-wave bound alone allows it 72, and it used 65)
+// One wave per workgroup and item (phylo_launch_map.h says which; two and four waves per workgroup, each with tables and an LDS slice
+// of its own, measured no faster on the remapped launch and slower without it: DESIGN.md section 8).  No barrier: a wave of the
+// rounded grid that has no item leaves at once.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8), amdgpu_num_vgpr(32)))
 void pk_rank_merge_nostore(const unsigned long long* __restrict__ rec, const double* __restrict__ Pmat, int S, int T, int ntiles,
-                           double* __restrict__ tilev, const pk_pi4 pi4, const pk_pat_args pat) {
+                           int n_xcd, double* __restrict__ tilev, const pk_pi4 pi4, const pk_pat_args pat) {
     // (row 5 of a table and lik25[25 .. 29] belong to the pad code beside a real one: never written, read only where the site is
     // past the end and the factor is replaced; lik25[30] = 1.0 is pad x pad)
     __shared__ __attribute__((aligned(16))) double tabL[PK_PAD_CODE + 1][4], tabR[PK_PAD_CODE + 1][4];
     __shared__ double lik25[PK_PAD_CODE * 6 + 1];
     // the pattern form's table of site likelihoods, sized by the launch (pk_pat_lds_bytes; nothing where the form is not taken)
     extern __shared__ __attribute__((aligned(16))) double pk_ulik[];
-    const int item = (int)blockIdx.x;
+    const int item = pk_launch_item((int)blockIdx.x, (int)gridDim.x, 1, 0, n_xcd < 0);
+    if (item >= (n_xcd < 0 ? -n_xcd : n_xcd)) return;      // (a surplus wave of the rounded grid)
     const int k = __builtin_amdgcn_readfirstlane(ntiles == 1 ? item : item / ntiles), tau = item - k * ntiles;
     // (the tile's bounds come out of an integer division, which the vector pipe computes: said to be wave-uniform here, or every
     // test on them below is a vector compare)

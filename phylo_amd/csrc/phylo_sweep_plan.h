@@ -40,6 +40,9 @@ struct sweep_facts {
     // the clade tables of the current leaves are built and the merge's pattern form is taken (phylo_site_patterns.h: pk_clade_take,
     // pk_pat_take -- the rule and PHYLO_CLADE_PATTERNS were applied when the leaves were set)
     bool clade_tables;
+    // PHYLO_LAUNCH_XCD as the context read it (A/B runs and tests): 0 = unset, -1 = off, 1 = on; for runs that price the two launches
+    // apart, 2 = the merge alone, 3 = the bookkeeping alone
+    int env_launch_xcd;
 };
 
 struct sweep_plan {
@@ -74,6 +77,8 @@ struct sweep_plan {
     int gather_launches;               // kernels of graph_gather behind the last rank event (sharded kept graph)
     bool clade_pat;                    // clade patterns: the root tables carry leaf bitsets, the record's flag word the new clade's,
                                        // and the merge's phase 1 runs over the clade's block
+    bool launch_xcd;                   // an XCD owns a contiguous range of particles in the record-form merge ...
+    bool book_xcd;                     // ... and in the particle part of the chain form's bookkeeping
 };
 
 // PHYLO_EAGER_NODES, as a flag or from the environment: every node is stored by its merge (also read by persist_plan)
@@ -186,6 +191,15 @@ inline sweep_plan sweep_plan_form(const sweep_facts& f, const sweep_limits& L) {
     // clade patterns: the record-form merge of one site tile, root tables in the two planes (a kept graph writes history planes,
     // which carry no bitsets).  Sharded, twisted and eager sweeps write no record.
     p.clade_pat = f.clade_tables && p.use_rec && !p.graph && f.ntiles == 1;
+    // How the record-form merge (one rank, plain proposal) and the chain bookkeeping are launched (phylo_launch_map.h; DESIGN.md
+    // section 8 has the measurements).  Neither changes a bit of the result; the switches override for A/B runs and the tests.
+    // Large launches only (batched sweeps): there the particles of a sweep share ancestors' rows and clade blocks in one L2 (merge
+    // 37.9 -> 36.4 us per rank event of 20 sweeps of 2 048).  A single sweep of 2 048 particles is a latency chain of small launches:
+    // its t_sweep read 1 % higher with the remap, so small launches keep the plain deal.
+    const int x = f.env_launch_xcd;
+    const bool large = (long)Kl * f.ntiles > L.small_max_kloc;
+    p.launch_xcd = p.use_rec && (x == 0 ? large : x == 1 || x == 2);
+    p.book_xcd = p.use_rec && (x == 0 ? large : x == 1 || x == 3);
     return p;
 }
 
