@@ -227,6 +227,27 @@ int phylo_trees_grad_rates(phylo_ctx* ctx, int T, const int32_t* child, const do
 int phylo_trees_grad_model(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int P, const double* dirs_Px16,
                            const double* prior4, double* loglik_T, double* grad, double* dtheta_TxP, double* dprior_Tx4,
                            phylo_stats* perf);
+/* Marginal ancestral state posteriors of a scored tree set: which state sat at every internal node at
+ * every site, and how sure we are.  T trees given as phylo_trees_grad takes them (same numbering, checks, state rules, prior4 ==
+ * NULL).  R = N - 1; row i of the outputs is internal node N + i of the caller's tree, row N - 2 the root.  With x_v = msg_l * msg_r
+ * (the upward pass's bits), abar_v the outer partial of section 13 (the prior at the root) and inv = 1 / L_s:
+ *   post_TxRxSx4[t][i][s][j] (may be NULL) = (abar_v[j] * x_v[j]) * inv, three IEEE operations each rounded on its own, NOT renormalised;
+ *   state_TxRxS[t][i][s]     (may be NULL) = the lowest j whose post is the largest of the four; PHYLO_ANC_NOSTATE if any is NaN;
+ *   pmax_TxRxS[t][i][s]      (may be NULL) = post[state], or NaN where there is no state;
+ *   loglik_T[t]              bit for bit phylo_trees_loglik's value (required).
+ * Not all three of post, state and pmax may be NULL.  NaN rule, per SITE: a site whose L_s lies below 2^-1020 or is not finite
+ * gets NaN / PHYLO_ANC_NOSTATE in its own column at every node; every other site of the tree is untouched and loglik_T stays the
+ * scoring call's bits.  No sum over sites: the call repeats its own bits, and chunking, the grid cap, a tree's place in the set
+ * and which outputs are asked for change none.  perf (may be NULL): sweep_ms = device time, n_launches, units = T S (N-1).
+ * Synchronous; on a sharded context a LOCAL call.  PHYLO_EINVAL before anything is queued for a bad tree (naming tree and row),
+ * for child, blen or loglik_T == NULL, for all three outputs NULL, and for a single tree whose requested outputs exceed 1 GiB
+ * (naming the size).  A chunk is the smallest of: the trees that fit phylo_trees_grad's 64 MiB slab, the trees whose requested
+ * outputs (R S (32 + 1 + 8) bytes each, over those asked for) fit a 256 MiB staging region (which grows to one tree's need), and
+ * PHYLO_TREES_CHUNK.  Own scratch and events, released with the context; everything phylo_trees_grad leaves alone, and the
+ * scratch of its siblings, is left alone. */
+#define PHYLO_ANC_NOSTATE 255
+int phylo_trees_ancestral(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
+                          double* post_TxRxSx4, uint8_t* state_TxRxS, double* pmax_TxRxS, phylo_stats* perf);
 /* The NNI neighbourhood of every tree of a set, at the tree's current branch lengths: for T trees given as
  * phylo_trees_loglik takes them (same numbering, same checks, same state rules),
  *   loglik_T[t]        bit for bit phylo_trees_loglik's value for the same tree, prior and site tile;

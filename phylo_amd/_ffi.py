@@ -22,11 +22,12 @@ KEEP_GRAPH = 1 << 4
 ONE_LAUNCH = 1 << 5
 FLAGS_DEFAULT = QUIRK_Q1_RAW_Q
 COMM_ID_BYTES = 128
+ANC_NOSTATE = 255                                          # PHYLO_ANC_NOSTATE: a site of trees_ancestral without a most probable state
 
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_grad_model", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_rell_multiscale", "phylo_debug_rell_multiscale_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_grad_model", "phylo_trees_ancestral", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_rell_multiscale", "phylo_debug_rell_multiscale_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -708,6 +709,31 @@ class Context:
                                                C.byref(st)))
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         return (out, grad, curv) if want_curv else (out, grad)
+
+    def trees_ancestral(self, child, blen, prior=None, want_post=True, want_state=True, want_pmax=False):
+        """Marginal ancestral state posteriors of T explicit trees (phylo_trees_ancestral): returns (loglik [T]) followed by post
+        [T][N-1][S][4] with want_post, state [T][N-1][S] (uint8, the most probable state; ANC_NOSTATE where the site has none)
+        with want_state and pmax [T][N-1][S] (its posterior) with want_pmax.  Row i is internal node N + i of the tree as given,
+        the last row the root.  post is not renormalised; a site whose factor lies below 2^-1020 has NaN / ANC_NOSTATE in its own
+        column and leaves every other site alone.  loglik is bit for bit trees_loglik's.  self.last_trees_stats holds the call's
+        stats.  phylo_amd.ancestral turns the arrays into sequences, clade names and summaries."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        if not (want_post or want_state or want_pmax):
+            raise ValueError("one of want_post, want_state and want_pmax must be set")
+        R = self.N - 1
+        out = np.empty(T)
+        post = np.empty((T, R, self.S, 4)) if want_post else None
+        state = np.empty((T, R, self.S), dtype=np.uint8) if want_state else None
+        pmax = np.empty((T, R, self.S)) if want_pmax else None
+        st = Stats()
+        self._check(self._lib.phylo_trees_ancestral(self._h, C.c_int(T), _ptr(child), _ptr(blen), _ptr(pr), _ptr(out), _ptr(post), _ptr(state),
+                                                    _ptr(pmax), C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return (out,) + tuple(x for x in (post, state, pmax) if x is not None)
 
     def trees_grad_model(self, child, blen, dirs, prior=None, want_grad=False, want_prior=True):
         """Derivatives of trees_loglik with respect to the substitution model (phylo_trees_grad_model): dirs [P][4][4] are P

@@ -305,7 +305,7 @@ class VCSMC:
         return [row[0] for row in tab]
 
     def score_trees(self, newicks, rates=None, want_sites=False, optimize=False, fit=(), search=None, search_rounds=20, fit_model=(),
-                    fit_on=None, fit_rounds=20):
+                    fit_on=None, fit_rounds=20, ancestral=0):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
         distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
         (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
@@ -335,7 +335,24 @@ class VCSMC:
         model is put back before this returns, and the fitted one is handed to the caller in self.last_model_fit ('Q', 'pi',
         'y_q', 'y_station', 'fit_on', 'rounds', 'objective_start', 'objective', 'history').  The scores and site factors come
         from one trees_loglik under the fitted model; self.last_tree_opt is as with optimize alone ('loglik_given' under the
-        model given, 'newicks' at the lengths climbed under the fitted model)."""
+        model given, 'newicks' at the lengths climbed under the fitted model).
+        ancestral=k (one rate only): after everything else asked for, and before a fitted model is put back, the k best trees by
+        the final score are reconstructed at the final lengths and model (phylo_trees_ancestral): self.last_ancestral holds
+        'trees' (their indices, best first), 'newicks', 'child', 'loglik', 'state' and 'pmax' [k][N-1][S]."""
+        ancestral = int(ancestral or 0)
+        if ancestral < 0 or (ancestral and rates is not None):
+            raise ValueError("score_trees: ancestral=%r needs k >= 1 and no rates (the posteriors are not built for mixtures)" % (ancestral,))
+        self.last_ancestral = None
+
+        def reconstruct(ctx, child, blen, loglik):
+            if not ancestral:
+                return
+            order = np.argsort(-np.asarray(loglik, dtype=np.float64), kind='stable')[:ancestral]
+            ll, state, pmax = ctx.trees_ancestral(child[order], blen[order], want_post=False, want_state=True, want_pmax=True)
+            self.last_ancestral = {'trees': [int(t) for t in order], 'child': child[order].copy(), 'loglik': [float(x) for x in ll],
+                                   'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(child[order], blen[order])],
+                                   'state': state, 'pmax': pmax}
+
         fit = tuple(fit)
         fit_model = tuple(fit_model)
         if fit_model and (not optimize or rates is not None or fit or search is not None):
@@ -420,6 +437,7 @@ class VCSMC:
                 blen = mf['blen']
                 under(mf['Q'], mf['pi'])
                 res = ctx.trees_loglik(child, blen, want_sites=True)
+                reconstruct(ctx, child, blen, res[0])       # under the fitted model, before the context's own is put back
             finally:
                 self._context()                             # the context's model again, from the same numbers: the same bits
             opt = mf['branches']
@@ -449,9 +467,11 @@ class VCSMC:
                                          'rounds': [int(r) for r in found['rounds']], 'converged': [bool(v) for v in found['converged']]}
                 child, blen = found['child'], found['blen']
             res = ctx.trees_loglik(child, blen, want_sites=True)
+            reconstruct(ctx, child, blen, res[0])
             res = res if want_sites else res[0]
         elif rates is None:
             res = ctx.trees_loglik(child, blen, want_sites=want_sites)
+            reconstruct(ctx, child, blen, res[0] if want_sites else res)
         else:
             res = ctx.trees_loglik_rates(child, blen, rates[0], rates[1], want_sites=want_sites)
         if want_sites:
@@ -498,6 +518,8 @@ class VCSMC:
         self.trees_ml = None
         self.trees_search = None
         self.model_ml = None
+        self.ancestral_results = None
+        anc = int(getattr(self.args, 'score_ancestral', None) or 0) if newicks else 0   # --score_ancestral K: the K best trees reconstructed
         mfit = getattr(self.args, 'score_model_fit', None) if ml else None  # --score_model_fit q | q+pi: one ML model for all trees
         mfit = tuple(mfit.split('+')) if mfit else None
         srch = getattr(self.args, 'score_search', None) if ml else None     # --score_search nni[:ROUNDS]: then an NNI search from there
@@ -510,18 +532,18 @@ class VCSMC:
             self.trees_ml, self.trees_search = opt['newicks'], found['newicks']
             srch, ml = fsrch, True
         elif srch:
-            ll_search, sites = self.score_trees(newicks, want_sites=True, optimize=True, search=srch[0], search_rounds=srch[1])
+            ll_search, sites = self.score_trees(newicks, want_sites=True, optimize=True, search=srch[0], search_rounds=srch[1], ancestral=anc)
             opt, found = self.last_tree_opt, self.last_tree_search
             ll, ll_ml = opt['loglik_given'], found['loglik_ml']
             self.trees_ml, self.trees_search = opt['newicks'], found['newicks']
         elif ml and mfit:
-            ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True, fit_model=mfit)
+            ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True, fit_model=mfit, ancestral=anc)
             opt = self.last_tree_opt
             ll = opt['loglik_given']
             self.trees_ml = opt['newicks']
             self.model_ml = self.last_model_fit
         elif ml:
-            ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True)
+            ll_ml, sites = self.score_trees(newicks, want_sites=True, optimize=True, ancestral=anc)
             opt = self.last_tree_opt
             ll = opt['loglik_given']
             self.trees_ml = opt['newicks']
@@ -532,9 +554,11 @@ class VCSMC:
             self.trees_ml = opt['newicks']
             ml = True
         elif tests and newicks:                            # --tree_tests: from the site factors of this very scoring call
-            ll, sites = self.score_trees(newicks, rates=mix, want_sites=True)
+            ll, sites = self.score_trees(newicks, rates=mix, want_sites=True, ancestral=anc)
         else:
-            ll = self.score_trees(newicks, rates=mix)
+            ll = self.score_trees(newicks, rates=mix, ancestral=anc)
+        if anc:                                            # (absent without --score_ancestral)
+            self.ancestral_results = self.last_ancestral
         if tests and newicks:                              # (with --score_opt: the site factors at the ML lengths)
             from . import treetests
             self.tree_test_results = self.tree_tests(sites, *treetests.parse_spec(tests), au=getattr(self.args, 'tree_tests_au', None))
@@ -576,6 +600,27 @@ class VCSMC:
             out['summary'] = {'map': scored(post.map_newick), 'consensus_bl': scored(post.consensus_bl), 'topologies': tops}
         return out
 
+    def _save_ancestral(self, save_dir, res):
+        """ancestral.fa and ancestral.json of --score_ancestral: per reconstructed tree one FASTA record per internal node
+        ('>tree{t}_node{N+i} clade=a,b,c', the most probable states as letters), and its index, Newick string and per node the
+        numbers of phylo_amd.ancestral.summarise"""
+        import json
+        import os
+        from . import ancestral as anc
+        taxa = [str(t) for t in self.taxa]
+        records, trees = [], []
+        nn = lambda a: [None if x != x else float(x) for x in a]           # NaN (a node without a usable site) is null in JSON
+        for t, child, nw, ll, state, pmax in zip(res['trees'], res['child'], res['newicks'], res['loglik'], res['state'], res['pmax']):
+            records += anc.fasta_records(state, child, taxa, tree=t)
+            sm = anc.summarise(pmax)
+            trees.append({'tree': t, 'newick': nw, 'loglik': ll,
+                          'nodes': [{'node': self.N + i, 'clade': cl, 'mean_pmax': m, 'share_below_0.9': sh, 'n_nan': int(k)}
+                                    for i, (cl, m, sh, k) in enumerate(zip(anc.node_clades(child, taxa), nn(sm['mean_pmax']),
+                                                                           nn(sm['share_below']), sm['n_nan']))]})
+        anc.write_fasta(os.path.join(save_dir, 'ancestral.fa'), records)
+        with open(os.path.join(save_dir, 'ancestral.json'), 'w') as f:
+            json.dump({'trees': trees}, f, indent=1)
+
     def _save_results(self, save_dir, initial, history):
         """run_parameters.txt and results.p with the reference's keys (vcsmc.py:503-516, 618-642); no plots."""
         import os
@@ -584,7 +629,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'tree_tests_au', 'score_opt', 'score_fit', 'score_search', 'score_fit_search', 'score_model_fit') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'tree_tests_au', 'score_opt', 'score_fit', 'score_search', 'score_fit_search', 'score_model_fit', 'score_ancestral') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))
@@ -718,6 +763,8 @@ class VCSMC:
                 if getattr(self, 'tree_test_results', None) is not None:
                     with open(os.path.join(save_dir, 'tree_tests.json'), 'w') as f:
                         json.dump(self.tree_test_results, f, indent=1)
+                if getattr(self, 'ancestral_results', None) is not None:
+                    self._save_ancestral(save_dir, self.ancestral_results)
             self.save_dir = save_dir
             print("Finished...")
         return self.elbos

@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--score_model_fit`, `--tree_tests`, `--tree_tests_au` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--score_model_fit`, `--score_ancestral`, `--tree_tests`, `--tree_tests_au` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -104,6 +104,14 @@ def parse_args(argv=None):
                              "trees found once more; writes trees_search.nwk, adds loglik_search, nni_moves and search_rounds (and "
                              "alpha_search, pinv_search where fitted) to every tree of tree_scores.json, and gives --tree_tests the "
                              "site likelihoods of the trees found")
+    parser.add_argument('--score_ancestral', default=None, type=int, metavar='K',
+                        help="with --score_trees: reconstruct the marginal ancestral states of the K best trees by their final score "
+                             "(K >= 1; phylo_trees_ancestral on the device), at the final lengths and model (after --score_opt, "
+                             "--score_search and --score_model_fit where given); writes ancestral.fa (one record per internal node, "
+                             "'>tree{t}_node{n} clade=a,b,c', the most probable state of every site as a letter, '?' where a site "
+                             "has none) and ancestral.json (per tree its index, its Newick string and per node the mean posterior "
+                             "of the most probable state and the share of sites below 0.9).  Not with --score_rates, --score_fit "
+                             "or --score_fit_search")
     parser.add_argument('--tree_tests', default=None, metavar='B[:SEED]',
                         help="with --score_trees: which of those trees are significantly worse than the best one?  A RELL bootstrap "
                              "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
@@ -180,6 +188,14 @@ def parse_args(argv=None):
             parser.error('--score_fit and --score_opt true exclude one another (--score_fit branches is --score_opt under the rate model)')
         if 'alpha' in args.score_fit and rates.parse_spec(args.score_rates)['C'] < 2:
             parser.error('--score_fit %s: one category has no shape to fit (--score_rates with C >= 2)' % args.score_fit)
+    if args.score_ancestral is not None:
+        if args.score_ancestral < 1:
+            parser.error('--score_ancestral: K >= 1 trees to reconstruct, not %d' % args.score_ancestral)
+        if not args.score_trees:
+            parser.error('--score_ancestral needs --score_trees FILE (it reconstructs the best of the trees scored there)')
+        if args.score_rates is not None or args.score_fit is not None or args.score_fit_search is not None:
+            parser.error('--score_ancestral: the ancestral posteriors are not built for rate mixtures (not with --score_rates, '
+                         '--score_fit or --score_fit_search)')
     if args.tree_branches and not args.tree_summary:
         parser.error('--tree_branches true needs --tree_summary true (it adds branch lengths to that summary)')
     if args.twisting is not None:

@@ -55,6 +55,8 @@ def cycle(i):
                                                             # ... and the mixture neighbourhood's, with its own pair of events
         c.trees_grad_model(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1), np.linspace(-1.0, 1.0, (1 + i % 16) * 16).reshape(-1, 4, 4),
                            want_grad=True)                  # ... and the model gradient's: a slab that grows with the directions
+        c.trees_ancestral(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1), want_pmax=i % 2 == 1)
+                                                            # ... and the ancestral posteriors': staged outputs that grow with what is asked for
     v = T.Variables(N2, np.log(10.0), False)            # a context of 66 taxa that trains: two steps, so two passes on one context
     tr = T.Trainer(g2, 32 + 4 * (i % 8), v, T.make_optimizer('Adam', 0.01), S2)
     try:

@@ -44,7 +44,14 @@ phylo_trees_loglik_rates' bits, and the worst relative difference of loglik + de
 --model times phylo_trees_grad_model along --dirs P directions of the row-softmax Q (and with P = 1)
 against phylo_trees_grad without curvature, phylo_trees_loglik, and the central-difference yardstick it replaces -- 2 P pairs of
 set_model and phylo_trees_loglik --, interleaved in the same run: device and wall times, their ratios, the number of chunks, and
-whether loglik and grad carry the siblings' bits."""
+whether loglik and grad carry the siblings' bits.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --ancestral --reps 7 --out profiles/trees_probe.jsonl
+
+--ancestral times phylo_trees_ancestral with states only and with post (the latter on the first
+--post_trees trees: its output is 32 bytes per node-site, on the device and on the host) against phylo_trees_grad without
+curvature on the same trees, interleaved in the same run: device and wall times, their ratios, the bytes each form writes, the
+number of chunks, and whether loglik carries phylo_trees_grad's bits."""
 import argparse
 import json
 import os
@@ -466,6 +473,63 @@ def nni_rates_probe(a):
     return 0 if same and worst < 1e-9 else 1
 
 
+def ancestral_probe(a):
+    """phylo_trees_ancestral with states only and with post against phylo_trees_grad without curvature: same trees, same context,
+    same run"""
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    n_post = min(a.post_trees, a.trees) if a.post_trees > 0 else a.trees
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    u64 = lambda x: np.ascontiguousarray(x).view(np.uint64)
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        lg, grad = ctx.trees_grad(child, blen)               # warm-up of all three
+        ls, state = ctx.trees_ancestral(child, blen, want_post=False, want_state=True)
+        lp, post, state_p = ctx.trees_ancestral(child[:n_post], blen[:n_post])
+        same = bool(np.array_equal(u64(lg), u64(ls)) and np.array_equal(u64(lg[:n_post]), u64(lp)) and np.array_equal(state[:n_post], state_p))
+        nostate = int((state == _ffi.ANC_NOSTATE).sum())
+        del post, state_p
+        calls = (('grad', lambda: ctx.trees_grad(child, blen)),
+                 ('state', lambda: ctx.trees_ancestral(child, blen, want_post=False, want_state=True)),
+                 ('post', lambda: ctx.trees_ancestral(child[:n_post], blen[:n_post], want_post=True, want_state=False)))
+        t = {k: ([], []) for k, _ in calls}
+        stats = {}
+        for _ in range(a.reps):                              # interleaved: all three see the same machine
+            for k, call in calls:
+                t0 = time.perf_counter()
+                call()
+                t[k][0].append((time.perf_counter() - t0) * 1e3)
+                t[k][1].append(ctx.last_trees_stats['sweep_ms'])
+                stats[k] = dict(ctx.last_trees_stats)
+    q = {k: (quartiles(v[0]), quartiles(v[1])) for k, v in t.items()}
+    per = 4 if ((g == 0) | (g == 1)).all() and (g.sum(axis=2) >= 1).all() else 3
+    rec = {'probe': 'trees_ancestral', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'post_trees': int(n_post), 'jc': jc,
+           'reps': a.reps, 'grad_wall_ms': q['grad'][0], 'grad_device_ms': q['grad'][1], 'state_wall_ms': q['state'][0],
+           'state_device_ms': q['state'][1], 'post_wall_ms': q['post'][0], 'post_device_ms': q['post'][1],
+           'device_ratio_state_over_grad': q['state'][1]['median'] / q['grad'][1]['median'],
+           'wall_ratio_state_over_grad': q['state'][0]['median'] / q['grad'][0]['median'],
+           'state_bytes_written': float(a.trees) * (N - 1) * S, 'post_bytes_written': float(n_post) * (N - 1) * S * 32,
+           'post_device_GB_per_s': float(n_post) * (N - 1) * S * 32 / (q['post'][1]['median'] * 1e-3) / 1e9,
+           'state_launches': stats['state']['n_launches'], 'state_chunks': stats['state']['n_launches'] // per,
+           'post_launches': stats['post']['n_launches'], 'post_chunks': stats['post']['n_launches'] // per,
+           'units': stats['state']['units'], 'units_per_s_device_state': stats['state']['units'] / (q['state'][1]['median'] * 1e-3),
+           'units_per_s_device_grad': stats['grad']['units'] / (q['grad'][1]['median'] * 1e-3),
+           'sites_without_state': nostate, 'loglik_bit_equal': same}
+    line = json.dumps(rec)
+    print(line)
+    print("loglik bit for bit phylo_trees_grad's: %s" % same)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -482,8 +546,12 @@ def main(argv=None):
     ap.add_argument('--nni', action='store_true', help='probe phylo_trees_nni against phylo_trees_loglik on the explicit neighbours, and phylo_trees_grad')
     ap.add_argument('--explicit_trees', type=int, default=512, help='with --nni: trees whose neighbours are built and scored explicitly (0: all)')
     ap.add_argument('--model', action='store_true', help='probe phylo_trees_grad_model against phylo_trees_grad, the plain call and central differences')
+    ap.add_argument('--ancestral', action='store_true', help='probe phylo_trees_ancestral (states only, and with post) against phylo_trees_grad')
+    ap.add_argument('--post_trees', type=int, default=512, help='with --ancestral: trees of the call that asks for post (0: all)')
     ap.add_argument('--dirs', type=int, default=12, help='with --model: directions of a call (1 .. 16)')
     a = ap.parse_args(argv)
+    if a.ancestral:
+        return ancestral_probe(a)
     if a.model:
         return model_probe(a)
     if a.nni and a.rates > 0:
