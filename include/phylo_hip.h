@@ -248,6 +248,37 @@ int phylo_trees_grad_model(phylo_ctx* ctx, int T, const int32_t* child, const do
 #define PHYLO_ANC_NOSTATE 255
 int phylo_trees_ancestral(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
                           double* post_TxRxSx4, uint8_t* state_TxRxS, double* pmax_TxRxS, phylo_stats* perf);
+/* phylo_trees_ancestral under a mixture of C rate categories, and the site-rate posteriors beside it.
+ * Trees, numbering, per-tree checks, state rules and prior4 == NULL as phylo_trees_grad_rates; rate, weight [C] (per_tree == 0) or
+ * [T][C] (per_tree == 1), 1 <= C <= 16, checked as phylo_trees_grad_rates checks them.  Category c of tree t is the tree (child,
+ * rate[t][c] blen), one multiply per length on the host.  R = N - 1; rows as phylo_trees_ancestral (row i is node N + i, row N - 2
+ * the root).  Inside category c everything is phylo_trees_ancestral's under that category's matrices: x_{v,c} = msg_l * msg_r, the
+ * outer partial abar_{v,c} (the prior at the root), f_c = prior . x_root,c.  m_s = w_0 f_0, then fma(w_c, f_c, m) in ascending c
+ * (phylo_trees_loglik_rates' site value); inv = 1 / m_s if m_s >= 2^-1020 and finite, else NaN.  Every line one IEEE operation:
+ *   loglik_T[t]               bit for bit phylo_trees_loglik_rates' value under that tree's mixture, prior and tile (required);
+ *   post_TxRxSx4[t][i][s][j]  (may be NULL) = acc_j * inv with acc_j = +0.0, then acc_j = acc_j + w_c * (abar_{v,c}[j] *
+ *                             (msg_l,c[j] * msg_r,c[j])) in ascending c; NOT renormalised;
+ *   state_TxRxS, pmax_TxRxS   (may be NULL) phylo_trees_ancestral's rule read from those post bits (PHYLO_ANC_NOSTATE, NaN);
+ *   catpost_TxCxS[t][c][s]    (may be NULL) = (w_c * f_c) * inv, the posterior probability that site s evolved in category c
+ *                             (f_c bit for bit phylo_trees_loglik_rates' cat_lik);
+ *   siterate_TxS[t][s]        (may be NULL) = e with e = +0.0, then e = e + r_c * catpost_c in ascending c: the posterior mean rate.
+ * Not all five of them may be NULL.  NaN rule, per SITE: a site whose m_s lies below 2^-1020 or is not finite gets NaN /
+ * PHYLO_ANC_NOSTATE in its own column of all five outputs; every other site of the tree is untouched and loglik_T stays the
+ * scoring call's bits.  A rate-0 category, a zero weight and a site with some f_c == 0 beside an in-range m_s are ordinary.  No
+ * output sums over sites: the call repeats its own bits, and chunking, the grid cap, a tree's place in the set, shared against
+ * per-tree passing of the same numbers and which outputs are asked for change none.  perf (may be NULL): units = T S (N-1) C.
+ * Synchronous; on a sharded context a LOCAL call.  PHYLO_EINVAL before anything is queued for a bad tree (naming tree and row), C
+ * outside 1 .. 16, a bad rate, weight or scaled length (naming tree, row and category), per_tree outside {0, 1}, T < 1, child,
+ * blen, rate, weight or loglik_T == NULL, all five outputs NULL, and a single tree whose requested outputs exceed 1 GiB (naming
+ * the size); PHYLO_ESTATE before phylo_set_leaves and phylo_set_model.  A chunk is the smallest of: the trees that fit
+ * phylo_trees_grad_rates' 64 MiB slab (without M' and M''), the trees whose requested outputs (R S (32 + 1 + 8) + S (8 C + 8) bytes
+ * each, over those asked for) fit phylo_trees_ancestral's 256 MiB staging region (which grows to one tree's need), and
+ * PHYLO_TREES_CHUNK.  Own scratch and events, released with the context; everything phylo_trees_ancestral leaves alone, and the
+ * scratch of every sibling, is left alone. */
+int phylo_trees_ancestral_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate,
+                                const double* weight, int per_tree, const double* prior4, double* loglik_T, double* post_TxRxSx4,
+                                uint8_t* state_TxRxS, double* pmax_TxRxS, double* catpost_TxCxS, double* siterate_TxS,
+                                phylo_stats* perf);
 /* The NNI neighbourhood of every tree of a set, at the tree's current branch lengths: for T trees given as
  * phylo_trees_loglik takes them (same numbering, same checks, same state rules),
  *   loglik_T[t]        bit for bit phylo_trees_loglik's value for the same tree, prior and site tile;

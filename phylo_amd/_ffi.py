@@ -27,7 +27,7 @@ ANC_NOSTATE = 255                                          # PHYLO_ANC_NOSTATE: 
 EXPORTS = [
     "phylo_version", "phylo_last_error", "phylo_device_count", "phylo_create", "phylo_destroy",
     "phylo_set_leaves", "phylo_set_model", "phylo_expm_batched", "phylo_cond_likelihood_K",
-    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_grad_model", "phylo_trees_ancestral", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_rell_multiscale", "phylo_debug_rell_multiscale_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
+    "phylo_forest_loglik", "phylo_tree_loglik", "phylo_trees_loglik", "phylo_trees_loglik_rates", "phylo_trees_grad", "phylo_trees_grad_rates", "phylo_trees_grad_model", "phylo_trees_ancestral", "phylo_trees_ancestral_rates", "phylo_trees_nni", "phylo_trees_nni_rates", "phylo_rell", "phylo_debug_rell_host", "phylo_rell_multiscale", "phylo_debug_rell_multiscale_host", "phylo_debug_tree_schedule", "phylo_resample", "phylo_log_zsmc", "phylo_sweep",
     "phylo_sweep_async", "phylo_sweep_batch_async", "phylo_sweep_batch_begin", "phylo_sweep_fetch_logz", "phylo_sweep_begin", "phylo_sweep_step", "phylo_sweep_step_a", "phylo_sweep_step_group", "phylo_sweep_finish", "phylo_sweep_fetch",
     "phylo_synchronize", "phylo_sweep_node", "phylo_sweep_backward", "phylo_sweep_backward_batch",
     "phylo_tree_summary", "phylo_tree_summary_fetch", "phylo_tree_branches", "phylo_tree_branches_fetch",
@@ -734,6 +734,50 @@ class Context:
                                                     _ptr(pmax), C.byref(st)))
         self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         return (out,) + tuple(x for x in (post, state, pmax) if x is not None)
+
+    def trees_ancestral_rates(self, child, blen, rates, weights, prior=None, want_post=True, want_state=True, want_pmax=False,
+                              want_catpost=False, want_siterate=False):
+        """trees_ancestral under a mixture of C rate categories, and the site-rate posteriors beside it
+        (phylo_trees_ancestral_rates).  rates and weights are [C] (one mixture for all trees) or [T][C] (tree t under row t).
+        Returns (loglik [T]) followed, in this order, by post [T][N-1][S][4] with want_post, state [T][N-1][S] (uint8;
+        ANC_NOSTATE where the site has none) with want_state, pmax [T][N-1][S] with want_pmax, catpost [T][C][S] (the posterior
+        probability that the site evolved in category c) with want_catpost and siterate [T][S] (the posterior mean rate of the
+        site, sum_c rates[c] catpost[c]) with want_siterate.  Rows as trees_ancestral.  post and catpost are not renormalised; a
+        site whose mixed value lies below 2^-1020 has NaN / ANC_NOSTATE in its own column of every output and leaves every other
+        site alone.  loglik is bit for bit trees_loglik_rates'.  self.last_trees_stats holds the call's stats.
+        phylo_amd.ancestral turns the arrays into sequences, summaries and a table of site rates."""
+        child, blen = _tree_rows(child, blen, self.N)
+        T = child.shape[0]
+        rates, weights = _f64(rates), _f64(weights)
+        if rates.shape != weights.shape:
+            raise ValueError("rates and weights must have one shape, got %r and %r" % (rates.shape, weights.shape))
+        if rates.ndim == 2:
+            if rates.shape[0] != T:
+                raise ValueError("per-tree rates must be [T][C] with T = %d, got %r" % (T, rates.shape))
+            per_tree = 1
+        elif rates.ndim == 1:
+            per_tree = 0
+        else:
+            raise ValueError("rates must be [C] or [T][C], got %r" % (rates.shape,))
+        nc = rates.shape[-1]
+        pr = None if prior is None else _f64(prior).reshape(-1)
+        if pr is not None and pr.shape != (4,):
+            raise ValueError("prior must hold 4 values")
+        if not (want_post or want_state or want_pmax or want_catpost or want_siterate):
+            raise ValueError("one of want_post, want_state, want_pmax, want_catpost and want_siterate must be set")
+        R = self.N - 1
+        out = np.empty(T)
+        post = np.empty((T, R, self.S, 4)) if want_post else None
+        state = np.empty((T, R, self.S), dtype=np.uint8) if want_state else None
+        pmax = np.empty((T, R, self.S)) if want_pmax else None
+        catpost = np.empty((T, nc, self.S)) if want_catpost else None
+        siterate = np.empty((T, self.S)) if want_siterate else None
+        st = Stats()
+        self._check(self._lib.phylo_trees_ancestral_rates(self._h, C.c_int(T), _ptr(child), _ptr(blen), C.c_int(nc), _ptr(rates),
+                                                          _ptr(weights), C.c_int(per_tree), _ptr(pr), _ptr(out), _ptr(post), _ptr(state),
+                                                          _ptr(pmax), _ptr(catpost), _ptr(siterate), C.byref(st)))
+        self.last_trees_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return (out,) + tuple(x for x in (post, state, pmax, catpost, siterate) if x is not None)
 
     def trees_grad_model(self, child, blen, dirs, prior=None, want_grad=False, want_prior=True):
         """Derivatives of trees_loglik with respect to the substitution model (phylo_trees_grad_model): dirs [P][4][4] are P

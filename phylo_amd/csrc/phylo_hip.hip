@@ -36,6 +36,7 @@
 #include "phylo_treenni_rates.h"
 #include "phylo_treegrad_model.h"
 #include "phylo_treeanc.h"
+#include "phylo_treeanc_rates.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -273,11 +274,11 @@ struct phylo_ctx {
     sweep_run run;
     int n_merge_events = 0;
     // grow-only scratch for the op-level entry points
-    DevBuf scratch[23];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
+    DevBuf scratch[24];                  // (8..10: the device-built lists of the reverse pass; 12, 13: the tree summary's and its branch pass's slabs;
                                          //  14: phylo_trees_loglik's chunk; 15: phylo_rell's logs and its chunk of replicates;
                                          //  16: phylo_trees_grad's chunk and node stores; 17: phylo_trees_grad_rates's; 18: phylo_trees_nni's;
                                          //  19: phylo_trees_nni_rates's; 20: phylo_trees_grad_model's; 21: phylo_rell_multiscale's logs and chunk;
-                                         //  22: phylo_trees_ancestral's chunk, staged outputs and node stores)
+                                         //  22: phylo_trees_ancestral's chunk, staged outputs and node stores; 23: phylo_trees_ancestral_rates's)
     phylo_comm comm;
     // the last phylo_tree_summary (phylo_trees.h): its tables live in scratch slot 12 until the next summary
     pt_bufs ts;
@@ -300,6 +301,7 @@ struct phylo_ctx {
     hipEvent_t ev_tm0 = nullptr, ev_tm1 = nullptr;   // phylo_trees_nni_rates' own pair
     hipEvent_t ev_tq0 = nullptr, ev_tq1 = nullptr;   // phylo_trees_grad_model's own pair
     hipEvent_t ev_ta0 = nullptr, ev_ta1 = nullptr;   // phylo_trees_ancestral's own pair
+    hipEvent_t ev_tz0 = nullptr, ev_tz1 = nullptr;   // phylo_trees_ancestral_rates' own pair
 };
 
 namespace {
@@ -883,6 +885,8 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_tq1) (void)hipEventDestroy(c->ev_tq1);
     if (c->ev_ta0) (void)hipEventDestroy(c->ev_ta0);
     if (c->ev_ta1) (void)hipEventDestroy(c->ev_ta1);
+    if (c->ev_tz0) (void)hipEventDestroy(c->ev_tz0);
+    if (c->ev_tz1) (void)hipEventDestroy(c->ev_tz1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -2078,6 +2082,142 @@ int phylo_trees_grad_rates(phylo_ctx* c, int T, const int32_t* child, const doub
         st.n_launches = launches;
         st.units = (double)T * S * R * C;
         st.alg_bytes = 96.0 * st.units;
+        *perf = st;
+    }
+    return PHYLO_OK;
+}
+
+// ---- marginal ancestral state posteriors and site-rate posteriors under a mixture (phylo_treeanc_rates.h) ----
+int phylo_trees_ancestral_rates(phylo_ctx* c, int T, const int32_t* child, const double* blen, int C, const double* rate, const double* weight,
+                                int per_tree, const double* prior4, double* loglik_T, double* post_TxRxSx4, uint8_t* state_TxRxS,
+                                double* pmax_TxRxS, double* catpost_TxCxS, double* siterate_TxS, phylo_stats* perf) {
+    CHK(bind(c));
+    if (!c->have_leaves || !c->have_model)
+        return fail(c, PHYLO_ESTATE, "phylo_trees_ancestral_rates needs phylo_set_leaves and phylo_set_model first");
+    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    if (C < 1 || C > PT2_MAX_CATS) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
+    if (per_tree != 0 && per_tree != 1) return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: per_tree must be 0 or 1 (per_tree=%d)", per_tree);
+    if (!child || !blen || !rate || !weight || !loglik_T)
+        return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: child, blen, rate, weight and loglik must be given (NULL pointer)");
+    if (!post_TxRxSx4 && !state_TxRxS && !pmax_TxRxS && !catpost_TxCxS && !siterate_TxS)
+        return fail(c, PHYLO_EINVAL,
+                    "phylo_trees_ancestral_rates: one of post, state, pmax, catpost and siterate must be given (all five are NULL pointers)");
+    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
+    const size_t mix_stride = per_tree ? (size_t)C : 0;    // tree t's mixture: row t, or the one row
+    for (int t = 0; t < T; ++t) {                          // every tree and its mixture are checked before anything is queued
+        int row = 0;
+        char msg[200];
+        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+        if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
+    }
+    const bool coded = c->leaves_coded;
+    const unsigned outs = (post_TxRxSx4 ? PTAR_POST : 0u) | (state_TxRxS ? PTAR_STATE : 0u) | (pmax_TxRxS ? PTAR_PMAX : 0u) |
+                          (catpost_TxCxS ? PTAR_CATPOST : 0u) | (siterate_TxS ? PTAR_SITERATE : 0u);
+    ptar_plan pl;
+    const int prc = ptar_make_plan(N, S, ntiles, T, C, coded, outs, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl);
+    if (prc == 2)
+        return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: the requested outputs of one tree take %zu bytes, more than %zu (N=%d, S=%d, C=%d)",
+                    pl.out_tree, (size_t)PTA_OUT_MAX, N, S, C);
+    if (prc) return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: no plan for N=%d, S=%d, %d tiles, T=%d, C=%d", N, S, ntiles, T, C);
+    const int chunk = pl.chunk;
+    void* slab = nullptr;
+    CHK(scratch_get(c, 23, pl.total, &slab));
+    char* base = (char*)slab;
+    double* d_prior = (double*)(base + pl.o_prior);
+    double* d_coef = (double*)(base + pl.o_coef);
+    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
+    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
+    double* d_P = (double*)(base + pl.o_P);
+    double* d_t = (double*)(base + pl.o_t);
+    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
+    double* d_tilev = (double*)(base + pl.o_tilev);
+    double* d_out = (double*)(base + pl.o_out);
+    double* d_post = post_TxRxSx4 ? (double*)(base + pl.o_post) : nullptr;
+    uint8_t* d_state = state_TxRxS ? (uint8_t*)(base + pl.o_state) : nullptr;
+    double* d_pmax = pmax_TxRxS ? (double*)(base + pl.o_pmax) : nullptr;
+    double* d_cat = catpost_TxCxS ? (double*)(base + pl.o_cat) : nullptr;
+    double* d_rate = siterate_TxS ? (double*)(base + pl.o_rate) : nullptr;
+    if (!c->ev_tz0) {
+        HIPCHK(c, hipEventCreate(&c->ev_tz0));
+        HIPCHK(c, hipEventCreate(&c->ev_tz1));
+    }
+    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
+    std::vector<double> ts((size_t)chunk * C * R * 2), coef((size_t)chunk * pl.ncoef);
+    const size_t cells_tree = (size_t)R * S;               // node-sites of one tree
+    double ms_total = 0.0;
+    int launches = 0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int n = std::min(chunk, T - t0);
+        int depth = 1;
+        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every category's lengths in its order
+            int32_t* o = ops.data() + (size_t)t * R * 4;
+            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
+            depth = std::max(depth, pt2_schedule(N, ch, o));
+            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
+                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
+            const double* b = blen + (size_t)(t0 + t) * R * 2;
+            const double* rt = rate + (t0 + t) * mix_stride;
+            for (int k = 0; k < C; ++k) {
+                double* tk = ts.data() + ((size_t)t * C + k) * R * 2;
+                for (int i = 0; i < R; ++i) {
+                    tk[2 * i] = rt[k] * b[2 * o[4 * i + 3]];
+                    tk[2 * i + 1] = rt[k] * b[2 * o[4 * i + 3] + 1];
+                }
+            }
+            ptar_coefficients(C, rt, weight + (t0 + t) * mix_stride, coef.data() + (size_t)t * pl.ncoef);
+        }
+        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * C * R * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_coef, coef.data(), (size_t)n * pl.ncoef * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_tz0, c->stream));
+        const long n_mat = (long)n * C * R * 2;
+        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
+        CHK(launch_check(c, "pk_expm_batched"));
+        ++launches;
+        if (coded) {
+            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
+            CHK(launch_check(c, "pt2_gap_rows"));
+            ++launches;
+        }
+        ptar_args g{};
+        pt2_args& a = g.a;
+        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
+        a.prior = prior4 ? d_prior : c->d_pi;
+        a.tilev = d_tilev; a.site_lik = nullptr;
+        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
+        g.dops = d_dops; g.coef = d_coef; g.store = (pk_d2*)(base + pl.o_store);
+        g.post = d_post; g.state = d_state; g.pmax = d_pmax; g.catpost = d_cat; g.siterate = d_rate;
+        g.n_items = n * ntiles; g.depth = depth; g.C = C;
+        ptar_launch(g, std::min(pl.grid, g.n_items), coded, c->stream);
+        CHK(launch_check(c, "ptar_updown"));
+        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
+        CHK(launch_check(c, "pt2_finish"));
+        launches += 2;
+        HIPCHK(c, hipEventRecord(c->ev_tz1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_post)                                        // every cell of the chunk was written: straight into the caller's rows
+            HIPCHK(c, hipMemcpyAsync(post_TxRxSx4 + (size_t)t0 * cells_tree * 4, d_post, (size_t)n * cells_tree * 32, hipMemcpyDeviceToHost, c->stream));
+        if (d_state) HIPCHK(c, hipMemcpyAsync(state_TxRxS + (size_t)t0 * cells_tree, d_state, (size_t)n * cells_tree, hipMemcpyDeviceToHost, c->stream));
+        if (d_pmax) HIPCHK(c, hipMemcpyAsync(pmax_TxRxS + (size_t)t0 * cells_tree, d_pmax, (size_t)n * cells_tree * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_cat) HIPCHK(c, hipMemcpyAsync(catpost_TxCxS + (size_t)t0 * C * S, d_cat, (size_t)n * C * S * 8, hipMemcpyDeviceToHost, c->stream));
+        if (d_rate) HIPCHK(c, hipMemcpyAsync(siterate_TxS + (size_t)t0 * S, d_rate, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tz0, c->ev_tz1));
+        ms_total += ms;
+    }
+    if (perf) {
+        phylo_stats st{};
+        st.sweep_ms = ms_total;
+        st.n_launches = launches;
+        st.units = (double)T * S * R * C;
+        st.alg_bytes = (double)T * S * (R * ((post_TxRxSx4 ? 32.0 : 0.0) + (state_TxRxS ? 1.0 : 0.0) + (pmax_TxRxS ? 8.0 : 0.0)) +
+                                        (catpost_TxCxS ? 8.0 * C : 0.0) + (siterate_TxS ? 8.0 : 0.0));
         *perf = st;
     }
     return PHYLO_OK;

@@ -305,7 +305,7 @@ class VCSMC:
         return [row[0] for row in tab]
 
     def score_trees(self, newicks, rates=None, want_sites=False, optimize=False, fit=(), search=None, search_rounds=20, fit_model=(),
-                    fit_on=None, fit_rounds=20, ancestral=0):
+                    fit_on=None, fit_rounds=20, ancestral=0, ancestral_rates=0):
         """Log-likelihoods of rooted Newick trees over the taxon names under the current model, the model's stationary
         distribution at the root (phylo_trees_loglik on the resident alignment: one call for all of them).  rates: a
         (rates, weights) pair, e.g. phylo_amd.rates.rate_model's -- the trees are then scored under that mixture of site
@@ -338,11 +338,36 @@ class VCSMC:
         model given, 'newicks' at the lengths climbed under the fitted model).
         ancestral=k (one rate only): after everything else asked for, and before a fitted model is put back, the k best trees by
         the final score are reconstructed at the final lengths and model (phylo_trees_ancestral): self.last_ancestral holds
-        'trees' (their indices, best first), 'newicks', 'child', 'loglik', 'state' and 'pmax' [k][N-1][S]."""
+        'trees' (their indices, best first), 'newicks', 'child', 'loglik', 'state' and 'pmax' [k][N-1][S].
+        ancestral_rates=k (with rates): the same under the mixture (phylo_trees_ancestral_rates) -- after everything else asked
+        for (fit, search, refit) the k best trees by the final score are reconstructed under each tree's own final mixture (the
+        fitted alpha and p_inv where fit gave them, passed per tree); self.last_ancestral holds ancestral=k's dictionary and
+        'catpost' [k][C][S] (every category's posterior per site), 'siterate' [k][S] (the posterior mean rate of the site),
+        'rates' and 'weights' [k][C] (the mixtures used) and 'alpha', 'pinv' (per tree where fitted, else None)."""
         ancestral = int(ancestral or 0)
         if ancestral < 0 or (ancestral and rates is not None):
-            raise ValueError("score_trees: ancestral=%r needs k >= 1 and no rates (the posteriors are not built for mixtures)" % (ancestral,))
+            raise ValueError("score_trees: ancestral=%r needs k >= 1 and no rates (the posteriors are not built for mixtures; "
+                             "ancestral_rates=k reconstructs under them)" % (ancestral,))
+        ancestral_rates = int(ancestral_rates or 0)
+        if ancestral_rates < 0 or (ancestral_rates and (rates is None or ancestral)):
+            raise ValueError("score_trees: ancestral_rates=%r needs k >= 1, rates, and no ancestral=" % (ancestral_rates,))
         self.last_ancestral = None
+
+        def reconstruct_rates(ctx, child, blen, loglik, r, w, alpha=None, pinv=None):
+            if not ancestral_rates:
+                return
+            order = np.argsort(-np.asarray(loglik, dtype=np.float64), kind='stable')[:ancestral_rates]
+            r, w = np.asarray(r, dtype=np.float64), np.asarray(w, dtype=np.float64)
+            if r.ndim == 1:                                 # one mixture for all trees
+                r, w = np.broadcast_to(r, (child.shape[0], r.size)), np.broadcast_to(w, (child.shape[0], w.size))
+            r, w = np.ascontiguousarray(r[order]), np.ascontiguousarray(w[order])
+            ll, state, pmax, catpost, siterate = ctx.trees_ancestral_rates(child[order], blen[order], r, w, want_post=False, want_state=True,
+                                                                           want_pmax=True, want_catpost=True, want_siterate=True)
+            self.last_ancestral = {'trees': [int(t) for t in order], 'child': child[order].copy(), 'loglik': [float(x) for x in ll],
+                                   'newicks': [treepost.rows_to_newick(c, b, self.taxa) for c, b in zip(child[order], blen[order])],
+                                   'state': state, 'pmax': pmax, 'catpost': catpost, 'siterate': siterate, 'rates': r, 'weights': w,
+                                   'alpha': None if alpha is None else [float(alpha[t]) for t in order],
+                                   'pinv': None if pinv is None else [float(pinv[t]) for t in order]}
 
         def reconstruct(ctx, child, blen, loglik):
             if not ancestral:
@@ -412,8 +437,10 @@ class VCSMC:
                 per = [ctx.trees_loglik_rates(child[t], blen[t], opt['rates'][t], opt['weights'][t], want_sites=True)
                        for t in range(child.shape[0])]
                 res = (np.array([p[0][0] for p in per]), np.array([p[1][0] for p in per]))
+                reconstruct_rates(ctx, child, blen, res[0], opt['rates'], opt['weights'], opt['alpha'], opt['pinv'])
             else:
                 res = ctx.trees_loglik_rates(child, blen, rates[0], rates[1], want_sites=True)
+                reconstruct_rates(ctx, child, blen, res[0], rates[0], rates[1])
             res = res if want_sites else res[0]
         elif optimize and fit_model:
             from . import treeopt
@@ -474,6 +501,7 @@ class VCSMC:
             reconstruct(ctx, child, blen, res[0] if want_sites else res)
         else:
             res = ctx.trees_loglik_rates(child, blen, rates[0], rates[1], want_sites=want_sites)
+            reconstruct_rates(ctx, child, blen, res[0] if want_sites else res, rates[0], rates[1])
         if want_sites:
             return [float(x) for x in res[0]], res[1]
         return [float(x) for x in res]
@@ -520,13 +548,14 @@ class VCSMC:
         self.model_ml = None
         self.ancestral_results = None
         anc = int(getattr(self.args, 'score_ancestral', None) or 0) if newicks else 0   # --score_ancestral K: the K best trees reconstructed
+        ancr = int(getattr(self.args, 'score_ancestral_rates', None) or 0) if newicks else 0   # --score_ancestral_rates K: under the rate model
         mfit = getattr(self.args, 'score_model_fit', None) if ml else None  # --score_model_fit q | q+pi: one ML model for all trees
         mfit = tuple(mfit.split('+')) if mfit else None
         srch = getattr(self.args, 'score_search', None) if ml else None     # --score_search nni[:ROUNDS]: then an NNI search from there
         fsrch = getattr(self.args, 'score_fit_search', None) if fit is not None else None   # --score_fit_search: the same under the rate model
         if fsrch:
             ll_search, sites = self.score_trees(newicks, rates=rm, want_sites=True, optimize=True, fit=fit, search=fsrch[0],
-                                                search_rounds=fsrch[1])
+                                                search_rounds=fsrch[1], ancestral_rates=ancr)
             opt, found = self.last_tree_opt, self.last_tree_search
             ll, ll_ml = opt['loglik_given'], found['loglik_ml']
             self.trees_ml, self.trees_search = opt['newicks'], found['newicks']
@@ -548,16 +577,16 @@ class VCSMC:
             ll = opt['loglik_given']
             self.trees_ml = opt['newicks']
         elif fit is not None:
-            ll_ml, sites = self.score_trees(newicks, rates=rm, want_sites=True, optimize=True, fit=fit)
+            ll_ml, sites = self.score_trees(newicks, rates=rm, want_sites=True, optimize=True, fit=fit, ancestral_rates=ancr)
             opt = self.last_tree_opt
             ll = opt['loglik_given']
             self.trees_ml = opt['newicks']
             ml = True
         elif tests and newicks:                            # --tree_tests: from the site factors of this very scoring call
-            ll, sites = self.score_trees(newicks, rates=mix, want_sites=True, ancestral=anc)
+            ll, sites = self.score_trees(newicks, rates=mix, want_sites=True, ancestral=anc, ancestral_rates=ancr)
         else:
-            ll = self.score_trees(newicks, rates=mix, ancestral=anc)
-        if anc:                                            # (absent without --score_ancestral)
+            ll = self.score_trees(newicks, rates=mix, ancestral=anc, ancestral_rates=ancr)
+        if anc or ancr:                                    # (absent without --score_ancestral / --score_ancestral_rates)
             self.ancestral_results = self.last_ancestral
         if tests and newicks:                              # (with --score_opt: the site factors at the ML lengths)
             from . import treetests
@@ -603,7 +632,9 @@ class VCSMC:
     def _save_ancestral(self, save_dir, res):
         """ancestral.fa and ancestral.json of --score_ancestral: per reconstructed tree one FASTA record per internal node
         ('>tree{t}_node{N+i} clade=a,b,c', the most probable states as letters), and its index, Newick string and per node the
-        numbers of phylo_amd.ancestral.summarise"""
+        numbers of phylo_amd.ancestral.summarise.  Under --score_ancestral_rates every tree of ancestral.json also carries the
+        mixture used ('rates', 'weights', and 'alpha' / 'pinv' where fitted) and 'site_rates' (phylo_amd.ancestral.summarise_rates'
+        numbers), and site_rates.tsv holds every site's posterior mean rate and category posteriors (write_site_rates)"""
         import json
         import os
         from . import ancestral as anc
@@ -617,6 +648,18 @@ class VCSMC:
                           'nodes': [{'node': self.N + i, 'clade': cl, 'mean_pmax': m, 'share_below_0.9': sh, 'n_nan': int(k)}
                                     for i, (cl, m, sh, k) in enumerate(zip(anc.node_clades(child, taxa), nn(sm['mean_pmax']),
                                                                            nn(sm['share_below']), sm['n_nan']))]})
+        if res.get('catpost') is not None:                 # (absent without --score_ancestral_rates)
+            sr = anc.summarise_rates(res['siterate'], res['catpost'])
+            for k, tree in enumerate(trees):
+                tree['rates'], tree['weights'] = [float(x) for x in res['rates'][k]], [float(x) for x in res['weights'][k]]
+                if res['alpha'] is not None:
+                    tree['alpha'] = res['alpha'][k]
+                if res['pinv'] is not None:
+                    tree['pinv'] = res['pinv'][k]
+                tree['site_rates'] = {'mean_rate': nn([sr['mean_rate'][k]])[0], 'quantile_levels': list(sr['q']),
+                                      'quantiles': nn(sr['quantiles'][k]), 'category_share': nn(sr['cat_share'][k]),
+                                      'n_nan': int(sr['n_nan'][k])}
+            anc.write_site_rates(os.path.join(save_dir, 'site_rates.tsv'), res['trees'], res['siterate'], res['catpost'])
         anc.write_fasta(os.path.join(save_dir, 'ancestral.fa'), records)
         with open(os.path.join(save_dir, 'ancestral.json'), 'w') as f:
             json.dump({'trees': trees}, f, indent=1)
@@ -629,7 +672,7 @@ class VCSMC:
         with open(os.path.join(save_dir, "run_parameters.txt"), "w") as rp:
             rp.write('Initial evaluation of ELBO : ' + str(initial) + '\n')
             for key, v in vars(self.args).items():
-                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'tree_tests_au', 'score_opt', 'score_fit', 'score_search', 'score_fit_search', 'score_model_fit', 'score_ancestral') and not v:   # (off: the file is what it was before the flag existed)
+                if key in ('tree_branches', 'score_trees', 'score_rates', 'tree_tests', 'tree_tests_au', 'score_opt', 'score_fit', 'score_search', 'score_fit_search', 'score_model_fit', 'score_ancestral', 'score_ancestral_rates') and not v:   # (off: the file is what it was before the flag existed)
                     continue
                 rp.write(str(key) + ' : ' + str(v) + '\n')
             rp.write(str(getattr(self, 'optimizer', '')))

@@ -4,7 +4,7 @@
 Same flags and defaults.  Differences: datasets come from an explicit table
 (phylo_amd/datasets.py) instead of `exec(args.dataset + ' = True')`; `--twisting` is accepted as an alias of
 `--nested` (the reference's README advertises it, its parser lacks it); `--seed`, `--n_gpus`, `--train_parallel`,
-`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--score_model_fit`, `--score_ancestral`, `--tree_tests`, `--tree_tests_au` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
+`--grad_samples`, `--grad_batched`, `--tree_summary`, `--tree_branches`, `--score_trees`, `--score_rates`, `--score_opt`, `--score_fit`, `--score_search`, `--score_fit_search`, `--score_model_fit`, `--score_ancestral`, `--score_ancestral_rates`, `--tree_tests`, `--tree_tests_au` and `--ambiguity` (default: the reference's KeyError on characters such as DS7's 'N'; `iupac`
 encodes them) are new.
 """
 import argparse
@@ -112,6 +112,15 @@ def parse_args(argv=None):
                              "has none) and ancestral.json (per tree its index, its Newick string and per node the mean posterior "
                              "of the most probable state and the share of sites below 0.9).  Not with --score_rates, --score_fit "
                              "or --score_fit_search")
+    parser.add_argument('--score_ancestral_rates', default=None, type=int, metavar='K',
+                        help="with --score_trees and --score_rates: --score_ancestral UNDER the rate model "
+                             "(phylo_trees_ancestral_rates on the device) -- the K best trees by their final score (after --score_fit "
+                             "and --score_fit_search where given), every tree under its own final mixture (the fitted alpha and "
+                             "p_inv where --score_fit gave them); writes ancestral.fa and ancestral.json as --score_ancestral does "
+                             "(ancestral.json also carries per tree the mixture used -- rates, weights, and alpha / pinv where "
+                             "fitted -- and the mean and quantiles of the posterior mean site rate and the share of sites per most "
+                             "probable category) and site_rates.tsv (tree, site, rate, cat, p0 .. p{C-1}: the empirical-Bayes rate "
+                             "of every site, its most probable category and every category's posterior).  Not with --score_ancestral")
     parser.add_argument('--tree_tests', default=None, metavar='B[:SEED]',
                         help="with --score_trees: which of those trees are significantly worse than the best one?  A RELL bootstrap "
                              "of B replicates (seed SEED, default 0) over the site likelihoods of that scoring call (under "
@@ -193,9 +202,19 @@ def parse_args(argv=None):
             parser.error('--score_ancestral: K >= 1 trees to reconstruct, not %d' % args.score_ancestral)
         if not args.score_trees:
             parser.error('--score_ancestral needs --score_trees FILE (it reconstructs the best of the trees scored there)')
+        if args.score_ancestral_rates is not None:
+            parser.error('--score_ancestral_rates and --score_ancestral exclude one another (one rate, or the rate model)')
         if args.score_rates is not None or args.score_fit is not None or args.score_fit_search is not None:
             parser.error('--score_ancestral: the ancestral posteriors are not built for rate mixtures (not with --score_rates, '
-                         '--score_fit or --score_fit_search)')
+                         '--score_fit or --score_fit_search); use --score_ancestral_rates K')
+    if args.score_ancestral_rates is not None:
+        if args.score_ancestral_rates < 1:
+            parser.error('--score_ancestral_rates: K >= 1 trees to reconstruct, not %d' % args.score_ancestral_rates)
+        if not args.score_trees:
+            parser.error('--score_ancestral_rates needs --score_trees FILE (it reconstructs the best of the trees scored there)')
+        if args.score_rates is None:
+            parser.error('--score_ancestral_rates needs --score_rates gamma:ALPHA:C[:PINV] (it reconstructs under that rate model; '
+                         'under one rate --score_ancestral does this)')
     if args.tree_branches and not args.tree_summary:
         parser.error('--tree_branches true needs --tree_summary true (it adds branch lengths to that summary)')
     if args.twisting is not None:

@@ -57,6 +57,9 @@ def cycle(i):
                            want_grad=True)                  # ... and the model gradient's: a slab that grows with the directions
         c.trees_ancestral(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1), want_pmax=i % 2 == 1)
                                                             # ... and the ancestral posteriors': staged outputs that grow with what is asked for
+        c.trees_ancestral_rates(np.tile(child, (n, 1, 1)), np.full((n, N - 1, 2), 0.1), np.linspace(0.0, 2.0, 2 + i % 4), np.full(2 + i % 4, 0.25),
+                                want_catpost=i % 2 == 1, want_siterate=i % 4 < 2)
+                                                            # ... and the same under a mixture: node stores and staging that grow with the categories
     v = T.Variables(N2, np.log(10.0), False)            # a context of 66 taxa that trains: two steps, so two passes on one context
     tr = T.Trainer(g2, 32 + 4 * (i % 8), v, T.make_optimizer('Adam', 0.01), S2)
     try:

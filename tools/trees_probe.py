@@ -51,7 +51,14 @@ whether loglik and grad carry the siblings' bits.
 --ancestral times phylo_trees_ancestral with states only and with post (the latter on the first
 --post_trees trees: its output is 32 bytes per node-site, on the device and on the host) against phylo_trees_grad without
 curvature on the same trees, interleaved in the same run: device and wall times, their ratios, the bytes each form writes, the
-number of chunks, and whether loglik carries phylo_trees_grad's bits."""
+number of chunks, and whether loglik carries phylo_trees_grad's bits.
+
+    python tools/trees_probe.py --dataset hohna_data --trees 4096 --ancestral --rates 4 --reps 7 --out profiles/trees_probe.jsonl
+
+--ancestral --rates C times phylo_trees_ancestral_rates under C discrete Gamma categories -- states only,
+the site rates only (catpost and siterate), and with post on the first --post_trees trees -- against phylo_trees_grad_rates
+without curvature and against C calls of phylo_trees_ancestral (states only) on the scaled trees, interleaved in the same run:
+device and wall times, their ratios, the number of chunks, and whether loglik and catpost carry phylo_trees_loglik_rates' bits."""
 import argparse
 import json
 import os
@@ -530,6 +537,80 @@ def ancestral_probe(a):
     return 0 if same else 1
 
 
+def ancestral_rates_probe(a):
+    """phylo_trees_ancestral_rates under C discrete Gamma categories -- states only, the site rates only (catpost and siterate),
+    and with post (on the first post_trees trees) -- against phylo_trees_grad_rates without curvature and against C calls of
+    phylo_trees_ancestral (states only) on the scaled trees: same trees, same context, same run"""
+    from phylo_amd import rates as rates_mod
+    jc = a.jc.lower() == 'true'
+    g = load_dataset(a.dataset)['genome']
+    N, S, _ = g.shape
+    rng = np.random.default_rng(a.seed)
+    rows = [random_rows(N, rng) for _ in range(a.trees)]
+    child, blen = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    n_post = min(a.post_trees, a.trees) if a.post_trees > 0 else a.trees
+    Q = model.jc_Q() if jc else model.get_Q(model.init_y_q())
+    r, w = rates_mod.rate_model(a.alpha, a.rates)
+    nc = r.size
+    u64 = lambda x: np.ascontiguousarray(x).view(np.uint64)
+    with _ffi.Context(4, N, S) as ctx:
+        ctx.set_leaves(g)
+        ctx.set_model(Q, np.full(4, 0.25), np.full(N - 1, 10.0), np.full(N - 1, 10.0), jc69_closed_form=jc)
+        calls = (('grad', lambda: ctx.trees_grad_rates(child, blen, r, w)),
+                 ('plain', lambda: [ctx.trees_ancestral(child, rc * blen, want_post=False, want_state=True) for rc in r]),
+                 ('state', lambda: ctx.trees_ancestral_rates(child, blen, r, w, want_post=False, want_state=True)),
+                 ('rates', lambda: ctx.trees_ancestral_rates(child, blen, r, w, want_post=False, want_state=False, want_catpost=True,
+                                                             want_siterate=True)),
+                 ('post', lambda: ctx.trees_ancestral_rates(child[:n_post], blen[:n_post], r, w, want_post=True, want_state=False)))
+        warm = {k: call() for k, call in calls}             # warm-up of all of them
+        ls, sites, cats = ctx.trees_loglik_rates(child, blen, r, w, want_sites=True, want_cats=True)
+        same = bool(np.array_equal(u64(warm['state'][0]), u64(ls)) and np.array_equal(u64(warm['grad'][0]), u64(ls)) and
+                    np.array_equal(u64(warm['rates'][1]), u64((w[None, :, None] * cats) * (1.0 / sites)[:, None, :])))
+        nostate = int((warm['state'][1] == _ffi.ANC_NOSTATE).sum())
+        mean_rate = float(np.nanmean(warm['rates'][2]))
+        del warm
+        t = {k: ([], []) for k, _ in calls}
+        stats = {}
+        for _ in range(a.reps):                              # interleaved: all of them see the same machine
+            for k, call in calls:
+                dev = 0.0
+                t0 = time.perf_counter()
+                if k == 'plain':
+                    for rc in r:
+                        ctx.trees_ancestral(child, rc * blen, want_post=False, want_state=True)
+                        dev += ctx.last_trees_stats['sweep_ms']
+                else:
+                    call()
+                    dev = ctx.last_trees_stats['sweep_ms']
+                t[k][0].append((time.perf_counter() - t0) * 1e3)
+                t[k][1].append(dev)
+                stats[k] = dict(ctx.last_trees_stats)
+    q = {k: (quartiles(v[0]), quartiles(v[1])) for k, v in t.items()}
+    per = 4 if ((g == 0) | (g == 1)).all() and (g.sum(axis=2) >= 1).all() else 3
+    rec = {'probe': 'trees_ancestral_rates', 'dataset': a.dataset, 'N': int(N), 'S': int(S), 'trees': a.trees, 'post_trees': int(n_post),
+           'C': int(nc), 'alpha': a.alpha, 'jc': jc, 'reps': a.reps}
+    for k in t:
+        rec[k + '_wall_ms'], rec[k + '_device_ms'] = q[k]
+    rec.update({'device_ratio_state_over_grad_rates': q['state'][1]['median'] / q['grad'][1]['median'],
+                'device_ratio_state_over_C_plain_calls': q['state'][1]['median'] / q['plain'][1]['median'],
+                'wall_ratio_state_over_C_plain_calls': q['state'][0]['median'] / q['plain'][0]['median'],
+                'state_launches': stats['state']['n_launches'], 'state_chunks': stats['state']['n_launches'] // per,
+                'post_launches': stats['post']['n_launches'], 'post_chunks': stats['post']['n_launches'] // per,
+                'post_bytes_written': float(n_post) * (N - 1) * S * 32,
+                'post_device_GB_per_s': float(n_post) * (N - 1) * S * 32 / (q['post'][1]['median'] * 1e-3) / 1e9,
+                'units': stats['state']['units'], 'units_per_s_device_state': stats['state']['units'] / (q['state'][1]['median'] * 1e-3),
+                'units_per_s_device_grad_rates': stats['grad']['units'] / (q['grad'][1]['median'] * 1e-3),
+                'sites_without_state': nostate, 'mean_site_rate': mean_rate, 'bit_contracts_hold': same})
+    line = json.dumps(rec)
+    print(line)
+    print("loglik bit for bit phylo_trees_loglik_rates', catpost its cat_lik and site_lik: %s" % same)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(line + '\n')
+    return 0 if same else 1
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dataset', default='hohna_data')
@@ -550,6 +631,8 @@ def main(argv=None):
     ap.add_argument('--post_trees', type=int, default=512, help='with --ancestral: trees of the call that asks for post (0: all)')
     ap.add_argument('--dirs', type=int, default=12, help='with --model: directions of a call (1 .. 16)')
     a = ap.parse_args(argv)
+    if a.ancestral and a.rates > 0:
+        return ancestral_rates_probe(a)
     if a.ancestral:
         return ancestral_probe(a)
     if a.model:
