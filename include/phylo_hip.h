@@ -117,7 +117,15 @@ int phylo_set_leaves(phylo_ctx* ctx, const double* genome_NxSxA);
 int phylo_set_model(phylo_ctx* ctx, const double* Q16, const double* pi4, const double* lam_l,
                     const double* lam_r, int jc69_closed_form);
 
-/* tf.linalg.expm(tensordot(t, Q, 0)) (vcsmc.py:181-184): P[i] = expm(Q * t[i]), [n,4,4]. */
+/* tf.linalg.expm(tensordot(t, Q, 0)) (vcsmc.py:181-184): P[i] = expm(Q * t[i]), [n,4,4].
+ * The domain of the matrix function: ||Q||_1 * |t| <= theta_13 * 2^23 = 4.50629e7, Q the model in force.
+ * Inside it every entry is within 2^s (8 * 116 + 4) * 2^-53 of the true value, relatively (s squarings; <= 2^-20 at s = 23), no
+ * entry is negative and t = +-0 gives the identity; beyond it the squarings lose every digit (a zero matrix from about 1e100
+ * on).  A length outside it -- NaN and +-inf included -- is PHYLO_EINVAL naming t[i], the length and the limit, before anything is
+ * queued.  The same limit holds for every length (every rate * length) of phylo_tree_loglik and of all phylo_trees_* calls, whose
+ * message names tree and row (and category).  Under jc69_closed_form there is no limit: the closed form is right at every length
+ * (1/4 everywhere at 1e100), exact in absolute terms (off-diagonal within 0.5 * 2^-53, diagonal within 2 * 2^-53), not in
+ * relative ones (off-diagonal within 4 * 2^-53 / min(t, 1) of itself; exactly 0 for t < 2^-54). */
 int phylo_expm_batched(phylo_ctx* ctx, const double* t, int n, double* P_nx4x4);
 
 /* VCSMC.broadcast_conditional_likelihood_K (vcsmc.py:180-188) == csmc.conditional_likelihood per
@@ -133,7 +141,9 @@ int phylo_forest_loglik(phylo_ctx* ctx, const double* core_KxXxSx4, const int32_
 /* CSMC.compute_log_conditional_likelihood (csmc.py:318-326) on an explicit binary tree.  Nodes
  * 0..n_leaves-1 are leaves (rows of leaves_LxSx4); node i >= n_leaves has children left[i], right[i]
  * (already-numbered nodes < i or leaves) with branch lengths bl[i], br[i].  prior4 is csmc's
- * `self.prior`.  out_loglik = sum_s log(prior . data_root[s]); root_data_Sx4 may be NULL. */
+ * `self.prior`.  out_loglik = sum_s log(prior . data_root[s]); root_data_Sx4 may be NULL.  A branch length of a node reachable
+ * from root that lies outside the domain of the matrix function (phylo_expm_batched; NaN and inf included) is PHYLO_EINVAL,
+ * "tree 0, row <node>: ...", before anything is queued; no limit under jc69_closed_form. */
 int phylo_tree_loglik(phylo_ctx* ctx, int n_nodes, int n_leaves, int S, const int32_t* left,
                       const int32_t* right, const double* bl, const double* br, int root,
                       const double* leaves_LxSx4, const double* prior4, double* out_loglik,
@@ -144,8 +154,9 @@ int phylo_tree_loglik(phylo_ctx* ctx, int n_nodes, int n_leaves, int S, const in
  * phylo_tree_loglik computes for one tree, in volume.  Numbering: leaves are nodes 0 .. N-1; row i of a
  * tree is internal node N + i with children child[t][i][0], child[t][i][1] (a leaf or a node of an earlier row) and branch
  * lengths blen[t][i][0], blen[t][i][1]; row N-2 is the root.  Every tree is checked on the host before anything is queued: each
- * leaf and each internal node but the root is a child exactly once, branch lengths are finite and >= 0 (PHYLO_EINVAL naming
- * tree and row); PHYLO_ESTATE before leaves and model are set; T >= 1.
+ * leaf and each internal node but the root is a child exactly once, branch lengths are finite and >= 0 and, unless the model is
+ * the JC69 closed form, inside the domain of the matrix function (phylo_expm_batched: ||Q||_1 * length <= 4.50629e7) (PHYLO_EINVAL
+ * naming tree and row); PHYLO_ESTATE before leaves and model are set; T >= 1.
  *   loglik_T[t] = sum_s log(prior . x_root[s]) by the arithmetic contract with the context's site tile: bit for bit what
  *     phylo_tree_loglik returns for the same tree, leaves, prior and site tile.  prior4 == NULL: the context's pi;
  *   site_lik_TxS[t][s] (may be NULL): the factor prior . x_root[s] that entered the product;
@@ -166,8 +177,9 @@ int phylo_trees_loglik(phylo_ctx* ctx, int T, const int32_t* child, const double
  *   perf (may be NULL): as phylo_trees_loglik, units = T S (N-1) C.
  * State rules, per-tree checks, chunking (the same 64 MiB slab, PHYLO_TREES_CHUNK) and what is left alone are
  * phylo_trees_loglik's; a tree's schedule is built once, not once per category.  PHYLO_EINVAL before anything is queued also for
- * C outside 1 .. 16, a rate or weight that is not finite and >= 0, and a scaled length rate_C[c] * blen that is not finite (the
- * message names tree, row and category). */
+ * C outside 1 .. 16, a rate or weight that is not finite and >= 0, and a scaled length rate_C[c] * blen that is not finite or lies
+ * outside the domain of the matrix function (phylo_expm_batched; the message names tree, row and category).  The other
+ * phylo_trees_*_rates calls hold every rate * length to the same limit. */
 int phylo_trees_loglik_rates(phylo_ctx* ctx, int T, const int32_t* child, const double* blen, int C, const double* rate_C,
                              const double* weight_C, const double* prior4, double* loglik_T, double* site_lik_TxS,
                              double* cat_lik_TxCxS, phylo_stats* perf);

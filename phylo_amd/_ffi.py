@@ -611,6 +611,11 @@ class Context:
 
     # ---- ops
     def expm_batched(self, t):
+        """P[i] = expm(Q t[i]) of the model in force, [n][4][4] (phylo_expm_batched; DESIGN.md section 16 is its contract).  A
+        length with ||Q||_1 |t| above theta_13 2^23 = 4.50629e7 -- where the squarings have lost the matrix's digits; NaN and inf
+        included -- raises PhyloError (PHYLO_EINVAL) naming t[i]; so does every such length, or rate * length, of tree_loglik and
+        of all trees_* calls, naming tree and row.  Under jc69_closed_form there is no limit (1/4 everywhere at 1e100); the closed
+        form is exact in absolute terms only: its off-diagonal entry is exactly 0 below t = 2^-54."""
         t = _f64(np.atleast_1d(t))
         P = np.empty((t.size, 4, 4))
         self._check(self._lib.phylo_expm_batched(self._h, _ptr(t), C.c_int(t.size), _ptr(P)))
@@ -651,7 +656,9 @@ class Context:
     def trees_loglik(self, child, blen, prior=None, want_sites=False):
         """Log-likelihoods of T explicit trees over the context's resident leaves (phylo_trees_loglik): child, blen [T][N-1][2],
         leaves 0 .. N-1, row i = internal node N + i, the last row the root; prior None = the model's pi.  Returns loglik [T],
-        or (loglik, site_lik [T][S]) with want_sites; self.last_trees_stats holds the call's stats."""
+        or (loglik, site_lik [T][S]) with want_sites; self.last_trees_stats holds the call's stats.  A tree that is no tree, or a
+        length that is not finite and >= 0 or lies outside the matrix function's domain (expm_batched), raises PhyloError naming
+        tree and row before anything is queued; every trees_* call does."""
         child, blen = _tree_rows(child, blen, self.N)
         T = child.shape[0]
         pr = None if prior is None else _f64(prior).reshape(-1)
@@ -670,7 +677,9 @@ class Context:
         Gamma and +I ones): category c scores the tree at rates[c] * blen, a site's value is sum_c weights[c] f_c by the fma chain
         in ascending c.  The weights are used as given (finite, >= 0, not normalised).  Returns loglik [T], followed by site_lik
         [T][S] (the mixed value) with want_sites and by cat_lik [T][C][S] (every category's factor) with want_cats;
-        self.last_trees_stats holds the call's stats."""
+        self.last_trees_stats holds the call's stats.  The matrix of category c is the matrix of the single rounded product
+        rates[c] * blen; that product is held to the matrix function's domain (expm_batched), as in every trees_*_rates call:
+        PhyloError naming tree, row and category."""
         child, blen = _tree_rows(child, blen, self.N)
         T = child.shape[0]
         rates, weights = _f64(rates).reshape(-1), _f64(weights).reshape(-1)

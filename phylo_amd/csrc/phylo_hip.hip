@@ -137,6 +137,7 @@ struct phylo_ctx {
     std::string err;
     bool have_leaves = false, have_model = false, swept = false, state_ready = false;
     int jc = 0;
+    double q_norm1 = 0.0;                // ||Q||_1 of the model in force (pt2_check_expm_range)
     std::vector<double> h_lam_l, h_lam_r, h_ldf;
     // model + leaves
     double *d_Q = nullptr, *d_pi = nullptr, *d_lam_l = nullptr, *d_lam_r = nullptr, *d_ldf = nullptr;
@@ -1021,6 +1022,7 @@ int phylo_set_model(phylo_ctx* c, const double* Q16, const double* pi4, const do
     c->h_lam_l.assign(lam_l, lam_l + R);
     c->h_lam_r.assign(lam_r, lam_r + R);
     c->jc = jc69_closed_form ? 1 : 0;
+    c->q_norm1 = pt2_q_norm1(Q16);
     // one upload for the 42 numbers, from a pinned image that outlives the call: everything that uses the model is ordered
     // behind it on the context's stream, so the call does not wait (a training step sets a new model every time).  Only a
     // previous upload still in flight has to be over before the image is overwritten.
@@ -1045,11 +1047,39 @@ int phylo_set_model(phylo_ctx* c, const double* Q16, const double* pi4, const do
     return PHYLO_OK;
 }
 
+// The 1-norm pt2_check_expm_range holds a call's lengths against: that of the model in force, or 0 (no limit) under the JC69 closed
+// form, which is right at every length
+static double expm_range_norm(const phylo_ctx* c) { return c->jc ? 0.0 : c->q_norm1; }
+
+// The 2 (N-1) lengths of each of the T trees at every rate of its mixture (tree t's: rate + t * mix_stride; a plain call passes C =
+// 1 and the rate 1.0), before anything is queued and after every tree went through the call's other checks: what those refuse (no
+// tree, a length or scaled length that is not finite) is named first, whichever tree it is in.
+static int check_trees_expm_range(phylo_ctx* c, int T, int R, const double* blen, int C, const double* rate, size_t mix_stride, bool mix) {
+    const double qn = expm_range_norm(c);
+    if (qn == 0.0) return PHYLO_OK;
+    char msg[240];
+    int bad = 0;
+    for (int t = 0; t < T; ++t)
+        for (int k = 0; k < C; ++k)
+            if (pt2_check_expm_range(qn, 2 * R, blen + (size_t)t * R * 2, rate[t * mix_stride + k], &bad, msg, sizeof msg)) {
+                if (mix) return fail(c, PHYLO_EINVAL, "tree %d, row %d, category %d: %s", t, bad / 2, k, msg);
+                return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, bad / 2, msg);
+            }
+    return PHYLO_OK;
+}
+static const double expm_rate_one = 1.0;
+
 int phylo_expm_batched(phylo_ctx* c, const double* t, int n, double* P) {
     CHK(bind(c));
     if (!c->have_model) return fail(c, PHYLO_ESTATE, "phylo_set_model has not been called");
     if (n < 0 || (n > 0 && (!t || !P))) return fail(c, PHYLO_EINVAL, "bad arguments to phylo_expm_batched");
     if (n == 0) return PHYLO_OK;
+    {
+        char msg[240];
+        int bad = 0;
+        if (pt2_check_expm_range(expm_range_norm(c), n, t, 1.0, &bad, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "phylo_expm_batched: t[%d]: %s", bad, msg);
+    }
     void *dt, *dP;
     CHK(scratch_get(c, 0, (size_t)n * 8, &dt));
     CHK(scratch_get(c, 1, (size_t)n * 16 * 8, &dP));
@@ -1155,6 +1185,12 @@ int phylo_tree_loglik(phylo_ctx* c, int n_nodes, int n_leaves, int S, const int3
         }
     }
     const int n_int = (int)(order.size() / 3);
+    {   // the lengths above the children of the reachable internal nodes, in pruning order (row = that node)
+        char msg[240];
+        int bad = 0;
+        if (pt2_check_expm_range(expm_range_norm(c), (int)ts.size(), ts.data(), 1.0, &bad, msg, sizeof msg))
+            return fail(c, PHYLO_EINVAL, "tree 0, row %d: %s", (int)order[3 * (size_t)(bad / 2)], msg);
+    }
     void *dnodes, *dorder, *dt, *dP, *dpr, *dout;
     CHK(scratch_get(c, 0, (size_t)n_nodes * S * 4 * 8, &dnodes));
     CHK(scratch_get(c, 1, (size_t)(n_int ? n_int : 1) * 3 * 4, &dorder));
@@ -1220,6 +1256,7 @@ static int trees_loglik_run(phylo_ctx* c, const char* who, int T, const int32_t*
                     return fail(c, PHYLO_EINVAL, "tree %d, row %d, category %d: branch length %g at rate %g is not finite", t, i / 2, k,
                                 b[i], rate_C[k]);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, nc, rate_C, 0, mix));
     // one chunk of trees in device scratch: prior and weights | ops | matrices | branch lengths | gap rows | tile values | results |
     // site values | category factors.  The rates call's four-step kernels keep the site values in that row between categories
     // (pt2_prune_rates), so it is there, asked for or not, when a chunk is that shallow: a chunk's depth is its deepest tree's.
@@ -1593,6 +1630,7 @@ int phylo_trees_grad(phylo_ctx* c, int T, const int32_t* child, const double* bl
         if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
     const bool coded = c->leaves_coded, want_curv = curv != nullptr;
     ptg_plan pl;
     if (ptg_make_plan(N, ntiles, T, coded, want_curv, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
@@ -1707,6 +1745,7 @@ int phylo_trees_ancestral(phylo_ctx* c, int T, const int32_t* child, const doubl
         if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
     const bool coded = c->leaves_coded;
     const unsigned outs = (post_TxRxSx4 ? PTA_POST : 0u) | (state_TxRxS ? PTA_STATE : 0u) | (pmax_TxRxS ? PTA_PMAX : 0u);
     pta_plan pl;
@@ -1825,6 +1864,7 @@ int phylo_trees_grad_model(phylo_ctx* c, int T, const int32_t* child, const doub
         if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
     const bool coded = c->leaves_coded, want_grad = grad != nullptr;
     ptm_plan pl;
     if (ptm_make_plan(N, ntiles, T, P, coded, want_grad, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
@@ -1971,6 +2011,7 @@ int phylo_trees_grad_rates(phylo_ctx* c, int T, const int32_t* child, const doub
         if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, C, rate, mix_stride, true));
     const bool coded = c->leaves_coded, want_curv = curv != nullptr, want_params = drate_TxC != nullptr || dweight_TxC != nullptr;
     ptgr_plan pl;
     if (ptgr_make_plan(N, ntiles, T, C, coded, want_curv, want_params, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
@@ -2112,6 +2153,7 @@ int phylo_trees_ancestral_rates(phylo_ctx* c, int T, const int32_t* child, const
         if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, C, rate, mix_stride, true));
     const bool coded = c->leaves_coded;
     const unsigned outs = (post_TxRxSx4 ? PTAR_POST : 0u) | (state_TxRxS ? PTAR_STATE : 0u) | (pmax_TxRxS ? PTAR_PMAX : 0u) |
                           (catpost_TxCxS ? PTAR_CATPOST : 0u) | (siterate_TxS ? PTAR_SITERATE : 0u);
@@ -2285,6 +2327,7 @@ int phylo_trees_nni(phylo_ctx* c, int T, const int32_t* child, const double* ble
         if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
     const bool coded = c->leaves_coded;
     ptn_plan pl;
     if (ptn_make_plan(N, ntiles, T, coded, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
@@ -2400,6 +2443,7 @@ int phylo_trees_nni_rates(phylo_ctx* c, int T, const int32_t* child, const doubl
         if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
             return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
     }
+    CHK(check_trees_expm_range(c, T, R, blen, C, rate, mix_stride, true));
     const bool coded = c->leaves_coded;
     ptnr_plan pl;
     if (ptnr_make_plan(N, ntiles, T, C, coded, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))

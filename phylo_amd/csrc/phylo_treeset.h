@@ -4,20 +4,31 @@
 // that adds a tree's tile values left to right.  All arithmetic is phylo_math.h's and pk_merge_site's: the bits are those of
 // phylo_tree_loglik (pk_tree_prune + pk_row_loglik) and of the C oracle.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
+#include <stddef.h>
 #include <stdint.h>
 
 #include <cmath>
 #include <cstdio>
 #include <vector>
 
+#if defined(__HIPCC__)
 #include "phylo_kernels.h"
+#endif
 
 #define PT2_MAX_DEPTH 10                          // floor(log2 PK_MAX_TAXA) + 1 slots
 #define PT2_SLOT_BYTES 2048                       // one slot of one site step: 64 lanes x 4 doubles
 #define PT2_WAVE_LDS (20 * 1024)                  // four site steps per pass while the stack stays within this, else two
 #define PT2_MAX_CATS 16                           // rate categories of phylo_trees_loglik_rates
 #define PT2_SCRATCH_BYTES ((size_t)64 << 20)      // device scratch of one chunk of trees (phylo_trees_loglik cuts T to fit)
+// The domain of pm_expm4: its entrywise relative error is at most 2^s (8 E + 4) u after s squarings, E = 116
+// the worst error (in u = 2^-53) of a plain restatement of the algorithm without squarings, over the generators of
+// tests/expm_cases.py.  PT2_EXPM_S_MAX is the largest s at which that bound is still <= 2^-20; a length with ||Q||_1 t above
+// theta_13 2^s_max is refused, not answered with a matrix that has lost its digits (and, from 1e100 on, all of them: a zero matrix).
+#define PT2_EXPM_S_MAX 23
+#define PT2_EXPM_NORM_MAX (5.371920351148152 * 8388608.0)   // theta_13 * 2^PT2_EXPM_S_MAX = 4.5063e7
 
 // ------------------------------------------------------------------------------------------------
 // host: one tree = child[N-1][2], blen[N-1][2]; leaves 0 .. N-1, row i = internal node N + i, children from earlier rows
@@ -46,6 +57,39 @@ inline int pt2_check_tree(int N, const int32_t* child, const double* blen, int* 
             }
         }
     // 2 (N-1) distinct children out of the 2 N - 2 nodes below the root: every one of them exactly once
+    return 0;
+}
+
+// ||Q||_1 the way pm_expm4 takes the norm of Q t: the largest column sum of |q_ij|, rows added in ascending order
+inline double pt2_q_norm1(const double* Q16) {
+    double norm = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        double cs = 0.0;
+        for (int i = 0; i < 4; ++i) cs = cs + std::fabs(Q16[i * 4 + j]);
+        if (cs > norm) norm = cs;
+    }
+    return norm;
+}
+
+// Are the n lengths rate * t[i] inside the domain of pm_expm4 under a generator of 1-norm q_norm1: fl(q_norm1 * |fl(rate * t[i])|) <=
+// PT2_EXPM_NORM_MAX?  0: all are; otherwise the first offender's index in *bad and a message that names its length and the limit
+// (a NaN product offends: the comparison is false).  q_norm1 = 0 asks for no limit: the callers pass it under jc69_closed_form,
+// whose pm_jc69 is right at every length.  No HIP: tests/expm_range_asan_main.cpp runs it under the host compiler's sanitizers.
+inline int pt2_check_expm_range(double q_norm1, int n, const double* t, double rate, int* bad, char* msg, size_t nmsg) {
+    if (q_norm1 == 0.0) return 0;
+    for (int i = 0; i < n; ++i) {
+        const double len = rate * t[i];
+        const double a = q_norm1 * std::fabs(len);
+        if (a <= PT2_EXPM_NORM_MAX) continue;
+        *bad = i;
+        if (rate == 1.0)
+            snprintf(msg, nmsg, "length %g gives ||Q t||_1 = %g, above %g (theta_13 2^%d), the limit of the matrix exponential", t[i], a,
+                     PT2_EXPM_NORM_MAX, PT2_EXPM_S_MAX);
+        else
+            snprintf(msg, nmsg, "length %g at rate %g gives ||Q t||_1 = %g, above %g (theta_13 2^%d), the limit of the matrix exponential",
+                     t[i], rate, a, PT2_EXPM_NORM_MAX, PT2_EXPM_S_MAX);
+        return 1;
+    }
     return 0;
 }
 
@@ -111,6 +155,8 @@ inline int pt2_unroll(int depth) { return depth * 4 * PT2_SLOT_BYTES <= PT2_WAVE
 // ------------------------------------------------------------------------------------------------
 // device
 // ------------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+
 struct pt2_args {
     const int32_t* ops;              // [trees][N-1][4] schedule (wave-uniform)
     const double* P;                 // [trees][N-1][2][16] matrices in schedule order, left then right
@@ -407,3 +453,5 @@ inline void pt2_launch(const pt2_args& a, int trees, int depth, bool coded, hipS
         else pt2_launch_as<2, false>(a, trees, depth, s);
     }
 }
+
+#endif  // __HIPCC__
