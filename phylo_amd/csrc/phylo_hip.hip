@@ -293,16 +293,9 @@ struct phylo_ctx {
     int tb_wide = -1, tb_cbits = 0, tb_tbits = 0;   // the plan the last finished branch pass took (-1: none yet; phylo_debug_tree_branches_of)
     unsigned long long sweep_serial = 0, ts_serial = 0;
     hipEvent_t ev_tb0 = nullptr, ev_tb1 = nullptr;
-    hipEvent_t ev_tl0 = nullptr, ev_tl1 = nullptr;   // phylo_trees_loglik's own pair (the sweep's and the summaries' stay theirs)
+    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // the scored-tree-set calls' one pair (the sweep's and the summaries' stay theirs)
     hipEvent_t ev_rl0 = nullptr, ev_rl1 = nullptr;   // phylo_rell's own pair
     hipEvent_t ev_rm0 = nullptr, ev_rm1 = nullptr;   // phylo_rell_multiscale's own pair
-    hipEvent_t ev_tg0 = nullptr, ev_tg1 = nullptr;   // phylo_trees_grad's own pair
-    hipEvent_t ev_tr0 = nullptr, ev_tr1 = nullptr;   // phylo_trees_grad_rates' own pair
-    hipEvent_t ev_tn0 = nullptr, ev_tn1 = nullptr;   // phylo_trees_nni's own pair
-    hipEvent_t ev_tm0 = nullptr, ev_tm1 = nullptr;   // phylo_trees_nni_rates' own pair
-    hipEvent_t ev_tq0 = nullptr, ev_tq1 = nullptr;   // phylo_trees_grad_model's own pair
-    hipEvent_t ev_ta0 = nullptr, ev_ta1 = nullptr;   // phylo_trees_ancestral's own pair
-    hipEvent_t ev_tz0 = nullptr, ev_tz1 = nullptr;   // phylo_trees_ancestral_rates' own pair
 };
 
 namespace {
@@ -868,26 +861,12 @@ int phylo_destroy(phylo_ctx* c) {
     if (c->ev_model) (void)hipEventDestroy(c->ev_model);
     if (c->ev_tb0) (void)hipEventDestroy(c->ev_tb0);
     if (c->ev_tb1) (void)hipEventDestroy(c->ev_tb1);
-    if (c->ev_tl0) (void)hipEventDestroy(c->ev_tl0);
-    if (c->ev_tl1) (void)hipEventDestroy(c->ev_tl1);
+    if (c->ev_t0) (void)hipEventDestroy(c->ev_t0);
+    if (c->ev_t1) (void)hipEventDestroy(c->ev_t1);
     if (c->ev_rl0) (void)hipEventDestroy(c->ev_rl0);
     if (c->ev_rl1) (void)hipEventDestroy(c->ev_rl1);
     if (c->ev_rm0) (void)hipEventDestroy(c->ev_rm0);
     if (c->ev_rm1) (void)hipEventDestroy(c->ev_rm1);
-    if (c->ev_tg0) (void)hipEventDestroy(c->ev_tg0);
-    if (c->ev_tg1) (void)hipEventDestroy(c->ev_tg1);
-    if (c->ev_tr0) (void)hipEventDestroy(c->ev_tr0);
-    if (c->ev_tr1) (void)hipEventDestroy(c->ev_tr1);
-    if (c->ev_tn0) (void)hipEventDestroy(c->ev_tn0);
-    if (c->ev_tn1) (void)hipEventDestroy(c->ev_tn1);
-    if (c->ev_tm0) (void)hipEventDestroy(c->ev_tm0);
-    if (c->ev_tm1) (void)hipEventDestroy(c->ev_tm1);
-    if (c->ev_tq0) (void)hipEventDestroy(c->ev_tq0);
-    if (c->ev_tq1) (void)hipEventDestroy(c->ev_tq1);
-    if (c->ev_ta0) (void)hipEventDestroy(c->ev_ta0);
-    if (c->ev_ta1) (void)hipEventDestroy(c->ev_ta1);
-    if (c->ev_tz0) (void)hipEventDestroy(c->ev_tz0);
-    if (c->ev_tz1) (void)hipEventDestroy(c->ev_tz1);
     if (c->ev_ts0) (void)hipEventDestroy(c->ev_ts0);
     if (c->ev_ts1) (void)hipEventDestroy(c->ev_ts1);
     if (c->ev_gfork) (void)hipEventDestroy(c->ev_gfork);
@@ -1069,6 +1048,230 @@ static int check_trees_expm_range(phylo_ctx* c, int T, int R, const double* blen
 }
 static const double expm_rate_one = 1.0;
 
+// ---- the stages of a scored-tree-set call ---------------------------------------------------------------
+// The nine entry points (phylo_trees_loglik .. phylo_trees_nni_rates) each keep their own loop over the chunks and own what is
+// theirs: argument struct, kernel, finish kernel, downloads.  What they share is below, one stage a function, and trees_call is
+// what the stages of one call hand on to one another.  A stage returns its status; the entry point returns early on it (CHK), so an
+// error exit leaves queued what it always left queued.
+struct trees_call {
+    phylo_ctx* c = nullptr;
+    int N = 0, R = 0, S = 0, ntiles = 0, T = 0;
+    bool coded = false;
+    const int32_t* child = nullptr;
+    const double *blen = nullptr, *prior4 = nullptr;
+    int C = 1;                                              // sets of lengths per tree
+    const double *rate = nullptr, *weight = nullptr;        // rate NULL: a plain call, every tree's own lengths
+    size_t mix_stride = 0;                                  // tree t's mixture: row t, or the one row
+    // the slab: what every call carves (trees_carve) and what some do (d_dops, d_nops, d_b: NULL is neither built nor uploaded)
+    char* base = nullptr;
+    int chunk = 0;
+    double *d_prior = nullptr, *d_P = nullptr, *d_t = nullptr, *d_gap = nullptr, *d_tilev = nullptr, *d_out = nullptr, *d_b = nullptr;
+    int32_t *d_ops = nullptr, *d_dops = nullptr, *d_nops = nullptr;
+    const double* prior = nullptr;                          // the prior the kernels read: the caller's in the slab, or the model's
+    std::vector<int32_t> ops, dops, nops;                   // the chunk on the host, in the slab's layouts
+    std::vector<double> ts, bs;
+    int n = 0, depth = 1;                                   // the chunk in flight: trees, deepest schedule, matrices
+    long n_mat = 0;
+    double ms_total = 0.0;
+    int launches = 0;
+};
+
+static int trees_cus(const phylo_ctx* c) { return c->n_cus > 0 ? c->n_cus : 1; }
+
+// Front, part one: the refusals every call opens with.  C and per_tree: NULL where the call has none.
+static int trees_front(phylo_ctx* c, const char* who, int T, const int* C, const int* per_tree) {
+    CHK(bind(c));
+    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "%s needs phylo_set_leaves and phylo_set_model first", who);
+    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    if (C && (*C < 1 || *C > PT2_MAX_CATS)) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, *C);
+    if (per_tree && *per_tree != 0 && *per_tree != 1) return fail(c, PHYLO_EINVAL, "%s: per_tree must be 0 or 1 (per_tree=%d)", who, *per_tree);
+    return PHYLO_OK;
+}
+
+static trees_call trees_open(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4) {
+    trees_call tc;
+    tc.c = c; tc.N = c->N; tc.R = c->N - 1; tc.S = c->S; tc.ntiles = c->ntiles; tc.T = T;
+    tc.coded = c->leaves_coded;
+    tc.child = child; tc.blen = blen; tc.prior4 = prior4;
+    return tc;
+}
+
+static void trees_mixture(trees_call& tc, int C, const double* rate, const double* weight, int per_tree) {
+    tc.C = C; tc.rate = rate; tc.weight = weight;
+    tc.mix_stride = per_tree ? (size_t)C : 0;
+}
+
+// Front, part two, after the call's own NULL-pointer refusals: every tree (and its mixture) is checked before anything is queued,
+// then every length against the domain of the matrix exponential
+static int trees_check(const trees_call& tc) {
+    const size_t R2 = (size_t)tc.R * 2;
+    for (int t = 0; t < tc.T; ++t) {
+        int row = 0;
+        char msg[200];
+        if (pt2_check_tree(tc.N, tc.child + t * R2, tc.blen + t * R2, &row, msg, sizeof msg))
+            return fail(tc.c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
+        if (tc.rate && ptgr_check_mixture(tc.N, tc.blen + t * R2, tc.C, tc.rate + t * tc.mix_stride, tc.weight + t * tc.mix_stride, msg, sizeof msg))
+            return fail(tc.c, PHYLO_EINVAL, "tree %d: %s", t, msg);
+    }
+    if (!tc.rate) return check_trees_expm_range(tc.c, tc.T, tc.R, tc.blen, 1, &expm_rate_one, 0, false);
+    return check_trees_expm_range(tc.c, tc.T, tc.R, tc.blen, tc.C, tc.rate, tc.mix_stride, true);
+}
+
+// the pointers every call carves from its slab; Plan: any plan of the family
+extern "C++" template <class Plan>
+static void trees_carve(trees_call& tc, void* slab, const Plan& pl) {
+    char* base = (char*)slab;
+    tc.base = base;
+    tc.chunk = pl.chunk;
+    tc.d_prior = (double*)(base + pl.o_prior);
+    tc.d_ops = (int32_t*)(base + pl.o_ops);
+    tc.d_P = (double*)(base + pl.o_P);
+    tc.d_t = (double*)(base + pl.o_t);
+    tc.d_gap = tc.coded ? (double*)(base + pl.o_gap) : nullptr;
+    tc.d_tilev = (double*)(base + pl.o_tilev);
+    tc.d_out = (double*)(base + pl.o_out);
+}
+
+// Before the first chunk: the family's one event pair (no two calls of a context overlap: each ends in a stream synchronise and a
+// context is one thread's), the caller's prior, the chunk's host buffers
+static int trees_begin(trees_call& tc) {
+    phylo_ctx* c = tc.c;
+    if (!c->ev_t0) {
+        HIPCHK(c, hipEventCreate(&c->ev_t0));
+        HIPCHK(c, hipEventCreate(&c->ev_t1));
+    }
+    if (tc.prior4) HIPCHK(c, hipMemcpyAsync(tc.d_prior, tc.prior4, 32, hipMemcpyHostToDevice, c->stream));
+    tc.prior = tc.prior4 ? tc.d_prior : c->d_pi;
+    const size_t rows = (size_t)tc.chunk * tc.R;
+    tc.ops.resize(rows * 4);
+    if (tc.d_dops) tc.dops.resize(rows * 4);                // (the optional pointers are set by the call between trees_carve and here)
+    if (tc.d_nops) tc.nops.resize(rows * 4);
+    tc.ts.resize(rows * tc.C * 2);
+    if (tc.d_b) tc.bs.resize(rows * 2);
+    return PHYLO_OK;
+}
+
+// Chunk host stage, trees t0 .. t0 + n: one schedule per tree (and its downward and NNI operations), every set of lengths in the
+// schedule's order -- gathered once, then rate * length, one rounded product, per category where the call has rates -- and the
+// deepest schedule
+static int trees_chunk_host(trees_call& tc, int t0) {
+    // (locals, not members read through tc inside the loop: the per-tree loop is a measurable part of a small call's wall time)
+    const int N = tc.N, R = tc.R, C = tc.C, n = std::min(tc.chunk, tc.T - t0);
+    int32_t* const ops = tc.ops.data();
+    int32_t* const dops = tc.d_dops ? tc.dops.data() : nullptr;
+    int32_t* const nops = tc.d_nops ? tc.nops.data() : nullptr;
+    double* const ts = tc.ts.data();
+    double* const bs = tc.d_b ? tc.bs.data() : nullptr;
+    const double* const rate = tc.rate;
+    int depth = 1;
+    for (int t = 0; t < n; ++t) {
+        int32_t* o = ops + (size_t)t * R * 4;
+        int32_t* d = dops ? dops + (size_t)t * R * 4 : nullptr;
+        const int32_t* ch = tc.child + (size_t)(t0 + t) * R * 2;
+        depth = std::max(depth, pt2_schedule(N, ch, o));
+        if ((d && ptg_down_ops(N, ch, o, d)) || (nops && ptn_nni_ops(N, o, d, nops + (size_t)t * R * 4)))
+            return fail(tc.c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
+        const double* b = tc.blen + (size_t)(t0 + t) * R * 2;
+        double* tk = ts + (size_t)t * C * R * 2;
+        double* bk = bs ? bs + (size_t)t * R * 2 : tk;      // the tree's own lengths, gathered once: into the first set where no row of theirs is uploaded
+        for (int i = 0; i < R; ++i) {
+            bk[2 * i] = b[2 * o[4 * i + 3]];
+            bk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
+        }
+        if (rate) {
+            const double* rt = rate + (t0 + t) * tc.mix_stride;
+            for (int k = 1; k < C; ++k) {
+                double* q = tk + (size_t)k * R * 2;
+                for (int i = 0; i < 2 * R; ++i) q[i] = rt[k] * bk[i];
+            }
+            for (int i = 0; i < 2 * R; ++i) tk[i] = rt[0] * bk[i];      // the first set last: it may be the gathered row itself
+        } else if (bs) memcpy(tk, bk, (size_t)R * 16);
+    }
+    tc.n = n;
+    tc.depth = depth;
+    tc.n_mat = (long)n * C * R * 2;
+    if (depth > PT2_MAX_DEPTH) return fail(tc.c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
+    return PHYLO_OK;
+}
+
+// Chunk device prologue: the uploads of what the host stage built (the call's own uploads follow), ...
+static int trees_chunk_upload(trees_call& tc) {
+    phylo_ctx* c = tc.c;
+    const size_t rows = (size_t)tc.n * tc.R * 16;
+    HIPCHK(c, hipMemcpyAsync(tc.d_ops, tc.ops.data(), rows, hipMemcpyHostToDevice, c->stream));
+    if (tc.d_dops) HIPCHK(c, hipMemcpyAsync(tc.d_dops, tc.dops.data(), rows, hipMemcpyHostToDevice, c->stream));
+    if (tc.d_nops) HIPCHK(c, hipMemcpyAsync(tc.d_nops, tc.nops.data(), rows, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tc.d_t, tc.ts.data(), rows * tc.C, hipMemcpyHostToDevice, c->stream));
+    if (tc.d_b) HIPCHK(c, hipMemcpyAsync(tc.d_b, tc.bs.data(), rows, hipMemcpyHostToDevice, c->stream));
+    return PHYLO_OK;
+}
+
+// ... the start event and every matrix of the chunk (the call's own ptg_dmats / ptm_dirmats follow), ...
+static int trees_chunk_expm(trees_call& tc) {
+    phylo_ctx* c = tc.c;
+    HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
+    hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(tc.n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)tc.d_t, (int)tc.n_mat, c->jc, tc.d_P);
+    CHK(launch_check(c, "pk_expm_batched"));
+    ++tc.launches;
+    return PHYLO_OK;
+}
+
+// ... and the gap rows of the matrices M where the leaves are coded
+static int trees_chunk_gap_rows(trees_call& tc) {
+    if (!tc.coded) return PHYLO_OK;
+    phylo_ctx* c = tc.c;
+    hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(tc.n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)tc.d_P, tc.n_mat, tc.d_gap);
+    CHK(launch_check(c, "pt2_gap_rows"));
+    ++tc.launches;
+    return PHYLO_OK;
+}
+
+// the arguments every kernel of the family starts with (site_lik: the loglik calls set their own)
+static void trees_args(const trees_call& tc, pt2_args& a) {
+    const phylo_ctx* c = tc.c;
+    a.ops = tc.d_ops; a.P = tc.d_P; a.gap = tc.d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
+    a.prior = tc.prior;
+    a.tilev = tc.d_tilev; a.site_lik = nullptr;
+    a.N = tc.N; a.S = tc.S; a.T = c->site_tile; a.ntiles = tc.ntiles;
+}
+
+// Chunk epilogue: every tree's tile values added (the call's own finish kernels follow), ...
+static int trees_chunk_finish(trees_call& tc) {
+    phylo_ctx* c = tc.c;
+    hipLaunchKernelGGL(pt2_finish, dim3(cdiv(tc.n, 256)), dim3(256), 0, c->stream, (const double*)tc.d_tilev, tc.ntiles, tc.n, tc.d_out);
+    CHK(launch_check(c, "pt2_finish"));
+    ++tc.launches;
+    return PHYLO_OK;
+}
+
+// ... the stop event and the log-likelihoods (the call's own downloads follow), ...
+static int trees_chunk_stop(trees_call& tc, double* loglik_chunk) {
+    phylo_ctx* c = tc.c;
+    HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
+    HIPCHK(c, hipMemcpyAsync(loglik_chunk, tc.d_out, (size_t)tc.n * 8, hipMemcpyDeviceToHost, c->stream));
+    return PHYLO_OK;
+}
+
+// ... and the wait: the chunk's host and device buffers are reused by the next one
+static int trees_chunk_end(trees_call& tc) {
+    phylo_ctx* c = tc.c;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
+    tc.ms_total += ms;
+    return PHYLO_OK;
+}
+
+static void trees_stats(const trees_call& tc, phylo_stats* perf, double units, double alg_bytes) {
+    if (!perf) return;
+    phylo_stats st{};
+    st.sweep_ms = tc.ms_total;
+    st.n_launches = tc.launches;
+    st.units = units;
+    st.alg_bytes = alg_bytes;
+    *perf = st;
+}
+
 int phylo_expm_batched(phylo_ctx* c, const double* t, int n, double* P) {
     CHK(bind(c));
     if (!c->have_model) return fail(c, PHYLO_ESTATE, "phylo_set_model has not been called");
@@ -1224,21 +1427,18 @@ int phylo_tree_loglik(phylo_ctx* c, int n_nodes, int n_leaves, int S, const int3
 static int trees_loglik_run(phylo_ctx* c, const char* who, int T, const int32_t* child, const double* blen, bool mix, int C, const double* rate_C,
                             const double* weight_C, const double* prior4, double* loglik_T, double* site_lik_TxS,
                             double* cat_lik_TxCxS, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "%s needs phylo_set_leaves and phylo_set_model first", who);
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
-    if (mix && (C < 1 || C > PT2_MAX_CATS)) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
+    CHK(trees_front(c, who, T, mix ? &C : nullptr, nullptr));
     if (!child || !blen || !loglik_T || (mix && (!rate_C || !weight_C))) return fail(c, PHYLO_EINVAL, "NULL pointer");
-    static const double one = 1.0;
-    const int nc = mix ? C : 1;                             // sets of lengths per tree; the plain call's set is the tree's own (1.0 * b == b)
-    if (!mix) rate_C = &one;
+    const int nc = mix ? C : 1;                             // sets of lengths per tree; the plain call's set is the tree's own
     for (int k = 0; mix && k < C; ++k) {
         if (!(rate_C[k] >= 0.0) || !std::isfinite(rate_C[k]))
             return fail(c, PHYLO_EINVAL, "rate %g of category %d is not a finite number >= 0", rate_C[k], k);
         if (!(weight_C[k] >= 0.0) || !std::isfinite(weight_C[k]))
             return fail(c, PHYLO_EINVAL, "weight %g of category %d is not a finite number >= 0", weight_C[k], k);
     }
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    if (mix) trees_mixture(tc, C, rate_C, weight_C, 0);
+    const int N = tc.N, R = tc.R, S = tc.S;
     std::vector<int> need, depth_of(mix ? (size_t)T : 0);   // (rates call) every tree's depth: can a chunk take four site steps?
     for (int t = 0; t < T; ++t) {                          // every tree (and every scaled length) is checked before anything is queued
         int row = 0;
@@ -1256,111 +1456,46 @@ static int trees_loglik_run(phylo_ctx* c, const char* who, int T, const int32_t*
                     return fail(c, PHYLO_EINVAL, "tree %d, row %d, category %d: branch length %g at rate %g is not finite", t, i / 2, k,
                                 b[i], rate_C[k]);
     }
-    CHK(check_trees_expm_range(c, T, R, blen, nc, rate_C, 0, mix));
-    // one chunk of trees in device scratch: prior and weights | ops | matrices | branch lengths | gap rows | tile values | results |
-    // site values | category factors.  The rates call's four-step kernels keep the site values in that row between categories
-    // (pt2_prune_rates), so it is there, asked for or not, when a chunk is that shallow: a chunk's depth is its deepest tree's.
-    const bool coded = c->leaves_coded;
-    bool sites = site_lik_TxS != nullptr;
-    size_t per_tree = 0;
-    int chunk = 0;
-    for (;;) {
-        per_tree = (size_t)R * 16 + (size_t)nc * R * (16 + 256 + (coded ? 64 : 0)) + (size_t)ntiles * 8 + 8 +
-                   (sites ? (size_t)S * 8 : 0) + (cat_lik_TxCxS ? (size_t)nc * S * 8 : 0);
-        size_t fit = PT2_SCRATCH_BYTES / per_tree;
-        if (fit < 1) fit = 1;
-        if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);   // one workgroup per (tree, tile)
-        chunk = (int)std::min<size_t>((size_t)T, c->env.trees_chunk > 0 ? std::min<size_t>(fit, (size_t)c->env.trees_chunk) : fit);
-        if (!mix || sites) break;
-        for (int t0 = 0; t0 < T && !sites; t0 += chunk)     // the chunks without the row: is one of them that shallow?
-            sites = pt2_unroll(*std::max_element(depth_of.begin() + t0, depth_of.begin() + std::min(T, t0 + chunk))) == 4;
-        if (!sites) break;
-    }
+    CHK(check_trees_expm_range(c, T, R, blen, nc, mix ? rate_C : &expm_rate_one, 0, mix));
+    pt2_plan pl;
+    if (pt2_make_plan(N, S, tc.ntiles, T, nc, mix, tc.coded, site_lik_TxS != nullptr, cat_lik_TxCxS != nullptr, c->env.trees_chunk,
+                      mix ? depth_of.data() : nullptr, &pl))
+        return fail(c, PHYLO_EINVAL, "%s: no plan for N=%d, S=%d, %d tiles, T=%d", who, N, S, tc.ntiles, T);   // (unreachable: a context has N >= 2, S >= 1, tiles >= 1, and T, C were checked above)
     void* slab = nullptr;
-    CHK(scratch_get(c, 14, per_tree * chunk + 32 + PT2_MAX_CATS * 8 + 256, &slab));
-    char* p = (char*)slab;
-    auto carve = [&](size_t bytes) { char* q = p; p += (bytes + 15) & ~(size_t)15; return q; };
-    double* d_prior = (double*)carve(32 + PT2_MAX_CATS * 8);   // the prior, then the weights: one pointer for pt2_prune_rates
-    int32_t* d_ops = (int32_t*)carve((size_t)chunk * R * 16);
-    double* d_P = (double*)carve((size_t)chunk * nc * R * 256);
-    double* d_t = (double*)carve((size_t)chunk * nc * R * 16);
-    double* d_gap = coded ? (double*)carve((size_t)chunk * nc * R * 64) : nullptr;
-    double* d_tilev = (double*)carve((size_t)chunk * ntiles * 8);
-    double* d_out = (double*)carve((size_t)chunk * 8);
-    double* d_site = sites ? (double*)carve((size_t)chunk * S * 8) : nullptr;
-    double* d_cat = cat_lik_TxCxS ? (double*)carve((size_t)chunk * nc * S * 8) : nullptr;
-    if (!c->ev_tl0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tl0));
-        HIPCHK(c, hipEventCreate(&c->ev_tl1));
+    CHK(scratch_get(c, 14, pl.total, &slab));
+    trees_carve(tc, slab, pl);
+    double* d_site = pl.sites ? (double*)(tc.base + pl.o_site) : nullptr;
+    double* d_cat = cat_lik_TxCxS ? (double*)(tc.base + pl.o_cat) : nullptr;
+    CHK(trees_begin(tc));
+    if (mix) {                                              // the prior, then the weights: one pointer for pt2_prune_rates
+        if (!prior4) HIPCHK(c, hipMemcpyAsync(tc.d_prior, c->d_pi, 32, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tc.d_prior + 4, weight_C, (size_t)C * 8, hipMemcpyHostToDevice, c->stream));
+        tc.prior = tc.d_prior;
     }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
-    else if (mix) HIPCHK(c, hipMemcpyAsync(d_prior, c->d_pi, 32, hipMemcpyDeviceToDevice, c->stream));
-    if (mix) HIPCHK(c, hipMemcpyAsync(d_prior + 4, weight_C, (size_t)C * 8, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> ops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * nc * R * 2);
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every set of lengths in its order
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            const int d = pt2_schedule(N, child + (size_t)(t0 + t) * R * 2, o);
-            depth = std::max(depth, d);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            for (int k = 0; k < nc; ++k) {
-                double* tk = ts.data() + ((size_t)t * nc + k) * R * 2;
-                for (int i = 0; i < R; ++i) {
-                    tk[2 * i] = rate_C[k] * b[2 * o[4 * i + 3]];
-                    tk[2 * i + 1] = rate_C[k] * b[2 * o[4 * i + 3] + 1];
-                }
-            }
-        }
-        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
-        if (mix && !d_site && pt2_unroll(depth) == 4)       // (never: the chunks were looked at above, by pt2_needs' depths)
-            return fail(c, PHYLO_EINVAL, "a chunk of depth %d without the row of site values its kernel needs", depth);
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * nc * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_tl0, c->stream));
-        const long n_mat = (long)n * nc * R * 2;
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        ++launches;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));
+        const int n = tc.n;
+        if (mix && !d_site && pt2_unroll(tc.depth) == 4)    // (never: pt2_make_plan looked at the chunks, by pt2_needs' depths)
+            return fail(c, PHYLO_EINVAL, "a chunk of depth %d without the row of site values its kernel needs", tc.depth);
+        CHK(trees_chunk_upload(tc));
+        CHK(trees_chunk_expm(tc));
+        CHK(trees_chunk_gap_rows(tc));
         pt2_rates_args ra{};
-        pt2_args& a = ra.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 || mix ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = d_site;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
+        trees_args(tc, ra.a);
+        ra.a.site_lik = d_site;
         ra.cat_lik = d_cat; ra.C = C;
-        if (mix) pt2_launch_rates(ra, n, depth, coded, c->stream);
-        else pt2_launch(a, n, depth, coded, c->stream);
+        if (mix) pt2_launch_rates(ra, n, tc.depth, tc.coded, c->stream);
+        else pt2_launch(ra.a, n, tc.depth, tc.coded, c->stream);
         CHK(launch_check(c, mix ? "pt2_prune_rates" : "pt2_prune"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
-        launches += 2;
-        HIPCHK(c, hipEventRecord(c->ev_tl1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        ++tc.launches;
+        CHK(trees_chunk_finish(tc));
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         if (site_lik_TxS) HIPCHK(c, hipMemcpyAsync(site_lik_TxS + (size_t)t0 * S, d_site, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
         if (d_cat) HIPCHK(c, hipMemcpyAsync(cat_lik_TxCxS + (size_t)t0 * nc * S, d_cat, (size_t)n * nc * S * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tl0, c->ev_tl1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R * nc;
-        st.alg_bytes = 96.0 * st.units;
-        *perf = st;
-    }
+    const double units = (double)T * S * R * nc;
+    trees_stats(tc, perf, units, 96.0 * units);
     return PHYLO_OK;
 }
 
@@ -1619,374 +1754,190 @@ int phylo_rell_multiscale(phylo_ctx* c, int T, int S, const double* site_lik_TxS
 // ---- branch-length derivatives of a scored tree set (phylo_treegrad.h) ----
 int phylo_trees_grad(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T, double* grad,
                      double* curv, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_grad needs phylo_set_leaves and phylo_set_model first");
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    CHK(trees_front(c, "phylo_trees_grad", T, nullptr, nullptr));
     if (!child || !blen || !loglik_T || !grad) return fail(c, PHYLO_EINVAL, "phylo_trees_grad: child, blen, loglik and grad must be given (NULL pointer)");
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
-        int row = 0;
-        char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
-    }
-    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
-    const bool coded = c->leaves_coded, want_curv = curv != nullptr;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    CHK(trees_check(tc));
+    const int N = tc.N, R = tc.R, S = tc.S, ntiles = tc.ntiles;
+    const bool want_curv = curv != nullptr;
     ptg_plan pl;
-    if (ptg_make_plan(N, ntiles, T, coded, want_curv, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+    if (ptg_make_plan(N, ntiles, T, tc.coded, want_curv, trees_cus(c), c->env.trees_chunk, &pl))
         return fail(c, PHYLO_EINVAL, "phylo_trees_grad: no plan for N=%d, %d tiles, T=%d", N, ntiles, T);
-    const int chunk = pl.chunk, nq = pl.nq;
+    const int nq = pl.nq;
     void* slab = nullptr;
     CHK(scratch_get(c, 16, pl.total, &slab));
-    char* base = (char*)slab;
-    double* d_prior = (double*)(base + pl.o_prior);
-    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
-    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
-    double* d_P = (double*)(base + pl.o_P);
-    double* d_t = (double*)(base + pl.o_t);
-    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
-    double* d_tilev = (double*)(base + pl.o_tilev);
-    double* d_out = (double*)(base + pl.o_out);
-    double* d_dtile = (double*)(base + pl.o_dtile);
-    double* d_dout = (double*)(base + pl.o_dout);
-    if (!c->ev_tg0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tg0));
-        HIPCHK(c, hipEventCreate(&c->ev_tg1));
-    }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * R * 2);
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
-            depth = std::max(depth, pt2_schedule(N, ch, o));
-            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
-                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            double* tk = ts.data() + (size_t)t * R * 2;
-            for (int i = 0; i < R; ++i) {
-                tk[2 * i] = b[2 * o[4 * i + 3]];
-                tk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
-            }
-        }
-        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_tg0, c->stream));
-        const long n_mat = (long)n * R * 2;                 // M | M' | M'' packed by this chunk's count
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_P, n_mat,
-                           d_P + n_mat * 16, d_P + 2 * n_mat * 16);
+    trees_carve(tc, slab, pl);
+    tc.d_dops = (int32_t*)(tc.base + pl.o_dops);            // set: trees_begin sizes the host buffer, the chunk stages build and upload it
+    double* d_dtile = (double*)(tc.base + pl.o_dtile);
+    double* d_dout = (double*)(tc.base + pl.o_dout);
+    CHK(trees_begin(tc));
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));
+        const int n = tc.n;
+        CHK(trees_chunk_upload(tc));
+        CHK(trees_chunk_expm(tc));
+        const long n_mat = tc.n_mat;                        // M | M' | M'' packed by this chunk's count
+        hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)tc.d_P, n_mat,
+                           tc.d_P + n_mat * 16, tc.d_P + 2 * n_mat * 16);
         CHK(launch_check(c, "ptg_dmats"));
-        launches += 2;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+        CHK(trees_chunk_gap_rows(tc));
         ptg_args g{};
-        pt2_args& a = g.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = nullptr;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        g.dops = d_dops; g.dtile = d_dtile; g.store = (pk_d2*)(base + pl.o_store);
+        trees_args(tc, g.a);
+        g.dops = tc.d_dops; g.dtile = d_dtile; g.store = (pk_d2*)(tc.base + pl.o_store);
         g.mat_plane = n_mat * 16;
-        g.n_items = n * ntiles; g.depth = depth;
-        ptg_launch(g, std::min(pl.grid, g.n_items), coded, want_curv, c->stream);
+        g.n_items = n * ntiles; g.depth = tc.depth;
+        ptg_launch(g, std::min(pl.grid, g.n_items), tc.coded, want_curv, c->stream);
         CHK(launch_check(c, "ptg_updown"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
-        hipLaunchKernelGGL(ptg_finish, dim3(cdiv((long)n * nq * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)d_ops,
-                           (const double*)d_out, ntiles, n, R, nq, d_dout);
+        CHK(trees_chunk_finish(tc));
+        hipLaunchKernelGGL(ptg_finish, dim3(cdiv((long)n * nq * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)tc.d_ops,
+                           (const double*)tc.d_out, ntiles, n, R, nq, d_dout);
         CHK(launch_check(c, "ptg_finish"));
-        launches += 3;
-        HIPCHK(c, hipEventRecord(c->ev_tg1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        tc.launches += 3;                                   // ptg_dmats, ptg_updown, ptg_finish
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         HIPCHK(c, hipMemcpyAsync(grad + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
         if (want_curv)
             HIPCHK(c, hipMemcpyAsync(curv + (size_t)t0 * 2 * R, d_dout + (size_t)n * 2 * R, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tg0, c->ev_tg1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R;
-        st.alg_bytes = 96.0 * st.units;
-        *perf = st;
-    }
+    const double units = (double)T * S * R;
+    trees_stats(tc, perf, units, 96.0 * units);
     return PHYLO_OK;
 }
 
 // ---- marginal ancestral state posteriors of a scored tree set (phylo_treeanc.h) ----
 int phylo_trees_ancestral(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T,
                           double* post_TxRxSx4, uint8_t* state_TxRxS, double* pmax_TxRxS, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_ancestral needs phylo_set_leaves and phylo_set_model first");
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    CHK(trees_front(c, "phylo_trees_ancestral", T, nullptr, nullptr));
     if (!child || !blen || !loglik_T) return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral: child, blen and loglik must be given (NULL pointer)");
     if (!post_TxRxSx4 && !state_TxRxS && !pmax_TxRxS)
         return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral: one of post, state and pmax must be given (all three are NULL pointers)");
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
-        int row = 0;
-        char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
-    }
-    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
-    const bool coded = c->leaves_coded;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    CHK(trees_check(tc));
+    const int N = tc.N, R = tc.R, S = tc.S, ntiles = tc.ntiles;
     const unsigned outs = (post_TxRxSx4 ? PTA_POST : 0u) | (state_TxRxS ? PTA_STATE : 0u) | (pmax_TxRxS ? PTA_PMAX : 0u);
     pta_plan pl;
-    const int prc = pta_make_plan(N, S, ntiles, T, coded, outs, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl);
+    const int prc = pta_make_plan(N, S, ntiles, T, tc.coded, outs, trees_cus(c), c->env.trees_chunk, &pl);
     if (prc == 2)
         return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral: the requested outputs of one tree take %zu bytes, more than %zu (N=%d, S=%d)",
                     pl.out_tree, (size_t)PTA_OUT_MAX, N, S);
     if (prc) return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral: no plan for N=%d, S=%d, %d tiles, T=%d", N, S, ntiles, T);
-    const int chunk = pl.chunk;
     void* slab = nullptr;
     CHK(scratch_get(c, 22, pl.total, &slab));
-    char* base = (char*)slab;
-    double* d_prior = (double*)(base + pl.o_prior);
-    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
-    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
-    double* d_P = (double*)(base + pl.o_P);
-    double* d_t = (double*)(base + pl.o_t);
-    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
-    double* d_tilev = (double*)(base + pl.o_tilev);
-    double* d_out = (double*)(base + pl.o_out);
-    double* d_post = post_TxRxSx4 ? (double*)(base + pl.o_post) : nullptr;
-    uint8_t* d_state = state_TxRxS ? (uint8_t*)(base + pl.o_state) : nullptr;
-    double* d_pmax = pmax_TxRxS ? (double*)(base + pl.o_pmax) : nullptr;
-    if (!c->ev_ta0) {
-        HIPCHK(c, hipEventCreate(&c->ev_ta0));
-        HIPCHK(c, hipEventCreate(&c->ev_ta1));
-    }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * R * 2);
+    trees_carve(tc, slab, pl);
+    tc.d_dops = (int32_t*)(tc.base + pl.o_dops);            // set: trees_begin sizes the host buffer, the chunk stages build and upload it
+    double* d_post = post_TxRxSx4 ? (double*)(tc.base + pl.o_post) : nullptr;
+    uint8_t* d_state = state_TxRxS ? (uint8_t*)(tc.base + pl.o_state) : nullptr;
+    double* d_pmax = pmax_TxRxS ? (double*)(tc.base + pl.o_pmax) : nullptr;
+    CHK(trees_begin(tc));
     const size_t cells_tree = (size_t)R * S;               // node-sites of one tree
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
-            depth = std::max(depth, pt2_schedule(N, ch, o));
-            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
-                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            double* tk = ts.data() + (size_t)t * R * 2;
-            for (int i = 0; i < R; ++i) {
-                tk[2 * i] = b[2 * o[4 * i + 3]];
-                tk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
-            }
-        }
-        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_ta0, c->stream));
-        const long n_mat = (long)n * R * 2;
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        ++launches;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));
+        const int n = tc.n;
+        CHK(trees_chunk_upload(tc));
+        CHK(trees_chunk_expm(tc));
+        CHK(trees_chunk_gap_rows(tc));
         pta_args g{};
-        pt2_args& a = g.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = nullptr;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        g.dops = d_dops; g.store = (pk_d2*)(base + pl.o_store);
+        trees_args(tc, g.a);
+        g.dops = tc.d_dops; g.store = (pk_d2*)(tc.base + pl.o_store);
         g.post = d_post; g.state = d_state; g.pmax = d_pmax;
-        g.n_items = n * ntiles; g.depth = depth;
-        pta_launch(g, std::min(pl.grid, g.n_items), coded, c->stream);
+        g.n_items = n * ntiles; g.depth = tc.depth;
+        pta_launch(g, std::min(pl.grid, g.n_items), tc.coded, c->stream);
         CHK(launch_check(c, "pta_updown"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
-        launches += 2;
-        HIPCHK(c, hipEventRecord(c->ev_ta1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        ++tc.launches;
+        CHK(trees_chunk_finish(tc));
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         if (d_post)                                        // every node-site of the chunk was written: straight into the caller's rows
             HIPCHK(c, hipMemcpyAsync(post_TxRxSx4 + (size_t)t0 * cells_tree * 4, d_post, (size_t)n * cells_tree * 32, hipMemcpyDeviceToHost, c->stream));
         if (d_state) HIPCHK(c, hipMemcpyAsync(state_TxRxS + (size_t)t0 * cells_tree, d_state, (size_t)n * cells_tree, hipMemcpyDeviceToHost, c->stream));
         if (d_pmax) HIPCHK(c, hipMemcpyAsync(pmax_TxRxS + (size_t)t0 * cells_tree, d_pmax, (size_t)n * cells_tree * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_ta0, c->ev_ta1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R;
-        st.alg_bytes = (double)T * S * R * ((post_TxRxSx4 ? 32.0 : 0.0) + (state_TxRxS ? 1.0 : 0.0) + (pmax_TxRxS ? 8.0 : 0.0));
-        *perf = st;
-    }
+    trees_stats(tc, perf, (double)T * S * R,
+                (double)T * S * R * ((post_TxRxSx4 ? 32.0 : 0.0) + (state_TxRxS ? 1.0 : 0.0) + (pmax_TxRxS ? 8.0 : 0.0)));
     return PHYLO_OK;
 }
 
 // ---- derivatives along directions of the generator and with respect to the prior (phylo_treegrad_model.h) ----
 int phylo_trees_grad_model(phylo_ctx* c, int T, const int32_t* child, const double* blen, int P, const double* dirs_Px16, const double* prior4,
                            double* loglik_T, double* grad, double* dtheta_TxP, double* dprior_Tx4, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_grad_model needs phylo_set_leaves and phylo_set_model first");
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    CHK(trees_front(c, "phylo_trees_grad_model", T, nullptr, nullptr));
     if (!child || !blen || !dirs_Px16 || !loglik_T || !dtheta_TxP)
         return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: child, blen, dirs, loglik and dtheta must be given (NULL pointer)");
     if (P < 1 || P > PTM_MAX_DIRS) return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: need 1 <= P <= %d directions (P=%d)", PTM_MAX_DIRS, P);
     for (int i = 0; i < P * 16; ++i)
         if (!std::isfinite(dirs_Px16[i]))
             return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: direction %d, entry %d is not finite (%g)", i / 16, i % 16, dirs_Px16[i]);
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
-        int row = 0;
-        char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
-    }
-    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
-    const bool coded = c->leaves_coded, want_grad = grad != nullptr;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    CHK(trees_check(tc));
+    const int N = tc.N, R = tc.R, S = tc.S, ntiles = tc.ntiles;
+    const bool want_grad = grad != nullptr;
     ptm_plan pl;
-    if (ptm_make_plan(N, ntiles, T, P, coded, want_grad, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+    if (ptm_make_plan(N, ntiles, T, P, tc.coded, want_grad, trees_cus(c), c->env.trees_chunk, &pl))
         return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: no plan for N=%d, %d tiles, T=%d, P=%d", N, ntiles, T, P);
     // From the deepest schedule there is, not a chunk's own, so that nothing is queued before it; with N <= 512, P <= 16 that is
     // 56 KiB, so the refusal cannot fire today: it guards a larger PT2_MAX_DEPTH or PTM_MAX_DIRS (the arithmetic is in the sanitizer program)
     if (ptm_lds_bytes(N, PT2_MAX_DEPTH, P, want_grad) > PTM_MAX_LDS)
         return fail(c, PHYLO_EINVAL, "phylo_trees_grad_model: %zu bytes of LDS for a wave exceed %zu (N=%d, P=%d)",
                     ptm_lds_bytes(N, PT2_MAX_DEPTH, P, want_grad), PTM_MAX_LDS, N, P);
-    const int chunk = pl.chunk, nm = pl.nm;
+    const int nm = pl.nm;
     void* slab = nullptr;
     CHK(scratch_get(c, 20, pl.total, &slab));
-    char* base = (char*)slab;
-    double* d_prior = (double*)(base + pl.o_prior);
-    double* d_dirs = (double*)(base + pl.o_dirs);
-    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
-    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
-    double* d_P = (double*)(base + pl.o_P);
-    double* d_D = (double*)(base + pl.o_D);
-    double* d_t = (double*)(base + pl.o_t);
-    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
-    double* d_tilev = (double*)(base + pl.o_tilev);
-    double* d_out = (double*)(base + pl.o_out);
-    double* d_dtile = want_grad ? (double*)(base + pl.o_dtile) : nullptr;
-    double* d_dout = want_grad ? (double*)(base + pl.o_dout) : nullptr;
-    double* d_mtile = (double*)(base + pl.o_mtile);
-    double* d_mout = (double*)(base + pl.o_mout);          // dtheta [n][P] | dprior [n][4]
-    if (!c->ev_tq0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tq0));
-        HIPCHK(c, hipEventCreate(&c->ev_tq1));
-    }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
+    trees_carve(tc, slab, pl);
+    tc.d_dops = (int32_t*)(tc.base + pl.o_dops);            // set: trees_begin sizes the host buffer, the chunk stages build and upload it
+    double* d_dirs = (double*)(tc.base + pl.o_dirs);
+    double* d_D = (double*)(tc.base + pl.o_D);
+    double* d_dtile = want_grad ? (double*)(tc.base + pl.o_dtile) : nullptr;
+    double* d_dout = want_grad ? (double*)(tc.base + pl.o_dout) : nullptr;
+    double* d_mtile = (double*)(tc.base + pl.o_mtile);
+    double* d_mout = (double*)(tc.base + pl.o_mout);       // dtheta [n][P] | dprior [n][4]
+    CHK(trees_begin(tc));
     HIPCHK(c, hipMemcpyAsync(d_dirs, dirs_Px16, (size_t)P * 128, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * R * 2);
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
-            depth = std::max(depth, pt2_schedule(N, ch, o));
-            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
-                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            double* tk = ts.data() + (size_t)t * R * 2;
-            for (int i = 0; i < R; ++i) {
-                tk[2 * i] = b[2 * o[4 * i + 3]];
-                tk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
-            }
-        }
-        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_tq0, c->stream));
-        const long n_mat = (long)n * R * 2;                 // M | M' packed by this chunk's count
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        ++launches;
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));
+        const int n = tc.n;
+        CHK(trees_chunk_upload(tc));
+        CHK(trees_chunk_expm(tc));
+        const long n_mat = tc.n_mat;                        // M | M' packed by this chunk's count
         if (want_grad) {                                    // M'' is ptg_dmats' second output: it goes where D is built next
-            hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_P, n_mat,
-                               d_P + n_mat * 16, d_D);
+            hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)tc.d_P, n_mat,
+                               tc.d_P + n_mat * 16, d_D);
             CHK(launch_check(c, "ptg_dmats"));
-            ++launches;
+            ++tc.launches;
         }
         hipLaunchKernelGGL(ptm_dirmats, dim3(cdiv(n_mat * P, 64)), dim3(64), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_dirs, P,
-                           (const double*)d_t, n_mat, d_D);
+                           (const double*)tc.d_t, n_mat, d_D);
         CHK(launch_check(c, "ptm_dirmats"));
-        ++launches;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+        ++tc.launches;
+        CHK(trees_chunk_gap_rows(tc));
         ptm_args m{};
         ptg_args& g = m.g;
-        pt2_args& a = g.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = nullptr;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        g.dops = d_dops; g.dtile = d_dtile; g.store = (pk_d2*)(base + pl.o_store);
+        trees_args(tc, g.a);
+        g.dops = tc.d_dops; g.dtile = d_dtile; g.store = (pk_d2*)(tc.base + pl.o_store);
         g.mat_plane = n_mat * 16;
-        g.n_items = n * ntiles; g.depth = depth;
+        g.n_items = n * ntiles; g.depth = tc.depth;
         m.D = d_D; m.mtile = d_mtile; m.P = P;
-        ptm_launch(m, std::min(pl.grid, g.n_items), coded, want_grad, c->stream);
+        ptm_launch(m, std::min(pl.grid, g.n_items), tc.coded, want_grad, c->stream);
         CHK(launch_check(c, "ptm_updown"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
-        launches += 2;
+        ++tc.launches;
+        CHK(trees_chunk_finish(tc));
         if (want_grad) {
-            hipLaunchKernelGGL(ptg_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)d_ops,
-                               (const double*)d_out, ntiles, n, R, 1, d_dout);
+            hipLaunchKernelGGL(ptg_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)tc.d_ops,
+                               (const double*)tc.d_out, ntiles, n, R, 1, d_dout);
             CHK(launch_check(c, "ptg_finish"));
-            ++launches;
+            ++tc.launches;
         }
-        hipLaunchKernelGGL(ptm_finish, dim3(cdiv((long)n * nm, 256)), dim3(256), 0, c->stream, (const double*)d_mtile, (const double*)d_out, ntiles, n, P,
+        hipLaunchKernelGGL(ptm_finish, dim3(cdiv((long)n * nm, 256)), dim3(256), 0, c->stream, (const double*)d_mtile, (const double*)tc.d_out, ntiles, n, P,
                            d_mout, d_mout + (size_t)n * P);
         CHK(launch_check(c, "ptm_finish"));
-        ++launches;
-        HIPCHK(c, hipEventRecord(c->ev_tq1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        ++tc.launches;
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         if (want_grad) HIPCHK(c, hipMemcpyAsync(grad + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(dtheta_TxP + (size_t)t0 * P, d_mout, (size_t)n * P * 8, hipMemcpyDeviceToHost, c->stream));
         if (dprior_Tx4)
             HIPCHK(c, hipMemcpyAsync(dprior_Tx4 + (size_t)t0 * 4, d_mout + (size_t)n * P, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tq0, c->ev_tq1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R * (1 + P);
-        st.alg_bytes = 96.0 * (double)T * S * R;
-        *perf = st;
-    }
+    trees_stats(tc, perf, (double)T * S * R * (1 + P), 96.0 * (double)T * S * R);
     return PHYLO_OK;
 }
 
@@ -1994,137 +1945,70 @@ int phylo_trees_grad_model(phylo_ctx* c, int T, const int32_t* child, const doub
 int phylo_trees_grad_rates(phylo_ctx* c, int T, const int32_t* child, const double* blen, int C, const double* rate, const double* weight,
                            int per_tree, const double* prior4, double* loglik_T, double* grad, double* curv, double* drate_TxC,
                            double* dweight_TxC, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_grad_rates needs phylo_set_leaves and phylo_set_model first");
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
-    if (C < 1 || C > PT2_MAX_CATS) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
-    if (per_tree != 0 && per_tree != 1) return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: per_tree must be 0 or 1 (per_tree=%d)", per_tree);
+    CHK(trees_front(c, "phylo_trees_grad_rates", T, &C, &per_tree));
     if (!child || !blen || !rate || !weight || !loglik_T || !grad)
         return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: child, blen, rate, weight, loglik and grad must be given (NULL pointer)");
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    const size_t mix_stride = per_tree ? (size_t)C : 0;    // tree t's mixture: row t, or the one row
-    for (int t = 0; t < T; ++t) {                          // every tree and its mixture are checked before anything is queued
-        int row = 0;
-        char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
-        if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
-    }
-    CHK(check_trees_expm_range(c, T, R, blen, C, rate, mix_stride, true));
-    const bool coded = c->leaves_coded, want_curv = curv != nullptr, want_params = drate_TxC != nullptr || dweight_TxC != nullptr;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    trees_mixture(tc, C, rate, weight, per_tree);
+    CHK(trees_check(tc));
+    const int N = tc.N, R = tc.R, S = tc.S, ntiles = tc.ntiles;
+    const bool want_curv = curv != nullptr, want_params = drate_TxC != nullptr || dweight_TxC != nullptr;
     ptgr_plan pl;
-    if (ptgr_make_plan(N, ntiles, T, C, coded, want_curv, want_params, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+    if (ptgr_make_plan(N, ntiles, T, C, tc.coded, want_curv, want_params, trees_cus(c), c->env.trees_chunk, &pl))
         return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: no plan for N=%d, %d tiles, T=%d, C=%d", N, ntiles, T, C);
-    const int chunk = pl.chunk, nq = pl.nq, np = pl.np;
+    const int nq = pl.nq, np = pl.np;
     void* slab = nullptr;
     CHK(scratch_get(c, 17, pl.total, &slab));
-    char* base = (char*)slab;
-    double* d_prior = (double*)(base + pl.o_prior);
-    double* d_coef = (double*)(base + pl.o_coef);
-    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
-    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
-    double* d_P = (double*)(base + pl.o_P);
-    double* d_t = (double*)(base + pl.o_t);
-    double* d_b = (double*)(base + pl.o_b);
-    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
-    double* d_tilev = (double*)(base + pl.o_tilev);
-    double* d_out = (double*)(base + pl.o_out);
-    double* d_dtile = (double*)(base + pl.o_dtile);
-    double* d_dout = (double*)(base + pl.o_dout);
-    double* d_ptile = want_params ? (double*)(base + pl.o_ptile) : nullptr;
-    double* d_pout = want_params ? (double*)(base + pl.o_pout) : nullptr;
-    if (!c->ev_tr0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tr0));
-        HIPCHK(c, hipEventCreate(&c->ev_tr1));
-    }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * C * R * 2), bs((size_t)chunk * R * 2), coef((size_t)chunk * pl.ncoef);
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every set of lengths in its order
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
-            depth = std::max(depth, pt2_schedule(N, ch, o));
-            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
-                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            const double* rt = rate + (t0 + t) * mix_stride;
-            double* bk = bs.data() + (size_t)t * R * 2;
-            for (int i = 0; i < R; ++i) {
-                bk[2 * i] = b[2 * o[4 * i + 3]];
-                bk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
-            }
-            for (int k = 0; k < C; ++k) {
-                double* tk = ts.data() + ((size_t)t * C + k) * R * 2;
-                for (int i = 0; i < 2 * R; ++i) tk[i] = rt[k] * bk[i];
-            }
-            ptgr_coefficients(C, rt, weight + (t0 + t) * mix_stride, coef.data() + (size_t)t * pl.ncoef);
-        }
-        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
-        if (ptgr_lds_bytes(N, depth, C, want_curv, want_params) > PTGR_MAX_LDS)
+    trees_carve(tc, slab, pl);
+    tc.d_dops = (int32_t*)(tc.base + pl.o_dops);            // set: trees_begin sizes the host buffer, the chunk stages build and upload it
+    tc.d_b = (double*)(tc.base + pl.o_b);                   // set: the given lengths in schedule order are kept per tree and uploaded, beside the scaled ones
+    double* d_coef = (double*)(tc.base + pl.o_coef);
+    double* d_dtile = (double*)(tc.base + pl.o_dtile);
+    double* d_dout = (double*)(tc.base + pl.o_dout);
+    double* d_ptile = want_params ? (double*)(tc.base + pl.o_ptile) : nullptr;
+    double* d_pout = want_params ? (double*)(tc.base + pl.o_pout) : nullptr;
+    CHK(trees_begin(tc));
+    std::vector<double> coef((size_t)tc.chunk * pl.ncoef);
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));
+        const int n = tc.n;
+        for (int t = 0; t < n; ++t)                         // (one mixture for all trees: the first tree's block, copied)
+            if (t && !per_tree) memcpy(coef.data() + (size_t)t * pl.ncoef, coef.data(), (size_t)pl.ncoef * 8);
+            else ptgr_coefficients(C, rate + (t0 + t) * tc.mix_stride, weight + (t0 + t) * tc.mix_stride, coef.data() + (size_t)t * pl.ncoef);
+        if (ptgr_lds_bytes(N, tc.depth, C, want_curv, want_params) > PTGR_MAX_LDS)
             return fail(c, PHYLO_EINVAL, "phylo_trees_grad_rates: %zu bytes of LDS for a wave exceed %zu (depth %d, N=%d, C=%d)",
-                        ptgr_lds_bytes(N, depth, C, want_curv, want_params), PTGR_MAX_LDS, depth, N, C);
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * C * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_b, bs.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
+                        ptgr_lds_bytes(N, tc.depth, C, want_curv, want_params), PTGR_MAX_LDS, tc.depth, N, C);
+        CHK(trees_chunk_upload(tc));
         HIPCHK(c, hipMemcpyAsync(d_coef, coef.data(), (size_t)n * pl.ncoef * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_tr0, c->stream));
-        const long n_mat = (long)n * C * R * 2;             // M | M' | M'' packed by this chunk's count
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)d_P, n_mat,
-                           d_P + n_mat * 16, d_P + 2 * n_mat * 16);
+        CHK(trees_chunk_expm(tc));
+        const long n_mat = tc.n_mat;                        // M | M' | M'' packed by this chunk's count
+        hipLaunchKernelGGL(ptg_dmats, dim3(cdiv(n_mat * 16, 256)), dim3(256), 0, c->stream, (const double*)c->d_Q, c->jc, (const double*)tc.d_P, n_mat,
+                           tc.d_P + n_mat * 16, tc.d_P + 2 * n_mat * 16);
         CHK(launch_check(c, "ptg_dmats"));
-        launches += 2;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+        CHK(trees_chunk_gap_rows(tc));
         ptgr_args g{};
-        pt2_args& a = g.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = nullptr;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        g.dops = d_dops; g.coef = d_coef; g.blen = d_b; g.dtile = d_dtile; g.ptile = d_ptile; g.store = (pk_d2*)(base + pl.o_store);
+        trees_args(tc, g.a);
+        g.dops = tc.d_dops; g.coef = d_coef; g.blen = tc.d_b; g.dtile = d_dtile; g.ptile = d_ptile; g.store = (pk_d2*)(tc.base + pl.o_store);
         g.mat_plane = n_mat * 16;
-        g.n_items = n * ntiles; g.depth = depth; g.C = C;
-        ptgr_launch(g, std::min(pl.grid, g.n_items), coded, want_curv, want_params, c->stream);
+        g.n_items = n * ntiles; g.depth = tc.depth; g.C = C;
+        ptgr_launch(g, std::min(pl.grid, g.n_items), tc.coded, want_curv, want_params, c->stream);
         CHK(launch_check(c, "ptgr_updown"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
+        CHK(trees_chunk_finish(tc));
         hipLaunchKernelGGL(ptgr_finish, dim3(cdiv((long)n * (nq * 2 * R + np * C), 256)), dim3(256), 0, c->stream, (const double*)d_dtile,
-                           (const double*)d_ptile, (const int32_t*)d_ops, (const double*)d_out, ntiles, n, R, nq, np, C, d_dout, d_pout);
+                           (const double*)d_ptile, (const int32_t*)tc.d_ops, (const double*)tc.d_out, ntiles, n, R, nq, np, C, d_dout, d_pout);
         CHK(launch_check(c, "ptgr_finish"));
-        launches += 3;
-        HIPCHK(c, hipEventRecord(c->ev_tr1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        tc.launches += 3;                                   // ptg_dmats, ptgr_updown, ptgr_finish
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         HIPCHK(c, hipMemcpyAsync(grad + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
         if (want_curv)
             HIPCHK(c, hipMemcpyAsync(curv + (size_t)t0 * 2 * R, d_dout + (size_t)n * 2 * R, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
         if (drate_TxC) HIPCHK(c, hipMemcpyAsync(drate_TxC + (size_t)t0 * C, d_pout, (size_t)n * C * 8, hipMemcpyDeviceToHost, c->stream));
         if (dweight_TxC)
             HIPCHK(c, hipMemcpyAsync(dweight_TxC + (size_t)t0 * C, d_pout + (size_t)n * C, (size_t)n * C * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tr0, c->ev_tr1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R * C;
-        st.alg_bytes = 96.0 * st.units;
-        *perf = st;
-    }
+    const double units = (double)T * S * R * C;
+    trees_stats(tc, perf, units, 96.0 * units);
     return PHYLO_OK;
 }
 
@@ -2132,136 +2016,68 @@ int phylo_trees_grad_rates(phylo_ctx* c, int T, const int32_t* child, const doub
 int phylo_trees_ancestral_rates(phylo_ctx* c, int T, const int32_t* child, const double* blen, int C, const double* rate, const double* weight,
                                 int per_tree, const double* prior4, double* loglik_T, double* post_TxRxSx4, uint8_t* state_TxRxS,
                                 double* pmax_TxRxS, double* catpost_TxCxS, double* siterate_TxS, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model)
-        return fail(c, PHYLO_ESTATE, "phylo_trees_ancestral_rates needs phylo_set_leaves and phylo_set_model first");
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
-    if (C < 1 || C > PT2_MAX_CATS) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
-    if (per_tree != 0 && per_tree != 1) return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: per_tree must be 0 or 1 (per_tree=%d)", per_tree);
+    CHK(trees_front(c, "phylo_trees_ancestral_rates", T, &C, &per_tree));
     if (!child || !blen || !rate || !weight || !loglik_T)
         return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: child, blen, rate, weight and loglik must be given (NULL pointer)");
     if (!post_TxRxSx4 && !state_TxRxS && !pmax_TxRxS && !catpost_TxCxS && !siterate_TxS)
         return fail(c, PHYLO_EINVAL,
                     "phylo_trees_ancestral_rates: one of post, state, pmax, catpost and siterate must be given (all five are NULL pointers)");
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    const size_t mix_stride = per_tree ? (size_t)C : 0;    // tree t's mixture: row t, or the one row
-    for (int t = 0; t < T; ++t) {                          // every tree and its mixture are checked before anything is queued
-        int row = 0;
-        char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
-        if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
-    }
-    CHK(check_trees_expm_range(c, T, R, blen, C, rate, mix_stride, true));
-    const bool coded = c->leaves_coded;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    trees_mixture(tc, C, rate, weight, per_tree);
+    CHK(trees_check(tc));
+    const int N = tc.N, R = tc.R, S = tc.S, ntiles = tc.ntiles;
     const unsigned outs = (post_TxRxSx4 ? PTAR_POST : 0u) | (state_TxRxS ? PTAR_STATE : 0u) | (pmax_TxRxS ? PTAR_PMAX : 0u) |
                           (catpost_TxCxS ? PTAR_CATPOST : 0u) | (siterate_TxS ? PTAR_SITERATE : 0u);
     ptar_plan pl;
-    const int prc = ptar_make_plan(N, S, ntiles, T, C, coded, outs, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl);
+    const int prc = ptar_make_plan(N, S, ntiles, T, C, tc.coded, outs, trees_cus(c), c->env.trees_chunk, &pl);
     if (prc == 2)
         return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: the requested outputs of one tree take %zu bytes, more than %zu (N=%d, S=%d, C=%d)",
                     pl.out_tree, (size_t)PTA_OUT_MAX, N, S, C);
     if (prc) return fail(c, PHYLO_EINVAL, "phylo_trees_ancestral_rates: no plan for N=%d, S=%d, %d tiles, T=%d, C=%d", N, S, ntiles, T, C);
-    const int chunk = pl.chunk;
     void* slab = nullptr;
     CHK(scratch_get(c, 23, pl.total, &slab));
-    char* base = (char*)slab;
-    double* d_prior = (double*)(base + pl.o_prior);
-    double* d_coef = (double*)(base + pl.o_coef);
-    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
-    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
-    double* d_P = (double*)(base + pl.o_P);
-    double* d_t = (double*)(base + pl.o_t);
-    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
-    double* d_tilev = (double*)(base + pl.o_tilev);
-    double* d_out = (double*)(base + pl.o_out);
-    double* d_post = post_TxRxSx4 ? (double*)(base + pl.o_post) : nullptr;
-    uint8_t* d_state = state_TxRxS ? (uint8_t*)(base + pl.o_state) : nullptr;
-    double* d_pmax = pmax_TxRxS ? (double*)(base + pl.o_pmax) : nullptr;
-    double* d_cat = catpost_TxCxS ? (double*)(base + pl.o_cat) : nullptr;
-    double* d_rate = siterate_TxS ? (double*)(base + pl.o_rate) : nullptr;
-    if (!c->ev_tz0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tz0));
-        HIPCHK(c, hipEventCreate(&c->ev_tz1));
-    }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * C * R * 2), coef((size_t)chunk * pl.ncoef);
+    trees_carve(tc, slab, pl);
+    tc.d_dops = (int32_t*)(tc.base + pl.o_dops);            // set: trees_begin sizes the host buffer, the chunk stages build and upload it
+    double* d_coef = (double*)(tc.base + pl.o_coef);
+    double* d_post = post_TxRxSx4 ? (double*)(tc.base + pl.o_post) : nullptr;
+    uint8_t* d_state = state_TxRxS ? (uint8_t*)(tc.base + pl.o_state) : nullptr;
+    double* d_pmax = pmax_TxRxS ? (double*)(tc.base + pl.o_pmax) : nullptr;
+    double* d_cat = catpost_TxCxS ? (double*)(tc.base + pl.o_cat) : nullptr;
+    double* d_rate = siterate_TxS ? (double*)(tc.base + pl.o_rate) : nullptr;
+    CHK(trees_begin(tc));
+    std::vector<double> coef((size_t)tc.chunk * pl.ncoef);
     const size_t cells_tree = (size_t)R * S;               // node-sites of one tree
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every category's lengths in its order
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
-            depth = std::max(depth, pt2_schedule(N, ch, o));
-            if (ptg_down_ops(N, ch, o, dops.data() + (size_t)t * R * 4))
-                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            const double* rt = rate + (t0 + t) * mix_stride;
-            for (int k = 0; k < C; ++k) {
-                double* tk = ts.data() + ((size_t)t * C + k) * R * 2;
-                for (int i = 0; i < R; ++i) {
-                    tk[2 * i] = rt[k] * b[2 * o[4 * i + 3]];
-                    tk[2 * i + 1] = rt[k] * b[2 * o[4 * i + 3] + 1];
-                }
-            }
-            ptar_coefficients(C, rt, weight + (t0 + t) * mix_stride, coef.data() + (size_t)t * pl.ncoef);
-        }
-        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * C * R * 16, hipMemcpyHostToDevice, c->stream));
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));
+        const int n = tc.n;
+        for (int t = 0; t < n; ++t)                         // (one mixture for all trees: the first tree's block, copied)
+            if (t && !per_tree) memcpy(coef.data() + (size_t)t * pl.ncoef, coef.data(), (size_t)pl.ncoef * 8);
+            else ptar_coefficients(C, rate + (t0 + t) * tc.mix_stride, weight + (t0 + t) * tc.mix_stride, coef.data() + (size_t)t * pl.ncoef);
+        CHK(trees_chunk_upload(tc));
         HIPCHK(c, hipMemcpyAsync(d_coef, coef.data(), (size_t)n * pl.ncoef * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_tz0, c->stream));
-        const long n_mat = (long)n * C * R * 2;
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        ++launches;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+        CHK(trees_chunk_expm(tc));
+        CHK(trees_chunk_gap_rows(tc));
         ptar_args g{};
-        pt2_args& a = g.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = nullptr;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        g.dops = d_dops; g.coef = d_coef; g.store = (pk_d2*)(base + pl.o_store);
+        trees_args(tc, g.a);
+        g.dops = tc.d_dops; g.coef = d_coef; g.store = (pk_d2*)(tc.base + pl.o_store);
         g.post = d_post; g.state = d_state; g.pmax = d_pmax; g.catpost = d_cat; g.siterate = d_rate;
-        g.n_items = n * ntiles; g.depth = depth; g.C = C;
-        ptar_launch(g, std::min(pl.grid, g.n_items), coded, c->stream);
+        g.n_items = n * ntiles; g.depth = tc.depth; g.C = C;
+        ptar_launch(g, std::min(pl.grid, g.n_items), tc.coded, c->stream);
         CHK(launch_check(c, "ptar_updown"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
-        launches += 2;
-        HIPCHK(c, hipEventRecord(c->ev_tz1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        ++tc.launches;
+        CHK(trees_chunk_finish(tc));
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         if (d_post)                                        // every cell of the chunk was written: straight into the caller's rows
             HIPCHK(c, hipMemcpyAsync(post_TxRxSx4 + (size_t)t0 * cells_tree * 4, d_post, (size_t)n * cells_tree * 32, hipMemcpyDeviceToHost, c->stream));
         if (d_state) HIPCHK(c, hipMemcpyAsync(state_TxRxS + (size_t)t0 * cells_tree, d_state, (size_t)n * cells_tree, hipMemcpyDeviceToHost, c->stream));
         if (d_pmax) HIPCHK(c, hipMemcpyAsync(pmax_TxRxS + (size_t)t0 * cells_tree, d_pmax, (size_t)n * cells_tree * 8, hipMemcpyDeviceToHost, c->stream));
         if (d_cat) HIPCHK(c, hipMemcpyAsync(catpost_TxCxS + (size_t)t0 * C * S, d_cat, (size_t)n * C * S * 8, hipMemcpyDeviceToHost, c->stream));
         if (d_rate) HIPCHK(c, hipMemcpyAsync(siterate_TxS + (size_t)t0 * S, d_rate, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tz0, c->ev_tz1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R * C;
-        st.alg_bytes = (double)T * S * (R * ((post_TxRxSx4 ? 32.0 : 0.0) + (state_TxRxS ? 1.0 : 0.0) + (pmax_TxRxS ? 8.0 : 0.0)) +
-                                        (catpost_TxCxS ? 8.0 * C : 0.0) + (siterate_TxS ? 8.0 : 0.0));
-        *perf = st;
-    }
+    trees_stats(tc, perf, (double)T * S * R * C,
+                (double)T * S * (R * ((post_TxRxSx4 ? 32.0 : 0.0) + (state_TxRxS ? 1.0 : 0.0) + (pmax_TxRxS ? 8.0 : 0.0)) +
+                                 (catpost_TxCxS ? 8.0 * C : 0.0) + (siterate_TxS ? 8.0 : 0.0)));
     return PHYLO_OK;
 }
 
@@ -2316,143 +2132,64 @@ int phylo_log_zsmc(phylo_ctx* c, const double* logw, int R, int K, double* out) 
 // ---- the NNI neighbourhood of a scored tree set (phylo_treenni.h) ----
 int phylo_trees_nni(phylo_ctx* c, int T, const int32_t* child, const double* blen, const double* prior4, double* loglik_T, double* delta,
                     phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_nni needs phylo_set_leaves and phylo_set_model first");
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
+    CHK(trees_front(c, "phylo_trees_nni", T, nullptr, nullptr));
     if (!child || !blen || !loglik_T || !delta) return fail(c, PHYLO_EINVAL, "phylo_trees_nni: child, blen, loglik and delta must be given (NULL pointer)");
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    for (int t = 0; t < T; ++t) {                          // every tree is checked before anything is queued
-        int row = 0;
-        char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
-    }
-    CHK(check_trees_expm_range(c, T, R, blen, 1, &expm_rate_one, 0, false));
-    const bool coded = c->leaves_coded;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    CHK(trees_check(tc));
+    const int N = tc.N, R = tc.R, S = tc.S, ntiles = tc.ntiles;
     ptn_plan pl;
-    if (ptn_make_plan(N, ntiles, T, coded, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+    if (ptn_make_plan(N, ntiles, T, tc.coded, trees_cus(c), c->env.trees_chunk, &pl))
         return fail(c, PHYLO_EINVAL, "phylo_trees_nni: no plan for N=%d, %d tiles, T=%d", N, ntiles, T);
-    const int chunk = pl.chunk;
     void* slab = nullptr;
     CHK(scratch_get(c, 18, pl.total, &slab));
-    char* base = (char*)slab;
-    double* d_prior = (double*)(base + pl.o_prior);
-    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
-    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
-    int32_t* d_nops = (int32_t*)(base + pl.o_nops);
-    double* d_P = (double*)(base + pl.o_P);
-    double* d_t = (double*)(base + pl.o_t);
-    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
-    double* d_tilev = (double*)(base + pl.o_tilev);
-    double* d_out = (double*)(base + pl.o_out);
-    double* d_dtile = (double*)(base + pl.o_dtile);
-    double* d_dout = (double*)(base + pl.o_dout);
-    if (!c->ev_tn0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tn0));
-        HIPCHK(c, hipEventCreate(&c->ev_tn1));
-    }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
-    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4), nops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * R * 2);
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            int32_t* d = dops.data() + (size_t)t * R * 4;
-            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
-            depth = std::max(depth, pt2_schedule(N, ch, o));
-            if (ptg_down_ops(N, ch, o, d) || ptn_nni_ops(N, o, d, nops.data() + (size_t)t * R * 4))
-                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            double* tk = ts.data() + (size_t)t * R * 2;
-            for (int i = 0; i < R; ++i) {
-                tk[2 * i] = b[2 * o[4 * i + 3]];
-                tk[2 * i + 1] = b[2 * o[4 * i + 3] + 1];
-            }
-        }
-        if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_nops, nops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_tn0, c->stream));
-        const long n_mat = (long)n * R * 2;
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        ++launches;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+    trees_carve(tc, slab, pl);
+    tc.d_dops = (int32_t*)(tc.base + pl.o_dops);            // set: trees_begin sizes the host buffer, the chunk stages build and upload it
+    tc.d_nops = (int32_t*)(tc.base + pl.o_nops);            // (the same for the NNI operations)
+    double* d_dtile = (double*)(tc.base + pl.o_dtile);
+    double* d_dout = (double*)(tc.base + pl.o_dout);
+    CHK(trees_begin(tc));
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));
+        const int n = tc.n;
+        CHK(trees_chunk_upload(tc));
+        CHK(trees_chunk_expm(tc));
+        CHK(trees_chunk_gap_rows(tc));
         ptn_args g{};
-        pt2_args& a = g.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = nullptr;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        g.dops = d_dops; g.nops = d_nops; g.dtile = d_dtile; g.store = (pk_d2*)(base + pl.o_store);
-        g.n_items = n * ntiles; g.depth = depth;
-        ptn_launch(g, std::min(pl.grid, g.n_items), coded, c->stream);
+        trees_args(tc, g.a);
+        g.dops = tc.d_dops; g.nops = tc.d_nops; g.dtile = d_dtile; g.store = (pk_d2*)(tc.base + pl.o_store);
+        g.n_items = n * ntiles; g.depth = tc.depth;
+        ptn_launch(g, std::min(pl.grid, g.n_items), tc.coded, c->stream);
         CHK(launch_check(c, "ptn_updown"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
-        hipLaunchKernelGGL(ptn_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)d_ops,
-                           (const double*)d_out, ntiles, n, R, d_dout);
+        CHK(trees_chunk_finish(tc));
+        hipLaunchKernelGGL(ptn_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)tc.d_ops,
+                           (const double*)tc.d_out, ntiles, n, R, d_dout);
         CHK(launch_check(c, "ptn_finish"));
-        launches += 3;
-        HIPCHK(c, hipEventRecord(c->ev_tn1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        tc.launches += 2;                                   // ptn_updown, ptn_finish
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         HIPCHK(c, hipMemcpyAsync(delta + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tn0, c->ev_tn1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R;
-        st.alg_bytes = 96.0 * st.units;
-        *perf = st;
-    }
+    const double units = (double)T * S * R;
+    trees_stats(tc, perf, units, 96.0 * units);
     return PHYLO_OK;
 }
 
 // ---- the same under a mixture of rate categories (phylo_treenni_rates.h) ----
 int phylo_trees_nni_rates(phylo_ctx* c, int T, const int32_t* child, const double* blen, int C, const double* rate, const double* weight,
                           int per_tree, const double* prior4, double* loglik_T, double* delta, phylo_stats* perf) {
-    CHK(bind(c));
-    if (!c->have_leaves || !c->have_model) return fail(c, PHYLO_ESTATE, "phylo_trees_nni_rates needs phylo_set_leaves and phylo_set_model first");
-    if (T < 1) return fail(c, PHYLO_EINVAL, "need T >= 1 trees (T=%d)", T);
-    if (C < 1 || C > PT2_MAX_CATS) return fail(c, PHYLO_EINVAL, "need 1 <= C <= %d rate categories (C=%d)", PT2_MAX_CATS, C);
-    if (per_tree != 0 && per_tree != 1) return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: per_tree must be 0 or 1 (per_tree=%d)", per_tree);
+    CHK(trees_front(c, "phylo_trees_nni_rates", T, &C, &per_tree));
     if (!child || !blen || !rate || !weight || !loglik_T || !delta)
         return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: child, blen, rate, weight, loglik and delta must be given (NULL pointer)");
-    const int N = c->N, R = N - 1, S = c->S, ntiles = c->ntiles;
-    const size_t mix_stride = per_tree ? (size_t)C : 0;    // tree t's mixture: row t, or the one row
-    for (int t = 0; t < T; ++t) {                          // every tree and its mixture are checked before anything is queued
-        int row = 0;
-        char msg[200];
-        if (pt2_check_tree(N, child + (size_t)t * R * 2, blen + (size_t)t * R * 2, &row, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d, row %d: %s", t, row, msg);
-        if (ptgr_check_mixture(N, blen + (size_t)t * R * 2, C, rate + t * mix_stride, weight + t * mix_stride, msg, sizeof msg))
-            return fail(c, PHYLO_EINVAL, "tree %d: %s", t, msg);
-    }
-    CHK(check_trees_expm_range(c, T, R, blen, C, rate, mix_stride, true));
-    const bool coded = c->leaves_coded;
+    trees_call tc = trees_open(c, T, child, blen, prior4);
+    trees_mixture(tc, C, rate, weight, per_tree);
+    CHK(trees_check(tc));
+    const int N = tc.N, R = tc.R, S = tc.S, ntiles = tc.ntiles;
     ptnr_plan pl;
-    if (ptnr_make_plan(N, ntiles, T, C, coded, c->n_cus > 0 ? c->n_cus : 1, c->env.trees_chunk, &pl))
+    if (ptnr_make_plan(N, ntiles, T, C, tc.coded, trees_cus(c), c->env.trees_chunk, &pl))
         return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: no plan for N=%d, %d tiles, T=%d, C=%d", N, ntiles, T, C);
-    const int chunk = pl.chunk;
-    std::vector<int32_t> ops((size_t)chunk * R * 4), dops((size_t)chunk * R * 4), nops((size_t)chunk * R * 4);
-    std::vector<double> ts((size_t)chunk * C * R * 2), ws((size_t)chunk * C);
+    std::vector<int32_t> sched((size_t)R * 4);
     for (int t = 0; t < T; ++t) {                          // the LDS of every tree's schedule, too, before anything is queued
-        const int depth = pt2_schedule(N, child + (size_t)t * R * 2, ops.data());
+        const int depth = pt2_schedule(N, child + (size_t)t * R * 2, sched.data());
         if (depth > PT2_MAX_DEPTH) return fail(c, PHYLO_EINVAL, "a schedule of %d slots exceeds %d", depth, PT2_MAX_DEPTH);
         if (ptnr_lds_bytes(N, depth) > PTGR_MAX_LDS)
             return fail(c, PHYLO_EINVAL, "phylo_trees_nni_rates: %zu bytes of LDS for a wave exceed %zu (tree %d, depth %d, N=%d)",
@@ -2460,95 +2197,40 @@ int phylo_trees_nni_rates(phylo_ctx* c, int T, const int32_t* child, const doubl
     }
     void* slab = nullptr;
     CHK(scratch_get(c, 19, pl.total, &slab));
-    char* base = (char*)slab;
-    double* d_prior = (double*)(base + pl.o_prior);
-    double* d_w = (double*)(base + pl.o_w);
-    int32_t* d_ops = (int32_t*)(base + pl.o_ops);
-    int32_t* d_dops = (int32_t*)(base + pl.o_dops);
-    int32_t* d_nops = (int32_t*)(base + pl.o_nops);
-    double* d_P = (double*)(base + pl.o_P);
-    double* d_t = (double*)(base + pl.o_t);
-    double* d_gap = coded ? (double*)(base + pl.o_gap) : nullptr;
-    double* d_tilev = (double*)(base + pl.o_tilev);
-    double* d_out = (double*)(base + pl.o_out);
-    double* d_dtile = (double*)(base + pl.o_dtile);
-    double* d_dout = (double*)(base + pl.o_dout);
-    if (!c->ev_tm0) {
-        HIPCHK(c, hipEventCreate(&c->ev_tm0));
-        HIPCHK(c, hipEventCreate(&c->ev_tm1));
-    }
-    if (prior4) HIPCHK(c, hipMemcpyAsync(d_prior, prior4, 32, hipMemcpyHostToDevice, c->stream));
-    double ms_total = 0.0;
-    int launches = 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int n = std::min(chunk, T - t0);
-        int depth = 1;
-        for (int t = 0; t < n; ++t) {                       // one schedule per tree; every category's lengths in its order
-            int32_t* o = ops.data() + (size_t)t * R * 4;
-            int32_t* d = dops.data() + (size_t)t * R * 4;
-            const int32_t* ch = child + (size_t)(t0 + t) * R * 2;
-            depth = std::max(depth, pt2_schedule(N, ch, o));
-            if (ptg_down_ops(N, ch, o, d) || ptn_nni_ops(N, o, d, nops.data() + (size_t)t * R * 4))
-                return fail(c, PHYLO_EINVAL, "tree %d: its schedule and its rows do not fit one another", t0 + t);
-            const double* b = blen + (size_t)(t0 + t) * R * 2;
-            const double* rt = rate + (t0 + t) * mix_stride;
-            const double* wt = weight + (t0 + t) * mix_stride;
-            for (int k = 0; k < C; ++k) {
-                double* tk = ts.data() + ((size_t)t * C + k) * R * 2;
-                for (int i = 0; i < R; ++i) {
-                    tk[2 * i] = rt[k] * b[2 * o[4 * i + 3]];
-                    tk[2 * i + 1] = rt[k] * b[2 * o[4 * i + 3] + 1];
-                }
-                ws[(size_t)t * C + k] = wt[k];
-            }
-        }
-        HIPCHK(c, hipMemcpyAsync(d_ops, ops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_dops, dops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_nops, nops.data(), (size_t)n * R * 16, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_t, ts.data(), (size_t)n * C * R * 16, hipMemcpyHostToDevice, c->stream));
+    trees_carve(tc, slab, pl);
+    tc.d_dops = (int32_t*)(tc.base + pl.o_dops);            // set: trees_begin sizes the host buffer, the chunk stages build and upload it
+    tc.d_nops = (int32_t*)(tc.base + pl.o_nops);            // (the same for the NNI operations)
+    double* d_w = (double*)(tc.base + pl.o_w);
+    double* d_dtile = (double*)(tc.base + pl.o_dtile);
+    double* d_dout = (double*)(tc.base + pl.o_dout);
+    CHK(trees_begin(tc));
+    std::vector<double> ws((size_t)tc.chunk * C);
+    for (int t0 = 0; t0 < T; t0 += tc.chunk) {
+        CHK(trees_chunk_host(tc, t0));                     // (its depth refusal cannot fire: every tree's was looked at above)
+        const int n = tc.n;
+        for (int t = 0; t < n; ++t)
+            for (int k = 0; k < C; ++k) ws[(size_t)t * C + k] = weight[(t0 + t) * tc.mix_stride + k];
+        CHK(trees_chunk_upload(tc));
         HIPCHK(c, hipMemcpyAsync(d_w, ws.data(), (size_t)n * C * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_tm0, c->stream));
-        const long n_mat = (long)n * C * R * 2;
-        hipLaunchKernelGGL(pk_expm_batched, dim3(cdiv(n_mat, 64)), dim3(64), 0, c->stream, c->d_Q, (const double*)d_t, (int)n_mat, c->jc, d_P);
-        CHK(launch_check(c, "pk_expm_batched"));
-        ++launches;
-        if (coded) {
-            hipLaunchKernelGGL(pt2_gap_rows, dim3(cdiv(n_mat * 4, 256)), dim3(256), 0, c->stream, (const double*)d_P, n_mat, d_gap);
-            CHK(launch_check(c, "pt2_gap_rows"));
-            ++launches;
-        }
+        CHK(trees_chunk_expm(tc));
+        CHK(trees_chunk_gap_rows(tc));
         ptnr_args g{};
-        pt2_args& a = g.a;
-        a.ops = d_ops; a.P = d_P; a.gap = d_gap; a.leaves = c->d_leaves; a.codes = c->d_leaf_codes;
-        a.prior = prior4 ? d_prior : c->d_pi;
-        a.tilev = d_tilev; a.site_lik = nullptr;
-        a.N = N; a.S = S; a.T = c->site_tile; a.ntiles = ntiles;
-        g.dops = d_dops; g.nops = d_nops; g.w = d_w; g.dtile = d_dtile; g.store = (pk_d2*)(base + pl.o_store);
-        g.n_items = n * ntiles; g.depth = depth; g.C = C;
-        ptnr_launch(g, std::min(pl.grid, g.n_items), coded, c->stream);
+        trees_args(tc, g.a);
+        g.dops = tc.d_dops; g.nops = tc.d_nops; g.w = d_w; g.dtile = d_dtile; g.store = (pk_d2*)(tc.base + pl.o_store);
+        g.n_items = n * ntiles; g.depth = tc.depth; g.C = C;
+        ptnr_launch(g, std::min(pl.grid, g.n_items), tc.coded, c->stream);
         CHK(launch_check(c, "ptnr_updown"));
-        hipLaunchKernelGGL(pt2_finish, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double*)d_tilev, ntiles, n, d_out);
-        CHK(launch_check(c, "pt2_finish"));
-        hipLaunchKernelGGL(ptnr_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)d_ops,
-                           (const double*)d_out, ntiles, n, R, d_dout);
+        CHK(trees_chunk_finish(tc));
+        hipLaunchKernelGGL(ptnr_finish, dim3(cdiv((long)n * 2 * R, 256)), dim3(256), 0, c->stream, (const double*)d_dtile, (const int32_t*)tc.d_ops,
+                           (const double*)tc.d_out, ntiles, n, R, d_dout);
         CHK(launch_check(c, "ptnr_finish"));
-        launches += 3;
-        HIPCHK(c, hipEventRecord(c->ev_tm1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(loglik_T + t0, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        tc.launches += 2;                                   // ptnr_updown, ptnr_finish
+        CHK(trees_chunk_stop(tc, loglik_T + t0));
         HIPCHK(c, hipMemcpyAsync(delta + (size_t)t0 * 2 * R, d_dout, (size_t)n * 2 * R * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));        // the chunk's host and device buffers are reused by the next one
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_tm0, c->ev_tm1));
-        ms_total += ms;
+        CHK(trees_chunk_end(tc));
     }
-    if (perf) {
-        phylo_stats st{};
-        st.sweep_ms = ms_total;
-        st.n_launches = launches;
-        st.units = (double)T * S * R * C;
-        st.alg_bytes = 96.0 * st.units;
-        *perf = st;
-    }
+    const double units = (double)T * S * R * C;
+    trees_stats(tc, perf, units, 96.0 * units);
     return PHYLO_OK;
 }
 

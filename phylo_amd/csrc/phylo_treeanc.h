@@ -31,50 +31,40 @@ struct pta_plan {
            o_store = 0, total = 0;
 };
 
+// the slab in slab order: prior | ops | downward ops | M | lengths | gap rows of M | tile values | loglik | staging of post, state, pmax
+inline int pta_regions(int N, int S, int ntiles, bool coded, unsigned outs, pta_plan& q, pts_region* r) {
+    const size_t R = (size_t)N - 1, nt = (size_t)ntiles, cells = R * (size_t)S;
+    int k = 0;
+    r[k++] = {PTS_FIXED, 32, true, &q.o_prior};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_ops};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_dops};
+    r[k++] = {PTS_TREE, R * 256, true, &q.o_P};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_t};
+    r[k++] = {PTS_TREE, R * 64, coded, &q.o_gap};
+    r[k++] = {PTS_TREE, nt * 8, true, &q.o_tilev};
+    r[k++] = {PTS_TREE, 8, true, &q.o_out};
+    r[k++] = {PTS_STAGED, cells * 32, (outs & PTA_POST) != 0, &q.o_post};
+    r[k++] = {PTS_STAGED, cells, (outs & PTA_STATE) != 0, &q.o_state};
+    r[k++] = {PTS_STAGED, cells * 8, (outs & PTA_PMAX) != 0, &q.o_pmax};
+    return k;
+}
+
 // 0: fine; 1: no plan for these numbers; 2: one tree's outputs exceed PTA_OUT_MAX (p->out_tree says by how much).
 // T trees of N taxa and S sites in ntiles site tiles; outs: which outputs are asked for; env_chunk > 0 caps the chunk.
 inline int pta_make_plan(int N, int S, int ntiles, int T, bool coded, unsigned outs, int n_cus, int env_chunk, pta_plan* p) {
     if (N < 2 || S < 1 || ntiles < 1 || T < 1 || n_cus < 1 || !(outs & 7u) || (outs & ~7u)) return 1;
-    const size_t R = (size_t)N - 1;
     pta_plan q;
-    // ops | downward ops | M | lengths | gap rows of M | tile values | loglik
-    q.per_tree = R * 16 + R * 16 + R * 256 + R * 16 + (coded ? R * 64 : 0) + (size_t)ntiles * 8 + 8;
-    const size_t cell = (outs & PTA_POST ? 32 : 0) + (outs & PTA_STATE ? 1 : 0) + (outs & PTA_PMAX ? 8 : 0);
-    q.out_tree = R * (size_t)S * cell;
+    pts_region r[PTS_MAX_REGIONS];
+    const int nr = pta_regions(N, S, ntiles, coded, outs, q, r);
+    q.per_tree = pts_sum(r, nr, PTS_TREE);
+    q.out_tree = pts_sum(r, nr, PTS_STAGED);
     if (q.out_tree > PTA_OUT_MAX) {
         *p = q;
         return 2;
     }
     q.out_region = q.out_tree > PTA_OUT_BYTES ? q.out_tree : PTA_OUT_BYTES;
-    size_t fit = PTG_CHUNK_BYTES / q.per_tree;
-    if (fit < 1) fit = 1;
-    if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);      // items of a chunk are counted in an int
-    const size_t fit_out = q.out_region / q.out_tree;                                  // >= 1
-    if (fit_out < fit) fit = fit_out;
-    if (env_chunk > 0 && (size_t)env_chunk < fit) fit = (size_t)env_chunk;
-    if (fit > (size_t)T) fit = (size_t)T;
-    q.chunk = (int)fit;
-    q.wg_store = R * PTG_U * PTG_SLOT_BYTES;
-    size_t cap = PTG_STORE_BYTES / q.wg_store;
-    if (cap > (size_t)n_cus * PTG_WG_PER_CU) cap = (size_t)n_cus * PTG_WG_PER_CU;
-    if (cap < 1) cap = 1;
-    const size_t items = fit * (size_t)ntiles;
-    q.grid = (int)(items < cap ? items : cap);
-    const size_t n = fit, cells = n * R * (size_t)S;
-    size_t o = 0;
-    q.o_prior = o; o += 256;
-    q.o_ops = o; o += ptg_up256(n * R * 16);
-    q.o_dops = o; o += ptg_up256(n * R * 16);
-    q.o_P = o; o += ptg_up256(n * R * 256);
-    q.o_t = o; o += ptg_up256(n * R * 16);
-    q.o_gap = o; o += coded ? ptg_up256(n * R * 64) : 0;
-    q.o_tilev = o; o += ptg_up256(n * ntiles * 8);
-    q.o_out = o; o += ptg_up256(n * 8);
-    q.o_post = o; o += outs & PTA_POST ? ptg_up256(cells * 32) : 0;
-    q.o_state = o; o += outs & PTA_STATE ? ptg_up256(cells) : 0;
-    q.o_pmax = o; o += outs & PTA_PMAX ? ptg_up256(cells * 8) : 0;
-    q.o_store = o; o += (size_t)q.grid * q.wg_store;
-    q.total = o;
+    q.wg_store = ((size_t)N - 1) * PTG_U * PTG_SLOT_BYTES;
+    ptg_finish_plan(q, r, nr, ntiles, T, n_cus, env_chunk, q.out_region, q.out_tree);
     *p = q;
     return 0;
 }

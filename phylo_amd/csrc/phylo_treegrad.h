@@ -9,6 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "phylo_treeset_plan.h"
+
 #define PTG_U 2                                   // site steps per pass: an operation of the downward pass holds the outer partial, two messages and two g
 #define PTG_SLOT_BYTES 2048                       // one node of one site step: 64 lanes x 4 doubles (PT2_SLOT_BYTES)
 #define PTG_CHUNK_BYTES ((size_t)64 << 20)        // device scratch of one chunk of trees, the node store apart
@@ -28,43 +30,48 @@ struct ptg_plan {
     size_t o_prior = 0, o_ops = 0, o_dops = 0, o_P = 0, o_t = 0, o_gap = 0, o_tilev = 0, o_out = 0, o_dtile = 0, o_dout = 0, o_store = 0, total = 0;
 };
 
-inline size_t ptg_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the slab in slab order: prior | ops | downward ops | M, M', M'' | lengths | gap rows of M | tile values | loglik | derivative tiles | derivatives
+inline int ptg_regions(int N, int ntiles, bool coded, ptg_plan& q, pts_region* r) {
+    const size_t R = (size_t)N - 1, nt = (size_t)ntiles, nq = (size_t)q.nq;
+    int k = 0;
+    r[k++] = {PTS_FIXED, 32, true, &q.o_prior};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_ops};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_dops};
+    r[k++] = {PTS_TREE, 3 * R * 256, true, &q.o_P};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_t};
+    r[k++] = {PTS_TREE, R * 64, coded, &q.o_gap};
+    r[k++] = {PTS_TREE, nt * 8, true, &q.o_tilev};
+    r[k++] = {PTS_TREE, 8, true, &q.o_out};
+    r[k++] = {PTS_TREE, nt * nq * 2 * R * 8, true, &q.o_dtile};
+    r[k++] = {PTS_TREE, nq * 2 * R * 8, true, &q.o_dout};
+    return k;
+}
+
+// What every plan with a node store does once its regions are stated: bytes per tree, chunk, grid, offsets, total.  P: a plan struct
+// with chunk, grid, per_tree, wg_store, o_store, total; out_region / out_tree: the staging of the ancestral calls, else 0.
+template <class P>
+inline void ptg_finish_plan(P& q, const pts_region* r, int nr, int ntiles, int T, int n_cus, int env_chunk, size_t out_region, size_t out_tree) {
+    q.per_tree = pts_sum(r, nr, PTS_TREE);
+    q.chunk = pts_chunk(q.per_tree, ntiles, T, env_chunk, PTG_CHUNK_BYTES, out_region, out_tree);
+    q.grid = pts_grid((size_t)q.chunk * (size_t)ntiles, q.wg_store, n_cus, PTG_STORE_BYTES, PTG_WG_PER_CU);
+    q.total = pts_lay_out(r, nr, (size_t)q.chunk, (size_t)q.grid * q.wg_store, &q.o_store);
+}
+
+// the same plan as pts_check_plan wants to see it
+template <class P>
+inline pts_plan_facts ptg_plan_facts(const P& q, int ntiles, int T, int n_cus, int env_chunk, size_t out_region) {
+    return {q.chunk, q.grid, q.per_tree, q.wg_store, q.o_store, q.total, ntiles, T, n_cus, env_chunk, PTG_CHUNK_BYTES, PTG_STORE_BYTES, PTG_WG_PER_CU,
+            out_region};
+}
 
 // 0: fine.  T trees of N taxa, ntiles site tiles, n_cus compute units; env_chunk > 0 caps the chunk (PHYLO_TREES_CHUNK).
 inline int ptg_make_plan(int N, int ntiles, int T, bool coded, bool curv, int n_cus, int env_chunk, ptg_plan* p) {
     if (N < 2 || ntiles < 1 || T < 1 || n_cus < 1) return 1;
-    const size_t R = (size_t)N - 1;
     ptg_plan q;
     q.nq = curv ? 2 : 1;
-    // ops | downward ops | M, M', M'' | lengths | gap rows of M | tile values | loglik | derivative tiles | derivatives
-    q.per_tree = R * 16 + R * 16 + 3 * R * 256 + R * 16 + (coded ? R * 64 : 0) + (size_t)ntiles * 8 + 8 +
-                 (size_t)ntiles * q.nq * 2 * R * 8 + (size_t)q.nq * 2 * R * 8;
-    size_t fit = PTG_CHUNK_BYTES / q.per_tree;
-    if (fit < 1) fit = 1;
-    if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);      // items of a chunk are counted in an int
-    if (env_chunk > 0 && (size_t)env_chunk < fit) fit = (size_t)env_chunk;
-    if (fit > (size_t)T) fit = (size_t)T;
-    q.chunk = (int)fit;
-    q.wg_store = R * PTG_U * PTG_SLOT_BYTES;
-    size_t cap = PTG_STORE_BYTES / q.wg_store;
-    if (cap > (size_t)n_cus * PTG_WG_PER_CU) cap = (size_t)n_cus * PTG_WG_PER_CU;
-    if (cap < 1) cap = 1;
-    const size_t items = fit * (size_t)ntiles;
-    q.grid = (int)(items < cap ? items : cap);
-    const size_t n = fit;
-    size_t o = 0;
-    q.o_prior = o; o += 256;
-    q.o_ops = o; o += ptg_up256(n * R * 16);
-    q.o_dops = o; o += ptg_up256(n * R * 16);
-    q.o_P = o; o += ptg_up256(n * 3 * R * 256);
-    q.o_t = o; o += ptg_up256(n * R * 16);
-    q.o_gap = o; o += coded ? ptg_up256(n * R * 64) : 0;
-    q.o_tilev = o; o += ptg_up256(n * ntiles * 8);
-    q.o_out = o; o += ptg_up256(n * 8);
-    q.o_dtile = o; o += ptg_up256(n * ntiles * q.nq * 2 * R * 8);
-    q.o_dout = o; o += ptg_up256(n * q.nq * 2 * R * 8);
-    q.o_store = o; o += (size_t)q.grid * q.wg_store;
-    q.total = o;
+    q.wg_store = ((size_t)N - 1) * PTG_U * PTG_SLOT_BYTES;
+    pts_region r[PTS_MAX_REGIONS];
+    ptg_finish_plan(q, r, ptg_regions(N, ntiles, coded, q, r), ntiles, T, n_cus, env_chunk, 0, 0);
     *p = q;
     return 0;
 }

@@ -32,46 +32,36 @@ inline size_t ptm_lds_bytes(int N, int depth, int P, bool grad) {
     return (size_t)depth * PTG_U * PTG_SLOT_BYTES + (grad ? 2 * ((size_t)N - 1) * 8 : 0) + (size_t)P * 64 * 8;
 }
 
+// the slab in slab order: prior | directions | ops | downward ops | M (and M') | D | lengths | gap rows of M | tile values | loglik |
+// branch tiles | branch sums | model tiles | model sums
+inline int ptm_regions(int N, int ntiles, int P, bool coded, bool grad, ptm_plan& q, pts_region* r) {
+    const size_t R = (size_t)N - 1, nt = (size_t)ntiles, np = (size_t)P, nm = (size_t)q.nm;
+    int k = 0;
+    r[k++] = {PTS_FIXED, 32, true, &q.o_prior};
+    r[k++] = {PTS_FIXED, np * 128, true, &q.o_dirs};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_ops};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_dops};
+    r[k++] = {PTS_TREE, (grad ? 2 : 1) * R * 256, true, &q.o_P};
+    r[k++] = {PTS_TREE, 2 * R * np * 128, true, &q.o_D};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_t};
+    r[k++] = {PTS_TREE, R * 64, coded, &q.o_gap};
+    r[k++] = {PTS_TREE, nt * 8, true, &q.o_tilev};
+    r[k++] = {PTS_TREE, 8, true, &q.o_out};
+    r[k++] = {PTS_TREE, nt * 2 * R * 8, grad, &q.o_dtile};
+    r[k++] = {PTS_TREE, 2 * R * 8, grad, &q.o_dout};
+    r[k++] = {PTS_TREE, nt * nm * 8, true, &q.o_mtile};
+    r[k++] = {PTS_TREE, nm * 8, true, &q.o_mout};
+    return k;
+}
+
 // 0: fine.  T trees of N taxa along P directions, ntiles site tiles, n_cus compute units; env_chunk > 0 caps the chunk.
 inline int ptm_make_plan(int N, int ntiles, int T, int P, bool coded, bool grad, int n_cus, int env_chunk, ptm_plan* p) {
     if (N < 2 || ntiles < 1 || T < 1 || n_cus < 1 || P < 1 || P > PTM_MAX_DIRS) return 1;
-    const size_t R = (size_t)N - 1, np = (size_t)P;
     ptm_plan q;
     q.nm = P + 4;
-    const size_t gq = grad ? 1 : 0;
-    // ops | downward ops | M (and M') | D | lengths | gap rows of M | tile values | loglik | branch tiles | branch sums | model tiles | model sums
-    q.per_tree = R * 16 + R * 16 + (1 + gq) * R * 256 + 2 * R * np * 128 + R * 16 + (coded ? R * 64 : 0) + (size_t)ntiles * 8 + 8 +
-                 gq * (size_t)ntiles * 2 * R * 8 + gq * 2 * R * 8 + (size_t)ntiles * q.nm * 8 + (size_t)q.nm * 8;
-    size_t fit = PTG_CHUNK_BYTES / q.per_tree;
-    if (fit < 1) fit = 1;
-    if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);      // items of a chunk are counted in an int
-    if (env_chunk > 0 && (size_t)env_chunk < fit) fit = (size_t)env_chunk;
-    if (fit > (size_t)T) fit = (size_t)T;
-    q.chunk = (int)fit;
-    q.wg_store = R * PTG_U * PTG_SLOT_BYTES;
-    size_t cap = PTG_STORE_BYTES / q.wg_store;
-    if (cap > (size_t)n_cus * PTG_WG_PER_CU) cap = (size_t)n_cus * PTG_WG_PER_CU;
-    if (cap < 1) cap = 1;
-    const size_t items = fit * (size_t)ntiles;
-    q.grid = (int)(items < cap ? items : cap);
-    const size_t n = fit;
-    size_t o = 0;
-    q.o_prior = o; o += 256;
-    q.o_dirs = o; o += ptg_up256(np * 128);
-    q.o_ops = o; o += ptg_up256(n * R * 16);
-    q.o_dops = o; o += ptg_up256(n * R * 16);
-    q.o_P = o; o += ptg_up256(n * (1 + gq) * R * 256);
-    q.o_D = o; o += ptg_up256(n * 2 * R * np * 128);
-    q.o_t = o; o += ptg_up256(n * R * 16);
-    q.o_gap = o; o += coded ? ptg_up256(n * R * 64) : 0;
-    q.o_tilev = o; o += ptg_up256(n * ntiles * 8);
-    q.o_out = o; o += ptg_up256(n * 8);
-    q.o_dtile = o; o += grad ? ptg_up256(n * ntiles * 2 * R * 8) : 0;
-    q.o_dout = o; o += grad ? ptg_up256(n * 2 * R * 8) : 0;
-    q.o_mtile = o; o += ptg_up256(n * ntiles * q.nm * 8);
-    q.o_mout = o; o += ptg_up256(n * q.nm * 8);
-    q.o_store = o; o += (size_t)q.grid * q.wg_store;
-    q.total = o;
+    q.wg_store = ((size_t)N - 1) * PTG_U * PTG_SLOT_BYTES;
+    pts_region r[PTS_MAX_REGIONS];
+    ptg_finish_plan(q, r, ptm_regions(N, ntiles, P, coded, grad, q, r), ntiles, T, n_cus, env_chunk, 0, 0);
     *p = q;
     return 0;
 }

@@ -27,43 +27,34 @@ struct ptnr_plan {
 // dynamic LDS of a launch: the stack of the upward pass | acc [2 (N-1)]
 inline size_t ptnr_lds_bytes(int N, int depth) { return (size_t)depth * PTG_U * PTG_SLOT_BYTES + 2 * ((size_t)N - 1) * 8; }
 
+// the slab in slab order: prior | weights | ops | downward ops | children's ops | per category: M, lengths, gap rows of M | tile values |
+// loglik | delta tiles | delta
+inline int ptnr_regions(int N, int ntiles, int C, bool coded, ptnr_plan& q, pts_region* r) {
+    const size_t R = (size_t)N - 1, nt = (size_t)ntiles, nc = (size_t)C;
+    int k = 0;
+    r[k++] = {PTS_FIXED, 32, true, &q.o_prior};
+    r[k++] = {PTS_TREE, nc * 8, true, &q.o_w};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_ops};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_dops};
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_nops};
+    r[k++] = {PTS_TREE, nc * R * 256, true, &q.o_P};
+    r[k++] = {PTS_TREE, nc * R * 16, true, &q.o_t};
+    r[k++] = {PTS_TREE, nc * R * 64, coded, &q.o_gap};
+    r[k++] = {PTS_TREE, nt * 8, true, &q.o_tilev};
+    r[k++] = {PTS_TREE, 8, true, &q.o_out};
+    r[k++] = {PTS_TREE, nt * 2 * R * 8, true, &q.o_dtile};
+    r[k++] = {PTS_TREE, 2 * R * 8, true, &q.o_dout};
+    return k;
+}
+
 // 0: fine.  T trees of N taxa under C categories, ntiles site tiles, n_cus compute units; env_chunk > 0 caps the chunk
 // (PHYLO_TREES_CHUNK).  The grid is ptgr_make_plan's: min(items, 8 per compute unit, 256 MiB of node stores), at least 1.
 inline int ptnr_make_plan(int N, int ntiles, int T, int C, bool coded, int n_cus, int env_chunk, ptnr_plan* p) {
     if (N < 2 || ntiles < 1 || T < 1 || n_cus < 1 || C < 1 || C > PTGR_MAX_CATS) return 1;
-    const size_t R = (size_t)N - 1, nc = (size_t)C;
     ptnr_plan q;
-    // ops | downward ops | children's ops | per category: lengths, M, gap rows of M | weights | tile values | loglik | delta tiles | delta
-    q.per_tree = R * 16 + R * 16 + R * 16 + nc * R * (16 + 256 + (coded ? 64 : 0)) + nc * 8 + (size_t)ntiles * 8 + 8 + (size_t)ntiles * 2 * R * 8 +
-                 2 * R * 8;
-    size_t fit = PTG_CHUNK_BYTES / q.per_tree;
-    if (fit < 1) fit = 1;
-    if (fit > (size_t)(0x7fffffff / ntiles)) fit = (size_t)(0x7fffffff / ntiles);      // items of a chunk are counted in an int
-    if (env_chunk > 0 && (size_t)env_chunk < fit) fit = (size_t)env_chunk;
-    if (fit > (size_t)T) fit = (size_t)T;
-    q.chunk = (int)fit;
-    q.wg_store = nc * R * PTG_U * PTG_SLOT_BYTES;
-    size_t cap = PTG_STORE_BYTES / q.wg_store;
-    if (cap > (size_t)n_cus * PTG_WG_PER_CU) cap = (size_t)n_cus * PTG_WG_PER_CU;
-    if (cap < 1) cap = 1;
-    const size_t items = fit * (size_t)ntiles;
-    q.grid = (int)(items < cap ? items : cap);
-    const size_t n = fit;
-    size_t o = 0;
-    q.o_prior = o; o += 256;
-    q.o_w = o; o += ptg_up256(n * nc * 8);
-    q.o_ops = o; o += ptg_up256(n * R * 16);
-    q.o_dops = o; o += ptg_up256(n * R * 16);
-    q.o_nops = o; o += ptg_up256(n * R * 16);
-    q.o_P = o; o += ptg_up256(n * nc * R * 256);
-    q.o_t = o; o += ptg_up256(n * nc * R * 16);
-    q.o_gap = o; o += coded ? ptg_up256(n * nc * R * 64) : 0;
-    q.o_tilev = o; o += ptg_up256(n * ntiles * 8);
-    q.o_out = o; o += ptg_up256(n * 8);
-    q.o_dtile = o; o += ptg_up256(n * ntiles * 2 * R * 8);
-    q.o_dout = o; o += ptg_up256(n * 2 * R * 8);
-    q.o_store = o; o += (size_t)q.grid * q.wg_store;
-    q.total = o;
+    q.wg_store = (size_t)C * ((size_t)N - 1) * PTG_U * PTG_SLOT_BYTES;
+    pts_region r[PTS_MAX_REGIONS];
+    ptg_finish_plan(q, r, ptnr_regions(N, ntiles, C, coded, q, r), ntiles, T, n_cus, env_chunk, 0, 0);
     *p = q;
     return 0;
 }

@@ -10,9 +10,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <vector>
+
+#include "phylo_treeset_plan.h"
 
 #if defined(__HIPCC__)
 #include "phylo_kernels.h"
@@ -151,6 +154,56 @@ inline int pt2_schedule(int N, const int32_t* child, int32_t* ops /*[N-1][4]*/) 
 // stack stays within PT2_WAVE_LDS (depth <= 2: caterpillar-like trees), else two -- at most 40 KiB per wave at depth 10.  (One
 // step per pass holds both matrices and all pointers in scalar registers at once and spills two of them: not built.)
 inline int pt2_unroll(int depth) { return depth * 4 * PT2_SLOT_BYTES <= PT2_WAVE_LDS ? 4 : 2; }
+
+// The plan of phylo_trees_loglik and phylo_trees_loglik_rates: one chunk of trees in device scratch, no node store.
+struct pt2_plan {
+    int chunk = 0;                 // trees per chunk
+    bool sites = false;            // the row of site values is carried (asked for, or a chunk's four-step kernel needs it)
+    size_t per_tree = 0;
+    // byte offsets into the slab (all multiples of 256)
+    size_t o_prior = 0, o_ops = 0, o_P = 0, o_t = 0, o_gap = 0, o_tilev = 0, o_out = 0, o_site = 0, o_cat = 0, total = 0;
+};
+
+// the slab in slab order: prior and weights | ops | matrices | lengths | gap rows | tile values | loglik | site values | category factors
+inline int pt2_regions(int N, int S, int ntiles, int nc, bool coded, bool sites, bool cat, pt2_plan& q, pts_region* r) {
+    const size_t R = (size_t)N - 1, c = (size_t)nc;
+    int k = 0;
+    r[k++] = {PTS_FIXED, 32 + PT2_MAX_CATS * 8, true, &q.o_prior};     // the prior, then the weights: one pointer for pt2_prune_rates
+    r[k++] = {PTS_TREE, R * 16, true, &q.o_ops};
+    r[k++] = {PTS_TREE, c * R * 256, true, &q.o_P};
+    r[k++] = {PTS_TREE, c * R * 16, true, &q.o_t};
+    r[k++] = {PTS_TREE, c * R * 64, coded, &q.o_gap};
+    r[k++] = {PTS_TREE, (size_t)ntiles * 8, true, &q.o_tilev};
+    r[k++] = {PTS_TREE, 8, true, &q.o_out};
+    r[k++] = {PTS_TREE, (size_t)S * 8, sites, &q.o_site};
+    r[k++] = {PTS_TREE, c * (size_t)S * 8, cat, &q.o_cat};
+    return k;
+}
+
+// 0: fine.  T trees of N taxa and S sites in ntiles tiles, nc sets of lengths per tree (mix: the rates call, C = nc).  The rates
+// call's four-step kernels keep the site values in their row between categories (pt2_prune_rates), so the row is there, asked for
+// or not, when a chunk is that shallow: a chunk's depth is its deepest tree's (depth_of[T], pt2_needs' depths; read when mix and
+// the row is not asked for).  Carrying the row makes the chunk smaller, so the chunks are looked at again with it.
+inline int pt2_make_plan(int N, int S, int ntiles, int T, int nc, bool mix, bool coded, bool want_sites, bool want_cat, int env_chunk,
+                         const int* depth_of, pt2_plan* p) {
+    if (N < 2 || S < 1 || ntiles < 1 || T < 1 || nc < 1 || nc > PT2_MAX_CATS || (mix && !want_sites && !depth_of)) return 1;
+    pt2_plan q;
+    pts_region r[PTS_MAX_REGIONS];
+    int nr = 0;
+    q.sites = want_sites;
+    for (;;) {
+        nr = pt2_regions(N, S, ntiles, nc, coded, q.sites, want_cat, q, r);
+        q.per_tree = pts_sum(r, nr, PTS_TREE);
+        q.chunk = pts_chunk(q.per_tree, ntiles, T, env_chunk, PT2_SCRATCH_BYTES, 0, 0);
+        if (!mix || q.sites) break;
+        for (int t0 = 0; t0 < T && !q.sites; t0 += q.chunk)  // the chunks without the row: is one of them that shallow?
+            q.sites = pt2_unroll(*std::max_element(depth_of + t0, depth_of + std::min(T, t0 + q.chunk))) == 4;
+        if (!q.sites) break;
+    }
+    q.total = pts_lay_out(r, nr, (size_t)q.chunk, 0, nullptr);
+    *p = q;
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // device

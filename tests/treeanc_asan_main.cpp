@@ -17,36 +17,26 @@ static long check_plan(int N, int S, int ntiles, int T, bool coded, unsigned out
     const int rc = pta_make_plan(N, S, ntiles, T, coded, outs, n_cus, env_chunk, &p);
     if (tree_out > PTA_OUT_MAX) return (rc != 2) + (p.out_tree != tree_out);          // refused, naming the size
     if (rc) return 1000000;
-    const size_t n = (size_t)p.chunk, cells = n * R * (size_t)S;
+    const size_t n = (size_t)p.chunk;
     bad += p.out_tree != tree_out;
     bad += p.out_region != (tree_out > PTA_OUT_BYTES ? tree_out : PTA_OUT_BYTES);     // grows to one tree's need, never further
-    bad += p.chunk < 1 || p.chunk > T || (env_chunk > 0 && p.chunk > env_chunk);
-    bad += p.chunk > 1 && n * p.per_tree > PTG_CHUNK_BYTES;                            // more than one tree: within the slab's budget
-    bad += n * tree_out > p.out_region;                                                // the chunk's outputs fit the staging region
-    bad += (size_t)p.chunk * ntiles > 0x7fffffffu;
+    // the chunk within the slab's budget (more than one tree), the caller's cap and T, its outputs within the staging region, its
+    // items within an int; the grid within its caps; every region aligned, in order, apart and inside the slab
+    pts_region r[PTS_MAX_REGIONS];
+    const int nr = pta_regions(N, S, ntiles, coded, outs, p, r);
+    const pts_plan_facts f = ptg_plan_facts(p, ntiles, T, n_cus, env_chunk, p.out_region);
+    bad += pts_check_plan(r, nr, f);
     // the chunk is the SMALLEST of the three bounds: one more tree would break one of them (or there is none left)
     if (p.chunk < T && !(env_chunk > 0 && p.chunk == env_chunk))
         bad += (n + 1) * p.per_tree <= PTG_CHUNK_BYTES && (n + 1) * tree_out <= p.out_region && (n + 1) * (size_t)ntiles <= 0x7fffffffu;
-    bad += p.grid < 1 || (size_t)p.grid > n * ntiles || p.grid > n_cus * PTG_WG_PER_CU;
-    bad += p.grid > 1 && (size_t)p.grid * p.wg_store > PTG_STORE_BYTES;
     bad += p.wg_store != R * PTG_U * PTG_SLOT_BYTES;
     // the grid cap is ptg_make_plan's
     ptg_plan gp;
     if (!ptg_make_plan(N, ntiles, p.chunk, coded, false, n_cus, p.chunk, &gp)) bad += gp.chunk == p.chunk && gp.grid != p.grid;
-    const size_t off[] = {p.o_prior, p.o_ops, p.o_dops, p.o_P, p.o_t, p.o_gap, p.o_tilev, p.o_out, p.o_post, p.o_state, p.o_pmax, p.o_store, p.total};
-    const size_t need[] = {32, n * R * 16, n * R * 16, n * R * 256, n * R * 16, coded ? n * R * 64 : 0, n * ntiles * 8, n * 8,
-                           outs & PTA_POST ? cells * 32 : 0, outs & PTA_STATE ? cells : 0, outs & PTA_PMAX ? cells * 8 : 0,
-                           (size_t)p.grid * p.wg_store};
-    for (int i = 0; i < 12; ++i) {
-        bad += off[i] % 256 != 0;
-        bad += off[i] + need[i] > off[i + 1];
-    }
     if (p.total <= ((size_t)8 << 20)) {                     // every region written end to end inside an exactly sized buffer
         unsigned char* slab = (unsigned char*)malloc(p.total);
         if (!slab) return 1000000;
-        for (int i = 0; i < 12; ++i) memset(slab + off[i], i, need[i]);
-        for (int i = 0; i < 12; ++i)
-            if (need[i]) bad += slab[off[i]] != i || slab[off[i] + need[i] - 1] != i;      // no region overwrote another
+        bad += pts_fill_plan(r, nr, f, slab);               // no region overwrote another
         free(slab);
     }
     return bad;

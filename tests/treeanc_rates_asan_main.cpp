@@ -24,13 +24,15 @@ static long check_plan(int N, int S, int ntiles, int T, int C, bool coded, unsig
     const int rc = ptar_make_plan(N, S, ntiles, T, C, coded, outs, n_cus, env_chunk, &p);
     if (tree_out > PTA_OUT_MAX) return (rc != 2) + (p.out_tree != tree_out);          // refused, naming the size
     if (rc) return 1000000;
-    const size_t n = (size_t)p.chunk, cells = n * R * (size_t)S;
+    const size_t n = (size_t)p.chunk;
     bad += p.out_tree != tree_out;
     bad += p.out_region != (tree_out > PTA_OUT_BYTES ? tree_out : PTA_OUT_BYTES);     // grows to one tree's need, never further
-    bad += p.chunk < 1 || p.chunk > T || (env_chunk > 0 && p.chunk > env_chunk);
-    bad += p.chunk > 1 && n * p.per_tree > PTG_CHUNK_BYTES;                            // more than one tree: within the slab's budget
-    bad += n * tree_out > p.out_region;                                                // the chunk's outputs fit the staging region
-    bad += (size_t)p.chunk * ntiles > 0x7fffffffu;
+    // the chunk within the slab's budget (more than one tree), the caller's cap and T, its outputs within the staging region, its
+    // items within an int; the grid within its caps; every region aligned, in order, apart and inside the slab
+    pts_region r[PTS_MAX_REGIONS];
+    const int nr = ptar_regions(N, S, ntiles, C, coded, outs, p, r);
+    const pts_plan_facts f = ptg_plan_facts(p, ntiles, T, n_cus, env_chunk, p.out_region);
+    bad += pts_check_plan(r, nr, f);
     bad += p.ncoef != 2 * C;
     // the slab is accounted as ptgr_make_plan's without M', M'', the given lengths, the derivative tiles and sums, and with w | r
     // in the place of w | u | v
@@ -40,27 +42,13 @@ static long check_plan(int N, int S, int ntiles, int T, int C, bool coded, unsig
     // the chunk is the SMALLEST of the three bounds: one more tree would break one of them (or there is none left)
     if (p.chunk < T && !(env_chunk > 0 && p.chunk == env_chunk))
         bad += (n + 1) * p.per_tree <= PTG_CHUNK_BYTES && (n + 1) * tree_out <= p.out_region && (n + 1) * (size_t)ntiles <= 0x7fffffffu;
-    bad += p.grid < 1 || (size_t)p.grid > n * ntiles || p.grid > n_cus * PTG_WG_PER_CU;
-    bad += p.grid > 1 && (size_t)p.grid * p.wg_store > PTG_STORE_BYTES;
     bad += p.wg_store != nc * R * PTG_U * PTG_SLOT_BYTES;
     // the grid cap is ptgr_make_plan's
     if (!ptgr_make_plan(N, ntiles, p.chunk, C, coded, false, false, n_cus, p.chunk, &gp)) bad += gp.chunk == p.chunk && gp.grid != p.grid;
-    const size_t off[] = {p.o_prior, p.o_coef, p.o_ops, p.o_dops, p.o_P, p.o_t, p.o_gap, p.o_tilev, p.o_out, p.o_post, p.o_state, p.o_pmax,
-                          p.o_cat, p.o_rate, p.o_store, p.total};
-    const size_t need[] = {32, n * 2 * nc * 8, n * R * 16, n * R * 16, n * nc * R * 256, n * nc * R * 16, coded ? n * nc * R * 64 : 0,
-                           n * ntiles * 8, n * 8, outs & PTAR_POST ? cells * 32 : 0, outs & PTAR_STATE ? cells : 0,
-                           outs & PTAR_PMAX ? cells * 8 : 0, outs & PTAR_CATPOST ? n * nc * (size_t)S * 8 : 0,
-                           outs & PTAR_SITERATE ? n * (size_t)S * 8 : 0, (size_t)p.grid * p.wg_store};
-    for (int i = 0; i < 15; ++i) {
-        bad += off[i] % 256 != 0;
-        bad += off[i] + need[i] > off[i + 1];
-    }
     if (p.total <= ((size_t)8 << 20)) {                     // every region written end to end inside an exactly sized buffer
         unsigned char* slab = (unsigned char*)malloc(p.total);
         if (!slab) return 1000000;
-        for (int i = 0; i < 15; ++i) memset(slab + off[i], i, need[i]);
-        for (int i = 0; i < 15; ++i)
-            if (need[i]) bad += slab[off[i]] != i || slab[off[i] + need[i] - 1] != i;      // no region overwrote another
+        bad += pts_fill_plan(r, nr, f, slab);               // no region overwrote another
         free(slab);
     }
     return bad;

@@ -14,22 +14,12 @@ static long check_plan(int N, int ntiles, int T, bool coded, bool curv, int n_cu
     long bad = 0;
     ptg_plan p;
     if (ptg_make_plan(N, ntiles, T, coded, curv, n_cus, env_chunk, &p)) return 1000000;
-    const size_t R = (size_t)N - 1, n = (size_t)p.chunk, nq = curv ? 2 : 1;
-    bad += p.nq != (int)nq;
-    bad += p.chunk < 1 || p.chunk > T || (env_chunk > 0 && p.chunk > env_chunk);
-    bad += p.chunk > 1 && (size_t)p.chunk * p.per_tree > PTG_CHUNK_BYTES;          // more than one tree: within the budget
-    bad += (size_t)p.chunk * ntiles > 0x7fffffffu;
-    bad += p.grid < 1 || (size_t)p.grid > n * ntiles || p.grid > n_cus * PTG_WG_PER_CU;
-    bad += p.grid > 1 && (size_t)p.grid * p.wg_store > PTG_STORE_BYTES;
-    bad += p.wg_store != R * PTG_U * PTG_SLOT_BYTES;
-    // every region holds what the host carves from it, in order, 256-byte aligned, inside the slab
-    const size_t off[] = {p.o_prior, p.o_ops, p.o_dops, p.o_P, p.o_t, p.o_gap, p.o_tilev, p.o_out, p.o_dtile, p.o_dout, p.o_store, p.total};
-    const size_t need[] = {32, n * R * 16, n * R * 16, n * 3 * R * 256, n * R * 16, coded ? n * R * 64 : 0, n * ntiles * 8, n * 8,
-                           n * ntiles * nq * 2 * R * 8, n * nq * 2 * R * 8, (size_t)p.grid * p.wg_store};
-    for (int i = 0; i < 11; ++i) {
-        bad += off[i] % 256 != 0;
-        bad += off[i] + need[i] > off[i + 1];
-    }
+    bad += p.nq != (curv ? 2 : 1);
+    bad += p.wg_store != ((size_t)N - 1) * PTG_U * PTG_SLOT_BYTES;
+    // the chunk and the grid within their bounds; every region holds what the host carves from it, in order, 256-byte aligned,
+    // inside the slab; the bytes of a tree are the sum of the list (pts_check_plan, over the plan's own regions)
+    pts_region r[PTS_MAX_REGIONS];
+    bad += pts_check_plan(r, ptg_regions(N, ntiles, coded, p, r), ptg_plan_facts(p, ntiles, T, n_cus, env_chunk, 0));
     return bad;
 }
 

@@ -30,29 +30,19 @@ int main() {
                             EXPECT(ptm_make_plan(N, nt, T, P, coded, grad, 256, env, &p) == 0);
                             ++plans;
                             const size_t R = (size_t)N - 1;
-                            EXPECT(p.chunk >= 1 && p.chunk <= T && (env == 0 || p.chunk <= env));
-                            EXPECT(p.chunk == 1 || (size_t)p.chunk * p.per_tree <= PTG_CHUNK_BYTES);
-                            EXPECT(p.grid >= 1 && (size_t)p.grid <= (size_t)p.chunk * nt && p.grid <= 256 * PTG_WG_PER_CU);
-                            EXPECT(p.grid == 1 || (size_t)p.grid * p.wg_store <= PTG_STORE_BYTES);
                             EXPECT(p.wg_store == R * PTG_U * PTG_SLOT_BYTES);
                             EXPECT(p.nm == P + 4);
-                            const size_t offs[] = {p.o_prior, p.o_dirs, p.o_ops, p.o_dops, p.o_P, p.o_D, p.o_t, p.o_gap, p.o_tilev, p.o_out,
-                                                   p.o_dtile, p.o_dout, p.o_mtile, p.o_mout, p.o_store, p.total};
-                            const size_t n = (size_t)p.chunk;
+                            // chunk and grid within their bounds, offsets ascending and aligned, regions apart and inside the slab
+                            pts_region r[PTS_MAX_REGIONS];
+                            const int nr = ptm_regions(N, nt, P, coded, grad, p, r);
+                            const pts_plan_facts f = ptg_plan_facts(p, nt, T, 256, env, 0);
+                            EXPECT(pts_check_plan(r, nr, f) == 0);
                             // (with grad, ptg_dmats writes M' behind M and its second output, 2 R matrices, where D is built next)
-                            const size_t need[] = {32, (size_t)P * 128, n * R * 16, n * R * 16, n * (grad ? 2 : 1) * R * 256, n * 2 * R * P * 128,
-                                                   n * R * 16, coded ? n * R * 64 : 0, n * nt * 8, n * 8, grad ? n * nt * 2 * R * 8 : 0,
-                                                   grad ? n * 2 * R * 8 : 0, n * nt * (P + 4) * 8, n * (P + 4) * 8, (size_t)p.grid * p.wg_store};
-                            EXPECT(n * 2 * R * 128 <= need[5]);
-                            for (int k = 0; k < 15; ++k) {
-                                EXPECT(offs[k] % 256 == 0);
-                                EXPECT(offs[k + 1] >= offs[k] + need[k]);
-                            }
-                            // a buffer of the plan's size takes every region's first and last byte
+                            EXPECT(r[5].off == &p.o_D && (size_t)p.chunk * 2 * R * 128 <= (size_t)p.chunk * r[5].bytes);
+                            // a buffer of the plan's size takes every region end to end
                             if (p.total < ((size_t)8 << 20)) {
                                 std::vector<unsigned char> slab(p.total);
-                                for (int k = 0; k < 15; ++k)
-                                    if (need[k]) slab[offs[k]] = 1, slab[offs[k] + need[k] - 1] = 1;
+                                EXPECT(pts_fill_plan(r, nr, f, slab.data()) == 0);
                             }
                         }
     {   // the edges the issue names: N = 2 and 512, P = 1 and 16, T = 1, a chunk cap of 1

@@ -31,27 +31,17 @@ int main() {
                             EXPECT(ptgr_make_plan(N, nt, T, C, coded, curv, params, 256, env, &p) == 0);
                             ++plans;
                             const size_t R = (size_t)N - 1;
-                            EXPECT(p.chunk >= 1 && p.chunk <= T && (env == 0 || p.chunk <= env));
-                            EXPECT(p.chunk == 1 || (size_t)p.chunk * p.per_tree <= PTG_CHUNK_BYTES);
-                            EXPECT(p.grid >= 1 && (size_t)p.grid <= (size_t)p.chunk * nt && p.grid <= 256 * PTG_WG_PER_CU);
-                            EXPECT(p.grid == 1 || (size_t)p.grid * p.wg_store <= PTG_STORE_BYTES);
                             EXPECT(p.wg_store == (size_t)C * R * PTG_U * PTG_SLOT_BYTES);
                             EXPECT(p.nq == (curv ? 2 : 1) && p.np == (params ? 2 : 0) && p.ncoef == 3 * C);
-                            const size_t offs[] = {p.o_prior, p.o_coef, p.o_ops, p.o_dops, p.o_P, p.o_t, p.o_b, p.o_gap, p.o_tilev, p.o_out,
-                                                   p.o_dtile, p.o_dout, p.o_ptile, p.o_pout, p.o_store, p.total};
-                            const size_t n = (size_t)p.chunk;
-                            const size_t need[] = {32, n * 3 * C * 8, n * R * 16, n * R * 16, n * C * 3 * R * 256, n * C * R * 16, n * R * 16,
-                                                   coded ? n * C * R * 64 : 0, n * nt * 8, n * 8, n * nt * p.nq * 2 * R * 8, n * p.nq * 2 * R * 8,
-                                                   params ? n * nt * 2 * C * 8 : 0, params ? n * 2 * C * 8 : 0, (size_t)p.grid * p.wg_store};
-                            for (int k = 0; k < 15; ++k) {
-                                EXPECT(offs[k] % 256 == 0);
-                                EXPECT(offs[k + 1] >= offs[k] + need[k]);
-                            }
-                            // a buffer of the plan's size takes every region's first and last byte
+                            // chunk and grid within their bounds, offsets ascending and aligned, regions apart and inside the slab
+                            pts_region r[PTS_MAX_REGIONS];
+                            const int nr = ptgr_regions(N, nt, C, coded, p, r);
+                            const pts_plan_facts f = ptg_plan_facts(p, nt, T, 256, env, 0);
+                            EXPECT(pts_check_plan(r, nr, f) == 0);
+                            // a buffer of the plan's size takes every region end to end
                             if (p.total < ((size_t)8 << 20)) {
                                 std::vector<unsigned char> slab(p.total);
-                                for (int k = 0; k < 15; ++k)
-                                    if (need[k]) slab[offs[k]] = 1, slab[offs[k] + need[k] - 1] = 1;
+                                EXPECT(pts_fill_plan(r, nr, f, slab.data()) == 0);
                             }
                         }
     {   // shapes without a plan

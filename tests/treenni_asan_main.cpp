@@ -14,24 +14,11 @@ static long check_plan(int N, int ntiles, int T, bool coded, int n_cus, int env_
     long bad = 0;
     ptn_plan p;
     if (ptn_make_plan(N, ntiles, T, coded, n_cus, env_chunk, &p)) return 1000000;
-    const size_t R = (size_t)N - 1, n = (size_t)p.chunk;
-    bad += p.chunk < 1 || p.chunk > T || (env_chunk > 0 && p.chunk > env_chunk);
-    bad += p.chunk > 1 && (size_t)p.chunk * p.per_tree > PTG_CHUNK_BYTES;          // more than one tree: within the budget
-    bad += (size_t)p.chunk * ntiles > 0x7fffffffu;
-    bad += p.grid < 1 || (size_t)p.grid > n * ntiles || p.grid > n_cus * PTG_WG_PER_CU;
-    bad += p.grid > 1 && (size_t)p.grid * p.wg_store > PTG_STORE_BYTES;
-    bad += p.wg_store != R * PTG_U * PTG_SLOT_BYTES;
-    // every region holds what the host carves from it, in order, 256-byte aligned, inside the slab
-    const size_t off[] = {p.o_prior, p.o_ops, p.o_dops, p.o_nops, p.o_P, p.o_t, p.o_gap, p.o_tilev, p.o_out, p.o_dtile, p.o_dout, p.o_store, p.total};
-    const size_t need[] = {32, n * R * 16, n * R * 16, n * R * 16, n * R * 256, n * R * 16, coded ? n * R * 64 : 0, n * ntiles * 8, n * 8,
-                           n * ntiles * 2 * R * 8, n * 2 * R * 8, (size_t)p.grid * p.wg_store};
-    size_t sum = 0;
-    for (int i = 0; i < 12; ++i) {
-        bad += off[i] % 256 != 0;
-        bad += off[i] + need[i] > off[i + 1];
-        if (i > 0 && i < 11) sum += need[i];
-    }
-    bad += p.per_tree * n != sum;                                                  // per-tree bytes are what the regions of a chunk hold
+    bad += p.wg_store != ((size_t)N - 1) * PTG_U * PTG_SLOT_BYTES;
+    // the chunk and the grid within their bounds; every region holds what the host carves from it, in order, 256-byte aligned,
+    // inside the slab; per-tree bytes are what the regions of a chunk hold (pts_check_plan, over the plan's own regions)
+    pts_region r[PTS_MAX_REGIONS];
+    bad += pts_check_plan(r, ptn_regions(N, ntiles, coded, p, r), ptg_plan_facts(p, ntiles, T, n_cus, env_chunk, 0));
     return bad;
 }
 

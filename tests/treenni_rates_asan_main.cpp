@@ -12,30 +12,20 @@ static long check_plan(int N, int ntiles, int T, int C, bool coded, int n_cus, i
     ptnr_plan p;
     if (ptnr_make_plan(N, ntiles, T, C, coded, n_cus, env_chunk, &p)) return 1000000;
     const size_t R = (size_t)N - 1, n = (size_t)p.chunk, nc = (size_t)C;
-    bad += p.chunk < 1 || p.chunk > T || (env_chunk > 0 && p.chunk > env_chunk);
-    bad += p.chunk > 1 && (size_t)p.chunk * p.per_tree > PTG_CHUNK_BYTES;          // more than one tree: within the budget
     bad += p.chunk < T && (env_chunk <= 0 || p.chunk < env_chunk) && ((size_t)p.chunk + 1) * p.per_tree <= PTG_CHUNK_BYTES &&
            ((size_t)p.chunk + 1) * ntiles <= 0x7fffffffu;                          // ... and no tree more would fit
-    bad += (size_t)p.chunk * ntiles > 0x7fffffffu;
     // the grid: min(items, 8 per compute unit, 256 MiB of node stores), at least 1
     size_t want = PTG_STORE_BYTES / p.wg_store;
     if (want > (size_t)n_cus * PTG_WG_PER_CU) want = (size_t)n_cus * PTG_WG_PER_CU;
     if (want < 1) want = 1;
     if (want > n * ntiles) want = n * ntiles;
     bad += (size_t)p.grid != want;
-    bad += p.grid > 1 && (size_t)p.grid * p.wg_store > PTG_STORE_BYTES;
     bad += p.wg_store != nc * R * PTG_U * PTG_SLOT_BYTES;
-    // every region holds what the host carves from it, in order, 256-byte aligned, inside the slab, none overlapping the next
-    const size_t off[] = {p.o_prior, p.o_w, p.o_ops, p.o_dops, p.o_nops, p.o_P, p.o_t, p.o_gap, p.o_tilev, p.o_out, p.o_dtile, p.o_dout, p.o_store, p.total};
-    const size_t need[] = {32, n * nc * 8, n * R * 16, n * R * 16, n * R * 16, n * nc * R * 256, n * nc * R * 16, coded ? n * nc * R * 64 : 0,
-                           n * ntiles * 8, n * 8, n * ntiles * 2 * R * 8, n * 2 * R * 8, (size_t)p.grid * p.wg_store};
-    size_t sum = 0;
-    for (int i = 0; i < 13; ++i) {
-        bad += off[i] % 256 != 0;
-        bad += off[i] + need[i] > off[i + 1];
-        if (i > 0 && i < 12) sum += need[i];
-    }
-    bad += p.per_tree * n != sum;                                                  // per-tree bytes are what the regions of a chunk hold
+    // the chunk within its bounds (within the budget when it holds more than one tree), items within an int, the grid within its
+    // caps; every region holds what the host carves from it, in order, 256-byte aligned, inside the slab, none overlapping the
+    // next; per-tree bytes are what the regions of a chunk hold (pts_check_plan, over the plan's own regions)
+    pts_region r[PTS_MAX_REGIONS];
+    bad += pts_check_plan(r, ptnr_regions(N, ntiles, C, coded, p, r), ptg_plan_facts(p, ntiles, T, n_cus, env_chunk, 0));
     return bad;
 }
 
